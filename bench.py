@@ -10,6 +10,11 @@ lambda_q + blended scorer + top-k) -- the reference's harnesses issue one query 
 (tests/test_4_msmarco_tau_sweep.py:216).  The index build runs once before the timed
 region and is reported next to it (index_build_sec).  Inputs are resident in HBM when
 either timed region starts.  Rank 0 prints ONE JSON line.
+
+A plain run does what the headline needs: data, index build, W warmup + K timed searches, the line.  --full adds
+every side measurement and check (roofline figures, in-distribution queries, threads, batched search, fp64
+brute-force verification, unfriendly distributions, the build from host memory, CPU baseline).
+--dump-outputs DIR writes the hits of the last timed search; the inputs depend on the arguments alone.
 """
 from __future__ import annotations
 
@@ -168,7 +173,7 @@ def live_traffic(workload_argv, timeout_s=150):
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):
             out = os.path.join(tmp, counter)
             cmd = [exe, "--pmc", counter, "--kernel-trace", "--output-format", "csv", "-d", out, "--",
-                   sys.executable, os.path.abspath(__file__), "--traffic-probe", "--no-cpu-baseline", "--steps", "20", "--warmup", "2"] + list(workload_argv)
+                   sys.executable, os.path.abspath(__file__), "--traffic-probe", "--full", "--no-cpu-baseline", "--steps", "20", "--warmup", "2"] + list(workload_argv)
             with open(os.path.join(tmp, counter + ".log"), "w") as log:
                 # (its own process group: a pass that runs out of time is ended with everything it started -- the profiled
                 # child must not keep the GPU busy under the measurement that follows)
@@ -223,19 +228,33 @@ def make_data(n, d, seed, device, nclust=1024, noise=0.5, return_centres=False):
     """SURVEY section 8(d) recipe, bit for bit and reproducible off the GPU: rng = np.random.default_rng(seed);
     C = rng.standard_normal((nclust, d)); z = rng.integers(0, nclust, n); X = C[z] + noise * rng.standard_normal((n, d));
     rows L2-normalised; cast fp32.  The noise is drawn in row chunks (the generator's stream is the same as for one
-    big call) so the host never holds more than one fp64 chunk."""
+    big call) so the host holds a few fp64 chunks, never the whole array.  The draws are serial; the rest of a chunk (centres,
+    normalisation, cast, copy) runs on a second thread under the next chunk's draw -- numpy and the copy release the
+    interpreter lock -- which takes about a third off the recipe's host time at 1M x 768 and changes no bit."""
+    from concurrent.futures import ThreadPoolExecutor
+
     import torch
 
     rng = np.random.default_rng(seed)
     C = rng.standard_normal((nclust, d))
     z = rng.integers(0, nclust, n)
     X = torch.empty((n, d), device=device, dtype=torch.float32)
-    step = 1 << 16
-    for s in range(0, n, step):
-        e = min(n, s + step)
-        blk = C[z[s:e]] + noise * rng.standard_normal((e - s, d))
+
+    def finish(s, e, draw):
+        blk = C[z[s:e]] + noise * draw
         blk /= np.linalg.norm(blk, axis=1, keepdims=True)
         X[s:e] = torch.from_numpy(blk.astype(np.float32)).to(device)
+
+    step = 1 << 16
+    with ThreadPoolExecutor(1) as pool:
+        pending = None
+        for s in range(0, n, step):
+            e = min(n, s + step)
+            draw = rng.standard_normal((e - s, d))
+            if pending is not None:
+                pending.result()
+            pending = pool.submit(finish, s, e, draw)
+        pending.result()
     return (X, C) if return_centres else X
 
 
@@ -481,6 +500,12 @@ def main():
                     help="edge weight: gaussian (north_star default) or 1/(1+(d/sigma)^p) of GRAPH_VARIABLES.md:9")
     ap.add_argument("--lambda-mode", choices=["item", "feature"], default="item",
                     help="item: node energy on the N-node graph; feature: F x F feature Laplacian of TAUMODE.md:8,12-27")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check beyond the headline: live PMC traffic passes, kernel-level scan timing, in-distribution "
+                         "queries, host threads, batched search, fp64 brute-force verification, unfriendly distributions, the build "
+                         "from host memory and the CPU baseline (the --no-* options below switch parts of it off)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the hits of the last timed search (DIR/hit_indices.npy, DIR/hit_scores.npy, float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-queries", type=int, default=24)
     ap.add_argument("--cpu-build-n", type=int, nargs="*", default=[20000, 100000],
@@ -494,13 +519,15 @@ def main():
     ap.add_argument("--verify-queries", type=int, default=64, help="timed queries (and as many in-distribution ones) re-issued after the timed loops and held against an fp64 brute force on the GPU")
     ap.add_argument("--traffic-probe", action="store_true", help=argparse.SUPPRESS)   # the short child pass live_traffic() profiles
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher around us: be the launcher (nothing in this process has touched the GPU yet, and nothing will)
         sys.exit(launch(args.gpus, sys.argv[1:]))
 
     live, live_note = None, "not attempted"
-    if "WORLD_SIZE" not in os.environ and not (args.no_live_traffic or args.traffic_probe):
+    if args.full and "WORLD_SIZE" not in os.environ and not (args.no_live_traffic or args.traffic_probe):
         # before this process touches the GPU: the two counter passes (children under rocprofv3) have the card to themselves
         wl = []
         for name in ("n", "d", "k", "topk", "tau", "eps", "metric", "kernel", "lambda_mode"):
@@ -599,7 +626,7 @@ def main():
 
         b = asdist.shard_bounds(n, world)
         shard = X[b[rank]:b[rank + 1]].clone()      # this rank's rows; the rest arrives by RCCL all-gather
-        Xh32 = X.cpu() if rank == 0 and not args.no_cpu_baseline else None   # (rank 0's CPU baseline scans all N items on the host)
+        Xh32 = X.cpu() if args.full and rank == 0 and not args.no_cpu_baseline else None   # (rank 0's CPU baseline scans all N items on the host)
         del X
         torch.cuda.empty_cache()
         barrier()
@@ -635,13 +662,61 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        searcher(Q[(args.warmup + i) % len(Q)])
+        hits = searcher(Q[(args.warmup + i) % len(Q)])
     barrier()
     dt = time.perf_counter() - t0
     tt = torch.tensor([dt], device=device, dtype=torch.float64)
     if dist is not None:
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     dt = float(tt.item())
+    step_operand = aspace.last_scan_operand if single else index.last_scan_operand()   # what the last timed scan read
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: the (index, score) hits, score descending
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "hit_indices.npy"), np.array([i for i, _ in hits], dtype=np.float64))
+        np.save(os.path.join(args.dump_outputs, "hit_scores.npy"), np.array([s for _, s in hits], dtype=np.float64))
+    ranks_seen = world
+    if dist is not None:
+        # the ranks the collective layer really connected (an all-reduce of ones: RCCL over xGMI, or gloo when the ranks
+        # of a rehearsal share a card)
+        ones = torch.ones(1, device=device, dtype=torch.float64)
+        dist.all_reduce(ones)
+        ranks_seen = int(round(float(ones.item())))
+    out = {
+        "metric": "queries/sec (single-query search, B=1) at N=%dx D=%d fp32; index-build sec alongside" % (n, d),
+        "value": args.steps / dt,
+        "unit": "queries/s",
+        "n_gpus": world,
+        "ranks_seen": ranks_seen,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": ("int8 prefilter (items' image) + fp64 exact re-evaluation of every candidate; items fp32 in HBM, API fp64"
+                  if step_operand in ("int8", "int8-high") else "f32 prefilter + fp64 exact re-evaluation"),
+        "data": "synthetic",
+        "config": {"workload": "SURVEY 8(d) synthetic: np.random.default_rng(42) clustered N=%d x D=%d fp32 (1024 centres, noise 0.5, "
+                               "rows normalised), k=%d topk=%d tau=%.2f eps=%.5f (calibrated: mean degree ~2k), metric=%s kernel=%s (p=2 is the kernel's "
+                               "exponent, GRAPH_VARIABLES.md:9 -- the distance is L2 or rectified cosine, never a general L_p) "
+                               "lambda_mode=%s; queries = items perturbed by default_rng(43) noise (deviation from 8(d): a fresh "
+                               "sample of the recipe has no neighbour inside eps); BASELINE.json headline config"
+                               % (n, d, args.k, args.topk, args.tau, eps, args.metric, args.kernel, args.lambda_mode),
+                   "n": n, "d": d, "metric": args.metric, "kernel": args.kernel, "lambda_mode": args.lambda_mode,
+                   "parallelism": "row-shard x%d" % world + (" (ranks share %d GPU(s): exchange steps staged through host memory, a "
+                                                              "rehearsal of the N-rank job, not a scaling measurement)" % shared_gpu if shared_gpu else "")},
+        "parity": PARITY,
+        "index_build_sec": build_s,
+        "priming_queries": primed,
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
     # kernel-level timing of the dominant kernel (scan_dots) with HIP events on its own stream,
     # taken over a second pass so the event reads do not perturb the timed region
     asp.enable_search_stats(True)
@@ -808,7 +883,6 @@ def main():
         except Exception as e:      # noqa: BLE001 -- a side key must not cost the headline line
             build_from_host = {"error": "%s: %s" % (type(e).__name__, e)}
 
-    qps = args.steps / dt
     # the scan reads the int8 two-digit image of the items when it can (2 bytes per element + the rows' norm and scale), else fp32
     scan_i8 = scan_operand in ("int8", "int8-high")
     rows_per_gpu = (n + world - 1) // world
@@ -821,13 +895,9 @@ def main():
         for key in ("2", "4", "native_1", "native_2", "native_4"):
             if key in threaded:
                 threaded[key]["frac"] = scan_moved * threaded[key]["value"] / 1e9 / HBM_PEAK_GBS
-    # N > 1: every rank's own scan (its rows, its launch time, its operand) next to rank 0's, and the ranks the collective
-    # layer really connected (an all-reduce of ones: RCCL over xGMI, or gloo when the ranks of a rehearsal share a card)
-    ranks_seen, per_rank = world if dist is None else None, None
+    # N > 1: every rank's own scan (its rows, its launch time, its operand) next to rank 0's
+    per_rank = None
     if dist is not None:
-        ones = torch.ones(1, device=device, dtype=torch.float64)
-        dist.all_reduce(ones)
-        ranks_seen = int(round(float(ones.item())))
         my_rows = (index.scan_rows[1] - index.scan_rows[0]) if not single else n
         my_moved = my_rows * ((1.0 if scan_coarse else 2.0) * d8 + 12.0) if scan_i8 else my_rows * (d + 2) * 4.0
         mine = {"rank": rank, "rows": int(my_rows), "avg_launch_ms": scan_ms, "operand": scan_operand, "bytes_per_launch": my_moved,
@@ -889,31 +959,7 @@ def main():
         except (OSError, KeyError, ValueError):
             pass
 
-    out = {
-        "metric": "queries/sec (single-query search, B=1) at N=%dx D=%d fp32; index-build sec alongside" % (n, d),
-        "value": qps,
-        "unit": "queries/s",
-        "n_gpus": world,
-        "ranks_seen": ranks_seen,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": ("int8 prefilter (items' image) + fp64 exact re-evaluation of every candidate; items fp32 in HBM, API fp64" if scan_i8
-                  else "f32 prefilter + fp64 exact re-evaluation"),
-        "data": "synthetic",
-        "config": {"workload": "SURVEY 8(d) synthetic: np.random.default_rng(42) clustered N=%d x D=%d fp32 (1024 centres, noise 0.5, "
-                               "rows normalised), k=%d topk=%d tau=%.2f eps=%.5f (calibrated: mean degree ~2k), metric=%s kernel=%s (p=2 is the kernel's "
-                               "exponent, GRAPH_VARIABLES.md:9 -- the distance is L2 or rectified cosine, never a general L_p) "
-                               "lambda_mode=%s; queries = items perturbed by default_rng(43) noise (deviation from 8(d): a fresh "
-                               "sample of the recipe has no neighbour inside eps); BASELINE.json headline config"
-                               % (n, d, args.k, args.topk, args.tau, eps, args.metric, args.kernel, args.lambda_mode),
-                   "n": n, "d": d, "metric": args.metric, "kernel": args.kernel, "lambda_mode": args.lambda_mode,
-                   "parallelism": "row-shard x%d" % world + (" (ranks share %d GPU(s): exchange steps staged through host memory, a "
-                                                              "rehearsal of the N-rank job, not a scaling measurement)" % shared_gpu if shared_gpu else "")},
-        "parity": PARITY,
+    out.update({
         "verified": verified,
         "distributions": distributions,
         "in_distribution_queries": {"value": (args.steps - zero_in) / dt_in if dt_in > 0 else None, "unit": "queries/s",
@@ -922,10 +968,8 @@ def main():
                                     "algorithmic_speedup": query_bytes / world / (dt_in / args.steps) / 1e9 / HBM_PEAK_GBS,
                                     "workload": "SURVEY 8(d) query recipe: the index's 1024 centres, labels and noise 0.5 from "
                                                 "np.random.default_rng(43), rows normalised"},
-        "index_build_sec": build_s,
         "index_build_from_host_sec": None if not build_from_host or "value" not in build_from_host else build_from_host["value"],
         "index_build_from_host": build_from_host,
-        "priming_queries": primed,
         "batched_queries_per_sec": batched_qps,
         "threaded_queries_per_sec": threaded,
         "zero_lambda_rate": zero_in / args.steps,
@@ -977,7 +1021,7 @@ def main():
                            "pipe": "f64" if feature else k2_pipe,
                            "note": "k-NN kernels of the build (threshold pass + symmetric pass: half the distance block); the "
                                    "pipe only prefilters -- graphs are bit-identical on int8, bf16 and fp32 (DESIGN.md 5.2)"},
-    }
+    })
 
     # ---------------- CPU baseline: the oracle (fp64 C/OpenMP restatement) on this box's host cores, rank 0 (at any N)
     lam_all = deg_all = None

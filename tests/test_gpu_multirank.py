@@ -251,7 +251,7 @@ def test_bench_line_of_a_two_rank_job():
     env = dict(os.environ, ARROWSPACE_BENCH_NDEV="1", ARROWSPACE_BENCH_LAUNCH_TIMEOUT="500")
     env.pop("WORLD_SIZE", None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--n", "120000", "--d", "128", "--k", "10", "--topk", "5",
-                        "--steps", "30", "--warmup", "5", "--cpu-queries", "4", "--cpu-build-n", "2000"],
+                        "--steps", "30", "--warmup", "5", "--full", "--cpu-queries", "4", "--cpu-build-n", "2000"],
                        env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [json.loads(l) for l in p.stdout.splitlines() if l.startswith('{"metric"')]

@@ -231,3 +231,48 @@ def test_batched_calls_beside_concurrent_single_searches():
     assert not errors, errors[:3]
     assert not bad, bad[:5]
     assert aspace.batch_dual_scans > 0
+
+
+def test_plain_bench_line_and_its_dumped_outputs(tmp_path):
+    """`bench.py --steps K --warmup W` without --full: the headline line alone (no side keys) over K timed steps, and
+    `--dump-outputs DIR` writes the hits of the last timed search -- the same in two runs with the same arguments, and the
+    same as a search of that query on an index built from the bench's own data recipe."""
+    import json
+
+    import numpy as np
+    import torch
+
+    import bench
+    import pyarrowspace_amd as asp
+
+    n, d, k, topk, steps, warmup = 20000, 64, 10, 7, 9, 3
+
+    def run(out):
+        env = dict(os.environ)
+        env.pop("WORLD_SIZE", None)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--n", str(n), "--d", str(d), "--k", str(k),
+                            "--topk", str(topk), "--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(out)],
+                           env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [json.loads(l) for l in p.stdout.splitlines() if l.startswith('{"metric"')]
+        assert len(lines) == 1
+        return lines[0], [np.load(out / (name + ".npy")) for name in ("hit_indices", "hit_scores")]
+
+    line, (idx, sc) = run(tmp_path / "a")
+    assert line["steps"] == steps and line["warmup"] == warmup and line["unit"] == "queries/s" and line["higher_is_better"] is True
+    assert abs(line["value"] * line["ms_per_step"] - 1e3) <= 1e-9 * 1e3 and line["index_build_sec"] > 0
+    assert not {"roofline", "verified", "distributions", "batched_queries_per_sec", "threaded_queries_per_sec", "cpu_baseline"} & set(line)
+    assert idx.dtype == np.float64 and sc.dtype == np.float64 and idx.shape == sc.shape == (topk,)
+    assert all(sc[t] >= sc[t + 1] for t in range(topk - 1))
+    _, (idx2, sc2) = run(tmp_path / "b")
+    np.testing.assert_array_equal(idx, idx2)
+    np.testing.assert_array_equal(sc, sc2)
+
+    X = bench.make_data(n, d, 42, torch.device("cuda", 0))
+    Q = bench.make_queries(X, max(steps + warmup, 64), 43)
+    gp = {"eps": bench.calibrate_eps(X, k, "l2"), "k": k, "topk": topk, "p": 2.0, "sigma": None, "metric": "l2", "kernel": "gaussian",
+          "lambda_mode": "item"}
+    aspace, gl = asp.ArrowSpaceBuilder.build_from_device(gp, X.data_ptr(), "float32", n, d, d)
+    want = aspace.search(Q[(warmup + steps - 1) % len(Q)], gl, 0.62)
+    np.testing.assert_array_equal(idx, [i for i, _ in want])
+    np.testing.assert_allclose(sc, [s for _, s in want], rtol=1e-12, atol=0.0)
