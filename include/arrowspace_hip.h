@@ -429,6 +429,17 @@ as_status as_last_search_stats(const as_space* sp, double* out, int32_t n);
  * [2] reruns after a failed k-NN a-posteriori check, [3] after a candidate-buffer overflow, [4] after a failed scorer
  * check, [5] searches that took at least one rerun.  A rerun costs a second pass over the items. */
 as_status as_search_counters(const as_space* sp, int64_t* out, int32_t n);
+/* Extension: one query under ntau taus (a tau sweep) -- list j, at out_idx / out_score + j * topk' (topk' = min(topk, nitems)),
+ * out_len[j] entries, is what as_search returns for taus[j].  lambda_q (one value, tau-independent) -> out_lambda_q; lambda_q == 0
+ * -> AS_EZEROLAMBDA.  Taus in [0, 1] share passes over the items, up to 8 per pass: one coarse scan, k-NN records and lambda_q,
+ * the union of the taus' candidate sets evaluated exactly once, one ranking per tau.  Equal taus are computed once; a tau outside
+ * [0, 1] (or NaN), a sweep of one distinct tau, and whatever a shared pass does not serve take the single search.  ntau = 0:
+ * nothing is launched.  Re-entrant as as_search (one workspace of the pool per call). */
+as_status as_search_taus(const as_space* sp, const as_graph* gr, const double* query, int64_t d, const double* taus, int64_t ntau,
+                         int64_t* out_idx, double* out_score, int64_t* out_len, double* out_lambda_q);
+/* out[0] as_search_taus calls, [1] shared passes that served at least one tau, [2] taus a shared pass did not serve, or could not
+ * be run for (feature graphs, force_exact, a scan the image cannot serve, ...), redone by the single search */
+as_status as_sweep_counters(const as_space* sp, int64_t* out, int32_t n);
 
 /* ---- index persistence (extension; the reference exposes none): one flat file
  * holding the items, lambdas and graph arrays.  Loading re-ingests the items and uploads the

@@ -289,6 +289,39 @@ class ArrowSpace:
         return [list(zip(ii, ss)) if l == topk else list(zip(ii[:l], ss[:l]))
                 for ii, ss, l in zip(idx.tolist(), sc.tolist(), ln.tolist())]
 
+    def search_taus(self, item, gl: GraphLaplacian, taus):
+        """Extension: one query under several taus (a tau sweep) -> one hit list per entry of `taus`, in order; list j is what
+        `search(item, gl, taus[j])` returns.  Taus in [0, 1] share passes over the items (up to 8 per pass: one scan, one k-NN
+        step, one exact evaluation of the union of the taus' candidates); equal taus are computed once, and a tau outside
+        [0, 1], a sweep of one distinct tau, or anything a shared pass does not serve takes the single search."""
+        if not isinstance(gl, GraphLaplacian):
+            raise TypeError("argument 'gl': expected GraphLaplacian")
+        q = self._query(item)
+        t = np.ascontiguousarray(taus, dtype=np.float64)
+        if t.ndim != 1:
+            raise TypeError("argument 'taus': expected a 1-D sequence of floats")
+        nt = t.shape[0]
+        topk = max(min(int(gl.graph_params["topk"]), self.nitems), 0)
+        idx = np.empty((max(nt, 1), max(topk, 1)), dtype=np.int64)
+        sc = np.empty((max(nt, 1), max(topk, 1)), dtype=np.float64)
+        ln = np.zeros(max(nt, 1), dtype=np.int64)
+        lq = C.c_double(0.0)
+        st = _L.as_search_taus(self._h, gl._h, q.ctypes.data, q.shape[0], t.ctypes.data, nt, idx.ctypes.data, sc.ctypes.data,
+                               ln.ctypes.data, C.byref(lq))
+        if st:
+            _raise(st)
+        idx, sc = idx[:, :topk], sc[:, :topk]
+        return [list(zip(ii[:l], ss[:l])) for ii, ss, l in zip(idx[:nt].tolist(), sc[:nt].tolist(), ln[:nt].tolist())]
+
+    def sweep_counters(self) -> dict:
+        """Extension: `search_taus` calls on this space, the shared passes that served them, and the taus those passes left
+        to the single search (taus_redone)."""
+        out = np.zeros(3, dtype=np.int64)
+        st = _L.as_sweep_counters(self._h, out.ctypes.data_as(C.c_void_p), 3)
+        if st:
+            _raise(st)
+        return dict(zip(("calls", "shared_passes", "taus_redone"), (int(v) for v in out)))
+
     def last_search_stats(self) -> dict:
         """Extension: device microseconds of the last search (HIP events on its stream)."""
         out = np.zeros(3, dtype=np.float64)

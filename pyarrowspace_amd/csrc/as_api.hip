@@ -795,6 +795,104 @@ static as_status search_single(const as_space* sp, const as_graph* gr, as_query*
     return s;
 }
 
+// Extension: one query under ntau taus (the evaluation scripts' tau sweeps) -- list j is what as_search returns for taus[j].
+// Equal taus are computed once; taus outside [0, 1] (NaN included) and a sweep of one distinct tau take the single search; the
+// others share passes of up to TAU_GROUP taus each (search_sweep), and whatever a pass does not serve is redone by the single
+// search, with its own escalation.  One workspace of the pool for the whole call; never part of a gang scan.
+as_status as_search_taus(const as_space* sp, const as_graph* gr, const double* query, int64_t d, const double* taus, int64_t ntau,
+                         int64_t* out_idx, double* out_score, int64_t* out_len, double* out_lambda_q) {
+    if (!sp || !gr || !query || ntau < 0 || (ntau > 0 && (!taus || !out_idx || !out_score || !out_len))) {
+        set_err("as_search_taus: null argument");
+        return AS_EINVAL;
+    }
+    if (d != sp->d) {
+        set_err("query length %lld must match nfeatures %lld", (long long)d, (long long)sp->d);
+        return AS_EINVAL;
+    }
+    AS_TRY(graph_matches(sp, gr, "as_search_taus"));
+    if (ntau == 0) return AS_OK;
+    sp->sweep_count[0].fetch_add(1, std::memory_order_relaxed);
+    const int64_t topk = std::min<int64_t>(gr->gp.topk, sp->n);
+    const int64_t ls = std::max<int64_t>(topk, 1);
+    // distinct taus (bit patterns), in order of first appearance; the shared passes take those in [0, 1]
+    std::vector<double> uniq;
+    std::vector<int64_t> slot((size_t)ntau);
+    for (int64_t j = 0; j < ntau; ++j) {
+        int64_t u = 0;
+        while (u < (int64_t)uniq.size() && memcmp(&uniq[u], &taus[j], sizeof(double)) != 0) ++u;
+        if (u == (int64_t)uniq.size()) uniq.push_back(taus[j]);
+        slot[j] = u;
+    }
+    const int64_t nu = (int64_t)uniq.size();
+    std::vector<int64_t> uidx((size_t)(nu * ls)), ulen((size_t)nu, 0);
+    std::vector<double> usc((size_t)(nu * ls));
+    std::vector<int> done((size_t)nu, 0);
+    std::vector<int64_t> shared;
+    for (int64_t u = 0; u < nu; ++u)
+        if (uniq[u] >= 0.0 && uniq[u] <= 1.0) shared.push_back(u);
+    if (shared.size() < 2) shared.clear();   // (one distinct tau: the single search is the whole sweep)
+    AS_HIP(hipSetDevice(sp->device));
+    int ps = -1;
+    as_query* q = nullptr;
+    AS_TRY(pool_acquire(sp, gr, &ps, &q));
+    as_status s = AS_OK;
+    double lq = 0.0;
+    int64_t passes = 0, redone = 0;
+    for (size_t g0 = 0; g0 < shared.size() && s == AS_OK; g0 += TAU_GROUP) {
+        const int nt = (int)std::min<size_t>(TAU_GROUP, shared.size() - g0);
+        if (nt < 2) break;   // (a last group of one: the single search below)
+        double gt[TAU_GROUP];
+        int served[TAU_GROUP];
+        int64_t glen[TAU_GROUP];
+        for (int j = 0; j < nt; ++j) gt[j] = uniq[shared[g0 + j]];
+        std::vector<int64_t> sidx((size_t)(nt * ls));
+        std::vector<double> ssc((size_t)(nt * ls));
+        s = search_sweep(q, query, d, gt, nt, ls, sidx.data(), ssc.data(), glen, &lq, served);
+        int nserved = 0;
+        for (int j = 0; j < nt; ++j) {
+            if (!served[j]) continue;
+            nserved += 1;
+            const int64_t u = shared[g0 + j];
+            done[u] = 1;
+            ulen[u] = glen[j];
+            for (int64_t t = 0; t < glen[j]; ++t) {
+                uidx[u * ls + t] = sidx[j * ls + t];
+                usc[u * ls + t] = ssc[j * ls + t];
+            }
+        }
+        if (nserved > 0) passes += 1;
+        if (s == AS_OK) redone += nt - nserved;
+    }
+    for (int64_t u = 0; u < nu && s == AS_OK; ++u) {
+        if (done[u]) continue;
+        s = search_single(sp, gr, q, query, d, uniq[u], &uidx[u * ls], &usc[u * ls], &ulen[u], &lq);
+        done[u] = 1;
+    }
+    pool_release(sp, ps);
+    sp->sweep_count[1].fetch_add(passes, std::memory_order_relaxed);
+    sp->sweep_count[2].fetch_add(redone, std::memory_order_relaxed);
+    if (out_lambda_q) *out_lambda_q = lq;
+    if (s != AS_OK) return s;   // (AS_EZEROLAMBDA: lambda_q does not depend on tau -- every tau would panic)
+    for (int64_t j = 0; j < ntau; ++j) {
+        const int64_t u = slot[j];
+        for (int64_t t = 0; t < ulen[u]; ++t) {
+            out_idx[j * topk + t] = uidx[u * ls + t];
+            out_score[j * topk + t] = usc[u * ls + t];
+        }
+        out_len[j] = ulen[u];
+    }
+    return AS_OK;
+}
+
+as_status as_sweep_counters(const as_space* sp, int64_t* out, int32_t n) {
+    if (!sp || !out) {
+        set_err("as_sweep_counters: null argument");
+        return AS_EINVAL;
+    }
+    for (int i = 0; i < n && i < 3; ++i) out[i] = sp->sweep_count[i].load(std::memory_order_relaxed);
+    return AS_OK;
+}
+
 as_status as_search_batch(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau,
                           int64_t* out_idx, double* out_score, int64_t* out_len, double* out_lambda_q, int32_t* out_status) {
     if (!sp || !gr || !queries || !out_idx || !out_score || !out_len) {

@@ -128,6 +128,9 @@ struct as_space {
     // [3] reruns because a candidate buffer overflowed, [4] reruns because the scorer's check failed, [5] searches that
     // took at least one rerun (under qmu)
     mutable int64_t scount[6] = {0, 0, 0, 0, 0, 0};
+    // as_sweep_counters: [0] as_search_taus calls, [1] shared passes that served at least one tau, [2] tau values a shared
+    // pass did not serve (or could not be run for) that were redone by the single search
+    mutable std::atomic<int64_t> sweep_count[3] = {};
     mutable int64_t unproven_searches = 0;   // searches returned although their a-posteriori check failed on the strongest path
     mutable double kstats[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // accumulated by as_knn_rows
 };
@@ -471,6 +474,8 @@ as_status exact_row_knn(as_query* ws, const as_graph_params* gp, int64_t row, in
                         double* out_key, double* out_dist, double* out_gy, int32_t* out_cnt);
 as_status search_once(as_query* q, const double* query, int64_t d, double tau, int exact, int64_t* out_idx,
                       double* out_score, int64_t* out_len, double* out_lambda_q);
+as_status search_sweep(as_query* q, const double* query, int64_t d, const double* taus, int nt, int64_t lstride, int64_t* out_idx,
+                       double* out_score, int64_t* out_len, double* out_lambda_q, int* served);
 void query_flags(const as_query* q, int* knn_inexact, int* score_inexact);
 int query_overflow_bits(const as_query* q);
 as_status query_create(const as_space* sp, const as_graph* gr, int cap, as_query** out, int pool_slot = 0);
@@ -479,5 +484,6 @@ as_status search_batch_launch_pair(as_query* a, as_query* b, const double* qa, i
 as_status search_batch_collect(as_query* q, int nb, double tau, int64_t topk, int64_t* out_idx, double* out_score, int64_t* out_len,
                                double* out_lambda_q, int32_t* out_status);
 constexpr int QUERY_BATCH = 32;  // == GQ in as_search.hip: query slots of the batched workspace
+constexpr int TAU_GROUP = 8;     // taus one shared pass of a tau sweep serves (search_sweep, as_search_taus)
 
 }  // namespace as

@@ -257,6 +257,9 @@ struct as_query {
     void* x1_head = nullptr;             // header of the block the last pass wrote (left zeroed by its finish kernel)
     int x1_dirty = 1;                    // ... unless that pass never reached its finish
     char* x1_own = nullptr;              // single space: the block of the fused tail's two-kernel form (search_once)
+    as::HostOut* swout = nullptr;        // tau sweep (search_sweep): TAU_GROUP pinned result lists, one per tau of a shared pass ...
+    as::HostOut* swout_dev = nullptr;
+    void* sw_gmin = nullptr;             // ... and the group minima of its TAU_GROUP scorer keys ([TAU_GROUP][CAND_CAP] doubles); both made on first use
 };
 
 namespace as {

@@ -3060,22 +3060,23 @@ static as_status query_begin(as_query* q, const double* query_host, int64_t src_
 }
 
 // wait for the final kernel's publication (pinned memory), without the driver's sync path
-static as_status wait_published(as_query* q, int slot = 0) {
+static as_status wait_published_at(as_query* q, const HostOut* h) {
     const int64_t want = q->seq;
     for (int spin = 0; spin < 2000000; ++spin) {
-        if (q->hout[slot].seq == want) {
+        if (h->seq == want) {
             std::atomic_thread_fence(std::memory_order_acquire);
             return AS_OK;
         }
         if ((spin & 1023) == 1023 && hipStreamQuery(q->stream) == hipSuccess) break;
     }
     AS_HIP(hipStreamSynchronize(q->stream));
-    if (q->hout[slot].seq != want) {
-        set_err("search result was not published (seq %lld != %lld)", (long long)q->hout[slot].seq, (long long)want);
+    if (h->seq != want) {
+        set_err("search result was not published (seq %lld != %lld)", (long long)h->seq, (long long)want);
         return AS_EHIP;
     }
     return AS_OK;
 }
+static as_status wait_published(as_query* q, int slot = 0) { return wait_published_at(q, q->hout + slot); }
 
 static as_status collect(as_query* q, int64_t* out_idx, double* out_score, int64_t* out_len, double* out_lambda_q,
                          int slot = 0) {
@@ -3324,6 +3325,8 @@ void as_query_free(as_query* q) {
     if (q->xsend) hipFree(q->xsend);
     if (q->xall) hipFree(q->xall);
     if (q->x1_own) hipFree(q->x1_own);
+    if (q->swout) hipHostFree(q->swout);
+    if (q->sw_gmin) hipFree(q->sw_gmin);
     if (q->xknn) hipFree(q->xknn);
     hipFree(q->rsel);
     if (q->own_records) {
@@ -3967,6 +3970,410 @@ as_status search_once(as_query* q, const double* query, int64_t d, double tau, i
                                q->hout->overflow, q->hout->knn_inexact, q->hout->score_inexact, q->coef_i8h);
     }
     return collect(q, out_idx, out_score, out_len, out_lambda_q);
+}
+
+// ------------------------------------------------------------------ tau sweep: one pass over the items for up to TAU_GROUP taus
+// Nothing the coarse chain's scan, k-NN records or lambda_q hold depends on tau: only the blend of the scorer key, the
+// threshold picked from it and the ranking do.  The two selection kernels below are the chain's score_gmin / score_pickfilter
+// for TAU_GROUP keys at once -- a row's fp32 dot, norm and lambda read once, the cosine and the lambda term's denominator
+// formed once, one key per tau in score_key<double>'s mixed form -- and the filter keeps the UNION of the rows each tau's own
+// threshold keeps.  Every row of a tau's true top-k is in that tau's kept set (coarse_score_stage), so it is in the union; the
+// union is evaluated exactly once (staged_x1_kernel, xmode 2) and ranked once per tau (sweep_final_kernel).
+struct SweepSel {
+    SelArgs<double> s;   // the chain's arguments (dots32, norms, lambdas, QInfo, rows, Ms); s.tau / s.margin unused
+    int nt;
+    double tau[TAU_GROUP], margin[TAU_GROUP];
+    double* gmin;        // [TAU_GROUP][CAND_CAP]
+};
+
+// the tau-independent half of score_key<double>'s mixed form: the cosine of the fp32 dot and the lambda term's denominator
+__device__ __forceinline__ void sweep_row(const SelArgs<double>& a, const ScoreCtx& c, int64_t row, double& cs, double& den) {
+    const double nrow = a.n64[row];
+    const double dv = (double)a.dots32[(row >> 5) * a.ts + (row & 31) * a.rs];
+    cs = nrow > 0.0 ? dv * rsqrt(nrow) * c.rq : 0.0;
+    den = 1.0 + fabs(c.lq - a.lam64[row]);
+}
+// element j of a by-value array of the kernel's arguments without a private copy (a dynamic index would spill it)
+__device__ __forceinline__ double sweep_pick(const double (&v)[TAU_GROUP], int j) {
+    double r = v[0];
+#pragma unroll
+    for (int i = 1; i < TAU_GROUP; ++i) r = j == i ? v[i] : r;
+    return r;
+}
+
+// (1) per-group minima of the nt keys; one wave per group of G rows (score_gmin_kernel<double, 0>)
+__global__ __launch_bounds__(256) void sweep_gmin_kernel(SweepSel a, int64_t G, int ngroups) {
+    const int lane = lane_id();
+    const int64_t g = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (g >= ngroups) return;
+    if (a.s.info->status == AS_EZEROLAMBDA) return;   // (the reference's panic: no scores are formed)
+    const ScoreCtx c = load_ctx(a.s.info, 1.0);
+    const int64_t lo = a.s.r0 + g * G;
+    const int64_t hi = lo + G < a.s.r1 ? lo + G : a.s.r1;
+    double m[TAU_GROUP];
+#pragma unroll
+    for (int j = 0; j < TAU_GROUP; ++j) m[j] = key_traits<double>::inf();
+    for (int64_t row = lo + lane; row < hi; row += 64) {
+        double cs, den;
+        sweep_row(a.s, c, row, cs, den);
+#pragma unroll
+        for (int j = 0; j < TAU_GROUP; ++j)
+            if (j < a.nt) {
+                const double k = -(a.tau[j] * cs + (1.0 - a.tau[j]) / den);
+                m[j] = k < m[j] ? k : m[j];
+            }
+    }
+#pragma unroll
+    for (int j = 0; j < TAU_GROUP; ++j)
+        if (j < a.nt) {
+            double v = m[j];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const double other = __shfl_xor(v, o, 64);
+                v = other < v ? other : v;
+            }
+            if (lane == 0) a.gmin[(int64_t)j * CAND_CAP + g] = v;
+        }
+}
+
+// (2) + (3) every block picks the nt thresholds from the group minima (pick_thr_block, plus each tau's margin) and appends the
+// rows of its share that pass ANY of them, once each, to the flat list staged_x1_kernel (xmode 2) evaluates -- through one
+// returning atomic per block, as score_pickfilter_kernel does
+__global__ __launch_bounds__(1024) void sweep_pickfilter_kernel(SweepSel a, int ng) {
+    if (a.s.info->status == AS_EZEROLAMBDA) return;
+    __shared__ double s_thr[TAU_GROUP];
+    for (int j = 0; j < a.nt; ++j) {
+        const double t = pick_thr_block<double>(a.gmin + (int64_t)j * CAND_CAP, ng, a.s.M) + sweep_pick(a.margin, j);
+        if (threadIdx.x == 0) s_thr[j] = t;
+        __syncthreads();   // (pick_thr_block's LDS is reused by the next tau)
+    }
+    double thr[TAU_GROUP];
+#pragma unroll
+    for (int j = 0; j < TAU_GROUP; ++j) thr[j] = j < a.nt ? s_thr[j] : -key_traits<double>::inf();
+    int* __restrict__ cidx = a.s.cidx;
+    int* counter = &a.s.info_w->sc_cnt;
+    const ScoreCtx c = load_ctx(a.s.info, 1.0);
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    constexpr int LCAP = 1024;
+    __shared__ int l_idx[LCAP];
+    __shared__ int s_ln, s_gbase;
+    if (threadIdx.x == 0) s_ln = 0;
+    __syncthreads();
+    const bool full0 = __hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > CAND_CAP;
+    for (int64_t row = a.s.r0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; row < a.s.r1 && !full0; row += stride) {
+        double cs, den;
+        sweep_row(a.s, c, row, cs, den);
+        bool keep = false;
+#pragma unroll
+        for (int j = 0; j < TAU_GROUP; ++j)
+            if (j < a.nt) keep = keep || -(a.tau[j] * cs + (1.0 - a.tau[j]) / den) <= thr[j];
+        if (keep) {
+            const int ls = atomicAdd(&s_ln, 1);
+            if (ls < LCAP) {
+                l_idx[ls] = (int)row;
+            } else {
+                const int slot = atomicAdd(counter, 1);
+                if (slot < CAND_CAP) cidx[slot] = (int)row;
+            }
+        }
+    }
+    __syncthreads();
+    const int ln = s_ln < LCAP ? s_ln : LCAP;
+    if (threadIdx.x == 0 && ln > 0) s_gbase = atomicAdd(counter, ln);
+    __syncthreads();
+    if (ln > 0) {
+        const int gb = s_gbase;
+        for (int t = threadIdx.x; t < ln; t += blockDim.x)
+            if (gb + t < CAND_CAP) cidx[gb + t] = l_idx[t];
+    }
+}
+
+struct SweepTaus {
+    int nt;
+    double tau[TAU_GROUP];
+};
+
+// staged_x1_final_kernel for nt taus (one space): lambda_q from the records while the other waves pull the union's exact
+// cosines and lambdas into LDS; then per tau the blend, the 1024-bin histogram prune to the topk-th bin and the (score desc,
+// id asc) rank count, list j into outs[j]; ONE publication (outs[0].seq) behind all lists.  Flags: the union's (k-NN list,
+// k-NN buffer, candidates that did not fit) go to every list, a prune overflow to its own.  The per-search state and the
+// block's head are cleared behind a pass in which every list is clean, as the single-tau kernel does.
+__global__ __launch_bounds__(1024) void sweep_final_kernel(const char* __restrict__ all, int64_t xbytes, int64_t krec, int xcap, int64_t k, int metric,
+                                                           int kernel, double sigma, double p, double tau0, SweepTaus st, int64_t topk, QInfo* info,
+                                                           HostOut* outs, int64_t seq, unsigned int* sc_hist, XHead* own_head) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    double* sc = (double*)smem;                 // CAND_CAP exact cosines
+    double* sl = sc + CAND_CAP;                 // lambdas
+    int* sid = (int*)(sl + CAND_CAP);           // ids
+    double* pk = (double*)(sid + CAND_CAP);     // PRUNE_CAP pruned scores (of the tau at hand)
+    int* pi = (int*)(pk + PRUNE_CAP);
+    __shared__ unsigned int khist[1024];
+    __shared__ int s_tot, s_flags, k_bin, k_cnt, s_lfl[TAU_GROUP];
+    const int tid = (int)threadIdx.x;
+    if (tid < 64) {
+        q_lambda_body((const as_knn_rec*)all, krec, krec, xbytes / (int64_t)sizeof(as_knn_rec), k, metric, kernel, sigma, p, tau0, info, 0);
+    } else {
+        const XHead* h = (const XHead*)(all + krec * (int64_t)sizeof(as_knn_rec));
+        const XCand* cs = (const XCand*)(h + 1);
+        int cnt = h->count, fl = h->flags;
+        if (cnt < 0 || cnt > xcap) {
+            cnt = 0;
+            fl |= 16;
+        }
+        if (tid == 64) {
+            s_tot = cnt;
+            s_flags = fl;
+        }
+        if (cnt <= CAND_CAP)
+            for (int t = tid - 64; t < cnt; t += (int)blockDim.x - 64) {
+                const XCand c = cs[t];
+                sc[t] = c.cosv;
+                sl[t] = c.lam;
+                sid[t] = (int)c.idx;
+            }
+    }
+    __syncthreads();
+    reset_query_hist(sc_hist, tid, blockDim.x);
+    int flags = s_flags;
+    int total = s_tot;
+    if (total > CAND_CAP) {
+        flags |= 16;
+        total = 0;
+    }
+    const double lq = info->lambda_q;
+    const int nhit = (int)(total < topk ? total : topk);
+    for (int j = 0; j < st.nt; ++j) {
+        const double tau = sweep_pick(st.tau, j);
+        khist[tid] = 0u;
+        if (tid == 0) k_cnt = 0;
+        __syncthreads();
+        double sv[4];
+        int mybin[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int t = tid + u * (int)blockDim.x;
+            mybin[u] = -1;
+            sv[u] = 0.0;
+            if (t < total) {
+                double s = blend_score(tau, sc[t], lq, sl[t]);
+                s = s == s ? s : -key_traits<double>::inf();
+                sv[u] = s;
+                const double fb = (1.0 - s) * 512.0;   // descending scores = ascending bins
+                mybin[u] = fb < 0.0 ? 0 : (fb >= 1023.0 ? 1023 : (int)fb);
+                atomicAdd(&khist[mybin[u]], 1u);
+            }
+        }
+        __syncthreads();
+        if (tid < 64) {   // 16 bins per lane, inclusive scan over the lanes, the lane whose bins reach nhit finishes
+            unsigned int hh[16], tot = 0;
+#pragma unroll
+            for (int b = 0; b < 16; ++b) {
+                hh[b] = khist[16 * tid + b];
+                tot += hh[b];
+            }
+            unsigned int incl = tot;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const unsigned int t2 = __shfl_up(incl, o, 64);
+                if (tid >= o) incl += t2;
+            }
+            const unsigned int excl = incl - tot, want_ = (unsigned)nhit;
+            if (tid == 0) k_bin = 1023;
+            if (want_ > 0 && excl < want_ && incl >= want_) {
+                unsigned int run = excl;
+                int bsel = 16 * tid;
+#pragma unroll
+                for (int b = 0; b < 16; ++b) {
+                    run += hh[b];
+                    if (run >= want_) break;
+                    bsel += 1;
+                }
+                k_bin = bsel;
+            }
+        }
+        __syncthreads();
+        const int bsel = k_bin;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int t = tid + u * (int)blockDim.x;
+            if (mybin[u] >= 0 && mybin[u] <= bsel) {
+                const int slot = atomicAdd(&k_cnt, 1);
+                if (slot < PRUNE_CAP) {
+                    pk[slot] = sv[u];
+                    pi[slot] = sid[t];
+                }
+            }
+        }
+        __syncthreads();
+        const int R = k_cnt;
+        if (tid == 0) s_lfl[j] = R > PRUNE_CAP ? 16 : 0;   // (mass ties in one bin: this tau goes to the single search)
+        if (R <= PRUNE_CAP) {
+            HostOut* out = outs + j;
+            for (int t = tid; t < R; t += blockDim.x) {
+                const double myk = -pk[t];
+                const int myi = pi[t];
+                int rank = 0;
+                for (int s2 = 0; s2 < R; ++s2) rank += lex_less<double>(-pk[s2], pi[s2], myk, myi) ? 1 : 0;
+                if (rank < nhit) {
+                    out->idx[rank] = myi;
+                    out->score[rank] = pk[t];
+                }
+            }
+        }
+        __syncthreads();   // (khist, k_cnt and the pruned list are the next tau's)
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+        int lany = 0;
+        for (int j = 0; j < st.nt; ++j) lany |= s_lfl[j];
+        const int clean = !flags && !lany;
+        for (int j = 0; j < st.nt; ++j) {
+            HostOut* out = outs + j;
+            const int fl = flags | s_lfl[j];
+            out->len = nhit;
+            out->lambda_q = info->lambda_q;
+            out->status = info->status;
+            out->knn_inexact = (fl & 1) ? 1 : 0;
+            out->score_inexact = 0;
+            out->overflow = ((fl & 4) ? 1 : 0) | ((fl & 8) ? 2 : 0) | ((fl & 16) ? 4 : 0) | ((fl & 32) ? 8 : 0);
+            out->state_reset = clean;
+            out->pad_ = 0;
+        }
+        if (clean) reset_query_state(info);
+        own_head->count = 0;
+        own_head->flags = 0;
+        own_head->pad[0] = 0;
+        own_head->pad[1] = 0;
+        publish(outs, seq);
+    }
+}
+
+// One shared pass of a tau sweep (as_search_taus) for nt <= TAU_GROUP distinct taus in [0, 1]: the coarse chain's scan, k-NN
+// records and lambda_q once, the union of the nt scorer candidate sets evaluated exactly once, nt rankings.  List j goes to
+// out_idx / out_score + j * lstride and out_len[j], served[j] = 1 -- or served[j] = 0 and nothing is written: the caller
+// redoes that tau with the single search (the chain cannot take this workspace or graph, the image did not serve the scan, a
+// candidate list did not fit, the k-NN list is not proven, tau j's prune overflowed).  Returns AS_EZEROLAMBDA (every list
+// served) when the pass proved lambda_q == 0.  The workspace's path hints move as after a coarse-chain search.
+as_status search_sweep(as_query* q, const double* query, int64_t d, const double* taus, int nt, int64_t lstride, int64_t* out_idx,
+                       double* out_score, int64_t* out_len, double* out_lambda_q, int* served) {
+    for (int j = 0; j < nt; ++j) served[j] = 0;
+    if (nt < 1 || nt > TAU_GROUP) {
+        set_err("search_sweep: %d taus (1 .. %d per pass)", nt, TAU_GROUP);
+        return AS_EINVAL;
+    }
+    const as_space* sp = q->sp;
+    const as_graph* gr = q->gr;
+    static const bool fused_x1_on = !(getenv("ARROWSPACE_FUSED_X1") && atoi(getenv("ARROWSPACE_FUSED_X1")) == 0);
+    static const bool chainc_on = !(getenv("ARROWSPACE_COARSE_CHAIN") && atoi(getenv("ARROWSPACE_COARSE_CHAIN")) == 0);
+    if (!chainc_on || !fused_x1_on || gr->lambda_mode == AS_LAMBDA_FEATURE || sp->opts.force_exact || (sp->opts.search_mode & 3) || q->no_fused ||
+        q->cap != 1 || sp->dp > 4096 || (q->scan_variant & 4) || std::max<int64_t>(q->k, 1) > REC_CAP || q->topk > lstride)
+        return AS_OK;
+    if (q->chainc_off > 0 && (q->chainc_off++ & 63) != 0) return AS_OK;   // (a recent coarse chain was not served cleanly)
+    q->exact = 0;
+    q->robust = 0;
+    const bool direct = q->crowded > 0 && (q->crowded++ & 63) != 0;   // (search_once: a crowded neighbourhood)
+    q->crowded_direct = direct ? 1 : 0;
+    q->fused_tail = 0;
+    q->tau_cur = taus[0];
+    q->chainc = 1;
+    q->allow_coarse = 1;
+    q->gang_ok = 0;
+    q->sc_late = 0;
+    const as_status qb = query_begin(q, query, -1, d, 0, sp->n, gr->gp.eps, -1);
+    q->allow_coarse = 0;
+    q->crowded_direct = 0;
+    const bool chainc = q->chainc && q->coarse;
+    q->chainc = 0;
+    AS_TRY(qb);
+    if (!chainc) return AS_OK;   // (the scan ran on another operand: its state is reset in front of the next one, info_clean = 0)
+    const int64_t krec = std::max<int64_t>(q->k, 1);
+    if (!q->x1_own) {
+        AS_HIP(hipMalloc(&q->x1_own, (size_t)as_query_x1_bytes(q, 1)));
+        AS_HIP(hipMemsetAsync(q->x1_own, 0, (size_t)as_query_x1_bytes(q, 1), q->stream));
+    } else if (q->x1_dirty) {
+        AS_HIP(hipMemsetAsync(q->x1_own + sizeof(as_knn_rec) * krec, 0, 16, q->stream));
+    }
+    if (!q->swout) {
+        AS_HIP(hipHostMalloc(&q->swout, sizeof(HostOut) * TAU_GROUP, hipHostMallocMapped | hipHostMallocCoherent));
+        AS_HIP(hipHostGetDevicePointer((void**)&q->swout_dev, q->swout, 0));
+        memset(q->swout, 0, sizeof(HostOut) * TAU_GROUP);
+        AS_HIP(hipMalloc(&q->sw_gmin, sizeof(double) * CAND_CAP * TAU_GROUP));
+        AS_HIP(hipFuncSetAttribute((const void*)sweep_final_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)x1_lds_b()));
+    }
+    hipStream_t st = q->stream;
+    q->x1_dirty = 1;
+    q->seq += 1;
+    // k-NN records and lambda_q (coarse_score_stage's first launch: it also zeroes the scorer's count)
+    if (direct) AS_TRY(knn_repair(q, gr->gp.eps, -1));
+    AS_TRY(x1_launch_block(q, q->x1_own, 1, false, true, 1));
+    hipLaunchKernelGGL(q_lambda_kernel, dim3(1), dim3(64), 0, st, (const as_knn_rec*)q->x1_own, krec, krec, krec, q->k, gr->metric, gr->kernel,
+                       gr->gp.sigma, gr->gp.p, gr->tau0, q->info, 1);
+    // the union of the nt threshold filters (coarse_score_stage's groups, threshold rank and margins, per tau)
+    const int64_t rows = q->r1 - q->r0;
+    int64_t G = (rows + CAND_CAP - 1) / CAND_CAP;
+    G = std::max<int64_t>(64, (G + 63) / 64 * 64);
+    const int ng = (int)((rows + G - 1) / G);
+    SweepSel a;
+    a.s = make_sel<double>(q, (const double*)nullptr, q->Ms, -1);
+    a.s.dots32 = q->dots32;
+    a.nt = nt;
+    const double coef = coef_query(q, false);
+    SweepTaus tt;
+    tt.nt = nt;
+    for (int j = 0; j < TAU_GROUP; ++j) {
+        const double t = j < nt ? taus[j] : 0.0;
+        a.tau[j] = t;
+        a.margin[j] = 2.0 * (t * coef * 1.0001 + 1.0e-9);
+        tt.tau[j] = t;
+    }
+    a.gmin = (double*)q->sw_gmin;
+    hipLaunchKernelGGL(sweep_gmin_kernel, dim3((unsigned)((ng + 3) / 4)), dim3(256), 0, st, a, G, ng);
+    const unsigned pg = (unsigned)std::min<int64_t>((rows + 1023) / 1024, std::max(q->cus, 1));
+    hipLaunchKernelGGL(sweep_pickfilter_kernel, dim3(pg), dim3(1024), 0, st, a, ng);
+    AS_HIP(hipGetLastError());
+    // the union's exact cosines and lambdas, once; nt rankings, one publication
+    AS_TRY(x1_launch_block(q, q->x1_own, 1, false, true, 2));
+    hipLaunchKernelGGL(sweep_final_kernel, dim3(1), dim3(1024), x1_lds_b(), st, (const char*)q->x1_own, as_query_x1_bytes(q, 1), krec, x1_cap(1), q->k,
+                       gr->metric, gr->kernel, gr->gp.sigma, gr->gp.p, gr->tau0, tt, q->topk, q->info, q->swout_dev, q->seq, q->sc_hist,
+                       (XHead*)q->x1_head);
+    AS_HIP(hipGetLastError());
+    if (q->ev_valid) AS_HIP(hipEventRecord(q->ev[2], st));
+    AS_TRY(wait_published_at(q, q->swout));
+    q->x1_dirty = 0;
+    q->xknn_dirty = 0;
+    int ov = 0;
+    bool all_clean = true;
+    for (int j = 0; j < nt; ++j) {
+        const HostOut* h = q->swout + j;
+        ov |= h->overflow;
+        all_clean = all_clean && !h->overflow && !h->knn_inexact && !h->score_inexact;
+    }
+    // (search_once's rules behind a coarse chain)
+    if (!direct) q->crowded = (ov & 1) ? 1 : 0;
+    if (all_clean) q->chainc_off = 0;
+    else if (!(!direct && (ov & 1) && !(ov & 6))) q->chainc_off = 1;
+    q->info_clean = q->swout[0].state_reset ? 1 : 0;
+    if (out_lambda_q) *out_lambda_q = q->swout[0].lambda_q;
+    if (all_clean && q->swout[0].status == AS_EZEROLAMBDA) {
+        for (int j = 0; j < nt; ++j) {
+            out_len[j] = 0;
+            served[j] = 1;
+        }
+        set_err("The lambdas are zero, check the magnitude of items and eps.");
+        return AS_EZEROLAMBDA;
+    }
+    for (int j = 0; j < nt; ++j) {
+        const HostOut* h = q->swout + j;
+        if (h->overflow || h->knn_inexact || h->score_inexact || h->status != AS_OK) continue;
+        for (int64_t t = 0; t < h->len; ++t) {
+            out_idx[j * lstride + t] = h->idx[t];
+            out_score[j * lstride + t] = h->score[t];
+        }
+        out_len[j] = h->len;
+        served[j] = 1;
+    }
+    return AS_OK;
 }
 
 // up to QB queries in one pass over the items (filter path, fp32 prefilters); out_status[b] is
