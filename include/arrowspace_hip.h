@@ -440,6 +440,19 @@ as_status as_search_taus(const as_space* sp, const as_graph* gr, const double* q
 /* out[0] as_search_taus calls, [1] shared passes that served at least one tau, [2] taus a shared pass did not serve, or could not
  * be run for (feature graphs, force_exact, a scan the image cannot serve, ...), redone by the single search */
 as_status as_sweep_counters(const as_space* sp, int64_t* out, int32_t n);
+/* Extension: b queries (row-major [b][d]) under ntau taus -- list (i, j), at out_idx / out_score + (i * ntau + j) * topk'
+ * (topk' = min(topk, nitems)), out_len[i * ntau + j] entries, is what as_search returns for query i and taus[j].  lambda_q per
+ * query -> out_lambda_q[i]; out_status[i] AS_OK / AS_EZEROLAMBDA (lambda_q == 0: every list of that query is empty).  Where
+ * as_search_batch batches (b > 1, no force_exact or search mode, no feature lambdas) the distinct taus in [0, 1] share batched
+ * passes, up to 8 per pass: one scan, k-NN step and lambda_q per 32 queries, a scorer tail per (query, tau) pair.  Equal taus are
+ * computed once; every other tau takes as_search_batch's route, and whatever a shared pass does not serve the single search.
+ * Serialised with as_search_batch (the batched workspaces). */
+as_status as_search_batch_taus(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d,
+                               const double* taus, int64_t ntau, int64_t* out_idx, double* out_score, int64_t* out_len,
+                               double* out_lambda_q, int32_t* out_status);
+/* out[0] as_search_batch_taus calls, [1] batched passes whose scorer tail served a tau sweep, [2] (query, tau) pairs those passes
+ * served, [3] pairs they left to the single search */
+as_status as_batch_sweep_counters(const as_space* sp, int64_t* out, int32_t n);
 
 /* ---- index persistence (extension; the reference exposes none): one flat file
  * holding the items, lambdas and graph arrays.  Loading re-ingests the items and uploads the

@@ -322,6 +322,50 @@ class ArrowSpace:
             _raise(st)
         return dict(zip(("calls", "shared_passes", "taus_redone"), (int(v) for v in out)))
 
+    def search_batch_taus(self, items, gl: GraphLaplacian, taus):
+        """Extension: B queries [B, D] under several taus -> B lists of one hit list per entry of `taus`; entry [b][j] is what
+        `search(items[b], gl, taus[j])` returns.  Where `search_batch` batches, the distinct taus in [0, 1] share its batched
+        passes (up to 8 per pass: one scan, k-NN step and lambda_q per 32 queries, a scorer tail per (query, tau) pair); equal
+        taus are computed once, any other tau takes `search_batch`'s route, and whatever a shared pass does not serve the single
+        search."""
+        if not isinstance(gl, GraphLaplacian):
+            raise TypeError("argument 'gl': expected GraphLaplacian")
+        Q = np.ascontiguousarray(items, dtype=np.float64)
+        if Q.ndim != 2:
+            raise TypeError("items must be a 2-D float64 array")
+        t = np.ascontiguousarray(taus, dtype=np.float64)
+        if t.ndim != 1:
+            raise TypeError("argument 'taus': expected a 1-D sequence of floats")
+        b, nt = Q.shape[0], t.shape[0]
+        if b == 0:
+            return []
+        if nt == 0:
+            return [[] for _ in range(b)]
+        topk = max(min(int(gl.graph_params["topk"]), self.nitems), 0)
+        idx = np.empty((b, nt, max(topk, 1)), dtype=np.int64)
+        sc = np.empty((b, nt, max(topk, 1)), dtype=np.float64)
+        ln = np.zeros((b, nt), dtype=np.int64)
+        lq = np.zeros(b, dtype=np.float64)
+        stt = np.zeros(b, dtype=np.int32)
+        st = _L.as_search_batch_taus(self._h, gl._h, Q.ctypes.data, b, Q.shape[1], t.ctypes.data, nt, idx.ctypes.data, sc.ctypes.data,
+                                     ln.ctypes.data, lq.ctypes.data, stt.ctypes.data)
+        if st:
+            _raise(st)
+        if (stt == _lib.AS_EZEROLAMBDA).any():
+            raise PanicException("The lambdas are zero, check the magnitude of items and eps.")
+        idx, sc = idx[:, :, :topk], sc[:, :, :topk]
+        return [[list(zip(ii[:l], ss[:l])) for ii, ss, l in zip(bi, bs, bl)]
+                for bi, bs, bl in zip(idx.tolist(), sc.tolist(), ln.tolist())]
+
+    def batch_sweep_counters(self) -> dict:
+        """Extension: `search_batch_taus` calls on this space, the batched passes whose scorer tail served them, the (query,
+        tau) pairs those passes served, and the pairs they left to the single search (pairs_redone)."""
+        out = np.zeros(4, dtype=np.int64)
+        st = _L.as_batch_sweep_counters(self._h, out.ctypes.data_as(C.c_void_p), 4)
+        if st:
+            _raise(st)
+        return dict(zip(("calls", "shared_passes", "pairs_served", "pairs_redone"), (int(v) for v in out)))
+
     def last_search_stats(self) -> dict:
         """Extension: device microseconds of the last search (HIP events on its stream)."""
         out = np.zeros(3, dtype=np.float64)

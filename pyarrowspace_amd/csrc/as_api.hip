@@ -893,6 +893,36 @@ as_status as_sweep_counters(const as_space* sp, int64_t* out, int32_t n) {
     return AS_OK;
 }
 
+// the batched workspaces for b > 1 queries (under sp->bmu); *unit = the passes launched together (2: a pair sharing one scan)
+static as_status batch_workspaces(const as_space* sp, const as_graph* gr, int64_t b, int* unit) {
+    if (sp->qcache_b && sp->qcache_b_gr != gr) {
+        for (as_query** w : {&sp->qcache_b, &sp->qcache_b2, &sp->qcache_b3, &sp->qcache_b4}) {
+            if (*w) as_query_free(*w);
+            *w = nullptr;
+        }
+    }
+    if (!sp->qcache_b) {
+        AS_TRY(query_create(sp, gr, QUERY_BATCH, &sp->qcache_b));
+        sp->qcache_b_gr = gr;
+    }
+    // More than one pass: a second workspace.  Rows of up to 768 columns: the two launch their passes as a PAIR, one scan for
+    // both (64 queries per read of the items: search_batch_launch_pair); more than one pair: a second pair of workspaces, pair
+    // p + 1 is queued before pair p is waited for.  Wider rows (a scan serves one workspace): the passes alternate between
+    // the two workspaces -- pass p + 1 is queued before pass p is waited for.  (No memory: fewer workspaces, the same results.)
+    static const bool no_pipe = getenv("ARROWSPACE_NO_BATCH_PIPELINE") != nullptr;
+    static const bool no_dual = getenv("ARROWSPACE_NO_BATCH_DUAL") != nullptr;
+    const bool pairs = !no_dual && (sp->dp + 63) / 64 * 64 / 2 <= 4 * 3 * 32 && gr->lambda_mode != AS_LAMBDA_FEATURE;
+    if (b > QUERY_BATCH && !sp->qcache_b2 && !no_pipe) {
+        if (query_create(sp, gr, QUERY_BATCH, &sp->qcache_b2) != AS_OK) sp->qcache_b2 = nullptr;
+    }
+    if (pairs && b > 2 * QUERY_BATCH && sp->qcache_b2 && !sp->qcache_b4 && !no_pipe) {
+        if (!sp->qcache_b3 && query_create(sp, gr, QUERY_BATCH, &sp->qcache_b3) != AS_OK) sp->qcache_b3 = nullptr;
+        if (sp->qcache_b3 && query_create(sp, gr, QUERY_BATCH, &sp->qcache_b4) != AS_OK) sp->qcache_b4 = nullptr;
+    }
+    *unit = pairs && sp->qcache_b2 && b > QUERY_BATCH ? 2 : 1;
+    return AS_OK;
+}
+
 as_status as_search_batch(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau,
                           int64_t* out_idx, double* out_score, int64_t* out_len, double* out_lambda_q, int32_t* out_status) {
     if (!sp || !gr || !queries || !out_idx || !out_score || !out_len) {
@@ -911,33 +941,7 @@ as_status as_search_batch(const as_space* sp, const as_graph* gr, const double* 
     // K-chunk passes of the same kernel): fp32 fast path only
     const bool batched = !sp->opts.force_exact && (sp->opts.search_mode & 3) == 0 && b > 1;
     int unit = 1;   // passes launched together
-    if (batched) {
-        if (sp->qcache_b && sp->qcache_b_gr != gr) {
-            for (as_query** w : {&sp->qcache_b, &sp->qcache_b2, &sp->qcache_b3, &sp->qcache_b4}) {
-                if (*w) as_query_free(*w);
-                *w = nullptr;
-            }
-        }
-        if (!sp->qcache_b) {
-            AS_TRY(query_create(sp, gr, QUERY_BATCH, &sp->qcache_b));
-            sp->qcache_b_gr = gr;
-        }
-        // More than one pass: a second workspace.  Rows of up to 768 columns: the two launch their passes as a PAIR, one scan for
-        // both (64 queries per read of the items: search_batch_launch_pair); more than one pair: a second pair of workspaces, pair
-        // p + 1 is queued before pair p is waited for.  Wider rows (a scan serves one workspace): the passes alternate between
-        // the two workspaces -- pass p + 1 is queued before pass p is waited for.  (No memory: fewer workspaces, the same results.)
-        static const bool no_pipe = getenv("ARROWSPACE_NO_BATCH_PIPELINE") != nullptr;
-        static const bool no_dual = getenv("ARROWSPACE_NO_BATCH_DUAL") != nullptr;
-        const bool pairs = !no_dual && (sp->dp + 63) / 64 * 64 / 2 <= 4 * 3 * 32 && gr->lambda_mode != AS_LAMBDA_FEATURE;
-        if (b > QUERY_BATCH && !sp->qcache_b2 && !no_pipe) {
-            if (query_create(sp, gr, QUERY_BATCH, &sp->qcache_b2) != AS_OK) sp->qcache_b2 = nullptr;
-        }
-        if (pairs && b > 2 * QUERY_BATCH && sp->qcache_b2 && !sp->qcache_b4 && !no_pipe) {
-            if (!sp->qcache_b3 && query_create(sp, gr, QUERY_BATCH, &sp->qcache_b3) != AS_OK) sp->qcache_b3 = nullptr;
-            if (sp->qcache_b3 && query_create(sp, gr, QUERY_BATCH, &sp->qcache_b4) != AS_OK) sp->qcache_b4 = nullptr;
-        }
-        unit = pairs && sp->qcache_b2 && b > QUERY_BATCH ? 2 : 1;
-    }
+    if (batched) AS_TRY(batch_workspaces(sp, gr, b, &unit));
     // a UNIT = the passes launched together: a pair (two workspaces), or one pass; two sets of workspaces alternate when there is
     // more than one unit and the workspaces exist (`piped`)
     as_query* ws[4] = {sp->qcache_b, sp->qcache_b2, sp->qcache_b3, sp->qcache_b4};
@@ -1005,6 +1009,176 @@ as_status as_search_batch(const as_space* sp, const as_graph* gr, const double* 
     }
     if (timing && batched) dbg("as_search_batch: %lld passes, host time per pass: launch half %.0f us, collect half (with its wait) %.0f us",
                                (long long)pass, t_launch / std::max<int64_t>(pass, 1), t_collect / std::max<int64_t>(pass, 1));
+    return AS_OK;
+}
+
+// One batched tau sweep over b > 1 queries for nt <= TAU_GROUP distinct taus in [0, 1] (under sp->bmu): as_search_batch's
+// workspaces, passes, pairs and pipelining, the scorer tail once per (query, tau) pair.  Pair (i, j): pidx / psc +
+// (i * nt + j) * topk, plen / pst [i * nt + j], plq [i]; pst -1: left to the single search.  *passes: passes that ran the tail.
+static as_status batch_sweep_run(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, const double* gt,
+                                 int nt, int64_t topk, int64_t* pidx, double* psc, int64_t* plen, double* plq, int32_t* pst,
+                                 int64_t* passes) {
+    int unit = 1;
+    AS_TRY(batch_workspaces(sp, gr, b, &unit));
+    as_query* ws[4] = {sp->qcache_b, sp->qcache_b2, sp->qcache_b3, sp->qcache_b4};
+    const bool piped = b > unit * QUERY_BATCH && ws[2 * unit - 1] != nullptr;
+    const int nws = unit * (piped ? 2 : 1);
+    auto drain = [&](as_status s) {
+        if (nws > 1)
+            for (int w = 0; w < nws; ++w) (void)hipStreamSynchronize((hipStream_t)as_query_stream(ws[w]));
+        return s;
+    };
+    const int64_t UNIT = (int64_t)unit * QUERY_BATCH;
+    auto launch_unit = [&](int64_t j) -> as_status {
+        as_query* const* w = ws + (piped ? unit * (j & 1) : 0);
+        const int64_t i0 = j * UNIT, i1 = i0 + QUERY_BATCH;
+        const int nb0 = (int)std::min<int64_t>(QUERY_BATCH, b - i0);
+        if (unit == 2 && i1 < b)
+            return search_batch_sweep_launch_pair(w[0], w[1], queries + i0 * d, nb0, queries + i1 * d, (int)std::min<int64_t>(QUERY_BATCH, b - i1), d,
+                                                  gt, nt);
+        return search_batch_sweep_launch(w[0], queries + i0 * d, nb0, d, gt, nt);
+    };
+    if (piped) {
+        const as_status s0 = launch_unit(0);
+        if (s0 != AS_OK) return drain(s0);
+    }
+    int64_t pass = 0;
+    for (int64_t i0 = 0; i0 < b; i0 += QUERY_BATCH, ++pass) {
+        const int nb = (int)std::min<int64_t>(QUERY_BATCH, b - i0);
+        const int64_t j = pass / unit;
+        as_query* cur = ws[(piped ? unit * (j & 1) : 0) + (int)(pass % unit)];
+        as_status s = AS_OK;
+        if (pass % unit == 0) {
+            if (!piped) s = launch_unit(j);
+            else if ((j + 1) * UNIT < b) s = launch_unit(j + 1);
+        }
+        if (s == AS_OK)
+            s = search_batch_sweep_collect(cur, nb, gt, nt, topk, pidx + i0 * nt * topk, psc + i0 * nt * topk, plen + i0 * nt, plq + i0,
+                                           pst + i0 * nt);
+        if (s != AS_OK) return drain(s);
+        *passes += query_sweep_ran(cur);
+    }
+    return AS_OK;
+}
+
+// Extension: b queries under ntau taus -- entry (i, j) is what as_search returns for query i and taus[j].  Equal taus are
+// computed once.  Where as_search_batch batches (b > 1, no force_exact or search_mode, no feature lambdas) the distinct taus in
+// [0, 1] share batched passes, up to TAU_GROUP per pass (batch_sweep_run); every other tau takes as_search_batch's own route,
+// and every pair a shared pass does not serve is redone by the single search with its own tau.
+as_status as_search_batch_taus(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, const double* taus,
+                               int64_t ntau, int64_t* out_idx, double* out_score, int64_t* out_len, double* out_lambda_q, int32_t* out_status) {
+    if (!sp || !gr || b < 0 || ntau < 0 || (b > 0 && !queries) || (b > 0 && ntau > 0 && (!taus || !out_idx || !out_score || !out_len))) {
+        set_err("as_search_batch_taus: null argument");
+        return AS_EINVAL;
+    }
+    if (d != sp->d) {
+        set_err("query length %lld must match nfeatures %lld", (long long)d, (long long)sp->d);
+        return AS_EINVAL;
+    }
+    AS_TRY(graph_matches(sp, gr, "as_search_batch_taus"));
+    if (b == 0 || ntau == 0) return AS_OK;
+    sp->bsweep_count[0].fetch_add(1, std::memory_order_relaxed);
+    const int64_t topk = std::min<int64_t>(gr->gp.topk, sp->n);
+    // distinct taus (bit patterns), in order of first appearance
+    std::vector<double> uniq;
+    std::vector<int64_t> slot((size_t)ntau);
+    for (int64_t j = 0; j < ntau; ++j) {
+        int64_t u = 0;
+        while (u < (int64_t)uniq.size() && memcmp(&uniq[u], &taus[j], sizeof(double)) != 0) ++u;
+        if (u == (int64_t)uniq.size()) uniq.push_back(taus[j]);
+        slot[j] = u;
+    }
+    const int64_t nu = (int64_t)uniq.size();
+    const bool batched = !sp->opts.force_exact && (sp->opts.search_mode & 3) == 0 && b > 1 && gr->lambda_mode != AS_LAMBDA_FEATURE;
+    std::vector<int64_t> shared;
+    std::vector<char> is_shared((size_t)nu, 0);
+    for (int64_t u = 0; u < nu && batched; ++u)
+        if (uniq[u] >= 0.0 && uniq[u] <= 1.0) {
+            shared.push_back(u);
+            is_shared[u] = 1;
+        }
+    // per distinct tau: [b][topk] lists, [b] lengths and statuses
+    const size_t per = (size_t)(b * std::max<int64_t>(topk, 1));
+    std::vector<int64_t> uidx(per * nu), ulen((size_t)(b * nu), 0);
+    std::vector<double> usc(per * nu), lq((size_t)b, 0.0);
+    std::vector<int32_t> ust((size_t)(b * nu), 0);
+    int64_t passes = 0, served = 0, redone = 0;
+    if (!shared.empty()) {
+        std::lock_guard<std::mutex> lock(sp->bmu);
+        AS_HIP(hipSetDevice(sp->device));
+        for (size_t g0 = 0; g0 < shared.size(); g0 += TAU_GROUP) {
+            const int nt = (int)std::min<size_t>(TAU_GROUP, shared.size() - g0);
+            double gt[TAU_GROUP];
+            for (int j = 0; j < nt; ++j) gt[j] = uniq[shared[g0 + j]];
+            std::vector<int64_t> pidx((size_t)(b * nt * std::max<int64_t>(topk, 1))), plen((size_t)(b * nt), 0);
+            std::vector<double> psc(pidx.size());
+            std::vector<int32_t> pst((size_t)(b * nt), -1);
+            AS_TRY(batch_sweep_run(sp, gr, queries, b, d, gt, nt, topk, pidx.data(), psc.data(), plen.data(), lq.data(), pst.data(), &passes));
+            for (int64_t i = 0; i < b; ++i)
+                for (int j = 0; j < nt; ++j) {
+                    const int64_t u = shared[g0 + j], p = i * nt + j;
+                    ust[u * b + i] = pst[p];
+                    if (pst[p] == -1) continue;
+                    served += 1;
+                    ulen[u * b + i] = plen[p];
+                    for (int64_t t = 0; t < plen[p]; ++t) {
+                        uidx[u * per + i * topk + t] = pidx[p * topk + t];
+                        usc[u * per + i * topk + t] = psc[p * topk + t];
+                    }
+                }
+        }
+    }
+    sp->bsweep_count[1].fetch_add(passes, std::memory_order_relaxed);
+    sp->bsweep_count[2].fetch_add(served, std::memory_order_relaxed);
+    // the other taus: as_search_batch's route for each
+    for (int64_t u = 0; u < nu; ++u) {
+        if (is_shared[u]) continue;
+        AS_TRY(as_search_batch(sp, gr, queries, b, d, uniq[u], uidx.data() + u * per, usc.data() + u * per, ulen.data() + u * b, lq.data(),
+                               ust.data() + u * b));
+    }
+    // the pairs a shared pass left: the single search with their own tau
+    for (int64_t u = 0; u < nu; ++u) {
+        if (!is_shared[u]) continue;
+        for (int64_t i = 0; i < b; ++i) {
+            if (ust[u * b + i] != -1) continue;
+            redone += 1;
+            double l = 0.0;
+            const as_status s1 = search_pooled(sp, gr, queries + i * d, d, uniq[u], uidx.data() + u * per + i * topk, usc.data() + u * per + i * topk,
+                                               ulen.data() + u * b + i, &l);
+            lq[i] = l;
+            ust[u * b + i] = (int32_t)s1;
+            if (s1 != AS_OK && s1 != AS_EZEROLAMBDA) {
+                sp->bsweep_count[3].fetch_add(redone, std::memory_order_relaxed);
+                return s1;
+            }
+        }
+    }
+    sp->bsweep_count[3].fetch_add(redone, std::memory_order_relaxed);
+    for (int64_t i = 0; i < b; ++i) {
+        int32_t st = AS_OK;
+        for (int64_t j = 0; j < ntau; ++j) {
+            const int64_t u = slot[j];
+            const int32_t su = ust[u * b + i];
+            const int64_t len = su == AS_EZEROLAMBDA ? 0 : ulen[u * b + i];
+            if (su == AS_EZEROLAMBDA) st = AS_EZEROLAMBDA;
+            for (int64_t t = 0; t < len; ++t) {
+                out_idx[(i * ntau + j) * topk + t] = uidx[u * per + i * topk + t];
+                out_score[(i * ntau + j) * topk + t] = usc[u * per + i * topk + t];
+            }
+            out_len[i * ntau + j] = len;
+        }
+        if (out_lambda_q) out_lambda_q[i] = lq[i];
+        if (out_status) out_status[i] = st;
+    }
+    return AS_OK;
+}
+
+as_status as_batch_sweep_counters(const as_space* sp, int64_t* out, int32_t n) {
+    if (!sp || !out) {
+        set_err("as_batch_sweep_counters: null argument");
+        return AS_EINVAL;
+    }
+    for (int i = 0; i < n && i < 4; ++i) out[i] = sp->bsweep_count[i].load(std::memory_order_relaxed);
     return AS_OK;
 }
 

@@ -131,6 +131,9 @@ struct as_space {
     // as_sweep_counters: [0] as_search_taus calls, [1] shared passes that served at least one tau, [2] tau values a shared
     // pass did not serve (or could not be run for) that were redone by the single search
     mutable std::atomic<int64_t> sweep_count[3] = {};
+    // as_batch_sweep_counters: [0] as_search_batch_taus calls, [1] batched passes whose scorer tail served a tau sweep, [2] (query,
+    // tau) pairs such a pass served, [3] pairs it left to the single search
+    mutable std::atomic<int64_t> bsweep_count[4] = {};
     mutable int64_t unproven_searches = 0;   // searches returned although their a-posteriori check failed on the strongest path
     mutable double kstats[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // accumulated by as_knn_rows
 };
@@ -483,6 +486,12 @@ as_status search_batch_launch(as_query* q, const double* queries, int nb, int64_
 as_status search_batch_launch_pair(as_query* a, as_query* b, const double* qa, int nba, const double* qb, int nbb, int64_t d, double tau);
 as_status search_batch_collect(as_query* q, int nb, double tau, int64_t topk, int64_t* out_idx, double* out_score, int64_t* out_len,
                                double* out_lambda_q, int32_t* out_status);
+as_status search_batch_sweep_launch(as_query* q, const double* queries, int nb, int64_t d, const double* taus, int nt);
+as_status search_batch_sweep_launch_pair(as_query* a, as_query* b, const double* qa, int nba, const double* qb, int nbb, int64_t d,
+                                         const double* taus, int nt);
+as_status search_batch_sweep_collect(as_query* q, int nb, const double* taus, int nt, int64_t topk, int64_t* out_idx, double* out_score,
+                                     int64_t* out_len, double* out_lambda_q, int32_t* out_status);
+int query_sweep_ran(const as_query* q);
 constexpr int QUERY_BATCH = 32;  // == GQ in as_search.hip: query slots of the batched workspace
 constexpr int TAU_GROUP = 8;     // taus one shared pass of a tau sweep serves (search_sweep, as_search_taus)
 

@@ -260,6 +260,15 @@ struct as_query {
     as::HostOut* swout = nullptr;        // tau sweep (search_sweep): TAU_GROUP pinned result lists, one per tau of a shared pass ...
     as::HostOut* swout_dev = nullptr;
     void* sw_gmin = nullptr;             // ... and the group minima of its TAU_GROUP scorer keys ([TAU_GROUP][CAND_CAP] doubles); both made on first use
+    // batched tau sweep (run_score_sweep): per (slot, tau) pair, [GQ][TAU_GROUP] each -- pinned result lists, QInfo (threshold,
+    // candidate count, flags), group minima, candidate keys and rows ([...][CAND_CAP]); made on the first sweep of the workspace
+    as::HostOut* bsw_out = nullptr;
+    as::HostOut* bsw_out_dev = nullptr;
+    as::QInfo* bsw_info = nullptr;
+    double* bsw_gmin = nullptr;
+    double* bsw_ckey = nullptr;
+    int* bsw_cidx = nullptr;
+    int bsw_ok = 0;                      // the last pass ran that tail (else every pair goes to the single search)
 };
 
 namespace as {

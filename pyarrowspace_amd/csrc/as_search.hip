@@ -750,6 +750,211 @@ __global__ __launch_bounds__(256) void score_filter_batch_kernel(BatchSel a, int
     }
 }
 
+// ------------------------------------------------------------------ batched tau sweep: all query slots x up to TAU_GROUP taus
+// The batched pass's scan, k-NN step and lambda_q do not depend on tau; only the blend of the scorer key, the threshold picked
+// from it and the ranking do.  The two kernels below are score_gmin_batch_kernel / score_filter_batch_kernel for NSW slots x
+// NTW taus at once: a row's norm, lambda and the slots' dots are read once, and every (slot, tau) pair gets the key
+// batch_key gives that slot under that tau (half mode of its own, as launch_score picks it), its own group minima, threshold,
+// candidate buffer and overflow flag.  score_finish_sweep_kernel then runs the batched finish once per pair, so a pair's
+// candidate set and exact evaluation are those of search_batch(..., tau) for that slot.
+struct BatchSweep {
+    BatchSel b;               // the pass's rows and slots (b.half: nonzero when the dots are fp16 cosines; b.tau / b.gmin / b.ckey /
+                              // b.cidx / b.info_w unused)
+    int nt;
+    int need32, need64;       // some tau takes the fp32 lambdas (half mode 1) / the fp64 ones
+    double tau[TAU_GROUP];
+    int half[TAU_GROUP];      // launch_score's half_mode for each tau
+    QInfo* pinfo;             // [GQ][TAU_GROUP] per-pair threshold (thr64) and candidate count (sc_cnt)
+    double* gmin;             // [GQ][TAU_GROUP][CAND_CAP]
+    double* ckey;
+    int* cidx;
+};
+
+// batch_key with the tau and half mode of one sweep tau (the same expressions: the same bits)
+__device__ __forceinline__ double sweep_batch_key(int half, double tau, float dot, double rn, double lrow, double rq, double lq) {
+    if (half == 1) return (double)batch_key32((float)tau, dot, (float)lrow, (float)lq);
+    const double cs = half ? (double)dot : (double)dot * rn * rq;
+    return -(tau * cs + (1.0 - tau) / (1.0 + fabs(lq - lrow)));
+}
+
+// wave-wide minima of P values per lane in 63 exchanges instead of 6 P: every step halves the values a lane holds and swaps the
+// other half with its partner (transpose-reduce); lane L ends with the minimum of value (L % P) over the whole wave
+template <int P>
+__device__ __forceinline__ double wave_min_transpose(double (&v)[P]) {
+    const int lane = lane_id();
+#pragma unroll
+    for (int h = P / 2; h >= 1; h >>= 1) {
+        const bool up = (lane & h) != 0;
+#pragma unroll
+        for (int i = 0; i < h; ++i) {
+            const double send = up ? v[i] : v[i + h];
+            const double keep = up ? v[i + h] : v[i];
+            const double recv = __shfl_xor(send, h, 64);
+            v[i] = recv < keep ? recv : keep;
+        }
+    }
+    double r = v[0];
+#pragma unroll
+    for (int o = P; o < 64; o <<= 1) {
+        const double other = __shfl_xor(r, o, 64);
+        r = other < r ? other : r;
+    }
+    return r;
+}
+
+// a row's lambdas as the taus' keys take them
+__device__ __forceinline__ void sweep_row_lambda(const BatchSweep& a, int64_t row, double& l32, double& l64) {
+    l32 = a.need32 ? (double)a.b.lam32[row] : 0.0;
+    l64 = a.need64 ? a.b.lam64[row] : 0.0;
+}
+
+// group minima: one wave per (group of G rows, NSW slots, NTW taus); blockIdx.y = slot octet, blockIdx.z = the z-th NTW taus
+// (NTW = 2: 16 minima per lane stay in registers -- 8 slots x 4 or 8 taus in one wave spilled them to scratch, 0.9 ms per
+// launch at 1M rows; a second tau pair re-reads the dots, mostly from L2)
+template <int NSW, int NTW>
+__global__ __launch_bounds__(256) void score_gmin_sweep_kernel(BatchSweep a, int64_t G, int ngroups) {
+    constexpr int P = NSW * NTW;
+    __shared__ double s_rq[NSW], s_lq[NSW];
+    const int s0 = blockIdx.y * NSW;
+    const int j0 = blockIdx.z * NTW;
+    if (threadIdx.x < NSW) {
+        const double nq = a.b.info[s0 + threadIdx.x].nq;
+        s_rq[threadIdx.x] = nq > 0.0 ? rsqrt(nq) : 0.0;
+        s_lq[threadIdx.x] = a.b.info[s0 + threadIdx.x].lambda_q;
+    }
+    __syncthreads();
+    const int lane = lane_id();
+    const int64_t g = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (g >= ngroups) return;
+    const int64_t lo = a.b.r0 + g * G;
+    const int64_t hi = lo + G < a.b.r1 ? lo + G : a.b.r1;
+    double tj[NTW];
+    int hj[NTW];
+#pragma unroll
+    for (int j = 0; j < NTW; ++j) {   // (taus j0 + j: selected, not indexed -- a dynamic index would copy the arrays to scratch)
+        tj[j] = a.tau[0];
+        hj[j] = a.half[0];
+#pragma unroll
+        for (int i = 1; i < TAU_GROUP; ++i) {
+            tj[j] = j0 + j == i ? a.tau[i] : tj[j];
+            hj[j] = j0 + j == i ? a.half[i] : hj[j];
+        }
+    }
+    double m[P];
+#pragma unroll
+    for (int p = 0; p < P; ++p) m[p] = key_traits<double>::inf();
+    for (int64_t row = lo + lane; row < hi; row += 64) {
+        double l32, l64;
+        sweep_row_lambda(a, row, l32, l64);
+        double rn = 0.0;
+        if (!a.b.half) {
+            const double nrow = a.b.n64[row];
+            rn = nrow > 0.0 ? rsqrt(nrow) : 0.0;
+        }
+        float dv[NSW];
+        batch_dots<NSW>(a.b, s0, row, dv);
+#pragma unroll
+        for (int s = 0; s < NSW; ++s)
+#pragma unroll
+            for (int j = 0; j < NTW; ++j)
+                if (j0 + j < a.nt) {
+                    const double k = sweep_batch_key(hj[j], tj[j], dv[s], rn, hj[j] == 1 ? l32 : l64, s_rq[s], s_lq[s]);
+                    m[s * NTW + j] = k < m[s * NTW + j] ? k : m[s * NTW + j];
+                }
+    }
+    const double v = wave_min_transpose<P>(m);
+    const int s = (lane % P) / NTW, j = j0 + lane % NTW;
+    if (lane < P && j < a.nt && s0 + s < a.b.ns) a.gmin[((int64_t)(s0 + s) * TAU_GROUP + j) * CAND_CAP + g] = v;
+}
+
+// thresholds of the (slot, tau) pairs: blockIdx.y = tau, blockIdx.z = slot (pick_thr_kernel's)
+__global__ __launch_bounds__(1024) void pick_thr_sweep_kernel(const double* __restrict__ gmin, int ng, int M, QInfo* pinfo) {
+    const int64_t p = (int64_t)blockIdx.z * TAU_GROUP + blockIdx.y;
+    const double thr = pick_thr_block<double>(gmin + p * CAND_CAP, ng, M);
+    if (threadIdx.x == 0) pinfo[p].thr64 = thr;
+}
+
+// the filter: a wave takes a 64-row chunk, lanes 0 .. P-1 ask whether their (slot, tau) pair can take rows of its group, one
+// ballot spreads the answer (score_filter_batch_kernel's pattern, one lane per pair); passing rows go to the pair's own buffer
+template <int NSW, int NTW>
+__global__ __launch_bounds__(256) void score_filter_sweep_kernel(BatchSweep a, int64_t G) {
+    constexpr int P = NSW * NTW;
+    static_assert(P <= 64, "one lane per (slot, tau) pair");
+    __shared__ double s_rq[NSW], s_lq[NSW], s_thr[P];
+    const int s0 = blockIdx.y * NSW;
+    if (threadIdx.x < NSW) {
+        const double nq = a.b.info[s0 + threadIdx.x].nq;
+        s_rq[threadIdx.x] = nq > 0.0 ? rsqrt(nq) : 0.0;
+        s_lq[threadIdx.x] = a.b.info[s0 + threadIdx.x].lambda_q;
+    }
+    if (threadIdx.x < P) {
+        const int s = threadIdx.x / NTW, j = threadIdx.x % NTW;
+        // idle pairs never pass
+        s_thr[threadIdx.x] = s0 + s < a.b.ns && j < a.nt ? a.pinfo[(s0 + s) * TAU_GROUP + j].thr64 : -key_traits<double>::inf();
+    }
+    __syncthreads();
+    unsigned long long full = 0;   // bit p: pair p has overflowed its candidate buffer (mass ties): stop adding to its counter
+    const int lane = lane_id();
+    const int ls = (lane % P) / NTW, lj = lane % NTW;
+    const bool lact = lane < P && lj < a.nt && s0 + ls < a.b.ns;
+    const int64_t lpair = (int64_t)(s0 + (lact ? ls : 0)) * TAU_GROUP + (lact ? lj : 0);
+    const int64_t nchunk = (a.b.r1 - a.b.r0 + 63) / 64;
+    const int64_t nwave = (int64_t)gridDim.x * (blockDim.x >> 6);
+    for (int64_t ch = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); ch < nchunk; ch += nwave) {
+        const int64_t g = (ch * 64) / G;
+        const bool mine = lact && a.gmin[lpair * CAND_CAP + g] <= s_thr[lane % P];
+        const unsigned long long actm = (unsigned long long)__ballot(mine);
+        if (!actm) continue;
+        const int64_t row = a.b.r0 + ch * 64 + lane;
+        if (row >= a.b.r1) continue;
+        double l32, l64;
+        sweep_row_lambda(a, row, l32, l64);
+        double rn = 0.0;
+        if (!a.b.half) {
+            const double nrow = a.b.n64[row];
+            rn = nrow > 0.0 ? rsqrt(nrow) : 0.0;
+        }
+        float dv[NSW];
+        batch_dots<NSW>(a.b, s0, row, dv);
+#pragma unroll
+        for (int s = 0; s < NSW; ++s)
+#pragma unroll
+            for (int j = 0; j < NTW; ++j) {
+                const int p = s * NTW + j;
+                if (!((actm >> p) & 1ull)) continue;
+                const double k = sweep_batch_key(a.half[j], a.tau[j], dv[s], rn, a.half[j] == 1 ? l32 : l64, s_rq[s], s_lq[s]);
+                if (k <= s_thr[p] && !((full >> p) & 1ull)) {
+                    const int64_t pp = (int64_t)(s0 + s) * TAU_GROUP + j;
+                    int* cnt = &a.pinfo[pp].sc_cnt;
+                    if (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > CAND_CAP) {   // (as score_filter_batch_kernel)
+                        full |= 1ull << p;
+                        continue;
+                    }
+                    const int slot = atomicAdd(cnt, 1);
+                    if (slot < CAND_CAP) {
+                        a.ckey[pp * CAND_CAP + slot] = k;
+                        a.cidx[pp * CAND_CAP + slot] = (int)row;
+                    } else {
+                        full |= 1ull << p;
+                    }
+                }
+            }
+    }
+}
+
+// every (slot, tau) pair starts from its slot's QInfo as the k-NN step left it (norm, lambda_q, status, k-NN flags), with an
+// empty candidate buffer: one thread per pair
+__global__ __launch_bounds__(256) void sweep_pair_info_kernel(const QInfo* __restrict__ info, QInfo* __restrict__ pinfo, int nb, int nt) {
+    const int t = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    const int s = t / TAU_GROUP, j = t % TAU_GROUP;
+    if (s >= nb || j >= nt) return;
+    QInfo v = info[s];
+    v.sc_cnt = 0;
+    v.score_inexact = 0;
+    v.nhit = 0;
+    pinfo[t] = v;
+}
+
 // ------------------------------------------------------------------ exact global selection (overflow fallback for wide lists)
 // Radix select over the composite (ordered key bits, row index) of ALL scanned rows: KP passes
 // over the key bytes, then 4 over the index bytes among the rows tied at the M-th key.  The
@@ -1517,14 +1722,16 @@ __device__ __forceinline__ void publish(HostOut* out, int64_t seq) {
 // them in a.ci); their keys -- the mixed form of score_key<double>: fp32 dot, everything else fp64 -- are formed here, now
 // that lambda_q exists.  The M smallest of them are the M smallest keys of all scanned rows (scan_dma_kernel, SC), so
 // what follows is what follows the threshold filter.  qx_pre: the query already staged in LDS by the caller.
+// z: the candidate buffer, QInfo, hit records and result list to use; zq: the query slot (the same, but for the (slot, tau)
+// pairs of a batched tau sweep, score_finish_sweep_kernel)
 template <typename T>
-__device__ __forceinline__ void score_finish_body(FinishArgs a, double coef_s, char* smem, const double* qx_pre, const float* scan_dots, int sc_total) {
+__device__ __forceinline__ void score_finish_body_at(FinishArgs a, double coef_s, char* smem, const double* qx_pre, const float* scan_dots, int sc_total,
+                                                     int z, int zq) {
     AS_STAMP(16);
-    const int z = blockIdx.z;
     const T* ckey = (const T*)a.ck + (int64_t)z * CAND_CAP;
     const int* cidx = a.ci + (int64_t)z * CAND_CAP;
     a.info += z;
-    a.q64 += (int64_t)z * a.ss.q;
+    a.q64 += (int64_t)zq * a.ss.q;
     if (a.hits) a.hits += (int64_t)z * a.ss.hits;
     if (a.hout) a.hout += z;
     T* sk = (T*)smem;
@@ -1738,11 +1945,33 @@ __device__ __forceinline__ void score_finish_body(FinishArgs a, double coef_s, c
     }
     AS_STAMP(20);
 }
+template <typename T>
+__device__ __forceinline__ void score_finish_body(FinishArgs a, double coef_s, char* smem, const double* qx_pre, const float* scan_dots, int sc_total) {
+    score_finish_body_at<T>(a, coef_s, smem, qx_pre, scan_dots, sc_total, (int)blockIdx.z, (int)blockIdx.z);
+}
 
 template <typename T>
 __global__ __launch_bounds__(1024) void score_finish_kernel(FinishArgs a, double coef_s) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     score_finish_body<T>(a, coef_s, smem, nullptr, nullptr, 0);
+}
+
+// the batched finish once per (slot, tau) pair of a tau sweep: blockIdx.y = tau, blockIdx.z = slot.  The pair's tau and coef_s,
+// its QInfo, candidate buffer and result list (a.info / a.ck / a.ci / a.hout: [GQ][TAU_GROUP]), the slot's query.
+struct SweepCoef {
+    double tau[TAU_GROUP], coef[TAU_GROUP];
+};
+__global__ __launch_bounds__(1024) void score_finish_sweep_kernel(FinishArgs a, SweepCoef c) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int j = (int)blockIdx.y, s = (int)blockIdx.z;
+    double tau = c.tau[0], coef = c.coef[0];
+#pragma unroll
+    for (int i = 1; i < TAU_GROUP; ++i) {   // (a dynamic index into the by-value arrays would copy them to scratch)
+        tau = j == i ? c.tau[i] : tau;
+        coef = j == i ? c.coef[i] : coef;
+    }
+    a.tau = tau;
+    score_finish_body_at<double>(a, coef, smem, nullptr, nullptr, 0, s * TAU_GROUP + j, s);
 }
 
 // Waves 1..15 of a finish kernel: gather the reports of the scan's waves (SC_WCAP words each: the count, then the rows;
@@ -2689,6 +2918,74 @@ static as_status run_score(as_query* q, double tau, int fuse_final) {
     return AS_OK;
 }
 
+// The batched pass's scorer tail for nt <= TAU_GROUP taus (search_batch_sweep_*): launch_score's batched branch with every
+// (slot, tau) pair in the place of a slot -- pair keys, minima, thresholds, candidate buffers and finish of their own, each
+// tau with launch_score's half mode and coef_s.  Each pair publishes to q->bsw_out[slot * TAU_GROUP + tau].  q->bsw_ok = 0
+// where launch_score would not take that branch (nothing is launched: the caller leaves every pair to the single search).
+// The per-pair buffers are made on the first sweep (search_batch alone never needs them).
+static as_status run_score_sweep(as_query* q, const double* taus, int nt) {
+    q->bsw_ok = 0;
+    if (q->r1 - q->r0 <= 0 || q->exact || q->robust || q->cap != GQ || nt < 1 || nt > TAU_GROUP) return AS_OK;
+    const size_t np = (size_t)GQ * TAU_GROUP;
+    if (!q->bsw_out) {
+        AS_HIP(hipHostMalloc(&q->bsw_out, sizeof(HostOut) * np, hipHostMallocMapped | hipHostMallocCoherent));
+        AS_HIP(hipHostGetDevicePointer((void**)&q->bsw_out_dev, q->bsw_out, 0));
+        memset(q->bsw_out, 0, sizeof(HostOut) * np);
+        AS_HIP(hipFuncSetAttribute((const void*)score_finish_sweep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)score_lds<double>()));
+    }
+    if (!q->bsw_info) AS_HIP(hipMalloc(&q->bsw_info, sizeof(QInfo) * np));
+    if (!q->bsw_gmin) AS_HIP(hipMalloc(&q->bsw_gmin, sizeof(double) * CAND_CAP * np));
+    if (!q->bsw_ckey) AS_HIP(hipMalloc(&q->bsw_ckey, sizeof(double) * CAND_CAP * np));
+    if (!q->bsw_cidx) AS_HIP(hipMalloc(&q->bsw_cidx, sizeof(int) * CAND_CAP * np));
+    hipStream_t st = q->stream;
+    const int64_t rows = q->r1 - q->r0;
+    int64_t G = (rows + CAND_CAP - 1) / CAND_CAP;
+    G = std::max<int64_t>(64, (G + 63) / 64 * 64);
+    const int ng = (int)((rows + G - 1) / G);
+    const int nb = q->nb;
+    BatchSweep w;
+    memset(&w, 0, sizeof(w));
+    BatchSel& b = w.b;
+    b.dots32 = q->dots32; b.n64 = q->sp->n64; b.lam64 = q->sp->lam64; b.lam32 = q->sp->lam32; b.info = q->info; b.info_w = q->info;
+    b.r0 = q->r0; b.r1 = q->r1; b.sd = q->ss.dots; b.ts = q->ss.dots_ts; b.rs = q->ss.dots_rs; b.ns = nb; b.half = q->dots_half ? 1 : 0;
+    w.nt = nt;
+    w.pinfo = q->bsw_info; w.gmin = q->bsw_gmin; w.ckey = q->bsw_ckey; w.cidx = q->bsw_cidx;
+    // launch_score's coef_s and half mode, tau by tau (the same expressions)
+    const double coefq = coef_query(q, false);
+    const double e_half = q->dots_half ? 4.8828125e-4 + 1.0e-6 : 0.0;
+    SweepCoef sc;
+    for (int j = 0; j < TAU_GROUP; ++j) {
+        const double t = j < nt ? taus[j] : 0.0;
+        const int half_mode = q->dots_half ? (t < 0.05 ? 2 : 1) : 0;
+        const double e_key32 = half_mode == 1 ? 1.5e-6 : 0.0;
+        w.tau[j] = t;
+        w.half[j] = half_mode;
+        if (j < nt) {
+            w.need32 |= half_mode == 1 ? 1 : 0;
+            w.need64 |= half_mode != 1 ? 1 : 0;
+        }
+        sc.tau[j] = t;
+        sc.coef[j] = t * (coefq + 1.0e-14 + e_half) + e_key32 + 4.0 * 2.220446049250313e-16;
+    }
+    constexpr int NSW = 8;
+    const unsigned ny = (unsigned)((nb + NSW - 1) / NSW);
+    const unsigned fg = (unsigned)std::min<int64_t>((rows + 255) / 256, 2048);
+    const dim3 gg((unsigned)((ng + 3) / 4), ny, (unsigned)((nt + 1) / 2)), fgrid(fg, ny);
+    hipLaunchKernelGGL(sweep_pair_info_kernel, dim3(1), dim3(GQ * TAU_GROUP), 0, st, (const QInfo*)q->info, q->bsw_info, nb, nt);
+    hipLaunchKernelGGL((score_gmin_sweep_kernel<NSW, 2>), gg, dim3(256), 0, st, w, G, ng);
+    hipLaunchKernelGGL(pick_thr_sweep_kernel, dim3(1, (unsigned)nt, (unsigned)nb), dim3(1024), 0, st, (const double*)q->bsw_gmin, ng, q->Ms, q->bsw_info);
+    if (nt <= 2) hipLaunchKernelGGL((score_filter_sweep_kernel<NSW, 2>), fgrid, dim3(256), 0, st, w, G);
+    else if (nt <= 4) hipLaunchKernelGGL((score_filter_sweep_kernel<NSW, 4>), fgrid, dim3(256), 0, st, w, G);
+    else hipLaunchKernelGGL((score_filter_sweep_kernel<NSW, 8>), fgrid, dim3(256), 0, st, w, G);
+    FinishArgs f = make_finish(q);
+    f.M = q->Ms; f.hits = nullptr; f.fuse = 1; f.hout = q->bsw_out_dev; f.seq = q->seq; f.auto_reset = 0;
+    f.info = q->bsw_info; f.ck = q->bsw_ckey; f.ci = q->bsw_cidx;
+    hipLaunchKernelGGL(score_finish_sweep_kernel, dim3(1, (unsigned)nt, (unsigned)nb), dim3(1024), score_lds<double>(), st, f, sc);
+    AS_HIP(hipGetLastError());
+    q->bsw_ok = 1;
+    return AS_OK;
+}
+
 // The scan of the int8 two-digit image (as_scan.hip, scan_dma_kernel<..., I8>; the image: as_k2bf.hip, quant_i8_kernel) reads half
 // the bytes of the fp32 items.  The query is quantised the same way -- q ~ s_q (128 q1 + q2) / 16256 -- on the host (D elements),
 // its digits laid out in the lanes' register order: for the 16-byte chunk ci of an image row (slab ci / 8; chunks 0-3 of a slab
@@ -3078,9 +3375,7 @@ static as_status wait_published_at(as_query* q, const HostOut* h) {
 }
 static as_status wait_published(as_query* q, int slot = 0) { return wait_published_at(q, q->hout + slot); }
 
-static as_status collect(as_query* q, int64_t* out_idx, double* out_score, int64_t* out_len, double* out_lambda_q,
-                         int slot = 0) {
-    const HostOut* h = q->hout + slot;
+static as_status collect_out(const HostOut* h, int64_t* out_idx, double* out_score, int64_t* out_len, double* out_lambda_q) {
     if (out_lambda_q) *out_lambda_q = h->lambda_q;
     if (h->status == AS_EZEROLAMBDA) {
         if (out_len) *out_len = 0;
@@ -3094,6 +3389,10 @@ static as_status collect(as_query* q, int64_t* out_idx, double* out_score, int64
     }
     if (out_len) *out_len = len;
     return AS_OK;
+}
+static as_status collect(as_query* q, int64_t* out_idx, double* out_score, int64_t* out_len, double* out_lambda_q,
+                         int slot = 0) {
+    return collect_out(q->hout + slot, out_idx, out_score, out_len, out_lambda_q);
 }
 
 }  // namespace as
@@ -3327,6 +3626,11 @@ void as_query_free(as_query* q) {
     if (q->x1_own) hipFree(q->x1_own);
     if (q->swout) hipHostFree(q->swout);
     if (q->sw_gmin) hipFree(q->sw_gmin);
+    if (q->bsw_out) hipHostFree(q->bsw_out);
+    if (q->bsw_info) hipFree(q->bsw_info);
+    if (q->bsw_gmin) hipFree(q->bsw_gmin);
+    if (q->bsw_ckey) hipFree(q->bsw_ckey);
+    if (q->bsw_cidx) hipFree(q->bsw_cidx);
     if (q->xknn) hipFree(q->xknn);
     hipFree(q->rsel);
     if (q->own_records) {
@@ -4382,7 +4686,8 @@ as_status search_sweep(as_query* q, const double* query, int64_t d, const double
 // The pass in two halves, so that two workspaces can alternate: every kernel of a pass is queued by _launch (nothing
 // waits), _collect waits for its slots and reads them.  While one workspace's selection and finish kernels run, the
 // other's scan -- on its own stream -- already streams the items.
-as_status search_batch_launch(as_query* q, const double* queries, int nb, int64_t d, double tau) {
+// everything of a batched pass in front of its scorer tail: staging, scan, k-NN step and lambda_q
+static as_status batch_pass_head(as_query* q, const double* queries, int nb, int64_t d) {
     q->exact = 0;
     q->robust = 0;
     q->nb = nb;
@@ -4390,6 +4695,11 @@ as_status search_batch_launch(as_query* q, const double* queries, int nb, int64_
     AS_TRY(query_begin(q, queries, -1, d, 0, q->sp->n, q->gr->gp.eps, -1));
     if (q->gr->lambda_mode != AS_LAMBDA_FEATURE) AS_TRY(run_knn(q, q->gr->gp.eps, -1, 1, nullptr, nullptr, nullptr, nullptr, nullptr));
     q->seq += 1;
+    return AS_OK;
+}
+
+as_status search_batch_launch(as_query* q, const double* queries, int nb, int64_t d, double tau) {
+    AS_TRY(batch_pass_head(q, queries, nb, d));
     return run_score(q, tau, 1);
 }
 
@@ -4397,7 +4707,9 @@ as_status search_batch_launch(as_query* q, const double* queries, int nb, int64_
 // queries (scan_gemm_dual_kernel, on a's stream; b's stream joins it through events), the selection and finish kernels of the
 // two passes run side by side.  Where the pair cannot share (no int8 image for these queries, rows wider than 768 columns) each
 // workspace scans for itself as before.
-as_status search_batch_launch_pair(as_query* a, as_query* b, const double* qa, int nba, const double* qb, int nbb, int64_t d, double tau) {
+// tail(q): the scorer tail of workspace q's pass (run_score, or run_score_sweep for a tau sweep)
+template <typename Tail>
+static as_status batch_launch_pair(as_query* a, as_query* b, const double* qa, int nba, const double* qb, int nbb, int64_t d, Tail tail) {
     as_query* m[2] = {a, b};
     const double* qs[2] = {qa, qb};
     const int nbs[2] = {nba, nbb};
@@ -4433,9 +4745,13 @@ as_status search_batch_launch_pair(as_query* a, as_query* b, const double* qa, i
         as_query* q = m[s];
         if (q->gr->lambda_mode != AS_LAMBDA_FEATURE) AS_TRY(run_knn(q, q->gr->gp.eps, -1, 1, nullptr, nullptr, nullptr, nullptr, nullptr));
         q->seq += 1;
-        AS_TRY(run_score(q, tau, 1));
+        AS_TRY(tail(q));
     }
     return AS_OK;
+}
+
+as_status search_batch_launch_pair(as_query* a, as_query* b, const double* qa, int nba, const double* qb, int nbb, int64_t d, double tau) {
+    return batch_launch_pair(a, b, qa, nba, qb, nbb, d, [tau](as_query* q) { return run_score(q, tau, 1); });
 }
 
 as_status search_batch_collect(as_query* q, int nb, double tau, int64_t topk, int64_t* out_idx, double* out_score, int64_t* out_len,
@@ -4478,6 +4794,72 @@ as_status search_batch_collect(as_query* q, int nb, double tau, int64_t topk, in
         const as_status s = collect(q, out_idx + b * topk, out_score + b * topk, out_len + b, out_lambda_q ? out_lambda_q + b : nullptr, b);
         out_status[b] = (int32_t)s;
     }
+    return AS_OK;
+}
+
+// ------------------------------------------------------------------ batched tau sweep (as_search_batch_taus)
+// search_batch_launch / _launch_pair / _collect for nt <= TAU_GROUP distinct taus in [0, 1]: the same staging, scan (a pair of
+// workspaces shares one where search_batch's would), k-NN step and lambda_q, then run_score_sweep's tail for every (slot, tau)
+// pair.  Pair (b, j) gets exactly the candidate set and exact evaluation search_batch(..., taus[j]) gives slot b.
+as_status search_batch_sweep_launch(as_query* q, const double* queries, int nb, int64_t d, const double* taus, int nt) {
+    AS_TRY(batch_pass_head(q, queries, nb, d));
+    return run_score_sweep(q, taus, nt);
+}
+
+as_status search_batch_sweep_launch_pair(as_query* a, as_query* b, const double* qa, int nba, const double* qb, int nbb, int64_t d,
+                                         const double* taus, int nt) {
+    return batch_launch_pair(a, b, qa, nba, qb, nbb, d, [taus, nt](as_query* q) { return run_score_sweep(q, taus, nt); });
+}
+
+int query_sweep_ran(const as_query* q) { return q && q->bsw_ok ? 1 : 0; }
+
+static as_status wait_sweep(as_query* q, int nb, int nt) {
+    if (!q->bsw_ok) return AS_OK;
+    for (int b = 0; b < nb; ++b)
+        for (int j = 0; j < nt; ++j) AS_TRY(wait_published_at(q, q->bsw_out + b * TAU_GROUP + j));
+    return AS_OK;
+}
+
+// search_batch_collect for a sweep pass: a crowded neighbourhood takes the threshold repair and re-scores every tau, a pass
+// beyond its int8 pricing runs once more for every tau.  Pair (b, j): out_idx / out_score + (b * nt + j) * topk,
+// out_len / out_status [b * nt + j]; status -1: the pair is left to the single search (its own overflow, k-NN or score check,
+// or a workspace run_score_sweep could not take).
+as_status search_batch_sweep_collect(as_query* q, int nb, const double* taus, int nt, int64_t topk, int64_t* out_idx, double* out_score,
+                                     int64_t* out_len, double* out_lambda_q, int32_t* out_status) {
+    AS_TRY(wait_sweep(q, nb, nt));
+    bool crowded = false;
+    if (q->bsw_ok)
+        for (int b = 0; b < nb; ++b) crowded = crowded || (q->bsw_out[b * TAU_GROUP].overflow & 1);   // (the slot's k-NN flag: every pair has it)
+    if (crowded && !q->dots_half) {
+        AS_TRY(knn_repair(q, q->gr->gp.eps, -1));
+        AS_TRY(run_knn(q, q->gr->gp.eps, -1, 1, nullptr, nullptr, nullptr, nullptr, nullptr, 1));
+        q->seq += 1;
+        AS_TRY(run_score_sweep(q, taus, nt));
+        AS_TRY(wait_sweep(q, nb, nt));
+    }
+    const bool held = q->i8_scan && q->cap > 1 ? batch_coef_holds(q) : true;
+    bool priced = held || !q->x8_verify;
+    if (!priced && !q->x8_nan && q->batch_assume == 1) {
+        q->batch_assume = 2;
+        const as_status s2 = query_begin(q, q->hq, -1, q->sp->d, 0, q->sp->n, q->gr->gp.eps, -1);
+        q->batch_assume = 1;
+        AS_TRY(s2);
+        if (q->gr->lambda_mode != AS_LAMBDA_FEATURE) AS_TRY(run_knn(q, q->gr->gp.eps, -1, 1, nullptr, nullptr, nullptr, nullptr, nullptr));
+        q->seq += 1;
+        AS_TRY(run_score_sweep(q, taus, nt));
+        AS_TRY(wait_sweep(q, nb, nt));
+        priced = !(q->i8_scan && q->cap > 1) || batch_coef_holds(q) || !q->x8_verify;
+    }
+    for (int b = 0; b < nb; ++b)
+        for (int j = 0; j < nt; ++j) {
+            const int64_t p = (int64_t)b * nt + j;
+            const HostOut* h = q->bsw_out ? q->bsw_out + b * TAU_GROUP + j : nullptr;
+            if (!q->bsw_ok || h->overflow || h->knn_inexact || h->score_inexact || !priced) {
+                out_status[p] = -1;
+                continue;
+            }
+            out_status[p] = (int32_t)collect_out(h, out_idx + p * topk, out_score + p * topk, out_len + p, out_lambda_q ? out_lambda_q + b : nullptr);
+        }
     return AS_OK;
 }
 
