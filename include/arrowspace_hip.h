@@ -454,6 +454,35 @@ as_status as_search_batch_taus(const as_space* sp, const as_graph* gr, const dou
  * served, [3] pairs they left to the single search */
 as_status as_batch_sweep_counters(const as_space* sp, int64_t* out, int32_t n);
 
+/* ---- Extension: filtered search.  A subset restricts which items a search may return; it does not change the index: lambda_q is
+ * the query's lambda against the whole index, the items' lambdas are their own -- the values as_search uses.
+ * as_subset_create: m item ids in HOST memory, any order, duplicates allowed (m = 0: the empty set); they are sorted and made
+ * unique once, on the host, and kept in device memory together with every buffer a search over them needs (scores, the
+ * selection's histograms, the pinned result): nothing is allocated per query.  An id outside [0, nitems) -> AS_EINVAL.  The
+ * handle belongs to the space it was made for (any other space -> AS_EINVAL) and must be freed before it. */
+typedef struct as_subset as_subset;
+as_status as_subset_create(const as_space* sp, const int64_t* ids_host, int64_t m, as_subset** out);
+int64_t as_subset_size(const as_subset* sub);                 /* distinct ids; 0 for NULL */
+as_status as_subset_ids(const as_subset* sub, int64_t* out);  /* sorted, unique: as_subset_size entries */
+void as_subset_free(as_subset* sub);                          /* NULL: no-op */
+/* The first min(topk, |S|) items of the subset by (S11 score descending, index ascending): with every item in S, what as_search
+ * returns.  Cost: ONE ORDINARY as_search per call (lambda_q comes from it, hits discarded: the same escalation, the same
+ * AS_EZEROLAMBDA -- whatever S is, the empty set included -- and the same out_lambda_q), then a gather of the subset's rows
+ * (fp64 items where the space keeps them, else fp32 widened; fp64 dot, the exact score of as_search) and an exact selection on
+ * the device.  Wrong d -> AS_EINVAL ("query length ... must match nfeatures ..."), non-finite tau -> AS_EINVAL, a shard of a
+ * row-sharded index -> AS_EUNSUPPORTED.  Calls on one handle are serialised; different handles and as_search run beside it. */
+as_status as_search_subset(const as_space* sp, const as_graph* gr, const double* query, int64_t d, double tau, const as_subset* sub,
+                           int64_t* out_idx, double* out_score, int64_t* out_len, double* out_lambda_q);
+/* out_scores[i] = the S11 score of item ids_host[i] (the caller's order, duplicates kept): the same kernel without the selection,
+ * the same checks and the same one as_search per call.  Its device buffers live in the space and grow on demand; calls on one
+ * space are serialised. */
+as_status as_score_items(const as_space* sp, const as_graph* gr, const double* query, int64_t d, double tau, const int64_t* ids_host,
+                         int64_t m, double* out_scores, double* out_lambda_q);
+/* measurement: HIP events around the score kernel of as_search_subset on this handle (off by default), and the device
+ * microseconds of the last timed call */
+void as_subset_set_timing(as_subset* sub, int32_t enabled);
+double as_subset_kernel_us(const as_subset* sub);
+
 /* ---- index persistence (extension; the reference exposes none): one flat file
  * holding the items, lambdas and graph arrays.  Loading re-ingests the items and uploads the
  * rest; no k-NN work is redone.  opts->device selects the GPU, metric/kernel come from the file. */

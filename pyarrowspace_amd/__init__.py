@@ -17,7 +17,7 @@ import numpy as np
 from . import _lib
 from ._lib import GraphParams, Opts
 
-__all__ = ["ArrowSpaceBuilder", "ArrowSpace", "GraphLaplacian", "set_debug", "PanicException"]
+__all__ = ["ArrowSpaceBuilder", "ArrowSpace", "GraphLaplacian", "ItemSubset", "set_debug", "PanicException"]
 __version__ = "0.1.0"
 
 _L = _lib.load()
@@ -183,6 +183,72 @@ class GraphLaplacian:
         return dict(zip(keys, out.tolist()))
 
 
+def _item_ids(ids_or_mask, nitems: int, what: str = "ids") -> np.ndarray:
+    """Item ids as a contiguous int64 array: an integer array or sequence as it is (any order, duplicates kept), a boolean
+    mask of length nitems through np.flatnonzero."""
+    a = np.asarray(ids_or_mask)
+    if a.dtype == np.bool_:
+        if a.ndim != 1 or a.shape[0] != nitems:
+            raise ValueError(f"argument '{what}': a boolean mask must have length nitems ({nitems}), got shape {a.shape}")
+        return np.flatnonzero(a).astype(np.int64)
+    if a.size == 0 and a.ndim == 1:
+        return np.empty(0, dtype=np.int64)   # (numpy types an empty list float64: an empty selection has no ids to mistype)
+    if a.dtype.kind not in "iu":
+        raise TypeError(f"argument '{what}': expected integer item ids or a boolean mask, got dtype {a.dtype}")
+    if a.ndim != 1:
+        raise TypeError(f"argument '{what}': expected a 1-D sequence of item ids")
+    if a.dtype == np.uint64 and a.size and int(a.max()) > np.iinfo(np.int64).max:
+        raise ValueError(f"argument '{what}': id {int(a.max())} is outside [0, {nitems})")
+    return np.ascontiguousarray(a, dtype=np.int64)
+
+
+class ItemSubset:
+    """Extension: a set of items of one ArrowSpace (`ArrowSpace.subset`), resident on the device with every buffer a
+    `search_subset` over it needs.  Holds a reference to its ArrowSpace."""
+
+    def __new__(cls, *a, **k):
+        raise ValueError("ItemSubset cannot be constructed directly; use ArrowSpace.subset")
+
+    @classmethod
+    def _wrap(cls, handle, space):
+        self = object.__new__(cls)
+        self._h = handle
+        self._space = space
+        return self
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and _L is not None:
+            _L.as_subset_free(h)
+            self._h = None
+        self._space = None
+
+    @property
+    def size(self) -> int:
+        """Extension: the number of distinct items in the subset."""
+        return int(_L.as_subset_size(self._h))
+
+    def __len__(self) -> int:
+        return self.size
+
+    def ids(self) -> np.ndarray:
+        """Extension: the subset's item ids, sorted and unique (int64)."""
+        out = np.empty(self.size, dtype=np.int64)
+        st = _L.as_subset_ids(self._h, out.ctypes.data_as(C.c_void_p))
+        if st:
+            _raise(st)
+        return out
+
+    def set_timing(self, enabled: bool) -> None:
+        """Measurement only (tools/subset_bench.py): record HIP events around the score kernel of `search_subset` calls on this subset (off by default)."""
+        _L.as_subset_set_timing(self._h, 1 if enabled else 0)
+
+    @property
+    def kernel_us(self) -> float:
+        """Measurement only: device microseconds of the score kernel in the last timed `search_subset` call on this subset."""
+        return float(_L.as_subset_kernel_us(self._h))
+
+
 class ArrowSpace:
     """Items + per-item lambdas resident in HBM (src/lib.rs:64-263)."""
 
@@ -312,6 +378,54 @@ class ArrowSpace:
             _raise(st)
         idx, sc = idx[:, :topk], sc[:, :topk]
         return [list(zip(ii[:l], ss[:l])) for ii, ss, l in zip(idx[:nt].tolist(), sc[:nt].tolist(), ln[:nt].tolist())]
+
+    def subset(self, ids_or_mask) -> ItemSubset:
+        """Extension: an `ItemSubset` of this space from integer item ids (array or sequence, any order, duplicates allowed)
+        or a boolean mask of length nitems.  Ids are sorted and made unique once; an id outside [0, nitems) raises
+        ValueError, floating-point ids TypeError."""
+        ids = _item_ids(ids_or_mask, self.nitems, "ids_or_mask")
+        h = C.c_void_p()
+        st = _L.as_subset_create(self._h, ids.ctypes.data_as(C.c_void_p), ids.shape[0], C.byref(h))
+        if st:
+            _raise(st)
+        return ItemSubset._wrap(h, self)
+
+    def search_subset(self, item, gl: GraphLaplacian, tau: float, subset):
+        """Extension: filtered search -> list[(index, score)]: the first min(topk, |subset|) items OF THE SUBSET by (score
+        descending, index ascending).  The filter restricts what may be returned, not the index: lambda_q and the items'
+        lambdas are the ones `search` uses, and with every item in the subset the result is `search`'s.  `subset`: an
+        `ItemSubset` of this space (prepared once, reused over queries) or anything `subset()` accepts (a temporary one is
+        made).  Costs one ordinary `search` (lambda_q comes from it; a query whose lambda_q is 0 panics as there, whatever
+        the subset) plus a gather of the subset's rows and an exact selection on the device."""
+        if not isinstance(gl, GraphLaplacian):
+            raise TypeError("argument 'gl': expected GraphLaplacian")
+        q = self._query(item)
+        sub = subset if isinstance(subset, ItemSubset) else self.subset(subset)
+        n = max(min(int(gl.graph_params["topk"]), sub.size), 1)
+        idx = np.empty(n, dtype=np.int64)
+        sc = np.empty(n, dtype=np.float64)
+        ln, lq = C.c_int64(0), C.c_double(0.0)
+        st = _L.as_search_subset(self._h, gl._h, q.ctypes.data, q.shape[0], float(tau), sub._h, idx.ctypes.data, sc.ctypes.data,
+                                 C.byref(ln), C.byref(lq))
+        if st:
+            _raise(st)
+        return list(zip(idx[:ln.value].tolist(), sc[:ln.value].tolist()))
+
+    def score_items(self, item, gl: GraphLaplacian, tau: float, ids) -> np.ndarray:
+        """Extension: re-ranking -> ndarray[float64]: entry i is the score `search` would give item ids[i] (the caller's
+        order, duplicates kept; integer ids or a boolean mask as for `subset`).  Costs one ordinary `search` (lambda_q) plus
+        a gather of the listed rows."""
+        if not isinstance(gl, GraphLaplacian):
+            raise TypeError("argument 'gl': expected GraphLaplacian")
+        q = self._query(item)
+        ids = _item_ids(ids, self.nitems, "ids")
+        out = np.empty(ids.shape[0], dtype=np.float64)
+        lq = C.c_double(0.0)
+        st = _L.as_score_items(self._h, gl._h, q.ctypes.data, q.shape[0], float(tau), ids.ctypes.data_as(C.c_void_p), ids.shape[0],
+                               out.ctypes.data_as(C.c_void_p), C.byref(lq))
+        if st:
+            _raise(st)
+        return out
 
     def sweep_counters(self) -> dict:
         """Extension: `search_taus` calls on this space, the shared passes that served them, and the taus those passes left

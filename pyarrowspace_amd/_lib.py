@@ -51,6 +51,7 @@ SYMBOLS = [
     "as_graph_degrees", "as_graph_tau0", "as_lambdas_dev", "as_build_stats", "as_query_stats", "as_last_search_stats", "as_search_counters", "as_search_taus", "as_sweep_counters", "as_search_batch_taus", "as_batch_sweep_counters", "as_enable_search_stats", "as_set_tuning", "as_index_save", "as_index_load", "as_free_space",
     "as_free_graph", "as_set_debug", "as_last_error", "as_device_count", "as_version",
     "as_comm_available", "as_comm_unique_id", "as_comm_create", "as_comm_free", "as_query_set_comm", "as_query_search_staged", "as_query_x1_bytes", "as_query_x1_usable", "as_query_x1_enabled", "as_query_set_x1", "as_query_x1_begin", "as_query_x1_finish", "as_query_x1_redo", "as_query_set_coarse", "as_query_x1_passes", "as_edges_bucket", "as_ring_i8_stats", "as_ring_i8_set", "as_ring_i8",
+    "as_subset_create", "as_subset_size", "as_subset_ids", "as_subset_free", "as_search_subset", "as_score_items", "as_subset_set_timing", "as_subset_kernel_us",
 ]
 
 _lib = None
@@ -198,6 +199,14 @@ def load():
         "as_sweep_counters": (i32, [vp, vp, i32]),
         "as_search_batch_taus": (i32, [vp, vp, vp, i64, i64, vp, i64, vp, vp, vp, vp, vp]),
         "as_batch_sweep_counters": (i32, [vp, vp, i32]),
+        "as_subset_create": (i32, [vp, vp, i64, pvp]),
+        "as_subset_size": (i64, [vp]),
+        "as_subset_ids": (i32, [vp, vp]),
+        "as_subset_free": (None, [vp]),
+        "as_search_subset": (i32, [vp, vp, vp, i64, f64, vp, vp, vp, C.POINTER(i64), C.POINTER(f64)]),
+        "as_score_items": (i32, [vp, vp, vp, i64, f64, vp, i64, vp, C.POINTER(f64)]),
+        "as_subset_set_timing": (None, [vp, i32]),
+        "as_subset_kernel_us": (f64, [vp]),
         "as_gang_counters": (i32, [vp, vp, i32]),
         "as_enable_search_stats": (None, [i32]),
         "as_set_tuning": (i32, [C.c_char_p, i32]),

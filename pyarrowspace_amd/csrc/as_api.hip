@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <new>
 #include <vector>
 
@@ -108,6 +109,7 @@ void as_free_space(as_space* sp) {
     if (sp->qcache_b2) as_query_free(sp->qcache_b2);
     if (sp->qcache_b3) as_query_free(sp->qcache_b3);
     if (sp->qcache_b4) as_query_free(sp->qcache_b4);
+    subset_work_free(sp->score_ws);
     if (sp->stream) hipStreamSynchronize(sp->stream);
     hipFree(sp->x32); hipFree(sp->xs); hipFree(sp->x8); hipFree(sp->x8h); hipFree(sp->fa8); hipFree(sp->x64); hipFree(sp->n64); hipFree(sp->n32); hipFree(sp->inorm32);
     hipFree(sp->lam64); hipFree(sp->lam32);
@@ -891,6 +893,158 @@ as_status as_sweep_counters(const as_space* sp, int64_t* out, int32_t n) {
     }
     for (int i = 0; i < n && i < 3; ++i) out[i] = sp->sweep_count[i].load(std::memory_order_relaxed);
     return AS_OK;
+}
+
+// ---------------------------------------------------------------- filtered search (extension; kernels: as_subset.hip)
+// what as_search_subset and as_score_items check alike, then lambda_q by the single search on a workspace of the pool, hits
+// discarded: its escalation, its AS_EZEROLAMBDA, its out_lambda_q
+static as_status subset_lambda(const char* who, const as_space* sp, const as_graph* gr, const double* query, int64_t d, double tau, double* lq) {
+    if (d != sp->d) {
+        set_err("query length %lld must match nfeatures %lld", (long long)d, (long long)sp->d);
+        return AS_EINVAL;
+    }
+    if (!std::isfinite(tau)) {
+        set_err("%s: tau must be finite", who);
+        return AS_EINVAL;
+    }
+    AS_TRY(graph_matches(sp, gr, who));
+    if (sp->row_offset != 0 || gr->ncols) {
+        set_err("%s: a shard of a row-sharded index is not supported", who);
+        return AS_EUNSUPPORTED;
+    }
+    int64_t hidx[SUBSET_TOPK], hlen = 0;
+    double hsc[SUBSET_TOPK];
+    return search_pooled(sp, gr, query, d, tau, hidx, hsc, &hlen, lq);
+}
+
+as_status as_subset_create(const as_space* sp, const int64_t* ids_host, int64_t m, as_subset** out) {
+    if (!sp || !out || m < 0 || (m > 0 && !ids_host)) {
+        set_err("as_subset_create: null argument");
+        return AS_EINVAL;
+    }
+    *out = nullptr;
+    for (int64_t i = 0; i < m; ++i)
+        if (ids_host[i] < 0 || ids_host[i] >= sp->n) {
+            set_err("as_subset_create: id %lld is outside [0, %lld)", (long long)ids_host[i], (long long)sp->n);
+            return AS_EINVAL;
+        }
+    std::vector<int32_t> ids;   // (item ids fit 32 bits: space_new refuses n >= 2^31)
+    as_subset* sub = nullptr;
+    try {
+        ids.assign(ids_host, ids_host + m);
+        std::sort(ids.begin(), ids.end());
+        ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+        sub = new as_subset();
+        sub->ids = new int64_t[ids.size() + 1];
+    } catch (const std::bad_alloc&) {
+        delete sub;
+        set_err("as_subset_create: out of host memory for %lld ids", (long long)m);
+        return AS_ENOMEM;
+    }
+    sub->sp = sp;
+    sub->m = (int64_t)ids.size();
+    for (int64_t i = 0; i < sub->m; ++i) sub->ids[i] = ids[i];
+    as_status s = hipSetDevice(sp->device) == hipSuccess ? AS_OK : AS_EHIP;
+    if (s != AS_OK) set_err("as_subset_create: hipSetDevice failed");
+    if (s == AS_OK) s = subset_work_create(sp, sub->m, &sub->w);
+    if (s == AS_OK) s = subset_set_ids(sub->w, ids.data(), sub->m);
+    if (s != AS_OK) {
+        as_subset_free(sub);
+        return s;
+    }
+    *out = sub;
+    return AS_OK;
+}
+
+int64_t as_subset_size(const as_subset* sub) { return sub ? sub->m : 0; }
+
+as_status as_subset_ids(const as_subset* sub, int64_t* out) {
+    if (!sub || (sub->m > 0 && !out)) {
+        set_err("as_subset_ids: null argument");
+        return AS_EINVAL;
+    }
+    for (int64_t i = 0; i < sub->m; ++i) out[i] = sub->ids[i];
+    return AS_OK;
+}
+
+void as_subset_free(as_subset* sub) {
+    if (!sub) return;
+    subset_work_free(sub->w);
+    delete[] sub->ids;
+    delete sub;
+}
+
+void as_subset_set_timing(as_subset* sub, int32_t enabled) {
+    if (!sub || !sub->w) return;
+    std::lock_guard<std::mutex> lk(sub->mu);
+    sub->w->timing = enabled ? 1 : 0;
+}
+double as_subset_kernel_us(const as_subset* sub) {
+    if (!sub || !sub->w) return 0.0;
+    std::lock_guard<std::mutex> lk(sub->mu);
+    return sub->w->kernel_us;
+}
+
+as_status as_search_subset(const as_space* sp, const as_graph* gr, const double* query, int64_t d, double tau, const as_subset* sub,
+                           int64_t* out_idx, double* out_score, int64_t* out_len, double* out_lambda_q) {
+    if (!sp || !gr || !query || !sub || !out_len || (sub->m > 0 && (!out_idx || !out_score))) {
+        set_err("as_search_subset: null argument");
+        return AS_EINVAL;
+    }
+    *out_len = 0;
+    if (sub->sp != sp) {
+        set_err("as_search_subset: the subset was made for another space");
+        return AS_EINVAL;
+    }
+    double lq = 0.0;
+    const as_status s = subset_lambda("as_search_subset", sp, gr, query, d, tau, &lq);
+    if (out_lambda_q) *out_lambda_q = lq;
+    if (s != AS_OK) return s;
+    if (sub->m == 0) return AS_OK;
+    const int64_t topk = std::min<int64_t>(gr->gp.topk, sp->n);
+    std::lock_guard<std::mutex> lk(sub->mu);
+    AS_TRY(subset_score(sp, sub->w, sub->m, query, tau, lq));
+    return subset_select(sub->w, sub->m, std::min<int64_t>(topk, sub->m), out_idx, out_score, out_len);
+}
+
+as_status as_score_items(const as_space* sp, const as_graph* gr, const double* query, int64_t d, double tau, const int64_t* ids_host,
+                         int64_t m, double* out_scores, double* out_lambda_q) {
+    if (!sp || !gr || !query || m < 0 || (m > 0 && (!ids_host || !out_scores))) {
+        set_err("as_score_items: null argument");
+        return AS_EINVAL;
+    }
+    for (int64_t i = 0; i < m; ++i)
+        if (ids_host[i] < 0 || ids_host[i] >= sp->n) {
+            set_err("as_score_items: id %lld is outside [0, %lld)", (long long)ids_host[i], (long long)sp->n);
+            return AS_EINVAL;
+        }
+    double lq = 0.0;
+    const as_status s = subset_lambda("as_score_items", sp, gr, query, d, tau, &lq);
+    if (out_lambda_q) *out_lambda_q = lq;
+    if (s != AS_OK) return s;
+    if (m == 0) return AS_OK;
+    if (m >= (int64_t)1 << 31) {
+        set_err("as_score_items: %lld ids exceed the supported maximum of 2^31 - 1 per call", (long long)m);
+        return AS_EUNSUPPORTED;
+    }
+    std::vector<int32_t> ids;   // (item ids fit 32 bits: space_new refuses n >= 2^31)
+    try {
+        ids.assign(ids_host, ids_host + m);
+    } catch (const std::bad_alloc&) {
+        set_err("as_score_items: out of host memory for %lld ids", (long long)m);
+        return AS_ENOMEM;
+    }
+    std::lock_guard<std::mutex> lk(sp->smu);
+    if (!sp->score_ws || sp->score_ws->cap < m) {   // grown on demand, never per query otherwise
+        subset_work_free(sp->score_ws);
+        sp->score_ws = nullptr;
+        int64_t cap = 1024;
+        while (cap < m) cap *= 2;
+        AS_TRY(subset_work_create(sp, cap, &sp->score_ws));
+    }
+    AS_TRY(subset_set_ids(sp->score_ws, ids.data(), m));
+    AS_TRY(subset_score(sp, sp->score_ws, m, query, tau, lq));
+    return subset_scores_out(sp->score_ws, m, out_scores);
 }
 
 // the batched workspaces for b > 1 queries (under sp->bmu); *unit = the passes launched together (2: a pair sharing one scan)

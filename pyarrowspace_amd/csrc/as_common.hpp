@@ -46,6 +46,8 @@ void dbg(const char* fmt, ...);
 
 }  // namespace as
 
+namespace as { struct SubsetWork; }
+
 // ---------------------------------------------------------------- handles
 // HBM layout: x32 is the scan/MFMA operand, [np][dp] fp32,
 // zero padded so that every tile load is a full 16-byte vector inside the allocation.
@@ -134,6 +136,9 @@ struct as_space {
     // as_batch_sweep_counters: [0] as_search_batch_taus calls, [1] batched passes whose scorer tail served a tau sweep, [2] (query,
     // tau) pairs such a pass served, [3] pairs it left to the single search
     mutable std::atomic<int64_t> bsweep_count[4] = {};
+    // as_score_items: the score kernel's buffers (as_subset.hip), made on first use and grown on demand; calls are serialised (smu)
+    mutable struct as::SubsetWork* score_ws = nullptr;
+    mutable std::mutex smu;
     mutable int64_t unproven_searches = 0;   // searches returned although their a-posteriori check failed on the strongest path
     mutable double kstats[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // accumulated by as_knn_rows
 };
@@ -175,6 +180,15 @@ struct as_graph {
 inline int64_t graph_items(const as_graph* gr) {   // items the index covers
     return gr->lambda_mode == AS_LAMBDA_FEATURE ? gr->nitems : (gr->ncols ? gr->ncols : gr->n);
 }
+
+// a set of items of one space (as_subset_create): sorted unique ids, on the host and in the work buffers
+struct as_subset {
+    const as_space* sp = nullptr;
+    int64_t m = 0;
+    int64_t* ids = nullptr;      // [m] host copy (as_subset_ids)
+    as::SubsetWork* w = nullptr;
+    mutable std::mutex mu;       // calls on one handle are serialised
+};
 
 // ---------------------------------------------------------------- device helpers
 #if defined(__HIPCC__)
@@ -391,6 +405,12 @@ struct WaveList2 {
     }
 };
 
+// the blend of src/lib.rs:166-173 as SPEC S11 has it, from an exact cosine: ONE definition, so that every path that ranks
+// exact scores (single GPU, staged, one-exchange, filtered) rounds alike
+__device__ __forceinline__ double blend_score(double tau, double c, double lq, double lj) {
+    return tau * c + (1.0 - tau) / (1.0 + fabs(lq - lj));
+}
+
 // SPEC S4 edge weight.  gaussian: exp(-0.5 (d/sigma)^p); rational: 1/(1+(d/sigma)^p)
 __device__ __forceinline__ double edge_weight(double d, double sigma, double p, int kernel) {
     const double t = d / sigma;
@@ -492,6 +512,39 @@ as_status search_batch_sweep_launch_pair(as_query* a, as_query* b, const double*
 as_status search_batch_sweep_collect(as_query* q, int nb, const double* taus, int nt, int64_t topk, int64_t* out_idx, double* out_score,
                                      int64_t* out_len, double* out_lambda_q, int32_t* out_status);
 int query_sweep_ran(const as_query* q);
+// filtered search (as_subset.hip): exact S11 scores of a list of items gathered by id, exact top-k of them.  A SubsetWork holds
+// everything a call needs on the device (ids, scores, the query, the selection's histograms and records) and the pinned result:
+// nothing is allocated per query.  One call at a time per SubsetWork (the owner's mutex).
+constexpr int SUBSET_TOPK = 1024;   // == MAX_TOPK: entries of the final one-block sort
+struct SubsetOut {
+    int64_t len;
+    int64_t idx[SUBSET_TOPK];
+    double score[SUBSET_TOPK];
+};
+struct SubsetSel;
+struct SubsetWork {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    int cus = 256;                 // compute units of that device (the score kernel's grid)
+    int64_t cap = 0, dp = 0;       // ids / scores the buffers hold (< 2^31: positions are 32-bit), padded query length
+    int32_t* ids = nullptr;        // [cap]
+    double* scores = nullptr;      // [cap]
+    double* q64 = nullptr;         // [dp] the query, zero padded
+    double* hq = nullptr;          // pinned staging of the query
+    unsigned int* hist = nullptr;  // selection: one histogram per radix pass, then the counter of selected positions
+    SubsetSel* state = nullptr;    // ... the threshold's digits found so far, per pass
+    int32_t* sel_pos = nullptr;    // ... [SUBSET_TOPK] positions at or above the threshold
+    SubsetOut* out = nullptr;      // pinned, written by the sort kernel
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    int timing = 0;                // record ev around the score kernel
+    double kernel_us = 0.0;        // ... and its duration in the last timed call
+};
+as_status subset_work_create(const as_space* sp, int64_t cap, SubsetWork** out);
+void subset_work_free(SubsetWork* w);
+as_status subset_set_ids(SubsetWork* w, const int32_t* ids_host, int64_t m);
+as_status subset_score(const as_space* sp, SubsetWork* w, int64_t m, const double* query, double tau, double lambda_q);
+as_status subset_select(SubsetWork* w, int64_t m, int64_t k, int64_t* out_idx, double* out_score, int64_t* out_len);
+as_status subset_scores_out(SubsetWork* w, int64_t m, double* out);
 constexpr int QUERY_BATCH = 32;  // == GQ in as_search.hip: query slots of the batched workspace
 constexpr int TAU_GROUP = 8;     // taus one shared pass of a tau sweep serves (search_sweep, as_search_taus)
 

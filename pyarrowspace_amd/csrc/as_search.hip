@@ -63,7 +63,7 @@ __global__ void q_prepare_kernel(const double* __restrict__ qin, int64_t d, int6
     info += blockIdx.z;
     double s = 0.0;
     for (int64_t c = threadIdx.x; c < dp; c += blockDim.x) {
-#pragma clang fp contract(off)   // product and sum rounded separately: host_query_norm reproduces this sum bit for bit
+#pragma clang fp contract(off)   // product and sum rounded separately: host_query_norm (and as_subset.hip, subset_query_norm) reproduce this sum bit for bit
         const double v = c < d ? qin[c] : 0.0;
         q64[c] = v;
         q32[c] = (float)v;
@@ -1705,12 +1705,6 @@ __global__ __launch_bounds__(64) void q_lambda_kernel(const as_knn_rec* __restri
     // (the coarse chain: the scorer's candidate count starts at zero for the selection kernels behind this one -- a 4-byte memset
     // between two kernels is 5 us of an idle GPU)
     if (zero_sc && threadIdx.x == 0) info[blockIdx.x].sc_cnt = 0;
-}
-
-// the blend of src/lib.rs:166-173 as SPEC S11 has it, from an exact cosine: ONE definition, so that every path that ranks
-// exact scores (single GPU, staged, one-exchange) rounds alike
-__device__ __forceinline__ double blend_score(double tau, double c, double lq, double lj) {
-    return tau * c + (1.0 - tau) / (1.0 + fabs(lq - lj));
 }
 
 __device__ __forceinline__ void publish(HostOut* out, int64_t seq) {
