@@ -421,6 +421,7 @@ void as_enable_search_stats(int32_t enabled);
 /* Measurement knob, no reference counterpart: launch parameters the library otherwise picks itself.  "tile_geom" = <blocks per
  * CU><two digits: ring KiB per wave> of the single query's tile scan (e.g. 406, 308, 216; ARROWSPACE_TILE_GEOM at load);
  * "x1_blocks" = blocks of the coarse scan's exact-evaluation kernel (16 .. 256, default 128).
+ * "subset_batch_mib" = MiB of scores one chunk of queries of the batched filtered forms may hold (default 256; <= 0: the default).
  * Returns 0, or 1 for an unknown key.  Results never depend on it. */
 int32_t as_set_tuning(const char* key, int32_t value);
 /* same, for the workspace as_search keeps inside the space (last as_search call) */
@@ -482,6 +483,22 @@ as_status as_score_items(const as_space* sp, const as_graph* gr, const double* q
  * microseconds of the last timed call */
 void as_subset_set_timing(as_subset* sub, int32_t enabled);
 double as_subset_kernel_us(const as_subset* sub);
+/* The batched forms: b queries, row-major [b][d] in HOST memory, against one subset / one id list.  List i (out_idx / out_score +
+ * i * kk, kk = min(topk, nitems, |S|), out_len[i] entries) is what as_search_subset returns for query i; out_scores [b][m] row i is
+ * what as_score_items returns for it.  The summation order differs from the single forms' (an fp64 GEMM on the matrix cores, one
+ * accumulation chain over the columns per score): scores agree to 1e-12 relative, indices except inside such ties; identical
+ * rows still score bit-equal and come back in index order.  lambda_q and out_status[i] (AS_OK or AS_EZEROLAMBDA: that query gets
+ * out_len 0, its row of out_scores is left unwritten) come from ONE as_search_batch call over all b queries, hits discarded.
+ * Checks and messages are the single forms'; b == 0 launches nothing; an empty subset / m == 0 still runs the lambda_q step.
+ * The gathered rows are read once per tile of 64 queries; queries run in chunks whose scores fit a budget (256 MiB;
+ * as_set_tuning("subset_batch_mib")), one stream wait per chunk.  The batched buffers are made on the first batched call on a
+ * handle (as_score_items_batch: in the space) and grow on demand.  out_lambda_q and out_status may be NULL.  With timing enabled
+ * as_subset_kernel_us reports the batched score kernel summed over the chunks of the last call. */
+as_status as_search_subset_batch(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau,
+                                 const as_subset* sub, int64_t* out_idx, double* out_score, int64_t* out_len, double* out_lambda_q,
+                                 int32_t* out_status);
+as_status as_score_items_batch(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau,
+                               const int64_t* ids_host, int64_t m, double* out_scores, double* out_lambda_q, int32_t* out_status);
 
 /* ---- index persistence (extension; the reference exposes none): one flat file
  * holding the items, lambdas and graph arrays.  Loading re-ingests the items and uploads the

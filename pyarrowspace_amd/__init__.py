@@ -240,12 +240,12 @@ class ItemSubset:
         return out
 
     def set_timing(self, enabled: bool) -> None:
-        """Measurement only (tools/subset_bench.py): record HIP events around the score kernel of `search_subset` calls on this subset (off by default)."""
+        """Measurement only (tools/subset_bench.py, tools/subset_batch_bench.py): record HIP events around the score kernel of `search_subset` / `search_batch_subset` calls on this subset (off by default)."""
         _L.as_subset_set_timing(self._h, 1 if enabled else 0)
 
     @property
     def kernel_us(self) -> float:
-        """Measurement only: device microseconds of the score kernel in the last timed `search_subset` call on this subset."""
+        """Measurement only: device microseconds of the score kernel in the last timed `search_subset` call on this subset (`search_batch_subset`: summed over the call's chunks)."""
         return float(_L.as_subset_kernel_us(self._h))
 
 
@@ -425,6 +425,61 @@ class ArrowSpace:
                                out.ctypes.data_as(C.c_void_p), C.byref(lq))
         if st:
             _raise(st)
+        return out
+
+    def search_batch_subset(self, items, gl: GraphLaplacian, tau: float, subset):
+        """Extension: batched filtered search, B queries [B, D] against one subset -> list of B hit lists; list i is what
+        `search_subset(items[i], gl, tau, subset)` returns (scores within 1e-12 relative: the batched kernel sums in another
+        order; indices equal except inside such ties).  `subset`: an `ItemSubset` of this space or anything `subset()` accepts.
+        Costs one `search_batch` over the B queries (lambda_q comes from it; any query whose lambda_q is 0 panics as there,
+        whatever the subset), then the subset's rows are gathered once per 64 queries for an fp64 matrix product on the
+        device and every query's list is selected there."""
+        if not isinstance(gl, GraphLaplacian):
+            raise TypeError("argument 'gl': expected GraphLaplacian")
+        Q = np.ascontiguousarray(items, dtype=np.float64)
+        if Q.ndim != 2:
+            raise TypeError("items must be a 2-D float64 array")
+        sub = subset if isinstance(subset, ItemSubset) else self.subset(subset)
+        b = Q.shape[0]
+        kk = max(min(int(gl.graph_params["topk"]), self.nitems, sub.size), 0)
+        idx = np.empty((max(b, 1), max(kk, 1)), dtype=np.int64)
+        sc = np.empty((max(b, 1), max(kk, 1)), dtype=np.float64)
+        ln = np.zeros(max(b, 1), dtype=np.int64)
+        stt = np.zeros(max(b, 1), dtype=np.int32)
+        st = _L.as_search_subset_batch(self._h, gl._h, Q.ctypes.data_as(C.c_void_p), b, Q.shape[1], float(tau), sub._h,
+                                       idx.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p), ln.ctypes.data_as(C.c_void_p),
+                                       None, stt.ctypes.data_as(C.c_void_p))
+        if st:
+            _raise(st)
+        if (stt[:b] == _lib.AS_EZEROLAMBDA).any():
+            raise PanicException("The lambdas are zero, check the magnitude of items and eps.")
+        if kk == 0:
+            return [[] for _ in range(b)]
+        # (the C ABI's lists are at stride kk)
+        idx, sc = idx.reshape(-1)[:b * kk].reshape(b, kk), sc.reshape(-1)[:b * kk].reshape(b, kk)
+        return [list(zip(ii[:l], ss[:l])) for ii, ss, l in zip(idx.tolist(), sc.tolist(), ln[:b].tolist())]
+
+    def score_items_batch(self, items, gl: GraphLaplacian, tau: float, ids) -> np.ndarray:
+        """Extension: batched re-ranking -> ndarray[float64] of shape (B, len(ids)): entry [i, j] is what
+        `score_items(items[i], gl, tau, ids)[j]` returns (the caller's order, duplicates kept; within 1e-12 relative: the
+        batched kernel sums in another order).  Costs one `search_batch` over the B queries (lambda_q; a query whose lambda_q
+        is 0 panics as there) plus one gather of the listed rows per 64 queries."""
+        if not isinstance(gl, GraphLaplacian):
+            raise TypeError("argument 'gl': expected GraphLaplacian")
+        Q = np.ascontiguousarray(items, dtype=np.float64)
+        if Q.ndim != 2:
+            raise TypeError("items must be a 2-D float64 array")
+        ids = _item_ids(ids, self.nitems, "ids")
+        b, m = Q.shape[0], ids.shape[0]
+        out = np.empty((b, m), dtype=np.float64)
+        stt = np.zeros(max(b, 1), dtype=np.int32)
+        st = _L.as_score_items_batch(self._h, gl._h, Q.ctypes.data_as(C.c_void_p), b, Q.shape[1], float(tau),
+                                     ids.ctypes.data_as(C.c_void_p), m, out.ctypes.data_as(C.c_void_p), None,
+                                     stt.ctypes.data_as(C.c_void_p))
+        if st:
+            _raise(st)
+        if (stt[:b] == _lib.AS_EZEROLAMBDA).any():
+            raise PanicException("The lambdas are zero, check the magnitude of items and eps.")
         return out
 
     def sweep_counters(self) -> dict:

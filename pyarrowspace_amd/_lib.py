@@ -52,6 +52,7 @@ SYMBOLS = [
     "as_free_graph", "as_set_debug", "as_last_error", "as_device_count", "as_version",
     "as_comm_available", "as_comm_unique_id", "as_comm_create", "as_comm_free", "as_query_set_comm", "as_query_search_staged", "as_query_x1_bytes", "as_query_x1_usable", "as_query_x1_enabled", "as_query_set_x1", "as_query_x1_begin", "as_query_x1_finish", "as_query_x1_redo", "as_query_set_coarse", "as_query_x1_passes", "as_edges_bucket", "as_ring_i8_stats", "as_ring_i8_set", "as_ring_i8",
     "as_subset_create", "as_subset_size", "as_subset_ids", "as_subset_free", "as_search_subset", "as_score_items", "as_subset_set_timing", "as_subset_kernel_us",
+    "as_search_subset_batch", "as_score_items_batch",
 ]
 
 _lib = None
@@ -205,6 +206,8 @@ def load():
         "as_subset_free": (None, [vp]),
         "as_search_subset": (i32, [vp, vp, vp, i64, f64, vp, vp, vp, C.POINTER(i64), C.POINTER(f64)]),
         "as_score_items": (i32, [vp, vp, vp, i64, f64, vp, i64, vp, C.POINTER(f64)]),
+        "as_search_subset_batch": (i32, [vp, vp, vp, i64, i64, f64, vp, vp, vp, vp, vp, vp]),
+        "as_score_items_batch": (i32, [vp, vp, vp, i64, i64, f64, vp, i64, vp, vp, vp]),
         "as_subset_set_timing": (None, [vp, i32]),
         "as_subset_kernel_us": (f64, [vp]),
         "as_gang_counters": (i32, [vp, vp, i32]),

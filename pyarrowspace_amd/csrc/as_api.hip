@@ -1166,6 +1166,110 @@ as_status as_search_batch(const as_space* sp, const as_graph* gr, const double* 
     return AS_OK;
 }
 
+// The batched filtered forms.  What both check (the single forms' checks and messages), then lambda_q and the status of every
+// query from ONE as_search_batch call over all b queries, hits discarded: its escalation, its values.  as_search_batch has
+// returned, and released sp->bmu, before the caller takes the handle's mutex: the two are never nested.
+static as_status subset_batch_lambda(const char* who, const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d,
+                                     double tau, std::vector<double>& lq, std::vector<int32_t>& st) {
+    if (d != sp->d) {
+        set_err("query length %lld must match nfeatures %lld", (long long)d, (long long)sp->d);
+        return AS_EINVAL;
+    }
+    if (!std::isfinite(tau)) {
+        set_err("%s: tau must be finite", who);
+        return AS_EINVAL;
+    }
+    AS_TRY(graph_matches(sp, gr, who));
+    if (sp->row_offset != 0 || gr->ncols) {
+        set_err("%s: a shard of a row-sharded index is not supported", who);
+        return AS_EUNSUPPORTED;
+    }
+    if (b == 0) return AS_OK;
+    const int64_t topk = std::max<int64_t>(std::min<int64_t>(gr->gp.topk, sp->n), 1);
+    std::vector<int64_t> hidx, hlen;
+    std::vector<double> hsc;
+    try {
+        hidx.resize((size_t)(b * topk));
+        hsc.resize((size_t)(b * topk));
+        hlen.resize((size_t)b);
+        lq.assign((size_t)b, 0.0);
+        st.assign((size_t)b, 0);
+    } catch (const std::bad_alloc&) {
+        set_err("%s: out of host memory for %lld queries", who, (long long)b);
+        return AS_ENOMEM;
+    }
+    return as_search_batch(sp, gr, queries, b, d, tau, hidx.data(), hsc.data(), hlen.data(), lq.data(), st.data());
+}
+
+as_status as_search_subset_batch(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau,
+                                 const as_subset* sub, int64_t* out_idx, double* out_score, int64_t* out_len, double* out_lambda_q,
+                                 int32_t* out_status) {
+    if (!sp || !gr || !sub || b < 0 || (b > 0 && (!queries || !out_len || (sub->m > 0 && (!out_idx || !out_score))))) {
+        set_err("as_search_subset_batch: null argument");
+        return AS_EINVAL;
+    }
+    for (int64_t i = 0; i < b; ++i) out_len[i] = 0;
+    if (sub->sp != sp) {
+        set_err("as_search_subset_batch: the subset was made for another space");
+        return AS_EINVAL;
+    }
+    std::vector<double> lq;
+    std::vector<int32_t> st;
+    AS_TRY(subset_batch_lambda("as_search_subset_batch", sp, gr, queries, b, d, tau, lq, st));
+    for (int64_t i = 0; i < b; ++i) {
+        if (out_lambda_q) out_lambda_q[i] = lq[i];
+        if (out_status) out_status[i] = st[i];
+    }
+    if (b == 0 || sub->m == 0) return AS_OK;
+    const int64_t kk = std::min<int64_t>(std::min<int64_t>(gr->gp.topk, sp->n), sub->m);
+    std::lock_guard<std::mutex> lk(sub->mu);
+    AS_HIP(hipSetDevice(sp->device));
+    return subset_batch_run(sp, sub->w, sub->m, queries, b, lq.data(), st.data(), tau, kk, kk, out_idx, out_score, out_len, nullptr);
+}
+
+as_status as_score_items_batch(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau,
+                               const int64_t* ids_host, int64_t m, double* out_scores, double* out_lambda_q, int32_t* out_status) {
+    if (!sp || !gr || b < 0 || m < 0 || (b > 0 && !queries) || (m > 0 && !ids_host) || (b > 0 && m > 0 && !out_scores)) {
+        set_err("as_score_items_batch: null argument");
+        return AS_EINVAL;
+    }
+    for (int64_t i = 0; i < m; ++i)
+        if (ids_host[i] < 0 || ids_host[i] >= sp->n) {
+            set_err("as_score_items_batch: id %lld is outside [0, %lld)", (long long)ids_host[i], (long long)sp->n);
+            return AS_EINVAL;
+        }
+    std::vector<double> lq;
+    std::vector<int32_t> st;
+    AS_TRY(subset_batch_lambda("as_score_items_batch", sp, gr, queries, b, d, tau, lq, st));
+    for (int64_t i = 0; i < b; ++i) {
+        if (out_lambda_q) out_lambda_q[i] = lq[i];
+        if (out_status) out_status[i] = st[i];
+    }
+    if (b == 0 || m == 0) return AS_OK;
+    if (m >= (int64_t)1 << 31) {
+        set_err("as_score_items_batch: %lld ids exceed the supported maximum of 2^31 - 1 per call", (long long)m);
+        return AS_EUNSUPPORTED;
+    }
+    std::vector<int32_t> ids;   // (item ids fit 32 bits: space_new refuses n >= 2^31)
+    try {
+        ids.assign(ids_host, ids_host + m);
+    } catch (const std::bad_alloc&) {
+        set_err("as_score_items_batch: out of host memory for %lld ids", (long long)m);
+        return AS_ENOMEM;
+    }
+    std::lock_guard<std::mutex> lk(sp->smu);
+    AS_HIP(hipSetDevice(sp->device));
+    if (!sp->score_ws || sp->score_ws->cap < m) {   // grown on demand, never per call otherwise
+        subset_work_free(sp->score_ws);
+        sp->score_ws = nullptr;
+        int64_t cap = 1024;
+        while (cap < m) cap *= 2;
+        AS_TRY(subset_work_create(sp, cap, &sp->score_ws));
+    }
+    AS_TRY(subset_set_ids(sp->score_ws, ids.data(), m));
+    return subset_batch_run(sp, sp->score_ws, m, queries, b, lq.data(), st.data(), tau, 0, 0, nullptr, nullptr, nullptr, out_scores);
+}
+
 // One batched tau sweep over b > 1 queries for nt <= TAU_GROUP distinct taus in [0, 1] (under sp->bmu): as_search_batch's
 // workspaces, passes, pairs and pipelining, the scorer tail once per (query, tau) pair.  Pair (i, j): pidx / psc +
 // (i * nt + j) * topk, plen / pst [i * nt + j], plq [i]; pst -1: left to the single search.  *passes: passes that ran the tail.

@@ -537,7 +537,18 @@ struct SubsetWork {
     SubsetOut* out = nullptr;      // pinned, written by the sort kernel
     hipEvent_t ev[2] = {nullptr, nullptr};
     int timing = 0;                // record ev around the score kernel
-    double kernel_us = 0.0;        // ... and its duration in the last timed call
+    double kernel_us = 0.0;        // ... and its duration in the last timed call (the batched forms: summed over the chunks)
+    // the batched forms (subset_batch_run): made on the first batched call on this work, grown on demand
+    int64_t bq = 0;                // queries the buffers below hold (a multiple of the batched score kernel's query tile)
+    int64_t bscores_n = 0;         // doubles in bscores
+    bool bsel = false, bhist_on = false;   // the selection's result / radix buffers exist for bq queries
+    double* bqd = nullptr;         // [bq][dp] the queries, zero padded, then [bq] |q|^2, then [bq] lambda_q
+    double* bqh = nullptr;         // pinned staging of the same
+    double* bscores = nullptr;     // [chunk][m]
+    unsigned int* bhist = nullptr; // per query: what hist / state / sel_pos / out are for one
+    SubsetSel* bstate = nullptr;
+    int32_t* bsel_pos = nullptr;
+    SubsetOut* bout = nullptr;     // pinned [bq]
 };
 as_status subset_work_create(const as_space* sp, int64_t cap, SubsetWork** out);
 void subset_work_free(SubsetWork* w);
@@ -545,6 +556,13 @@ as_status subset_set_ids(SubsetWork* w, const int32_t* ids_host, int64_t m);
 as_status subset_score(const as_space* sp, SubsetWork* w, int64_t m, const double* query, double tau, double lambda_q);
 as_status subset_select(SubsetWork* w, int64_t m, int64_t k, int64_t* out_idx, double* out_score, int64_t* out_len);
 as_status subset_scores_out(SubsetWork* w, int64_t m, double* out);
+// The batched forms over the m ids of `w`: b queries [b][d] with their lambda_q and status (AS_EZEROLAMBDA: no output for that
+// query), in chunks of queries on the work's stream, one wait per chunk.  k > 0: the first k of every query's scores ->
+// out_idx / out_score at stride `stride`, out_len; k == 0: all scores -> out_scores [b][m].
+as_status subset_batch_run(const as_space* sp, SubsetWork* w, int64_t m, const double* queries, int64_t b, const double* lq,
+                           const int32_t* status, double tau, int64_t k, int64_t stride, int64_t* out_idx, double* out_score,
+                           int64_t* out_len, double* out_scores);
+void set_subset_batch_mib(int v);   // as_set_tuning("subset_batch_mib", v)
 constexpr int QUERY_BATCH = 32;  // == GQ in as_search.hip: query slots of the batched workspace
 constexpr int TAU_GROUP = 8;     // taus one shared pass of a tau sweep serves (search_sweep, as_search_taus)
 

@@ -3410,6 +3410,10 @@ int32_t as_set_tuning(const char* key, int32_t value) {
         set_x1_blocks(value);
         return 0;
     }
+    if (key && !strcmp(key, "subset_batch_mib")) {
+        set_subset_batch_mib(value);
+        return 0;
+    }
     return 1;
 }
 

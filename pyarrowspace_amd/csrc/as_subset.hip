@@ -3,6 +3,7 @@
 // score's bits, then the inverted position: no two keys are equal), then a one-block sort of the k selected entries.
 // Entry points: as_api.hip (as_search_subset, as_score_items).
 #include <algorithm>
+#include <atomic>
 #include <new>
 
 #include "as_common.hpp"
@@ -123,6 +124,135 @@ __global__ __launch_bounds__(256) void subset_score_kernel(SubsetArgs a) {
 }
 static_assert(SUB_ROWS == 4, "the lane selects of subset_score_kernel are written for four rows");
 
+// ------------------------------------------------------------------ batched score kernel
+// scores[q][i] for a tile of SB_ROWS gathered rows and SB_Q queries per block: an fp64 GEMM on v_mfma_f64_16x16x4_f64 with the
+// operand layouts of gram_f64_kernel (as_feat.hip).  A operand = queries (lane l: query l & 15, k = l >> 4), B operand = gathered
+// rows (lane l: position l & 15, k = l >> 4), so C/D has the position on its column (lane & 15) and the query on its row
+// ((lane >> 4) + 4 reg): the 16 scores of one query a wave stores per register are 128 contiguous bytes.  Wave (wi, wj) owns 64
+// positions x 32 queries: 4 x 2 accumulators.  K runs in stages of SB_K columns: the gathered rows (as stored: fp32 rows of
+// [np][dp], 16 bytes per lane, 8 lanes a row; or the fp64 rows of [n][d], 8-byte aligned only: one double per lane, 32 lanes a
+// row) and the query tile (fp64) go through LDS, the next stage's global loads are issued in front of a stage's MFMAs.  Row
+// pitches against bank conflicts of the operand reads (the 16 positions x 2 k of a 32-lane group): fp64 tiles 34 doubles (68
+// dwords, 64 banks: 32 distinct bank pairs), the fp32 tile 34 floats (32 banks for a 4-byte read: 32 distinct banks; its rows
+// are 8-byte aligned, so a lane's 16 bytes are written as two 8-byte halves).  Tail rows, the zero queries that pad a tile and columns >= d are zeros in LDS:
+// no branch inside the MFMA loop.  Every score is ONE accumulation chain over k = 0 .. dp - 1 in that order, whatever its
+// position in a tile: identical rows score bit-equal for one query.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+constexpr int SB_ROWS = 128;
+constexpr int SB_Q = 64;          // the query tile: chunks are multiples of it
+constexpr int SB_K = 32;
+constexpr int SB_PQ = SB_K + 2;   // pitch of an fp64 tile row, doubles
+constexpr int SB_PF = SB_K + 2;   // pitch of an fp32 tile row, floats
+
+struct SubsetBatchArgs {
+    const int32_t* ids;
+    int64_t m;
+    const float* x32;
+    const double* x64;
+    const double* n64;
+    const double* lam64;
+    const double* q64;   // [nqp][dp], nqp a multiple of SB_Q, rows >= nq zero
+    const double* nq;    // [nqp] |q|^2
+    const double* lq;    // [nqp] lambda_q
+    double* scores;      // [nq][ld]
+    int64_t ld, d, dp;
+    int nq_valid;
+    double tau;
+};
+
+template <bool F64>
+__global__ __launch_bounds__(256) void subset_score_batch_kernel(SubsetBatchArgs a) {
+    constexpr int PX = F64 ? SB_PQ : SB_PF;
+    constexpr int NR = F64 ? 16 : 4;   // rows a thread stages per K stage
+    __shared__ __attribute__((aligned(16))) double qs[SB_Q * SB_PQ];
+    __shared__ __attribute__((aligned(16))) char xs_raw[SB_ROWS * PX * (F64 ? 8 : 4)];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, wi = w >> 1, wj = w & 1;
+    const int lk = lane >> 4, lc = lane & 15;
+    const int64_t row0 = (int64_t)blockIdx.x * SB_ROWS;
+    const int64_t q0 = (int64_t)blockIdx.y * SB_Q;
+    // staging maps.  fp32 rows: thread t holds floats 4 (t & 7) .. + 3 of rows (t >> 3) + 32 i; fp64 rows: double t & 31 of rows
+    // (t >> 5) + 8 i; queries: doubles 2 (t & 15), + 1 of queries (t >> 4) + 16 i
+    const int xc = F64 ? (tid & 31) : (tid & 7) * 4, xr = F64 ? (tid >> 5) : (tid >> 3), xstep = F64 ? 8 : 32;
+    const int qc = (tid & 15) * 2, qr = tid >> 4;
+    int64_t rbase[NR];   // element offset of the staged rows; -1: past the end of the list (zeros)
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+        const int64_t pos = row0 + xr + xstep * i;
+        rbase[i] = pos < a.m ? (int64_t)a.ids[pos] * (F64 ? a.d : a.dp) : -1;
+    }
+    const double* qsrc = a.q64 + (q0 + qr) * a.dp + qc;
+    f32x4 vf[F64 ? 1 : NR];
+    double vd[F64 ? NR : 1];
+    f64x2 vq[4];
+    auto load_stage = [&](int64_t k0) {
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+            if (F64) vd[i] = (rbase[i] >= 0 && k0 + xc < a.d) ? a.x64[rbase[i] + k0 + xc] : 0.0;
+            else vf[i] = rbase[i] >= 0 ? *(const f32x4*)(a.x32 + rbase[i] + k0 + xc) : f32x4{0, 0, 0, 0};
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) vq[i] = *(const f64x2*)(qsrc + (int64_t)16 * i * a.dp + k0);
+    };
+    f64x4 acc[2][4];
+#pragma unroll
+    for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+        for (int jb = 0; jb < 4; ++jb) acc[ib][jb] = f64x4{0.0, 0.0, 0.0, 0.0};
+    load_stage(0);
+    for (int64_t k0 = 0; k0 < a.dp; k0 += SB_K) {
+        __syncthreads();   // the previous stage has been consumed
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+            if (F64) ((double*)xs_raw)[(xr + xstep * i) * PX + xc] = vd[i];
+            else {
+                f32x2* dst = (f32x2*)((float*)xs_raw + (xr + xstep * i) * PX + xc);
+                dst[0] = f32x2{vf[i][0], vf[i][1]};
+                dst[1] = f32x2{vf[i][2], vf[i][3]};
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) *(f64x2*)(qs + (qr + 16 * i) * SB_PQ + qc) = vq[i];
+        __syncthreads();
+        if (k0 + SB_K < a.dp) load_stage(k0 + SB_K);   // in flight under the MFMAs below
+#pragma unroll
+        for (int ks = 0; ks < SB_K / 4; ++ks) {
+            double av[2], bv[4];
+#pragma unroll
+            for (int ib = 0; ib < 2; ++ib) av[ib] = qs[(32 * wj + 16 * ib + lc) * SB_PQ + 4 * ks + lk];
+#pragma unroll
+            for (int jb = 0; jb < 4; ++jb) {
+                const int e = (64 * wi + 16 * jb + lc) * PX + 4 * ks + lk;
+                bv[jb] = F64 ? ((const double*)xs_raw)[e] : (double)((const float*)xs_raw)[e];
+            }
+#pragma unroll
+            for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+                for (int jb = 0; jb < 4; ++jb) acc[ib][jb] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[ib], bv[jb], acc[ib][jb], 0, 0, 0);
+        }
+    }
+    // C/D of v_mfma_f64_16x16x4_f64: col = lane & 15 (position), row = (lane >> 4) + 4 reg (query)
+#pragma unroll
+    for (int jb = 0; jb < 4; ++jb) {
+        const int64_t pos = row0 + 64 * wi + 16 * jb + lc;
+        if (pos >= a.m) continue;
+        const int64_t j = a.ids[pos];
+        const double nrm = a.n64[j], lam = a.lam64[j];
+#pragma unroll
+        for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int64_t q = q0 + 32 * wj + 16 * ib + lk + 4 * r;
+                if (q < a.nq_valid) {
+                    const double den = sqrt(nrm * a.nq[q]);
+                    const double c = den > 0.0 ? acc[ib][jb][r] / den : 0.0;
+                    a.scores[q * a.ld + pos] = blend_score(a.tau, c, a.lq[q], lam);
+                }
+            }
+    }
+}
+
 // ------------------------------------------------------------------ selection
 // Key of the entry at position i: 96 bits, hi = the score's bits mapped so that a larger score is a larger number (NaN lowest,
 // -0 as +0), lo = ~i (a smaller position is a larger number).  The k-th largest key T is found digit by digit, SEL_BITS bits a
@@ -222,8 +352,7 @@ __device__ __forceinline__ SubsetSel sel_state(int p, int k, SubsetSel* state, c
     return st;
 }
 
-__global__ __launch_bounds__(256) void subset_hist_kernel(const double* __restrict__ scores, int64_t m, int k, int p, SubsetSel* state,
-                                                          unsigned int* hist) {
+__device__ __forceinline__ void sel_hist_body(const double* __restrict__ scores, int64_t m, int k, int p, SubsetSel* state, unsigned int* hist) {
     __shared__ unsigned int lh[SEL_BINS];
     for (int b = threadIdx.x; b < SEL_BINS; b += blockDim.x) lh[b] = 0u;
     const SubsetSel st = sel_state(p, k, state, hist);   // (its barriers order the zeroing above, too)
@@ -238,10 +367,20 @@ __global__ __launch_bounds__(256) void subset_hist_kernel(const double* __restri
     for (int b = threadIdx.x; b < SEL_BINS; b += blockDim.x)
         if (lh[b]) atomicAdd(&gh[b], lh[b]);
 }
+__global__ __launch_bounds__(256) void subset_hist_kernel(const double* __restrict__ scores, int64_t m, int k, int p, SubsetSel* state,
+                                                          unsigned int* hist) {
+    sel_hist_body(scores, m, k, p, state, hist);
+}
+// the batched forms: query blockIdx.y of a chunk, its scores at stride ld, its own histograms, state, positions and result
+__global__ __launch_bounds__(256) void subset_hist_batch_kernel(const double* __restrict__ scores, int64_t ld, int64_t m, int k, int p,
+                                                                SubsetSel* state, unsigned int* hist) {
+    const int64_t q = blockIdx.y;
+    sel_hist_body(scores + q * ld, m, k, p, state + q * (SEL_PASSES + 1), hist + q * SEL_HIST_WORDS);
+}
 
 // the positions whose key is at or above T, in any order: exactly k of them
-__global__ __launch_bounds__(256) void subset_collect_kernel(const double* __restrict__ scores, int64_t m, int k, SubsetSel* state,
-                                                             unsigned int* hist, int32_t* sel_pos) {
+__device__ __forceinline__ void sel_collect_body(const double* __restrict__ scores, int64_t m, int k, SubsetSel* state, unsigned int* hist,
+                                                 int32_t* sel_pos) {
     const SubsetSel st = sel_state(SEL_PASSES, k, state, hist);
     unsigned int* cnt = hist + (int64_t)SEL_PASSES * SEL_BINS;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
@@ -253,12 +392,20 @@ __global__ __launch_bounds__(256) void subset_collect_kernel(const double* __res
         }
     }
 }
+__global__ __launch_bounds__(256) void subset_collect_kernel(const double* __restrict__ scores, int64_t m, int k, SubsetSel* state,
+                                                             unsigned int* hist, int32_t* sel_pos) {
+    sel_collect_body(scores, m, k, state, hist, sel_pos);
+}
+__global__ __launch_bounds__(256) void subset_collect_batch_kernel(const double* __restrict__ scores, int64_t ld, int64_t m, int k,
+                                                                   SubsetSel* state, unsigned int* hist, int32_t* sel_pos) {
+    const int64_t q = blockIdx.y;
+    sel_collect_body(scores + q * ld, m, k, state + q * (SEL_PASSES + 1), hist + q * SEL_HIST_WORDS, sel_pos + q * SUBSET_TOPK);
+}
 
 // One block: the selected entries (sel_pos; null: all m <= SUBSET_TOPK positions) ranked by (score descending, position
 // ascending) -- positions of a sorted id list are in id order --, the first k published to the pinned result.
-__global__ __launch_bounds__(1024) void subset_sort_kernel(const double* __restrict__ scores, const int32_t* __restrict__ ids, int64_t m,
-                                                           int k, const int32_t* __restrict__ sel_pos, const unsigned int* __restrict__ sel_cnt,
-                                                           SubsetOut* out) {
+__device__ __forceinline__ void sel_sort_body(const double* __restrict__ scores, const int32_t* __restrict__ ids, int64_t m, int k,
+                                              const int32_t* __restrict__ sel_pos, const unsigned int* __restrict__ sel_cnt, SubsetOut* out) {
     __shared__ unsigned long long sk[SUBSET_TOPK];
     __shared__ int32_t sp[SUBSET_TOPK];
     int n = sel_pos ? (int)(*sel_cnt < (unsigned int)SUBSET_TOPK ? *sel_cnt : (unsigned int)SUBSET_TOPK) : (int)m;
@@ -284,6 +431,18 @@ __global__ __launch_bounds__(1024) void subset_sort_kernel(const double* __restr
     }
     if (t == 0) out->len = n < k ? n : k;
 }
+__global__ __launch_bounds__(1024) void subset_sort_kernel(const double* __restrict__ scores, const int32_t* __restrict__ ids, int64_t m,
+                                                           int k, const int32_t* __restrict__ sel_pos, const unsigned int* __restrict__ sel_cnt,
+                                                           SubsetOut* out) {
+    sel_sort_body(scores, ids, m, k, sel_pos, sel_cnt, out);
+}
+__global__ __launch_bounds__(1024) void subset_sort_batch_kernel(const double* __restrict__ scores, int64_t ld, const int32_t* __restrict__ ids,
+                                                                 int64_t m, int k, const int32_t* __restrict__ sel_pos,
+                                                                 const unsigned int* __restrict__ hist, SubsetOut* out) {
+    const int64_t q = blockIdx.y;
+    sel_sort_body(scores + q * ld, ids, m, k, sel_pos ? sel_pos + q * SUBSET_TOPK : nullptr,
+                  sel_pos ? hist + q * SEL_HIST_WORDS + (int64_t)SEL_PASSES * SEL_BINS : nullptr, out + q);
+}
 
 // ------------------------------------------------------------------ host side
 // |q|^2 as the search forms it (as_search.hip: q_prepare_kernel on the device, host_query_norm on the host -- 256 partial sums,
@@ -302,6 +461,23 @@ static double subset_query_norm(const double* q, int64_t d) {
     return p[0];
 }
 
+static void subset_batch_release(SubsetWork* w) {
+    (void)hipFree(w->bqd);
+    (void)hipFree(w->bscores);
+    (void)hipFree(w->bhist);
+    (void)hipFree(w->bstate);
+    (void)hipFree(w->bsel_pos);
+    if (w->bqh) (void)hipHostFree(w->bqh);
+    if (w->bout) (void)hipHostFree(w->bout);
+    w->bqd = w->bqh = w->bscores = nullptr;
+    w->bhist = nullptr;
+    w->bstate = nullptr;
+    w->bsel_pos = nullptr;
+    w->bout = nullptr;
+    w->bq = w->bscores_n = 0;
+    w->bsel = w->bhist_on = false;
+}
+
 void subset_work_free(SubsetWork* w) {
     if (!w) return;
     (void)hipSetDevice(w->device);
@@ -314,6 +490,7 @@ void subset_work_free(SubsetWork* w) {
     (void)hipFree(w->sel_pos);
     if (w->hq) (void)hipHostFree(w->hq);
     if (w->out) (void)hipHostFree(w->out);
+    subset_batch_release(w);
     for (int i = 0; i < 2; ++i)
         if (w->ev[i]) (void)hipEventDestroy(w->ev[i]);
     if (w->stream) (void)hipStreamDestroy(w->stream);
@@ -436,6 +613,149 @@ as_status subset_scores_out(SubsetWork* w, int64_t m, double* out) {
     if (m > 0) AS_HIP(hipMemcpyAsync(out, w->scores, sizeof(double) * m, hipMemcpyDeviceToHost, w->stream));
     AS_HIP(hipStreamSynchronize(w->stream));
     return m > 0 ? subset_finish_timing(w) : AS_OK;
+}
+
+// ------------------------------------------------------------------ batched forms
+// Queries per chunk: the largest multiple of the score kernel's query tile whose scores ([chunk][m] doubles) fit this budget, at
+// least one tile, at most SB_QC_MAX (the selection keeps 128 KiB of histograms and a 16 KiB pinned result per query).  Results
+// never depend on it.
+static std::atomic<int> g_subset_batch_mib{256};
+void set_subset_batch_mib(int v) { g_subset_batch_mib.store(v > 0 ? v : 256, std::memory_order_relaxed); }
+constexpr int64_t SB_QC_MAX = 4096;
+
+static as_status subset_batch_reserve(SubsetWork* w, int64_t nq, int64_t m, bool sel, bool hist) {
+    hipError_t e = hipSuccess;
+    const char* what = "queries";
+    if (nq > w->bq) {
+        subset_batch_release(w);
+        const size_t qbytes = sizeof(double) * (size_t)nq * (size_t)(w->dp + 2);
+        if ((e = hipMalloc((void**)&w->bqd, qbytes)) == hipSuccess && (e = hipHostMalloc((void**)&w->bqh, qbytes, hipHostMallocDefault)) == hipSuccess)
+            w->bq = nq;
+    }
+    if (e == hipSuccess && nq * m > w->bscores_n) {
+        what = "scores";
+        (void)hipFree(w->bscores);
+        w->bscores = nullptr;
+        w->bscores_n = 0;
+        if ((e = hipMalloc((void**)&w->bscores, sizeof(double) * (size_t)(w->bq * m))) == hipSuccess) w->bscores_n = w->bq * m;
+    }
+    if (e == hipSuccess && sel && !w->bsel) {
+        what = "results";
+        if ((e = hipHostMalloc((void**)&w->bout, sizeof(SubsetOut) * (size_t)w->bq, hipHostMallocDefault)) == hipSuccess) w->bsel = true;
+    }
+    if (e == hipSuccess && hist && !w->bhist_on) {
+        what = "selection";
+        if ((e = hipMalloc((void**)&w->bhist, sizeof(unsigned int) * SEL_HIST_WORDS * (size_t)w->bq)) == hipSuccess &&
+            (e = hipMalloc((void**)&w->bstate, sizeof(SubsetSel) * (SEL_PASSES + 1) * (size_t)w->bq)) == hipSuccess &&
+            (e = hipMalloc((void**)&w->bsel_pos, sizeof(int32_t) * SUBSET_TOPK * (size_t)w->bq)) == hipSuccess)
+            w->bhist_on = true;
+    }
+    if (e != hipSuccess) {
+        set_err("subset: allocation of the batched buffers (%s, %lld queries x %lld ids) failed: %s", what, (long long)nq, (long long)m,
+                hipGetErrorString(e));
+        subset_batch_release(w);
+        return e == hipErrorOutOfMemory ? AS_ENOMEM : AS_EHIP;
+    }
+    return AS_OK;
+}
+
+as_status subset_batch_run(const as_space* sp, SubsetWork* w, int64_t m, const double* queries, int64_t b, const double* lq,
+                           const int32_t* status, double tau, int64_t k, int64_t stride, int64_t* out_idx, double* out_score,
+                           int64_t* out_len, double* out_scores) {
+    if (m <= 0 || b <= 0) return AS_OK;
+    const bool sel = k > 0;
+    if (sel) k = std::min<int64_t>(std::min<int64_t>(k, m), SUBSET_TOPK);
+    const int64_t budget = (int64_t)g_subset_batch_mib.load(std::memory_order_relaxed) << 20;
+    int64_t qc = budget / (m * (int64_t)sizeof(double)) / SB_Q * SB_Q;
+    qc = std::min<int64_t>(std::max<int64_t>(qc, SB_Q), SB_QC_MAX);
+    qc = std::min<int64_t>(qc, (b + SB_Q - 1) / SB_Q * SB_Q);
+    const bool hist = sel && m > SUBSET_TOPK;
+    AS_TRY(subset_batch_reserve(w, qc, m, sel, hist));
+    const int64_t d = sp->d, dp = w->dp;
+    w->kernel_us = 0.0;
+    for (int64_t i0 = 0; i0 < b; i0 += qc) {
+        const int64_t nb = std::min<int64_t>(qc, b - i0), nbp = (nb + SB_Q - 1) / SB_Q * SB_Q;
+        double* hq = w->bqh;
+        double* hn = hq + nbp * dp;
+        double* hl = hn + nbp;
+        for (int64_t t = 0; t < nbp; ++t) {
+            double* row = hq + t * dp;
+            if (t < nb) {
+                const double* q = queries + (i0 + t) * d;
+                for (int64_t c = 0; c < d; ++c) row[c] = q[c];
+                for (int64_t c = d; c < dp; ++c) row[c] = 0.0;
+                hn[t] = subset_query_norm(q, d);
+                hl[t] = lq[i0 + t];
+            } else {
+                for (int64_t c = 0; c < dp; ++c) row[c] = 0.0;
+                hn[t] = hl[t] = 0.0;
+            }
+        }
+        AS_HIP(hipMemcpyAsync(w->bqd, hq, sizeof(double) * (size_t)(nbp * (dp + 2)), hipMemcpyHostToDevice, w->stream));
+        SubsetBatchArgs a;
+        a.ids = w->ids; a.m = m; a.x32 = sp->x32; a.x64 = sp->x64; a.n64 = sp->n64; a.lam64 = sp->lam64; a.q64 = w->bqd;
+        a.nq = w->bqd + nbp * dp; a.lq = a.nq + nbp; a.scores = w->bscores; a.ld = m; a.d = d; a.dp = dp; a.nq_valid = (int)nb; a.tau = tau;
+        const dim3 grid((unsigned)((m + SB_ROWS - 1) / SB_ROWS), (unsigned)(nbp / SB_Q));
+        if (w->timing) AS_HIP(hipEventRecord(w->ev[0], w->stream));
+        if (sp->x64) hipLaunchKernelGGL(subset_score_batch_kernel<true>, grid, dim3(256), 0, w->stream, a);
+        else hipLaunchKernelGGL(subset_score_batch_kernel<false>, grid, dim3(256), 0, w->stream, a);
+        AS_HIP(hipGetLastError());
+        if (w->timing) AS_HIP(hipEventRecord(w->ev[1], w->stream));
+        if (sel) {
+            const unsigned ny = (unsigned)nb;
+            if (!hist) {
+                hipLaunchKernelGGL(subset_sort_batch_kernel, dim3(1, ny), dim3(1024), 0, w->stream, (const double*)w->bscores, m,
+                                   (const int32_t*)w->ids, m, (int)k, (const int32_t*)nullptr, (const unsigned int*)nullptr, w->bout);
+            } else {
+                AS_HIP(hipMemsetAsync(w->bhist, 0, sizeof(unsigned int) * SEL_HIST_WORDS * (size_t)nb, w->stream));
+                const unsigned gx = (unsigned)std::min<int64_t>((m + 2047) / 2048, 512);
+                for (int p = 0; p < SEL_PASSES; ++p)
+                    hipLaunchKernelGGL(subset_hist_batch_kernel, dim3(gx, ny), dim3(256), 0, w->stream, (const double*)w->bscores, m, m, (int)k, p,
+                                       w->bstate, w->bhist);
+                hipLaunchKernelGGL(subset_collect_batch_kernel, dim3(gx, ny), dim3(256), 0, w->stream, (const double*)w->bscores, m, m, (int)k,
+                                   w->bstate, w->bhist, w->bsel_pos);
+                hipLaunchKernelGGL(subset_sort_batch_kernel, dim3(1, ny), dim3(1024), 0, w->stream, (const double*)w->bscores, m,
+                                   (const int32_t*)w->ids, m, (int)k, (const int32_t*)w->bsel_pos, (const unsigned int*)w->bhist, w->bout);
+            }
+            AS_HIP(hipGetLastError());
+        } else {
+            // one copy per chunk; a zero-lambda query's row stays unwritten: the copy is split around it
+            for (int64_t t = 0; t < nb;) {
+                if (status[i0 + t] == AS_EZEROLAMBDA) {
+                    ++t;
+                    continue;
+                }
+                int64_t u = t;
+                while (u < nb && status[i0 + u] != AS_EZEROLAMBDA) ++u;
+                AS_HIP(hipMemcpyAsync(out_scores + (i0 + t) * m, w->bscores + t * m, sizeof(double) * (size_t)((u - t) * m), hipMemcpyDeviceToHost,
+                                      w->stream));
+                t = u;
+            }
+        }
+        AS_HIP(hipStreamSynchronize(w->stream));
+        if (w->timing) {
+            float ms = 0.0f;
+            AS_HIP(hipEventElapsedTime(&ms, w->ev[0], w->ev[1]));
+            w->kernel_us += (double)ms * 1e3;
+        }
+        if (sel)
+            for (int64_t t = 0; t < nb; ++t) {
+                const int64_t i = i0 + t;
+                out_len[i] = 0;
+                if (status[i] == AS_EZEROLAMBDA) continue;
+                const SubsetOut* o = w->bout + t;
+                if (o->len != k) {
+                    set_err("subset: the selection returned %lld of %lld entries for query %lld", (long long)o->len, (long long)k, (long long)i);
+                    return AS_EHIP;
+                }
+                for (int64_t r = 0; r < k; ++r) {
+                    out_idx[i * stride + r] = o->idx[r];
+                    out_score[i * stride + r] = o->score[r];
+                }
+                out_len[i] = k;
+            }
+    }
+    return AS_OK;
 }
 
 }  // namespace as
