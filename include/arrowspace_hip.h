@@ -103,7 +103,10 @@ as_status as_knn_rows(const as_space* sp, const as_graph_params* gp, int64_t row
                       int32_t* out_idx_dev, double* out_key_dev, double* out_dist_dev, double* out_gy_dev,
                       int32_t* out_cnt_dev);
 /* step 3: symmetrise + normalised Laplacian + per-item energy + lambdas from the
- * complete n x k lists (device).  Writes lambdas into the space. */
+ * complete n x k lists (device).  Writes lambdas into the space.
+ * The lists are taken as as_knn_rows leaves them and are NOT validated (as_graph_from_knn_global alike): row i holds
+ * cnt[i] <= k entries; every id is in [0, n), is not i, and occurs once in its row; slots past cnt[i] are never read,
+ * whatever they hold.  An id outside [0, n) is an out-of-bounds access.  (as_graph_shard_csr checks its ids.) */
 as_status as_graph_from_knn(as_space* sp, const as_graph_params* gp, const int32_t* idx_dev,
                             const double* dist_dev, const double* gy_dev, const int32_t* cnt_dev,
                             as_graph** out_graph);
@@ -180,7 +183,9 @@ as_status as_knn_block_exact(const as_space* sp, const as_space* cols, const as_
                              double* p_gy_dev, int32_t* p_idx_dev, int32_t* p_cnt_dev, float* p_t32_dev);
 /* step 3 over the lists of ALL n_global items for a space that holds the rows [row_offset, row_offset + nitems):
  * global graph, Laplacian, energies, tau0; this shard's lambdas into the space.  n64_global_dev: fp64 squared norms
- * of all items (device).  Searches on the space then report global item ids. */
+ * of all items (device).  Searches on the space then report global item ids.
+ * Lists: n_global x k, under as_graph_from_knn's assumptions (ids in [0, n_global), no self, no repeat in a row,
+ * cnt <= k, slots past cnt ignored) -- assumed, not checked. */
 as_status as_graph_from_knn_global(as_space* sp, const as_graph_params* gp, int64_t n_global, int64_t row_offset,
                                    const int32_t* idx_dev, const double* dist_dev, const double* gy_dev,
                                    const int32_t* cnt_dev, const double* n64_global_dev, as_graph** out_graph);
