@@ -85,6 +85,48 @@ static as_status pick_device(const as_opts* opts, int* dev) {
     return AS_OK;
 }
 
+// The pass pipeline of the batched searches (as_search_batch, batch_sweep_run; under sp->bmu, b > 1 queries on the workspaces of
+// batch_workspaces).  A UNIT = the passes launched together: a pair (two workspaces), or one pass; two sets of workspaces
+// alternate when there is more than one unit and the workspaces exist (`piped`): unit j + 1 is queued before unit j is waited for.
+// launch(w0, i0, nb0, w1, i1, nb1): queue the pass of queries [i0, i0 + nb0) on w0 -- w1 set: with that of [i1, i1 + nb1) on w1,
+// as a pair; collect(w, i0, nb): wait for the pass of queries [i0, i0 + nb) on w and hand out its results.
+template <typename Launch, typename Collect>
+static as_status batch_passes(const as_space* sp, int unit, int64_t b, Launch launch, Collect collect) {
+    as_query* ws[4] = {sp->qcache_b, sp->qcache_b2, sp->qcache_b3, sp->qcache_b4};
+    const bool piped = b > unit * QUERY_BATCH && ws[2 * unit - 1] != nullptr;
+    const int nws = unit * (piped ? 2 : 1);
+    // an error leaves no pass in flight behind it (the other workspaces' kernels would otherwise still be running when the
+    // caller comes back)
+    auto drain = [&](as_status s) {
+        if (nws > 1)
+            for (int w = 0; w < nws; ++w) (void)hipStreamSynchronize((hipStream_t)as_query_stream(ws[w]));
+        return s;
+    };
+    const int64_t UNIT = (int64_t)unit * QUERY_BATCH;
+    auto launch_unit = [&](int64_t j) -> as_status {
+        as_query* const* w = ws + (piped ? unit * (j & 1) : 0);
+        const int64_t i0 = j * UNIT, i1 = i0 + QUERY_BATCH;
+        const bool pair = unit == 2 && i1 < b;
+        return launch(w[0], i0, (int)std::min<int64_t>(QUERY_BATCH, b - i0), pair ? w[1] : nullptr, i1, pair ? (int)std::min<int64_t>(QUERY_BATCH, b - i1) : 0);
+    };
+    if (piped) {
+        const as_status s0 = launch_unit(0);
+        if (s0 != AS_OK) return drain(s0);
+    }
+    int64_t pass = 0;
+    for (int64_t i0 = 0; i0 < b; i0 += QUERY_BATCH, ++pass) {
+        const int64_t j = pass / unit;
+        as_status s = AS_OK;
+        if (pass % unit == 0) {   // a unit's first pass: queue the next unit (piped), or this one
+            if (!piped) s = launch_unit(j);
+            else if ((j + 1) * UNIT < b) s = launch_unit(j + 1);
+        }
+        if (s == AS_OK) s = collect(ws[(piped ? unit * (j & 1) : 0) + (int)(pass % unit)], i0, (int)std::min<int64_t>(QUERY_BATCH, b - i0));
+        if (s != AS_OK) return drain(s);
+    }
+    return AS_OK;
+}
+
 }  // namespace as
 
 using namespace as;
@@ -1091,78 +1133,57 @@ as_status as_search_batch(const as_space* sp, const as_graph* gr, const double* 
     const int64_t topk = std::min<int64_t>(gr->gp.topk, sp->n);
     std::lock_guard<std::mutex> lock(sp->bmu);   // (the batched workspaces; single-query fallbacks below go through the pool)
     AS_HIP(hipSetDevice(sp->device));
-    // the batched pass serves QUERY_BATCH queries per read of the items (MFMA pass; rows wider than 768 floats in
-    // K-chunk passes of the same kernel): fp32 fast path only
-    const bool batched = !sp->opts.force_exact && (sp->opts.search_mode & 3) == 0 && b > 1;
-    int unit = 1;   // passes launched together
-    if (batched) AS_TRY(batch_workspaces(sp, gr, b, &unit));
-    // a UNIT = the passes launched together: a pair (two workspaces), or one pass; two sets of workspaces alternate when there is
-    // more than one unit and the workspaces exist (`piped`)
-    as_query* ws[4] = {sp->qcache_b, sp->qcache_b2, sp->qcache_b3, sp->qcache_b4};
-    const bool piped = batched && b > unit * QUERY_BATCH && ws[2 * unit - 1] != nullptr;
-    const int nws = batched ? unit * (piped ? 2 : 1) : 0;
-    // an error leaves no pass in flight behind it (the other workspaces' kernels would otherwise still be running when the
-    // caller comes back)
-    auto drain = [&](as_status s) {
-        if (nws > 1)
-            for (int w = 0; w < nws; ++w) (void)hipStreamSynchronize((hipStream_t)as_query_stream(ws[w]));
-        return s;
-    };
     int32_t st_chunk[QUERY_BATCH];
-    const int64_t UNIT = (int64_t)unit * QUERY_BATCH;
-    auto launch_unit = [&](int64_t j) -> as_status {
-        as_query* const* w = ws + (piped ? unit * (j & 1) : 0);
-        const int64_t i0 = j * UNIT, i1 = i0 + QUERY_BATCH;
-        const int nb0 = (int)std::min<int64_t>(QUERY_BATCH, b - i0);
-        if (unit == 2 && i1 < b) return search_batch_launch_pair(w[0], w[1], queries + i0 * d, nb0, queries + i1 * d, (int)std::min<int64_t>(QUERY_BATCH, b - i1), d, tau);
-        return search_batch_launch(w[0], queries + i0 * d, nb0, d, tau);
-    };
-    if (piped) {
-        const as_status s0 = launch_unit(0);
-        if (s0 != AS_OK) return drain(s0);
-    }
-    int64_t pass = 0;
-    static const bool timing = getenv("ARROWSPACE_DEBUG") != nullptr;   // host time of the two halves of a pass, per call
-    double t_launch = 0.0, t_collect = 0.0;
-    auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    for (int64_t i0 = 0; i0 < b; i0 += QUERY_BATCH, ++pass) {
-        const int nb = (int)std::min<int64_t>(QUERY_BATCH, b - i0);
-        if (batched) {
-            const int64_t j = pass / unit;
-            as_query* cur = ws[(piped ? unit * (j & 1) : 0) + (int)(pass % unit)];
-            as_status s = AS_OK;
-            const double t0 = timing ? now() : 0.0;
-            if (pass % unit == 0) {   // a unit's first pass: queue the next unit (piped), or this one
-                if (!piped) s = launch_unit(j);
-                else if ((j + 1) * UNIT < b) s = launch_unit(j + 1);
-            }
-            const double t1 = timing ? now() : 0.0;
-            if (s == AS_OK)
-                s = search_batch_collect(cur, nb, tau, topk, out_idx + i0 * topk, out_score + i0 * topk, out_len + i0,
-                                         out_lambda_q ? out_lambda_q + i0 : nullptr, st_chunk);
-            if (timing) {
-                t_launch += t1 - t0;
-                t_collect += now() - t1;
-            }
-            if (s != AS_OK) return drain(s);
-        } else {
-            for (int t = 0; t < nb; ++t) st_chunk[t] = -1;
-        }
+    // the slots of a pass the batched fast path did not prove exact (or all of them: batching unavailable) on the single-query path
+    auto singles = [&](int64_t i0, int nb) -> as_status {
         for (int t = 0; t < nb; ++t) {
             const int64_t i = i0 + t;
-            if (st_chunk[t] == -1) {  // not provably exact on the batched fast path (or batching unavailable)
+            if (st_chunk[t] == -1) {
                 double lq = 0.0;
                 const as_status s1 = search_pooled(sp, gr, queries + i * d, d, tau, out_idx + i * topk, out_score + i * topk, out_len + i, &lq);
                 if (out_lambda_q) out_lambda_q[i] = lq;
                 st_chunk[t] = (int32_t)s1;
-                if (s1 != AS_OK && s1 != AS_EZEROLAMBDA) return drain(s1);
+                if (s1 != AS_OK && s1 != AS_EZEROLAMBDA) return s1;
             }
             if (st_chunk[t] == AS_EZEROLAMBDA) out_len[i] = 0;
             if (out_status) out_status[i] = st_chunk[t];
         }
+        return AS_OK;
+    };
+    // the batched pass serves QUERY_BATCH queries per read of the items (MFMA pass; rows wider than 768 floats in
+    // K-chunk passes of the same kernel): fp32 fast path only
+    if (sp->opts.force_exact || (sp->opts.search_mode & 3) != 0 || b <= 1) {
+        for (int64_t i0 = 0; i0 < b; i0 += QUERY_BATCH) {
+            for (int t = 0; t < QUERY_BATCH; ++t) st_chunk[t] = -1;
+            AS_TRY(singles(i0, (int)std::min<int64_t>(QUERY_BATCH, b - i0)));
+        }
+        return AS_OK;
     }
-    if (timing && batched) dbg("as_search_batch: %lld passes, host time per pass: launch half %.0f us, collect half (with its wait) %.0f us",
-                               (long long)pass, t_launch / std::max<int64_t>(pass, 1), t_collect / std::max<int64_t>(pass, 1));
+    int unit = 1;   // passes launched together
+    AS_TRY(batch_workspaces(sp, gr, b, &unit));
+    int64_t passes = 0;
+    static const bool timing = getenv("ARROWSPACE_DEBUG") != nullptr;   // host time of the two halves of a pass, per call
+    double t_launch = 0.0, t_collect = 0.0;
+    auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    AS_TRY(batch_passes(
+        sp, unit, b,
+        [&](as_query* w0, int64_t i0, int nb0, as_query* w1, int64_t i1, int nb1) -> as_status {
+            const double t0 = timing ? now() : 0.0;
+            const as_status s = w1 ? search_batch_launch_pair(w0, w1, queries + i0 * d, nb0, queries + i1 * d, nb1, d, tau)
+                                   : search_batch_launch(w0, queries + i0 * d, nb0, d, tau);
+            if (timing) t_launch += now() - t0;
+            return s;
+        },
+        [&](as_query* w, int64_t i0, int nb) -> as_status {
+            const double t1 = timing ? now() : 0.0;
+            const as_status s = search_batch_collect(w, nb, tau, topk, out_idx + i0 * topk, out_score + i0 * topk, out_len + i0,
+                                                     out_lambda_q ? out_lambda_q + i0 : nullptr, st_chunk);
+            if (timing) t_collect += now() - t1;
+            passes += 1;
+            return s != AS_OK ? s : singles(i0, nb);
+        }));
+    if (timing) dbg("as_search_batch: %lld passes, host time per pass: launch half %.0f us, collect half (with its wait) %.0f us",
+                    (long long)passes, t_launch / std::max<int64_t>(passes, 1), t_collect / std::max<int64_t>(passes, 1));
     return AS_OK;
 }
 
@@ -1278,45 +1299,17 @@ static as_status batch_sweep_run(const as_space* sp, const as_graph* gr, const d
                                  int64_t* passes) {
     int unit = 1;
     AS_TRY(batch_workspaces(sp, gr, b, &unit));
-    as_query* ws[4] = {sp->qcache_b, sp->qcache_b2, sp->qcache_b3, sp->qcache_b4};
-    const bool piped = b > unit * QUERY_BATCH && ws[2 * unit - 1] != nullptr;
-    const int nws = unit * (piped ? 2 : 1);
-    auto drain = [&](as_status s) {
-        if (nws > 1)
-            for (int w = 0; w < nws; ++w) (void)hipStreamSynchronize((hipStream_t)as_query_stream(ws[w]));
-        return s;
-    };
-    const int64_t UNIT = (int64_t)unit * QUERY_BATCH;
-    auto launch_unit = [&](int64_t j) -> as_status {
-        as_query* const* w = ws + (piped ? unit * (j & 1) : 0);
-        const int64_t i0 = j * UNIT, i1 = i0 + QUERY_BATCH;
-        const int nb0 = (int)std::min<int64_t>(QUERY_BATCH, b - i0);
-        if (unit == 2 && i1 < b)
-            return search_batch_sweep_launch_pair(w[0], w[1], queries + i0 * d, nb0, queries + i1 * d, (int)std::min<int64_t>(QUERY_BATCH, b - i1), d,
-                                                  gt, nt);
-        return search_batch_sweep_launch(w[0], queries + i0 * d, nb0, d, gt, nt);
-    };
-    if (piped) {
-        const as_status s0 = launch_unit(0);
-        if (s0 != AS_OK) return drain(s0);
-    }
-    int64_t pass = 0;
-    for (int64_t i0 = 0; i0 < b; i0 += QUERY_BATCH, ++pass) {
-        const int nb = (int)std::min<int64_t>(QUERY_BATCH, b - i0);
-        const int64_t j = pass / unit;
-        as_query* cur = ws[(piped ? unit * (j & 1) : 0) + (int)(pass % unit)];
-        as_status s = AS_OK;
-        if (pass % unit == 0) {
-            if (!piped) s = launch_unit(j);
-            else if ((j + 1) * UNIT < b) s = launch_unit(j + 1);
-        }
-        if (s == AS_OK)
-            s = search_batch_sweep_collect(cur, nb, gt, nt, topk, pidx + i0 * nt * topk, psc + i0 * nt * topk, plen + i0 * nt, plq + i0,
-                                           pst + i0 * nt);
-        if (s != AS_OK) return drain(s);
-        *passes += query_sweep_ran(cur);
-    }
-    return AS_OK;
+    return batch_passes(
+        sp, unit, b,
+        [&](as_query* w0, int64_t i0, int nb0, as_query* w1, int64_t i1, int nb1) {
+            return w1 ? search_batch_sweep_launch_pair(w0, w1, queries + i0 * d, nb0, queries + i1 * d, nb1, d, gt, nt)
+                      : search_batch_sweep_launch(w0, queries + i0 * d, nb0, d, gt, nt);
+        },
+        [&](as_query* w, int64_t i0, int nb) -> as_status {
+            AS_TRY(search_batch_sweep_collect(w, nb, gt, nt, topk, pidx + i0 * nt * topk, psc + i0 * nt * topk, plen + i0 * nt, plq + i0, pst + i0 * nt));
+            *passes += query_sweep_ran(w);
+            return AS_OK;
+        });
 }
 
 // Extension: b queries under ntau taus -- entry (i, j) is what as_search returns for query i and taus[j].  Equal taus are

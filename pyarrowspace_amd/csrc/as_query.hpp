@@ -201,16 +201,11 @@ struct as_query {
     double coef_i8h = 0.0;               // the coarse scan's coefficient for THIS query (host_query_digits)
     int coarse = 0;                      // the last scan was the coarse one
     int coarse_off = 0;                  // > 0: counting the searches that skip it
-    int coarse_never = 0;                // set around the redo of a query whose coarse candidates did not fit
-    int allow_coarse = 0;                // set by search_once around query_begin: the caller's tail evaluates every k-NN candidate exactly
-    int chainc = 0;                      // ... and this search is a COARSE CHAIN: coarse scan without scan-side scorer candidates, every candidate list
-                                         // derived from the kept dots and evaluated exactly (search_once, coarse_score_stage)
-    int chainc_off = 0;                  // > 0: a coarse chain did not serve a recent query cleanly (counts the searches that skip it)
+    int coarse_never = 0;                // as_query_set_coarse(q, 0): this workspace's scans never take the coarse image
+    int chainc_off = 0;                  // > 0: a COARSE CHAIN (ScanRequest::chainc) did not serve a recent query cleanly (counts the searches that skip it)
     int xknn_dirty = 0;                  // ... its counter may be non-zero (a pass died before its finish kernel)
     void* xknn = nullptr;                // [CAND_CAP] exact (id, key, distance, gy) of the coarse scan's k-NN candidates (staged_x1_kernel, xk)
     int pool_slot = 0;       // slot in the space's pool of single-query workspaces (as_search): picks the stream's priority
-    int gang_ok = 0;         // set by search_once around query_begin: this scan may be shared with other callers' (gang_launch)
-    as::PreArgs* defer_pre = nullptr;   // set: query_begin stops in front of the scan's launch and leaves its arguments there (search_batch_launch_pair)
     hipEvent_t gang_ev = nullptr;   // recorded behind a gang's scan on its leader's stream: the followers' tails wait for it
     float* dots32 = nullptr; // [np]
     float* part32 = nullptr; // batched workspace of rows wider than 768 floats: [K-chunk pass][slots x np] fp32 partial dots (as_scan.hip, gemm_chunks)
@@ -224,7 +219,6 @@ struct as_query {
     int* sc_widx = nullptr;  // fused tail: the scan's scorer candidates, a report of SC_WCAP words per wave of the scan
     unsigned int* sc_hist = nullptr;   // SC_COPIES x SC_HSTRIDE words, zero between searches
     int sc_nw = 0;           // waves of the last fused scan
-    int sc_late = 0;         // this search's tail validates lossy wave reports (set around query_begin by the paths whose tail is staged_x1_kernel)
     int last_sc_m = 0;       // what the last fused scan collected with (make_pre): the tail recomputes the bound from the final histogram
     float last_sc_w = 0.0f;
     void* gmin = nullptr;    // group minima of the scorer key
@@ -237,11 +231,8 @@ struct as_query {
     int ev_valid = 0;
     double stats[4] = {0, 0, 0, 0};
     int crowded = 0;         // > 0: recent queries overflowed the scan's candidate buffer (counts queries since)
-    int crowded_direct = 0;  // this query skips the prefilter and takes the threshold repair straight away
-    int fused_tail = 0;      // this search: the scan collects the scorer's candidates, ONE kernel behind it finishes the query
     int sc_crowded = 0;      // > 0: a recent query's scan-side scorer candidates overflowed (counts queries since): plain chain
     int no_fused = 0;        // ARROWSPACE_NO_FUSED_TAIL: always the plain chain (A/B runs)
-    double tau_cur = 1.0;    // the tau of the search being launched (the scan's cosine window depends on it)
     int* unproven_dev = nullptr;   // build fallback: device counter (caller-owned) of rows that stay unproven
     double staged_tau = -1.0;            // as_query_search_staged: the tau of the search whose scan comes next (-1: not announced)
     int staged_sc = 0;                   // the last as_query_scan collected the scorer's candidates (SC)
@@ -318,11 +309,28 @@ struct PreArgs {
     const float* faqv = nullptr;   // batched pass on the int8 images: the slots' scales
 };
 
+// What a caller asks of ONE scan (query_begin; make_pre and gang_launch read it): per-call mode travels here, never through the
+// workspace.  A default-constructed request is the plain scan: prefilter on, the two-digit image or the fp32 items, no scan-side
+// scorer candidates, launched at once and for this workspace alone.
+struct ScanRequest {
+    int sc = 0;              // the scan collects the scorer's candidates (fused tail: ONE kernel chain behind it finishes the query) ...
+    double tau = 1.0;        // ... for this tau (the scan's cosine window depends on it)
+    int sc_late = 0;         // the caller's tail validates lossy wave reports (the paths whose tail is staged_x1_kernel)
+    int allow_coarse = 0;    // the coarse scan may serve: the caller's tail evaluates every k-NN candidate exactly
+    int chainc = 0;          // ... and this search is a COARSE CHAIN: coarse scan without scan-side scorer candidates, every candidate list
+                             // derived from the kept dots and evaluated exactly (search_once, coarse_score_stage)
+    int gang_ok = 0;         // this scan may be shared with other callers' (gang_launch)
+    int direct = 0;          // this query skips the prefilter and takes the threshold repair straight away (crowded neighbourhood)
+    int no_coarse = 0;       // not the coarse scan for this call, whatever the switches say (the redo of a query it did not serve)
+    PreArgs* defer_pre = nullptr;   // set: query_begin stops in front of the scan's launch and leaves its arguments there (batch_launch_pair)
+    int sc_ran = 0;          // OUT: the scan does collect the scorer's candidates (rows of 1025 .. 4096 floats: only when the int8 image serves it)
+};
+
 constexpr int GEMM_NSW = 6;   // slabs per wave of the batched MFMA scan: rows up to 4 * 6 * 32 floats
 constexpr int GEMM_NSW_WIDE = 8;   // ... of the instantiation for wider rows (bf16 products): 1024 columns per K-chunk pass
 double coef_query(const as_query* q, bool exact);
 int gemm_chunks(int64_t dp, int64_t* chunk, bool bf16_products);
-PreArgs make_pre(as_query* q, double eps, int64_t exclude, bool enabled);
+PreArgs make_pre(as_query* q, const ScanRequest& rq, double eps, int64_t exclude, bool enabled);
 as_status launch_scan(as_query* q, const PreArgs& pre);
 bool scan_dual_ok(const as_query* a, const as_query* b);
 as_status launch_scan_dual(as_query* a, as_query* b, const PreArgs& pa, const PreArgs& pb, hipStream_t st);

@@ -2097,7 +2097,7 @@ double coef_query(const as_query* q, bool exact) {
     return (double)(dp / 64 + 24) * u;
 }
 
-PreArgs make_pre(as_query* q, double eps, int64_t exclude, bool enabled) {
+PreArgs make_pre(as_query* q, const ScanRequest& rq, double eps, int64_t exclude, bool enabled) {
     const as_space* sp = q->sp;
     PreArgs p;
     p.n32 = sp->n32; p.inorm32 = sp->inorm32; p.n64 = sp->n64; p.info = q->info; p.infow = q->info;
@@ -2118,17 +2118,17 @@ PreArgs make_pre(as_query* q, double eps, int64_t exclude, bool enabled) {
         p.nq32 = (float)q->h_nq; p.inq32 = q->h_nq > 0.0 ? (float)(1.0 / sqrt(q->h_nq)) : 0.0f;
         p.q64_host = q->hq_dev; p.q64_dev = q->q64; p.qdp = (int)sp->dp;
     }
-    if (q->fused_tail && enabled) {
+    if (rq.sc_ran && enabled) {
         // window of the cosine bound + slack for the fp32 cosine of the scan against the fp64-over-fp32-dot cosine of the
         // finish kernel's keys (a few ulp of fp32 each way)
         p.sc_enabled = 1;
         p.sc_m = q->Ms;
         // ... and for the scan's own error, twice: a cosine off by at most `coef` (the int8 image: 3e-4 .. 2e-3; fp32: 2e-6) both in
         // the rows that set the bound and in the row held against it
-        p.sc_w = (float)((1.0 - q->tau_cur) / (2.0 * q->tau_cur) + 2.0 * p.coef * 1.0001 + 1.0e-5);
+        p.sc_w = (float)((1.0 - rq.tau) / (2.0 * rq.tau) + 2.0 * p.coef * 1.0001 + 1.0e-5);
         p.sc_idx = q->sc_widx;
         p.sc_hist = q->sc_hist;
-        p.sc_late = q->sc_late;
+        p.sc_late = rq.sc_late;
         q->last_sc_m = p.sc_m;
         q->last_sc_w = p.sc_w;
 #ifdef AS_ABLATION   // measurement switches that return wrong answers exist in `make ABLATION=1` builds only

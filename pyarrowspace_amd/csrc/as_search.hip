@@ -2723,6 +2723,17 @@ static size_t finish_lds() {
     return (sizeof(T) + sizeof(int)) * (size_t)(CAND_CAP + PRUNE_CAP) + sizeof(double) * CAND_CAP + sizeof(double) * Q_LDS_MAX;
 }
 
+// groups of the threshold selections over the scanned rows: at most CAND_CAP groups of G rows, G a multiple of 64
+struct SelGroups {
+    int64_t rows, G;
+    int ng;
+};
+static SelGroups sel_groups(const as_query* q) {
+    const int64_t rows = q->r1 - q->r0;
+    const int64_t G = std::max<int64_t>(64, ((rows + CAND_CAP - 1) / CAND_CAP + 63) / 64 * 64);
+    return {rows, G, (int)((rows + G - 1) / G)};
+}
+
 // k-NN candidates of the scanned rows -> records (or row lists for the build fallback)
 // Second chance of a neighbourhood that overflowed the scan's candidate buffer (more than CAND_CAP rows inside
 // eps): the dots are still in HBM, so the candidates are re-derived by threshold -- the Mk-th smallest group
@@ -2730,10 +2741,7 @@ static size_t finish_lds() {
 template <typename T, typename U, int PASSES>
 static void launch_knn_repair(as_query* q, const T* dots, double eps, int64_t exclude) {
     hipStream_t st = q->stream;
-    const int64_t rows = q->r1 - q->r0;
-    int64_t G = (rows + CAND_CAP - 1) / CAND_CAP;
-    G = std::max<int64_t>(64, (G + 63) / 64 * 64);
-    const int ng = (int)((rows + G - 1) / G);
+    const auto [rows, G, ng] = sel_groups(q);
     SelArgs<T> a = make_sel<T>(q, dots, q->Mk, exclude);
     a.epskey = q->sp->opts.metric == AS_METRIC_L2 ? eps * eps : eps;
     a.coef = coef_query(q, sizeof(T) == 8);
@@ -2865,10 +2873,7 @@ static void launch_score(as_query* q, const T* dots, FinishArgs f, int fuse_fina
         f.ck = q->pkey; f.ci = q->pidx;
         hipLaunchKernelGGL((score_finish_kernel<T>), dim3(1), dim3(1024), score_lds<T>(), st, f, coef_s);
     } else {
-        const int64_t rows = q->r1 - q->r0;
-        int64_t G = (rows + CAND_CAP - 1) / CAND_CAP;
-        G = std::max<int64_t>(64, (G + 63) / 64 * 64);
-        const int ng = (int)((rows + G - 1) / G);
+        const auto [rows, G, ng] = sel_groups(q);
         SelArgs<T> a = make_sel<T>(q, dots, q->Ms, -1);
         a.dots32 = dots32;
         a.tau = f.tau;
@@ -2932,10 +2937,7 @@ static as_status run_score_sweep(as_query* q, const double* taus, int nt) {
     if (!q->bsw_ckey) AS_HIP(hipMalloc(&q->bsw_ckey, sizeof(double) * CAND_CAP * np));
     if (!q->bsw_cidx) AS_HIP(hipMalloc(&q->bsw_cidx, sizeof(int) * CAND_CAP * np));
     hipStream_t st = q->stream;
-    const int64_t rows = q->r1 - q->r0;
-    int64_t G = (rows + CAND_CAP - 1) / CAND_CAP;
-    G = std::max<int64_t>(64, (G + 63) / 64 * 64);
-    const int ng = (int)((rows + G - 1) / G);
+    const auto [rows, G, ng] = sel_groups(q);
     const int nb = q->nb;
     BatchSweep w;
     memset(&w, 0, sizeof(w));
@@ -3155,11 +3157,11 @@ namespace as {
 // and everything a search returns is re-evaluated behind it.
 static double gang_now_us() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-static as_status gang_launch(as_query* q, const PreArgs& pre) {
+static as_status gang_launch(as_query* q, const ScanRequest& rq, const PreArgs& pre) {
     const as_space* sp = q->sp;
     static const bool gang_off = getenv("ARROWSPACE_GANG") && atoi(getenv("ARROWSPACE_GANG")) == 0;
     static const double linger_us = getenv("ARROWSPACE_GANG_LINGER_US") ? atof(getenv("ARROWSPACE_GANG_LINGER_US")) : 60.0;
-    if (gang_off || !q->gang_ok || sp->gang_hint.load(std::memory_order_relaxed) <= 0) return launch_scan(q, pre);
+    if (gang_off || !rq.gang_ok || sp->gang_hint.load(std::memory_order_relaxed) <= 0) return launch_scan(q, pre);
     std::shared_ptr<as_gang> g;
     bool leader = false;
     {
@@ -3240,7 +3242,7 @@ static as_status gang_launch(as_query* q, const PreArgs& pre) {
 }
 
 static as_status query_begin(as_query* q, const double* query_host, int64_t src_row, int64_t d, int64_t r0, int64_t r1,
-                             double eps, int64_t exclude) {
+                             double eps, int64_t exclude, ScanRequest& rq) {
     const as_space* sp = q->sp;
     if (d != sp->d) {
         set_err("query length %lld must match nfeatures %lld", (long long)d, (long long)sp->d);
@@ -3267,7 +3269,7 @@ static as_status query_begin(as_query* q, const double* query_host, int64_t src_
     // and the idle gap behind it (6 + 5 us in front of every scan) are gone.
     static const bool no_hostq = getenv("ARROWSPACE_NO_HOSTQ") != nullptr;
     // Rows of 1025 .. 4096 floats: their int8 image is a row of at most 2048 image floats -- the same scan, when the image serves
-    // this query; otherwise the generic path below (and no fused tail: search_once reads q->fused_tail back).
+    // this query; otherwise the generic path below (and no fused tail: ScanRequest::sc_ran).
     const bool narrow = sp->dp <= 1024, wide8 = !narrow && (sp->dp + 63) / 64 * 64 <= 4096;
     bool host_path = query_host && q->cap == 1 && !q->exact && !feature && (narrow || wide8) && !(q->scan_variant & 4) && q->hq32 && !no_hostq;
     if (host_path) {
@@ -3286,7 +3288,7 @@ static as_status query_begin(as_query* q, const double* query_host, int64_t src_
         const char* coarse_env = getenv("ARROWSPACE_SCAN_COARSE");   // (per call: an A/B switch)
         const bool coarse_env_off = coarse_env && atoi(coarse_env) == 0;
         const bool coarse_always = coarse_env && atoi(coarse_env) == 2;   // (tests: probe with every search, whatever the last one did)
-        if (host_path && q->allow_coarse && !q->coarse_never && q->i8_scan && (q->fused_tail || q->chainc) && q->hq8h && !coarse_env_off && !q->robust && (!q->crowded_direct || q->chainc) && q->coef_i8h <= 4.0e-2 &&
+        if (host_path && rq.allow_coarse && !q->coarse_never && !rq.no_coarse && q->i8_scan && (rq.sc || rq.chainc) && q->hq8h && !coarse_env_off && !q->robust && (!rq.direct || rq.chainc) && q->coef_i8h <= 4.0e-2 &&
             (coarse_always || !(q->coarse_off > 0 && (q->coarse_off++ & 63) != 0))) {
             bool have = false;
             if (space_i8h_image(sp, &have) == AS_OK && have) {
@@ -3295,7 +3297,7 @@ static as_status query_begin(as_query* q, const double* query_host, int64_t src_
             }
         }
     }
-    if (!host_path && !narrow) q->fused_tail = 0;
+    rq.sc_ran = rq.sc && (host_path || narrow) ? 1 : 0;
     if (host_path) {
         q->host_q = 1;
         // (device memory: the scan copies the fp64 query there on its way, PreArgs::q64_dev -- an empty row range launches no scan)
@@ -3305,12 +3307,12 @@ static as_status query_begin(as_query* q, const double* query_host, int64_t src_
         if (!q->info_clean) hipLaunchKernelGGL(reset_info_kernel, dim3(1), dim3(64), 0, st, q->info, q->sc_hist);
         q->info_clean = 0;
         if (stats) AS_HIP(hipEventRecord(q->ev[0], st));
-        const PreArgs pre = make_pre(q, eps, exclude, !q->robust && !q->crowded_direct);
+        const PreArgs pre = make_pre(q, rq, eps, exclude, !q->robust && !rq.direct);
         // (a scan that may be shared with other callers': the coarse scan of a whole single space that collects scorer candidates,
         // nothing queued on this workspace's stream that the scan must follow, no per-launch timing asked for)
-        const int why = sp->gang_hint.load(std::memory_order_relaxed) <= 0 ? 0 : (!q->gang_ok || !pre.sc_enabled) ? 1 : !q->coarse ? 2 : !was_clean ? 3 : stats ? 4 : (r0 != 0 || r1 != sp->n) ? 5 : -1;
+        const int why = sp->gang_hint.load(std::memory_order_relaxed) <= 0 ? 0 : (!rq.gang_ok || !pre.sc_enabled) ? 1 : !q->coarse ? 2 : !was_clean ? 3 : stats ? 4 : (r0 != 0 || r1 != sp->n) ? 5 : -1;
         if (why < 0) {
-            AS_TRY(gang_launch(q, pre));
+            AS_TRY(gang_launch(q, rq, pre));
         } else {
             if (q->cap == 1) sp->gang_skip[why].fetch_add(1, std::memory_order_relaxed);
             AS_TRY(launch_scan(q, pre));
@@ -3338,9 +3340,9 @@ static as_status query_begin(as_query* q, const double* query_host, int64_t src_
         hipLaunchKernelGGL(q_quant_batch_kernel, dim3((unsigned)q->cap), dim3(256), 0, st, (const float*)q->q32, sp->dp, sp->dp8, q->q8img_dev, q->faqv_dev,
                            (const QInfo*)q->info, q->hx8stat_dev);
     if (stats) AS_HIP(hipEventRecord(q->ev[0], st));
-    const PreArgs pre = make_pre(q, eps, exclude, !q->robust && !feature && !q->crowded_direct);
-    if (q->defer_pre) {   // (a batched pass that may share its scan with the other workspace of its pair: search_batch_launch_pair)
-        *q->defer_pre = pre;
+    const PreArgs pre = make_pre(q, rq, eps, exclude, !q->robust && !feature && !rq.direct);
+    if (rq.defer_pre) {   // (a batched pass that may share its scan with the other workspace of its pair: batch_launch_pair)
+        *rq.defer_pre = pre;
         q->ev_valid = 0;
         return AS_OK;
     }
@@ -3688,13 +3690,12 @@ as_status as_query_scan(as_query* q, const double* query_host, int64_t d, int64_
     // scorer's candidates by its cosine bound, as on one GPU (search_once), and ONE kernel does the step between the two
     // exchanges (staged_score_kernel).
     const bool sc = q->staged_tau >= 0.4 && q->staged_tau <= 1.0 && q->gr->lambda_mode != AS_LAMBDA_FEATURE && !q->robust && !q->exact &&
-                    !q->no_fused && q->cap == 1 && q->sc_widx && q->sp->dp <= 4096 && !(q->scan_variant & 4) && !q->crowded_direct;
-    q->fused_tail = sc ? 1 : 0;
-    q->tau_cur = q->staged_tau;
-    const as_status qb = query_begin(q, query_host, -1, d, row_begin, row_end, q->gr->gp.eps, -1);
-    const bool sc_ran = q->fused_tail != 0;   // (rows of 1025 .. 4096 floats: only when the int8 image served the scan)
-    q->fused_tail = 0;
-    q->staged_sc = sc_ran && qb == AS_OK && row_end > row_begin ? 1 : 0;
+                    !q->no_fused && q->cap == 1 && q->sc_widx && q->sp->dp <= 4096 && !(q->scan_variant & 4);
+    ScanRequest rq;
+    rq.sc = sc ? 1 : 0;
+    rq.tau = q->staged_tau;
+    const as_status qb = query_begin(q, query_host, -1, d, row_begin, row_end, q->gr->gp.eps, -1, rq);
+    q->staged_sc = rq.sc_ran && qb == AS_OK && row_end > row_begin ? 1 : 0;
     AS_TRY(qb);
     if (q->gr->lambda_mode == AS_LAMBDA_FEATURE) return AS_OK;   // lambda_q is already there; the k-NN records stay empty
     return run_knn(q, q->gr->gp.eps, -1, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, q->coarse);
@@ -3793,10 +3794,7 @@ static as_status coarse_score_stage(as_query* q, void* block, double tau) {
     hipStream_t st = q->stream;
     hipLaunchKernelGGL(q_lambda_kernel, dim3(1), dim3(64), 0, st, (const as_knn_rec*)block, krec, krec, krec, q->k, gr->metric, gr->kernel, gr->gp.sigma,
                        gr->gp.p, gr->tau0, q->info, 1);
-    const int64_t rows = q->r1 - q->r0;
-    int64_t G = (rows + CAND_CAP - 1) / CAND_CAP;
-    G = std::max<int64_t>(64, (G + 63) / 64 * 64);
-    const int ng = (int)((rows + G - 1) / G);
+    const auto [rows, G, ng] = sel_groups(q);
     SelArgs<double> a = make_sel<double>(q, (const double*)nullptr, q->Ms, -1);
     a.dots32 = q->dots32;
     a.tau = tau;
@@ -3829,19 +3827,14 @@ as_status as_query_x1_begin(as_query* q, const double* query_host, int64_t d, in
     if (q->x1_dirty || q->x1_head != head) AS_HIP(hipMemsetAsync(head, 0, sizeof(XHead), q->stream));
     q->x1_dirty = 1;
     q->x1_head = head;
-    const bool sc = !q->no_fused && q->sc_widx && sp->dp <= 4096 && !(q->scan_variant & 4) && !q->crowded_direct;
-    q->fused_tail = sc ? 1 : 0;
-    q->tau_cur = tau;
-    q->allow_coarse = sc ? 1 : 0;   // (the block kernels evaluate every k-NN candidate of a coarse scan: x1_launch_block, exact_knn)
-    q->sc_late = sc ? 1 : 0;
-    const as_status qb = query_begin(q, query_host, -1, d, row_begin, row_end, q->gr->gp.eps, -1);
-    q->allow_coarse = 0;
-    q->sc_late = 0;
-    const bool sc_ran = q->fused_tail != 0;   // (rows of 1025 .. 4096 floats: only when the int8 image served the scan)
-    q->fused_tail = 0;
+    const bool sc = !q->no_fused && q->sc_widx && sp->dp <= 4096 && !(q->scan_variant & 4);
+    ScanRequest rq;
+    rq.sc = rq.sc_late = sc ? 1 : 0;
+    rq.tau = tau;
+    rq.allow_coarse = sc ? 1 : 0;   // (the block kernels evaluate every k-NN candidate of a coarse scan: x1_launch_block, exact_knn)
     q->staged_sc = 0;
-    AS_TRY(qb);
-    return x1_launch_block(q, send_dev, world, sc_ran, q->coarse != 0);
+    AS_TRY(query_begin(q, query_host, -1, d, row_begin, row_end, q->gr->gp.eps, -1, rq));
+    return x1_launch_block(q, send_dev, world, rq.sc_ran != 0, q->coarse != 0);
 }
 
 as_status as_query_x1_finish(as_query* q, const void* all_dev, int32_t world, double tau, int64_t* out_idx, double* out_score, int64_t* out_len,
@@ -3955,7 +3948,8 @@ as_status as_query_scan_batch(as_query* q, const double* queries_host, int32_t n
     }
     q->nb = nb;
     q->batch_assume = 0;
-    AS_TRY(query_begin(q, queries_host, -1, d, row_begin, row_end, q->gr->gp.eps, -1));
+    ScanRequest rq;
+    AS_TRY(query_begin(q, queries_host, -1, d, row_begin, row_end, q->gr->gp.eps, -1, rq));
     if (q->gr->lambda_mode == AS_LAMBDA_FEATURE) return AS_OK;
     q->nb = q->cap;   // idle slots get empty records too: the gathered buffers are read slot by slot
     const as_status s = run_knn(q, q->gr->gp.eps, -1, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
@@ -4067,9 +4061,53 @@ void query_flags(const as_query* q, int* knn_inexact, int* score_inexact) {
 int query_overflow_bits(const as_query* q) { return q->hout->overflow; }
 extern "C" int32_t as_query_scan_int8(const as_query* q) { return q ? (q->i8_scan ? 1 + q->coarse : 0) : 0; }   // 0 fp32 items, 1 the int8 image, 2 its high digits alone (coarse scan)   // bit0 k-NN candidates, bit1 scorer's, bit2 the scan's scorer candidates
 
-// one full single-GPU search on q's stream: 6 launches, one host wait
-as_status search_once(as_query* q, const double* query, int64_t d, double tau, int mode, int64_t* out_idx, double* out_score,
-                      int64_t* out_len, double* out_lambda_q) {
+// ARROWSPACE_FUSED_X1=0: the fused tail as ONE launch (fused_finish_kernel), no coarse scan; ARROWSPACE_COARSE_CHAIN=0: no coarse chain
+// (A/B switches, read once per process)
+static bool fused_x1_on() {
+    static const char* e = getenv("ARROWSPACE_FUSED_X1");
+    static const bool on = !(e && atoi(e) == 0);
+    return on;
+}
+static bool chainc_on() {
+    static const char* e = getenv("ARROWSPACE_COARSE_CHAIN");
+    static const bool on = !(e && atoi(e) == 0);
+    return on;
+}
+
+// the block of the fused tail's two-kernel form and of the coarse chain (q->x1_own), its header at zero: behind the scan, in front
+// of the block kernels
+static as_status x1_own_prepare(as_query* q) {
+    if (!q->x1_own) {
+        AS_HIP(hipMalloc(&q->x1_own, (size_t)as_query_x1_bytes(q, 1)));
+        AS_HIP(hipMemsetAsync(q->x1_own, 0, (size_t)as_query_x1_bytes(q, 1), q->stream));
+    } else if (q->x1_dirty) {
+        AS_HIP(hipMemsetAsync(q->x1_own + sizeof(as_knn_rec) * std::max<int64_t>(q->k, 1), 0, 16, q->stream));
+    }
+    return AS_OK;
+}
+
+// the scan's scorer candidates did not fit: lambda_q stands, the scorer runs on the threshold chain over the kept dots
+static as_status rescore_on_chain(as_query* q, double tau) {
+    AS_HIP(hipMemsetAsync(&q->info->sc_cnt, 0, sizeof(int), q->stream));
+    AS_HIP(hipMemsetAsync(&q->info->overflow, 0, sizeof(int), q->stream));
+    q->seq += 1;
+    AS_TRY(run_score(q, tau, 1));
+    return wait_published(q);
+}
+
+// the workspace's path hints behind a coarse chain (search_once, search_sweep): ov = the overflow bits of what it published,
+// clean = every list was served.  A k-NN buffer that alone did not fit sends the next search of the crowded neighbourhood to the
+// threshold repair; anything else that was not served sends the next 63 searches past the chain.
+static void chain_hints(as_query* q, bool direct, int ov, bool clean) {
+    if (!direct) q->crowded = (ov & 1) ? 1 : 0;
+    if (clean) q->chainc_off = 0;
+    else if (!(!direct && (ov & 1) && !(ov & 6))) q->chainc_off = 1;
+}
+
+// one full single-GPU search on q's stream: 6 launches, one host wait.  no_coarse: the redo of a query the coarse scan did not
+// serve -- this call scans the two-digit image, whatever the switches say
+static as_status search_run(as_query* q, const double* query, int64_t d, double tau, int mode, int64_t* out_idx, double* out_score,
+                            int64_t* out_len, double* out_lambda_q, bool no_coarse) {
     q->exact = (mode & 1) || q->sp->opts.force_exact;
     q->robust = (mode & 2) ? 1 : 0;
     const bool feature = q->gr->lambda_mode == AS_LAMBDA_FEATURE;
@@ -4078,7 +4116,6 @@ as_status search_once(as_query* q, const double* query, int64_t d, double tau, i
     // and derive their neighbours from the dots by threshold straight away -- not a whole selection chain and a host
     // wait later.  Every 64th query probes the plain path again.
     const bool direct = !feature && !q->robust && q->crowded > 0 && (q->crowded++ & 63) != 0;
-    q->crowded_direct = direct ? 1 : 0;
     // Fused tail: the scan collects the scorer's candidates by a cosine bound and ONE kernel finishes the query.  The
     // bound's window is (1 - tau) / (2 tau) wide in cosine: pointless below tau = 0.4 (every row would qualify).  A query
     // whose candidates overflow the buffer falls back to the threshold chain over the kept dots, and the following 63
@@ -4086,45 +4123,34 @@ as_status search_once(as_query* q, const double* query, int64_t d, double tau, i
     const bool sc_skip = q->sc_crowded > 0 && (q->sc_crowded++ & 63) != 0;
     const bool want_fused = !feature && !q->robust && !q->exact && !direct && !q->no_fused && !sc_skip && q->cap == 1 && tau >= 0.4 && tau <= 1.0 &&
                             q->sp->dp <= 4096 && !(q->scan_variant & 4);
-    q->fused_tail = want_fused ? 1 : 0;
-    q->tau_cur = tau;
-    static const bool fused_x1_on = !(getenv("ARROWSPACE_FUSED_X1") && atoi(getenv("ARROWSPACE_FUSED_X1")) == 0);
     // Coarse chain: what the fused tail cannot serve -- tau below 0.4, scorer candidates that overflowed lately (sc_skip), crowded
     // neighbourhoods (direct) -- still scans the one-byte image: no scan-side scorer candidates, k-NN candidates from the scan's
     // prefilter or (direct) by threshold over the kept dots, the scorer's by threshold over the kept dots once lambda_q is known,
     // everything evaluated exactly by the tail's blocks (coarse_score_stage).  A query it does not serve cleanly is redone on the
     // two-digit image through the proof-carrying chain, and the next 63 skip it.
-    static const bool chainc_on = !(getenv("ARROWSPACE_COARSE_CHAIN") && atoi(getenv("ARROWSPACE_COARSE_CHAIN")) == 0);
+    const bool coarse_never = q->coarse_never || no_coarse;
     const bool chainc_skip = q->chainc_off > 0 && (q->chainc_off++ & 63) != 0;
-    const bool want_chainc = chainc_on && fused_x1_on && !want_fused && !feature && !q->robust && !q->exact && !q->no_fused && q->cap == 1 && tau >= 0.0 && tau <= 1.0 &&
-                             q->sp->dp <= 4096 && !(q->scan_variant & 4) && !chainc_skip && !q->coarse_never && (int64_t)std::max<int64_t>(q->k, 1) <= REC_CAP;
-    q->chainc = want_chainc ? 1 : 0;
-    q->allow_coarse = (want_fused || want_chainc) && fused_x1_on ? 1 : 0;   // (the coarse scan needs the two-launch tail: its k-NN candidates are evaluated by all blocks)
-    q->gang_ok = want_fused && fused_x1_on ? 1 : 0;
-    q->sc_late = want_fused && fused_x1_on ? 1 : 0;   // (the two-launch tail validates lossy wave reports against the final histogram)
+    const bool want_chainc = chainc_on() && fused_x1_on() && !want_fused && !feature && !q->robust && !q->exact && !q->no_fused && q->cap == 1 && tau >= 0.0 && tau <= 1.0 &&
+                             q->sp->dp <= 4096 && !(q->scan_variant & 4) && !chainc_skip && !coarse_never && (int64_t)std::max<int64_t>(q->k, 1) <= REC_CAP;
+    ScanRequest rq;
+    rq.sc = want_fused ? 1 : 0;
+    rq.tau = tau;
+    rq.direct = direct ? 1 : 0;
+    rq.no_coarse = no_coarse ? 1 : 0;
+    rq.chainc = want_chainc ? 1 : 0;
+    rq.allow_coarse = (want_fused || want_chainc) && fused_x1_on() ? 1 : 0;   // (the coarse scan needs the two-launch tail: its k-NN candidates are evaluated by all blocks)
+    rq.gang_ok = rq.sc_late = want_fused && fused_x1_on() ? 1 : 0;   // (the two-launch tail validates lossy wave reports against the final histogram)
     // (ARROWSPACE_HOST_TIMING=1: host microseconds of the fused path's parts -- preparation + scan launch, the two tail launches,
     // the wait for the publication -- averaged over 200 searches, on stderr)
     static const bool host_timing = getenv("ARROWSPACE_HOST_TIMING") != nullptr;
     auto now_us = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double ht0 = host_timing ? now_us() : 0.0;
-    const as_status qb = query_begin(q, query, -1, d, 0, q->sp->n, q->gr->gp.eps, -1);
+    AS_TRY(query_begin(q, query, -1, d, 0, q->sp->n, q->gr->gp.eps, -1, rq));
     const double ht1 = host_timing ? now_us() : 0.0;
-    q->allow_coarse = 0;
-    q->gang_ok = 0;
-    q->sc_late = 0;
-    const bool fused = q->fused_tail != 0;   // (rows of 1025 .. 4096 floats: only when the int8 image served the scan)
-    const bool chainc = q->chainc && q->coarse;   // (the coarse scan did serve this query's scan)
-    q->chainc = 0;
-    q->crowded_direct = 0;
-    q->fused_tail = 0;
-    AS_TRY(qb);
+    const bool fused = rq.sc_ran != 0;
+    const bool chainc = rq.chainc && q->coarse;   // (the coarse scan did serve this query's scan)
     if (chainc) {
-        if (!q->x1_own) {
-            AS_HIP(hipMalloc(&q->x1_own, (size_t)as_query_x1_bytes(q, 1)));
-            AS_HIP(hipMemsetAsync(q->x1_own, 0, (size_t)as_query_x1_bytes(q, 1), q->stream));
-        } else if (q->x1_dirty) {
-            AS_HIP(hipMemsetAsync(q->x1_own + sizeof(as_knn_rec) * std::max<int64_t>(q->k, 1), 0, 16, q->stream));
-        }
+        AS_TRY(x1_own_prepare(q));
         q->x1_dirty = 1;
         q->seq += 1;
         if (direct) AS_TRY(knn_repair(q, q->gr->gp.eps, -1));   // (crowded neighbourhood: the k-NN candidates by threshold over the kept dots)
@@ -4135,19 +4161,13 @@ as_status search_once(as_query* q, const double* query, int64_t d, double tau, i
         AS_TRY(wait_published(q));
         q->x1_dirty = 0;
         q->xknn_dirty = 0;
-        if (!direct) q->crowded = (q->hout->overflow & 1) ? 1 : 0;
-        if (q->hout->overflow || q->hout->knn_inexact || q->hout->score_inexact) {
-            // not served cleanly (a candidate list that did not fit): this query again without the coarse chain -- the next search
-            // of a crowded neighbourhood takes the threshold repair (crowded, above), anything else sends the next 63 past it
+        const bool clean = !(q->hout->overflow || q->hout->knn_inexact || q->hout->score_inexact);
+        chain_hints(q, direct, q->hout->overflow, clean);
+        if (!clean) {   // (a candidate list that did not fit): this query again without the coarse chain
             dbg("coarse chain: overflow bits %d (coefficient %.3e) -> this search again on the two-digit image", q->hout->overflow, q->coef_i8h);
-            if (!(!direct && (q->hout->overflow & 1) && !(q->hout->overflow & 6))) q->chainc_off = 1;
-            q->coarse_never = 1;
             q->info_clean = 0;
-            const as_status redo = search_once(q, query, d, tau, mode, out_idx, out_score, out_len, out_lambda_q);
-            q->coarse_never = 0;
-            return redo;
+            return search_run(q, query, d, tau, mode, out_idx, out_score, out_len, out_lambda_q, true);
         }
-        q->chainc_off = 0;
         q->info_clean = q->hout->state_reset ? 1 : 0;
         return collect(q, out_idx, out_score, out_len, out_lambda_q);
     }
@@ -4156,14 +4176,8 @@ as_status search_once(as_query* q, const double* query, int64_t d, double tau, i
     // instead of the one 1024-thread block that does the phases one after the other (fused_finish_kernel, ARROWSPACE_FUSED_X1=0).
     // Same box, interleaved (tools/fused_x1_ab.sh): 1M x 768 3 240-3 268 -> 3 340 queries/s, 400k x 384 k = 4 topk = 2 9 560-9 590 ->
     // 10 950-11 120, 200k x 768 8 620-8 720 -> 8 620-8 660.
-    static const bool fused_x1 = !(getenv("ARROWSPACE_FUSED_X1") && atoi(getenv("ARROWSPACE_FUSED_X1")) == 0);
-    if (fused && fused_x1 && (int64_t)std::max<int64_t>(q->k, 1) <= REC_CAP) {
-        if (!q->x1_own) {
-            AS_HIP(hipMalloc(&q->x1_own, (size_t)as_query_x1_bytes(q, 1)));
-            AS_HIP(hipMemsetAsync(q->x1_own, 0, (size_t)as_query_x1_bytes(q, 1), q->stream));
-        } else if (q->x1_dirty) {
-            AS_HIP(hipMemsetAsync(q->x1_own + sizeof(as_knn_rec) * std::max<int64_t>(q->k, 1), 0, 16, q->stream));   // (behind the scan, in front of the block kernels)
-        }
+    if (fused && fused_x1_on() && (int64_t)std::max<int64_t>(q->k, 1) <= REC_CAP) {
+        AS_TRY(x1_own_prepare(q));
         q->x1_dirty = 1;
         q->seq += 1;
         AS_TRY(x1_launch_block(q, q->x1_own, 1, true, q->coarse != 0));
@@ -4188,7 +4202,7 @@ as_status search_once(as_query* q, const double* query, int64_t d, double tau, i
         }
         q->x1_dirty = 0;
         q->xknn_dirty = 0;
-        if (q->coarse && (q->hout->overflow & 5) && chainc_on && !chainc_skip && !q->coarse_never) {
+        if (q->coarse && (q->hout->overflow & 5) && chainc_on() && !chainc_skip && !coarse_never) {
             // the scan's candidate lists did not fit -- a neighbourhood of more than 4 096 rows (bit 0), a cosine window that takes in
             // too many rows (bit 2): this query again as a coarse chain, which derives those lists from the kept dots by threshold;
             // the next 63 searches go there directly
@@ -4196,7 +4210,7 @@ as_status search_once(as_query* q, const double* query, int64_t d, double tau, i
             if (q->hout->overflow & 1) q->crowded = 1;
             if (q->hout->overflow & 4) q->sc_crowded = 1;
             q->info_clean = 0;
-            return search_once(q, query, d, tau, mode, out_idx, out_score, out_len, out_lambda_q);
+            return search_run(q, query, d, tau, mode, out_idx, out_score, out_len, out_lambda_q, no_coarse);
         }
         if (q->coarse && (q->hout->overflow & 5)) {
             // the coarse scan's candidates did not fit (its wider windows took in too many rows): the same query on the two-digit
@@ -4205,21 +4219,12 @@ as_status search_once(as_query* q, const double* query, int64_t d, double tau, i
                 "with an overflowed wave report %d, k-NN candidates %d) -> the two-digit scan for this and the next 63 searches",
                 q->hout->overflow, q->coef_i8h, q->hout->pad_ & 0xffff, (q->hout->pad_ >> 16) & 0xff, (q->hout->pad_ >> 24) & 0xff, 0);
             q->coarse_off = 1;
-            q->coarse_never = 1;   // (for the call below, whatever the switches say: it must not come back here)
             q->info_clean = 0;
-            const as_status redo = search_once(q, query, d, tau, mode, out_idx, out_score, out_len, out_lambda_q);
-            q->coarse_never = 0;
-            return redo;
+            return search_run(q, query, d, tau, mode, out_idx, out_score, out_len, out_lambda_q, true);   // (no_coarse: it must not come back here)
         }
         q->crowded = (q->hout->overflow & 1) ? 1 : 0;
         q->sc_crowded = (q->hout->overflow & 4) ? 1 : 0;
-        if ((q->hout->overflow & 4) && !(q->hout->overflow & 1) && !q->hout->knn_inexact) {
-            AS_HIP(hipMemsetAsync(&q->info->sc_cnt, 0, sizeof(int), q->stream));
-            AS_HIP(hipMemsetAsync(&q->info->overflow, 0, sizeof(int), q->stream));
-            q->seq += 1;
-            AS_TRY(run_score(q, tau, 1));
-            AS_TRY(wait_published(q));
-        }
+        if ((q->hout->overflow & 4) && !(q->hout->overflow & 1) && !q->hout->knn_inexact) AS_TRY(rescore_on_chain(q, tau));
     } else if (fused) {
         q->seq += 1;
         AS_TRY(run_fused(q, q->gr->gp.eps, tau));
@@ -4227,14 +4232,7 @@ as_status search_once(as_query* q, const double* query, int64_t d, double tau, i
         AS_TRY(wait_published(q));
         q->crowded = (q->hout->overflow & 1) ? 1 : 0;
         q->sc_crowded = (q->hout->overflow & 4) ? 1 : 0;
-        if ((q->hout->overflow & 4) && !(q->hout->overflow & 1) && !q->hout->knn_inexact) {
-            // the scan's scorer candidates did not fit: lambda_q stands, the scorer runs on the threshold chain
-            AS_HIP(hipMemsetAsync(&q->info->sc_cnt, 0, sizeof(int), q->stream));
-            AS_HIP(hipMemsetAsync(&q->info->overflow, 0, sizeof(int), q->stream));
-            q->seq += 1;
-            AS_TRY(run_score(q, tau, 1));
-            AS_TRY(wait_published(q));
-        }
+        if ((q->hout->overflow & 4) && !(q->hout->overflow & 1) && !q->hout->knn_inexact) AS_TRY(rescore_on_chain(q, tau));
     } else if (direct) {
         AS_TRY(knn_repair(q, q->gr->gp.eps, -1));
         AS_TRY(run_knn(q, q->gr->gp.eps, -1, 1, nullptr, nullptr, nullptr, nullptr, nullptr, 1));
@@ -4272,6 +4270,11 @@ as_status search_once(as_query* q, const double* query, int64_t d, double tau, i
                                q->hout->overflow, q->hout->knn_inexact, q->hout->score_inexact, q->coef_i8h);
     }
     return collect(q, out_idx, out_score, out_len, out_lambda_q);
+}
+
+as_status search_once(as_query* q, const double* query, int64_t d, double tau, int mode, int64_t* out_idx, double* out_score,
+                      int64_t* out_len, double* out_lambda_q) {
+    return search_run(q, query, d, tau, mode, out_idx, out_score, out_len, out_lambda_q, false);
 }
 
 // ------------------------------------------------------------------ tau sweep: one pass over the items for up to TAU_GROUP taus
@@ -4566,36 +4569,20 @@ as_status search_sweep(as_query* q, const double* query, int64_t d, const double
     }
     const as_space* sp = q->sp;
     const as_graph* gr = q->gr;
-    static const bool fused_x1_on = !(getenv("ARROWSPACE_FUSED_X1") && atoi(getenv("ARROWSPACE_FUSED_X1")) == 0);
-    static const bool chainc_on = !(getenv("ARROWSPACE_COARSE_CHAIN") && atoi(getenv("ARROWSPACE_COARSE_CHAIN")) == 0);
-    if (!chainc_on || !fused_x1_on || gr->lambda_mode == AS_LAMBDA_FEATURE || sp->opts.force_exact || (sp->opts.search_mode & 3) || q->no_fused ||
+    if (!chainc_on() || !fused_x1_on() || gr->lambda_mode == AS_LAMBDA_FEATURE || sp->opts.force_exact || (sp->opts.search_mode & 3) || q->no_fused ||
         q->cap != 1 || sp->dp > 4096 || (q->scan_variant & 4) || std::max<int64_t>(q->k, 1) > REC_CAP || q->topk > lstride)
         return AS_OK;
     if (q->chainc_off > 0 && (q->chainc_off++ & 63) != 0) return AS_OK;   // (a recent coarse chain was not served cleanly)
     q->exact = 0;
     q->robust = 0;
     const bool direct = q->crowded > 0 && (q->crowded++ & 63) != 0;   // (search_once: a crowded neighbourhood)
-    q->crowded_direct = direct ? 1 : 0;
-    q->fused_tail = 0;
-    q->tau_cur = taus[0];
-    q->chainc = 1;
-    q->allow_coarse = 1;
-    q->gang_ok = 0;
-    q->sc_late = 0;
-    const as_status qb = query_begin(q, query, -1, d, 0, sp->n, gr->gp.eps, -1);
-    q->allow_coarse = 0;
-    q->crowded_direct = 0;
-    const bool chainc = q->chainc && q->coarse;
-    q->chainc = 0;
-    AS_TRY(qb);
-    if (!chainc) return AS_OK;   // (the scan ran on another operand: its state is reset in front of the next one, info_clean = 0)
+    ScanRequest rq;
+    rq.direct = direct ? 1 : 0;
+    rq.chainc = rq.allow_coarse = 1;
+    AS_TRY(query_begin(q, query, -1, d, 0, sp->n, gr->gp.eps, -1, rq));
+    if (!q->coarse) return AS_OK;   // (the scan ran on another operand: its state is reset in front of the next one, info_clean = 0)
     const int64_t krec = std::max<int64_t>(q->k, 1);
-    if (!q->x1_own) {
-        AS_HIP(hipMalloc(&q->x1_own, (size_t)as_query_x1_bytes(q, 1)));
-        AS_HIP(hipMemsetAsync(q->x1_own, 0, (size_t)as_query_x1_bytes(q, 1), q->stream));
-    } else if (q->x1_dirty) {
-        AS_HIP(hipMemsetAsync(q->x1_own + sizeof(as_knn_rec) * krec, 0, 16, q->stream));
-    }
+    AS_TRY(x1_own_prepare(q));
     if (!q->swout) {
         AS_HIP(hipHostMalloc(&q->swout, sizeof(HostOut) * TAU_GROUP, hipHostMallocMapped | hipHostMallocCoherent));
         AS_HIP(hipHostGetDevicePointer((void**)&q->swout_dev, q->swout, 0));
@@ -4612,10 +4599,7 @@ as_status search_sweep(as_query* q, const double* query, int64_t d, const double
     hipLaunchKernelGGL(q_lambda_kernel, dim3(1), dim3(64), 0, st, (const as_knn_rec*)q->x1_own, krec, krec, krec, q->k, gr->metric, gr->kernel,
                        gr->gp.sigma, gr->gp.p, gr->tau0, q->info, 1);
     // the union of the nt threshold filters (coarse_score_stage's groups, threshold rank and margins, per tau)
-    const int64_t rows = q->r1 - q->r0;
-    int64_t G = (rows + CAND_CAP - 1) / CAND_CAP;
-    G = std::max<int64_t>(64, (G + 63) / 64 * 64);
-    const int ng = (int)((rows + G - 1) / G);
+    const auto [rows, G, ng] = sel_groups(q);
     SweepSel a;
     a.s = make_sel<double>(q, (const double*)nullptr, q->Ms, -1);
     a.s.dots32 = q->dots32;
@@ -4651,10 +4635,7 @@ as_status search_sweep(as_query* q, const double* query, int64_t d, const double
         ov |= h->overflow;
         all_clean = all_clean && !h->overflow && !h->knn_inexact && !h->score_inexact;
     }
-    // (search_once's rules behind a coarse chain)
-    if (!direct) q->crowded = (ov & 1) ? 1 : 0;
-    if (all_clean) q->chainc_off = 0;
-    else if (!(!direct && (ov & 1) && !(ov & 6))) q->chainc_off = 1;
+    chain_hints(q, direct, ov, all_clean);
     q->info_clean = q->swout[0].state_reset ? 1 : 0;
     if (out_lambda_q) *out_lambda_q = q->swout[0].lambda_q;
     if (all_clean && q->swout[0].status == AS_EZEROLAMBDA) {
@@ -4690,7 +4671,8 @@ static as_status batch_pass_head(as_query* q, const double* queries, int nb, int
     q->robust = 0;
     q->nb = nb;
     q->batch_assume = 1;
-    AS_TRY(query_begin(q, queries, -1, d, 0, q->sp->n, q->gr->gp.eps, -1));
+    ScanRequest rq;
+    AS_TRY(query_begin(q, queries, -1, d, 0, q->sp->n, q->gr->gp.eps, -1, rq));
     if (q->gr->lambda_mode != AS_LAMBDA_FEATURE) AS_TRY(run_knn(q, q->gr->gp.eps, -1, 1, nullptr, nullptr, nullptr, nullptr, nullptr));
     q->seq += 1;
     return AS_OK;
@@ -4718,10 +4700,9 @@ static as_status batch_launch_pair(as_query* a, as_query* b, const double* qa, i
         q->robust = 0;
         q->nb = nbs[s];
         q->batch_assume = 1;
-        q->defer_pre = &pre[s];
-        const as_status st = query_begin(q, qs[s], -1, d, 0, q->sp->n, q->gr->gp.eps, -1);
-        q->defer_pre = nullptr;
-        AS_TRY(st);
+        ScanRequest rq;
+        rq.defer_pre = &pre[s];
+        AS_TRY(query_begin(q, qs[s], -1, d, 0, q->sp->n, q->gr->gp.eps, -1, rq));
     }
     // (Measured and dropped, profiles/r05_batch_dual.txt: this pair's scan ordered behind the other pair's selection and finish
     // kernels -- they starve beside a scan that holds every CU's LDS and registers --: 117 700 against 129 700 queries/s; the scan
@@ -4752,19 +4733,23 @@ as_status search_batch_launch_pair(as_query* a, as_query* b, const double* qa, i
     return batch_launch_pair(a, b, qa, nba, qb, nbb, d, [tau](as_query* q) { return run_score(q, tau, 1); });
 }
 
-as_status search_batch_collect(as_query* q, int nb, double tau, int64_t topk, int64_t* out_idx, double* out_score, int64_t* out_len,
-                               double* out_lambda_q, int32_t* out_status) {
-    bool crowded = false;
-    for (int b = 0; b < nb; ++b) {
-        AS_TRY(wait_published(q, b));
-        crowded = crowded || (q->hout[b].overflow & 1);
-    }
-    if (crowded && !q->dots_half) {   // (fp16 cosines cannot repair a neighbourhood: those slots go to the single-query path below)
+// A batched pass collected, parameterised as batch_launch_pair is.  tail(q): the pass's scorer tail again; wait(): for everything
+// the tail publishes; crowded(b): slot b's neighbourhood overflowed its candidate buffer; out(b, priced): slot b's results and
+// status -- -1 where the slot goes to the single-query path (its own flags, or a pass whose int8 pricing did not hold).
+static bool slot_unproven(const HostOut* h) { return h->overflow || h->knn_inexact || h->score_inexact; }
+
+template <typename Tail, typename Wait, typename Crowded, typename Out>
+static as_status batch_collect(as_query* q, int nb, Tail tail, Wait wait, Crowded crowded, Out out) {
+    AS_TRY(wait());
+    bool any = false;
+    for (int b = 0; b < nb; ++b) any = any || crowded(b);
+    if (any && !q->dots_half) {   // (fp16 cosines cannot repair a neighbourhood: those slots go to the single-query path)
         // some neighbourhood overflowed its candidate buffer: threshold repair of every slot over the kept dots
         AS_TRY(knn_repair(q, q->gr->gp.eps, -1));
         AS_TRY(run_knn(q, q->gr->gp.eps, -1, 1, nullptr, nullptr, nullptr, nullptr, nullptr, 1));
         q->seq += 1;
-        AS_TRY(run_score(q, tau, 1));
+        AS_TRY(tail(q));
+        AS_TRY(wait());
     }
     // (int8 pass: its error was priced with ASSUMED residue norms of the queries -- hold the measured ones against them)
     const bool held = q->i8_scan && q->cap > 1 ? batch_coef_holds(q) : true;   // (always: the space's estimate follows the measurements)
@@ -4772,27 +4757,34 @@ as_status search_batch_collect(as_query* q, int nb, double tau, int64_t topk, in
     if (!priced && !q->x8_nan && q->batch_assume == 1) {
         // the assumption did not hold: ONE more pass over the same slots (their queries are still staged in this workspace's
         // pinned buffer), priced with the measured values -- not 32 single-query searches
+        ScanRequest rq;
         q->batch_assume = 2;
-        const as_status s2 = query_begin(q, q->hq, -1, q->sp->d, 0, q->sp->n, q->gr->gp.eps, -1);
+        const as_status s2 = query_begin(q, q->hq, -1, q->sp->d, 0, q->sp->n, q->gr->gp.eps, -1, rq);
         q->batch_assume = 1;
         AS_TRY(s2);
         if (q->gr->lambda_mode != AS_LAMBDA_FEATURE) AS_TRY(run_knn(q, q->gr->gp.eps, -1, 1, nullptr, nullptr, nullptr, nullptr, nullptr));
         q->seq += 1;
-        AS_TRY(run_score(q, tau, 1));
-        for (int b = 0; b < nb; ++b) AS_TRY(wait_published(q, b));
+        AS_TRY(tail(q));
+        AS_TRY(wait());
         priced = !(q->i8_scan && q->cap > 1) || batch_coef_holds(q) || !q->x8_verify;
     }
-    for (int b = 0; b < nb; ++b) {
-        AS_TRY(wait_published(q, b));
-        const HostOut* h = q->hout + b;
-        if (h->overflow || h->knn_inexact || h->score_inexact || !priced) {
-            out_status[b] = -1;
-            continue;
-        }
-        const as_status s = collect(q, out_idx + b * topk, out_score + b * topk, out_len + b, out_lambda_q ? out_lambda_q + b : nullptr, b);
-        out_status[b] = (int32_t)s;
-    }
+    for (int b = 0; b < nb; ++b) out(b, priced);
     return AS_OK;
+}
+
+as_status search_batch_collect(as_query* q, int nb, double tau, int64_t topk, int64_t* out_idx, double* out_score, int64_t* out_len,
+                               double* out_lambda_q, int32_t* out_status) {
+    return batch_collect(
+        q, nb, [tau](as_query* w) { return run_score(w, tau, 1); },
+        [q, nb]() -> as_status {
+            for (int b = 0; b < nb; ++b) AS_TRY(wait_published(q, b));
+            return AS_OK;
+        },
+        [q](int b) { return (q->hout[b].overflow & 1) != 0; },
+        [&](int b, bool priced) {
+            const bool ok = priced && !slot_unproven(q->hout + b);
+            out_status[b] = !ok ? -1 : (int32_t)collect(q, out_idx + b * topk, out_score + b * topk, out_len + b, out_lambda_q ? out_lambda_q + b : nullptr, b);
+        });
 }
 
 // ------------------------------------------------------------------ batched tau sweep (as_search_batch_taus)
@@ -4824,41 +4816,17 @@ static as_status wait_sweep(as_query* q, int nb, int nt) {
 // or a workspace run_score_sweep could not take).
 as_status search_batch_sweep_collect(as_query* q, int nb, const double* taus, int nt, int64_t topk, int64_t* out_idx, double* out_score,
                                      int64_t* out_len, double* out_lambda_q, int32_t* out_status) {
-    AS_TRY(wait_sweep(q, nb, nt));
-    bool crowded = false;
-    if (q->bsw_ok)
-        for (int b = 0; b < nb; ++b) crowded = crowded || (q->bsw_out[b * TAU_GROUP].overflow & 1);   // (the slot's k-NN flag: every pair has it)
-    if (crowded && !q->dots_half) {
-        AS_TRY(knn_repair(q, q->gr->gp.eps, -1));
-        AS_TRY(run_knn(q, q->gr->gp.eps, -1, 1, nullptr, nullptr, nullptr, nullptr, nullptr, 1));
-        q->seq += 1;
-        AS_TRY(run_score_sweep(q, taus, nt));
-        AS_TRY(wait_sweep(q, nb, nt));
-    }
-    const bool held = q->i8_scan && q->cap > 1 ? batch_coef_holds(q) : true;
-    bool priced = held || !q->x8_verify;
-    if (!priced && !q->x8_nan && q->batch_assume == 1) {
-        q->batch_assume = 2;
-        const as_status s2 = query_begin(q, q->hq, -1, q->sp->d, 0, q->sp->n, q->gr->gp.eps, -1);
-        q->batch_assume = 1;
-        AS_TRY(s2);
-        if (q->gr->lambda_mode != AS_LAMBDA_FEATURE) AS_TRY(run_knn(q, q->gr->gp.eps, -1, 1, nullptr, nullptr, nullptr, nullptr, nullptr));
-        q->seq += 1;
-        AS_TRY(run_score_sweep(q, taus, nt));
-        AS_TRY(wait_sweep(q, nb, nt));
-        priced = !(q->i8_scan && q->cap > 1) || batch_coef_holds(q) || !q->x8_verify;
-    }
-    for (int b = 0; b < nb; ++b)
-        for (int j = 0; j < nt; ++j) {
-            const int64_t p = (int64_t)b * nt + j;
-            const HostOut* h = q->bsw_out ? q->bsw_out + b * TAU_GROUP + j : nullptr;
-            if (!q->bsw_ok || h->overflow || h->knn_inexact || h->score_inexact || !priced) {
-                out_status[p] = -1;
-                continue;
+    return batch_collect(
+        q, nb, [taus, nt](as_query* w) { return run_score_sweep(w, taus, nt); }, [q, nb, nt] { return wait_sweep(q, nb, nt); },
+        [q](int b) { return q->bsw_ok && (q->bsw_out[b * TAU_GROUP].overflow & 1); },   // (the slot's k-NN flag: every pair has it)
+        [&](int b, bool priced) {
+            for (int j = 0; j < nt; ++j) {
+                const int64_t p = (int64_t)b * nt + j;
+                const HostOut* h = q->bsw_ok ? q->bsw_out + b * TAU_GROUP + j : nullptr;
+                const bool ok = priced && h && !slot_unproven(h);
+                out_status[p] = !ok ? -1 : (int32_t)collect_out(h, out_idx + p * topk, out_score + p * topk, out_len + p, out_lambda_q ? out_lambda_q + b : nullptr);
             }
-            out_status[p] = (int32_t)collect_out(h, out_idx + p * topk, out_score + p * topk, out_len + p, out_lambda_q ? out_lambda_q + b : nullptr);
-        }
-    return AS_OK;
+        });
 }
 
 as_status exact_row_knn(as_query* ws, const as_graph_params* gp, int64_t row, int32_t* out_idx, double* out_key,
@@ -4872,7 +4840,8 @@ as_status exact_row_knn(as_query* ws, const as_graph_params* gp, int64_t row, in
     }
     ws->exact = 1;
     ws->robust = 1;  // rows with many near-ties are exactly the ones that overflow a filter buffer
-    AS_TRY(query_begin(ws, nullptr, row, sp->d, 0, sp->n, gp->eps, row));
+    ScanRequest rq;
+    AS_TRY(query_begin(ws, nullptr, row, sp->d, 0, sp->n, gp->eps, row, rq));
     return run_knn(ws, gp->eps, row, 0, out_idx, out_key, out_dist, out_gy, out_cnt);
 }
 
