@@ -118,7 +118,17 @@ as_status as_graph_from_knn(as_space* sp, const as_graph_params* gp, const int32
  *      something a block dropped could still belong to the answer; those rows go round once more through
  *      as_knn_block_band (complete collection inside the proven band), then as_knn_merge again.  Partial arrays are
  *      device memory, caller-allocated: key / dist / gy fp64 and idx int32 [nblocks][rows][M], cnt int32 and t32 fp32
- *      [nblocks][rows]; the pointers passed to as_knn_block / _band are those of ONE block's slice. ---- */
+ *      [nblocks][rows]; the pointers passed to as_knn_block / _band are those of ONE block's slice.
+ *      A SLICE, per row: the low 16 bits of cnt = the number of entries (<= M), ordered by (key ascending, id ascending),
+ *      no (key, id) pair twice; slots past the count are never read, and unspecified after a call.  Bits 16-29 of cnt are
+ *      0.  Bit 30 = "this slice dropped or turned away something", and then t32 is a lower bound of the fp32 keys of what
+ *      it dropped (-inf: no bound is known; the row fails its proof); without bit 30, t32 is not read.  Bit 30 and t32
+ *      count whatever the number of entries: a slice that kept NO entry may still have turned candidates away (a gated
+ *      transposed slice), and as_knn_fold and as_knn_merge both honour its bound.  Cutting exact entries beyond the M-th
+ *      in a fold sets no bit (k <= M - 8: they cannot be among the k nearest).  A row is proven when, for every slice
+ *      with bit 30, t32 - e > B strictly (B = its k-th key inside eps, or the eps key with fewer; e = the fp32 error term
+ *      of the row against that block, 0 for a folded slice, whose t32 already carries it); equality, NaN and -inf flag
+ *      the row.  tests/test_gpu_ring_lists.py states all of it against oracle/oracle_np.py. ---- */
 int32_t as_knn_list_width(int64_t k);                 /* M; < 0 when k is not supported */
 int32_t as_record_capacity(int32_t which);            /* 0: k-NN records a query merges (ranks x k); 1: hit records (ranks x (topk + 1)) */
 double as_space_nmax(const as_space* sp);             /* largest squared norm (error bound of a block's dropped candidates) */

@@ -284,6 +284,110 @@ def synth_lambda(E, G, tau0):
     return tau0 * (E / (E + tau0)) + (1.0 - tau0) * G
 
 
+# ---- the ring's per-row bookkeeping between the block passes (as_knn_fold / as_knn_merge / as_knn_thresholds), on the
+# arrays as they lie in memory.  A slice is the tuple (key, dist, gy fp64 [rows][M], idx int32 [rows][M], cnt int32
+# [rows], t32 fp32 [rows]): cnt & 0xffff entries per row ordered by (key, id), bit 30 of cnt = "this slice dropped or
+# turned away something", t32 = a lower bound of the fp32 keys of what it dropped (include/arrowspace_hip.h).
+RING_DROPPED = 1 << 30
+
+
+def rd32(x):
+    """fp64 -> fp32, rounded toward -inf."""
+    with np.errstate(over="ignore"):
+        f = np.float32(x)
+    return np.nextafter(f, np.float32(-np.inf)) if float(f) > x else f
+
+
+def ru32(x):
+    """fp64 -> fp32, rounded toward +inf."""
+    with np.errstate(over="ignore"):
+        f = np.float32(x)
+    return np.nextafter(f, np.float32(np.inf)) if float(f) < x else f
+
+
+def ring_coef_i8(u_max, v_max):
+    """The coefficient as_ring_i8_set fixes: 2.001 U + V^2 + 12 * 2^-24."""
+    return 2.001 * u_max + v_max * v_max + 12.0 * 2.0 ** -24
+
+
+def ring_coef_default(dp):
+    """The bf16 head + tail coefficient of a space of dp padded columns."""
+    return float(6 * dp + 32) * 2.0 ** -24 + 3.03 * 2.0 ** -16
+
+
+def ring_err(coef, metric, n_i, nmax):
+    """e: by how much an fp32 key of row i against a block of largest squared norm nmax may sit above the exact one."""
+    return coef * (n_i + nmax) if metric == METRIC_L2 else coef
+
+
+def ring_fold(run, blk, M, metric, coef, n_rows, nmax_b, mode=0, flag=None):
+    """as_knn_fold: the running slice after the block's slice was folded in (new arrays; `run` is left alone).
+    n_rows[r] = squared norm of the space's row row_begin + r.  mode 0: every row; 1: rows with flag != 0; 2: those
+    rows, their running list (entries, dropped bit, bound) discarded first.  Slots past a row's new count keep what
+    `run` held: the kernel leaves them unspecified."""
+    out = [np.array(a, copy=True) for a in run]
+    bk, bd, bg, bi, bc, bt = blk
+    for r in range(len(out[4])):
+        if mode != 0 and not flag[r]:
+            continue
+        c_run = 0 if mode == 2 else int(run[4][r]) & 0xFFFF
+        d_run = 0 if mode == 2 else (int(run[4][r]) >> 30) & 1
+        c_blk, d_blk = int(bc[r]) & 0xFFFF, (int(bc[r]) >> 30) & 1
+        key, dist, gy, idx = (np.concatenate([a[r, :c_run], b[r, :c_blk]]) for a, b in zip(run[:4], (bk, bd, bg, bi)))
+        o = np.lexsort((idx, key))[:M]
+        m = len(o)
+        out[0][r, :m], out[1][r, :m], out[2][r, :m], out[3][r, :m] = key[o], dist[o], gy[o], idx[o]
+        out[4][r] = m | ((d_run | d_blk) << 30)
+        t = run[5][r] if d_run else np.float32(np.inf)
+        if d_blk:
+            nb = rd32(float(bt[r]) - ring_err(coef, metric, float(n_rows[r]), nmax_b))
+            if nb < t:
+                t = nb
+        out[5][r] = t
+    return tuple(out)
+
+
+def ring_merge(slices, M, k, metric, coef, eps, n_rows, block_nmax=None):
+    """as_knn_merge over the slices of all blocks (block_nmax[b] given), or over ONE folded slice (block_nmax None: its
+    bound already carries the blocks' error terms).  -> dict: idx (-1 past cnt), key / dist / gy (0 past cnt: the kernel
+    leaves those unspecified), cnt, flag, band (B where flagged, NaN elsewhere: the kernel writes flagged rows only),
+    nflagged."""
+    rows = len(slices[0][4])
+    ek = _eps_key(eps, metric)
+    res = dict(idx=np.full((rows, k), -1, dtype=np.int32), key=np.zeros((rows, k)), dist=np.zeros((rows, k)), gy=np.zeros((rows, k)),
+               cnt=np.zeros(rows, dtype=np.int32), flag=np.zeros(rows, dtype=np.int32), band=np.full(rows, np.nan))
+    for r in range(rows):
+        c = [int(s[4][r]) & 0xFFFF for s in slices]
+        key, dist, gy, idx = (np.concatenate([s[j][r, :cb] for s, cb in zip(slices, c)]) for j in range(4))
+        ok = key <= ek                       # (a NaN key does not pass)
+        key, dist, gy, idx = key[ok], dist[ok], gy[ok], idx[ok]
+        o = np.lexsort((idx, key))[:k]
+        m = len(o)
+        res["idx"][r, :m], res["key"][r, :m], res["dist"][r, :m], res["gy"][r, :m], res["cnt"][r] = idx[o], key[o], dist[o], gy[o], m
+        B = float(key[o][k - 1]) if len(key) >= k else ek
+        bad = False
+        for b, s in enumerate(slices):
+            if not (int(s[4][r]) >> 30) & 1:
+                continue
+            e = 0.0 if block_nmax is None else ring_err(coef, metric, float(n_rows[r]), float(block_nmax[b]))
+            if not (float(s[5][r]) - e > B):     # equality, NaN and -inf leave the row unproven
+                bad = True
+        if bad:
+            res["flag"][r], res["band"][r] = 1, B
+    res["nflagged"] = int(res["flag"].sum())
+    return res
+
+
+def ring_thresholds(key, cnt, M, metric, coef, n_rows, nmax):
+    """as_knn_thresholds: an upper bound of each row's M-th smallest fp32 key, +inf while its list is not full.  nmax =
+    max(nmax_all, the space's own)."""
+    out = np.full(len(cnt), np.inf, dtype=np.float32)
+    for r in range(len(cnt)):
+        if int(cnt[r]) & 0xFFFF >= M:
+            out[r] = ru32((float(key[r, M - 1]) + ring_err(coef, metric, float(n_rows[r]), nmax)) * 1.000001)
+    return out
+
+
 def query_neighbours(idx: dict, q, r0=0, r1=None):
     """SPEC S10, first half: the k nearest items of q within eps among rows [r0, r1):
     (item index, key, dist, gy), ordered by (key asc, index asc)."""

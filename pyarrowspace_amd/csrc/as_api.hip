@@ -474,8 +474,16 @@ as_status as_knn_merge(const as_space* sp, const as_graph_params* gp, int64_t ro
         set_err("as_knn_merge: null argument");
         return AS_EINVAL;
     }
+    if (row_begin < 0 || row_end > sp->n || row_begin > row_end) {   // the kernel reads the rows' norms
+        set_err("as_knn_merge: bad row range [%lld,%lld) for n=%lld", (long long)row_begin, (long long)row_end, (long long)sp->n);
+        return AS_EINVAL;
+    }
     as_graph_params r;
     AS_TRY(resolve_params(gp, &r));
+    if (knn_list_width(r.k) < 0) {
+        set_err("graph_params['k']=%lld exceeds the supported maximum of 120", (long long)r.k);
+        return AS_EUNSUPPORTED;
+    }
     AS_HIP(hipSetDevice(sp->device));
     const double t0 = now_s();
     const as_status s = knn_merge(sp, &r, row_begin, row_end, nblocks, knn_list_width(r.k), p_key_dev, p_dist_dev, p_gy_dev, p_idx_dev,
@@ -494,8 +502,16 @@ as_status as_knn_fold(const as_space* sp, const as_graph_params* gp, int64_t row
         set_err("as_knn_fold: null argument or bad mode");
         return AS_EINVAL;
     }
+    if (row_begin < 0 || row_end > sp->n || row_begin > row_end) {   // the kernel reads the rows' norms
+        set_err("as_knn_fold: bad row range [%lld,%lld) for n=%lld", (long long)row_begin, (long long)row_end, (long long)sp->n);
+        return AS_EINVAL;
+    }
     as_graph_params r;
     AS_TRY(resolve_params(gp, &r));
+    if (knn_list_width(r.k) < 0) {
+        set_err("graph_params['k']=%lld exceeds the supported maximum of 120", (long long)r.k);
+        return AS_EUNSUPPORTED;
+    }
     AS_HIP(hipSetDevice(sp->device));
     return knn_fold(sp, row_begin, row_end, knn_list_width(r.k), mode, block_nmax, flag_dev, r_key_dev, r_dist_dev, r_gy_dev, r_idx_dev,
                     r_cnt_dev, r_t32_dev, b_key_dev, b_dist_dev, b_gy_dev, b_idx_dev, b_cnt_dev, b_t32_dev);

@@ -2333,7 +2333,7 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(MergeArgs a) {
     char* base = smem + (size_t)w * ((sizeof(double) + sizeof(int) * 2) * cap);
     double* mk = (double*)base;
     int* mi = (int*)(mk + cap);
-    int* mp = mi + cap;          // position in the partial arrays
+    int* mp = mi + cap;          // position in the partial arrays: block * M + slot
     const int64_t lr = (int64_t)blockIdx.x * 4 + w;
     if (lr >= a.rows) return;
     int C = 0;
@@ -2343,7 +2343,7 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(MergeArgs a) {
         for (int t = lane; t < c; t += 64) {
             mk[C + t] = a.p_key[ob + t];
             mi[C + t] = a.p_idx[ob + t];
-            mp[C + t] = (int)(ob + t - (size_t)lr * a.M);   // relative: fits an int
+            mp[C + t] = b * a.M + t;   // (block, slot): below cap, whatever nblocks * rows * M is
         }
         C += c;
     }
@@ -2357,7 +2357,7 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(MergeArgs a) {
         int rank = 0;
         for (int s2 = 0; s2 < C; ++s2) rank += lex_less<double>(mk[s2], mi[s2], kk, mi[t]) ? 1 : 0;
         if (rank < a.k) {
-            const size_t src = (size_t)lr * a.M + (size_t)mp[t];
+            const size_t src = ((size_t)(mp[t] / a.M) * a.rows + lr) * a.M + (size_t)(mp[t] % a.M);
             a.out_idx[lr * a.k + rank] = mi[t];
             a.out_key[lr * a.k + rank] = kk;
             a.out_dist[lr * a.k + rank] = a.p_dist[src];
@@ -2380,7 +2380,9 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(MergeArgs a) {
         int bad = 0;
         for (int b = 0; b < a.nblocks; ++b) {
             const int cc = a.p_cnt[(size_t)b * a.rows + lr];
-            if (!((cc >> 30) & 1) || (cc & 0xffff) == 0) continue;   // nothing was dropped from this block
+            // bit 30 clear: nothing was dropped from this block.  Set on a slice without an entry: it kept nothing and still
+            // turned candidates away, and its bound counts as in knn_fold_kernel
+            if (!((cc >> 30) & 1)) continue;
             const double e = a.folded ? 0.0 : (a.metric == AS_METRIC_L2 ? a.coef * (ni + a.nmax[b]) : a.coef);
             if (!((double)a.p_t32[(size_t)b * a.rows + lr] - e > B)) bad = 1;
         }
