@@ -514,6 +514,34 @@ as_status as_search_subset_batch(const as_space* sp, const as_graph* gr, const d
                                  int32_t* out_status);
 as_status as_score_items_batch(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau,
                                const int64_t* ids_host, int64_t m, double* out_scores, double* out_lambda_q, int32_t* out_status);
+/* Tau sweeps over a subset: the four filtered forms under ntau taus, with ONE lambda_q step (lambda_q does not depend on tau: the
+ * single search, or ONE as_search_batch call, run with taus[0], hits discarded) and ONE gather of the subset's rows per up to 8
+ * distinct taus: every (query, item) cosine is formed once and blended with each tau of the group.  Layouts as as_search_taus /
+ * as_search_batch_taus: list (i, j) at out_idx / out_score + (i * ntau + j) * kk, kk = min(topk, nitems, |S|), out_len[i * ntau + j]
+ * entries (the single forms: i = 0); out_scores [ntau][m], batched [b][ntau][m]; one out_lambda_q per query, one out_status per
+ * query of the batched forms.  List j / row j is what the single-tau form of the same route returns for taus[j]: the same score
+ * bits given the same lambda_q (as_search_subset / as_score_items for the single forms, as_search_subset_batch /
+ * as_score_items_batch for the batched ones); across routes 1e-12 relative as documented above.  Every finite tau is served; a
+ * NaN or infinite tau anywhere in the list -> AS_EINVAL before anything is launched.  Taus equal by bit pattern are computed
+ * once, their lists / rows copied.  ntau == 0 launches nothing.  The other checks, codes and messages are the single-tau forms';
+ * lambda_q == 0 -> AS_EZEROLAMBDA (batched: out_status, out_len 0 for every list of that query, its rows of out_scores left
+ * unwritten), whatever the subset; an empty subset / m == 0 still runs the lambda_q step.  The batched forms pick the taus per
+ * gather (<= 8) and the queries per chunk from the "subset_batch_mib" budget; results never depend on either.  The sweep's
+ * buffers are made on a handle's first sweep (as_score_items*_taus: in the space) and grow on demand.  Serialised as the
+ * single-tau forms.  With timing enabled as_subset_kernel_us reports the sweep's score kernel summed over the call's launches. */
+as_status as_search_subset_taus(const as_space* sp, const as_graph* gr, const double* query, int64_t d, const double* taus, int64_t ntau,
+                                const as_subset* sub, int64_t* out_idx, double* out_score, int64_t* out_len, double* out_lambda_q);
+as_status as_score_items_taus(const as_space* sp, const as_graph* gr, const double* query, int64_t d, const double* taus, int64_t ntau,
+                              const int64_t* ids_host, int64_t m, double* out_scores, double* out_lambda_q);
+as_status as_search_subset_batch_taus(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d,
+                                      const double* taus, int64_t ntau, const as_subset* sub, int64_t* out_idx, double* out_score,
+                                      int64_t* out_len, double* out_lambda_q, int32_t* out_status);
+as_status as_score_items_batch_taus(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d,
+                                    const double* taus, int64_t ntau, const int64_t* ids_host, int64_t m, double* out_scores,
+                                    double* out_lambda_q, int32_t* out_status);
+/* out[0] tau sweeps over a subset (the four calls above), [1] score-kernel launches they made, [2] tau planes those launches wrote,
+ * [3] lambda_q steps run (single searches plus as_search_batch calls) */
+as_status as_subset_sweep_counters(const as_space* sp, int64_t* out, int32_t n);
 
 /* ---- index persistence (extension; the reference exposes none): one flat file
  * holding the items, lambdas and graph arrays.  Loading re-ingests the items and uploads the

@@ -240,12 +240,12 @@ class ItemSubset:
         return out
 
     def set_timing(self, enabled: bool) -> None:
-        """Measurement only (tools/subset_bench.py, tools/subset_batch_bench.py): record HIP events around the score kernel of `search_subset` / `search_batch_subset` calls on this subset (off by default)."""
+        """Measurement only (tools/subset_bench.py, tools/subset_batch_bench.py, tools/subset_sweep_bench.py): record HIP events around the score kernel of `search_subset` / `search_batch_subset` calls and their `*_taus` sweeps on this subset (off by default)."""
         _L.as_subset_set_timing(self._h, 1 if enabled else 0)
 
     @property
     def kernel_us(self) -> float:
-        """Measurement only: device microseconds of the score kernel in the last timed `search_subset` call on this subset (`search_batch_subset`: summed over the call's chunks)."""
+        """Measurement only: device microseconds of the score kernel in the last timed `search_subset` call on this subset (`search_batch_subset`: summed over the call's chunks; the sweeps: over the call's launches)."""
         return float(_L.as_subset_kernel_us(self._h))
 
 
@@ -481,6 +481,118 @@ class ArrowSpace:
         if (stt[:b] == _lib.AS_EZEROLAMBDA).any():
             raise PanicException("The lambdas are zero, check the magnitude of items and eps.")
         return out
+
+    @staticmethod
+    def _taus(taus) -> np.ndarray:
+        t = np.ascontiguousarray(taus, dtype=np.float64)
+        if t.ndim != 1:
+            raise TypeError("argument 'taus': expected a 1-D sequence of floats")
+        return t
+
+    def search_subset_taus(self, item, gl: GraphLaplacian, taus, subset):
+        """Extension: filtered search under several taus -> one hit list per entry of `taus`, in order; list j is what
+        `search_subset(item, gl, taus[j], subset)` returns, with the same score bits.  Costs ONE ordinary `search` (lambda_q
+        does not depend on tau; a query whose lambda_q is 0 panics as there) and ONE gather of the subset's rows per up to 8
+        distinct taus: every cosine is formed once and blended with each tau.  Every finite tau is served; a NaN or infinite
+        one raises ValueError before anything runs; equal taus are computed once; `taus = []` returns `[]`."""
+        if not isinstance(gl, GraphLaplacian):
+            raise TypeError("argument 'gl': expected GraphLaplacian")
+        q = self._query(item)
+        t = self._taus(taus)
+        sub = subset if isinstance(subset, ItemSubset) else self.subset(subset)
+        nt = t.shape[0]
+        kk = max(min(int(gl.graph_params["topk"]), self.nitems, sub.size), 0)
+        idx = np.empty(max(nt * kk, 1), dtype=np.int64)
+        sc = np.empty(max(nt * kk, 1), dtype=np.float64)
+        ln = np.zeros(max(nt, 1), dtype=np.int64)
+        lq = C.c_double(0.0)
+        st = _L.as_search_subset_taus(self._h, gl._h, q.ctypes.data, q.shape[0], t.ctypes.data, nt, sub._h, idx.ctypes.data, sc.ctypes.data,
+                                      ln.ctypes.data, C.byref(lq))
+        if st:
+            _raise(st)
+        idx, sc = idx[:nt * kk].reshape(nt, kk), sc[:nt * kk].reshape(nt, kk)   # (the C ABI's lists are at stride kk)
+        return [list(zip(ii[:l], ss[:l])) for ii, ss, l in zip(idx.tolist(), sc.tolist(), ln[:nt].tolist())]
+
+    def score_items_taus(self, item, gl: GraphLaplacian, taus, ids) -> np.ndarray:
+        """Extension: re-ranking under several taus -> ndarray[float64] of shape (len(taus), len(ids)): row j is what
+        `score_items(item, gl, taus[j], ids)` returns, with the same bits (and the bits `search_subset_taus` gives the same
+        tau and item).  Costs one ordinary `search` (lambda_q) and one gather of the listed rows per up to 8 distinct taus."""
+        if not isinstance(gl, GraphLaplacian):
+            raise TypeError("argument 'gl': expected GraphLaplacian")
+        q = self._query(item)
+        t = self._taus(taus)
+        ids = _item_ids(ids, self.nitems, "ids")
+        nt, m = t.shape[0], ids.shape[0]
+        out = np.empty((nt, m), dtype=np.float64)
+        lq = C.c_double(0.0)
+        st = _L.as_score_items_taus(self._h, gl._h, q.ctypes.data, q.shape[0], t.ctypes.data, nt, ids.ctypes.data_as(C.c_void_p), m,
+                                    out.ctypes.data_as(C.c_void_p), C.byref(lq))
+        if st:
+            _raise(st)
+        return out
+
+    def search_batch_subset_taus(self, items, gl: GraphLaplacian, taus, subset):
+        """Extension: batched filtered search under several taus, B queries [B, D] -> for each query a list of one hit list
+        per entry of `taus`; entry [i][j] is what `search_batch_subset(items, gl, taus[j], subset)[i]` returns, with the same
+        score bits.  Costs ONE `search_batch` over the B queries (lambda_q; a query whose lambda_q is 0 panics as there) and
+        one gather of the subset's rows per 64 queries and up to 8 distinct taus (fewer where the score planes would exceed
+        the chunk budget).  Finite taus only (ValueError otherwise); equal taus are computed once; `taus = []` returns B empty
+        lists."""
+        if not isinstance(gl, GraphLaplacian):
+            raise TypeError("argument 'gl': expected GraphLaplacian")
+        Q = np.ascontiguousarray(items, dtype=np.float64)
+        if Q.ndim != 2:
+            raise TypeError("items must be a 2-D float64 array")
+        t = self._taus(taus)
+        sub = subset if isinstance(subset, ItemSubset) else self.subset(subset)
+        b, nt = Q.shape[0], t.shape[0]
+        kk = max(min(int(gl.graph_params["topk"]), self.nitems, sub.size), 0)
+        idx = np.empty(max(b * nt * kk, 1), dtype=np.int64)
+        sc = np.empty(max(b * nt * kk, 1), dtype=np.float64)
+        ln = np.zeros(max(b * nt, 1), dtype=np.int64)
+        stt = np.zeros(max(b, 1), dtype=np.int32)
+        st = _L.as_search_subset_batch_taus(self._h, gl._h, Q.ctypes.data_as(C.c_void_p), b, Q.shape[1], t.ctypes.data, nt, sub._h,
+                                            idx.ctypes.data, sc.ctypes.data, ln.ctypes.data, None, stt.ctypes.data)
+        if st:
+            _raise(st)
+        if (stt[:b] == _lib.AS_EZEROLAMBDA).any():
+            raise PanicException("The lambdas are zero, check the magnitude of items and eps.")
+        idx, sc, ln = idx[:b * nt * kk].reshape(b, nt, kk), sc[:b * nt * kk].reshape(b, nt, kk), ln[:b * nt].reshape(b, nt)
+        return [[list(zip(ii[:l], ss[:l])) for ii, ss, l in zip(bi, bs, bl)]
+                for bi, bs, bl in zip(idx.tolist(), sc.tolist(), ln.tolist())]
+
+    def score_items_batch_taus(self, items, gl: GraphLaplacian, taus, ids) -> np.ndarray:
+        """Extension: batched re-ranking under several taus -> ndarray[float64] of shape (B, len(taus), len(ids)): entry
+        [i, j] is row i of `score_items_batch(items, gl, taus[j], ids)`, with the same bits.  Costs one `search_batch` over the
+        B queries (lambda_q; a query whose lambda_q is 0 panics as there) and one gather of the listed rows per 64 queries and
+        up to 8 distinct taus."""
+        if not isinstance(gl, GraphLaplacian):
+            raise TypeError("argument 'gl': expected GraphLaplacian")
+        Q = np.ascontiguousarray(items, dtype=np.float64)
+        if Q.ndim != 2:
+            raise TypeError("items must be a 2-D float64 array")
+        t = self._taus(taus)
+        ids = _item_ids(ids, self.nitems, "ids")
+        b, nt, m = Q.shape[0], t.shape[0], ids.shape[0]
+        out = np.empty((b, nt, m), dtype=np.float64)
+        stt = np.zeros(max(b, 1), dtype=np.int32)
+        st = _L.as_score_items_batch_taus(self._h, gl._h, Q.ctypes.data_as(C.c_void_p), b, Q.shape[1], t.ctypes.data, nt,
+                                          ids.ctypes.data_as(C.c_void_p), m, out.ctypes.data_as(C.c_void_p), None, stt.ctypes.data)
+        if st:
+            _raise(st)
+        if (stt[:b] == _lib.AS_EZEROLAMBDA).any():
+            raise PanicException("The lambdas are zero, check the magnitude of items and eps.")
+        return out
+
+    def subset_sweep_counters(self) -> dict:
+        """Extension: tau sweeps over a subset on this space (all four `*_taus` forms of the filtered search), the score-kernel
+        launches they made, the tau planes those launches wrote, and the lambda_q steps run (single searches plus
+        `search_batch` calls)."""
+        out = np.zeros(4, dtype=np.int64)
+        st = _L.as_subset_sweep_counters(self._h, out.ctypes.data_as(C.c_void_p), 4)
+        if st:
+            _raise(st)
+        return dict(zip(("calls", "score_launches", "tau_planes", "lambda_steps"), (int(v) for v in out)))
 
     def sweep_counters(self) -> dict:
         """Extension: `search_taus` calls on this space, the shared passes that served them, and the taus those passes left

@@ -53,6 +53,7 @@ SYMBOLS = [
     "as_comm_available", "as_comm_unique_id", "as_comm_create", "as_comm_free", "as_query_set_comm", "as_query_search_staged", "as_query_x1_bytes", "as_query_x1_usable", "as_query_x1_enabled", "as_query_set_x1", "as_query_x1_begin", "as_query_x1_finish", "as_query_x1_redo", "as_query_set_coarse", "as_query_x1_passes", "as_edges_bucket", "as_ring_i8_stats", "as_ring_i8_set", "as_ring_i8",
     "as_subset_create", "as_subset_size", "as_subset_ids", "as_subset_free", "as_search_subset", "as_score_items", "as_subset_set_timing", "as_subset_kernel_us",
     "as_search_subset_batch", "as_score_items_batch",
+    "as_search_subset_taus", "as_score_items_taus", "as_search_subset_batch_taus", "as_score_items_batch_taus", "as_subset_sweep_counters",
 ]
 
 _lib = None
@@ -208,6 +209,11 @@ def load():
         "as_score_items": (i32, [vp, vp, vp, i64, f64, vp, i64, vp, C.POINTER(f64)]),
         "as_search_subset_batch": (i32, [vp, vp, vp, i64, i64, f64, vp, vp, vp, vp, vp, vp]),
         "as_score_items_batch": (i32, [vp, vp, vp, i64, i64, f64, vp, i64, vp, vp, vp]),
+        "as_search_subset_taus": (i32, [vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, C.POINTER(f64)]),
+        "as_score_items_taus": (i32, [vp, vp, vp, i64, vp, i64, vp, i64, vp, C.POINTER(f64)]),
+        "as_search_subset_batch_taus": (i32, [vp, vp, vp, i64, i64, vp, i64, vp, vp, vp, vp, vp, vp]),
+        "as_score_items_batch_taus": (i32, [vp, vp, vp, i64, i64, vp, i64, vp, i64, vp, vp, vp]),
+        "as_subset_sweep_counters": (i32, [vp, vp, i32]),
         "as_subset_set_timing": (None, [vp, i32]),
         "as_subset_kernel_us": (f64, [vp]),
         "as_gang_counters": (i32, [vp, vp, i32]),

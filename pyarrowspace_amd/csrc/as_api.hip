@@ -954,22 +954,28 @@ as_status as_sweep_counters(const as_space* sp, int64_t* out, int32_t n) {
 }
 
 // ---------------------------------------------------------------- filtered search (extension; kernels: as_subset.hip)
-// what as_search_subset and as_score_items check alike, then lambda_q by the single search on a workspace of the pool, hits
-// discarded: its escalation, its AS_EZEROLAMBDA, its out_lambda_q
-static as_status subset_lambda(const char* who, const as_space* sp, const as_graph* gr, const double* query, int64_t d, double tau, double* lq) {
+// what every filtered form checks alike (the tau sweeps: every tau of the list)
+static as_status subset_checks(const char* who, const as_space* sp, const as_graph* gr, int64_t d, const double* taus, int64_t ntau) {
     if (d != sp->d) {
         set_err("query length %lld must match nfeatures %lld", (long long)d, (long long)sp->d);
         return AS_EINVAL;
     }
-    if (!std::isfinite(tau)) {
-        set_err("%s: tau must be finite", who);
-        return AS_EINVAL;
-    }
+    for (int64_t j = 0; j < ntau; ++j)
+        if (!std::isfinite(taus[j])) {
+            set_err("%s: tau must be finite", who);
+            return AS_EINVAL;
+        }
     AS_TRY(graph_matches(sp, gr, who));
     if (sp->row_offset != 0 || gr->ncols) {
         set_err("%s: a shard of a row-sharded index is not supported", who);
         return AS_EUNSUPPORTED;
     }
+    return AS_OK;
+}
+// those checks, then lambda_q by the single search on a workspace of the pool, hits discarded: its escalation, its
+// AS_EZEROLAMBDA, its out_lambda_q
+static as_status subset_lambda(const char* who, const as_space* sp, const as_graph* gr, const double* query, int64_t d, double tau, double* lq) {
+    AS_TRY(subset_checks(who, sp, gr, d, &tau, 1));
     int64_t hidx[SUBSET_TOPK], hlen = 0;
     double hsc[SUBSET_TOPK];
     return search_pooled(sp, gr, query, d, tau, hidx, hsc, &hlen, lq);
@@ -1065,6 +1071,18 @@ as_status as_search_subset(const as_space* sp, const as_graph* gr, const double*
     return subset_select(sub->w, sub->m, std::min<int64_t>(topk, sub->m), out_idx, out_score, out_len);
 }
 
+// the space's work buffers for m ids (under sp->smu): grown on demand, never per call otherwise; the ids uploaded
+static as_status score_ws_ids(const as_space* sp, const int32_t* ids, int64_t m) {
+    if (!sp->score_ws || sp->score_ws->cap < m) {
+        subset_work_free(sp->score_ws);
+        sp->score_ws = nullptr;
+        int64_t cap = 1024;
+        while (cap < m) cap *= 2;
+        AS_TRY(subset_work_create(sp, cap, &sp->score_ws));
+    }
+    return subset_set_ids(sp->score_ws, ids, m);
+}
+
 as_status as_score_items(const as_space* sp, const as_graph* gr, const double* query, int64_t d, double tau, const int64_t* ids_host,
                          int64_t m, double* out_scores, double* out_lambda_q) {
     if (!sp || !gr || !query || m < 0 || (m > 0 && (!ids_host || !out_scores))) {
@@ -1093,14 +1111,7 @@ as_status as_score_items(const as_space* sp, const as_graph* gr, const double* q
         return AS_ENOMEM;
     }
     std::lock_guard<std::mutex> lk(sp->smu);
-    if (!sp->score_ws || sp->score_ws->cap < m) {   // grown on demand, never per query otherwise
-        subset_work_free(sp->score_ws);
-        sp->score_ws = nullptr;
-        int64_t cap = 1024;
-        while (cap < m) cap *= 2;
-        AS_TRY(subset_work_create(sp, cap, &sp->score_ws));
-    }
-    AS_TRY(subset_set_ids(sp->score_ws, ids.data(), m));
+    AS_TRY(score_ws_ids(sp, ids.data(), m));
     AS_TRY(subset_score(sp, sp->score_ws, m, query, tau, lq));
     return subset_scores_out(sp->score_ws, m, out_scores);
 }
@@ -1206,21 +1217,8 @@ as_status as_search_batch(const as_space* sp, const as_graph* gr, const double* 
 // The batched filtered forms.  What both check (the single forms' checks and messages), then lambda_q and the status of every
 // query from ONE as_search_batch call over all b queries, hits discarded: its escalation, its values.  as_search_batch has
 // returned, and released sp->bmu, before the caller takes the handle's mutex: the two are never nested.
-static as_status subset_batch_lambda(const char* who, const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d,
-                                     double tau, std::vector<double>& lq, std::vector<int32_t>& st) {
-    if (d != sp->d) {
-        set_err("query length %lld must match nfeatures %lld", (long long)d, (long long)sp->d);
-        return AS_EINVAL;
-    }
-    if (!std::isfinite(tau)) {
-        set_err("%s: tau must be finite", who);
-        return AS_EINVAL;
-    }
-    AS_TRY(graph_matches(sp, gr, who));
-    if (sp->row_offset != 0 || gr->ncols) {
-        set_err("%s: a shard of a row-sharded index is not supported", who);
-        return AS_EUNSUPPORTED;
-    }
+static as_status batch_lambda_step(const char* who, const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d,
+                                   double tau, std::vector<double>& lq, std::vector<int32_t>& st) {
     if (b == 0) return AS_OK;
     const int64_t topk = std::max<int64_t>(std::min<int64_t>(gr->gp.topk, sp->n), 1);
     std::vector<int64_t> hidx, hlen;
@@ -1236,6 +1234,11 @@ static as_status subset_batch_lambda(const char* who, const as_space* sp, const 
         return AS_ENOMEM;
     }
     return as_search_batch(sp, gr, queries, b, d, tau, hidx.data(), hsc.data(), hlen.data(), lq.data(), st.data());
+}
+static as_status subset_batch_lambda(const char* who, const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d,
+                                     double tau, std::vector<double>& lq, std::vector<int32_t>& st) {
+    AS_TRY(subset_checks(who, sp, gr, d, &tau, 1));
+    return batch_lambda_step(who, sp, gr, queries, b, d, tau, lq, st);
 }
 
 as_status as_search_subset_batch(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau,
@@ -1296,15 +1299,247 @@ as_status as_score_items_batch(const as_space* sp, const as_graph* gr, const dou
     }
     std::lock_guard<std::mutex> lk(sp->smu);
     AS_HIP(hipSetDevice(sp->device));
-    if (!sp->score_ws || sp->score_ws->cap < m) {   // grown on demand, never per call otherwise
-        subset_work_free(sp->score_ws);
-        sp->score_ws = nullptr;
-        int64_t cap = 1024;
-        while (cap < m) cap *= 2;
-        AS_TRY(subset_work_create(sp, cap, &sp->score_ws));
-    }
-    AS_TRY(subset_set_ids(sp->score_ws, ids.data(), m));
+    AS_TRY(score_ws_ids(sp, ids.data(), m));
     return subset_batch_run(sp, sp->score_ws, m, queries, b, lq.data(), st.data(), tau, 0, 0, nullptr, nullptr, nullptr, out_scores);
+}
+
+// ---------------------------------------------------------------- tau sweeps over a subset (extension)
+// distinct taus (bit patterns) in order of first appearance: row[u] = the first j with taus[j] == uniq[u], slot[j] = its u
+static void distinct_taus(const double* taus, int64_t ntau, std::vector<double>& uniq, std::vector<int64_t>& row, std::vector<int64_t>& slot) {
+    slot.resize((size_t)ntau);
+    for (int64_t j = 0; j < ntau; ++j) {
+        int64_t u = 0;
+        while (u < (int64_t)uniq.size() && memcmp(&uniq[u], &taus[j], sizeof(double)) != 0) ++u;
+        if (u == (int64_t)uniq.size()) {
+            uniq.push_back(taus[j]);
+            row.push_back(j);
+        }
+        slot[j] = u;
+    }
+}
+static void sweep_counts_add(const as_space* sp, const int64_t* counts) {
+    sp->ssweep_count[1].fetch_add(counts[0], std::memory_order_relaxed);
+    sp->ssweep_count[2].fetch_add(counts[1], std::memory_order_relaxed);
+}
+// lambda_q of a single sweep: ONE single search with taus[0], hits discarded
+static as_status sweep_lambda(const as_space* sp, const as_graph* gr, const double* query, int64_t d, double tau, double* lq) {
+    sp->ssweep_count[0].fetch_add(1, std::memory_order_relaxed);
+    sp->ssweep_count[3].fetch_add(1, std::memory_order_relaxed);
+    int64_t hidx[SUBSET_TOPK], hlen = 0;
+    double hsc[SUBSET_TOPK];
+    return search_pooled(sp, gr, query, d, tau, hidx, hsc, &hlen, lq);
+}
+static as_status checked_ids(const char* who, const as_space* sp, const int64_t* ids_host, int64_t m, std::vector<int32_t>& ids) {
+    if (m >= (int64_t)1 << 31) {
+        set_err("%s: %lld ids exceed the supported maximum of 2^31 - 1 per call", who, (long long)m);
+        return AS_EUNSUPPORTED;
+    }
+    try {
+        ids.assign(ids_host, ids_host + m);   // (item ids fit 32 bits: space_new refuses n >= 2^31)
+    } catch (const std::bad_alloc&) {
+        set_err("%s: out of host memory for %lld ids", who, (long long)m);
+        return AS_ENOMEM;
+    }
+    return AS_OK;
+}
+
+as_status as_search_subset_taus(const as_space* sp, const as_graph* gr, const double* query, int64_t d, const double* taus, int64_t ntau,
+                                const as_subset* sub, int64_t* out_idx, double* out_score, int64_t* out_len, double* out_lambda_q) {
+    if (!sp || !gr || !query || !sub || ntau < 0 || (ntau > 0 && (!taus || !out_len || (sub->m > 0 && (!out_idx || !out_score))))) {
+        set_err("as_search_subset_taus: null argument");
+        return AS_EINVAL;
+    }
+    for (int64_t j = 0; j < ntau; ++j) out_len[j] = 0;
+    if (sub->sp != sp) {
+        set_err("as_search_subset_taus: the subset was made for another space");
+        return AS_EINVAL;
+    }
+    AS_TRY(subset_checks("as_search_subset_taus", sp, gr, d, taus, ntau));
+    if (ntau == 0) return AS_OK;
+    double lq = 0.0;
+    const as_status s = sweep_lambda(sp, gr, query, d, taus[0], &lq);
+    if (out_lambda_q) *out_lambda_q = lq;
+    if (s != AS_OK) return s;
+    if (sub->m == 0) return AS_OK;
+    const int64_t kk = std::min<int64_t>(std::min<int64_t>(gr->gp.topk, sp->n), sub->m);
+    std::vector<double> uniq;
+    std::vector<int64_t> row, slot;
+    distinct_taus(taus, ntau, uniq, row, slot);
+    int64_t counts[2] = {0, 0};
+    as_status r;
+    {
+        std::lock_guard<std::mutex> lk(sub->mu);
+        r = subset_sweep_run(sp, sub->w, sub->m, query, lq, uniq.data(), (int64_t)uniq.size(), row.data(), kk, out_idx, out_score, out_len,
+                             nullptr, counts);
+    }
+    sweep_counts_add(sp, counts);
+    if (r != AS_OK) return r;
+    for (int64_t j = 0; j < ntau; ++j) {   // equal taus: copies of the first one's list
+        const int64_t f = row[slot[j]];
+        if (f == j) continue;
+        for (int64_t t = 0; t < out_len[f]; ++t) {
+            out_idx[j * kk + t] = out_idx[f * kk + t];
+            out_score[j * kk + t] = out_score[f * kk + t];
+        }
+        out_len[j] = out_len[f];
+    }
+    return AS_OK;
+}
+
+as_status as_score_items_taus(const as_space* sp, const as_graph* gr, const double* query, int64_t d, const double* taus, int64_t ntau,
+                              const int64_t* ids_host, int64_t m, double* out_scores, double* out_lambda_q) {
+    if (!sp || !gr || !query || ntau < 0 || m < 0 || (ntau > 0 && !taus) || (m > 0 && !ids_host) || (ntau > 0 && m > 0 && !out_scores)) {
+        set_err("as_score_items_taus: null argument");
+        return AS_EINVAL;
+    }
+    for (int64_t i = 0; i < m; ++i)
+        if (ids_host[i] < 0 || ids_host[i] >= sp->n) {
+            set_err("as_score_items_taus: id %lld is outside [0, %lld)", (long long)ids_host[i], (long long)sp->n);
+            return AS_EINVAL;
+        }
+    AS_TRY(subset_checks("as_score_items_taus", sp, gr, d, taus, ntau));
+    if (ntau == 0) return AS_OK;
+    double lq = 0.0;
+    const as_status s = sweep_lambda(sp, gr, query, d, taus[0], &lq);
+    if (out_lambda_q) *out_lambda_q = lq;
+    if (s != AS_OK) return s;
+    if (m == 0) return AS_OK;
+    std::vector<int32_t> ids;
+    AS_TRY(checked_ids("as_score_items_taus", sp, ids_host, m, ids));
+    std::vector<double> uniq;
+    std::vector<int64_t> row, slot;
+    distinct_taus(taus, ntau, uniq, row, slot);
+    int64_t counts[2] = {0, 0};
+    as_status r;
+    {
+        std::lock_guard<std::mutex> lk(sp->smu);
+        r = score_ws_ids(sp, ids.data(), m);
+        if (r == AS_OK)
+            r = subset_sweep_run(sp, sp->score_ws, m, query, lq, uniq.data(), (int64_t)uniq.size(), row.data(), 0, nullptr, nullptr, nullptr,
+                                 out_scores, counts);
+    }
+    sweep_counts_add(sp, counts);
+    if (r != AS_OK) return r;
+    for (int64_t j = 0; j < ntau; ++j)
+        if (row[slot[j]] != j) memcpy(out_scores + j * m, out_scores + row[slot[j]] * m, sizeof(double) * (size_t)m);
+    return AS_OK;
+}
+
+// lambda_q and status of every query of a batched sweep: ONE as_search_batch call with taus[0], hits discarded (it has returned,
+// and released sp->bmu, before the caller takes the handle's mutex)
+static as_status batch_sweep_lambda(const char* who, const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d,
+                                    double tau, std::vector<double>& lq, std::vector<int32_t>& st, double* out_lambda_q, int32_t* out_status) {
+    sp->ssweep_count[0].fetch_add(1, std::memory_order_relaxed);
+    sp->ssweep_count[3].fetch_add(1, std::memory_order_relaxed);
+    AS_TRY(batch_lambda_step(who, sp, gr, queries, b, d, tau, lq, st));
+    for (int64_t i = 0; i < b; ++i) {
+        if (out_lambda_q) out_lambda_q[i] = lq[i];
+        if (out_status) out_status[i] = st[i];
+    }
+    return AS_OK;
+}
+
+as_status as_search_subset_batch_taus(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, const double* taus,
+                                      int64_t ntau, const as_subset* sub, int64_t* out_idx, double* out_score, int64_t* out_len,
+                                      double* out_lambda_q, int32_t* out_status) {
+    if (!sp || !gr || !sub || b < 0 || ntau < 0 || (b > 0 && !queries) || (ntau > 0 && !taus) ||
+        (b > 0 && ntau > 0 && (!out_len || (sub->m > 0 && (!out_idx || !out_score))))) {
+        set_err("as_search_subset_batch_taus: null argument");
+        return AS_EINVAL;
+    }
+    for (int64_t p = 0; p < b * ntau; ++p) out_len[p] = 0;
+    if (sub->sp != sp) {
+        set_err("as_search_subset_batch_taus: the subset was made for another space");
+        return AS_EINVAL;
+    }
+    AS_TRY(subset_checks("as_search_subset_batch_taus", sp, gr, d, taus, ntau));
+    if (b == 0 || ntau == 0) return AS_OK;
+    std::vector<double> lq;
+    std::vector<int32_t> st;
+    AS_TRY(batch_sweep_lambda("as_search_subset_batch_taus", sp, gr, queries, b, d, taus[0], lq, st, out_lambda_q, out_status));
+    if (sub->m == 0) return AS_OK;
+    const int64_t kk = std::min<int64_t>(std::min<int64_t>(gr->gp.topk, sp->n), sub->m);
+    std::vector<double> uniq;
+    std::vector<int64_t> row, slot;
+    distinct_taus(taus, ntau, uniq, row, slot);
+    int64_t counts[2] = {0, 0};
+    as_status r;
+    {
+        std::lock_guard<std::mutex> lk(sub->mu);
+        r = hipSetDevice(sp->device) == hipSuccess ? AS_OK : AS_EHIP;
+        if (r != AS_OK) set_err("as_search_subset_batch_taus: hipSetDevice failed");
+        else
+            r = subset_batch_sweep_run(sp, sub->w, sub->m, queries, b, lq.data(), st.data(), uniq.data(), (int64_t)uniq.size(), row.data(), ntau,
+                                       kk, out_idx, out_score, out_len, nullptr, counts);
+    }
+    sweep_counts_add(sp, counts);
+    if (r != AS_OK) return r;
+    for (int64_t i = 0; i < b; ++i)
+        for (int64_t j = 0; j < ntau; ++j) {
+            const int64_t f = i * ntau + row[slot[j]], p = i * ntau + j;
+            if (f == p) continue;
+            for (int64_t t = 0; t < out_len[f]; ++t) {
+                out_idx[p * kk + t] = out_idx[f * kk + t];
+                out_score[p * kk + t] = out_score[f * kk + t];
+            }
+            out_len[p] = out_len[f];
+        }
+    return AS_OK;
+}
+
+as_status as_score_items_batch_taus(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, const double* taus,
+                                    int64_t ntau, const int64_t* ids_host, int64_t m, double* out_scores, double* out_lambda_q,
+                                    int32_t* out_status) {
+    if (!sp || !gr || b < 0 || ntau < 0 || m < 0 || (b > 0 && !queries) || (ntau > 0 && !taus) || (m > 0 && !ids_host) ||
+        (b > 0 && ntau > 0 && m > 0 && !out_scores)) {
+        set_err("as_score_items_batch_taus: null argument");
+        return AS_EINVAL;
+    }
+    for (int64_t i = 0; i < m; ++i)
+        if (ids_host[i] < 0 || ids_host[i] >= sp->n) {
+            set_err("as_score_items_batch_taus: id %lld is outside [0, %lld)", (long long)ids_host[i], (long long)sp->n);
+            return AS_EINVAL;
+        }
+    AS_TRY(subset_checks("as_score_items_batch_taus", sp, gr, d, taus, ntau));
+    if (b == 0 || ntau == 0) return AS_OK;
+    std::vector<double> lq;
+    std::vector<int32_t> st;
+    AS_TRY(batch_sweep_lambda("as_score_items_batch_taus", sp, gr, queries, b, d, taus[0], lq, st, out_lambda_q, out_status));
+    if (m == 0) return AS_OK;
+    std::vector<int32_t> ids;
+    AS_TRY(checked_ids("as_score_items_batch_taus", sp, ids_host, m, ids));
+    std::vector<double> uniq;
+    std::vector<int64_t> row, slot;
+    distinct_taus(taus, ntau, uniq, row, slot);
+    int64_t counts[2] = {0, 0};
+    as_status r;
+    {
+        std::lock_guard<std::mutex> lk(sp->smu);
+        r = hipSetDevice(sp->device) == hipSuccess ? AS_OK : AS_EHIP;
+        if (r != AS_OK) set_err("as_score_items_batch_taus: hipSetDevice failed");
+        if (r == AS_OK) r = score_ws_ids(sp, ids.data(), m);
+        if (r == AS_OK)
+            r = subset_batch_sweep_run(sp, sp->score_ws, m, queries, b, lq.data(), st.data(), uniq.data(), (int64_t)uniq.size(), row.data(), ntau,
+                                       0, nullptr, nullptr, nullptr, out_scores, counts);
+    }
+    sweep_counts_add(sp, counts);
+    if (r != AS_OK) return r;
+    for (int64_t i = 0; i < b; ++i) {
+        if (st[i] == AS_EZEROLAMBDA) continue;   // (its rows stay unwritten)
+        for (int64_t j = 0; j < ntau; ++j)
+            if (row[slot[j]] != j)
+                memcpy(out_scores + (i * ntau + j) * m, out_scores + (i * ntau + row[slot[j]]) * m, sizeof(double) * (size_t)m);
+    }
+    return AS_OK;
+}
+
+as_status as_subset_sweep_counters(const as_space* sp, int64_t* out, int32_t n) {
+    if (!sp || !out) {
+        set_err("as_subset_sweep_counters: null argument");
+        return AS_EINVAL;
+    }
+    for (int i = 0; i < n && i < 4; ++i) out[i] = sp->ssweep_count[i].load(std::memory_order_relaxed);
+    return AS_OK;
 }
 
 // One batched tau sweep over b > 1 queries for nt <= TAU_GROUP distinct taus in [0, 1] (under sp->bmu): as_search_batch's

@@ -136,6 +136,9 @@ struct as_space {
     // as_batch_sweep_counters: [0] as_search_batch_taus calls, [1] batched passes whose scorer tail served a tau sweep, [2] (query,
     // tau) pairs such a pass served, [3] pairs it left to the single search
     mutable std::atomic<int64_t> bsweep_count[4] = {};
+    // as_subset_sweep_counters: [0] tau sweeps over a subset (all four forms), [1] score-kernel launches they made, [2] tau planes
+    // those launches wrote, [3] lambda_q steps run (single searches plus as_search_batch calls)
+    mutable std::atomic<int64_t> ssweep_count[4] = {};
     // as_score_items: the score kernel's buffers (as_subset.hip), made on first use and grown on demand; calls are serialised (smu)
     mutable struct as::SubsetWork* score_ws = nullptr;
     mutable std::mutex smu;
@@ -549,6 +552,18 @@ struct SubsetWork {
     SubsetSel* bstate = nullptr;
     int32_t* bsel_pos = nullptr;
     SubsetOut* bout = nullptr;     // pinned [bq]
+    // the tau sweeps (subset_sweep_run, subset_batch_sweep_run): made on the first sweep on this work, each grown on demand.  A
+    // (query, tau) pair takes the place of a query of the batched forms.
+    int64_t sw_nq = 0;             // queries sw_qd / sw_qh hold (the batched sweep only)
+    int64_t sw_scores_n = 0;       // doubles in sw_scores
+    int64_t sw_out_n = 0, sw_hist_n = 0;   // pairs the result / the radix buffers hold
+    double* sw_qd = nullptr;       // [sw_nq][dp] queries, zero padded, then [sw_nq] |q|^2, then [sw_nq] lambda_q
+    double* sw_qh = nullptr;       // pinned staging of the same
+    double* sw_scores = nullptr;   // [query][tau][m] score planes of one (chunk, tau group)
+    unsigned int* sw_hist = nullptr;
+    SubsetSel* sw_state = nullptr;
+    int32_t* sw_sel_pos = nullptr;
+    SubsetOut* sw_out = nullptr;   // pinned [sw_out_n]
 };
 as_status subset_work_create(const as_space* sp, int64_t cap, SubsetWork** out);
 void subset_work_free(SubsetWork* w);
@@ -564,6 +579,16 @@ as_status subset_batch_run(const as_space* sp, SubsetWork* w, int64_t m, const d
                            int64_t* out_len, double* out_scores);
 void set_subset_batch_mib(int v);   // as_set_tuning("subset_batch_mib", v)
 constexpr int QUERY_BATCH = 32;  // == GQ in as_search.hip: query slots of the batched workspace
-constexpr int TAU_GROUP = 8;     // taus one shared pass of a tau sweep serves (search_sweep, as_search_taus)
+constexpr int TAU_GROUP = 8;     // taus one shared pass of a tau sweep serves (search_sweep, as_search_taus; one gather of a subset)
+// Tau sweeps over the m ids of `w`: nt distinct finite taus, up to TAU_GROUP per gather.  The list / the
+// scores of taus[u] go to row row[u] of the outputs: k > 0: out_idx / out_score + row * k, out_len[row]; k == 0: out_scores +
+// row * m.  The batched form: rows i * ntau + row[u] for query i; status AS_EZEROLAMBDA: nothing is written for that query.
+// counts[0] += score-kernel launches, counts[1] += tau planes they wrote.  One stream wait per (chunk, tau group).
+as_status subset_sweep_run(const as_space* sp, SubsetWork* w, int64_t m, const double* query, double lambda_q, const double* taus, int64_t nt,
+                           const int64_t* row, int64_t k, int64_t* out_idx, double* out_score, int64_t* out_len, double* out_scores,
+                           int64_t* counts);
+as_status subset_batch_sweep_run(const as_space* sp, SubsetWork* w, int64_t m, const double* queries, int64_t b, const double* lq,
+                                 const int32_t* status, const double* taus, int64_t nt, const int64_t* row, int64_t ntau, int64_t k,
+                                 int64_t* out_idx, double* out_score, int64_t* out_len, double* out_scores, int64_t* counts);
 
 }  // namespace as

@@ -1,7 +1,7 @@
 // Filtered search: the exact S11 scores of a list of items gathered by id (subset_score_kernel) and the
 // exact top-k of them by (score descending, position ascending) -- a radix select over an order-preserving 96-bit key (the
 // score's bits, then the inverted position: no two keys are equal), then a one-block sort of the k selected entries.
-// Entry points: as_api.hip (as_search_subset, as_score_items).
+// Entry points: as_api.hip (as_search_subset, as_score_items; the batched forms, section 5.10; the tau sweeps, section 5.11).
 #include <algorithm>
 #include <atomic>
 #include <new>
@@ -253,6 +253,216 @@ __global__ __launch_bounds__(256) void subset_score_batch_kernel(SubsetBatchArgs
     }
 }
 
+// ------------------------------------------------------------------ tau sweep score kernels
+// Textual copies of the two score kernels above with another epilogue: the cosine of a (query, item) pair is formed once and
+// blended with each of nt <= TAU_GROUP taus.  Gather, staging, accumulation order and the cosine's operands are the originals',
+// so for the same lambda_q a plane holds the bits the single-tau kernel of the same route writes for that tau.  Copies, not a
+// shared device function: moving the originals' bodies into one changed their generated code, and they stay as they were --
+// whoever changes a loop above changes it here.  The taus and their count travel in the argument struct (scalar loads); the
+// loop over them is unrolled and predicated on the wave-uniform count.
+struct SubsetTausArgs {
+    SubsetArgs s;   // (s.tau is not read)
+    int64_t ld;     // plane j: scores + j * ld
+    int nt;
+    double taus[TAU_GROUP];
+};
+// lanes 0 .. 3 store one score per tau to the planes scores[j * ld + pos]
+template <bool F64, bool QLDS>
+__global__ __launch_bounds__(256) void subset_score_taus_kernel(SubsetTausArgs t) {
+    const SubsetArgs& a = t.s;
+    extern __shared__ double qs[];
+    if (QLDS) {
+        for (int64_t c = threadIdx.x; c < a.dp; c += blockDim.x) qs[c] = a.q64[c];
+        __syncthreads();
+    }
+    const int lane = lane_id();
+    // (the wave's number as a scalar: the id loads below are scalar loads then)
+    const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t step = (int64_t)gridDim.x * (blockDim.x >> 6) * SUB_ROWS;
+    int32_t next[SUB_ROWS];   // the ids of the next group: loaded one trip ahead, no id load in front of a trip's row loads
+#pragma unroll
+    for (int r = 0; r < SUB_ROWS; ++r) next[r] = a.ids[min(wave * SUB_ROWS + r, a.m - 1)];
+    for (int64_t g = wave * SUB_ROWS; g < a.m; g += step) {
+        int64_t row[SUB_ROWS];
+#pragma unroll
+        for (int r = 0; r < SUB_ROWS; ++r) row[r] = next[r];   // (a short last group reads its last row again)
+#pragma unroll
+        for (int r = 0; r < SUB_ROWS; ++r) next[r] = a.ids[min(g + step + r, a.m - 1)];
+        // norm and lambda of row `lane` of the group, in flight under the dot products (lanes 0 .. SUB_ROWS - 1)
+        double nrm = 0.0, lam = 0.0;
+        if (lane < SUB_ROWS) {
+            const int64_t j = lane == 0 ? row[0] : lane == 1 ? row[1] : lane == 2 ? row[2] : row[3];
+            nrm = a.n64[j];
+            lam = a.lam64[j];
+        }
+        double acc[SUB_ROWS];
+#pragma unroll
+        for (int r = 0; r < SUB_ROWS; ++r) acc[r] = 0.0;
+        if (F64) {
+            constexpr int U = 6;   // 64 doubles per load of a wave: 384 columns of 4 rows before the first FMA
+            for (int64_t base = 0; base < a.d; base += 64 * U) {
+                double v[SUB_ROWS][U];
+#pragma unroll
+                for (int r = 0; r < SUB_ROWS; ++r) {
+                    const double* pj = a.x64 + row[r] * a.d;
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        const int64_t e = base + 64 * u + lane;
+                        v[r][u] = e < a.d ? pj[e] : 0.0;
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const int64_t e = base + 64 * u + lane;
+                    if (e < a.d) {
+                        const double qv = QLDS ? qs[e] : a.q64[e];
+#pragma unroll
+                        for (int r = 0; r < SUB_ROWS; ++r) acc[r] += qv * v[r][u];
+                    }
+                }
+            }
+        } else {
+            constexpr int U = 3;   // 256 floats per load of a wave: a whole 768-float row of 4 rows before the first FMA
+            for (int64_t base = 0; base < a.dp; base += 256 * U) {
+                f32x4 v[SUB_ROWS][U];
+#pragma unroll
+                for (int r = 0; r < SUB_ROWS; ++r) {
+                    const float* pj = a.x32 + row[r] * a.dp;
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        const int64_t e = base + 256 * u + 4 * lane;   // (dp is a multiple of 32: e < dp leaves 4 floats)
+                        v[r][u] = e < a.dp ? *(const f32x4*)(pj + e) : f32x4{0, 0, 0, 0};
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const int64_t e = base + 256 * u + 4 * lane;
+                    if (e < a.dp) {
+#pragma unroll
+                        for (int t = 0; t < 4; ++t) {
+                            const double qv = QLDS ? qs[e + t] : a.q64[e + t];
+#pragma unroll
+                            for (int r = 0; r < SUB_ROWS; ++r) acc[r] += qv * (double)v[r][u][t];
+                        }
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < SUB_ROWS; ++r) acc[r] = wave_sum(acc[r]);   // (__shfl_xor butterfly: every lane holds the sums)
+        if (lane < SUB_ROWS && g + lane < a.m) {
+            const double dot = lane == 0 ? acc[0] : lane == 1 ? acc[1] : lane == 2 ? acc[2] : acc[3];
+            const double den = sqrt(nrm * a.nq);
+            const double c = den > 0.0 ? dot / den : 0.0;
+#pragma unroll
+            for (int j = 0; j < TAU_GROUP; ++j)   // (unrolled: taus[j] is a scalar load, j < nt a scalar compare)
+                if (j < t.nt) a.scores[j * t.ld + g + lane] = blend_score(t.taus[j], c, a.lq, lam);   // lanes 0 .. 3: 32 bytes a plane
+        }
+    }
+}
+
+struct SubsetBatchTausArgs {
+    SubsetBatchArgs s;   // (s.tau is not read)
+    int nt;
+    double taus[TAU_GROUP];
+};
+// plane (q, j) of the chunk at scores[(q * nt + j) * ld + pos]: a (query, tau) pair is a row of the selection kernels
+template <bool F64>
+__global__ __launch_bounds__(256) void subset_score_batch_taus_kernel(SubsetBatchTausArgs t) {
+    const SubsetBatchArgs& a = t.s;
+    constexpr int PX = F64 ? SB_PQ : SB_PF;
+    constexpr int NR = F64 ? 16 : 4;   // rows a thread stages per K stage
+    __shared__ __attribute__((aligned(16))) double qs[SB_Q * SB_PQ];
+    __shared__ __attribute__((aligned(16))) char xs_raw[SB_ROWS * PX * (F64 ? 8 : 4)];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, wi = w >> 1, wj = w & 1;
+    const int lk = lane >> 4, lc = lane & 15;
+    const int64_t row0 = (int64_t)blockIdx.x * SB_ROWS;
+    const int64_t q0 = (int64_t)blockIdx.y * SB_Q;
+    // staging maps.  fp32 rows: thread t holds floats 4 (t & 7) .. + 3 of rows (t >> 3) + 32 i; fp64 rows: double t & 31 of rows
+    // (t >> 5) + 8 i; queries: doubles 2 (t & 15), + 1 of queries (t >> 4) + 16 i
+    const int xc = F64 ? (tid & 31) : (tid & 7) * 4, xr = F64 ? (tid >> 5) : (tid >> 3), xstep = F64 ? 8 : 32;
+    const int qc = (tid & 15) * 2, qr = tid >> 4;
+    int64_t rbase[NR];   // element offset of the staged rows; -1: past the end of the list (zeros)
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+        const int64_t pos = row0 + xr + xstep * i;
+        rbase[i] = pos < a.m ? (int64_t)a.ids[pos] * (F64 ? a.d : a.dp) : -1;
+    }
+    const double* qsrc = a.q64 + (q0 + qr) * a.dp + qc;
+    f32x4 vf[F64 ? 1 : NR];
+    double vd[F64 ? NR : 1];
+    f64x2 vq[4];
+    auto load_stage = [&](int64_t k0) {
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+            if (F64) vd[i] = (rbase[i] >= 0 && k0 + xc < a.d) ? a.x64[rbase[i] + k0 + xc] : 0.0;
+            else vf[i] = rbase[i] >= 0 ? *(const f32x4*)(a.x32 + rbase[i] + k0 + xc) : f32x4{0, 0, 0, 0};
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) vq[i] = *(const f64x2*)(qsrc + (int64_t)16 * i * a.dp + k0);
+    };
+    f64x4 acc[2][4];
+#pragma unroll
+    for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+        for (int jb = 0; jb < 4; ++jb) acc[ib][jb] = f64x4{0.0, 0.0, 0.0, 0.0};
+    load_stage(0);
+    for (int64_t k0 = 0; k0 < a.dp; k0 += SB_K) {
+        __syncthreads();   // the previous stage has been consumed
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+            if (F64) ((double*)xs_raw)[(xr + xstep * i) * PX + xc] = vd[i];
+            else {
+                f32x2* dst = (f32x2*)((float*)xs_raw + (xr + xstep * i) * PX + xc);
+                dst[0] = f32x2{vf[i][0], vf[i][1]};
+                dst[1] = f32x2{vf[i][2], vf[i][3]};
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) *(f64x2*)(qs + (qr + 16 * i) * SB_PQ + qc) = vq[i];
+        __syncthreads();
+        if (k0 + SB_K < a.dp) load_stage(k0 + SB_K);   // in flight under the MFMAs below
+#pragma unroll
+        for (int ks = 0; ks < SB_K / 4; ++ks) {
+            double av[2], bv[4];
+#pragma unroll
+            for (int ib = 0; ib < 2; ++ib) av[ib] = qs[(32 * wj + 16 * ib + lc) * SB_PQ + 4 * ks + lk];
+#pragma unroll
+            for (int jb = 0; jb < 4; ++jb) {
+                const int e = (64 * wi + 16 * jb + lc) * PX + 4 * ks + lk;
+                bv[jb] = F64 ? ((const double*)xs_raw)[e] : (double)((const float*)xs_raw)[e];
+            }
+#pragma unroll
+            for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+                for (int jb = 0; jb < 4; ++jb) acc[ib][jb] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[ib], bv[jb], acc[ib][jb], 0, 0, 0);
+        }
+    }
+    // C/D of v_mfma_f64_16x16x4_f64: col = lane & 15 (position), row = (lane >> 4) + 4 reg (query)
+#pragma unroll
+    for (int jb = 0; jb < 4; ++jb) {
+        const int64_t pos = row0 + 64 * wi + 16 * jb + lc;
+        if (pos >= a.m) continue;
+        const int64_t j = a.ids[pos];
+        const double nrm = a.n64[j], lam = a.lam64[j];
+#pragma unroll
+        for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int64_t q = q0 + 32 * wj + 16 * ib + lk + 4 * r;
+                if (q < a.nq_valid) {
+                    const double den = sqrt(nrm * a.nq[q]);
+                    const double c = den > 0.0 ? acc[ib][jb][r] / den : 0.0;
+                    const double lq = a.lq[q];
+                    double* dst = a.scores + q * t.nt * a.ld + pos;   // plane (q, j): 16 lanes store 128 contiguous bytes
+#pragma unroll
+                    for (int u = 0; u < TAU_GROUP; ++u)
+                        if (u < t.nt) dst[u * a.ld] = blend_score(t.taus[u], c, lq, lam);
+                }
+            }
+    }
+}
+
 // ------------------------------------------------------------------ selection
 // Key of the entry at position i: 96 bits, hi = the score's bits mapped so that a larger score is a larger number (NaN lowest,
 // -0 as +0), lo = ~i (a smaller position is a larger number).  The k-th largest key T is found digit by digit, SEL_BITS bits a
@@ -478,6 +688,22 @@ static void subset_batch_release(SubsetWork* w) {
     w->bsel = w->bhist_on = false;
 }
 
+static void subset_sweep_release(SubsetWork* w) {
+    (void)hipFree(w->sw_qd);
+    (void)hipFree(w->sw_scores);
+    (void)hipFree(w->sw_hist);
+    (void)hipFree(w->sw_state);
+    (void)hipFree(w->sw_sel_pos);
+    if (w->sw_qh) (void)hipHostFree(w->sw_qh);
+    if (w->sw_out) (void)hipHostFree(w->sw_out);
+    w->sw_qd = w->sw_qh = w->sw_scores = nullptr;
+    w->sw_hist = nullptr;
+    w->sw_state = nullptr;
+    w->sw_sel_pos = nullptr;
+    w->sw_out = nullptr;
+    w->sw_nq = w->sw_scores_n = w->sw_out_n = w->sw_hist_n = 0;
+}
+
 void subset_work_free(SubsetWork* w) {
     if (!w) return;
     (void)hipSetDevice(w->device);
@@ -491,6 +717,7 @@ void subset_work_free(SubsetWork* w) {
     if (w->hq) (void)hipHostFree(w->hq);
     if (w->out) (void)hipHostFree(w->out);
     subset_batch_release(w);
+    subset_sweep_release(w);
     for (int i = 0; i < 2; ++i)
         if (w->ev[i]) (void)hipEventDestroy(w->ev[i]);
     if (w->stream) (void)hipStreamDestroy(w->stream);
@@ -754,6 +981,236 @@ as_status subset_batch_run(const as_space* sp, SubsetWork* w, int64_t m, const d
                 }
                 out_len[i] = k;
             }
+    }
+    return AS_OK;
+}
+
+// ------------------------------------------------------------------ tau sweeps
+// The sweep's buffers: nq queries (the batched sweep; 0: none), `pairs` score planes of m doubles, and for a selection one
+// pinned result per pair (sel) and the radix select's histograms, state and positions per pair (hist).
+static as_status subset_sweep_reserve(SubsetWork* w, int64_t nq, int64_t pairs, int64_t m, bool sel, bool hist) {
+    hipError_t e = hipSuccess;
+    const char* what = "queries";
+    if (nq > w->sw_nq) {
+        (void)hipFree(w->sw_qd);
+        if (w->sw_qh) (void)hipHostFree(w->sw_qh);
+        w->sw_qd = w->sw_qh = nullptr;
+        w->sw_nq = 0;
+        const size_t qbytes = sizeof(double) * (size_t)nq * (size_t)(w->dp + 2);
+        if ((e = hipMalloc((void**)&w->sw_qd, qbytes)) == hipSuccess && (e = hipHostMalloc((void**)&w->sw_qh, qbytes, hipHostMallocDefault)) == hipSuccess)
+            w->sw_nq = nq;
+    }
+    if (e == hipSuccess && pairs * m > w->sw_scores_n) {
+        what = "scores";
+        (void)hipFree(w->sw_scores);
+        w->sw_scores = nullptr;
+        w->sw_scores_n = 0;
+        if ((e = hipMalloc((void**)&w->sw_scores, sizeof(double) * (size_t)(pairs * m))) == hipSuccess) w->sw_scores_n = pairs * m;
+    }
+    if (e == hipSuccess && sel && pairs > w->sw_out_n) {
+        what = "results";
+        if (w->sw_out) (void)hipHostFree(w->sw_out);
+        w->sw_out = nullptr;
+        w->sw_out_n = 0;
+        if ((e = hipHostMalloc((void**)&w->sw_out, sizeof(SubsetOut) * (size_t)pairs, hipHostMallocDefault)) == hipSuccess) w->sw_out_n = pairs;
+    }
+    if (e == hipSuccess && hist && pairs > w->sw_hist_n) {
+        what = "selection";
+        (void)hipFree(w->sw_hist);
+        (void)hipFree(w->sw_state);
+        (void)hipFree(w->sw_sel_pos);
+        w->sw_hist = nullptr;
+        w->sw_state = nullptr;
+        w->sw_sel_pos = nullptr;
+        w->sw_hist_n = 0;
+        if ((e = hipMalloc((void**)&w->sw_hist, sizeof(unsigned int) * SEL_HIST_WORDS * (size_t)pairs)) == hipSuccess &&
+            (e = hipMalloc((void**)&w->sw_state, sizeof(SubsetSel) * (SEL_PASSES + 1) * (size_t)pairs)) == hipSuccess &&
+            (e = hipMalloc((void**)&w->sw_sel_pos, sizeof(int32_t) * SUBSET_TOPK * (size_t)pairs)) == hipSuccess)
+            w->sw_hist_n = pairs;
+    }
+    if (e != hipSuccess) {
+        set_err("subset: allocation of the sweep buffers (%s, %lld planes x %lld ids) failed: %s", what, (long long)pairs, (long long)m,
+                hipGetErrorString(e));
+        subset_sweep_release(w);
+        return e == hipErrorOutOfMemory ? AS_ENOMEM : AS_EHIP;
+    }
+    return AS_OK;
+}
+
+// the first k of each of the `pairs` score planes (stride m) -> w->sw_out[pair]: the batched forms' selection kernels with a
+// (query, tau) pair per blockIdx.y.  m <= SUBSET_TOPK: the sort alone; else one memset, the radix passes, collect and sort.
+static as_status subset_sweep_select(SubsetWork* w, int64_t m, int64_t k, int64_t pairs) {
+    const unsigned ny = (unsigned)pairs;
+    if (m <= SUBSET_TOPK) {
+        hipLaunchKernelGGL(subset_sort_batch_kernel, dim3(1, ny), dim3(1024), 0, w->stream, (const double*)w->sw_scores, m, (const int32_t*)w->ids,
+                           m, (int)k, (const int32_t*)nullptr, (const unsigned int*)nullptr, w->sw_out);
+    } else {
+        AS_HIP(hipMemsetAsync(w->sw_hist, 0, sizeof(unsigned int) * SEL_HIST_WORDS * (size_t)pairs, w->stream));
+        const unsigned gx = (unsigned)std::min<int64_t>((m + 2047) / 2048, 512);
+        for (int p = 0; p < SEL_PASSES; ++p)
+            hipLaunchKernelGGL(subset_hist_batch_kernel, dim3(gx, ny), dim3(256), 0, w->stream, (const double*)w->sw_scores, m, m, (int)k, p,
+                               w->sw_state, w->sw_hist);
+        hipLaunchKernelGGL(subset_collect_batch_kernel, dim3(gx, ny), dim3(256), 0, w->stream, (const double*)w->sw_scores, m, m, (int)k,
+                           w->sw_state, w->sw_hist, w->sw_sel_pos);
+        hipLaunchKernelGGL(subset_sort_batch_kernel, dim3(1, ny), dim3(1024), 0, w->stream, (const double*)w->sw_scores, m, (const int32_t*)w->ids,
+                           m, (int)k, (const int32_t*)w->sw_sel_pos, (const unsigned int*)w->sw_hist, w->sw_out);
+    }
+    AS_HIP(hipGetLastError());
+    return AS_OK;
+}
+
+static as_status subset_sweep_wait(SubsetWork* w) {
+    AS_HIP(hipStreamSynchronize(w->stream));
+    if (w->timing) {
+        float ms = 0.0f;
+        AS_HIP(hipEventElapsedTime(&ms, w->ev[0], w->ev[1]));
+        w->kernel_us += (double)ms * 1e3;
+    }
+    return AS_OK;
+}
+
+static as_status subset_sweep_list(const SubsetOut* o, int64_t k, int64_t* out_idx, double* out_score, int64_t* out_len) {
+    if (o->len != k) {
+        set_err("subset: the selection returned %lld of %lld entries", (long long)o->len, (long long)k);
+        return AS_EHIP;
+    }
+    for (int64_t r = 0; r < k; ++r) {
+        out_idx[r] = o->idx[r];
+        out_score[r] = o->score[r];
+    }
+    *out_len = k;
+    return AS_OK;
+}
+
+as_status subset_sweep_run(const as_space* sp, SubsetWork* w, int64_t m, const double* query, double lambda_q, const double* taus, int64_t nt,
+                           const int64_t* row, int64_t k, int64_t* out_idx, double* out_score, int64_t* out_len, double* out_scores,
+                           int64_t* counts) {
+    if (m <= 0 || nt <= 0) return AS_OK;
+    const bool sel = k > 0;
+    if (sel) k = std::min<int64_t>(std::min<int64_t>(k, m), SUBSET_TOPK);
+    const int64_t gmax = std::min<int64_t>(nt, TAU_GROUP);
+    AS_TRY(subset_sweep_reserve(w, 0, gmax, m, sel, sel && m > SUBSET_TOPK));
+    for (int64_t c = 0; c < sp->d; ++c) w->hq[c] = query[c];   // (the pad stays zero)
+    AS_HIP(hipMemcpyAsync(w->q64, w->hq, sizeof(double) * w->dp, hipMemcpyHostToDevice, w->stream));
+    SubsetTausArgs a;
+    a.s.ids = w->ids; a.s.m = m; a.s.x32 = sp->x32; a.s.x64 = sp->x64; a.s.n64 = sp->n64; a.s.lam64 = sp->lam64; a.s.q64 = w->q64;
+    a.s.scores = w->sw_scores; a.s.d = sp->d; a.s.dp = sp->dp; a.s.nq = subset_query_norm(query, sp->d); a.s.lq = lambda_q; a.s.tau = 0.0;
+    a.ld = m;
+    const int64_t groups = (m + SUB_ROWS - 1) / SUB_ROWS;   // (the grid of subset_score)
+    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((groups + 3) / 4, (int64_t)w->cus * SUB_BLOCKS_PER_CU));
+    const bool qlds = sp->dp <= SUB_Q_LDS;
+    const size_t lds = qlds ? sizeof(double) * (size_t)sp->dp : 0;
+    w->kernel_us = 0.0;
+    for (int64_t g0 = 0; g0 < nt; g0 += TAU_GROUP) {
+        const int64_t ng = std::min<int64_t>(TAU_GROUP, nt - g0);
+        a.nt = (int)ng;
+        for (int64_t j = 0; j < TAU_GROUP; ++j) a.taus[j] = j < ng ? taus[g0 + j] : 0.0;
+        if (w->timing) AS_HIP(hipEventRecord(w->ev[0], w->stream));
+        if (sp->x64) {
+            if (qlds) hipLaunchKernelGGL((subset_score_taus_kernel<true, true>), dim3(grid), dim3(256), lds, w->stream, a);
+            else hipLaunchKernelGGL((subset_score_taus_kernel<true, false>), dim3(grid), dim3(256), 0, w->stream, a);
+        } else {
+            if (qlds) hipLaunchKernelGGL((subset_score_taus_kernel<false, true>), dim3(grid), dim3(256), lds, w->stream, a);
+            else hipLaunchKernelGGL((subset_score_taus_kernel<false, false>), dim3(grid), dim3(256), 0, w->stream, a);
+        }
+        AS_HIP(hipGetLastError());
+        if (w->timing) AS_HIP(hipEventRecord(w->ev[1], w->stream));
+        counts[0] += 1;
+        counts[1] += ng;
+        if (sel) AS_TRY(subset_sweep_select(w, m, k, ng));
+        else
+            for (int64_t j = 0; j < ng; ++j)
+                AS_HIP(hipMemcpyAsync(out_scores + row[g0 + j] * m, w->sw_scores + j * m, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, w->stream));
+        AS_TRY(subset_sweep_wait(w));
+        if (sel)
+            for (int64_t j = 0; j < ng; ++j) {
+                const int64_t r = row[g0 + j];
+                AS_TRY(subset_sweep_list(w->sw_out + j, k, out_idx + r * k, out_score + r * k, out_len + r));
+            }
+    }
+    return AS_OK;
+}
+
+as_status subset_batch_sweep_run(const as_space* sp, SubsetWork* w, int64_t m, const double* queries, int64_t b, const double* lq,
+                                 const int32_t* status, const double* taus, int64_t nt, const int64_t* row, int64_t ntau, int64_t k,
+                                 int64_t* out_idx, double* out_score, int64_t* out_len, double* out_scores, int64_t* counts) {
+    if (m <= 0 || b <= 0 || nt <= 0) return AS_OK;
+    const bool sel = k > 0;
+    if (sel) k = std::min<int64_t>(std::min<int64_t>(k, m), SUBSET_TOPK);
+    // taus per group: the planes of one query tile fit the budget; queries per chunk: subset_batch_run's rule over m * tg scores
+    // a query, the pairs of a chunk at most SB_QC_MAX
+    const int64_t budget = (int64_t)g_subset_batch_mib.load(std::memory_order_relaxed) << 20;
+    int64_t tg = budget / (SB_Q * m * (int64_t)sizeof(double));
+    tg = std::min<int64_t>(std::min<int64_t>(std::max<int64_t>(tg, 1), TAU_GROUP), nt);
+    int64_t qc = budget / (m * tg * (int64_t)sizeof(double)) / SB_Q * SB_Q;
+    qc = std::min<int64_t>(std::max<int64_t>(qc, SB_Q), SB_QC_MAX / tg / SB_Q * SB_Q);
+    qc = std::min<int64_t>(qc, (b + SB_Q - 1) / SB_Q * SB_Q);
+    AS_TRY(subset_sweep_reserve(w, qc, qc * tg, m, sel, sel && m > SUBSET_TOPK));
+    const int64_t d = sp->d, dp = w->dp;
+    w->kernel_us = 0.0;
+    for (int64_t i0 = 0; i0 < b; i0 += qc) {
+        const int64_t nb = std::min<int64_t>(qc, b - i0), nbp = (nb + SB_Q - 1) / SB_Q * SB_Q;
+        double* hq = w->sw_qh;
+        double* hn = hq + nbp * dp;
+        double* hl = hn + nbp;
+        for (int64_t t = 0; t < nbp; ++t) {   // (the staging of subset_batch_run: the same |q|^2, the same operands)
+            double* qrow = hq + t * dp;
+            if (t < nb) {
+                const double* q = queries + (i0 + t) * d;
+                for (int64_t c = 0; c < d; ++c) qrow[c] = q[c];
+                for (int64_t c = d; c < dp; ++c) qrow[c] = 0.0;
+                hn[t] = subset_query_norm(q, d);
+                hl[t] = lq[i0 + t];
+            } else {
+                for (int64_t c = 0; c < dp; ++c) qrow[c] = 0.0;
+                hn[t] = hl[t] = 0.0;
+            }
+        }
+        AS_HIP(hipMemcpyAsync(w->sw_qd, hq, sizeof(double) * (size_t)(nbp * (dp + 2)), hipMemcpyHostToDevice, w->stream));
+        SubsetBatchTausArgs a;
+        a.s.ids = w->ids; a.s.m = m; a.s.x32 = sp->x32; a.s.x64 = sp->x64; a.s.n64 = sp->n64; a.s.lam64 = sp->lam64; a.s.q64 = w->sw_qd;
+        a.s.nq = w->sw_qd + nbp * dp; a.s.lq = a.s.nq + nbp; a.s.scores = w->sw_scores; a.s.ld = m; a.s.d = d; a.s.dp = dp;
+        a.s.nq_valid = (int)nb; a.s.tau = 0.0;
+        const dim3 grid((unsigned)((m + SB_ROWS - 1) / SB_ROWS), (unsigned)(nbp / SB_Q));
+        for (int64_t g0 = 0; g0 < nt; g0 += tg) {
+            const int64_t ng = std::min<int64_t>(tg, nt - g0);
+            a.nt = (int)ng;
+            for (int64_t j = 0; j < TAU_GROUP; ++j) a.taus[j] = j < ng ? taus[g0 + j] : 0.0;
+            if (w->timing) AS_HIP(hipEventRecord(w->ev[0], w->stream));
+            if (sp->x64) hipLaunchKernelGGL(subset_score_batch_taus_kernel<true>, grid, dim3(256), 0, w->stream, a);
+            else hipLaunchKernelGGL(subset_score_batch_taus_kernel<false>, grid, dim3(256), 0, w->stream, a);
+            AS_HIP(hipGetLastError());
+            if (w->timing) AS_HIP(hipEventRecord(w->ev[1], w->stream));
+            counts[0] += 1;
+            counts[1] += ng;
+            if (sel) AS_TRY(subset_sweep_select(w, m, k, nb * ng));
+            else {
+                // plane j of every query of a run in one strided copy; a zero-lambda query's rows stay unwritten: runs split around it
+                for (int64_t t = 0; t < nb;) {
+                    if (status[i0 + t] == AS_EZEROLAMBDA) {
+                        ++t;
+                        continue;
+                    }
+                    int64_t u = t;
+                    while (u < nb && status[i0 + u] != AS_EZEROLAMBDA) ++u;
+                    for (int64_t j = 0; j < ng; ++j)
+                        AS_HIP(hipMemcpy2DAsync(out_scores + ((i0 + t) * ntau + row[g0 + j]) * m, sizeof(double) * (size_t)(ntau * m),
+                                                w->sw_scores + (t * ng + j) * m, sizeof(double) * (size_t)(ng * m), sizeof(double) * (size_t)m,
+                                                (size_t)(u - t), hipMemcpyDeviceToHost, w->stream));
+                    t = u;
+                }
+            }
+            AS_TRY(subset_sweep_wait(w));
+            if (sel)
+                for (int64_t t = 0; t < nb; ++t) {
+                    const int64_t i = i0 + t;
+                    if (status[i] == AS_EZEROLAMBDA) continue;   // (its out_len entries are zero already)
+                    for (int64_t j = 0; j < ng; ++j) {
+                        const int64_t r = i * ntau + row[g0 + j];
+                        AS_TRY(subset_sweep_list(w->sw_out + t * ng + j, k, out_idx + r * k, out_score + r * k, out_len + r));
+                    }
+                }
+        }
     }
     return AS_OK;
 }
