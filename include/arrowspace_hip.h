@@ -295,7 +295,29 @@ as_status as_search_batch(const as_space* sp, const as_graph* gr, const double* 
 
 /* ---- staged search (row-sharded multi-GPU; as_search composes these on one GPU) ---- */
 
-/* fixed-size device records exchanged between ranks */
+/* fixed-size device records exchanged between ranks.
+ * THE TWO MERGES (as_query_lambda / _batch over as_knn_rec, as_query_finish / _batch over as_hit_rec; both run identically on
+ * every rank over the all-gathered records; tests/test_gpu_staged_records.py states all of it against oracle/oracle_np.py):
+ *   - an EMPTY slot is idx == -1, anywhere in the buffer; none of its other fields is ever read, whatever they hold;
+ *   - k-NN records are ordered by (key ascending, idx ascending) and the first k valid ones are the query's neighbours: lambda_q
+ *     comes from their dist / gy / deg / ny alone, summed in that order (the same bits whatever the layout of the records);
+ *     hit records by (score descending, idx ascending; +0.0 and -0.0 tie), cut at topk; a valid hit may carry -inf;
+ *   - at most as_record_capacity(0) = 1 024 k-NN records (ranks x k) and as_record_capacity(1) = 8 208 hit records
+ *     (ranks x (topk + 1)) per query; one more returns AS_EUNSUPPORTED and nothing is launched: the workspace keeps the state of
+ *     the previous step;
+ *   - a hit record with idx == -2 is a FLAG record: (int)score holds bits, OR-ed over all such records of the merge (none at
+ *     all = 0) and with the flags of the workspace's own scan.  1: the k-NN list is not provably exact, 2: nor the scorer's
+ *     (as_query_flags bit 0 of knn_inexact / score_inexact), 4: the k-NN candidate buffer overflowed, 8: the scorer's (bit 1
+ *     of the same), 16: a rank's candidates did not fit its one-exchange block (as_query_x1_redo), 32: a rank failed its part
+ *     of as_query_search_staged -- neither of the last two shows in as_query_flags.  The batched finish reports a slot with any
+ *     bit as out_status -1, out_len 0;
+ *   - NO id may occur twice among the valid records of one merge (the ranks own disjoint rows): two equal (key, idx) or
+ *     (score, idx) pairs would take the same rank and leave the place behind it unwritten.  Ids are below 2^31 - 1;
+ *   - m == 0 (any non-null pointer), only empty slots, weights that all underflow or edge energies that are all zero give
+ *     lambda_q == 0: the following finish returns AS_EZEROLAMBDA, out_len 0, whatever hit records it is handed;
+ *   - under AS_LAMBDA_FEATURE as_query_lambda / _batch are no-ops behind their checks: lambda_q is the scan's;
+ *   - per as_query_scan: as_query_lambda and as_query_finish may be repeated, as_query_score runs ONCE (the scorer appends
+ *     its candidates behind the previous call's until a scan resets the count). */
 typedef struct {
     int64_t idx;  /* global item index, -1 = empty slot */
     double key;   /* eps-test / ordering key: squared L2 distance or cosine distance */

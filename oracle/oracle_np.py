@@ -406,7 +406,6 @@ def query_neighbours(idx: dict, q, r0=0, r1=None):
 
 def lambda_from_neighbours(idx: dict, q, items, dist, gy, deg=None, ny=None) -> float:
     """SPEC S10, second half: q appended as a node with the given neighbours."""
-    prm = idx["prm"]
     q = np.asarray(q, dtype=np.float64)
     nq = float(q @ q)
     if len(items) == 0:
@@ -415,6 +414,15 @@ def lambda_from_neighbours(idx: dict, q, items, dist, gy, deg=None, ny=None) -> 
     items, dist, gy = np.asarray(items)[o], np.asarray(dist)[o], np.asarray(gy)[o]
     deg = idx["deg"][items] if deg is None else np.asarray(deg)[o]
     ny = idx["ny"][items] if ny is None else np.asarray(ny)[o]
+    return neighbour_lambda(idx["prm"], idx["tau0"], nq, dist, gy, deg, ny)
+
+
+def neighbour_lambda(prm, tau0, nq, dist, gy, deg, ny) -> float:
+    """SPEC S10, second half, on the neighbours' pair quantities alone: dist / gy of q against each neighbour, the
+    neighbour's degree in the index graph and |y|^2, summed in the order given."""
+    if len(dist) == 0:
+        return 0.0
+    dist, gy, deg, ny = (np.asarray(a, dtype=np.float64) for a in (dist, gy, deg, ny))
     a = _edge_weight(dist, prm["sigma"], prm["p"], prm["kernel"])
     degq = 0.0
     for v in a:
@@ -425,9 +433,8 @@ def lambda_from_neighbours(idx: dict, q, items, dist, gy, deg=None, ny=None) -> 
     if not nyq > 0.0:
         return 0.0
     es = []
-    for t in range(len(items)):
+    for t in range(len(dist)):
         dj = deg[t] + a[t]
-        sdd = np.sqrt(degq * dj)
         es.append(edge_energy(a[t], prm["metric"], dist[t], gy[t], degq, dj, nyq, ny[t]))
     S = 0.0
     for v in es:
@@ -439,8 +446,41 @@ def lambda_from_neighbours(idx: dict, q, items, dist, gy, deg=None, ny=None) -> 
             r = v / S
             Gq += r * r
         Gq = min(1.0, max(0.0, Gq))
-    tau0 = idx["tau0"]
     return float(tau0 * (Eq / (Eq + tau0)) + (1.0 - tau0) * Gq)
+
+
+# ---- the two record merges of a row-sharded search (as_query_lambda / as_query_finish and their batched forms), on the
+# records as they lie in memory: (m, 6) / (m, 2) float64 arrays in as_knn_rec / as_hit_rec layout
+# (include/arrowspace_hip.h), column 0 = the int64 id as a bit pattern.
+def rec_ids(recs):
+    """Column 0 of a record array as int64 ids."""
+    return np.ascontiguousarray(np.asarray(recs, dtype=np.float64)[:, 0]).view(np.int64)
+
+
+def staged_lambda(prm, tau0, nq, recs, k):
+    """lambda_q from m all-gathered as_knn_rec: slots with id < 0 are empty whatever else they hold; the valid ones are
+    ordered by (key ascending, id ascending), the first k are the neighbours, and SPEC S10's second half runs on their
+    dist / gy / deg / ny (summed in id order, as lambda_from_neighbours).  -> (lambda_q, ids kept in rank order)."""
+    recs = np.asarray(recs, dtype=np.float64).reshape(-1, 6)
+    ids = rec_ids(recs)
+    ok = np.nonzero(ids >= 0)[0]
+    sel = ok[np.lexsort((ids[ok], recs[ok, 1]))][:k]
+    s = sel[np.argsort(ids[sel], kind="stable")]
+    return neighbour_lambda(prm, tau0, nq, recs[s, 2], recs[s, 3], recs[s, 4], recs[s, 5]), ids[sel]
+
+
+def staged_merge(hits, topk):
+    """The answer from m all-gathered as_hit_rec: id >= 0 ranked by (score descending, id ascending) and cut at topk; id == -2
+    carries flag bits in its score (several are OR-ed); id == -1 is an empty slot whatever its score.
+    -> ([(id, score)], flags)."""
+    hits = np.asarray(hits, dtype=np.float64).reshape(-1, 2)
+    ids = rec_ids(hits)
+    ok = np.nonzero(ids >= 0)[0]
+    o = ok[np.lexsort((ids[ok], -hits[ok, 1]))][:topk]
+    flags = 0
+    for s in hits[ids == -2, 1]:
+        flags |= int(s)
+    return [(int(ids[t]), float(hits[t, 1])) for t in o], flags
 
 
 def query_lambda(idx: dict, q) -> float:

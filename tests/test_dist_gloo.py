@@ -221,13 +221,7 @@ class OracleEngine:
         self.knn_local.copy_(__import__("torch").from_numpy(rec))
 
     def query_lambda(self, knn_all):
-        r = knn_all.numpy()
-        ids = r[:, 0].copy().view(np.int64)
-        ok = ids >= 0
-        ids, key = ids[ok], r[ok, 1]
-        o = np.lexsort((ids, key))[: self.k]
-        sel = np.nonzero(ok)[0][o]
-        self.lq = self.o.lambda_from_neighbours(self.index, self.q, ids[o], r[sel, 2], r[sel, 3], r[sel, 4], r[sel, 5])
+        self.lq, _ = self.o.staged_lambda(self.prm, self.index["tau0"], float(self.q @ self.q), knn_all.numpy(), self.k)
 
     def query_score(self, tau):
         rec = np.zeros((self.topk + 1, 2))
@@ -243,12 +237,7 @@ class OracleEngine:
         self.hits_local.copy_(__import__("torch").from_numpy(rec))
 
     def query_finish(self, hits_all):
-        r = hits_all.numpy()
-        ids = r[:, 0].copy().view(np.int64)
-        ok = ids >= 0
-        ids, sc = ids[ok], r[ok, 1]
-        o = np.lexsort((ids, -sc))[: self.topk]
-        hits = [(int(ids[t]), float(sc[t])) for t in o]
+        hits, _flags = self.o.staged_merge(hits_all.numpy(), self.topk)
         return hits, self.lq, self.lq == 0.0, False, False
 
     # ---- batched staged search: the single-query steps slot by slot, in the [slot][...] record layout
