@@ -458,6 +458,8 @@ void as_enable_search_stats(int32_t enabled);
 /* Measurement knob, no reference counterpart: launch parameters the library otherwise picks itself.  "tile_geom" = <blocks per
  * CU><two digits: ring KiB per wave> of the single query's tile scan (e.g. 406, 308, 216; ARROWSPACE_TILE_GEOM at load);
  * "x1_blocks" = blocks of the coarse scan's exact-evaluation kernel (16 .. 256, default 128).
+ * "x1_final_rank" = 1 / 0: the fused tail's final kernel / its first kernel's last block ranks the rows inside eps, for every
+ * workspace; any other value: each workspace's own switch again (ARROWSPACE_X1_FINAL_RANK when it was made; default 1).
  * "subset_batch_mib" = MiB of scores one chunk of queries of the batched filtered forms may hold (default 256; <= 0: the default).
  * Returns 0, or 1 for an unknown key.  Results never depend on it. */
 int32_t as_set_tuning(const char* key, int32_t value);

@@ -243,7 +243,9 @@ struct as_query {
     as_hit_rec* hits_all = nullptr;      // [world][topk + 1] gathered hit records
     char* xsend = nullptr;               // one-exchange pass: this rank's block (as_query_x1_bytes) ...
     char* xall = nullptr;                // ... and the gathered blocks of all ranks
-    int x1_off = 0;                      // the one-exchange pass is switched off for this workspace (ARROWSPACE_STAGED_X1=0 when it was made; as_query_set_x1)
+    int x1_final_rank = 1;               // the fused tail's final kernel ranks the k-NN entries (0: the first kernel's last block does; ARROWSPACE_X1_FINAL_RANK when
+                                         // the workspace was made, as_set_tuning("x1_final_rank") over it; results never depend on it)
+    int x1_off = 0;                     // the one-exchange pass is switched off for this workspace (ARROWSPACE_STAGED_X1=0 when it was made; as_query_set_x1)
     int64_t x1_passes = 0;               // one-exchange passes this workspace has finished
     void* x1_head = nullptr;             // header of the block the last pass wrote (left zeroed by its finish kernel)
     int x1_dirty = 1;                    // ... unless that pass never reached its finish
@@ -338,6 +340,7 @@ as_status launch_scan_gang(as_query* const* m, const PreArgs* pre, int n, hipStr
 void set_tile_geom(int v);
 void set_tile_dyn(int v);
 void set_x1_blocks(int v);
+void set_x1_final_rank(int v);   // as_set_tuning("x1_final_rank", 0 | 1): over every workspace's own switch; any other value hands it back to them
 as_status set_scan_attrs();   // per-device dynamic-LDS opt-in of the scan kernels
 
 }  // namespace as

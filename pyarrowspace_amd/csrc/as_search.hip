@@ -18,16 +18,24 @@ namespace as {
 static std::atomic<int> g_search_stats{0};
 
 // In-kernel phase stamps of the two single-block finish kernels (diagnostic build only: make STAMPS=1; no stamp
-// executes in the product library).  100 MHz wall clock; slots 0..15 knn_finish, 16..31 score_finish.
+// executes in the product library).  100 MHz wall clock; slots 0..15 knn_finish, 16..31 score_finish, 32..35 block 0 of
+// staged_x1_kernel (start, lists gathered, rows evaluated, filed), 36..42 staged_x1_final_kernel (start, pulled, records ranked,
+// lambda_q, scored, ranked, published).
 #ifdef AS_STAMPS
-__device__ unsigned long long g_stamps[32];
+constexpr int AS_NSTAMPS = 48;
+__device__ unsigned long long g_stamps[AS_NSTAMPS];
 #define AS_STAMP(i)                                                           \
     do {                                                                      \
         if (threadIdx.x == 0 && blockIdx.z == 0) g_stamps[i] = wall_clock64(); \
     } while (0)
+#define AS_STAMP_B0(i)                                                                            \
+    do {                                                                                          \
+        if (threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.z == 0) g_stamps[i] = wall_clock64(); \
+    } while (0)
 #define AS_STAMP_VAL(i, v) do { g_stamps[i] = (unsigned long long)(v); } while (0)
 #else
 #define AS_STAMP(i) do {} while (0)
+#define AS_STAMP_B0(i) do {} while (0)
 #define AS_STAMP_VAL(i, v) do {} while (0)
 #endif
 
@@ -1407,12 +1415,12 @@ struct FinishArgs {
 
 // SPEC S10 given the selected neighbours in LDS in (key, index) rank order; one wave, lane t
 // owns neighbour t, sums are fixed-order butterflies (deterministic).
-__device__ __forceinline__ void lambda_from_sorted(int cnt, const double* s_dist, const double* s_gy, const double* s_deg,
-                                                   const double* s_ny, int metric, int kernel, double sigma, double p,
-                                                   double tau0, QInfo* info) {
+// (nq = info->nq, handed in by a caller that loaded it early; returns lambda_q, the same value in every lane)
+__device__ __forceinline__ double lambda_from_sorted_nq(int cnt, const double* s_dist, const double* s_gy, const double* s_deg,
+                                                        const double* s_ny, int metric, int kernel, double sigma, double p,
+                                                        double tau0, double nq, QInfo* info) {
     // lane t owns neighbours t and 64 + t (k up to 120); every sum adds a lane's two terms, then runs the fixed butterfly
     const int lane = lane_id();
-    const double nq = info->nq;
     const double nyq = metric == AS_METRIC_L2 ? nq : (nq > 0.0 ? 1.0 : 0.0);
     const bool on0 = lane < cnt, on1 = 64 + lane < cnt;
     const double at0 = on0 ? edge_weight(s_dist[lane], sigma, p, kernel) : 0.0;
@@ -1437,6 +1445,12 @@ __device__ __forceinline__ void lambda_from_sorted(int cnt, const double* s_dist
         info->lambda_q = lam;
         info->status = lam == 0.0 ? AS_EZEROLAMBDA : AS_OK;
     }
+    return lam;
+}
+__device__ __forceinline__ void lambda_from_sorted(int cnt, const double* s_dist, const double* s_gy, const double* s_deg,
+                                                   const double* s_ny, int metric, int kernel, double sigma, double p,
+                                                   double tau0, QInfo* info) {
+    lambda_from_sorted_nq(cnt, s_dist, s_gy, s_deg, s_ny, metric, kernel, sigma, p, tau0, info->nq, info);
 }
 
 // k-NN of the query: candidates -> M smallest fp32 keys -> fp64 re-evaluation -> (key64, idx)
@@ -2111,21 +2125,210 @@ constexpr int X1_BLOCKS_COARSE = 128; // blocks of the coarse scan's tail: score
 constexpr int X1_LOCAL_CAP = 4096;   // candidates one block gathers from its share of the scan's reports
 static std::atomic<int> g_x1_blocks{X1_BLOCKS_COARSE};   // measurement: as_set_tuning("x1_blocks", v), 16 .. 256
 void set_x1_blocks(int v) { g_x1_blocks.store(v < 16 ? 16 : (v > 256 ? 256 : v), std::memory_order_relaxed); }
+// who ranks the k-NN entries of the fused tail (one space): 1 the final kernel, 0 the first kernel's last block (the form before),
+// -1 each workspace's own switch (ARROWSPACE_X1_FINAL_RANK when it was made).  A/B and tests: results never depend on it.
+static std::atomic<int> g_x1_final_rank{-1};
+void set_x1_final_rank(int v) { g_x1_final_rank.store(v == 0 || v == 1 ? v : -1, std::memory_order_relaxed); }
+static bool x1_final_ranks(const as_query* q) {
+    const int g = g_x1_final_rank.load(std::memory_order_relaxed);
+    return (g >= 0 ? g : q->x1_final_rank) != 0;
+}
 
 // grid 1 + X1_BLOCKS: block 0 = knn_finish (records into the exchange block), blocks 1.. = the scan waves' reports -> exact
 // cosines.  The two halves do not depend on each other: the k-NN phase (17 us, one block) hides the candidates' evaluation.
 // xk != null (the coarse scan: k-NN candidates by the hundred, every one of them to be evaluated exactly): no k-NN block --
 // every block takes its share of the k-NN candidate buffer as well and appends (id, exact key, distance, gy) of the candidates
-// inside eps to xk; the last block to finish ranks them and writes the records (below).
+// inside eps to xk; staged_x1_final_kernel ranks them and writes the records (final_ranks: the fused tail of one space), or the
+// last block to finish here does (below).
 struct XKnn {
     int idx;   // local row
     int pad;
     double key, dist, gy;
+    double deg, ny;   // of the row (graph side): what a record needs beside the three above, so that whoever ranks gathers nothing
 };
+static_assert(sizeof(XKnn) == 48, "XKnn: x1_launch_block sizes q->xknn by it");
+
+// The ranking of the entries inside eps, for both of its callers -- the last block of staged_x1_kernel (NT = 1024) and the
+// ranking waves of staged_x1_final_kernel (NT = 512: threads tid < NT are `active`).  EVERY thread of the block calls it (block
+// barriers inside); only active threads touch the entries.  The k nearest of P <= CAND_CAP entries by (key, id): a 1024-bin
+// histogram over [min key, max key] finds the bin that holds the k-th key, only the entries up to that bin are selected (keys and
+// ids into sel_k / sel_i, at most selcap of them), and a selected entry's rank among the SELECTED is its rank among all -- the
+// entries of later bins have larger keys (P <= XK_DIRECT: every entry is selected, no histogram).  Keys and ids stay in the
+// owner's registers (CAND_CAP / NT per thread), the whole entry of a thread's first one too (P <= NT: no entry is read twice).
+// P is the same in every thread (the barriers depend on it).  The owner of rank r < k writes record r (recs, where given) and
+// slot r of the l_* lists (where given: lambda_from_sorted's input, in rank order); records want .. k - 1 are written empty.
+// Returns min(k, P), the same in every thread, or -1: more than selcap entries selected (a mass tie) -- nothing written.  The
+// caller's barrier stands between the l_* lists and their reader.
+constexpr int XK_DIRECT = 64;   // up to this many entries are ranked against each other as they are, without the selection
+struct XRankLds {
+    unsigned int* hist;            // 1024 bins, zero on entry
+    unsigned long long* kminmax;   // [2]: ~0, 0 on entry
+    int* kbin_nsel;                // [2]: 1023, 0 on entry
+    double* sel_k;
+    int* sel_i;
+    int selcap;
+    double *l_dist, *l_gy, *l_deg, *l_ny;   // MAX_KLIST each, or null
+};
+template <int NT>
+__device__ __forceinline__ int xk_rank_entries(const XKnn* __restrict__ xk, int P, int64_t k, int64_t goff, as_knn_rec* recs, int tid, const XKnn first,
+                                               const XRankLds L) {
+    constexpr int J = CAND_CAP / NT;
+    const bool active = tid < NT;
+    const int want_k = (int)(k < (int64_t)P ? k : (int64_t)P);
+    double rk[J];
+    int ri[J];
+    // (keys are >= 0 -- squared distances, rectified-cosine distances --: their bit patterns order like the values)
+    unsigned long long lmin = ~0ull, lmax = 0ull;
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+        const int u = tid + j * NT;
+        rk[j] = 0.0;
+        ri[j] = 0;
+        if (active && u < P) {
+            rk[j] = j == 0 ? first.key : xk[u].key;
+            ri[j] = j == 0 ? first.idx : xk[u].idx;
+            const unsigned long long bits = (unsigned long long)__double_as_longlong(rk[j]);
+            lmin = bits < lmin ? bits : lmin;
+            lmax = bits > lmax ? bits : lmax;
+        }
+    }
+    unsigned int mysel = 0u;
+    int nsel;
+    if (P <= XK_DIRECT) {
+        // the usual case, a few dozen entries (P is the same in every thread): nothing to select -- every entry goes to the list,
+        // behind ONE barrier instead of the selection's four
+        if (active && tid < P) {
+            mysel = 1u;
+            L.sel_k[tid] = rk[0];
+            L.sel_i[tid] = ri[0];
+        }
+        __syncthreads();
+        nsel = P;
+    } else {
+        // (a wave's extremes by shuffles, then one LDS atomic per wave and bound: hundreds of atomics on one word run one by one)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long a = __shfl_xor(lmin, o, 64), b = __shfl_xor(lmax, o, 64);
+            lmin = a < lmin ? a : lmin;
+            lmax = b > lmax ? b : lmax;
+        }
+        if ((tid & 63) == 0 && lmax >= lmin) {
+            atomicMin(&L.kminmax[0], lmin);
+            atomicMax(&L.kminmax[1], lmax);
+        }
+        __syncthreads();
+        const double kmin = __longlong_as_double((long long)L.kminmax[0]), kmax = __longlong_as_double((long long)L.kminmax[1]);
+        const double kscale = kmax > kmin ? 1023.0 / (kmax - kmin) : 0.0;
+        auto kbin_of = [&](double kk) {
+            const double fb = (kk - kmin) * kscale;
+            return fb >= 1023.0 ? 1023 : (fb > 0.0 ? (int)fb : 0);   // (monotone in the key: a larger bin means a larger key)
+        };
+#pragma unroll
+        for (int j = 0; j < J; ++j)
+            if (active && tid + j * NT < P) atomicAdd(&L.hist[kbin_of(rk[j])], 1u);
+        __syncthreads();
+        if (tid < 64) {   // 16 bins per lane, inclusive scan over the lanes, the lane whose bins reach k finishes
+            unsigned int hh[16], tot = 0;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                hh[j] = L.hist[16 * tid + j];
+                tot += hh[j];
+            }
+            unsigned int incl = tot;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const unsigned int t2 = __shfl_up(incl, o, 64);
+                if (tid >= o) incl += t2;
+            }
+            const unsigned int excl = incl - tot, want_ = (unsigned)want_k;
+            if (want_ > 0 && excl < want_ && incl >= want_) {
+                unsigned int run = excl;
+                int bsel = 16 * tid;
+#pragma unroll
+                for (int j = 0; j < 16; ++j) {
+                    run += hh[j];
+                    if (run >= want_) break;
+                    bsel += 1;
+                }
+                L.kbin_nsel[0] = bsel;
+            }
+        }
+        __syncthreads();
+        const int kbin = L.kbin_nsel[0];
+#pragma unroll
+        for (int j = 0; j < J; ++j)
+            if (active && tid + j * NT < P && kbin_of(rk[j]) <= kbin) {
+                mysel |= 1u << j;
+                const int slot = atomicAdd(&L.kbin_nsel[1], 1);
+                if (slot < L.selcap) {
+                    L.sel_k[slot] = rk[j];
+                    L.sel_i[slot] = ri[j];
+                }
+            }
+        __syncthreads();
+        nsel = L.kbin_nsel[1];
+    }
+    if (nsel > L.selcap) return -1;
+#pragma unroll
+    for (int j = 0; j < J; ++j)
+        if (mysel & (1u << j)) {
+            int rank = 0;
+#pragma unroll 8
+            for (int s2 = 0; s2 < nsel; ++s2) rank += lex_less<double>(L.sel_k[s2], L.sel_i[s2], rk[j], ri[j]) ? 1 : 0;   // (one address per step: LDS broadcasts)
+            if (rank < k) {
+                const XKnn e = j == 0 ? first : xk[tid + j * NT];
+                if (L.l_dist && rank < MAX_KLIST) {
+                    L.l_dist[rank] = e.dist;
+                    L.l_gy[rank] = e.gy;
+                    L.l_deg[rank] = e.deg;
+                    L.l_ny[rank] = e.ny;
+                }
+                if (recs) {
+                    as_knn_rec r;
+                    r.idx = (int64_t)ri[j] + goff;
+                    r.key = rk[j];
+                    r.dist = e.dist;
+                    r.gy = e.gy;
+                    r.deg = e.deg;
+                    r.ny = e.ny;
+                    recs[rank] = r;
+                }
+            }
+        }
+    if (recs && active)
+        for (int64_t t = want_k + tid; t < k; t += NT) {
+            as_knn_rec r;
+            r.idx = -1;
+            r.key = key_traits<double>::inf();
+            r.dist = 0; r.gy = 0; r.deg = 0; r.ny = 0;
+            recs[t] = r;
+        }
+    return want_k;
+}
 // xmode (xk form only): 0 both shares, 1 the k-NN share alone (the coarse chain: the scorer's candidates come later), 2 the scorer's
 // candidates alone, from a FLAT list (as_.ci, as_.info->sc_cnt entries: the threshold filter over the kept dots) -- no ranking
-__global__ __launch_bounds__(1024) void staged_x1_kernel(FinishArgs ak, FinishArgs as_, XHead* head, XCand* cands, int xcap, int preset_flags, XKnn* xk, int xmode) {
+// final_ranks (xmode 0, one space): staged_x1_final_kernel ranks the entries of xk -- this kernel is evaluation only: no fence,
+// no ticket, no last block, no records.  The kernel boundary is the one hand-off between the blocks' appends and their reader.
+__global__ __launch_bounds__(1024) void staged_x1_kernel(FinishArgs ak, FinishArgs as_, XHead* head, XCand* cands, int xcap, int preset_flags, XKnn* xk, int xmode,
+                                                         int final_ranks) {
     int* xk_count = (int*)(xk + CAND_CAP);   // (behind the entries: zero at the start of a pass -- the finish kernel leaves it so)
+    // xk form: the loads that need nothing from each other go out together, in front of everything else -- the counts, the
+    // block's share of the k-NN candidate buffer (every slot of it that lies inside the buffer, masked by the count once that is
+    // here: entries b, b + nb, ..., at most CAND_CAP / 16 + 1 of them, one per thread) and the head of the thread's first report
+    int pre_raw = 0, pre_ci = 0;
+    double pre_nq = 0.0;
+    int4 pre_rep = make_int4(0, 0, 0, 0);
+    if (xk && xmode == 0) AS_STAMP_B0(32);
+    if (xk) {
+        pre_nq = ak.info->nq;
+        if (xmode != 2) {
+            pre_raw = ak.info->knn_cnt;
+            const int e = (int)blockIdx.x + (int)gridDim.x * (int)threadIdx.x;
+            if (e < CAND_CAP) pre_ci = ak.ci[e];
+        }
+        const int w = (int)blockIdx.x + (int)gridDim.x * (int)threadIdx.x;
+        if (xmode == 0 && w < as_.sc_nw) pre_rep = *(const int4*)(as_.ci + (int64_t)w * SC_WCAP);
+    }
     extern __shared__ __attribute__((aligned(16))) char smem[];
     double* qs = (double*)smem;
     const double* qx = nullptr;
@@ -2172,7 +2375,7 @@ __global__ __launch_bounds__(1024) void staged_x1_kernel(FinishArgs ak, FinishAr
         // its share of the scan waves' scorer reports behind -- evaluated exactly in rounds of 64 rows (one round at 1M x 768 on
         // 128 blocks: 10 + 9 rows), each row then filed by its kind.  (Before: the two shares in rounds of their own on 32 blocks,
         // three serial rounds per block.)
-        const int raw = xmode == 2 ? 0 : ak.info->knn_cnt;
+        const int raw = pre_raw;
         int mine = 0;
         if (raw > CAND_CAP) {
             if (b == 0 && threadIdx.x == 0) {
@@ -2180,8 +2383,8 @@ __global__ __launch_bounds__(1024) void staged_x1_kernel(FinishArgs ak, FinishAr
                 atomicOr(&head->flags, 4);
             }
         } else {
-            mine = raw > b ? (raw - b + nb - 1) / nb : 0;   // <= CAND_CAP / nb + 1
-            for (int t = threadIdx.x; t < mine; t += blockDim.x) si[t] = ak.ci[b + nb * t];
+            mine = raw > b ? (raw - b + nb - 1) / nb : 0;   // <= CAND_CAP / nb + 1 <= 257 (nb >= 16: set_x1_blocks)
+            if ((int)threadIdx.x < mine) si[threadIdx.x] = pre_ci;
         }
         if (b == 0 && threadIdx.x == 0 && (preset_flags || (ak.info->overflow & 2))) atomicOr(&head->flags, preset_flags | ((ak.info->overflow & 2) ? 8 : 0));
         const int room = X1_LOCAL_CAP - mine;
@@ -2195,17 +2398,26 @@ __global__ __launch_bounds__(1024) void staged_x1_kernel(FinishArgs ak, FinishAr
                 if (threadIdx.x == 0) s_tot = ms;
             }
         }
+        bool first_rep = true;
         for (int w = b + nb * (int)threadIdx.x; xmode == 0 && w < as_.sc_nw; w += nb * (int)blockDim.x) {
             const int* rep = as_.ci + (int64_t)w * SC_WCAP;
-            const int c2 = report_rows(rep, s_thrf);
+            const int4 h4 = first_rep ? pre_rep : *(const int4*)rep;   // (the count and the first three rows)
+            first_rep = false;
+            int c2 = h4.x;   // (report_rows, on the count already here)
+            if (c2 >= 0 && (c2 & SC_REPORT_LOSSY)) c2 = __int_as_float(rep[SC_WCAP - 1]) < s_thrf ? (c2 & 0xffff) : -1;
             if (c2 < 0) s_ovf = 1;
             else if (c2 > 0) {
                 const int base = atomicAdd(&s_tot, c2);
-                if (base + c2 <= room)
-                    for (int e = 0; e < c2; ++e) si[mine + base + e] = rep[1 + e];
+                if (base + c2 <= room) {
+                    si[mine + base] = h4.y;
+                    if (c2 > 1) si[mine + base + 1] = h4.z;
+                    if (c2 > 2) si[mine + base + 2] = h4.w;
+                    for (int e = 3; e < c2; ++e) si[mine + base + e] = rep[1 + e];
+                }
             }
         }
         __syncthreads();
+        if (xmode == 0) AS_STAMP_B0(33);
         int tot = s_tot;
         if (s_ovf || tot > room) {
             if (threadIdx.x == 0) {
@@ -2215,7 +2427,7 @@ __global__ __launch_bounds__(1024) void staged_x1_kernel(FinishArgs ak, FinishAr
             }
             tot = 0;
         }
-        const double nqk = ak.info->nq;
+        const double nqk = pre_nq;
         const int total = mine + tot;
         for (int base = 0; base < total; base += 64) {   // (block-uniform)
             const int m = total - base < 64 ? total - base : 64;
@@ -2224,37 +2436,53 @@ __global__ __launch_bounds__(1024) void staged_x1_kernel(FinishArgs ak, FinishAr
             // (in flight under the evaluation instead of behind it: the round's ticket and, per row, its norm and lambda)
             int ticket = 0;
             if (threadIdx.x == 0 && m_sc > 0) ticket = atomicAdd(&head->count, m_sc);   // one ticket per block and round
-            double pre_n = 0.0, pre_l = 0.0;
+            double pre_n = 0.0, pre_l = 0.0, pre_deg = 0.0, pre_ny = 0.0;
             if ((int)threadIdx.x < m) {
                 const int jp = si[base + (int)threadIdx.x];
                 pre_n = ak.n64[jp];
-                pre_l = base + (int)threadIdx.x >= mine ? as_.lam64[jp] : 0.0;
+                if (base + (int)threadIdx.x >= mine) {
+                    pre_l = as_.lam64[jp];
+                } else {   // (a k-NN candidate: what its record would need)
+                    pre_deg = ak.deg ? ak.deg[jp + ak.goff] : 0.0;
+                    pre_ny = ak.ny ? ak.ny[jp + ak.goff] : 0.0;
+                }
             }
             exact_eval_all(ak.x32, ak.x64, qx ? qx : ak.q64, ak.d, ak.dp, si + base, m, o_sq, o_dot);
             if (threadIdx.x == 0 && m_sc > 0) s_base = ticket;
             __syncthreads();
-            if ((int)threadIdx.x < m) {
+            if (xmode == 0) AS_STAMP_B0(34);
+            if (threadIdx.x < 64) {   // (wave 0: m <= 64 rows, a row per lane)
+                const bool row = (int)threadIdx.x < m;
                 const int e_ = base + (int)threadIdx.x;
-                const int j = si[e_];
-                const double sq = o_sq[threadIdx.x], dot = o_dot[threadIdx.x];
-                if (e_ < mine) {
-                    XKnn e;
-                    e.idx = j;
-                    e.pad = 0;
-                    if (ak.metric == AS_METRIC_L2) {   // (knn_finish_body's expressions, one for one)
-                        e.key = sq;
-                        e.dist = sqrt(sq);
-                        e.gy = dot;
-                    } else {
-                        const double den = sqrt(nqk * pre_n);
-                        const double c = den > 0.0 ? dot / den : 0.0;
-                        const double dd = cosine_distance(c);
-                        e.key = dd;
-                        e.dist = dd;
-                        e.gy = c;
-                    }
-                    if (e.key <= ak.epskey) xk[atomicAdd(xk_count, 1)] = e;   // (the few dozen inside eps: the last block ranks them)
+                const int j = row ? si[e_] : 0;
+                const double sq = row ? o_sq[threadIdx.x] : 0.0, dot = row ? o_dot[threadIdx.x] : 0.0;
+                XKnn e;
+                e.idx = j;
+                e.pad = 0;
+                e.deg = pre_deg;
+                e.ny = pre_ny;
+                if (ak.metric == AS_METRIC_L2) {   // (knn_finish_body's expressions, one for one)
+                    e.key = sq;
+                    e.dist = sqrt(sq);
+                    e.gy = dot;
                 } else {
+                    const double den = sqrt(nqk * pre_n);
+                    const double c = den > 0.0 ? dot / den : 0.0;
+                    const double dd = cosine_distance(c);
+                    e.key = dd;
+                    e.dist = dd;
+                    e.gy = c;
+                }
+                // the entries inside eps (a few dozen over all blocks): ONE ticket per block and round, the lanes' slots by ballot
+                const bool inside = row && e_ < mine && e.key <= ak.epskey;
+                const unsigned long long in_mask = __ballot(inside);
+                if (in_mask) {
+                    int xbase = 0;
+                    if (threadIdx.x == 0) xbase = atomicAdd(xk_count, __popcll(in_mask));
+                    xbase = __shfl(xbase, 0, 64);
+                    if (inside) xk[xbase + __popcll(in_mask & ((1ull << threadIdx.x) - 1ull))] = e;
+                }
+                if (row && e_ >= mine) {
                     const int slot = s_base + (e_ - sc_lo);
                     if (slot < xcap) {
                         const double den = sqrt(pre_n * nqk);
@@ -2314,9 +2542,12 @@ __global__ __launch_bounds__(1024) void staged_x1_kernel(FinishArgs ak, FinishAr
         }
         return;
     }
-    if (xmode == 2) return;   // (the records stand from the launch that evaluated the k-NN share)
-    // The coarse scan's k-NN records: the LAST block to get here ranks the candidates inside eps that all blocks have appended
-    // (a few dozen) by (key, id) and writes the k nearest as records -- knn_finish_body's selection with nothing left to prove.
+    if (xmode == 0) AS_STAMP_B0(35);
+    if (xmode == 2 || final_ranks) return;   // (the records stand from the launch that evaluated the k-NN share / the final kernel ranks)
+    // The coarse scan's k-NN records where something stands between this launch and the final kernel -- the coarse chain and the
+    // tau sweeps (lambda_q between the two block launches), a row-sharded index (the exchange) -- or the switch says so: the LAST
+    // block to get here ranks the entries inside eps that all blocks have appended by (key, id) and writes the k nearest as
+    // records (xk_rank_entries) -- knn_finish_body's selection with nothing left to prove.
     // (Release / acquire at agent scope around one ticket per block: the blocks sit on different XCDs, each with its own L2.)
     // One fence per block, by the thread that draws the ticket, behind a barrier (the block's appends happen before it): sixteen
     // waves fencing in each of 32 blocks -- an L2 write-back each -- made this kernel 38 us instead of 15.
@@ -2331,113 +2562,25 @@ __global__ __launch_bounds__(1024) void staged_x1_kernel(FinishArgs ak, FinishAr
     if (s_ticket != nb - 1) return;
     const int raw = ak.info->knn_cnt;
     const int P = raw <= CAND_CAP ? __hip_atomic_load(xk_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-    double* rk = (double*)work;            // P keys (P <= CAND_CAP: 32 KB + 16 KB + 8 KB of the work area)
-    int* ri = (int*)(rk + CAND_CAP);
-    unsigned short* sel = (unsigned short*)(ri + CAND_CAP);   // entries that may be among the k nearest (P <= CAND_CAP = 4096: 16 bits)
+    const XKnn first = xk[threadIdx.x];   // (inside the buffer whatever P is; used where threadIdx.x < P)
     __shared__ unsigned int khist[1024];
-    __shared__ unsigned long long s_kmin, s_kmax;
-    __shared__ int s_kbin, s_nsel;
+    __shared__ unsigned long long s_kminmax[2];
+    __shared__ int s_kbin_nsel[2];
     khist[threadIdx.x] = 0u;
     if (threadIdx.x == 0) {
-        s_kmin = ~0ull;
-        s_kmax = 0ull;
-        s_kbin = 1023;
-        s_nsel = 0;
+        s_kminmax[0] = ~0ull;
+        s_kminmax[1] = 0ull;
+        s_kbin_nsel[0] = 1023;
+        s_kbin_nsel[1] = 0;
     }
     __syncthreads();
-    {
-        // (keys are >= 0 -- squared distances, rectified-cosine distances --: their bit patterns order like the values)
-        unsigned long long lmin = ~0ull, lmax = 0ull;
-        for (int u = threadIdx.x; u < P; u += blockDim.x) {
-            const double kk = xk[u].key;
-            rk[u] = kk;
-            ri[u] = xk[u].idx;
-            const unsigned long long bits = (unsigned long long)__double_as_longlong(kk);
-            lmin = bits < lmin ? bits : lmin;
-            lmax = bits > lmax ? bits : lmax;
-        }
-        if (lmax >= lmin) {
-            atomicMin(&s_kmin, lmin);
-            atomicMax(&s_kmax, lmax);
-        }
-    }
-    if (ak.recs)
-        for (int64_t t = threadIdx.x; t < ak.k; t += blockDim.x) {
-            as_knn_rec r;
-            r.idx = -1;
-            r.key = key_traits<double>::inf();
-            r.dist = 0; r.gy = 0; r.deg = 0; r.ny = 0;
-            ak.recs[t] = r;
-        }
-    __syncthreads();
-    // The k nearest of P entries: a dense neighbourhood puts hundreds of rows inside eps (a query at the heart of a cluster: a
-    // thousand), and ranking every entry against every other in ONE block was this kernel's long tail (P = 500: +20 us, P = 1000:
-    // +80 us; a tenth of the queries at 1M x 768).  A 1024-bin histogram over [min key, max key] finds the bin that holds the k-th
-    // key; only the entries up to that bin are ranked (entries of later bins have larger keys), one WAVE per entry, the P
-    // comparisons of an entry spread over its lanes.
-    const double kmin = __longlong_as_double((long long)s_kmin), kmax = __longlong_as_double((long long)s_kmax);
-    const double kscale = P > 0 && kmax > kmin ? 1023.0 / (kmax - kmin) : 0.0;
-    auto kbin_of = [&](double kk) {
-        const double fb = (kk - kmin) * kscale;
-        return fb >= 1023.0 ? 1023 : (fb > 0.0 ? (int)fb : 0);   // (monotone in the key: a larger bin means a larger key)
-    };
-    for (int u = threadIdx.x; u < P; u += blockDim.x) atomicAdd(&khist[kbin_of(rk[u])], 1u);
-    __syncthreads();
-    const int want_k = (int)(ak.k < (int64_t)P ? ak.k : (int64_t)P);
-    if (threadIdx.x < 64) {   // 16 bins per lane, inclusive scan over the lanes, the lane whose bins reach k finishes
-        unsigned int hh[16], tot = 0;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            hh[j] = khist[16 * threadIdx.x + j];
-            tot += hh[j];
-        }
-        unsigned int incl = tot;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned int t2 = __shfl_up(incl, o, 64);
-            if ((int)threadIdx.x >= o) incl += t2;
-        }
-        const unsigned int excl = incl - tot, want_ = (unsigned)want_k;
-        if (want_ > 0 && excl < want_ && incl >= want_) {
-            unsigned int run = excl;
-            int bsel = 16 * (int)threadIdx.x;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                run += hh[j];
-                if (run >= want_) break;
-                bsel += 1;
-            }
-            s_kbin = bsel;
-        }
-    }
-    __syncthreads();
-    const int kbin = s_kbin;
-    for (int u = threadIdx.x; u < P; u += blockDim.x)
-        if (kbin_of(rk[u]) <= kbin) sel[atomicAdd(&s_nsel, 1)] = (unsigned short)u;
-    __syncthreads();
-    const int nsel = s_nsel;
-    {
-        const int wv = (int)(threadIdx.x >> 6), nwv = (int)(blockDim.x >> 6), lane = (int)(threadIdx.x & 63);
-        for (int c = wv; c < nsel; c += nwv) {   // (wave-uniform)
-            const int u = sel[c];
-            const double myk = rk[u];
-            const int myi = ri[u];
-            int cnt = 0;
-            for (int s2 = lane; s2 < P; s2 += 64) cnt += lex_less<double>(rk[s2], ri[s2], myk, myi) ? 1 : 0;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-            if (lane == 0 && cnt < ak.k && ak.recs) {
-                as_knn_rec r;
-                r.idx = (int64_t)myi + ak.goff;
-                r.key = myk;
-                r.dist = xk[u].dist;
-                r.gy = xk[u].gy;
-                r.deg = ak.deg ? ak.deg[myi + ak.goff] : 0.0;
-                r.ny = ak.ny ? ak.ny[myi + ak.goff] : 0.0;
-                ak.recs[cnt] = r;
-            }
-        }
-    }
+    XRankLds rl;
+    rl.hist = khist; rl.kminmax = s_kminmax; rl.kbin_nsel = s_kbin_nsel;
+    rl.sel_k = (double*)work;              // every entry may be selected (all keys equal): 32 KB + 16 KB of the work area
+    rl.sel_i = (int*)(rl.sel_k + CAND_CAP);
+    rl.selcap = CAND_CAP;
+    rl.l_dist = rl.l_gy = rl.l_deg = rl.l_ny = nullptr;
+    xk_rank_entries<1024>(xk, P, ak.k, ak.goff, ak.recs, (int)threadIdx.x, first, rl);
     if (threadIdx.x == 0) {
         ak.info->knn_total = raw <= CAND_CAP ? raw : CAND_CAP;
         ak.info->knn_inexact = 0;
@@ -2451,7 +2594,8 @@ __global__ __launch_bounds__(1024) void staged_x1_kernel(FinishArgs ak, FinishAr
 // publication.  Clears the per-search state and the scan's histograms behind a clean search.
 __global__ __launch_bounds__(1024) void staged_x1_final_kernel(const char* __restrict__ all, int world, int64_t xbytes, int64_t krec, int xcap, int64_t k,
                                                                int metric, int kernel, double sigma, double p, double tau0, double tau, int64_t topk,
-                                                               int64_t ntotal, QInfo* info, HostOut* out, int64_t seq, unsigned int* sc_hist, XHead* own_head) {
+                                                               int64_t ntotal, QInfo* info, HostOut* out, int64_t seq, unsigned int* sc_hist, XHead* own_head,
+                                                               XKnn* xk, int64_t goff) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     double* sc = (double*)smem;                 // CAND_CAP cosines, then scores
     double* sl = sc + CAND_CAP;                 // lambdas
@@ -2459,16 +2603,105 @@ __global__ __launch_bounds__(1024) void staged_x1_final_kernel(const char* __res
     double* pk = (double*)(sid + CAND_CAP);     // PRUNE_CAP pruned scores
     int* pi = (int*)(pk + PRUNE_CAP);
     __shared__ unsigned int khist[1024];
-    __shared__ int s_tot, s_flags, k_bin, k_cnt;
+    __shared__ int s_tot, s_flags, k_bin, k_cnt, s_status;
+    __shared__ double s_lq;
+    AS_STAMP(36);
     khist[threadIdx.x] = 0u;
     if (threadIdx.x == 0) {
         s_tot = 0;
         s_flags = 0;
         k_cnt = 0;
     }
-    __syncthreads();
-    if (threadIdx.x < 64) {
+    if (xk) {
+        // One space (world == 1), handed the entries inside eps as staged_x1_kernel's blocks appended them (final_ranks): the
+        // kernel boundary was their hand-off.  Waves 0..7 rank them -- keys in registers, the selected few in the pk / pi area,
+        // idle until the prune -- write the k records into the block (callers and the chains behind an overflow read them) and
+        // leave the neighbours in rank order in LDS, from where wave 0 forms lambda_q; waves 8..15 pull the scorer's candidates
+        // meanwhile.  Every load that needs nothing from another goes out first: the counts, a thread's first entry, its first two
+        // candidates (inside their buffers whatever the counts say: xk holds CAND_CAP entries, the block xcap >= 512 candidates).
+        constexpr int NR = 512;
+        int* xk_count = (int*)(xk + CAND_CAP);
+        const XHead* h = (const XHead*)(all + krec * (int64_t)sizeof(as_knn_rec));
+        const XCand* cs = (const XCand*)(h + 1);
+        const int tid = (int)threadIdx.x;
+        const int raw = info->knn_cnt;
+        const double nq = info->nq;
+        int P = xk_count[0], cnt = 0, fl = 0;   // (P in every thread: the ranking's barriers depend on it)
+        XKnn first = {};
+        XCand c0 = {}, c1 = {};
+        if (tid < NR) {
+            first = xk[tid];
+        } else {
+            cnt = h->count;
+            fl = h->flags;
+            c0 = cs[tid - NR];
+            if (tid < xcap) c1 = cs[tid];   // (a second one: up to 1 024 candidates without a dependent load)
+        }
+        __shared__ unsigned int rhist[1024];
+        __shared__ unsigned long long s_kminmax[2];
+        __shared__ int s_kbin_nsel[2];
+        __shared__ double l_dist[MAX_KLIST], l_gy[MAX_KLIST], l_deg[MAX_KLIST], l_ny[MAX_KLIST];
+        rhist[tid] = 0u;
+        if (tid == 0) {
+            s_kminmax[0] = ~0ull;
+            s_kminmax[1] = 0ull;
+            s_kbin_nsel[0] = 1023;
+            s_kbin_nsel[1] = 0;
+        }
+        __syncthreads();
+        AS_STAMP(37);
+        if (raw > CAND_CAP) P = 0;   // (overflow bit 0 stands in the block's flags: staged_x1_kernel, block 0; the records are written empty)
+        if (tid >= NR) {
+            if (cnt < 0 || cnt > xcap) {
+                cnt = 0;
+                fl |= 16;
+            }
+            if (tid == NR) {
+                if (fl) atomicOr(&s_flags, fl);
+                s_tot = cnt;
+            }
+            if (cnt <= CAND_CAP)
+                for (int t = tid - NR; t < cnt; t += NR) {
+                    const XCand c = t == tid - NR ? c0 : (t == tid ? c1 : cs[t]);
+                    sc[t] = c.cosv;
+                    sl[t] = c.lam;
+                    sid[t] = (int)c.idx;
+                }
+        }
+        XRankLds rl;
+        rl.hist = rhist; rl.kminmax = s_kminmax; rl.kbin_nsel = s_kbin_nsel;
+        rl.sel_k = pk; rl.sel_i = pi; rl.selcap = PRUNE_CAP;
+        rl.l_dist = l_dist; rl.l_gy = l_gy; rl.l_deg = l_deg; rl.l_ny = l_ny;
+        const int nn = xk_rank_entries<NR>(xk, P, k, goff, (as_knn_rec*)const_cast<char*>(all), tid, first, rl);
+        __syncthreads();
+        AS_STAMP(38);
+        if (tid < 64) {
+            // (more selected entries than the area holds -- a mass tie at the k-th key --: the k-NN list is not proven, flag bit 0,
+            // and the host's exact pass over the candidate buffer takes the query)
+            const int cn = nn < 0 ? 0 : (nn < MAX_KLIST ? nn : MAX_KLIST);
+            const double lam = lambda_from_sorted_nq(cn, l_dist, l_gy, l_deg, l_ny, metric, kernel, sigma, p, tau0, nq, info);
+            if (tid == 0) {
+                s_lq = lam;
+                s_status = lam == 0.0 ? AS_EZEROLAMBDA : AS_OK;
+                if (nn < 0) atomicOr(&s_flags, 1);
+                // what the last block of staged_x1_kernel leaves behind where it ranks
+                info->knn_total = raw <= CAND_CAP ? raw : CAND_CAP;
+                info->knn_inexact = nn < 0 ? 1 : 0;
+                xk_count[0] = 0;   // (the next pass's appends and tickets start at zero)
+                xk_count[1] = 0;
+            }
+            AS_STAMP(39);
+        }
+    } else {
+        __syncthreads();
+    }
+    if (xk) {   // (done above)
+    } else if (threadIdx.x < 64) {
         q_lambda_body((const as_knn_rec*)all, krec * world, krec, xbytes / (int64_t)sizeof(as_knn_rec), k, metric, kernel, sigma, p, tau0, info, 0);
+        if (threadIdx.x == 0) {   // (its own stores)
+            s_lq = info->lambda_q;
+            s_status = info->status;
+        }
     } else {
         const int wv = (int)(threadIdx.x >> 6) - 1, nwv = 15, lane = (int)(threadIdx.x & 63);
         // (a rank per wave; a rank's base in the list by one LDS ticket)
@@ -2503,7 +2736,7 @@ __global__ __launch_bounds__(1024) void staged_x1_final_kernel(const char* __res
         flags |= 16;
         total = 0;
     }
-    const double lq = info->lambda_q;
+    const double lq = s_lq;   // (lambda_q and the status stay in LDS for the scores and the header)
     int mybin[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -2519,6 +2752,7 @@ __global__ __launch_bounds__(1024) void staged_x1_final_kernel(const char* __res
         }
     }
     __syncthreads();
+    if (xk) AS_STAMP(40);
     const int64_t want64 = topk < ntotal ? topk : ntotal;
     const int nhit = (int)(total < want64 ? total : want64);
     if (threadIdx.x < 64) {   // 16 bins per lane, inclusive scan over the lanes, the lane whose bins reach nhit finishes
@@ -2575,29 +2809,38 @@ __global__ __launch_bounds__(1024) void staged_x1_final_kernel(const char* __res
                 out->score[rank] = pk[t];
             }
         }
+    // The header, a field per lane of the last wave, beside the hits and under the same wait (every thread holds the same flags:
+    // s_flags behind a barrier, the scores' count); thread 0 publishes behind the barrier.
+    {
+        const int clean = !flags;
+        switch ((int)threadIdx.x - ((int)blockDim.x - 8)) {
+            case 0: out->len = nhit; break;
+            case 1: out->lambda_q = s_lq; break;
+            case 2: out->status = s_status; break;
+            case 3: out->knn_inexact = (flags & 1) ? 1 : 0; break;
+            case 4: out->score_inexact = 0; break;
+            case 5: out->overflow = ((flags & 4) ? 1 : 0) | ((flags & 8) ? 2 : 0) | ((flags & 16) ? 4 : 0) | ((flags & 32) ? 8 : 0); break;
+            case 6: out->state_reset = clean; break;
+            case 7:
+                if (own_head) {   // this rank's block starts the next pass empty (its count and flags are accumulated by atomics)
+                    // (what did not fit, for the host's debug line: candidates written, the largest share of a block that did not fit,
+                    // blocks that met an overflowed wave report)
+                    out->pad_ = (flags & 16) ? ((own_head->count & 0xffff) | ((own_head->pad[0] & 0xff) << 16) | ((own_head->pad[1] & 0xff) << 24)) : 0;
+                    own_head->count = 0;
+                    own_head->flags = 0;
+                    own_head->pad[0] = 0;
+                    own_head->pad[1] = 0;
+                }
+                break;
+            default: break;
+        }
+        if (threadIdx.x == 0 && clean) reset_query_state(info);   // (the thread whose stores to QInfo these follow)
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (threadIdx.x == 0) {
-        out->len = nhit;
-        out->lambda_q = info->lambda_q;
-        out->status = info->status;
-        out->knn_inexact = (flags & 1) ? 1 : 0;
-        out->score_inexact = 0;
-        out->overflow = ((flags & 4) ? 1 : 0) | ((flags & 8) ? 2 : 0) | ((flags & 16) ? 4 : 0) | ((flags & 32) ? 8 : 0);
-        const int clean = !flags;
-        out->state_reset = clean;
-        if (clean) reset_query_state(info);
-        if (own_head) {   // this rank's block starts the next pass empty (its count and flags are accumulated by atomics)
-            // (what did not fit, for the host's debug line: candidates written, the largest share of a block that did not fit, blocks
-            // that met an overflowed wave report)
-            out->pad_ = (flags & 16) ? ((own_head->count & 0xffff) | ((own_head->pad[0] & 0xff) << 16) | ((own_head->pad[1] & 0xff) << 24)) : 0;
-            own_head->count = 0;
-            own_head->flags = 0;
-            own_head->pad[0] = 0;
-            own_head->pad[1] = 0;
-        }
-        publish(out, seq);
-    }
+    if (xk) AS_STAMP(41);
+    if (threadIdx.x == 0) publish(out, seq);
+    if (xk) AS_STAMP(42);
 }
 
 // merge m hit records (own or all-gathered) -> final topk, written to pinned host memory
@@ -3412,6 +3655,10 @@ int32_t as_set_tuning(const char* key, int32_t value) {
         set_x1_blocks(value);
         return 0;
     }
+    if (key && !strcmp(key, "x1_final_rank")) {
+        set_x1_final_rank(value);
+        return 0;
+    }
     if (key && !strcmp(key, "subset_batch_mib")) {
         set_subset_batch_mib(value);
         return 0;
@@ -3422,7 +3669,7 @@ int32_t as_set_tuning(const char* key, int32_t value) {
 #ifdef AS_STAMPS
 // diagnostic build only (not declared in the public header): the raw stamps of the last finish kernels
 int as_debug_stamps(unsigned long long* out) {
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(as::g_stamps), sizeof(unsigned long long) * 32) == hipSuccess ? 0 : 1;
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(as::g_stamps), sizeof(unsigned long long) * as::AS_NSTAMPS) == hipSuccess ? 0 : 1;   // (48 slots: tools/stamps.py)
 }
 #endif
 
@@ -3476,6 +3723,7 @@ static as_status query_alloc(as_query* q) {
     const size_t C = (size_t)q->cap;
     q->nwaves = 4096;
     if (const char* ev = getenv("ARROWSPACE_STAGED_X1")) q->x1_off = atoi(ev) == 0 ? 1 : 0;
+    if (const char* ev = getenv("ARROWSPACE_X1_FINAL_RANK")) q->x1_final_rank = atoi(ev) == 0 ? 0 : 1;
     if (const char* ev = getenv("ARROWSPACE_SCAN_VARIANT")) q->scan_variant = atoi(ev) & 7;
     if (const char* ev = getenv("ARROWSPACE_GEMM_VARIANT")) q->gemm_variant = atoi(ev);
     q->half_enabled = getenv("ARROWSPACE_BATCH_F32_DOTS") ? 0 : 1;
@@ -3733,7 +3981,8 @@ static FinishArgs x1_knn_args(as_query* q, void* send_dev) {
 }
 
 // exact_knn: the single space's coarse scan -- no k-NN block, every block evaluates its share of the k-NN candidates into q->xknn
-static as_status x1_launch_block(as_query* q, void* send_dev, int world, bool sc_ran, bool exact_knn = false, int xmode = 0) {
+// final_ranks (exact_knn, xmode 0, one space): evaluation only -- x1_launch_final, handed q->xknn, ranks the entries inside eps
+static as_status x1_launch_block(as_query* q, void* send_dev, int world, bool sc_ran, bool exact_knn = false, int xmode = 0, bool final_ranks = false) {
     const as_space* sp = q->sp;
     const int64_t krec = std::max<int64_t>(q->k, 1);
     XHead* head = (XHead*)((char*)send_dev + sizeof(as_knn_rec) * krec);
@@ -3762,20 +4011,24 @@ static as_status x1_launch_block(as_query* q, void* send_dev, int world, bool sc
     }
     // (a rank that could not collect candidates -- no fused scan for this query here -- says so: every rank reads the flag and
     // the pass is rerun on the two-exchange chain)
-    const size_t lds_xk = (sp->dp <= Q_LDS_MAX ? sizeof(double) * (size_t)sp->dp : 0) + (sizeof(double) + sizeof(int) + sizeof(short)) * (size_t)CAND_CAP + 64;
+    // (work area of the xk form: the block's list and a round's results; where its last block ranks, the selected keys and ids)
+    const size_t work_xk = final_ranks || xmode == 2 ? sizeof(int) * (size_t)X1_LOCAL_CAP + sizeof(double) * 128 : (sizeof(double) + sizeof(int)) * (size_t)CAND_CAP;
+    const size_t lds_xk = (sp->dp <= Q_LDS_MAX ? sizeof(double) * (size_t)sp->dp : 0) + work_xk + 64;
     hipLaunchKernelGGL(staged_x1_kernel, dim3(exact_knn ? g_x1_blocks.load(std::memory_order_relaxed) : 1 + X1_BLOCKS), dim3(1024), exact_knn ? lds_xk : x1_lds_a(), q->stream, fk, fs, head, cands, x1_cap(world),
-                       !sc_ran && rows > 0 && xmode == 0 ? 16 : 0, exact_knn ? (XKnn*)q->xknn : (XKnn*)nullptr, xmode);
+                       !sc_ran && rows > 0 && xmode == 0 ? 16 : 0, exact_knn ? (XKnn*)q->xknn : (XKnn*)nullptr, xmode, exact_knn && xmode == 0 && final_ranks ? 1 : 0);
     AS_HIP(hipGetLastError());
     q->x1_head = head;
     return AS_OK;
 }
 
-static as_status x1_launch_final(as_query* q, const void* all_dev, int world, double tau) {
+// ranks_knn: all_dev is this workspace's own block (world 1) behind an evaluation-only x1_launch_block -- the kernel ranks q->xknn
+static as_status x1_launch_final(as_query* q, const void* all_dev, int world, double tau, bool ranks_knn = false) {
     const as_graph* gr = q->gr;
     const int64_t krec = std::max<int64_t>(q->k, 1);
     hipLaunchKernelGGL(staged_x1_final_kernel, dim3(1), dim3(1024), x1_lds_b(), q->stream, (const char*)all_dev, (int)world, as_query_x1_bytes(q, world),
                        krec, x1_cap(world), q->k, gr->metric, gr->kernel, gr->gp.sigma, gr->gp.p, gr->tau0, tau, q->topk,
-                       (int64_t)0x7fffffffffffffffll, q->info, q->hout_dev, q->seq, q->sc_hist, (XHead*)q->x1_head);
+                       (int64_t)0x7fffffffffffffffll, q->info, q->hout_dev, q->seq, q->sc_hist, (XHead*)q->x1_head,
+                       ranks_knn && world == 1 ? (XKnn*)q->xknn : (XKnn*)nullptr, (int64_t)q->sp->row_offset);
     AS_HIP(hipGetLastError());
     return AS_OK;
 }
@@ -4180,8 +4433,14 @@ static as_status search_run(as_query* q, const double* query, int64_t d, double 
         AS_TRY(x1_own_prepare(q));
         q->x1_dirty = 1;
         q->seq += 1;
-        AS_TRY(x1_launch_block(q, q->x1_own, 1, true, q->coarse != 0));
-        AS_TRY(x1_launch_final(q, q->x1_own, 1, tau));
+        // The k-NN entries inside eps: ranked by the final kernel, not by the first one's last block -- the kernel boundary is the only
+        // hand-off between the blocks' appends and their reader (ARROWSPACE_X1_FINAL_RANK=0 / as_set_tuning("x1_final_rank", 0): the
+        // last-block form; same results bit for bit).  Same box, interleaved (tools/x1_final_rank_ab.sh): 1M x 768 median 5 841 ->
+        // 6 056 queries/s, 200k x 768 13 830 -> 15 340, 400k x 384 k = 4 topk = 2 14 320 -> 15 090; first kernel 18.9 -> 9.6 us, final
+        // kernel 11.4 -> 12.7 us.
+        const bool final_ranks = q->coarse != 0 && x1_final_ranks(q);
+        AS_TRY(x1_launch_block(q, q->x1_own, 1, true, q->coarse != 0, 0, final_ranks));
+        AS_TRY(x1_launch_final(q, q->x1_own, 1, tau, final_ranks));
         const double ht2 = host_timing ? now_us() : 0.0;
         if (q->ev_valid) AS_HIP(hipEventRecord(q->ev[2], q->stream));
         AS_TRY(wait_published(q));

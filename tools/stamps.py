@@ -16,7 +16,7 @@ acc = []
 knn_tot = []
 for i in range(48):
     a.search(Q[i], g, 0.62)
-    st = np.zeros(32, dtype=np.uint64)
+    st = np.zeros(48, dtype=np.uint64)
     assert L.as_debug_stamps(st.ctypes.data_as(C.c_void_p)) == 0
     if i >= 8: acc.append(st.astype(np.float64) * 0.01)   # us
 # rows inside eps = the scan's neighbour candidates (counted after the timed loop: a 3 GB torch temporary between searches
@@ -30,6 +30,12 @@ names_s = ["select_candidates", "exact eval + scores", "rank + hit records", "a-
 print("knn_finish phases (us):", {nm: round(s[i + 1] - s[i], 2) for i, nm in enumerate(names_k)}, "total", round(s[6] - s[0], 2))
 print("score_finish phases (us):", {nm: round(s[17 + i] - s[16 + i], 2) for i, nm in enumerate(names_s)}, "total", round(s[20] - s[16], 2))
 print("knn_finish end -> score_finish start (gmin, pick_thr, filter + boundaries):", round(s[16] - s[6], 2))
+if s[36] > 0:   # fused tail as two launches (staged_x1_kernel: its block 0; staged_x1_final_kernel with the k-NN ranking)
+    dd = lambda a_, b_: round(float(np.mean([x[a_] - x[b_] for x in acc])), 2)   # noqa: E731  (per search, then averaged)
+    print("two-launch tail, first kernel, block 0 (us): lists gathered", dd(33, 32), "| rows evaluated", dd(34, 33), "| filed", dd(35, 34), "| whole block", dd(35, 32))
+    print("two-launch tail, block 0 filed -> final kernel starts (the other blocks, the boundary) (us):", dd(36, 35))
+    print("two-launch tail, final kernel (us): pulled", dd(37, 36), "| records ranked", dd(38, 37), "| lambda_q", dd(39, 38), "| scored", dd(40, 39),
+          "| ranked", dd(41, 40), "| published", dd(42, 41), "| whole kernel", dd(42, 36), "| first kernel's start -> published", dd(42, 32))
 if s[22] > 0:   # fused tail (fused_finish_kernel): one launch, both phases
     print("fused tail (us): query staging", round(s[0] - s[22], 2), "| knn phase", round(s[6] - s[0], 2), "| barrier behind the gather of the waves' reports", round(s[24] - s[6], 2),
           "| keys", round(s[25] - s[16], 2), "| select", round(s[17] - s[25], 2),
