@@ -460,7 +460,8 @@ void as_enable_search_stats(int32_t enabled);
  * "x1_blocks" = blocks of the coarse scan's exact-evaluation kernel (16 .. 256, default 128).
  * "x1_final_rank" = 1 / 0: the fused tail's final kernel / its first kernel's last block ranks the rows inside eps, for every
  * workspace; any other value: each workspace's own switch again (ARROWSPACE_X1_FINAL_RANK when it was made; default 1).
- * "subset_batch_mib" = MiB of scores one chunk of queries of the batched filtered forms may hold (default 256; <= 0: the default).
+ * "subset_batch_mib" = MiB of scores one chunk of queries of the batched filtered forms may hold (default 256; <= 0: the default);
+ * the per-query list forms chunk by it too.  "lists_timing" = 1 / 0: HIP events around their score kernel (as_lists_kernel_us).
  * Returns 0, or 1 for an unknown key.  Results never depend on it. */
 int32_t as_set_tuning(const char* key, int32_t value);
 /* same, for the workspace as_search keeps inside the space (last as_search call) */
@@ -566,6 +567,38 @@ as_status as_score_items_batch_taus(const as_space* sp, const as_graph* gr, cons
 /* out[0] tau sweeps over a subset (the four calls above), [1] score-kernel launches they made, [2] tau planes those launches wrote,
  * [3] lambda_q steps run (single searches plus as_search_batch calls) */
 as_status as_subset_sweep_counters(const as_space* sp, int64_t* out, int32_t n);
+/* Per-query candidate lists (re-ranking): b queries, row-major [b][d] in HOST memory, EACH WITH ITS OWN id list -- list i is
+ * ids_host[offsets_host[i] .. offsets_host[i + 1]) (offsets_host: b + 1 entries, offsets[0] == 0, non-decreasing; any order,
+ * duplicates allowed, lists may be empty and may share ids).  as_score_lists_batch: out_scores[offsets[i] + j] = what
+ * as_score_items returns for query i and entry j of its list (the caller's order, duplicates kept).  as_search_lists_batch: list
+ * i, at out_idx / out_score + i * kk (kk = min(topk, nitems)), out_len[i] = min(kk, distinct ids of list i) entries, is what
+ * as_search_subset returns for query i over its list.  Scores agree with the single forms to 1e-12 relative, indices except inside
+ * such ties.  The bits of the score of (query i, item j) depend on that query, that row, tau and lambda_q only -- not on the
+ * entry's position, the other lists of the call, the chunk budget or which of the two forms ran: identical rows score bit-equal
+ * and come back in index order, an id listed twice gets the same bits twice.  lambda_q and out_status[i] (AS_OK or
+ * AS_EZEROLAMBDA: that query gets out_len 0, its scores are left unwritten, the others are served) come from ONE as_search_batch
+ * call over all b queries, hits discarded; empty lists still run it; b == 0 launches nothing.  Checked before anything is
+ * launched, that step included: a null argument ("<name>: null argument", nothing written), offsets that do not start at 0 or
+ * decrease, an id outside [0, nitems) (the message names the id and its list) -> AS_EINVAL; offsets[b] >= 2^31 -> AS_EUNSUPPORTED;
+ * wrong d, a non-finite tau and a shard of a row-sharded index as the single forms.  out_lambda_q and out_status may be NULL.
+ * One ragged launch scores all pairs of a chunk of queries (the lists cut into segments of at most 64 entries, a block per segment, the
+ * single form's summation order per row), one block per list selects (the search form removes each list's repeated ids on the
+ * host first); queries run in chunks whose scores fit the "subset_batch_mib" budget, a list longer than it a chunk of its own,
+ * one stream wait per chunk.  The buffers live in the space and grow on demand; calls on one space are serialised, as_search runs
+ * beside them. */
+as_status as_score_lists_batch(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau,
+                               const int64_t* ids_host, const int64_t* offsets_host, double* out_scores, double* out_lambda_q,
+                               int32_t* out_status);
+as_status as_search_lists_batch(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau,
+                                const int64_t* ids_host, const int64_t* offsets_host, int64_t* out_idx, double* out_score,
+                                int64_t* out_len, double* out_lambda_q, int32_t* out_status);
+/* out[0] calls of the two entries above that passed their checks, [1] score-kernel launches they made, [2] (query, item) pairs
+ * those launches scored, [3] lambda_q steps run (as_search_batch calls), [4] host nanoseconds spent on id checks, deduplication and
+ * work tables */
+as_status as_lists_counters(const as_space* sp, int64_t* out, int32_t n);
+/* measurement: the device microseconds of the ragged score kernel, summed over the chunks of the last call on this space that
+ * ran under as_set_tuning("lists_timing", 1) (HIP events around the kernel; off by default) */
+double as_lists_kernel_us(const as_space* sp);
 
 /* ---- index persistence (extension; the reference exposes none): one flat file
  * holding the items, lambdas and graph arrays.  Loading re-ingests the items and uploads the

@@ -202,6 +202,25 @@ def _item_ids(ids_or_mask, nitems: int, what: str = "ids") -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.int64)
 
 
+def _id_lists(lists, nitems: int) -> tuple[np.ndarray, np.ndarray]:
+    """B id lists as (ids int64 flat, offsets int64 [B + 1]): a 2-D integer array (B, C) is B lists of C ids; any other
+    sequence holds one entry per list, each whatever `_item_ids` accepts (integer ids in any order, duplicates kept, or a
+    boolean mask of length nitems).  Non-integer ids raise TypeError."""
+    if isinstance(lists, np.ndarray) and lists.ndim == 2 and lists.dtype != np.bool_:
+        if lists.dtype.kind not in "iu":
+            raise TypeError(f"argument 'lists': expected integer item ids or boolean masks, got dtype {lists.dtype}")
+        if lists.dtype == np.uint64 and lists.size and int(lists.max()) > np.iinfo(np.int64).max:
+            raise ValueError(f"argument 'lists': id {int(lists.max())} is outside [0, {nitems})")
+        b, c = lists.shape
+        return np.ascontiguousarray(lists, dtype=np.int64).reshape(-1), np.arange(b + 1, dtype=np.int64) * c
+    parts = [l if isinstance(l, np.ndarray) and l.ndim == 1 and l.dtype == np.int64 else _item_ids(l, nitems, "lists") for l in lists]
+    offsets = np.zeros(len(parts) + 1, dtype=np.int64)
+    if parts:
+        np.cumsum([p.shape[0] for p in parts], out=offsets[1:])
+    ids = np.ascontiguousarray(np.concatenate(parts), dtype=np.int64) if parts else np.empty(0, dtype=np.int64)
+    return ids, offsets
+
+
 class ItemSubset:
     """Extension: a set of items of one ArrowSpace (`ArrowSpace.subset`), resident on the device with every buffer a
     `search_subset` over it needs.  Holds a reference to its ArrowSpace."""
@@ -481,6 +500,75 @@ class ArrowSpace:
         if (stt[:b] == _lib.AS_EZEROLAMBDA).any():
             raise PanicException("The lambdas are zero, check the magnitude of items and eps.")
         return out
+
+    def _lists_args(self, items, gl, lists):
+        if not isinstance(gl, GraphLaplacian):
+            raise TypeError("argument 'gl': expected GraphLaplacian")
+        Q = np.ascontiguousarray(items, dtype=np.float64)
+        if Q.ndim != 2:
+            raise TypeError("items must be a 2-D float64 array")
+        ids, offsets = _id_lists(lists, self.nitems)
+        if offsets.shape[0] - 1 != Q.shape[0]:
+            raise ValueError(f"argument 'lists': {offsets.shape[0] - 1} id lists for {Q.shape[0]} queries")
+        return Q, ids, offsets
+
+    def search_batch_lists(self, items, gl: GraphLaplacian, tau: float, lists):
+        """Extension: re-ranking of per-query candidate lists, B queries [B, D] EACH WITH ITS OWN id list -> list of B hit
+        lists; list i is what `search_subset(items[i], gl, tau, lists[i])` returns: the first min(topk, distinct ids of
+        lists[i]) items of that list by (score descending, index ascending) (scores within 1e-12 relative, indices equal
+        except inside such ties).  `lists`: a sequence of B id sequences (any order, duplicates allowed, empty lists allowed,
+        lists may share ids; a boolean mask of length nitems per list is accepted) or a 2-D integer array (B, C).  Costs one
+        `search_batch` over the B queries (lambda_q comes from it; any query whose lambda_q is 0 panics as there, whatever
+        its list), then ONE ragged launch on the device scores every (query, item) pair, each query against its own rows,
+        and every list is selected there."""
+        Q, ids, offsets = self._lists_args(items, gl, lists)
+        b = Q.shape[0]
+        kk = max(min(int(gl.graph_params["topk"]), self.nitems), 1)
+        idx = np.empty((max(b, 1), kk), dtype=np.int64)
+        sc = np.empty((max(b, 1), kk), dtype=np.float64)
+        ln = np.zeros(max(b, 1), dtype=np.int64)
+        stt = np.zeros(max(b, 1), dtype=np.int32)
+        st = _L.as_search_lists_batch(self._h, gl._h, Q.ctypes.data_as(C.c_void_p), b, Q.shape[1], float(tau),
+                                      ids.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p),
+                                      idx.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p), ln.ctypes.data_as(C.c_void_p),
+                                      None, stt.ctypes.data_as(C.c_void_p))
+        if st:
+            _raise(st)
+        if (stt[:b] == _lib.AS_EZEROLAMBDA).any():
+            raise PanicException("The lambdas are zero, check the magnitude of items and eps.")
+        return [list(zip(ii[:l], ss[:l])) for ii, ss, l in zip(idx[:b].tolist(), sc[:b].tolist(), ln[:b].tolist())]
+
+    def score_lists_batch(self, items, gl: GraphLaplacian, tau: float, lists):
+        """Extension: scores of per-query candidate lists -> a list of B float64 arrays (a 2-D integer array (B, C) as `lists`
+        returns an array (B, C)): entry j of array i is what `score_items(items[i], gl, tau, lists[i])[j]` returns (the
+        caller's order, duplicates kept; within 1e-12 relative).  `lists` as for `search_batch_lists`.  Costs one
+        `search_batch` over the B queries (lambda_q; a query whose lambda_q is 0 panics as there) plus ONE ragged launch that
+        gathers each query's own rows.  The bits of a score depend on its query, its item, tau and lambda_q only: not on the
+        entry's position, the other lists, or whether this method or `search_batch_lists` computed it."""
+        Q, ids, offsets = self._lists_args(items, gl, lists)
+        b = Q.shape[0]
+        out = np.empty(ids.shape[0], dtype=np.float64)
+        stt = np.zeros(max(b, 1), dtype=np.int32)
+        st = _L.as_score_lists_batch(self._h, gl._h, Q.ctypes.data_as(C.c_void_p), b, Q.shape[1], float(tau),
+                                     ids.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p),
+                                     out.ctypes.data_as(C.c_void_p), None, stt.ctypes.data_as(C.c_void_p))
+        if st:
+            _raise(st)
+        if (stt[:b] == _lib.AS_EZEROLAMBDA).any():
+            raise PanicException("The lambdas are zero, check the magnitude of items and eps.")
+        if isinstance(lists, np.ndarray) and lists.ndim == 2 and lists.dtype != np.bool_:
+            return out.reshape(lists.shape)
+        return [out[offsets[i]:offsets[i + 1]] for i in range(b)]
+
+    def lists_counters(self) -> dict:
+        """Extension: `search_batch_lists` / `score_lists_batch` calls on this space that passed their checks, the score-kernel
+        launches they made, the (query, item) pairs those scored, the lambda_q steps run (`search_batch` calls), and the host
+        nanoseconds spent on id checks, deduplication and work tables."""
+        out = np.zeros(5, dtype=np.int64)
+        st = _L.as_lists_counters(self._h, out.ctypes.data_as(C.c_void_p), 5)
+        if st:
+            _raise(st)
+        return dict(zip(("calls", "score_launches", "pairs", "lambda_steps", "host_ns"), (int(v) for v in out)))
 
     @staticmethod
     def _taus(taus) -> np.ndarray:

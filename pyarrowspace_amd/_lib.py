@@ -54,6 +54,7 @@ SYMBOLS = [
     "as_subset_create", "as_subset_size", "as_subset_ids", "as_subset_free", "as_search_subset", "as_score_items", "as_subset_set_timing", "as_subset_kernel_us",
     "as_search_subset_batch", "as_score_items_batch",
     "as_search_subset_taus", "as_score_items_taus", "as_search_subset_batch_taus", "as_score_items_batch_taus", "as_subset_sweep_counters",
+    "as_score_lists_batch", "as_search_lists_batch", "as_lists_counters", "as_lists_kernel_us",
 ]
 
 _lib = None
@@ -214,6 +215,10 @@ def load():
         "as_search_subset_batch_taus": (i32, [vp, vp, vp, i64, i64, vp, i64, vp, vp, vp, vp, vp, vp]),
         "as_score_items_batch_taus": (i32, [vp, vp, vp, i64, i64, vp, i64, vp, i64, vp, vp, vp]),
         "as_subset_sweep_counters": (i32, [vp, vp, i32]),
+        "as_score_lists_batch": (i32, [vp, vp, vp, i64, i64, f64, vp, vp, vp, vp, vp]),
+        "as_search_lists_batch": (i32, [vp, vp, vp, i64, i64, f64, vp, vp, vp, vp, vp, vp, vp]),
+        "as_lists_counters": (i32, [vp, vp, i32]),
+        "as_lists_kernel_us": (f64, [vp]),
         "as_subset_set_timing": (None, [vp, i32]),
         "as_subset_kernel_us": (f64, [vp]),
         "as_gang_counters": (i32, [vp, vp, i32]),

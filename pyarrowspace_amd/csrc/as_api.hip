@@ -6,6 +6,8 @@
 #include <chrono>
 #include <cmath>
 #include <new>
+#include <system_error>
+#include <thread>
 #include <vector>
 
 #include "as_common.hpp"
@@ -152,6 +154,7 @@ void as_free_space(as_space* sp) {
     if (sp->qcache_b3) as_query_free(sp->qcache_b3);
     if (sp->qcache_b4) as_query_free(sp->qcache_b4);
     subset_work_free(sp->score_ws);
+    lists_work_free(sp->lists_ws);
     if (sp->stream) hipStreamSynchronize(sp->stream);
     hipFree(sp->x32); hipFree(sp->xs); hipFree(sp->x8); hipFree(sp->x8h); hipFree(sp->fa8); hipFree(sp->x64); hipFree(sp->n64); hipFree(sp->n32); hipFree(sp->inorm32);
     hipFree(sp->lam64); hipFree(sp->lam32);
@@ -1301,6 +1304,152 @@ as_status as_score_items_batch(const as_space* sp, const as_graph* gr, const dou
     AS_HIP(hipSetDevice(sp->device));
     AS_TRY(score_ws_ids(sp, ids.data(), m));
     return subset_batch_run(sp, sp->score_ws, m, queries, b, lq.data(), st.data(), tau, 0, 0, nullptr, nullptr, nullptr, out_scores);
+}
+
+// ---------------------------------------------------------------- per-query candidate lists (extension)
+// What both forms check before anything is launched, the lambda_q step included: the offsets, the total, every id.
+static as_status lists_checks(const char* who, const as_space* sp, const int64_t* ids_host, const int64_t* offs, int64_t b) {
+    if (offs[0] != 0) {
+        set_err("%s: offsets[0] must be 0, got %lld", who, (long long)offs[0]);
+        return AS_EINVAL;
+    }
+    for (int64_t i = 0; i < b; ++i)
+        if (offs[i + 1] < offs[i]) {
+            set_err("%s: offsets must not decrease (offsets[%lld] = %lld after %lld)", who, (long long)(i + 1), (long long)offs[i + 1],
+                    (long long)offs[i]);
+            return AS_EINVAL;
+        }
+    if (offs[b] >= (int64_t)1 << 31) {
+        set_err("%s: %lld ids exceed the supported maximum of 2^31 - 1 per call", who, (long long)offs[b]);
+        return AS_EUNSUPPORTED;
+    }
+    for (int64_t i = 0; i < b; ++i)
+        for (int64_t e = offs[i]; e < offs[i + 1]; ++e)
+            if (ids_host[e] < 0 || ids_host[e] >= sp->n) {
+                set_err("%s: id %lld of list %lld is outside [0, %lld)", who, (long long)ids_host[e], (long long)i, (long long)sp->n);
+                return AS_EINVAL;
+            }
+    return AS_OK;
+}
+// the lists as 32-bit ids (item ids fit: space_new refuses n >= 2^31); dedupe: every list without its repeated ids, the first
+// occurrence kept (offs: the new offsets) -- one pass with a stamp per item, the list that saw it last.  Does not depend on
+// lambda_q: lists_call runs it on a helper thread beside the lambda_q step (no set_err here: the message is the caller's).
+// false: out of host memory
+static bool lists_ids32(const as_space* sp, const int64_t* ids_host, const int64_t* offs_in, int64_t b, bool dedupe, std::vector<int32_t>& ids,
+                        std::vector<int64_t>& offs) {
+    try {
+        ids.resize((size_t)offs_in[b]);
+        offs.assign(offs_in, offs_in + b + 1);
+        if (!dedupe) {
+            for (int64_t e = 0; e < offs_in[b]; ++e) ids[e] = (int32_t)ids_host[e];
+            return true;
+        }
+        std::vector<int32_t> seen((size_t)sp->n, -1);
+        int64_t o = 0;
+        for (int64_t i = 0; i < b; ++i) {
+            offs[i] = o;
+            for (int64_t e = offs_in[i]; e < offs_in[i + 1]; ++e) {
+                const int64_t j = ids_host[e];
+                if (seen[j] == (int32_t)i) continue;
+                seen[j] = (int32_t)i;
+                ids[o++] = (int32_t)j;
+            }
+        }
+        offs[b] = o;
+    } catch (const std::bad_alloc&) {
+        return false;
+    }
+    return true;
+}
+static int64_t host_ns_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+}
+// the two forms: select: the first kk of every list, else every score.  lists_count[4] takes the host time the call spends
+// serially: the checks, the wait for the helper thread after the lambda_q step, the work tables.
+static as_status lists_call(const char* who, const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau,
+                            const int64_t* ids_host, const int64_t* offs_host, bool select, int64_t* out_idx, double* out_score,
+                            int64_t* out_len, double* out_scores, double* out_lambda_q, int32_t* out_status) {
+    AS_TRY(subset_checks(who, sp, gr, d, &tau, 1));
+    auto t0 = std::chrono::steady_clock::now();
+    AS_TRY(lists_checks(who, sp, ids_host, offs_host, b));
+    sp->lists_count[4].fetch_add(host_ns_since(t0), std::memory_order_relaxed);
+    sp->lists_count[0].fetch_add(1, std::memory_order_relaxed);
+    if (b == 0) return AS_OK;
+    std::vector<int32_t> ids;
+    std::vector<int64_t> offs;
+    bool ids_ok = true;
+    std::thread helper;
+    try {
+        helper = std::thread([&] { ids_ok = lists_ids32(sp, ids_host, offs_host, b, select, ids, offs); });
+    } catch (const std::system_error&) {   // no thread to be had: in line
+        ids_ok = lists_ids32(sp, ids_host, offs_host, b, select, ids, offs);
+    }
+    std::vector<double> lq;
+    std::vector<int32_t> st;
+    sp->lists_count[3].fetch_add(1, std::memory_order_relaxed);
+    const as_status ls = batch_lambda_step(who, sp, gr, queries, b, d, tau, lq, st);
+    t0 = std::chrono::steady_clock::now();
+    if (helper.joinable()) helper.join();
+    sp->lists_count[4].fetch_add(host_ns_since(t0), std::memory_order_relaxed);
+    if (ls != AS_OK) return ls;
+    if (!ids_ok) {
+        set_err("%s: out of host memory for %lld ids", who, (long long)offs_host[b]);
+        return AS_ENOMEM;
+    }
+    for (int64_t i = 0; i < b; ++i) {
+        if (out_lambda_q) out_lambda_q[i] = lq[i];
+        if (out_status) out_status[i] = st[i];
+    }
+    const int64_t kk = select ? std::min<int64_t>(gr->gp.topk, sp->n) : 0;
+    int64_t counts[3] = {0, 0, 0};
+    as_status r;
+    {
+        std::lock_guard<std::mutex> lk(sp->lmu);
+        r = hipSetDevice(sp->device) == hipSuccess ? AS_OK : AS_EHIP;
+        if (r != AS_OK) set_err("%s: hipSetDevice failed", who);
+        else r = lists_run(sp, ids.data(), offs.data(), queries, b, lq.data(), st.data(), tau, kk, out_idx, out_score, out_len, out_scores, counts);
+    }
+    sp->lists_count[1].fetch_add(counts[0], std::memory_order_relaxed);
+    sp->lists_count[2].fetch_add(counts[1], std::memory_order_relaxed);
+    sp->lists_count[4].fetch_add(counts[2], std::memory_order_relaxed);
+    return r;
+}
+
+as_status as_score_lists_batch(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau,
+                               const int64_t* ids_host, const int64_t* offsets_host, double* out_scores, double* out_lambda_q,
+                               int32_t* out_status) {
+    if (!sp || !gr || b < 0 || !offsets_host || (b > 0 && !queries) || (offsets_host[b] > 0 && (!ids_host || !out_scores))) {
+        set_err("as_score_lists_batch: null argument");
+        return AS_EINVAL;
+    }
+    return lists_call("as_score_lists_batch", sp, gr, queries, b, d, tau, ids_host, offsets_host, false, nullptr, nullptr, nullptr, out_scores,
+                      out_lambda_q, out_status);
+}
+
+as_status as_search_lists_batch(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau,
+                                const int64_t* ids_host, const int64_t* offsets_host, int64_t* out_idx, double* out_score, int64_t* out_len,
+                                double* out_lambda_q, int32_t* out_status) {
+    if (!sp || !gr || b < 0 || !offsets_host || (b > 0 && (!queries || !out_len)) || (offsets_host[b] > 0 && (!ids_host || !out_idx || !out_score))) {
+        set_err("as_search_lists_batch: null argument");
+        return AS_EINVAL;
+    }
+    return lists_call("as_search_lists_batch", sp, gr, queries, b, d, tau, ids_host, offsets_host, true, out_idx, out_score, out_len, nullptr,
+                      out_lambda_q, out_status);
+}
+
+as_status as_lists_counters(const as_space* sp, int64_t* out, int32_t n) {
+    if (!sp || !out) {
+        set_err("as_lists_counters: null argument");
+        return AS_EINVAL;
+    }
+    for (int i = 0; i < n && i < 5; ++i) out[i] = sp->lists_count[i].load(std::memory_order_relaxed);
+    return AS_OK;
+}
+
+double as_lists_kernel_us(const as_space* sp) {
+    if (!sp) return 0.0;
+    std::lock_guard<std::mutex> lk(sp->lmu);
+    return lists_kernel_us(sp->lists_ws);
 }
 
 // ---------------------------------------------------------------- tau sweeps over a subset (extension)

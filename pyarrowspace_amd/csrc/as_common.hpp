@@ -46,7 +46,7 @@ void dbg(const char* fmt, ...);
 
 }  // namespace as
 
-namespace as { struct SubsetWork; }
+namespace as { struct SubsetWork; struct ListsWork; }
 
 // ---------------------------------------------------------------- handles
 // HBM layout: x32 is the scan/MFMA operand, [np][dp] fp32,
@@ -142,6 +142,12 @@ struct as_space {
     // as_score_items: the score kernel's buffers (as_subset.hip), made on first use and grown on demand; calls are serialised (smu)
     mutable struct as::SubsetWork* score_ws = nullptr;
     mutable std::mutex smu;
+    // as_score_lists_batch / as_search_lists_batch: their buffers (as_lists.hip), made on first use and grown on demand; calls
+    // are serialised (lmu).  as_lists_counters: [0] calls, [1] score-kernel launches, [2] (query, item) pairs scored, [3] lambda_q
+    // steps run, [4] host nanoseconds spent on id checks, deduplication and work tables
+    mutable struct as::ListsWork* lists_ws = nullptr;
+    mutable std::mutex lmu;
+    mutable std::atomic<int64_t> lists_count[5] = {};
     mutable int64_t unproven_searches = 0;   // searches returned although their a-posteriori check failed on the strongest path
     mutable double kstats[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // accumulated by as_knn_rows
 };
@@ -590,5 +596,18 @@ as_status subset_sweep_run(const as_space* sp, SubsetWork* w, int64_t m, const d
 as_status subset_batch_sweep_run(const as_space* sp, SubsetWork* w, int64_t m, const double* queries, int64_t b, const double* lq,
                                  const int32_t* status, const double* taus, int64_t nt, const int64_t* row, int64_t ntau, int64_t k,
                                  int64_t* out_idx, double* out_score, int64_t* out_len, double* out_scores, int64_t* counts);
+// Per-query candidate lists (as_lists.hip): list i = ids[offs[i] .. offs[i + 1]) (item ids, checked by the
+// caller; the search form: distinct within a list) belongs to query i.  One ragged score launch per chunk of queries whose
+// entries fit the "subset_batch_mib" budget.  kk > 0: the first min(kk, list length) of every list by (score descending, index
+// ascending) -> out_idx / out_score + i * kk, out_len[i]; kk == 0: every score -> out_scores[offs[i] ..].  status
+// AS_EZEROLAMBDA: nothing is scored or written for that query (out_len 0).  counts[0] += score-kernel launches, [1] += pairs
+// scored, [2] += host nanoseconds spent on the work tables.  The buffers live in sp->lists_ws (under sp->lmu).
+as_status lists_run(const as_space* sp, const int32_t* ids, const int64_t* offs, const double* queries, int64_t b, const double* lq,
+                    const int32_t* status, double tau, int64_t kk, int64_t* out_idx, double* out_score, int64_t* out_len,
+                    double* out_scores, int64_t* counts);
+void lists_work_free(ListsWork* w);
+double lists_kernel_us(const ListsWork* w);
+void set_lists_timing(int v);   // as_set_tuning("lists_timing", 0 | 1)
+void set_lists_budget_mib(int v);   // as_set_tuning("subset_batch_mib", v): the value set_subset_batch_mib gets
 
 }  // namespace as

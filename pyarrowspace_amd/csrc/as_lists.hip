@@ -1,0 +1,564 @@
+// Per-query candidate lists: b queries, each with its own list of item ids.  One ragged launch scores
+// every (query, item) pair of a chunk of queries (lists_score_kernel: the lists cut into segments of at most LISTS_R entries, a block
+// per segment, the single-query kernel's row loop inside), one block per list selects its first k entries exactly
+// (lists_select_kernel: a radix select over LDS histograms, then a rank of at most 1024 entries).
+// Entry points: as_api.hip (as_score_lists_batch, as_search_lists_batch).
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <new>
+
+#include "as_common.hpp"
+
+namespace as {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int LISTS_ROWS = 4;         // rows in flight per wave, as subset_score_kernel (as_subset.hip)
+constexpr int LISTS_WAVES = 4;        // waves per block
+constexpr int LISTS_R = 64;           // entries per segment: staging a query (dp * 8 bytes) is 2 / R of the segment's fp32 row bytes (1 / R of fp64 rows)
+constexpr int LISTS_Q_LDS = 4096;     // the query sits in LDS up to this many doubles, as SUB_Q_LDS
+constexpr int LISTS_BLOCKS_PER_CU = 4;
+constexpr int64_t LISTS_QC_MAX = 4096;   // queries per chunk at most (the pinned results and the tables are sized by it)
+
+struct ListsSeg {    // a work item of lists_score_kernel: 1 <= `count` <= LISTS_R consecutive entries of one list of the chunk
+    int64_t first;   // entry of the chunk
+    int32_t query;   // query of the chunk
+    int32_t count;
+};
+struct ListsList {   // a list of the chunk for lists_select_kernel
+    int64_t first;
+    int64_t len;     // 0: empty, or a query that is not served (lambda_q == 0)
+};
+
+struct ListsArgs {
+    const ListsSeg* segs;
+    int64_t nseg;
+    const int32_t* ids;
+    const float* x32;
+    const double* x64;
+    const double* n64;
+    const double* lam64;
+    const double* q64;   // [nb][dp] the chunk's queries, zero padded
+    const double* nq;    // [nb] |q|^2
+    const double* lq;    // [nb] lambda_q
+    double* scores;      // [entries of the chunk]
+    int64_t d, dp;
+    double tau;
+};
+
+// A block takes segments grid-stride; per segment it stages the segment's query in LDS (QLDS; not again when the block's
+// previous segment had the same one) and runs subset_score_kernel's trip over the segment's rows: one wave per row, LISTS_ROWS
+// rows at a time, every load of the four issued before the first FMA, the ids wave-uniform and fetched one trip ahead.  Lane
+// partition, accumulation order and butterfly are that kernel's, and a row's are the same wherever its entry stands: the bits
+// of a score depend on the query, the row, tau and lambda_q only (and equal the single form's for the same lambda_q).
+template <bool F64, bool QLDS>
+__global__ __launch_bounds__(256) void lists_score_kernel(ListsArgs a) {
+    extern __shared__ double qs[];
+    const int lane = lane_id();
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    constexpr int64_t step = LISTS_WAVES * LISTS_ROWS;
+    int staged = -1;
+    for (int64_t s = blockIdx.x; s < a.nseg; s += gridDim.x) {
+        const ListsSeg sg = a.segs[s];   // (s is uniform: scalar loads)
+        const double* qg = a.q64 + (int64_t)sg.query * a.dp;
+        if (QLDS && sg.query != staged) {
+            __syncthreads();   // every wave has finished the previous segment's reads of qs
+            for (int64_t c = threadIdx.x; c < a.dp; c += blockDim.x) qs[c] = qg[c];
+            __syncthreads();
+            staged = sg.query;
+        }
+        const double nqv = a.nq[sg.query], lqv = a.lq[sg.query];
+        const int64_t end = sg.first + sg.count, last = end - 1;
+        int64_t g = sg.first + (int64_t)w * LISTS_ROWS;
+        int32_t next[LISTS_ROWS];
+#pragma unroll
+        for (int r = 0; r < LISTS_ROWS; ++r) next[r] = a.ids[min(g + r, last)];
+        for (; g < end; g += step) {
+            int64_t row[LISTS_ROWS];
+#pragma unroll
+            for (int r = 0; r < LISTS_ROWS; ++r) row[r] = next[r];   // (a short last group reads its last row again)
+#pragma unroll
+            for (int r = 0; r < LISTS_ROWS; ++r) next[r] = a.ids[min(g + step + r, last)];
+            double nrm = 0.0, lam = 0.0;
+            if (lane < LISTS_ROWS) {
+                const int64_t j = lane == 0 ? row[0] : lane == 1 ? row[1] : lane == 2 ? row[2] : row[3];
+                nrm = a.n64[j];
+                lam = a.lam64[j];
+            }
+            double acc[LISTS_ROWS];
+#pragma unroll
+            for (int r = 0; r < LISTS_ROWS; ++r) acc[r] = 0.0;
+            if (F64) {
+                constexpr int U = 6;
+                for (int64_t base = 0; base < a.d; base += 64 * U) {
+                    double v[LISTS_ROWS][U];
+#pragma unroll
+                    for (int r = 0; r < LISTS_ROWS; ++r) {
+                        const double* pj = a.x64 + row[r] * a.d;
+#pragma unroll
+                        for (int u = 0; u < U; ++u) {
+                            const int64_t e = base + 64 * u + lane;
+                            v[r][u] = e < a.d ? pj[e] : 0.0;
+                        }
+                    }
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        const int64_t e = base + 64 * u + lane;
+                        if (e < a.d) {
+                            const double qv = QLDS ? qs[e] : qg[e];
+#pragma unroll
+                            for (int r = 0; r < LISTS_ROWS; ++r) acc[r] += qv * v[r][u];
+                        }
+                    }
+                }
+            } else {
+                constexpr int U = 3;
+                for (int64_t base = 0; base < a.dp; base += 256 * U) {
+                    f32x4 v[LISTS_ROWS][U];
+#pragma unroll
+                    for (int r = 0; r < LISTS_ROWS; ++r) {
+                        const float* pj = a.x32 + row[r] * a.dp;
+#pragma unroll
+                        for (int u = 0; u < U; ++u) {
+                            const int64_t e = base + 256 * u + 4 * lane;   // (dp is a multiple of 32: e < dp leaves 4 floats)
+                            v[r][u] = e < a.dp ? *(const f32x4*)(pj + e) : f32x4{0, 0, 0, 0};
+                        }
+                    }
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        const int64_t e = base + 256 * u + 4 * lane;
+                        if (e < a.dp) {
+#pragma unroll
+                            for (int t = 0; t < 4; ++t) {
+                                const double qv = QLDS ? qs[e + t] : qg[e + t];
+#pragma unroll
+                                for (int r = 0; r < LISTS_ROWS; ++r) acc[r] += qv * (double)v[r][u][t];
+                            }
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < LISTS_ROWS; ++r) acc[r] = wave_sum(acc[r]);
+            if (lane < LISTS_ROWS && g + lane < end) {
+                const double dot = lane == 0 ? acc[0] : lane == 1 ? acc[1] : lane == 2 ? acc[2] : acc[3];
+                const double den = sqrt(nrm * nqv);
+                const double c = den > 0.0 ? dot / den : 0.0;
+                a.scores[g + lane] = blend_score(a.tau, c, lqv, lam);
+            }
+        }
+    }
+}
+static_assert(LISTS_ROWS == 4, "the lane selects of lists_score_kernel are written for four rows");
+
+// ------------------------------------------------------------------ selection
+// Key of an entry: 96 bits, hi = the score's bits mapped so that a larger score is a larger number (as_subset.hip's sel_ord,
+// restated here: NaN lowest, -0 as +0), lo = ~id: among equal scores the smaller index is the larger key, whatever the caller's
+// order.  The ids of a list are distinct (the host removes duplicates), so no two keys of a list are equal.
+constexpr int LSEL_NT = 256;
+constexpr int LSEL_BINS = 4096;   // 12 bits a pass, most significant first
+constexpr int LSEL_PASSES = 8;
+constexpr int LSEL_CAP = 1024;    // entries the final rank takes (== SUBSET_TOPK >= k)
+static_assert(LSEL_BINS == 16 * LSEL_NT && LSEL_CAP >= SUBSET_TOPK, "a thread owns 16 bins; the rank holds every requested entry");
+
+__device__ __forceinline__ unsigned long long lsel_ord(double s) {
+    if (s != s) return 0ull;
+    if (s == 0.0) s = 0.0;
+    const unsigned long long b = (unsigned long long)__double_as_longlong(s);
+    return (b & 0x8000000000000000ull) ? ~b : (b | 0x8000000000000000ull);
+}
+// digit p (0 = most significant) of the key hi:lo
+__device__ __forceinline__ unsigned int lsel_digit(unsigned long long hi, unsigned int lo, int p) {
+    if (p <= 4) return (unsigned int)(hi >> (52 - 12 * p)) & 0xfffu;
+    if (p == 5) return ((unsigned int)(hi & 0xfull) << 8) | (lo >> 24);
+    return p == 6 ? (lo >> 12) & 0xfffu : lo & 0xfffu;
+}
+// the key agrees with T in its first p digits
+__device__ __forceinline__ bool lsel_match(unsigned long long hi, unsigned int lo, unsigned long long t_hi, unsigned int t_lo, int p) {
+    const int nb = 12 * p;
+    const unsigned long long mh = nb >= 64 ? ~0ull : (nb == 0 ? 0ull : ~0ull << (64 - nb));
+    const unsigned int ml = nb <= 64 ? 0u : ~0u << (96 - nb);
+    return ((hi ^ t_hi) & mh) == 0ull && ((lo ^ t_lo) & ml) == 0u;
+}
+
+struct ListsSelArgs {
+    const ListsList* lists;
+    const double* scores;
+    const int32_t* ids;
+    int64_t kk;          // entries asked for per list; the stride of out_idx / out_score
+    int64_t* out_len;    // pinned [nb]
+    int64_t* out_idx;    // pinned [nb][kk]
+    double* out_score;
+};
+
+// One block per list, any length.  A list of more than LSEL_CAP entries: the digits of the k-th largest key T are found most
+// significant first, each pass a histogram in LDS of the entries that agree with T's digits so far; the passes stop as soon as
+// the entries at or above T's prefix (T's unknown digits zero) number at most LSEL_CAP -- after the last pass exactly k do.
+// Then (every list) the entries with key >= T are collected in LDS and ranked; the first k go to the pinned result.
+__global__ __launch_bounds__(LSEL_NT) void lists_select_kernel(ListsSelArgs a) {
+    __shared__ unsigned int hist[LSEL_BINS];
+    __shared__ unsigned long long sk[LSEL_CAP];
+    __shared__ int32_t sid[LSEL_CAP], spos[LSEL_CAP];
+    __shared__ unsigned int wtot[LSEL_NT / 64], r_dg, r_krem, r_cnt, s_n;
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const ListsList L = a.lists[blockIdx.x];
+    const int64_t m = L.len;
+    if (m <= 0) {   // (uniform)
+        if (t == 0) a.out_len[blockIdx.x] = 0;
+        return;
+    }
+    const unsigned int k = (unsigned int)min(a.kk, m);
+    const double* __restrict__ sc = a.scores + L.first;
+    const int32_t* __restrict__ id = a.ids + L.first;
+    unsigned long long t_hi = 0ull;
+    unsigned int t_lo = 0u;
+    if (m > LSEL_CAP) {
+        unsigned int krem = k;   // rank still to find among the entries that agree with T's digits (1-based, from the top)
+        for (int p = 0; p < LSEL_PASSES; ++p) {
+            for (int b = t; b < LSEL_BINS; b += LSEL_NT) hist[b] = 0u;
+            __syncthreads();
+            for (int64_t i = t; i < m; i += LSEL_NT) {
+                const unsigned long long hi = lsel_ord(sc[i]);
+                const unsigned int lo = ~(unsigned int)id[i];
+                if (lsel_match(hi, lo, t_hi, t_lo, p)) atomicAdd(&hist[lsel_digit(hi, lo, p)], 1u);
+            }
+            __syncthreads();
+            // the bin that holds rank krem: thread t owns bins 16 t .. 16 t + 15 (sel_advance of as_subset.hip)
+            unsigned int h[16], s = 0;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                h[j] = hist[16 * t + j];
+                s += h[j];
+            }
+            unsigned int sfx = s;   // inclusive suffix sum over the lanes
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const unsigned int v = __shfl_down(sfx, o, 64);
+                if (lane + o < 64) sfx += v;
+            }
+            if (lane == 0) wtot[w] = sfx;
+            if (t == 0) {
+                r_dg = 0;
+                r_krem = krem;
+                r_cnt = 0;
+            }
+            __syncthreads();
+            unsigned int above = sfx - s;
+            for (int u = w + 1; u < LSEL_NT / 64; ++u) above += wtot[u];
+            if (above < krem && krem <= above + s) {   // the rank falls into this thread's 16 bins
+                unsigned int acc = above;
+                bool done = false;
+#pragma unroll
+                for (int j = 15; j >= 0; --j) {
+                    if (!done) {
+                        if (krem <= acc + h[j]) {
+                            r_dg = 16 * t + j;
+                            r_krem = krem - acc;
+                            r_cnt = h[j];
+                            done = true;
+                        } else {
+                            acc += h[j];
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+            const unsigned int dg = r_dg, cnt = r_cnt;
+            krem = r_krem;
+            if (p <= 4) t_hi |= (unsigned long long)dg << (52 - 12 * p);
+            else if (p == 5) {
+                t_hi |= (unsigned long long)(dg >> 8);
+                t_lo |= (dg & 0xffu) << 24;
+            } else t_lo |= p == 6 ? dg << 12 : dg;
+            // k - krem entries lie above T's prefix, cnt agree with it
+            if (k - krem + cnt <= (unsigned int)LSEL_CAP) break;   // (uniform)
+        }
+    }
+    if (t == 0) s_n = 0u;
+    __syncthreads();
+    for (int64_t i = t; i < m; i += LSEL_NT) {
+        const unsigned long long hi = lsel_ord(sc[i]);
+        const int32_t j = id[i];
+        const unsigned int lo = ~(unsigned int)j;
+        if (hi > t_hi || (hi == t_hi && lo >= t_lo)) {
+            const unsigned int slot = atomicAdd(&s_n, 1u);
+            if (slot < (unsigned int)LSEL_CAP) {
+                sk[slot] = hi;
+                sid[slot] = j;
+                spos[slot] = (int32_t)i;
+            }
+        }
+    }
+    __syncthreads();
+    const int n = (int)min(s_n, (unsigned int)LSEL_CAP);
+    for (int e = t; e < n; e += LSEL_NT) {
+        const unsigned long long myk = sk[e];
+        const int32_t myi = sid[e];
+        unsigned int rank = 0;
+        for (int u = 0; u < n; ++u) rank += (sk[u] > myk || (sk[u] == myk && sid[u] < myi)) ? 1u : 0u;
+        if (rank < k) {
+            a.out_idx[blockIdx.x * a.kk + rank] = myi;
+            a.out_score[blockIdx.x * a.kk + rank] = sc[spos[e]];
+        }
+    }
+    if (t == 0) a.out_len[blockIdx.x] = (int64_t)min((unsigned int)n, k);
+}
+
+// ------------------------------------------------------------------ host side
+// |q|^2 in subset_query_norm's order (as_subset.hip; the order of q_prepare_kernel and host_query_norm of as_search.hip): 256
+// partial sums, element c in partial c % 256, products and sums rounded separately, then a pairwise tree -- the same bits, so the
+// cosines share their denominator with the single forms.  Whoever changes that order there changes it here.
+static double lists_query_norm(const double* q, int64_t d) {
+    double p[256];
+    for (int t = 0; t < 256; ++t) p[t] = 0.0;
+    for (int64_t c = 0; c < d; ++c) {
+        volatile double sq = q[c] * q[c];
+        p[c & 255] = p[c & 255] + sq;
+    }
+    for (int o = 128; o > 0; o >>= 1)
+        for (int t = 0; t < o; ++t) p[t] += p[t + o];
+    return p[0];
+}
+
+static std::atomic<int> g_lists_timing{0};
+static std::atomic<int> g_lists_budget_mib{256};
+void set_lists_timing(int v) { g_lists_timing.store(v ? 1 : 0, std::memory_order_relaxed); }
+void set_lists_budget_mib(int v) { g_lists_budget_mib.store(v > 0 ? v : 256, std::memory_order_relaxed); }
+
+struct ListsWork {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    int cus = 256;
+    // one upload per chunk: [nb][dp] queries, [nb] |q|^2, [nb] lambda_q, the segments, the lists, the ids
+    char* up_d = nullptr;
+    char* up_h = nullptr;          // pinned staging of the same
+    size_t up_bytes = 0;
+    double* scores = nullptr;      // [scores_n] the chunk's scores, entry by entry
+    int64_t scores_n = 0;
+    int64_t* out_len = nullptr;    // pinned results of the selection: [out_q], [out_e] entries at stride kk
+    int64_t* out_idx = nullptr;
+    double* out_score = nullptr;
+    int64_t out_q = 0, out_e = 0;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    double kernel_us = 0.0;        // the score kernel summed over the chunks of the last timed call
+};
+
+void lists_work_free(ListsWork* w) {
+    if (!w) return;
+    (void)hipSetDevice(w->device);
+    if (w->stream) (void)hipStreamSynchronize(w->stream);
+    (void)hipFree(w->up_d);
+    (void)hipFree(w->scores);
+    if (w->up_h) (void)hipHostFree(w->up_h);
+    if (w->out_len) (void)hipHostFree(w->out_len);
+    if (w->out_idx) (void)hipHostFree(w->out_idx);
+    if (w->out_score) (void)hipHostFree(w->out_score);
+    for (int i = 0; i < 2; ++i)
+        if (w->ev[i]) (void)hipEventDestroy(w->ev[i]);
+    if (w->stream) (void)hipStreamDestroy(w->stream);
+    delete w;
+}
+
+double lists_kernel_us(const ListsWork* w) { return w ? w->kernel_us : 0.0; }
+
+static as_status lists_work_create(const as_space* sp, ListsWork** out) {
+    ListsWork* w = new (std::nothrow) ListsWork();
+    if (!w) {
+        set_err("lists: out of host memory");
+        return AS_ENOMEM;
+    }
+    w->device = sp->device;
+    if (hipDeviceGetAttribute(&w->cus, hipDeviceAttributeMultiprocessorCount, sp->device) != hipSuccess || w->cus <= 0) w->cus = 256;
+    hipError_t e;
+    if ((e = hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking)) != hipSuccess || (e = hipEventCreate(&w->ev[0])) != hipSuccess ||
+        (e = hipEventCreate(&w->ev[1])) != hipSuccess) {
+        set_err("lists: creation of the stream and events failed: %s", hipGetErrorString(e));
+        lists_work_free(w);
+        return AS_EHIP;
+    }
+    *out = w;
+    return AS_OK;
+}
+
+// room for a chunk: `up` bytes of upload, ne scores, and for the selection nb lists of kk entries; each grown by half again
+static as_status lists_reserve(ListsWork* w, size_t up, int64_t ne, int64_t nb, int64_t kk) {
+    hipError_t e = hipSuccess;
+    const char* what = "upload";
+    if (up > w->up_bytes) {
+        (void)hipFree(w->up_d);
+        if (w->up_h) (void)hipHostFree(w->up_h);
+        w->up_d = w->up_h = nullptr;
+        w->up_bytes = 0;
+        const size_t cap = up + up / 2;
+        if ((e = hipMalloc((void**)&w->up_d, cap)) == hipSuccess && (e = hipHostMalloc((void**)&w->up_h, cap, hipHostMallocDefault)) == hipSuccess)
+            w->up_bytes = cap;
+    }
+    if (e == hipSuccess && ne > w->scores_n) {
+        what = "scores";
+        (void)hipFree(w->scores);
+        w->scores = nullptr;
+        w->scores_n = 0;
+        const int64_t cap = ne + ne / 2;
+        if ((e = hipMalloc((void**)&w->scores, sizeof(double) * (size_t)cap)) == hipSuccess) w->scores_n = cap;
+    }
+    if (e == hipSuccess && kk > 0 && (nb > w->out_q || nb * kk > w->out_e)) {
+        what = "results";
+        if (w->out_len) (void)hipHostFree(w->out_len);
+        if (w->out_idx) (void)hipHostFree(w->out_idx);
+        if (w->out_score) (void)hipHostFree(w->out_score);
+        w->out_len = w->out_idx = nullptr;
+        w->out_score = nullptr;
+        w->out_q = w->out_e = 0;
+        const int64_t cq = std::max<int64_t>(nb + nb / 2, w->out_q), ce = std::max<int64_t>(cq * kk, w->out_e);
+        if ((e = hipHostMalloc((void**)&w->out_len, sizeof(int64_t) * (size_t)cq, hipHostMallocDefault)) == hipSuccess &&
+            (e = hipHostMalloc((void**)&w->out_idx, sizeof(int64_t) * (size_t)ce, hipHostMallocDefault)) == hipSuccess &&
+            (e = hipHostMalloc((void**)&w->out_score, sizeof(double) * (size_t)ce, hipHostMallocDefault)) == hipSuccess) {
+            w->out_q = cq;
+            w->out_e = ce;
+        }
+    }
+    if (e != hipSuccess) {
+        set_err("lists: allocation of the work buffers (%s, %lld queries, %lld entries) failed: %s", what, (long long)nb, (long long)ne,
+                hipGetErrorString(e));
+        return e == hipErrorOutOfMemory ? AS_ENOMEM : AS_EHIP;
+    }
+    return AS_OK;
+}
+
+as_status lists_run(const as_space* sp, const int32_t* ids, const int64_t* offs, const double* queries, int64_t b, const double* lq,
+                    const int32_t* status, double tau, int64_t kk, int64_t* out_idx, double* out_score, int64_t* out_len,
+                    double* out_scores, int64_t* counts) {
+    const bool sel = kk > 0;
+    if (sel)
+        for (int64_t i = 0; i < b; ++i) out_len[i] = 0;
+    if (b <= 0 || offs[b] == 0) return AS_OK;
+    if (!sp->lists_ws) AS_TRY(lists_work_create(sp, &sp->lists_ws));
+    ListsWork* w = sp->lists_ws;
+    const int64_t d = sp->d, dp = sp->dp;
+    const int64_t budget = std::max<int64_t>(((int64_t)g_lists_budget_mib.load(std::memory_order_relaxed) << 20) / (int64_t)sizeof(double), 1);
+    const bool timing = g_lists_timing.load(std::memory_order_relaxed) != 0;
+    const bool qlds = dp <= LISTS_Q_LDS;
+    const size_t lds = qlds ? sizeof(double) * (size_t)dp : 0;
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    w->kernel_us = 0.0;
+    for (int64_t i0 = 0; i0 < b;) {
+        // the chunk: queries i0 .. i1 - 1, as many as the budget holds scores for; a list longer than the budget is a chunk of its own
+        int64_t i1 = i0, ne = 0;
+        while (i1 < b && i1 - i0 < LISTS_QC_MAX) {
+            const int64_t m = offs[i1 + 1] - offs[i1];
+            if (i1 > i0 && ne + m > budget) break;
+            ne += m;
+            ++i1;
+        }
+        const int64_t nb = i1 - i0, base = offs[i0];
+        if (ne == 0) {   // empty lists only
+            i0 = i1;
+            continue;
+        }
+        const auto t0 = now();
+        const int64_t nseg_max = ne / LISTS_R + nb;
+        const size_t q_bytes = sizeof(double) * (size_t)(nb * (dp + 2));
+        const size_t seg_off = q_bytes, list_off = seg_off + sizeof(ListsSeg) * (size_t)nseg_max;
+        const size_t ids_off = list_off + sizeof(ListsList) * (size_t)nb, up = ids_off + sizeof(int32_t) * (size_t)ne;
+        AS_TRY(lists_reserve(w, up, ne, nb, kk));
+        double* hq = (double*)w->up_h;
+        double* hn = hq + nb * dp;
+        double* hl = hn + nb;
+        ListsSeg* hseg = (ListsSeg*)(w->up_h + seg_off);
+        ListsList* hlist = (ListsList*)(w->up_h + list_off);
+        int64_t nseg = 0, pairs = 0;
+        for (int64_t t = 0; t < nb; ++t) {
+            const int64_t i = i0 + t, first = offs[i] - base, m = offs[i + 1] - offs[i];
+            const double* q = queries + i * d;
+            double* row = hq + t * dp;
+            for (int64_t c = 0; c < d; ++c) row[c] = q[c];
+            for (int64_t c = d; c < dp; ++c) row[c] = 0.0;
+            hn[t] = lists_query_norm(q, d);
+            hl[t] = lq[i];
+            const bool served = status[i] != AS_EZEROLAMBDA;
+            hlist[t].first = first;
+            hlist[t].len = served ? m : 0;
+            if (!served) continue;
+            pairs += m;
+            // ceil(m / R) segments of nearly equal length (a list of 100: 50 + 50, not 64 + 36: the blocks' shares stay even)
+            const int64_t ns = (m + LISTS_R - 1) / LISTS_R;
+            for (int64_t u = 0, o = 0; u < ns; ++u) {
+                const int64_t cnt = m / ns + (u < m % ns ? 1 : 0);
+                hseg[nseg].first = first + o;
+                hseg[nseg].query = (int32_t)t;
+                hseg[nseg].count = (int32_t)cnt;
+                ++nseg;
+                o += cnt;
+            }
+        }
+        memcpy(w->up_h + ids_off, ids + base, sizeof(int32_t) * (size_t)ne);
+        counts[2] += std::chrono::duration_cast<std::chrono::nanoseconds>(now() - t0).count();
+        if (nseg > 0) {
+            AS_HIP(hipMemcpyAsync(w->up_d, w->up_h, up, hipMemcpyHostToDevice, w->stream));
+            ListsArgs a;
+            a.segs = (const ListsSeg*)(w->up_d + seg_off); a.nseg = nseg; a.ids = (const int32_t*)(w->up_d + ids_off);
+            a.x32 = sp->x32; a.x64 = sp->x64; a.n64 = sp->n64; a.lam64 = sp->lam64; a.q64 = (const double*)w->up_d;
+            a.nq = a.q64 + nb * dp; a.lq = a.nq + nb; a.scores = w->scores; a.d = d; a.dp = dp; a.tau = tau;
+            const unsigned grid = (unsigned)std::min<int64_t>(nseg, (int64_t)w->cus * LISTS_BLOCKS_PER_CU);
+            if (timing) AS_HIP(hipEventRecord(w->ev[0], w->stream));
+            if (sp->x64) {
+                if (qlds) hipLaunchKernelGGL((lists_score_kernel<true, true>), dim3(grid), dim3(256), lds, w->stream, a);
+                else hipLaunchKernelGGL((lists_score_kernel<true, false>), dim3(grid), dim3(256), 0, w->stream, a);
+            } else {
+                if (qlds) hipLaunchKernelGGL((lists_score_kernel<false, true>), dim3(grid), dim3(256), lds, w->stream, a);
+                else hipLaunchKernelGGL((lists_score_kernel<false, false>), dim3(grid), dim3(256), 0, w->stream, a);
+            }
+            AS_HIP(hipGetLastError());
+            if (timing) AS_HIP(hipEventRecord(w->ev[1], w->stream));
+            counts[0] += 1;
+            counts[1] += pairs;
+            if (sel) {
+                ListsSelArgs s;
+                s.lists = (const ListsList*)(w->up_d + list_off); s.scores = w->scores; s.ids = a.ids; s.kk = kk;
+                s.out_len = w->out_len; s.out_idx = w->out_idx; s.out_score = w->out_score;
+                hipLaunchKernelGGL(lists_select_kernel, dim3((unsigned)nb), dim3(LSEL_NT), 0, w->stream, s);
+                AS_HIP(hipGetLastError());
+            } else {
+                // one copy per run of served queries: the scores of a query that is not served stay unwritten
+                for (int64_t t = 0; t < nb;) {
+                    if (status[i0 + t] == AS_EZEROLAMBDA) {
+                        ++t;
+                        continue;
+                    }
+                    int64_t u = t;
+                    while (u < nb && status[i0 + u] != AS_EZEROLAMBDA) ++u;
+                    const int64_t e0 = offs[i0 + t] - base, e1 = offs[i0 + u] - base;
+                    if (e1 > e0)
+                        AS_HIP(hipMemcpyAsync(out_scores + base + e0, w->scores + e0, sizeof(double) * (size_t)(e1 - e0), hipMemcpyDeviceToHost,
+                                              w->stream));
+                    t = u;
+                }
+            }
+            AS_HIP(hipStreamSynchronize(w->stream));
+            if (timing) {
+                float ms = 0.0f;
+                AS_HIP(hipEventElapsedTime(&ms, w->ev[0], w->ev[1]));
+                w->kernel_us += (double)ms * 1e3;
+            }
+            if (sel)
+                for (int64_t t = 0; t < nb; ++t) {
+                    const int64_t i = i0 + t, want = std::min<int64_t>(kk, hlist[t].len);
+                    if (w->out_len[t] != want) {
+                        set_err("lists: the selection returned %lld of %lld entries for query %lld", (long long)w->out_len[t], (long long)want,
+                                (long long)i);
+                        return AS_EHIP;
+                    }
+                    for (int64_t r = 0; r < want; ++r) {
+                        out_idx[i * kk + r] = w->out_idx[t * kk + r];
+                        out_score[i * kk + r] = w->out_score[t * kk + r];
+                    }
+                    out_len[i] = want;
+                }
+        }
+        i0 = i1;
+    }
+    return AS_OK;
+}
+
+}  // namespace as

@@ -3661,6 +3661,11 @@ int32_t as_set_tuning(const char* key, int32_t value) {
     }
     if (key && !strcmp(key, "subset_batch_mib")) {
         set_subset_batch_mib(value);
+        set_lists_budget_mib(value);   // (the per-query list forms chunk by the same budget: as_lists.hip keeps its copy)
+        return 0;
+    }
+    if (key && !strcmp(key, "lists_timing")) {
+        set_lists_timing(value);
         return 0;
     }
     return 1;
