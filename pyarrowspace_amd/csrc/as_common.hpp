@@ -420,6 +420,28 @@ __device__ __forceinline__ double blend_score(double tau, double c, double lq, d
     return tau * c + (1.0 - tau) / (1.0 + fabs(lq - lj));
 }
 
+// Selection key of a scored entry (the filtered and the list searches): 96 bits hi:lo, hi = the score's bits mapped so that a
+// larger score is a larger number (NaN lowest, -0 as +0), lo = the caller's tie-break.  Eight digits of 12 bits.
+__device__ __forceinline__ unsigned long long sel_ord(double s) {
+    if (s != s) return 0ull;
+    if (s == 0.0) s = 0.0;
+    const unsigned long long b = (unsigned long long)__double_as_longlong(s);
+    return (b & 0x8000000000000000ull) ? ~b : (b | 0x8000000000000000ull);
+}
+// digit p (0 = most significant) of the key hi:lo
+__device__ __forceinline__ unsigned int sel_digit(unsigned long long hi, unsigned int lo, int p) {
+    if (p <= 4) return (unsigned int)(hi >> (52 - 12 * p)) & 0xfffu;
+    if (p == 5) return ((unsigned int)(hi & 0xfull) << 8) | (lo >> 24);
+    return p == 6 ? (lo >> 12) & 0xfffu : lo & 0xfffu;
+}
+// the key agrees with t_hi:t_lo in its first p digits
+__device__ __forceinline__ bool sel_match(unsigned long long hi, unsigned int lo, unsigned long long t_hi, unsigned int t_lo, int p) {
+    const int nb = 12 * p;
+    const unsigned long long mh = nb >= 64 ? ~0ull : (nb == 0 ? 0ull : ~0ull << (64 - nb));
+    const unsigned int ml = nb <= 64 ? 0u : ~0u << (96 - nb);
+    return ((hi ^ t_hi) & mh) == 0ull && ((lo ^ t_lo) & ml) == 0u;
+}
+
 // SPEC S4 edge weight.  gaussian: exp(-0.5 (d/sigma)^p); rational: 1/(1+(d/sigma)^p)
 __device__ __forceinline__ double edge_weight(double d, double sigma, double p, int kernel) {
     const double t = d / sigma;
@@ -432,6 +454,23 @@ __device__ __forceinline__ double edge_weight(double d, double sigma, double p, 
 
 // ---------------------------------------------------------------- internal entry points
 namespace as {
+
+// |q|^2 exactly as q_prepare_kernel (as_search.hip) forms it on the device -- 256 strided partial sums, element c in partial
+// c % 256, rounded products and sums, then the halving tree: the host-prepared fast path, the staged / batched paths and the
+// filtered and list searches must give a query the same norm, bit for bit, so that their cosines share a denominator.  Whoever
+// changes the order there changes it here.  (No fma on either side: std::fma without -mfma is a library call, 6 us for 768
+// elements.)
+inline double host_sumsq(const double* q, int64_t d) {
+    double p[256];
+    for (int t = 0; t < 256; ++t) p[t] = 0.0;
+    for (int64_t c = 0; c < d; ++c) {     // element c belongs to partial c % 256, visited in increasing c: the kernel's order
+        volatile double sq = q[c] * q[c];   // rounded product, kept apart from the sum (no contraction whatever the flags)
+        p[c & 255] = p[c & 255] + sq;
+    }
+    for (int o = 128; o > 0; o >>= 1)
+        for (int t = 0; t < o; ++t) p[t] += p[t + o];
+    return p[0];
+}
 
 struct Scratch;  // growable device scratch owned by a call
 

@@ -153,34 +153,14 @@ __global__ __launch_bounds__(256) void lists_score_kernel(ListsArgs a) {
 static_assert(LISTS_ROWS == 4, "the lane selects of lists_score_kernel are written for four rows");
 
 // ------------------------------------------------------------------ selection
-// Key of an entry: 96 bits, hi = the score's bits mapped so that a larger score is a larger number (as_subset.hip's sel_ord,
-// restated here: NaN lowest, -0 as +0), lo = ~id: among equal scores the smaller index is the larger key, whatever the caller's
+// Key of an entry: 96 bits, hi = the score's bits mapped so that a larger score is a larger number (sel_ord of as_common.hpp:
+// NaN lowest, -0 as +0), lo = ~id: among equal scores the smaller index is the larger key, whatever the caller's
 // order.  The ids of a list are distinct (the host removes duplicates), so no two keys of a list are equal.
 constexpr int LSEL_NT = 256;
 constexpr int LSEL_BINS = 4096;   // 12 bits a pass, most significant first
 constexpr int LSEL_PASSES = 8;
 constexpr int LSEL_CAP = 1024;    // entries the final rank takes (== SUBSET_TOPK >= k)
 static_assert(LSEL_BINS == 16 * LSEL_NT && LSEL_CAP >= SUBSET_TOPK, "a thread owns 16 bins; the rank holds every requested entry");
-
-__device__ __forceinline__ unsigned long long lsel_ord(double s) {
-    if (s != s) return 0ull;
-    if (s == 0.0) s = 0.0;
-    const unsigned long long b = (unsigned long long)__double_as_longlong(s);
-    return (b & 0x8000000000000000ull) ? ~b : (b | 0x8000000000000000ull);
-}
-// digit p (0 = most significant) of the key hi:lo
-__device__ __forceinline__ unsigned int lsel_digit(unsigned long long hi, unsigned int lo, int p) {
-    if (p <= 4) return (unsigned int)(hi >> (52 - 12 * p)) & 0xfffu;
-    if (p == 5) return ((unsigned int)(hi & 0xfull) << 8) | (lo >> 24);
-    return p == 6 ? (lo >> 12) & 0xfffu : lo & 0xfffu;
-}
-// the key agrees with T in its first p digits
-__device__ __forceinline__ bool lsel_match(unsigned long long hi, unsigned int lo, unsigned long long t_hi, unsigned int t_lo, int p) {
-    const int nb = 12 * p;
-    const unsigned long long mh = nb >= 64 ? ~0ull : (nb == 0 ? 0ull : ~0ull << (64 - nb));
-    const unsigned int ml = nb <= 64 ? 0u : ~0u << (96 - nb);
-    return ((hi ^ t_hi) & mh) == 0ull && ((lo ^ t_lo) & ml) == 0u;
-}
 
 struct ListsSelArgs {
     const ListsList* lists;
@@ -219,9 +199,9 @@ __global__ __launch_bounds__(LSEL_NT) void lists_select_kernel(ListsSelArgs a) {
             for (int b = t; b < LSEL_BINS; b += LSEL_NT) hist[b] = 0u;
             __syncthreads();
             for (int64_t i = t; i < m; i += LSEL_NT) {
-                const unsigned long long hi = lsel_ord(sc[i]);
+                const unsigned long long hi = sel_ord(sc[i]);
                 const unsigned int lo = ~(unsigned int)id[i];
-                if (lsel_match(hi, lo, t_hi, t_lo, p)) atomicAdd(&hist[lsel_digit(hi, lo, p)], 1u);
+                if (sel_match(hi, lo, t_hi, t_lo, p)) atomicAdd(&hist[sel_digit(hi, lo, p)], 1u);
             }
             __syncthreads();
             // the bin that holds rank krem: thread t owns bins 16 t .. 16 t + 15 (sel_advance of as_subset.hip)
@@ -278,7 +258,7 @@ __global__ __launch_bounds__(LSEL_NT) void lists_select_kernel(ListsSelArgs a) {
     if (t == 0) s_n = 0u;
     __syncthreads();
     for (int64_t i = t; i < m; i += LSEL_NT) {
-        const unsigned long long hi = lsel_ord(sc[i]);
+        const unsigned long long hi = sel_ord(sc[i]);
         const int32_t j = id[i];
         const unsigned int lo = ~(unsigned int)j;
         if (hi > t_hi || (hi == t_hi && lo >= t_lo)) {
@@ -306,21 +286,6 @@ __global__ __launch_bounds__(LSEL_NT) void lists_select_kernel(ListsSelArgs a) {
 }
 
 // ------------------------------------------------------------------ host side
-// |q|^2 in subset_query_norm's order (as_subset.hip; the order of q_prepare_kernel and host_query_norm of as_search.hip): 256
-// partial sums, element c in partial c % 256, products and sums rounded separately, then a pairwise tree -- the same bits, so the
-// cosines share their denominator with the single forms.  Whoever changes that order there changes it here.
-static double lists_query_norm(const double* q, int64_t d) {
-    double p[256];
-    for (int t = 0; t < 256; ++t) p[t] = 0.0;
-    for (int64_t c = 0; c < d; ++c) {
-        volatile double sq = q[c] * q[c];
-        p[c & 255] = p[c & 255] + sq;
-    }
-    for (int o = 128; o > 0; o >>= 1)
-        for (int t = 0; t < o; ++t) p[t] += p[t + o];
-    return p[0];
-}
-
 static std::atomic<int> g_lists_timing{0};
 static std::atomic<int> g_lists_budget_mib{256};
 void set_lists_timing(int v) { g_lists_timing.store(v ? 1 : 0, std::memory_order_relaxed); }
@@ -474,7 +439,7 @@ as_status lists_run(const as_space* sp, const int32_t* ids, const int64_t* offs,
             double* row = hq + t * dp;
             for (int64_t c = 0; c < d; ++c) row[c] = q[c];
             for (int64_t c = d; c < dp; ++c) row[c] = 0.0;
-            hn[t] = lists_query_norm(q, d);
+            hn[t] = host_sumsq(q, d);
             hl[t] = lq[i];
             const bool served = status[i] != AS_EZEROLAMBDA;
             hlist[t].first = first;

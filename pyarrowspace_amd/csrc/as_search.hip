@@ -71,7 +71,7 @@ __global__ void q_prepare_kernel(const double* __restrict__ qin, int64_t d, int6
     info += blockIdx.z;
     double s = 0.0;
     for (int64_t c = threadIdx.x; c < dp; c += blockDim.x) {
-#pragma clang fp contract(off)   // product and sum rounded separately: host_query_norm (and as_subset.hip, subset_query_norm) reproduce this sum bit for bit
+#pragma clang fp contract(off)   // product and sum rounded separately: host_sumsq (as_common.hpp) reproduces this sum bit for bit
         const double v = c < d ? qin[c] : 0.0;
         q64[c] = v;
         q32[c] = (float)v;
@@ -149,21 +149,6 @@ __global__ __launch_bounds__(256) void q_quant_batch_kernel(const float* __restr
         stat_host[2 * blockIdx.x] = u;
         stat_host[2 * blockIdx.x + 1] = v;
     }
-}
-
-// |q|^2 exactly as q_prepare_kernel forms it (256 strided partial sums, rounded products and sums, then the halving
-// tree): the host-prepared fast path and the staged / batched paths must give a query the same norm, bit for bit.
-// (No fma on either side: std::fma without -mfma is a library call, 6 us for 768 elements.)
-static double host_query_norm(const double* q, int64_t d) {
-    double p[256];
-    for (int t = 0; t < 256; ++t) p[t] = 0.0;
-    for (int64_t c = 0; c < d; ++c) {     // element c belongs to partial c % 256, visited in increasing c: the kernel's order
-        volatile double sq = q[c] * q[c];   // rounded product, kept apart from the sum (no contraction whatever the flags)
-        p[c & 255] = p[c & 255] + sq;
-    }
-    for (int o = 128; o > 0; o >>= 1)
-        for (int t = 0; t < o; ++t) p[t] += p[t + o];
-    return p[0];
 }
 
 // the per-search state of QInfo, cleared behind a finished search so that the next one starts without a launch for it
@@ -1152,6 +1137,63 @@ __device__ __forceinline__ void merge_partials(const T* pkey, const int* pidx, i
 constexpr int PRUNE_CAP = 2048;  // compact list of the radix-pruned candidates
 constexpr int Q_LDS_MAX = 4096;  // widest query (padded floats) the finish kernels keep in LDS (beyond: read from where it is staged)
 
+// Wave 0 (lane = its thread): the bin of a 1024-bin LDS histogram in which the running count reaches `want` -- 16 bins per lane,
+// inclusive scan over the lanes, the lane whose bins reach `want` finishes and stores the bin.
+// Contract: *bin is stored only where 1 <= want <= the histogram's sum; a caller that cannot promise that presets *bin.
+__device__ __forceinline__ void hist_kth_bin(const unsigned int* hist, unsigned int want, int lane, int* bin) {
+    unsigned int h[16], tot = 0;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        h[j] = hist[16 * lane + j];
+        tot += h[j];
+    }
+    unsigned int incl = tot;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned int t2 = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += t2;
+    }
+    const unsigned int excl = incl - tot;
+    if (want > 0 && excl < want && incl >= want) {
+        unsigned int run = excl;
+        int b = 16 * lane;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            run += h[j];
+            if (run >= want) break;
+            b += 1;
+        }
+        *bin = b;
+    }
+}
+
+// Every thread of the block.  Compacts the entries that `keep` keeps -- keep(u) for the thread's entries u = 0 .. 3; entry(u, key,
+// idx) gives a kept one's key and id -- into (pk, pi) through the LDS counter *cnt (0 on entry), barrier, and returns their
+// number R, the same in every thread.  R <= PRUNE_CAP: the kept entries are ranked against each other by (key asc, id asc) and
+// emit(rank, key, idx) is called for the ranks below M.  R > PRUNE_CAP: over() is called instead (every thread: a flag the
+// caller files) and nothing is emitted; what then is the caller's business.  No barrier behind the emits.
+template <typename T, typename Keep, typename Entry, typename Emit, typename Over>
+__device__ __forceinline__ int prune_and_rank(int* cnt, T* pk, int* pi, int M, Keep keep, Entry entry, Emit emit, Over over) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+        if (keep(u)) {
+            const int slot = atomicAdd(cnt, 1);
+            if (slot < PRUNE_CAP) entry(u, pk[slot], pi[slot]);
+        }
+    __syncthreads();
+    const int R = *cnt;
+    if (R > PRUNE_CAP) over();
+    else
+        for (int t = threadIdx.x; t < R; t += blockDim.x) {
+            const T k = pk[t];
+            const int i = pi[t];
+            int rank = 0;
+            for (int s = 0; s < R; ++s) rank += lex_less<T>(pk[s], pi[s], k, i) ? 1 : 0;
+            if (rank < M) emit(rank, k, i);
+        }
+    return R;
+}
+
 // rank-select the M smallest (key, idx) of the C buffered candidates into (fk, fi), sorted.
 // Large C (dense neighbourhoods) is first pruned to the candidates at or below the M-th
 // smallest key by a radix select, so the quadratic ranking only ever sees ~M entries.
@@ -1173,12 +1215,15 @@ __device__ __forceinline__ void select_candidates(const T* ckey, const int* cidx
         s_cnt = 0;
     }
     __syncthreads();
-    const T* rk = sk;
-    const int* ri = si;
-    int R = C;
+    auto emit = [&](int rank, T k, int i) {
+        fk[rank] = k;
+        fi[rank] = i;
+    };
     // a list as wide as the candidate set (topk above the number of rows that passed) keeps everything: a k-th
     // smallest beyond the set does not exist, and a select would return an arbitrary threshold
-    if (C > 128 && M < C) {
+    const bool pruned = C > 128 && M < C;
+    bool ranked = false;   // a prune has ranked its entries into (fk, fi)
+    if (pruned) {
         // One-pass prune: 1024 linear bins between the smallest and the largest key; the bin in which the cumulative
         // count reaches M bounds the M smallest (monotone binning), and the quadratic ranking below only sees that
         // prefix -- about M entries unless the keys pile up in one bin, which the radix select then handles.
@@ -1232,55 +1277,16 @@ __device__ __forceinline__ void select_candidates(const T* ckey, const int* cidx
             }
         }
         __syncthreads();
-        if (threadIdx.x < 64) {
-            // wave 0: 16 bins per lane, inclusive scan over lanes, the lane whose range reaches M finishes
-            unsigned int h[16], tot = 0;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                h[j] = lhist[16 * threadIdx.x + j];
-                tot += h[j];
-            }
-            unsigned int incl = tot;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const unsigned int t2 = __shfl_up(incl, o, 64);
-                if ((int)threadIdx.x >= o) incl += t2;
-            }
-            const unsigned int excl = incl - tot;
-            if (excl < (unsigned)M && incl >= (unsigned)M) {
-                unsigned int run = excl;
-                int b = 16 * threadIdx.x;
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    run += h[j];
-                    if (run >= (unsigned)M) break;
-                    b += 1;
-                }
-                s_bin = b;
-            }
-        }
+        if (threadIdx.x < 64) hist_kth_bin(lhist, (unsigned)M, (int)threadIdx.x, &s_bin);   // (1 <= M < C: the bin is always found)
         __syncthreads();
         const int bsel = s_bin;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if (have[q] && bin[q] <= bsel) {
-                const int slot = atomicAdd(&s_cnt, 1);
-                if (slot < PRUNE_CAP) {
-                    const int i = threadIdx.x + q * 1024;
-                    pk[slot] = v[q];
-                    pi[slot] = si[i];
-                }
-            }
-        }
-        __syncthreads();
-        if (s_cnt <= PRUNE_CAP) {
-            rk = pk;
-            ri = pi;
-            R = s_cnt;
-        }
+        ranked = prune_and_rank<T>(&s_cnt, pk, pi, M, [&](int q) { return have[q] && bin[q] <= bsel; }, [&](int q, T& key, int& idx) {
+            key = v[q];
+            idx = si[threadIdx.x + q * 1024];
+        }, emit, [] {}) <= PRUNE_CAP;
         __syncthreads();   // everybody has read s_cnt before it is reused
     }
-    if (R > PRUNE_CAP && M < C) {
+    if (pruned && !ranked) {
         // the linear bins did not separate the keys (mass ties, outliers): exact radix select
         if (threadIdx.x == 0) s_cnt = 0;
         U v[4];
@@ -1292,34 +1298,20 @@ __device__ __forceinline__ void select_candidates(const T* ckey, const int* cidx
             v[q] = have[q] ? ord_bits(sk[i]) : (U)0;
         }
         const U kth = block_kth<U, ord_of<T>::passes>(v, have, M - 1, hist, &s_prefix, &s_rank);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if (have[q] && v[q] <= kth) {
-                const int slot = atomicAdd(&s_cnt, 1);
-                if (slot < PRUNE_CAP) {
-                    const int i = threadIdx.x + q * 1024;
-                    pk[slot] = sk[i];
-                    pi[slot] = si[i];
-                }
-            }
-        }
-        __syncthreads();
-        if (s_cnt <= PRUNE_CAP) {  // otherwise (mass ties at the threshold) rank the full set
-            rk = pk;
-            ri = pi;
-            R = s_cnt;
-        }
+        ranked = prune_and_rank<T>(&s_cnt, pk, pi, M, [&](int q) { return have[q] && v[q] <= kth; }, [&](int q, T& key, int& idx) {
+            const int i = threadIdx.x + q * 1024;
+            key = sk[i];
+            idx = si[i];
+        }, emit, [] {}) <= PRUNE_CAP;
     }
-    for (int t = threadIdx.x; t < R; t += blockDim.x) {
-        const T k = rk[t];
-        const int i = ri[t];
-        int rank = 0;
-        for (int s = 0; s < R; ++s) rank += lex_less<T>(rk[s], ri[s], k, i) ? 1 : 0;
-        if (rank < M) {
-            fk[rank] = k;
-            fi[rank] = i;
+    if (!ranked)   // no prune, or mass ties at the threshold: rank the full set
+        for (int t = threadIdx.x; t < C; t += blockDim.x) {
+            const T k = sk[t];
+            const int i = si[t];
+            int rank = 0;
+            for (int s = 0; s < C; ++s) rank += lex_less<T>(sk[s], si[s], k, i) ? 1 : 0;
+            if (rank < M) emit(rank, k, i);
         }
-    }
     __syncthreads();
 }
 
@@ -1797,61 +1789,22 @@ __device__ __forceinline__ void score_finish_body_at(FinishArgs a, double coef_s
         __syncthreads();
         AS_STAMP(25);
         if (threadIdx.x == 0) AS_STAMP_VAL(26, total);
-        if (threadIdx.x < 64) {   // wave 0: 16 bins per lane, inclusive scan over the lanes, the lane whose bins reach M finishes
-            unsigned int hh[16], tot = 0;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                hh[j] = khist[16 * threadIdx.x + j];
-                tot += hh[j];
-            }
-            unsigned int incl = tot;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const unsigned int t2 = __shfl_up(incl, o, 64);
-                if ((int)threadIdx.x >= o) incl += t2;
-            }
-            const unsigned int excl = incl - tot;
-            const unsigned int want_ = (unsigned)(a.M < total ? a.M : total);
-            if (threadIdx.x == 0) k_bin = 1023;
-            if (want_ > 0 && excl < want_ && incl >= want_) {
-                unsigned int run = excl;
-                int b = 16 * (int)threadIdx.x;
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    run += hh[j];
-                    if (run >= want_) break;
-                    b += 1;
-                }
-                k_bin = b;
-            }
+        if (threadIdx.x < 64) {
+            if (threadIdx.x == 0) k_bin = 1023;   // (nothing to rank: hist_kth_bin stores no bin)
+            hist_kth_bin(khist, (unsigned)(a.M < total ? a.M : total), (int)threadIdx.x, &k_bin);
         }
         __syncthreads();
         const int bsel = k_bin;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
+        const int R = prune_and_rank<T>(&k_cnt, pk, pi, a.M, [&](int u) { return mybin[u] >= 0 && mybin[u] <= bsel; }, [&](int u, T& key, int& idx) {
             const int t = (int)threadIdx.x + u * (int)blockDim.x;
-            if (mybin[u] >= 0 && mybin[u] <= bsel) {
-                const int slot = atomicAdd(&k_cnt, 1);
-                if (slot < PRUNE_CAP) {
-                    pk[slot] = sk[t];
-                    pi[slot] = si[t];
-                }
-            }
-        }
-        __syncthreads();
-        const int R = k_cnt;
+            key = sk[t];
+            idx = si[t];
+        }, [&](int rank, T k, int i) {
+            fk[rank] = k;
+            fi[rank] = i;
+        }, [] {});
         if (R <= PRUNE_CAP) {
             if (threadIdx.x == 0) fcount = total < a.M ? total : a.M;
-            for (int t = threadIdx.x; t < R; t += blockDim.x) {
-                const T k = pk[t];
-                const int i = pi[t];
-                int rank = 0;
-                for (int s2 = 0; s2 < R; ++s2) rank += lex_less<T>(pk[s2], pi[s2], k, i) ? 1 : 0;
-                if (rank < a.M) {
-                    fk[rank] = k;
-                    fi[rank] = i;
-                }
-            }
             __syncthreads();
         } else {   // the keys pile up in one bin (mass ties): the generic selection sorts it out
             select_candidates<T>(nullptr, nullptr, total, a.M, sk, si, pk, pi, fk, fi, &fcount);
@@ -2227,32 +2180,7 @@ __device__ __forceinline__ int xk_rank_entries(const XKnn* __restrict__ xk, int 
         for (int j = 0; j < J; ++j)
             if (active && tid + j * NT < P) atomicAdd(&L.hist[kbin_of(rk[j])], 1u);
         __syncthreads();
-        if (tid < 64) {   // 16 bins per lane, inclusive scan over the lanes, the lane whose bins reach k finishes
-            unsigned int hh[16], tot = 0;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                hh[j] = L.hist[16 * tid + j];
-                tot += hh[j];
-            }
-            unsigned int incl = tot;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const unsigned int t2 = __shfl_up(incl, o, 64);
-                if (tid >= o) incl += t2;
-            }
-            const unsigned int excl = incl - tot, want_ = (unsigned)want_k;
-            if (want_ > 0 && excl < want_ && incl >= want_) {
-                unsigned int run = excl;
-                int bsel = 16 * tid;
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    run += hh[j];
-                    if (run >= want_) break;
-                    bsel += 1;
-                }
-                L.kbin_nsel[0] = bsel;
-            }
-        }
+        if (tid < 64) hist_kth_bin(L.hist, (unsigned)want_k, tid, &L.kbin_nsel[0]);   // (the bin is preset: XRankLds)
         __syncthreads();
         const int kbin = L.kbin_nsel[0];
 #pragma unroll
@@ -2589,6 +2517,68 @@ __global__ __launch_bounds__(1024) void staged_x1_kernel(FinishArgs ak, FinishAr
     }
 }
 
+// HostOut::overflow of a block's flag bits (XHead::flags and what the final kernels add): bits 2 .. 5 -> bits 0 .. 3
+__device__ __forceinline__ int overflow_bits(int flags) {
+    return ((flags & 4) ? 1 : 0) | ((flags & 8) ? 2 : 0) | ((flags & 16) ? 4 : 0) | ((flags & 32) ? 8 : 0);
+}
+
+// A thread's share of one rank's candidates (entries start, start + stride, ... below cnt) into the cosine / lambda / id lists.
+// NPRE of them the caller has loaded already (c0 = cs[start], c1 = cs[start + stride]): loads that went out ahead of a barrier.
+template <int NPRE>
+__device__ __forceinline__ void pull_block(const XCand* __restrict__ cs, int cnt, int start, int stride, double* sc, double* sl, int* sid,
+                                           const XCand c0 = {}, const XCand c1 = {}) {
+    for (int t = start; t < cnt; t += stride) {
+        const XCand c = NPRE > 0 && t == start ? c0 : (NPRE > 1 && t == start + stride ? c1 : cs[t]);
+        sc[t] = c.cosv;
+        sl[t] = c.lam;
+        sid[t] = (int)c.idx;
+    }
+}
+
+// The scorer stage of the final kernels for one tau; every thread of the block.  Blends the `total` candidates (sc: cosines, sl:
+// lambdas, sid: ids -- all left as they are; the scores stay in registers), NaN -> -inf, 1024 fixed bins over [-1, 1] (a score
+// lies there), the bin of the nhit-th best score, prune, rank by (score desc, id asc), the nhit hits into out->idx / out->score.
+// On entry khist is zero and *k_cnt 0, behind a barrier; pk / pi hold PRUNE_CAP entries.  A prune that overflowed (mass ties in
+// one bin) calls over() in every thread and writes nothing.  No barrier behind the stores.  stamp: the "scored" stamp of the
+// diagnostic build.
+template <typename Over>
+__device__ __forceinline__ void final_rank_tau(double tau, int total, int nhit, double lq, const double* sc, const double* sl, const int* sid,
+                                               double* pk, int* pi, unsigned int* khist, int* k_bin, int* k_cnt, HostOut* out, bool stamp, Over over) {
+    const int tid = (int)threadIdx.x;
+    double sv[4];
+    int mybin[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int t = tid + u * (int)blockDim.x;
+        mybin[u] = -1;
+        sv[u] = 0.0;
+        if (t < total) {
+            double s = blend_score(tau, sc[t], lq, sl[t]);
+            s = s == s ? s : -key_traits<double>::inf();
+            sv[u] = s;
+            const double fb = (1.0 - s) * 512.0;   // descending scores = ascending bins
+            mybin[u] = fb < 0.0 ? 0 : (fb >= 1023.0 ? 1023 : (int)fb);
+            atomicAdd(&khist[mybin[u]], 1u);
+        }
+    }
+    __syncthreads();
+    if (stamp) AS_STAMP(40);
+    if (tid < 64) {
+        if (tid == 0) *k_bin = 1023;   // (nhit == 0: hist_kth_bin stores no bin)
+        hist_kth_bin(khist, (unsigned)nhit, tid, k_bin);
+    }
+    __syncthreads();
+    const int bsel = *k_bin;
+    // (a key is minus a score: the sign is flipped back where a hit is stored)
+    prune_and_rank<double>(k_cnt, pk, pi, nhit, [&](int u) { return mybin[u] >= 0 && mybin[u] <= bsel; }, [&](int u, double& key, int& idx) {
+        key = -sv[u];
+        idx = sid[tid + u * (int)blockDim.x];
+    }, [&](int rank, double k, int i) {
+        out->idx[rank] = i;
+        out->score[rank] = -k;
+    }, over);
+}
+
 // After the exchange, on every rank alike: lambda_q (wave 0) while the other waves pull the ranks' candidates into LDS; exact
 // scores; the topk by (score desc, id asc) through a fixed-range histogram prune (a score lies in [-1, 1]) and a rank count;
 // publication.  Clears the per-search state and the scan's histograms behind a clean search.
@@ -2597,10 +2587,10 @@ __global__ __launch_bounds__(1024) void staged_x1_final_kernel(const char* __res
                                                                int64_t ntotal, QInfo* info, HostOut* out, int64_t seq, unsigned int* sc_hist, XHead* own_head,
                                                                XKnn* xk, int64_t goff) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    double* sc = (double*)smem;                 // CAND_CAP cosines, then scores
+    double* sc = (double*)smem;                 // CAND_CAP exact cosines
     double* sl = sc + CAND_CAP;                 // lambdas
     int* sid = (int*)(sl + CAND_CAP);           // ids
-    double* pk = (double*)(sid + CAND_CAP);     // PRUNE_CAP pruned scores
+    double* pk = (double*)(sid + CAND_CAP);     // PRUNE_CAP pruned keys (minus the scores)
     int* pi = (int*)(pk + PRUNE_CAP);
     __shared__ unsigned int khist[1024];
     __shared__ int s_tot, s_flags, k_bin, k_cnt, s_status;
@@ -2660,13 +2650,7 @@ __global__ __launch_bounds__(1024) void staged_x1_final_kernel(const char* __res
                 if (fl) atomicOr(&s_flags, fl);
                 s_tot = cnt;
             }
-            if (cnt <= CAND_CAP)
-                for (int t = tid - NR; t < cnt; t += NR) {
-                    const XCand c = t == tid - NR ? c0 : (t == tid ? c1 : cs[t]);
-                    sc[t] = c.cosv;
-                    sl[t] = c.lam;
-                    sid[t] = (int)c.idx;
-                }
+            if (cnt <= CAND_CAP) pull_block<2>(cs, cnt, tid - NR, NR, sc, sl, sid, c0, c1);
         }
         XRankLds rl;
         rl.hist = rhist; rl.kminmax = s_kminmax; rl.kbin_nsel = s_kbin_nsel;
@@ -2719,13 +2703,7 @@ __global__ __launch_bounds__(1024) void staged_x1_final_kernel(const char* __res
                 base = atomicAdd(&s_tot, cnt);
             }
             base = __shfl(base, 0, 64);
-            if (base + cnt <= CAND_CAP)
-                for (int t = lane; t < cnt; t += 64) {
-                    const XCand c = cs[t];
-                    sc[base + t] = c.cosv;
-                    sl[base + t] = c.lam;
-                    sid[base + t] = (int)c.idx;
-                }
+            if (base + cnt <= CAND_CAP) pull_block<0>(cs, cnt, lane, 64, sc + base, sl + base, sid + base);
         }
     }
     __syncthreads();
@@ -2737,78 +2715,10 @@ __global__ __launch_bounds__(1024) void staged_x1_final_kernel(const char* __res
         total = 0;
     }
     const double lq = s_lq;   // (lambda_q and the status stay in LDS for the scores and the header)
-    int mybin[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const int t = (int)threadIdx.x + u * (int)blockDim.x;
-        mybin[u] = -1;
-        if (t < total) {
-            double s = blend_score(tau, sc[t], lq, sl[t]);
-            s = s == s ? s : -key_traits<double>::inf();
-            sc[t] = s;
-            const double fb = (1.0 - s) * 512.0;   // descending scores = ascending bins
-            mybin[u] = fb < 0.0 ? 0 : (fb >= 1023.0 ? 1023 : (int)fb);
-            atomicAdd(&khist[mybin[u]], 1u);
-        }
-    }
-    __syncthreads();
-    if (xk) AS_STAMP(40);
     const int64_t want64 = topk < ntotal ? topk : ntotal;
     const int nhit = (int)(total < want64 ? total : want64);
-    if (threadIdx.x < 64) {   // 16 bins per lane, inclusive scan over the lanes, the lane whose bins reach nhit finishes
-        unsigned int hh[16], tot = 0;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            hh[j] = khist[16 * threadIdx.x + j];
-            tot += hh[j];
-        }
-        unsigned int incl = tot;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned int t2 = __shfl_up(incl, o, 64);
-            if ((int)threadIdx.x >= o) incl += t2;
-        }
-        const unsigned int excl = incl - tot, want_ = (unsigned)nhit;
-        if (threadIdx.x == 0) k_bin = 1023;
-        if (want_ > 0 && excl < want_ && incl >= want_) {
-            unsigned int run = excl;
-            int bsel = 16 * (int)threadIdx.x;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                run += hh[j];
-                if (run >= want_) break;
-                bsel += 1;
-            }
-            k_bin = bsel;
-        }
-    }
-    __syncthreads();
-    const int bsel = k_bin;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const int t = (int)threadIdx.x + u * (int)blockDim.x;
-        if (mybin[u] >= 0 && mybin[u] <= bsel) {
-            const int slot = atomicAdd(&k_cnt, 1);
-            if (slot < PRUNE_CAP) {
-                pk[slot] = sc[t];
-                pi[slot] = sid[t];
-            }
-        }
-    }
-    __syncthreads();
-    const int R = k_cnt;
-    if (R > PRUNE_CAP) flags |= 16;   // mass ties in one bin: the two-exchange chain sorts them out
-    else
-        for (int t = threadIdx.x; t < R; t += blockDim.x) {
-            const double myk = -pk[t];
-            const int myi = pi[t];
-            int rank = 0;
-            for (int s2 = 0; s2 < R; ++s2) rank += lex_less<double>(-pk[s2], pi[s2], myk, myi) ? 1 : 0;
-            if (rank < nhit) {
-                out->idx[rank] = myi;
-                out->score[rank] = pk[t];
-            }
-        }
+    // (mass ties in one bin: the two-exchange chain sorts them out)
+    final_rank_tau(tau, total, nhit, lq, sc, sl, sid, pk, pi, khist, &k_bin, &k_cnt, out, xk != nullptr, [&] { flags |= 16; });
     // The header, a field per lane of the last wave, beside the hits and under the same wait (every thread holds the same flags:
     // s_flags behind a barrier, the scores' count); thread 0 publishes behind the barrier.
     {
@@ -2819,7 +2729,7 @@ __global__ __launch_bounds__(1024) void staged_x1_final_kernel(const char* __res
             case 2: out->status = s_status; break;
             case 3: out->knn_inexact = (flags & 1) ? 1 : 0; break;
             case 4: out->score_inexact = 0; break;
-            case 5: out->overflow = ((flags & 4) ? 1 : 0) | ((flags & 8) ? 2 : 0) | ((flags & 16) ? 4 : 0) | ((flags & 32) ? 8 : 0); break;
+            case 5: out->overflow = overflow_bits(flags); break;
             case 6: out->state_reset = clean; break;
             case 7:
                 if (own_head) {   // this rank's block starts the next pass empty (its count and flags are accumulated by atomics)
@@ -2895,7 +2805,7 @@ __global__ __launch_bounds__(1024) void hits_final_kernel(const as_hit_rec* __re
         out->score_inexact = (info->score_inexact || (fl & 2)) ? 1 : 0;
         // (bit 3: some rank could not finish its part of a staged search -- as_query_search_staged files the flag so that every
         // rank leaves the pass with the same error instead of waiting for a collective its peer never enters)
-        out->overflow = (info->overflow & 7) | ((fl & 4) ? 1 : 0) | ((fl & 8) ? 2 : 0) | ((fl & 16) ? 4 : 0) | ((fl & 32) ? 8 : 0);
+        out->overflow = (info->overflow & 7) | overflow_bits(fl);
         publish(out, seq);
     }
 }
@@ -3521,7 +3431,7 @@ static as_status query_begin(as_query* q, const double* query_host, int64_t src_
             q->hq[c] = v;
             q->hq32[c] = (float)v;
         }
-        q->h_nq = host_query_norm(query_host, d);
+        q->h_nq = host_sumsq(query_host, d);
         q->h_inq = q->h_nq > 0.0 ? 1.0 / sqrt(q->h_nq) : 0.0;
         q->i8_scan = host_query_digits(q, d) ? 1 : 0;
         if (!narrow && !q->i8_scan) host_path = false;
@@ -4674,7 +4584,7 @@ __global__ __launch_bounds__(1024) void sweep_final_kernel(const char* __restric
     double* sc = (double*)smem;                 // CAND_CAP exact cosines
     double* sl = sc + CAND_CAP;                 // lambdas
     int* sid = (int*)(sl + CAND_CAP);           // ids
-    double* pk = (double*)(sid + CAND_CAP);     // PRUNE_CAP pruned scores (of the tau at hand)
+    double* pk = (double*)(sid + CAND_CAP);     // PRUNE_CAP pruned keys (minus the scores of the tau at hand)
     int* pi = (int*)(pk + PRUNE_CAP);
     __shared__ unsigned int khist[1024];
     __shared__ int s_tot, s_flags, k_bin, k_cnt, s_lfl[TAU_GROUP];
@@ -4693,13 +4603,7 @@ __global__ __launch_bounds__(1024) void sweep_final_kernel(const char* __restric
             s_tot = cnt;
             s_flags = fl;
         }
-        if (cnt <= CAND_CAP)
-            for (int t = tid - 64; t < cnt; t += (int)blockDim.x - 64) {
-                const XCand c = cs[t];
-                sc[t] = c.cosv;
-                sl[t] = c.lam;
-                sid[t] = (int)c.idx;
-            }
+        if (cnt <= CAND_CAP) pull_block<0>(cs, cnt, tid - 64, (int)blockDim.x - 64, sc, sl, sid);
     }
     __syncthreads();
     reset_query_hist(sc_hist, tid, blockDim.x);
@@ -4714,81 +4618,13 @@ __global__ __launch_bounds__(1024) void sweep_final_kernel(const char* __restric
     for (int j = 0; j < st.nt; ++j) {
         const double tau = sweep_pick(st.tau, j);
         khist[tid] = 0u;
-        if (tid == 0) k_cnt = 0;
-        __syncthreads();
-        double sv[4];
-        int mybin[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int t = tid + u * (int)blockDim.x;
-            mybin[u] = -1;
-            sv[u] = 0.0;
-            if (t < total) {
-                double s = blend_score(tau, sc[t], lq, sl[t]);
-                s = s == s ? s : -key_traits<double>::inf();
-                sv[u] = s;
-                const double fb = (1.0 - s) * 512.0;   // descending scores = ascending bins
-                mybin[u] = fb < 0.0 ? 0 : (fb >= 1023.0 ? 1023 : (int)fb);
-                atomicAdd(&khist[mybin[u]], 1u);
-            }
+        if (tid == 0) {
+            k_cnt = 0;
+            s_lfl[j] = 0;
         }
         __syncthreads();
-        if (tid < 64) {   // 16 bins per lane, inclusive scan over the lanes, the lane whose bins reach nhit finishes
-            unsigned int hh[16], tot = 0;
-#pragma unroll
-            for (int b = 0; b < 16; ++b) {
-                hh[b] = khist[16 * tid + b];
-                tot += hh[b];
-            }
-            unsigned int incl = tot;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const unsigned int t2 = __shfl_up(incl, o, 64);
-                if (tid >= o) incl += t2;
-            }
-            const unsigned int excl = incl - tot, want_ = (unsigned)nhit;
-            if (tid == 0) k_bin = 1023;
-            if (want_ > 0 && excl < want_ && incl >= want_) {
-                unsigned int run = excl;
-                int bsel = 16 * tid;
-#pragma unroll
-                for (int b = 0; b < 16; ++b) {
-                    run += hh[b];
-                    if (run >= want_) break;
-                    bsel += 1;
-                }
-                k_bin = bsel;
-            }
-        }
-        __syncthreads();
-        const int bsel = k_bin;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int t = tid + u * (int)blockDim.x;
-            if (mybin[u] >= 0 && mybin[u] <= bsel) {
-                const int slot = atomicAdd(&k_cnt, 1);
-                if (slot < PRUNE_CAP) {
-                    pk[slot] = sv[u];
-                    pi[slot] = sid[t];
-                }
-            }
-        }
-        __syncthreads();
-        const int R = k_cnt;
-        if (tid == 0) s_lfl[j] = R > PRUNE_CAP ? 16 : 0;   // (mass ties in one bin: this tau goes to the single search)
-        if (R <= PRUNE_CAP) {
-            HostOut* out = outs + j;
-            for (int t = tid; t < R; t += blockDim.x) {
-                const double myk = -pk[t];
-                const int myi = pi[t];
-                int rank = 0;
-                for (int s2 = 0; s2 < R; ++s2) rank += lex_less<double>(-pk[s2], pi[s2], myk, myi) ? 1 : 0;
-                if (rank < nhit) {
-                    out->idx[rank] = myi;
-                    out->score[rank] = pk[t];
-                }
-            }
-        }
+        // (mass ties in one bin: this tau goes to the single search)
+        final_rank_tau(tau, total, nhit, lq, sc, sl, sid, pk, pi, khist, &k_bin, &k_cnt, outs + j, false, [&] { if (tid == 0) s_lfl[j] = 16; });
         __syncthreads();   // (khist, k_cnt and the pruned list are the next tau's)
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -4805,7 +4641,7 @@ __global__ __launch_bounds__(1024) void sweep_final_kernel(const char* __restric
             out->status = info->status;
             out->knn_inexact = (fl & 1) ? 1 : 0;
             out->score_inexact = 0;
-            out->overflow = ((fl & 4) ? 1 : 0) | ((fl & 8) ? 2 : 0) | ((fl & 16) ? 4 : 0) | ((fl & 32) ? 8 : 0);
+            out->overflow = overflow_bits(fl);
             out->state_reset = clean;
             out->pad_ = 0;
         }

@@ -480,25 +480,6 @@ struct SubsetSel {
     unsigned int krem;         // rank still to find among the entries that agree with them (1-based, from the top)
 };
 
-__device__ __forceinline__ unsigned long long sel_ord(double s) {
-    if (s != s) return 0ull;
-    if (s == 0.0) s = 0.0;
-    const unsigned long long b = (unsigned long long)__double_as_longlong(s);
-    return (b & 0x8000000000000000ull) ? ~b : (b | 0x8000000000000000ull);
-}
-// digit p (0 = most significant) of the key hi:lo
-__device__ __forceinline__ unsigned int sel_digit(unsigned long long hi, unsigned int lo, int p) {
-    if (p <= 4) return (unsigned int)(hi >> (52 - 12 * p)) & 0xfffu;
-    if (p == 5) return ((unsigned int)(hi & 0xfull) << 8) | (lo >> 24);
-    return p == 6 ? (lo >> 12) & 0xfffu : lo & 0xfffu;
-}
-// the key agrees with T in its first p digits
-__device__ __forceinline__ bool sel_match(unsigned long long hi, unsigned int lo, const SubsetSel& st, int p) {
-    const int nb = 12 * p;
-    const unsigned long long mh = nb >= 64 ? ~0ull : (nb == 0 ? 0ull : ~0ull << (64 - nb));
-    const unsigned int ml = nb <= 64 ? 0u : ~0u << (96 - nb);
-    return ((hi ^ st.t_hi) & mh) == 0ull && ((lo ^ st.t_lo) & ml) == 0u;
-}
 // T after pass p from T after pass p - 1 and pass p's finished histogram: by all 256 threads of a block
 __device__ __forceinline__ SubsetSel sel_advance(SubsetSel st, const unsigned int* __restrict__ hist, int p) {
     __shared__ unsigned int wtot[4], r_dg, r_krem;
@@ -570,7 +551,7 @@ __device__ __forceinline__ void sel_hist_body(const double* __restrict__ scores,
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
         const unsigned long long hi = sel_ord(scores[i]);
         const unsigned int lo = ~(unsigned int)i;
-        if (sel_match(hi, lo, st, p)) atomicAdd(&lh[sel_digit(hi, lo, p)], 1u);
+        if (sel_match(hi, lo, st.t_hi, st.t_lo, p)) atomicAdd(&lh[sel_digit(hi, lo, p)], 1u);
     }
     __syncthreads();
     unsigned int* gh = hist + (int64_t)p * SEL_BINS;
@@ -655,22 +636,6 @@ __global__ __launch_bounds__(1024) void subset_sort_batch_kernel(const double* _
 }
 
 // ------------------------------------------------------------------ host side
-// |q|^2 as the search forms it (as_search.hip: q_prepare_kernel on the device, host_query_norm on the host -- 256 partial sums,
-// element c in partial c % 256, products and sums rounded separately, then a pairwise tree): the same bits, so the cosines of
-// the two routes share their denominator.  A third statement of that order (q_prepare_kernel points back here): whoever
-// changes it there changes it here.  A drift would cost a last bit of the cosine, inside the 1e-12 the tests hold the two routes to.
-static double subset_query_norm(const double* q, int64_t d) {
-    double p[256];
-    for (int t = 0; t < 256; ++t) p[t] = 0.0;
-    for (int64_t c = 0; c < d; ++c) {
-        volatile double sq = q[c] * q[c];
-        p[c & 255] = p[c & 255] + sq;
-    }
-    for (int o = 128; o > 0; o >>= 1)
-        for (int t = 0; t < o; ++t) p[t] += p[t + o];
-    return p[0];
-}
-
 static void subset_batch_release(SubsetWork* w) {
     (void)hipFree(w->bqd);
     (void)hipFree(w->bscores);
@@ -774,7 +739,7 @@ as_status subset_score(const as_space* sp, SubsetWork* w, int64_t m, const doubl
     AS_HIP(hipMemcpyAsync(w->q64, w->hq, sizeof(double) * w->dp, hipMemcpyHostToDevice, w->stream));
     SubsetArgs a;
     a.ids = w->ids; a.m = m; a.x32 = sp->x32; a.x64 = sp->x64; a.n64 = sp->n64; a.lam64 = sp->lam64; a.q64 = w->q64;
-    a.scores = w->scores; a.d = sp->d; a.dp = sp->dp; a.nq = subset_query_norm(query, sp->d); a.lq = lambda_q; a.tau = tau;
+    a.scores = w->scores; a.d = sp->d; a.dp = sp->dp; a.nq = host_sumsq(query, sp->d); a.lq = lambda_q; a.tau = tau;
     const int64_t groups = (m + SUB_ROWS - 1) / SUB_ROWS;   // one per wave and trip
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((groups + 3) / 4, (int64_t)w->cus * SUB_BLOCKS_PER_CU));
     const bool qlds = sp->dp <= SUB_Q_LDS;
@@ -911,7 +876,7 @@ as_status subset_batch_run(const as_space* sp, SubsetWork* w, int64_t m, const d
                 const double* q = queries + (i0 + t) * d;
                 for (int64_t c = 0; c < d; ++c) row[c] = q[c];
                 for (int64_t c = d; c < dp; ++c) row[c] = 0.0;
-                hn[t] = subset_query_norm(q, d);
+                hn[t] = host_sumsq(q, d);
                 hl[t] = lq[i0 + t];
             } else {
                 for (int64_t c = 0; c < dp; ++c) row[c] = 0.0;
@@ -1094,7 +1059,7 @@ as_status subset_sweep_run(const as_space* sp, SubsetWork* w, int64_t m, const d
     AS_HIP(hipMemcpyAsync(w->q64, w->hq, sizeof(double) * w->dp, hipMemcpyHostToDevice, w->stream));
     SubsetTausArgs a;
     a.s.ids = w->ids; a.s.m = m; a.s.x32 = sp->x32; a.s.x64 = sp->x64; a.s.n64 = sp->n64; a.s.lam64 = sp->lam64; a.s.q64 = w->q64;
-    a.s.scores = w->sw_scores; a.s.d = sp->d; a.s.dp = sp->dp; a.s.nq = subset_query_norm(query, sp->d); a.s.lq = lambda_q; a.s.tau = 0.0;
+    a.s.scores = w->sw_scores; a.s.d = sp->d; a.s.dp = sp->dp; a.s.nq = host_sumsq(query, sp->d); a.s.lq = lambda_q; a.s.tau = 0.0;
     a.ld = m;
     const int64_t groups = (m + SUB_ROWS - 1) / SUB_ROWS;   // (the grid of subset_score)
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((groups + 3) / 4, (int64_t)w->cus * SUB_BLOCKS_PER_CU));
@@ -1159,7 +1124,7 @@ as_status subset_batch_sweep_run(const as_space* sp, SubsetWork* w, int64_t m, c
                 const double* q = queries + (i0 + t) * d;
                 for (int64_t c = 0; c < d; ++c) qrow[c] = q[c];
                 for (int64_t c = d; c < dp; ++c) qrow[c] = 0.0;
-                hn[t] = subset_query_norm(q, d);
+                hn[t] = host_sumsq(q, d);
                 hl[t] = lq[i0 + t];
             } else {
                 for (int64_t c = 0; c < dp; ++c) qrow[c] = 0.0;

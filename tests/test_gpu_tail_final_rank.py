@@ -16,7 +16,13 @@ kmax == kmin), k = 1 with topk = 1, k = 120, both metrics, tau 0.4 / 0.62 / 1, 4
 buffer holds: the overflow chain answers), a sequence of searches on one workspace with a zero-lambda query in between, and
 the two callers of the last-block form (a tau sweep, the coarse chain at tau = 0.2).  topk = 500 -- more hits than the
 query's group and halo hold -- is not served by the fused tail on this index (the cosine window would have to take in the
-background: the scan's scorer candidates overflow and the threshold chain answers); the case checks the answer only."""
+background: the scan's scorer candidates overflow and the threshold chain answers); the case checks the answer only.
+2 500 copies of one row with the query on it ("dups2500": they and the halo fit the candidate buffers, and every score falls
+into one bin of the final kernels' histogram -- more entries than their pruned list, PRUNE_CAP = 2 048, holds, so the tail hands
+the query on) in a single search and in a tau sweep: the cases check the answers, not the path.  (Where they were first run,
+the search counter that moved was rerun_score_check -- 2 500 equal scores cannot be proven at the cut -- and neither
+rerun_overflow nor rerun_knn_check; the sweep redid its three taus, shared_passes stayed 0.  The library's debug lines showed
+the final kernel's overflow bit with 2 500 candidates written and nothing else that did not fit.)"""
 import functools
 import os
 
@@ -35,12 +41,16 @@ CAND_CAP = 4096  # the scan's candidate buffer (as_query.hpp)
 COARSE_COEF_MAX = 4e-2   # the largest error coefficient the coarse scan accepts (query_begin)
 
 # group name -> rows of its core; "pairs": 15 rows, each twice; "dups" / "dups100": one row 40 / 100 times (ranked as they are /
-# through the selection, whose histogram then has one bin)
-GROUPS = {"none": 0, "lt_k": 7, "eq_k": 10, "k_plus_1": 11, "mid": 300, "dense": 1300, "pairs": 30, "dups": 40, "crowd": 4500, "dups100": 100}
+# through the selection, whose histogram then has one bin); "dups2500": one row 2 500 times (more than the pruned list of the final
+# kernels holds; last, so that the rows of the groups before it are what they were without it)
+GROUPS = {"none": 0, "lt_k": 7, "eq_k": 10, "k_plus_1": 11, "mid": 300, "dense": 1300, "pairs": 30, "dups": 40, "crowd": 4500, "dups100": 100,
+          "dups2500": 2500}
+PRUNE_CAP = 2048   # the pruned list of the final kernels (as_search.hip)
 # index name -> (metric, k, topk)
-# (the "crowd" searches leave their workspace's path hints set -- the next 63 searches skip the prefilter --: indexes of their own)
+# (the "crowd" and "dups2500" searches leave their workspace's path hints set -- the next 63 searches skip the prefilter --:
+# indexes of their own)
 INDEXES = {"l2": ("l2", 10, 8), "cosine": ("cosine", 10, 8), "l2_k1": ("l2", 1, 1), "l2_k120": ("l2", 120, 15), "l2_topk500": ("l2", 10, 500),
-           "l2_crowd": ("l2", 10, 8), "cosine_crowd": ("cosine", 10, 8)}
+           "l2_crowd": ("l2", 10, 8), "cosine_crowd": ("cosine", 10, 8), "l2_dups2500": ("l2", 10, 8), "cosine_dups2500": ("cosine", 10, 8)}
 # (index, group the query sits on, tau, served by the fused tail without a rerun)
 CASES = [("l2", "none", 0.62, True), ("l2", "lt_k", 0.62, True), ("l2", "eq_k", 0.62, True), ("l2", "k_plus_1", 0.62, True),
          ("l2", "mid", 0.62, True), ("l2", "dense", 0.62, True), ("l2", "pairs", 0.62, True), ("l2", "dups", 0.62, True),
@@ -50,7 +60,8 @@ CASES = [("l2", "none", 0.62, True), ("l2", "lt_k", 0.62, True), ("l2", "eq_k", 
          ("l2_k1", "dense", 0.62, True), ("l2_k1", "pairs", 0.62, True), ("l2_k1", "dups", 0.62, True),
          ("l2_k120", "k_plus_1", 0.62, True), ("l2_k120", "mid", 0.62, True), ("l2_k120", "dense", 0.62, True),
          ("l2_topk500", "lt_k", 0.62, False), ("l2_topk500", "dense", 0.62, False),
-         ("l2_crowd", "crowd", 0.62, False), ("cosine_crowd", "crowd", 0.62, False)]
+         ("l2_crowd", "crowd", 0.62, False), ("cosine_crowd", "crowd", 0.62, False),
+         ("l2_dups2500", "dups2500", 0.62, False), ("cosine_dups2500", "dups2500", 0.62, False)]
 ZERO_GROUP = "none"   # the one query per index with no row inside eps
 
 
@@ -159,6 +170,7 @@ def test_final_kernel_ranking_matches_oracle_and_last_block_form(oracle_lib, ind
         assert group != ZERO_GROUP
         assert_hits_match(new, want, ref.scores(q, tau, lq), rtol=RTOL)
         assert abs(lq_new - lq) <= RTOL * abs(lq)
+        assert all(a[0] < b[0] for a, b in zip(new, new[1:]) if a[1] == b[1])   # ids ascending among equal scores
     if fused:
         assert op_new == op_old == "int8-high"
         assert c1["searches_with_rerun"] == c0["searches_with_rerun"], (c0, c1)
@@ -205,3 +217,26 @@ def test_last_block_callers_are_unchanged(oracle_lib, index):
         for t, hits in zip(taus + [0.2], got[1][0] + [got[1][1]]):
             want, lq = ref.search(q, t)
             assert_hits_match(hits, want, ref.scores(q, t, lq), rtol=RTOL)
+
+
+@pytest.mark.parametrize("index", ["l2_dups2500", "cosine_dups2500"])
+def test_mass_tie_in_a_tau_sweep(oracle_lib, index):
+    """The "dups2500" query under three taus at once, as the first call on an index of its own (no path hints yet: the shared
+    pass runs): each list is search()'s for that tau (test_gpu_tau_sweep's rule: the same ids in the same order except where
+    scores tie to 1e-12) and the oracle's."""
+    import pyarrowspace_amd as asp
+    from test_gpu_tau_sweep import same_as_single
+    ref = _index(index, oracle_lib)[2]
+    aspace, gl = asp.ArrowSpaceBuilder.build(graph_params(index), make_data()[0])
+    q = query_of("dups2500")
+    taus = [1.0, 0.62, 0.4]
+    c0, s0 = aspace.search_counters(), aspace.sweep_counters()
+    got = aspace.search_taus(q, gl, taus)
+    c1, s1 = aspace.search_counters(), aspace.sweep_counters()
+    print(f"{index} dups2500 sweep: counters {c0} -> {c1}, sweep {s0} -> {s1}")
+    assert len(got) == len(taus)
+    for tau, hits in zip(taus, got):
+        same_as_single(hits, aspace.search(q, gl, tau))
+        want, lq = ref.search(q, tau)
+        assert_hits_match(hits, want, ref.scores(q, tau, lq), rtol=RTOL)
+        assert all(a[0] < b[0] for a, b in zip(hits, hits[1:]) if a[1] == b[1])

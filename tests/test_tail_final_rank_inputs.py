@@ -2,7 +2,8 @@
 (oracle_np.pair_quantities, fp64): the number P of rows inside eps of every query; the rows inside the ball widened by the largest
 error coefficient the coarse scan accepts (4e-2: what its prefilter may append to the candidate buffer) fit the buffer for the
 cases that must not overflow, and the ball itself holds more than the buffer for the one that must; exactly one designated
-query has P = 0; the tie cases tie exactly."""
+query has P = 0; the tie cases tie exactly; the mass tie ("dups2500") holds more rows than the final kernels' pruned list and,
+with everything the prefilter may add, fewer than the candidate buffer."""
 import numpy as np
 import pytest
 
@@ -58,11 +59,19 @@ def test_rows_inside_eps_are_the_cores(index):
 @pytest.mark.parametrize("index", ["l2", "cosine"])
 def test_tie_cases_tie(index):
     spans = tf.make_data()[2]
-    for g in ("dups", "dups100"):
+    for g in ("dups", "dups100", "dups2500"):
         key, epskey, _ = _keys(index, g)
         lo, m = spans[g]
         assert len(np.unique(key[lo:lo + m])) == 1                  # every key equal: kmax == kmin
     assert tf.GROUPS["dups"] <= 64 < tf.GROUPS["dups100"]           # (on either side of what is ranked without the selection)
+    # the mass tie: 2 500 rows inside eps, all on the query (cosine 1: every score in one bin), more than the pruned list holds,
+    # and with the halo and whatever the coarse prefilter may add fewer than the candidate buffer
+    key, epskey, slack = _keys(index, "dups2500")
+    lo, m = spans["dups2500"]
+    X = tf.make_data()[0]
+    assert m == tf.GROUPS["dups2500"] == 2500 > tf.PRUNE_CAP and int((key <= epskey).sum()) == 2500
+    assert (X[lo:lo + m] == tf.query_of("dups2500")[None, :]).all()
+    assert int((key <= epskey + slack).sum()) < tf.CAND_CAP and m + tf.HALO < tf.CAND_CAP
     key, epskey, _ = _keys(index, "pairs")
     lo, m = spans["pairs"]
     kk = key[lo:lo + m]
@@ -80,6 +89,10 @@ def test_cases_cover_what_the_issue_lists():
     assert {"none", "mid", "dense", "pairs", "dups", "dups100"} <= by_index["cosine"]
     assert by_index["l2_crowd"] == by_index["cosine_crowd"] == {"crowd"}
     assert tf.INDEXES["l2_crowd"] == tf.INDEXES["l2"] and tf.INDEXES["cosine_crowd"] == tf.INDEXES["cosine"]
+    assert by_index["l2_dups2500"] == by_index["cosine_dups2500"] == {"dups2500"}
+    assert tf.INDEXES["l2_dups2500"] == tf.INDEXES["l2"] and tf.INDEXES["cosine_dups2500"] == tf.INDEXES["cosine"]
+    assert list(tf.GROUPS)[-1] == "dups2500"      # appended: the generator draws in order, the groups before it keep their rows
+    assert ("l2_dups2500", "dups2500", 0.62, False) in tf.CASES and ("cosine_dups2500", "dups2500", 0.62, False) in tf.CASES
     assert tf.INDEXES["l2_k1"][1:] == (1, 1) and tf.INDEXES["l2_k120"][1] == 120
     assert tf.INDEXES["l2_topk500"][2] > tf.GROUPS["lt_k"] + tf.HALO      # more hits asked for than the query's own group holds
     assert sum(group == tf.ZERO_GROUP for index, group, tau, fused in tf.CASES if index == "l2") == 1
