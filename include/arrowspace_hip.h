@@ -270,6 +270,17 @@ int32_t as_space_knn_pipe(const as_space* sp);
  * floats, queries or items the image represents badly).  Either way the scan only prefilters: results are exact. */
 int32_t as_query_scan_int8(const as_query* q);
 int32_t as_last_scan_int8(const as_space* sp);
+/* Width in bits of the coarse operand that scan read: 4 when it took the NIBBLE tiles (the items quantised afresh to 16 levels per
+ * row, half the bytes of the high digits), 8 otherwise -- as_query_scan_int8 keeps answering 2 for the coarse scan at
+ * either width.  as_set_tuning("coarse_bits", v) / ARROWSPACE_COARSE_BITS: -1 the library decides (default), 8 never the nibble
+ * tiles, 4 the nibble tiles wherever rows of 512 columns and more allow them, at any row count. */
+int32_t as_query_scan_bits(const as_query* q);
+int32_t as_last_scan_bits(const as_space* sp);
+/* Debugging aid (tests of the nibble tiles).  as_debug_nibble_image makes the image if need be and reports info[0] = 1 when it is
+ * usable (0: a zero or non-finite row, rows outside 512 .. 4 096 columns, no memory), info[1] = R4 = max_i |x_i - x~_i| / |x_i|,
+ * info[2] = 32-column chunks per row, info[3] = rows of the image; tiles (may be null; info[3] * info[2] * 16 bytes,
+ * [tile][chunk][64 rows][16 bytes]) and fa4 (may be null; nrows level steps) are copied to the host. */
+as_status as_debug_nibble_image(const as_space* sp, void* tiles, int64_t tiles_bytes, float* fa4, int64_t nrows, double* info);
 /* 1 when the last batched pass of as_search_batch (its first workspace) ran on the int8 images of items and queries
  * (v_mfma_i32_32x32x32_i8, three products per column) rather than on the bf16 head + tail of the fp32 items. */
 int32_t as_last_batch_int8(const as_space* sp);
@@ -458,6 +469,7 @@ void as_enable_search_stats(int32_t enabled);
 /* Measurement knob, no reference counterpart: launch parameters the library otherwise picks itself.  "tile_geom" = <blocks per
  * CU><two digits: ring KiB per wave> of the single query's tile scan (e.g. 406, 308, 216; ARROWSPACE_TILE_GEOM at load);
  * "x1_blocks" = blocks of the coarse scan's exact-evaluation kernel (16 .. 256, default 128).
+ * "coarse_bits" = -1 / 8 / 4: width of the single query's coarse operand (as_query_scan_bits).
  * "x1_final_rank" = 1 / 0: the fused tail's final kernel / its first kernel's last block ranks the rows inside eps, for every
  * workspace; any other value: each workspace's own switch again (ARROWSPACE_X1_FINAL_RANK when it was made; default 1).
  * "subset_batch_mib" = MiB of scores one chunk of queries of the batched filtered forms may hold (default 256; <= 0: the default);
@@ -468,7 +480,8 @@ int32_t as_set_tuning(const char* key, int32_t value);
 as_status as_last_search_stats(const as_space* sp, double* out, int32_t n);
 /* single-query searches on this space since it was made: out[0] searches, [1] zero-lambda results (src/lib.rs:156-159),
  * [2] reruns after a failed k-NN a-posteriori check, [3] after a candidate-buffer overflow, [4] after a failed scorer
- * check, [5] searches that took at least one rerun.  A rerun costs a second pass over the items. */
+ * check, [5] searches that took at least one rerun.  A rerun costs a second pass over the items.  [6] scans that read the nibble
+ * tiles, [7] those of them whose search was redone on the 8-bit tiles (not counted in [2] .. [5]). */
 as_status as_search_counters(const as_space* sp, int64_t* out, int32_t n);
 /* Extension: one query under ntau taus (a tau sweep) -- list j, at out_idx / out_score + j * topk' (topk' = min(topk, nitems)),
  * out_len[j] entries, is what as_search returns for taus[j].  lambda_q (one value, tau-independent) -> out_lambda_q; lambda_q == 0

@@ -752,11 +752,13 @@ class ArrowSpace:
     def search_counters(self) -> dict:
         """Extension: what the single-query searches on this space cost so far -- reruns (a second pass over the items) by
         cause, zero-lambda results."""
-        out = np.zeros(6, dtype=np.int64)
-        st = _L.as_search_counters(self._h, out.ctypes.data_as(C.c_void_p), 6)
+        out = np.zeros(8, dtype=np.int64)
+        st = _L.as_search_counters(self._h, out.ctypes.data_as(C.c_void_p), 8)
         if st:
             _raise(st)
-        keys = ("searches", "zero_lambda", "rerun_knn_check", "rerun_overflow", "rerun_score_check", "searches_with_rerun")
+        # (nibble_scans: scans that read the 4-bit tiles; nibble_reruns: those whose search was redone on the 8-bit tiles)
+        keys = ("searches", "zero_lambda", "rerun_knn_check", "rerun_overflow", "rerun_score_check", "searches_with_rerun",
+                "nibble_scans", "nibble_reruns")
         return dict(zip(keys, (int(v) for v in out)))
 
     @property
@@ -775,6 +777,41 @@ class ArrowSpace:
         """Extension: what the last single-query scan read -- "fp32" items, their "int8" two-digit image, or "int8-high" (the
         image's high digits alone: the coarse scan, every candidate re-evaluated exactly)."""
         return {0: "fp32", 1: "int8", 2: "int8-high"}.get(int(_L.as_last_scan_int8(self._h)), "fp32")
+
+    @property
+    def last_scan_bits(self) -> int:
+        """Extension: width of the coarse operand the last single-query scan read -- 4 for the nibble tiles, 8 otherwise
+        (`last_scan_operand` answers "int8-high" for the coarse scan at either width)."""
+        return int(_L.as_last_scan_bits(self._h))
+
+    def debug_nibble_image(self):
+        """Debugging aid: the nibble tiles as they lie in device memory -- None when the items have no usable image, else a dict
+        with `tiles` (uint8 [tile][chunk][64 rows][16 bytes]), `fa4` (the rows' level steps), `r4max` and `chunks`."""
+        info = np.zeros(4, dtype=np.float64)
+        st = _L.as_debug_nibble_image(self._h, None, 0, None, 0, info.ctypes.data_as(C.c_void_p))
+        if st:
+            _raise(st)
+        if info[0] == 0.0:
+            return None
+        chunks, rows = int(info[2]), int(info[3])
+        tiles = np.zeros((rows // 64, chunks, 64, 16), dtype=np.uint8)
+        fa4 = np.zeros(rows, dtype=np.float32)
+        st = _L.as_debug_nibble_image(self._h, tiles.ctypes.data_as(C.c_void_p), tiles.nbytes, fa4.ctypes.data_as(C.c_void_p), rows,
+                                      info.ctypes.data_as(C.c_void_p))
+        if st:
+            _raise(st)
+        return {"tiles": tiles, "fa4": fa4, "r4max": float(info[1]), "chunks": chunks}
+
+    def debug_last_dots(self):
+        """Debugging aid: the dots the last single-query scan kept (fp32, one per item) and the error coefficient they carry:
+        |dot - x.q| <= coef |x||q|."""
+        n = int(_L.as_nitems(self._h))
+        dots = np.zeros(n, dtype=np.float32)
+        coef = C.c_double(0.0)
+        st = _L.as_debug_last_dots(self._h, dots.ctypes.data_as(C.c_void_p), n, C.byref(coef))
+        if st:
+            _raise(st)
+        return dots, float(coef.value)
 
     @property
     def last_batch_int8(self) -> bool:

@@ -156,7 +156,7 @@ void as_free_space(as_space* sp) {
     subset_work_free(sp->score_ws);
     lists_work_free(sp->lists_ws);
     if (sp->stream) hipStreamSynchronize(sp->stream);
-    hipFree(sp->x32); hipFree(sp->xs); hipFree(sp->x8); hipFree(sp->x8h); hipFree(sp->fa8); hipFree(sp->x64); hipFree(sp->n64); hipFree(sp->n32); hipFree(sp->inorm32);
+    hipFree(sp->x32); hipFree(sp->xs); hipFree(sp->x8); hipFree(sp->x8h); hipFree(sp->x4); hipFree(sp->fa4); hipFree(sp->fa8); hipFree(sp->x64); hipFree(sp->n64); hipFree(sp->n32); hipFree(sp->inorm32);
     hipFree(sp->lam64); hipFree(sp->lam32);
     if (sp->stream) hipStreamDestroy(sp->stream);
     delete sp;
@@ -772,6 +772,40 @@ static as_status graph_matches(const as_space* sp, const as_graph* gr, const cha
 int32_t as_space_knn_pipe(const as_space* sp) { return sp ? sp->k2_last_pipe : -1; }
 int32_t as_last_scan_int8(const as_space* sp) { return sp && sp->qcache ? as_query_scan_int8(sp->qcache) : 0; }
 int64_t as_batch_dual_scans(const as_space* sp) { return sp ? (int64_t)sp->batch_dual_scans.load(std::memory_order_relaxed) : 0; }
+int32_t as_last_scan_bits(const as_space* sp) { return sp && sp->qcache ? as_query_scan_bits(sp->qcache) : 8; }
+
+// Debugging aids of the nibble tiles (tests): the image as it lies in HBM, and the dots the last single-query scan kept.
+as_status as_debug_nibble_image(const as_space* sp, void* tiles, int64_t tiles_bytes, float* fa4, int64_t nrows, double* info) {
+    if (!sp || !info) {
+        set_err("as_debug_nibble_image: null argument");
+        return AS_EINVAL;
+    }
+    AS_HIP(hipSetDevice(sp->device));
+    bool have = false;
+    AS_TRY(space_nib_image(sp, &have));
+    info[0] = have ? 1.0 : 0.0;
+    info[1] = have ? sp->r4max : 0.0;
+    info[2] = (double)(sp->dp8 / 32);
+    info[3] = (double)(sp->np + ROW_TILE);
+    if (!have) return AS_OK;
+    const int64_t all = (sp->np + ROW_TILE) * (sp->dp8 / 2);
+    if (tiles) {
+        if (tiles_bytes != all) {
+            set_err("as_debug_nibble_image: the tiles are %lld bytes", (long long)all);
+            return AS_EINVAL;
+        }
+        AS_HIP(hipMemcpy(tiles, sp->x4, (size_t)all, hipMemcpyDeviceToHost));
+    }
+    if (fa4) {
+        if (nrows < 0 || nrows > sp->np + ROW_TILE) {
+            set_err("as_debug_nibble_image: at most %lld rows", (long long)(sp->np + ROW_TILE));
+            return AS_EINVAL;
+        }
+        AS_HIP(hipMemcpy(fa4, sp->fa4, sizeof(float) * (size_t)nrows, hipMemcpyDeviceToHost));
+    }
+    return AS_OK;
+}
+
 int32_t as_last_batch_int8(const as_space* sp) { return sp && sp->qcache_b ? as_query_scan_int8(sp->qcache_b) : 0; }
 
 as_status as_gang_counters(const as_space* sp, int64_t* out, int32_t n) {
@@ -1949,6 +1983,7 @@ as_status as_search_counters(const as_space* sp, int64_t* out, int32_t n) {
     }
     std::lock_guard<std::mutex> lk(sp->qmu);
     for (int i = 0; i < n && i < 6; ++i) out[i] = sp->scount[i];
+    for (int i = 6; i < n && i < 8; ++i) out[i] = sp->nib_count[i - 6].load(std::memory_order_relaxed);
     return AS_OK;
 }
 

@@ -145,6 +145,170 @@ as_status space_i8h_image(const as_space* sp, bool* present) {
     return AS_OK;
 }
 
+// NIBBLE tiles: the single query's coarse scan at HALF the bytes again (as_scan.hip, scan_tile_kernel_dyn<.., NIB>).
+// The items are quantised AFRESH from fp32 -- the top nibble of a1 is too coarse (coefficient 0.21: thousands of candidates):
+// per row 16 levels lv in [-8, 7] of value (lv + 1/2) t, lv = clamp(floor(x / t), -8, 7), t = f max_c |x_c| / 7.5, with the clip
+// factor f the one of NIB_CLIPS that leaves the smallest residual |x - x~|_2 (the first of equals).  One wave per row, the row in
+// registers: lane l holds the 8 columns 512 s + 8 l .. + 7 of step s -- one dword of the row's 16 bytes in chunk 16 s + l / 4.
+// Columns beyond d hold level 0 (the query's digits are zero there and do not count in Sq: host_query_digits); padding rows are
+// all zero with scale 0.  maxima[0] = max_i |x_i - x~_i|_2 / |x_i| (float bits, rounded up), maxima[1] != 0: a zero or
+// non-finite row -- no image.
+template <int STEPS>
+__global__ __launch_bounds__(256) void quant_nib_kernel(const float* __restrict__ x32, const float* __restrict__ n32, unsigned int* __restrict__ x4,
+                                                        float* __restrict__ fa4, int64_t rows, int64_t n, int64_t d, int64_t dp, int C4,
+                                                        unsigned int* maxima) {
+    const int lane = lane_id();
+    const int64_t gw = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nw = (int64_t)gridDim.x * 4;
+    float wr = 0.0f;
+    bool bad = false;
+    for (int64_t row = gw; row < rows; row += nw) {
+        const bool real = row < n;
+        const float* x = x32 + row * dp;
+        float v[STEPS][8];
+        float m = 0.0f;
+#pragma unroll
+        for (int s = 0; s < STEPS; ++s)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int64_t c = (int64_t)s * 512 + lane * 8 + j;
+                v[s][j] = real && c < d ? x[c] : 0.0f;
+                const float a = fabsf(v[s][j]);
+                m = fmaxf(m, a);
+                bad = bad || !(a <= 3.0e38f);
+            }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+        const float nx2 = real ? n32[row] : 0.0f;
+        const bool ok = real && m > 0.0f && m <= 3.0e38f && nx2 > 0.0f && nx2 <= 3.0e38f;
+        if (real && !ok) bad = true;
+        float best = 3.4e38f, bt = 0.0f;
+        if (ok) {
+            constexpr float NIB_CLIPS[6] = {1.0f, 0.9f, 0.8f, 0.7f, 0.6f, 0.5f};
+#pragma unroll
+            for (int fi = 0; fi < 6; ++fi) {
+                const float t = __fdiv_rn(__fmul_rn(NIB_CLIPS[fi], m), 7.5f);
+                float res = 0.0f;
+#pragma unroll
+                for (int s = 0; s < STEPS; ++s)
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        const int64_t c = (int64_t)s * 512 + lane * 8 + j;
+                        const float lv = fminf(fmaxf(floorf(__fdiv_rn(v[s][j], t)), -8.0f), 7.0f);
+                        const float r = v[s][j] - (lv + 0.5f) * t;
+                        res += c < d ? r * r : 0.0f;
+                    }
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) res += __shfl_xor(res, o, 64);
+                if (res < best) {   // (wave-uniform: the butterfly leaves every lane the same sum)
+                    best = res;
+                    bt = t;
+                }
+            }
+            if (!(bt > 0.0f) || !(best < 3.4e38f)) {   // (a row whose scale underflows: no image)
+                bad = true;
+                bt = 0.0f;
+            }
+        }
+        const int64_t tile = row >> 6;
+#pragma unroll
+        for (int s = 0; s < STEPS; ++s) {
+            unsigned int wd = 0u;
+            if (bt > 0.0f) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const int64_t c = (int64_t)s * 512 + lane * 8 + j;
+                    const int lv = (int)fminf(fmaxf(floorf(__fdiv_rn(v[s][j], bt)), -8.0f), 7.0f);
+                    wd |= c < d ? ((unsigned int)lv & 15u) << (4 * j) : 0u;
+                }
+            }
+            const int chunk = s * 16 + (lane >> 2);
+            if (chunk < C4) x4[((tile * C4 + chunk) * 64 + (row & 63)) * 4 + (lane & 3)] = wd;
+        }
+        if (lane == 0) {
+            fa4[row] = bt;
+            if (bt > 0.0f) wr = fmaxf(wr, sqrtf(best) / sqrtf(nx2) * 1.001f);   // (fp32 sums of d squares: rounded up generously)
+        }
+    }
+    if (lane == 0 && wr > 0.0f) atomicMax(maxima, __float_as_uint(wr));   // non-negative floats order like their bit patterns
+    if (__any(bad) && lane == 0) atomicOr(maxima + 1, 1u);
+}
+
+// Lazy, behind sp->imu, like space_i8h_image: ready state 1 (x4, fa4, r4max published) or 2 (no memory, rows outside 512 .. 4 096
+// columns, a zero or non-finite row: the 8-bit tiles stay in use and nothing is tried again).
+as_status space_nib_image(const as_space* sp, bool* present) {
+    *present = false;
+    const int rdy = sp->x4_ready.load(std::memory_order_acquire);
+    if (rdy) {
+        *present = rdy == 1;
+        return AS_OK;
+    }
+    bool have = false;
+    AS_TRY(space_i8_image(sp, &have));   // (dp8 is the int8 image's)
+    std::lock_guard<std::mutex> lk(sp->imu);
+    if (sp->x4_ready.load(std::memory_order_relaxed)) {
+        *present = sp->x4_ready.load(std::memory_order_relaxed) == 1;
+        return AS_OK;
+    }
+    auto give_up = [&]() {
+        sp->x4_ready.store(2, std::memory_order_release);
+        return AS_OK;
+    };
+    if (!have || sp->dp8 < 512 || sp->dp8 > 4096 || sp->dp8 % 64) return give_up();
+    const int64_t rows_alloc = sp->np + ROW_TILE;
+    const int C4 = (int)(sp->dp8 / 32);
+    void* p = nullptr;
+    float* fa = nullptr;
+    if (hipMalloc(&p, (size_t)rows_alloc * (size_t)(sp->dp8 / 2)) != hipSuccess) {
+        (void)hipGetLastError();
+        return give_up();
+    }
+    if (hipMalloc(&fa, sizeof(float) * rows_alloc) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(p);
+        return give_up();
+    }
+    dev_tmp<unsigned int> mx;
+    as_status s = AS_OK;
+    if (mx.alloc(2) != hipSuccess || hipMemsetAsync(mx, 0, sizeof(unsigned int) * 2, sp->stream) != hipSuccess) s = AS_EHIP;
+    unsigned int h[2] = {0, 0};
+    if (s == AS_OK) {
+        const unsigned grid = (unsigned)std::min<int64_t>((rows_alloc + 3) / 4, 256 * 8);
+        const int steps = (int)((sp->dp8 + 511) / 512);
+#define AS_QNIB(S) hipLaunchKernelGGL(quant_nib_kernel<S>, dim3(grid), dim3(256), 0, sp->stream, (const float*)sp->x32, (const float*)sp->n32, (unsigned int*)p, fa, rows_alloc, sp->n, sp->d, sp->dp, C4, (unsigned int*)mx)
+        if (steps <= 1) AS_QNIB(1);
+        else if (steps <= 2) AS_QNIB(2);
+        else if (steps <= 4) AS_QNIB(4);
+        else AS_QNIB(8);
+#undef AS_QNIB
+        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(h, mx, sizeof(h), hipMemcpyDeviceToHost, sp->stream) != hipSuccess ||
+            hipStreamSynchronize(sp->stream) != hipSuccess)
+            s = AS_EHIP;
+    }
+    if (s != AS_OK) {
+        // (remembered like a failed allocation: the 8-bit tiles stay in use, and no later search retries 0.39 GB and a kernel under imu)
+        (void)hipFree(p);
+        (void)hipFree(fa);
+        set_err("quant_nib_kernel failed: %s", hipGetErrorString(hipGetLastError()));
+        sp->x4_ready.store(2, std::memory_order_release);
+        return s;
+    }
+    float R;
+    memcpy(&R, &h[0], 4);
+    if (h[1] || !(R > 0.0f) || !(R < 1.0f)) {
+        (void)hipFree(p);
+        (void)hipFree(fa);
+        dbg("space_nib_image: a zero or non-finite row (or a residual of %.3e): no nibble tiles", R);
+        return give_up();
+    }
+    sp->x4 = p;
+    sp->fa4 = fa;
+    sp->r4max = (double)R;
+    sp->x4_ready.store(1, std::memory_order_release);
+    dbg("space_nib_image: R4 = %.3e over %lld rows of %d chunks", R, (long long)sp->n, C4);
+    *present = true;
+    return AS_OK;
+}
+
 static as_status k2_items_i8(const as_space* sp, bool* usable) {
     *usable = false;
     if (!sp->x8 && !sp->x8_bad) {

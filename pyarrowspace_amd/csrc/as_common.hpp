@@ -74,6 +74,15 @@ struct as_space {
     // image state for readers that do not take imu: 0 nothing decided, 1 x8 / fa8 / coef8 published (or x8_bad set): read-only from now on
     mutable std::atomic<int> x8_ready{0};
     mutable std::atomic<int> x8h_ready{0};   // ... the planar high digits: 1 x8h published, 2 not available (no memory)
+    // NIBBLE tiles (as_build.hip, space_nib_image): the items quantised afresh to 4 bits, x ~ (lv + 1/2) t_i with lv in [-8, 7], one
+    // KiB per 64 consecutive rows and 32-column chunk ([tile][chunk][64 rows][16 bytes], dp8 / 32 chunks; column 2 j in the low
+    // nibble of byte j, column 2 j + 1 in the high one); fa4[i] = t_i; r4max = max_i |x_i - x~_i| / |x_i|, rounded up
+    mutable void* x4 = nullptr;
+    mutable float* fa4 = nullptr;
+    mutable double r4max = 0.0;
+    mutable std::atomic<int> x4_ready{0};    // 1 x4 / fa4 / r4max published, 2 not available (no memory, a failed build, a zero or non-finite row)
+    // as_search_counters [6], [7]: single-query scans that read the nibble tiles, and those of them that were redone on the 8-bit tiles
+    mutable std::atomic<int64_t> nib_count[2] = {};
     mutable std::mutex imu;           // makes the images (first use), per space
     mutable int k2_i8 = 0;
     mutable int k2_last_pipe = -1;   // matrix pipe of the last k-NN pass on this space: 0 fp32, 1 bf16 head + tail, 2 int8 two digits (as_space_knn_pipe)
@@ -123,7 +132,7 @@ struct as_space {
     mutable std::atomic<hipEvent_t> last_scan_ev{nullptr};
     mutable int64_t gang_scans[5] = {0, 0, 0, 0, 0};   // scans launched with 1 .. 4 members (index = members; under gmu)
     // host-prepared single-query scans that did NOT take the shared path, by first reason: [0] no concurrent callers lately, [1] the
-    // search is not one for the fused tail (tau < 0.4, crowded candidates lately, ...), [2] not a coarse scan, [3] per-search
+    // search is not one for the fused tail (tau < 0.4, crowded candidates lately, ...), [2] not a coarse scan of the 8-bit tiles (the two-digit image, or a search prepared for the nibble tiles), [3] per-search
     // state still to be reset on the workspace's stream, [4] per-launch timing on, [5] a row range
     mutable std::atomic<int64_t> gang_skip[6] = {};
     // as_search_counters: [0] searches, [1] zero-lambda results, [2] reruns because the k-NN a-posteriori check failed,
@@ -485,6 +494,7 @@ as_status ring_i8_set(as_space* sp, double u_max, double v_max, int32_t usable);
 // holds no non-finite item (whether its error is acceptable is the caller's call: build pass, scan)
 as_status space_i8_image(const as_space* sp, bool* present);
 as_status space_i8h_image(const as_space* sp, bool* present);
+as_status space_nib_image(const as_space* sp, bool* present);
 
 // build stages (as_build.hip)
 as_status ingest(as_space* sp, const void* items_dev, int dtype, int64_t ld);

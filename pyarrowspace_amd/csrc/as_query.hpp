@@ -202,6 +202,18 @@ struct as_query {
     int coarse = 0;                      // the last scan was the coarse one
     int coarse_off = 0;                  // > 0: counting the searches that skip it
     int coarse_never = 0;                // as_query_set_coarse(q, 0): this workspace's scans never take the coarse image
+    // ... on the NIBBLE tiles (space_nib_image: half the coarse operand's bytes again): the query's high digit q1 alone, per
+    // 32-column chunk 16 bytes of the even columns then 16 of the odd ones; Sq = sum of q1 over the d real columns (the levels'
+    // half-step offset: x~ . q~ = t s_q (sum lv q1 + Sq / 2)); faq4 = s_q 128 / 16256
+    int* hq4 = nullptr;                  // pinned
+    int* hq4_dev = nullptr;
+    double coef_i4 = 0.0;                // the nibble scan's coefficient for THIS query (host_query_digits)
+    double uv4 = 0.0;                    // ... its query part, (u_q + v_q) and the roundings: coef_i4 = 1.001 R4 + (1 + R4) uv4
+    int sq4 = 0;
+    float h_faq4 = 0.0f;
+    int nib_try = 0;                     // this search may read the nibble tiles (query_begin: hq4, uv4, sq4 are written for it)
+    int nib = 0;                         // the last scan read the nibble tiles
+    int nib_off = 0;                     // > 0: a nibble scan ended in a rerun lately (counts the searches that skip the tiles)
     int chainc_off = 0;                  // > 0: a COARSE CHAIN (ScanRequest::chainc) did not serve a recent query cleanly (counts the searches that skip it)
     int xknn_dirty = 0;                  // ... its counter may be non-zero (a pass died before its finish kernel)
     void* xknn = nullptr;                // [CAND_CAP] exact (id, key, distance, gy) of the coarse scan's k-NN candidates (staged_x1_kernel, xk)
@@ -309,6 +321,10 @@ struct PreArgs {
     const int* q8 = nullptr;
     float faq = 0.0f;
     const float* faqv = nullptr;   // batched pass on the int8 images: the slots' scales
+    // nibble tiles (scan_tile_kernel_dyn<.., NIB>): fa8 = the rows' level steps t_i, q8 = the query's q1 (even / odd columns),
+    // faq = s_q 128 / (16256 * 16), sq8 = 8 Sq
+    int nib = 0;
+    int sq8 = 0;
 };
 
 // What a caller asks of ONE scan (query_begin; make_pre and gang_launch read it): per-call mode travels here, never through the
@@ -324,6 +340,7 @@ struct ScanRequest {
     int gang_ok = 0;         // this scan may be shared with other callers' (gang_launch)
     int direct = 0;          // this query skips the prefilter and takes the threshold repair straight away (crowded neighbourhood)
     int no_coarse = 0;       // not the coarse scan for this call, whatever the switches say (the redo of a query it did not serve)
+    int allow_nib = 0;       // the coarse scan may read the nibble tiles (search_once's fused tail alone: a rerun there redoes the query on 8 bits)
     PreArgs* defer_pre = nullptr;   // set: query_begin stops in front of the scan's launch and leaves its arguments there (batch_launch_pair)
     int sc_ran = 0;          // OUT: the scan does collect the scorer's candidates (rows of 1025 .. 4096 floats: only when the int8 image serves it)
 };
@@ -339,6 +356,9 @@ as_status launch_scan_dual(as_query* a, as_query* b, const PreArgs& pa, const Pr
 as_status launch_scan_gang(as_query* const* m, const PreArgs* pre, int n, hipStream_t st);
 void set_tile_geom(int v);
 void set_tile_dyn(int v);
+void set_coarse_bits(int v);   // as_set_tuning("coarse_bits", -1 | 8 | 4)
+int coarse_bits();
+bool nib_scan_fits(const as_query* q, bool sc_enabled, int64_t rows, bool forced);
 void set_x1_blocks(int v);
 void set_x1_final_rank(int v);   // as_set_tuning("x1_final_rank", 0 | 1): over every workspace's own switch; any other value hands it back to them
 as_status set_scan_attrs();   // per-device dynamic-LDS opt-in of the scan kernels

@@ -1493,7 +1493,10 @@ __global__ __launch_bounds__(256) void scan_tile_kernel(const signed char* __res
 // 129.5 us instead of 132.5, the waves' ends 115.5 .. 126 (p10 .. p90) instead of 111 .. 128.  Chunks of 32 rows (half the lanes
 // of every DMA idle) 133.6 us, of 16 rows 193: the chunk stays 64 rows, a tile.  Half chunks for the waves' LAST tickets only (the
 // last 1/16 .. 1/4 of the rows): 134-136 us against 132-133 on the same box -- no gain, not kept.
-template <int NSLOT, bool SC>
+// NIB: the same ring over the NIBBLE tiles (as_build.hip, space_nib_image) -- a KiB is a 32-column chunk of 64 rows, C = dp8 / 32, the
+// query area again 32 bytes per KiB (q1 of the chunk's even columns, then of its odd ones).  Only the consume step and the scaling
+// differ: per dword two masks and a shift, two v_dot4_i32_i8 -- 20 VALU instructions per KiB, all exact in int32.
+template <int NSLOT, bool SC, bool NIB = false>
 __global__ __launch_bounds__(256) void scan_tile_kernel_dyn(const signed char* __restrict__ xt, int C, int64_t r0, int64_t r1, float* __restrict__ dots,
                                                             PreArgs pre, int crows, int ng) {
     constexpr int U = 2;
@@ -1656,7 +1659,18 @@ __global__ __launch_bounds__(256) void scan_tile_kernel_dyn(const signed char* _
             for (int e = 0; e < 4; ++e)
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
-                    if (u & 1) {
+                    if (NIB) {
+                        // a dword = 8 levels: the even columns' in the low nibbles, the odd columns' in the high ones; moved to the top of
+                        // their bytes they read 16 lv as int8 -- against q1 of the even (qa_) and of the odd (qb_) columns
+                        const int ev = (int)(((unsigned)xv[u][e] << 4) & 0xF0F0F0F0u), od = (int)((unsigned)xv[u][e] & 0xF0F0F0F0u);
+                        if (u & 1) {
+                            hi1 = __builtin_amdgcn_sdot4(ev, qa_[u][e], hi1, false);
+                            xs1 = __builtin_amdgcn_sdot4(od, qb_[u][e], xs1, false);
+                        } else {
+                            hi0 = __builtin_amdgcn_sdot4(ev, qa_[u][e], hi0, false);
+                            xs0 = __builtin_amdgcn_sdot4(od, qb_[u][e], xs0, false);
+                        }
+                    } else if (u & 1) {
                         hi1 = __builtin_amdgcn_sdot4(xv[u][e], qa_[u][e], hi1, false);
                         xs1 = __builtin_amdgcn_sdot4(xv[u][e], qb_[u][e], xs1, false);
                     } else {
@@ -1671,10 +1685,13 @@ __global__ __launch_bounds__(256) void scan_tile_kernel_dyn(const signed char* _
         const float aux = lds_read1(ax0 + lane * 4);
         // x_i . q = (128 HI + XS) fa_i fa_q: the integer is exact, its conversion the one rounding the row-ring kernel's fused
         // multiply-add makes
-        const long long tot = (long long)(hi0 + hi1) * 128 + (long long)(xs0 + xs1);
+        // (NIB: x~_i . q~ = t_i s_q 128 / 16256 (sum lv q1 + Sq / 2) -- the four sums hold 16 lv q1, pre.sq8 = 8 Sq, pre.faq carries the
+        // 1 / 16; |sum| <= 16256 d: exact in int32 for every row the DMA scans serve)
+        const long long tot = NIB ? (long long)(hi0 + hi1 + xs0 + xs1 + pre.sq8) : (long long)(hi0 + hi1) * 128 + (long long)(xs0 + xs1);
         const float mydot = (float)tot * (lds_read1(fx0 + lane * 4) * pre.faq);
         scan_chunk_end<SC, TILE_PEND>(pre, w, dots, t, 1 << 30, gw, lane, base, cnt, mydot, aux, hread, hx0, px0, nq32, inq32);
-        // (the ticket drawn at this chunk's start has retired: C >= 16 items were issued behind it and all but the ring's youngest waited for)
+        // (the ticket drawn at this chunk's start has retired: C >= 16 items were issued behind it and all but the ring's youngest waited
+        // for -- the nibble tiles' C is dp8 / 32: rows of 512 columns and more, launch_scan and nib_scan_fits hold C >= 16 for both)
         asm volatile("" : "+v"(tk));
         ccur = cnxt;
         cnxt = NW + (int64_t)__builtin_amdgcn_readfirstlane(tk) * ng + grp;
@@ -2111,6 +2128,13 @@ PreArgs make_pre(as_query* q, const ScanRequest& rq, double eps, int64_t exclude
         p.fa8 = sp->fa8;
         p.q8 = q->coarse ? q->hq8h_dev : q->hq8_dev;
         p.faq = q->h_faq;
+        if (q->coarse && q->nib) {   // the nibble tiles: the rows' level steps, q1 by even / odd columns, s_q 128 / 16256 / 16, 8 Sq
+            p.fa8 = sp->fa4;
+            p.q8 = q->hq4_dev;
+            p.faq = q->h_faq4;
+            p.nib = 1;
+            p.sq8 = 8 * q->sq4;
+        }
     }
     p.tile_ctrs = q->sc_hist;   // (the tile scan's chunk cursors live in the histogram copies' padding)
     if (q->host_q) {
@@ -2151,6 +2175,39 @@ void set_tile_geom(int v) { g_tile_geom.store(v, std::memory_order_relaxed); }
 static std::atomic<int> g_tile_dyn{getenv("ARROWSPACE_TILE_DYN") ? atoi(getenv("ARROWSPACE_TILE_DYN")) : 1};
 void set_tile_dyn(int v) { g_tile_dyn.store(v, std::memory_order_relaxed); }   // (0 static, 1 dynamic, 16 / 32: dynamic with chunks of that many rows)
 
+// width of the single query's coarse operand: -1 auto (the nibble tiles where query_begin's conditions hold), 8 never the nibble
+// tiles, 4 the nibble tiles at any row count on the dynamic schedule (tests reach the kernel at small shapes); ARROWSPACE_COARSE_BITS at
+// load, as_set_tuning("coarse_bits", v) later
+static int coarse_bits_arg(int v) { return v == 4 || v == 8 ? v : -1; }
+static std::atomic<int> g_coarse_bits{coarse_bits_arg(getenv("ARROWSPACE_COARSE_BITS") ? atoi(getenv("ARROWSPACE_COARSE_BITS")) : -1)};
+void set_coarse_bits(int v) { g_coarse_bits.store(coarse_bits_arg(v), std::memory_order_relaxed); }
+int coarse_bits() { return g_coarse_bits.load(std::memory_order_relaxed); }
+
+static int sc_rows_per_block() {   // (A/B: launch_scan)
+    static const int v = getenv("ARROWSPACE_SC_ROWS_PER_BLOCK") ? atoi(getenv("ARROWSPACE_SC_ROWS_PER_BLOCK")) : 128;
+    return v;
+}
+static void tile_schedule(const as_query* q, int64_t rows, int bpc, int64_t* nblk, int* rounds, int* tail_rows, int* crows);
+// blocks per CU and ring of the tile scans: as_set_tuning("tile_geom") = <blocks per CU><two digits: ring KiB per wave>
+static int tile_bpc() { return std::max(1, std::min((g_tile_geom.load(std::memory_order_relaxed) / 100) % 10, 4)); }
+// Does the dynamic schedule serve the coarse scan of `rows` rows with the nibble tiles' C = dp8 / 32?  C >= 16 (the ticket argument
+// of scan_tile_kernel_dyn), the ring of 8 KiB in steps of two, and -- unless forced -- the schedule switched on and three chunks
+// per wave and more of the launch tile_schedule plans: launch_scan's nibble branch launches exactly that plan.
+bool nib_scan_fits(const as_query* q, bool sc_enabled, int64_t rows, bool forced) {
+    const as_space* sp = q->sp;
+    const int C = (int)(sp->dp8 / 32);
+    const int tgeom = g_tile_geom.load(std::memory_order_relaxed);
+    const int tslots = tgeom % 100 >= 16 ? 16 : (tgeom % 100 >= 12 ? 12 : (tgeom % 100 >= 8 ? 8 : 6));
+    const int tstep = tgeom / 1000 == 4 && tslots >= 8 ? 4 : 2;
+    if (C < 16 || sp->dp8 % 64 || tslots != 8 || tstep != 2 || !q->sc_hist || rows <= 0 || !sc_enabled || (q->scan_variant & 4)) return false;
+    if (forced) return true;
+    if (!g_tile_dyn.load(std::memory_order_relaxed)) return false;
+    int64_t nblk;
+    int rounds, tail_rows, crows;
+    tile_schedule(q, rows, tile_bpc(), &nblk, &rounds, &tail_rows, &crows);
+    return rows >= nblk * 4 * crows * 3;
+}
+
 static constexpr size_t gang_lds(int nslot, int nq, int64_t chunks) {
     return 4 * ((size_t)nslot * 1024 + 512 + (size_t)nq * (256 + GANG_PEND * 8) + (size_t)nq * 512) + (size_t)nq * chunks * 32 + 32;
 }
@@ -2183,6 +2240,7 @@ as_status set_scan_attrs() {
     AS_ATTR((scan_tile_kernel<8, false>), tile_lds(8, false, 256));
     AS_ATTR((scan_tile_kernel_dyn<8, true>), tile_lds(8, true, 256));
     AS_ATTR((scan_tile_kernel_dyn<8, false>), tile_lds(8, false, 256));
+    AS_ATTR((scan_tile_kernel_dyn<8, true, true>), tile_lds(8, true, 256));
     AS_ATTR((scan_tile_gang_kernel<8, 2>), gang_lds(8, 2, 256));
     AS_ATTR((scan_tile_gang_kernel<8, 3>), gang_lds(8, 3, 256));
     AS_ATTR((scan_tile_gang_kernel<8, 4>), gang_lds(8, 4, 256));
@@ -2228,9 +2286,8 @@ as_status set_scan_attrs() {
 
 // chunk schedule of a tile scan over `rows` rows that collects the scorer's candidates (launch_scan's, for the coarse operand)
 static void tile_schedule(const as_query* q, int64_t rows, int bpc, int64_t* nblk, int* rounds, int* tail_rows, int* crows) {
-    static const int sc_rows_per_block = getenv("ARROWSPACE_SC_ROWS_PER_BLOCK") ? atoi(getenv("ARROWSPACE_SC_ROWS_PER_BLOCK")) : 128;
     const int64_t want = std::max<int64_t>(1, (rows + 63) / 64);
-    const int64_t want_sc = std::max<int64_t>(1, rows / std::max(sc_rows_per_block, 64));
+    const int64_t want_sc = std::max<int64_t>(1, rows / std::max(sc_rows_per_block(), 64));
     *nblk = std::min<int64_t>(std::min(want, want_sc), bpc * (int64_t)q->cus);
     const int64_t NW = *nblk * 4;
     auto chunks = [&](int c) { return rows / (NW * c) + (rows % (NW * c) ? 1 : 0); };
@@ -2249,6 +2306,11 @@ as_status launch_scan_gang(as_query* const* m, const PreArgs* pre, int n, hipStr
         set_err("launch_scan_gang: bad gang");
         return AS_EINVAL;
     }
+    for (int i = 0; i < n; ++i)
+        if (pre[i].nib || m[i]->nib) {   // (digits, scales and coefficient of the nibble tiles: not this kernel's operand)
+            set_err("launch_scan_gang: member %d was prepared for the nibble tiles", i);
+            return AS_EINVAL;
+        }
     int64_t nblk;
     int rounds, tail_rows, crows;
     tile_schedule(m[0], rows, 2, &nblk, &rounds, &tail_rows, &crows);
@@ -2511,8 +2573,7 @@ as_status launch_scan(as_query* q, const PreArgs& pre) {
             // (collecting the scorer's candidates: every wave needs a chunk in front of its last to publish from -- at least 32 rows
             // per wave, two chunks of 16; a 30 000-row index on 1 876 waves had 16 rows per wave, no bound, and every row a candidate)
             // (A/B: 256 rows per block instead of 128 -- 200k x 768 11 700 -> 9 000 queries/s, 100k x 768 13 700 -> 10 900, 65536 x 4096 unchanged)
-            static const int sc_rows_per_block = getenv("ARROWSPACE_SC_ROWS_PER_BLOCK") ? atoi(getenv("ARROWSPACE_SC_ROWS_PER_BLOCK")) : 128;
-            const int64_t want_sc = pre.sc_enabled ? std::max<int64_t>(1, rows / std::max(sc_rows_per_block, 64)) : want;
+            const int64_t want_sc = pre.sc_enabled ? std::max<int64_t>(1, rows / std::max(sc_rows_per_block(), 64)) : want;
             const int64_t nblk = std::min<int64_t>(std::min(want, want_sc), bpc * (int64_t)q->cus);
             const int64_t NW = nblk * 4;
             q->sc_nw = (int)NW;
@@ -2532,6 +2593,26 @@ as_status launch_scan(as_query* q, const PreArgs& pre) {
             const int rounds = (int)(rows / (NW * crows));
             const int64_t rem = rows - (int64_t)rounds * NW * crows;
             const int tail_rows = (int)((rem + NW - 1) / NW);
+            if (coarse && pre.nib) {
+                // the nibble tiles: the dynamic schedule's kernel alone, on the plan nib_scan_fits judged (tile_schedule; query_begin
+                // asked before it prepared digits and coefficient for these tiles, so there is no 8-bit launch to fall back to here)
+                const int C = (int)(sp->dp8 / 32);
+                const int dynv = g_tile_dyn.load(std::memory_order_relaxed);
+                if (!sp->x4 || !pre.sc_enabled || C < 16 || !pre.tile_ctrs) {
+                    set_err("launch_scan: a nibble scan without its image, scorer candidates or 16 chunks per row");
+                    return AS_EINVAL;
+                }
+                int64_t nblk4;
+                int rounds4, tail4, crows4;
+                tile_schedule(q, rows, tile_bpc(), &nblk4, &rounds4, &tail4, &crows4);
+                q->sc_nw = (int)(nblk4 * 4);
+                if (dynv == 16 || dynv == 32) crows4 = std::min(crows4, dynv);
+                const int ng = nblk4 >= 32 ? SC_COPIES : (nblk4 >= 8 ? 8 : (nblk4 >= 4 ? 4 : (nblk4 >= 2 ? 2 : 1)));
+                hipLaunchKernelGGL((scan_tile_kernel_dyn<8, true, true>), dim3((unsigned)nblk4), dim3(256), tile_lds(8, true, C), st, (const signed char*)sp->x4, C, q->r0,
+                                   q->r1, q->dots32, pre, crows4, ng);
+                AS_HIP(hipGetLastError());
+                return AS_OK;
+            }
             if (coarse) {
                 const int C = (int)(sp->dp8 / 16);
                 const signed char* xt = (const signed char*)sp->x8h;

@@ -3165,6 +3165,7 @@ static bool host_query_digits(as_query* q, int64_t d) {
     const int64_t dp8 = sp->dp8;
     signed char* out = (signed char*)q->hq8;
     double st2 = 0.0, sa2 = 0.0;
+    int64_t sq = 0;   // the nibble tiles' Sq: the sum of q1 over the d real columns (zero beyond them: v = 0 there)
     for (int64_t c0 = 0; c0 < dp8; c0 += 16) {   // 16 columns = one a1 chunk and one a2 chunk of the image row
         signed char q1v[16], q2v[16];
         float tq[16];
@@ -3198,6 +3199,15 @@ static bool host_query_digits(as_query* q, int64_t d) {
             memcpy(hc, q1v, 16);
             memcpy(hc + 16, q2v, 16);
         }
+        if (q->nib_try) {   // the nibble tiles: chunk c0 / 32 = 32 columns, 16 bytes of q1 at its even columns, then 16 at its odd ones
+            signed char* nc = (signed char*)q->hq4 + (c0 >> 5) * 32 + ((c0 >> 4) & 1) * 8;
+            for (int j = 0; j < 8; ++j) {
+                const int qe = c0 + 2 * j < d ? q1v[2 * j] : 0, qo = c0 + 2 * j + 1 < d ? q1v[2 * j + 1] : 0;   // (zero at the padded columns)
+                nc[j] = (signed char)qe;
+                nc[16 + j] = (signed char)qo;
+                sq += qe + qo;
+            }
+        }
     }
     const double nq = std::sqrt(q->h_nq);
     const double uq = (double)m * std::sqrt(st2) / (16256.0 * nq) * 1.001, vq = (double)m * std::sqrt(sa2) / (16256.0 * nq) * 1.001;
@@ -3210,6 +3220,21 @@ static bool host_query_digits(as_query* q, int64_t d) {
     // the coarse scan drops a2 . (128 q1 + q2) as well: at most V |x||q| (1 + u_q)
     q->coef_i8h = uq + 1.001 * sp->u8max + 1.002 * sp->v8max + rnd;
     q->h_faq = m * (11.313708498984761f / 16256.0f);   // s_q sqrt(128) / 16256
+    // The NIBBLE tiles (as_build.hip, space_nib_image): x~_c = (lv_c + 1/2) t_i on the d real columns, q~_c = s_q 128 q1_c / 16256 --
+    // the query's high digit alone.  The scan forms x~ . q~ = t_i (s_q 128 / 16256) (sum_c lv_c q1_c + Sq / 2) exactly in int32
+    // (16 lv per product, 8 Sq added: |.| <= 16256 d), then scales in fp32.  With x - x~ = e_x, |e_x| <= R4 |x| (sp->r4max, measured
+    // row by row) and q - q~ = s_q (theta + q2) / 16256, |q - q~| <= |q| (u_q + v_q):
+    //   x.q - x~.q~ = e_x . q + x~ . (q - q~),   |.| <= R4 |x||q| + |x~| |q| (u_q + v_q) <= |x||q| (R4 + (1 + R4)(u_q + v_q))
+    // (Cauchy-Schwarz twice, |x~| <= (1 + R4) |x|).  Roundings: the integer's conversion (exact below 2^24, i.e. up to 1 032
+    // columns; one rounding beyond), the product of the two scales, the scaling, the query scale's own two -- of a value of at
+    // most |x~||q~| <= 1.3 |x||q|: ten (twelve for the wider rows) times 2^-24 cover them with room.
+    // (R4 is known once the image stands: query_begin forms coef_i4 from uv4 behind space_nib_image)
+    q->coef_i4 = 0.0;
+    if (q->nib_try) {
+        q->uv4 = (uq + vq) * 1.001 + (sp->dp8 > 1024 ? 12.0 : 10.0) * 5.9604644775390625e-8;
+        q->sq4 = (int)sq;
+        q->h_faq4 = m * (128.0f / 16256.0f) * 0.0625f;   // s_q 128 / 16256, and the 1/16 of the kernel's 16 lv
+    }
     return true;
 }
 
@@ -3314,7 +3339,9 @@ static as_status gang_launch(as_query* q, const ScanRequest& rq, const PreArgs& 
     const as_space* sp = q->sp;
     static const bool gang_off = getenv("ARROWSPACE_GANG") && atoi(getenv("ARROWSPACE_GANG")) == 0;
     static const double linger_us = getenv("ARROWSPACE_GANG_LINGER_US") ? atof(getenv("ARROWSPACE_GANG_LINGER_US")) : 60.0;
-    if (gang_off || !rq.gang_ok || sp->gang_hint.load(std::memory_order_relaxed) <= 0) return launch_scan(q, pre);
+    // (a scan prepared for the nibble tiles is never filed into a gang: the gang kernel reads the 8-bit tiles, 8-bit digits and
+    // the FIRST member's scales for everybody -- query_begin keeps such a search away from here; held again where it would matter)
+    if (gang_off || !rq.gang_ok || q->nib || pre.nib || sp->gang_hint.load(std::memory_order_relaxed) <= 0) return launch_scan(q, pre);
     std::shared_ptr<as_gang> g;
     bool leader = false;
     {
@@ -3414,6 +3441,7 @@ static as_status query_begin(as_query* q, const double* query_host, int64_t src_
     q->host_q = 0;
     q->i8_scan = 0;
     q->coarse = 0;
+    q->nib = q->nib_try = 0;
     q->q64_src = q->q64;
     q->q32_src = q->q32;
     // Host-prepared query: one query, fp32 LDS-DMA scan (rows up to 1024 floats), item mode.  The host converts the query
@@ -3433,6 +3461,13 @@ static as_status query_begin(as_query* q, const double* query_host, int64_t src_
         }
         q->h_nq = host_sumsq(query_host, d);
         q->h_inq = q->h_nq > 0.0 ? 1.0 / sqrt(q->h_nq) : 0.0;
+        // (the nibble tiles' digits are written only for a search that may read them: everything the routing below asks except what
+        // host_query_digits itself decides)
+        const int cbits = coarse_bits();
+        q->nib_try = rq.allow_nib && rq.sc && !rq.chainc && !rq.direct && cbits != 8 && q->hq4 && r0 == 0 && r1 == sp->n && r1 > r0 &&
+                             sp->x4_ready.load(std::memory_order_relaxed) != 2 && sp->gang_hint.load(std::memory_order_relaxed) <= 0 &&
+                             nib_scan_fits(q, true, r1 - r0, cbits == 4)
+                         ? 1 : 0;
         q->i8_scan = host_query_digits(q, d) ? 1 : 0;
         if (!narrow && !q->i8_scan) host_path = false;
         // Coarse scan: only where everything it collects is re-evaluated exactly (the fused tail: tau >= 0.4, scan-side scorer
@@ -3449,6 +3484,22 @@ static as_status query_begin(as_query* q, const double* query_host, int64_t src_
                 q->coef_i8 = q->coef_i8h;   // (coef_query returns it: prefilter, window and proofs all price the coarse dots)
             }
         }
+        // ... on the NIBBLE tiles (half the coarse operand's bytes): the fused tail's search of a whole single space with no
+        // concurrent callers seen lately (gang_hint: gang scans stay on the 8-bit tiles, and so does every search between them -- with
+        // two Python threads, searches that alternated between the two images ran 6 400-6 600 -> 5 800 queries/s), where the
+        // dynamic schedule serves the tiles' dp8 / 32 chunks (nib_scan_fits) and the image stands.  No fixed gate on the coefficient
+        // (0.15 - 0.17 on clustered unit rows; a number here would be a guess): the route is outcome-driven -- a nibble search that
+        // ends in a rerun is redone on 8 bits by search_run, and the workspace's next 63 eligible searches skip the tiles (nib_off).
+        q->nib = 0;
+        if (q->coarse && q->nib_try && !(q->nib_off > 0 && (q->nib_off++ & 63) != 0)) {
+            bool have4 = false;
+            if (space_nib_image(sp, &have4) == AS_OK && have4) {
+                q->nib = 1;
+                q->coef_i4 = 1.001 * sp->r4max + (1.0 + sp->r4max) * q->uv4;
+                q->coef_i8 = q->coef_i4;
+                sp->nib_count[0].fetch_add(1, std::memory_order_relaxed);
+            }
+        }
     }
     rq.sc_ran = rq.sc && (host_path || narrow) ? 1 : 0;
     if (host_path) {
@@ -3463,7 +3514,9 @@ static as_status query_begin(as_query* q, const double* query_host, int64_t src_
         const PreArgs pre = make_pre(q, rq, eps, exclude, !q->robust && !rq.direct);
         // (a scan that may be shared with other callers': the coarse scan of a whole single space that collects scorer candidates,
         // nothing queued on this workspace's stream that the scan must follow, no per-launch timing asked for)
-        const int why = sp->gang_hint.load(std::memory_order_relaxed) <= 0 ? 0 : (!rq.gang_ok || !pre.sc_enabled) ? 1 : !q->coarse ? 2 : !was_clean ? 3 : stats ? 4 : (r0 != 0 || r1 != sp->n) ? 5 : -1;
+        // (a search prepared for the NIBBLE tiles never joins or leads a gang -- its digits, scales and coefficient are not the
+        // 8-bit tiles': a second caller may have arrived, and raised gang_hint, since nib_try read it; counted with reason [2])
+        const int why = sp->gang_hint.load(std::memory_order_relaxed) <= 0 ? 0 : (!rq.gang_ok || !pre.sc_enabled) ? 1 : (!q->coarse || q->nib || pre.nib) ? 2 : !was_clean ? 3 : stats ? 4 : (r0 != 0 || r1 != sp->n) ? 5 : -1;
         if (why < 0) {
             AS_TRY(gang_launch(q, rq, pre));
         } else {
@@ -3561,6 +3614,10 @@ int32_t as_set_tuning(const char* key, int32_t value) {
         set_tile_dyn(value);
         return 0;
     }
+    if (key && !strcmp(key, "coarse_bits")) {
+        set_coarse_bits(value);
+        return 0;
+    }
     if (key && !strcmp(key, "x1_blocks")) {
         set_x1_blocks(value);
         return 0;
@@ -3579,6 +3636,26 @@ int32_t as_set_tuning(const char* key, int32_t value) {
         return 0;
     }
     return 1;
+}
+
+// (test hook of the nibble tiles, not declared in the public header: the dots the space's first pooled workspace kept from its
+// last scan and the coefficient they carry, |dot - x.q| <= coef |x||q|; under qmu, for a caller with no search in flight)
+as_status as_debug_last_dots(const as_space* sp, float* dots, int64_t nrows, double* coef) {
+    if (!sp || !dots || nrows < 0 || nrows > sp->n) {
+        set_err("as_debug_last_dots: null argument, or more rows than items");
+        return AS_EINVAL;
+    }
+    std::lock_guard<std::mutex> lk(sp->qmu);
+    if (!sp->qcache || !sp->qcache->dots32 || sp->qbusy[0]) {
+        set_err("as_debug_last_dots: no single-query search yet, or one in flight");
+        return AS_EINVAL;
+    }
+    AS_HIP(hipSetDevice(sp->device));
+    as_query* q = sp->qcache;
+    AS_HIP(hipStreamSynchronize(q->stream));
+    AS_HIP(hipMemcpy(dots, q->dots32, sizeof(float) * (size_t)nrows, hipMemcpyDeviceToHost));
+    if (coef) *coef = coef_query(q, false);
+    return AS_OK;
 }
 
 #ifdef AS_STAMPS
@@ -3691,6 +3768,9 @@ static as_status query_alloc(as_query* q) {
         AS_HIP(hipHostMalloc(&q->hq8h, dp8 * 2, hipHostMallocMapped | hipHostMallocCoherent));
         memset(q->hq8h, 0, dp8 * 2);
         AS_HIP(hipHostGetDevicePointer((void**)&q->hq8h_dev, q->hq8h, 0));
+        AS_HIP(hipHostMalloc(&q->hq4, dp8, hipHostMallocMapped | hipHostMallocCoherent));   // (dp8 / 32 chunks of 32 bytes)
+        memset(q->hq4, 0, dp8);
+        AS_HIP(hipHostGetDevicePointer((void**)&q->hq4_dev, q->hq4, 0));
     }
     AS_HIP(hipMalloc(&q->q64, sizeof(double) * sp->dp * C));
     AS_HIP(hipMalloc(&q->q32, sizeof(float) * sp->dp * C));
@@ -3768,6 +3848,7 @@ void as_query_free(as_query* q) {
     if (q->hq32) hipHostFree(q->hq32);
     if (q->hq8) hipHostFree(q->hq8);
     if (q->hq8h) hipHostFree(q->hq8h);
+    if (q->hq4) hipHostFree(q->hq4);
     if (q->gang_ev) {
         hipEvent_t mine = q->gang_ev;
         if (q->sp) q->sp->last_scan_ev.compare_exchange_strong(mine, nullptr);   // (nobody may poll an event that is gone)
@@ -4227,6 +4308,8 @@ void query_flags(const as_query* q, int* knn_inexact, int* score_inexact) {
 }
 
 int query_overflow_bits(const as_query* q) { return q->hout->overflow; }
+// width of the coarse operand the last scan read: 4 the nibble tiles, 8 everything else (as_query_scan_int8 tells which operand)
+extern "C" int32_t as_query_scan_bits(const as_query* q) { return q && q->i8_scan && q->coarse && q->nib ? 4 : 8; }
 extern "C" int32_t as_query_scan_int8(const as_query* q) { return q ? (q->i8_scan ? 1 + q->coarse : 0) : 0; }   // 0 fp32 items, 1 the int8 image, 2 its high digits alone (coarse scan)   // bit0 k-NN candidates, bit1 scorer's, bit2 the scan's scorer candidates
 
 // ARROWSPACE_FUSED_X1=0: the fused tail as ONE launch (fused_finish_kernel), no coarse scan; ARROWSPACE_COARSE_CHAIN=0: no coarse chain
@@ -4275,7 +4358,7 @@ static void chain_hints(as_query* q, bool direct, int ov, bool clean) {
 // one full single-GPU search on q's stream: 6 launches, one host wait.  no_coarse: the redo of a query the coarse scan did not
 // serve -- this call scans the two-digit image, whatever the switches say
 static as_status search_run(as_query* q, const double* query, int64_t d, double tau, int mode, int64_t* out_idx, double* out_score,
-                            int64_t* out_len, double* out_lambda_q, bool no_coarse) {
+                            int64_t* out_len, double* out_lambda_q, bool no_coarse, bool no_nib = false) {
     q->exact = (mode & 1) || q->sp->opts.force_exact;
     q->robust = (mode & 2) ? 1 : 0;
     const bool feature = q->gr->lambda_mode == AS_LAMBDA_FEATURE;
@@ -4308,6 +4391,7 @@ static as_status search_run(as_query* q, const double* query, int64_t d, double 
     rq.chainc = want_chainc ? 1 : 0;
     rq.allow_coarse = (want_fused || want_chainc) && fused_x1_on() ? 1 : 0;   // (the coarse scan needs the two-launch tail: its k-NN candidates are evaluated by all blocks)
     rq.gang_ok = rq.sc_late = want_fused && fused_x1_on() ? 1 : 0;   // (the two-launch tail validates lossy wave reports against the final histogram)
+    rq.allow_nib = want_fused && fused_x1_on() && !no_nib && (int64_t)std::max<int64_t>(q->k, 1) <= REC_CAP ? 1 : 0;
     // (ARROWSPACE_HOST_TIMING=1: host microseconds of the fused path's parts -- preparation + scan launch, the two tail launches,
     // the wait for the publication -- averaged over 200 searches, on stderr)
     static const bool host_timing = getenv("ARROWSPACE_HOST_TIMING") != nullptr;
@@ -4376,6 +4460,18 @@ static as_status search_run(as_query* q, const double* query, int64_t d, double 
         }
         q->x1_dirty = 0;
         q->xknn_dirty = 0;
+        if (q->nib && (q->hout->overflow || q->hout->knn_inexact || q->hout->score_inexact)) {
+            // The nibble tiles did not serve this query -- a candidate list that did not fit their wider windows, a wave report the
+            // tail did not accept, a proof that failed: the same query again on the 8-bit tiles, as if the nibble scan had never
+            // run, and this workspace's next 63 eligible searches skip the tiles.
+            dbg("nibble scan: overflow bits %d, k-NN %d, scorer %d (coefficient %.3e) -> this search again on the 8-bit tiles, which the next 63 take directly",
+                q->hout->overflow, q->hout->knn_inexact, q->hout->score_inexact, q->coef_i4);
+            q->nib_off = 1;
+            q->sp->nib_count[1].fetch_add(1, std::memory_order_relaxed);
+            q->info_clean = 0;
+            return search_run(q, query, d, tau, mode, out_idx, out_score, out_len, out_lambda_q, no_coarse, true);
+        }
+        if (q->nib) q->nib_off = 0;
         if (q->coarse && (q->hout->overflow & 5) && chainc_on() && !chainc_skip && !coarse_never) {
             // the scan's candidate lists did not fit -- a neighbourhood of more than 4 096 rows (bit 0), a cosine window that takes in
             // too many rows (bit 2): this query again as a coarse chain, which derives those lists from the kept dots by threshold;
@@ -4384,7 +4480,7 @@ static as_status search_run(as_query* q, const double* query, int64_t d, double 
             if (q->hout->overflow & 1) q->crowded = 1;
             if (q->hout->overflow & 4) q->sc_crowded = 1;
             q->info_clean = 0;
-            return search_run(q, query, d, tau, mode, out_idx, out_score, out_len, out_lambda_q, no_coarse);
+            return search_run(q, query, d, tau, mode, out_idx, out_score, out_len, out_lambda_q, no_coarse, no_nib);
         }
         if (q->coarse && (q->hout->overflow & 5)) {
             // the coarse scan's candidates did not fit (its wider windows took in too many rows): the same query on the two-digit

@@ -1295,6 +1295,13 @@ class ShardedIndex:
         q = e.qs if self._lib_comm else e.q
         return {0: "fp32", 1: "int8", 2: "int8-high"}.get(int(e.L.as_query_scan_int8(q)), "fp32")
 
+    @property
+    def last_scan_bits(self):
+        """Width of the coarse operand this rank's last single-query scan read: 4 (nibble tiles) or 8."""
+        e = self.engine
+        q = e.qs if self._lib_comm else e.q
+        return int(e.L.as_query_scan_bits(q))
+
     def build_stats(self):
         return getattr(self.engine, "stats", lambda: {})()
 
