@@ -612,6 +612,35 @@ as_status as_lists_counters(const as_space* sp, int64_t* out, int32_t n);
 /* measurement: the device microseconds of the ragged score kernel, summed over the chunks of the last call on this space that
  * ran under as_set_tuning("lists_timing", 1) (HIP events around the kernel; off by default) */
 double as_lists_kernel_us(const as_space* sp);
+/* Tau sweeps over per-query candidate lists: the two forms above under ntau taus, with ONE lambda_q step (ONE as_search_batch call
+ * over all b queries, run with taus[0], hits discarded), ONE upload per chunk of queries and ONE ragged gather per chunk and up to
+ * 8 distinct taus: every (query, item) cosine is formed once and blended with each tau of the group.  Query-major layouts.
+ * as_score_lists_batch_taus: with m_i = offsets[i + 1] - offsets[i], the score of (query i, tau j, entry e) is at
+ * out_scores[ntau * offsets[i] + j * m_i + e]: query i owns one contiguous [ntau][m_i] block, row j of it is what
+ * as_score_lists_batch writes for query i under taus[j] (the caller's order, duplicates kept).  as_search_lists_batch_taus: list
+ * (i, j) at out_idx / out_score + (i * ntau + j) * kk, kk = min(topk, nitems), out_len[i * ntau + j] = min(kk, distinct ids of list
+ * i) entries, is what as_search_lists_batch returns for query i under taus[j].  The same score bits as the single-tau forms given
+ * the same lambda_q; the two sweep forms give the same bits for the same (query, tau, item).  One out_lambda_q and one out_status
+ * per query (both may be NULL); lambda_q == 0 -> AS_EZEROLAMBDA in out_status, out_len 0 for every list of that query, its block
+ * of out_scores left unwritten, the others served.  Checked before anything is launched, the lambda_q step included: the
+ * single-tau forms' checks with their codes and messages, a NaN or infinite tau anywhere in the list and a null taus with ntau > 0
+ * -> AS_EINVAL; every finite tau is served.  ntau == 0 and b == 0 launch nothing (ntau == 0: no lambda_q step either); empty lists
+ * still run the lambda_q step.  Taus equal by bit pattern are computed once, their rows / lists copied.  The taus per gather
+ * (<= 8) and the queries per chunk follow from the "subset_batch_mib" budget (a list too long for it: a chunk of its own, one tau
+ * per gather); results never depend on either.  One selection block per (list, tau) pair, one stream wait per (chunk, tau group).
+ * The buffers are the single-tau forms' (in the space, grown on demand); calls are serialised with them, as_search runs beside
+ * them.  Under "lists_timing" as_lists_kernel_us reports the sweep's score kernel summed over the launches of the call. */
+as_status as_score_lists_batch_taus(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d,
+                                    const double* taus, int64_t ntau, const int64_t* ids_host, const int64_t* offsets_host,
+                                    double* out_scores, double* out_lambda_q, int32_t* out_status);
+as_status as_search_lists_batch_taus(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d,
+                                     const double* taus, int64_t ntau, const int64_t* ids_host, const int64_t* offsets_host,
+                                     int64_t* out_idx, double* out_score, int64_t* out_len, double* out_lambda_q, int32_t* out_status);
+/* out[0] calls of the two sweeps above that passed their checks, [1] score-kernel launches they made, [2] (query, item) pairs those
+ * launches gathered (once per launch, not per tau), [3] (query, item, tau) scores they wrote, [4] lambda_q steps run, [5]
+ * (measurement) host nanoseconds spent on id checks, deduplication and work tables.  as_lists_counters counts the single-tau forms
+ * only. */
+as_status as_lists_sweep_counters(const as_space* sp, int64_t* out, int32_t n);
 
 /* ---- index persistence (extension; the reference exposes none): one flat file
  * holding the items, lambdas and graph arrays.  Loading re-ingests the items and uploads the

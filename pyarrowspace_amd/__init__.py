@@ -577,6 +577,66 @@ class ArrowSpace:
             raise TypeError("argument 'taus': expected a 1-D sequence of floats")
         return t
 
+    def search_batch_lists_taus(self, items, gl: GraphLaplacian, taus, lists):
+        """Extension: re-ranking of per-query candidate lists under several taus, B queries [B, D] each with its own id list ->
+        for each query a list of one hit list per entry of `taus`; entry [i][j] is what
+        `search_batch_lists(items, gl, taus[j], lists)[i]` returns, with the same score bits.  `lists` as for
+        `search_batch_lists`.  Costs ONE `search_batch` over the B queries (lambda_q does not depend on tau; a query whose
+        lambda_q is 0 panics as there), one upload per chunk of queries and ONE ragged gather per up to 8 distinct taus: every
+        cosine is formed once and blended with each tau.  Finite taus only (ValueError otherwise, before anything runs); equal
+        taus are computed once; `taus = []` returns B empty lists."""
+        Q, ids, offsets = self._lists_args(items, gl, lists)
+        t = self._taus(taus)
+        b, nt = Q.shape[0], t.shape[0]
+        kk = max(min(int(gl.graph_params["topk"]), self.nitems), 1)
+        idx = np.empty(max(b * nt * kk, 1), dtype=np.int64)
+        sc = np.empty(max(b * nt * kk, 1), dtype=np.float64)
+        ln = np.zeros(max(b * nt, 1), dtype=np.int64)
+        stt = np.zeros(max(b, 1), dtype=np.int32)
+        st = _L.as_search_lists_batch_taus(self._h, gl._h, Q.ctypes.data_as(C.c_void_p), b, Q.shape[1], t.ctypes.data, nt,
+                                           ids.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p), idx.ctypes.data,
+                                           sc.ctypes.data, ln.ctypes.data, None, stt.ctypes.data)
+        if st:
+            _raise(st)
+        if (stt[:b] == _lib.AS_EZEROLAMBDA).any():
+            raise PanicException("The lambdas are zero, check the magnitude of items and eps.")
+        idx, sc, ln = idx[:b * nt * kk].reshape(b, nt, kk), sc[:b * nt * kk].reshape(b, nt, kk), ln[:b * nt].reshape(b, nt)
+        return [[list(zip(ii[:l], ss[:l])) for ii, ss, l in zip(bi, bs, bl)]
+                for bi, bs, bl in zip(idx.tolist(), sc.tolist(), ln.tolist())]
+
+    def score_lists_batch_taus(self, items, gl: GraphLaplacian, taus, lists):
+        """Extension: scores of per-query candidate lists under several taus -> a list of B float64 arrays of shape
+        (len(taus), m_i), views of one output buffer (a 2-D integer array (B, C) as `lists` returns an array
+        (B, len(taus), C)): row j of array i is what `score_lists_batch(items, gl, taus[j], lists)[i]` returns, with the same
+        bits (and the bits `search_batch_lists_taus` gives the same query, tau and item).  Costs one `search_batch` over the B
+        queries (lambda_q; a query whose lambda_q is 0 panics as there) and one ragged gather per up to 8 distinct taus.
+        `taus = []` returns arrays of shape (0, m_i)."""
+        Q, ids, offsets = self._lists_args(items, gl, lists)
+        t = self._taus(taus)
+        b, nt = Q.shape[0], t.shape[0]
+        out = np.empty(nt * ids.shape[0], dtype=np.float64)
+        stt = np.zeros(max(b, 1), dtype=np.int32)
+        st = _L.as_score_lists_batch_taus(self._h, gl._h, Q.ctypes.data_as(C.c_void_p), b, Q.shape[1], t.ctypes.data, nt,
+                                          ids.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p),
+                                          out.ctypes.data_as(C.c_void_p), None, stt.ctypes.data)
+        if st:
+            _raise(st)
+        if (stt[:b] == _lib.AS_EZEROLAMBDA).any():
+            raise PanicException("The lambdas are zero, check the magnitude of items and eps.")
+        if isinstance(lists, np.ndarray) and lists.ndim == 2 and lists.dtype != np.bool_:
+            return out.reshape(lists.shape[0], nt, lists.shape[1])
+        return [out[nt * offsets[i]:nt * offsets[i + 1]].reshape(nt, offsets[i + 1] - offsets[i]) for i in range(b)]
+
+    def lists_sweep_counters(self) -> dict:
+        """Extension: `search_batch_lists_taus` / `score_lists_batch_taus` calls on this space that passed their checks, the
+        score-kernel launches they made, the (query, item) pairs those gathered (once per launch, not per tau), the (query,
+        item, tau) scores they wrote, and the lambda_q steps run (`search_batch` calls)."""
+        out = np.zeros(5, dtype=np.int64)
+        st = _L.as_lists_sweep_counters(self._h, out.ctypes.data_as(C.c_void_p), 5)
+        if st:
+            _raise(st)
+        return dict(zip(("calls", "score_launches", "pairs", "scores", "lambda_steps"), (int(v) for v in out)))
+
     def search_subset_taus(self, item, gl: GraphLaplacian, taus, subset):
         """Extension: filtered search under several taus -> one hit list per entry of `taus`, in order; list j is what
         `search_subset(item, gl, taus[j], subset)` returns, with the same score bits.  Costs ONE ordinary `search` (lambda_q

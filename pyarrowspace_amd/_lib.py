@@ -55,6 +55,7 @@ SYMBOLS = [
     "as_search_subset_batch", "as_score_items_batch",
     "as_search_subset_taus", "as_score_items_taus", "as_search_subset_batch_taus", "as_score_items_batch_taus", "as_subset_sweep_counters",
     "as_score_lists_batch", "as_search_lists_batch", "as_lists_counters", "as_lists_kernel_us",
+    "as_score_lists_batch_taus", "as_search_lists_batch_taus", "as_lists_sweep_counters",
 ]
 
 _lib = None
@@ -224,6 +225,9 @@ def load():
         "as_search_lists_batch": (i32, [vp, vp, vp, i64, i64, f64, vp, vp, vp, vp, vp, vp, vp]),
         "as_lists_counters": (i32, [vp, vp, i32]),
         "as_lists_kernel_us": (f64, [vp]),
+        "as_score_lists_batch_taus": (i32, [vp, vp, vp, i64, i64, vp, i64, vp, vp, vp, vp, vp]),
+        "as_search_lists_batch_taus": (i32, [vp, vp, vp, i64, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
+        "as_lists_sweep_counters": (i32, [vp, vp, i32]),
         "as_subset_set_timing": (None, [vp, i32]),
         "as_subset_kernel_us": (f64, [vp]),
         "as_gang_counters": (i32, [vp, vp, i32]),

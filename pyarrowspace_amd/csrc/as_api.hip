@@ -1725,6 +1725,116 @@ as_status as_subset_sweep_counters(const as_space* sp, int64_t* out, int32_t n) 
     return AS_OK;
 }
 
+// ---------------------------------------------------------------- tau sweeps over per-query lists (extension)
+// lists_call with a list of taus: the same checks before anything is launched (every tau finite), ONE lambda_q step with taus[0]
+// beside the helper thread's deduplication, the distinct taus through lists_run_taus under sp->lmu, repeated taus copied here.
+static as_status lists_taus_call(const char* who, const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d,
+                                 const double* taus, int64_t ntau, const int64_t* ids_host, const int64_t* offs_host, bool select,
+                                 int64_t* out_idx, double* out_score, int64_t* out_len, double* out_scores, double* out_lambda_q,
+                                 int32_t* out_status) {
+    AS_TRY(subset_checks(who, sp, gr, d, taus, ntau));
+    auto t0 = std::chrono::steady_clock::now();
+    AS_TRY(lists_checks(who, sp, ids_host, offs_host, b));
+    sp->lsweep_count[5].fetch_add(host_ns_since(t0), std::memory_order_relaxed);
+    sp->lsweep_count[0].fetch_add(1, std::memory_order_relaxed);
+    if (b == 0 || ntau == 0) return AS_OK;
+    std::vector<int32_t> ids;
+    std::vector<int64_t> offs;
+    bool ids_ok = true;
+    std::thread helper;
+    try {
+        helper = std::thread([&] { ids_ok = lists_ids32(sp, ids_host, offs_host, b, select, ids, offs); });
+    } catch (const std::system_error&) {   // no thread to be had: in line
+        ids_ok = lists_ids32(sp, ids_host, offs_host, b, select, ids, offs);
+    }
+    std::vector<double> lq;
+    std::vector<int32_t> st;
+    sp->lsweep_count[4].fetch_add(1, std::memory_order_relaxed);
+    const as_status ls = batch_lambda_step(who, sp, gr, queries, b, d, taus[0], lq, st);
+    t0 = std::chrono::steady_clock::now();
+    if (helper.joinable()) helper.join();
+    sp->lsweep_count[5].fetch_add(host_ns_since(t0), std::memory_order_relaxed);
+    if (ls != AS_OK) return ls;
+    if (!ids_ok) {
+        set_err("%s: out of host memory for %lld ids", who, (long long)offs_host[b]);
+        return AS_ENOMEM;
+    }
+    for (int64_t i = 0; i < b; ++i) {
+        if (out_lambda_q) out_lambda_q[i] = lq[i];
+        if (out_status) out_status[i] = st[i];
+    }
+    const int64_t kk = select ? std::min<int64_t>(gr->gp.topk, sp->n) : 0;
+    std::vector<double> uniq;
+    std::vector<int64_t> row, slot;
+    distinct_taus(taus, ntau, uniq, row, slot);
+    int64_t counts[4] = {0, 0, 0, 0};
+    as_status r;
+    {
+        std::lock_guard<std::mutex> lk(sp->lmu);
+        r = hipSetDevice(sp->device) == hipSuccess ? AS_OK : AS_EHIP;
+        if (r != AS_OK) set_err("%s: hipSetDevice failed", who);
+        else
+            r = lists_run_taus(sp, ids.data(), offs.data(), queries, b, lq.data(), st.data(), uniq.data(), (int64_t)uniq.size(), row.data(), ntau,
+                               kk, out_idx, out_score, out_len, out_scores, counts);
+    }
+    for (int c = 0; c < 3; ++c) sp->lsweep_count[1 + c].fetch_add(counts[c], std::memory_order_relaxed);
+    sp->lsweep_count[5].fetch_add(counts[3], std::memory_order_relaxed);
+    if (r != AS_OK || uniq.size() == (size_t)ntau) return r;
+    for (int64_t i = 0; i < b; ++i) {   // equal taus: copies of the first one's list / row
+        if (st[i] == AS_EZEROLAMBDA) continue;   // (nothing of it was written)
+        const int64_t m = offs_host[i + 1] - offs_host[i];
+        for (int64_t j = 0; j < ntau; ++j) {
+            const int64_t fj = row[slot[j]];
+            if (fj == j) continue;
+            if (select) {
+                const int64_t f = i * ntau + fj, p = i * ntau + j;
+                for (int64_t t = 0; t < out_len[f]; ++t) {
+                    out_idx[p * kk + t] = out_idx[f * kk + t];
+                    out_score[p * kk + t] = out_score[f * kk + t];
+                }
+                out_len[p] = out_len[f];
+            } else if (m > 0) {
+                double* blk = out_scores + ntau * offs_host[i];
+                memcpy(blk + j * m, blk + fj * m, sizeof(double) * (size_t)m);
+            }
+        }
+    }
+    return AS_OK;
+}
+
+as_status as_score_lists_batch_taus(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, const double* taus,
+                                    int64_t ntau, const int64_t* ids_host, const int64_t* offsets_host, double* out_scores,
+                                    double* out_lambda_q, int32_t* out_status) {
+    if (!sp || !gr || b < 0 || ntau < 0 || !offsets_host || (b > 0 && !queries) || (ntau > 0 && !taus) ||
+        (offsets_host[b] > 0 && (!ids_host || (ntau > 0 && !out_scores)))) {
+        set_err("as_score_lists_batch_taus: null argument");
+        return AS_EINVAL;
+    }
+    return lists_taus_call("as_score_lists_batch_taus", sp, gr, queries, b, d, taus, ntau, ids_host, offsets_host, false, nullptr, nullptr,
+                           nullptr, out_scores, out_lambda_q, out_status);
+}
+
+as_status as_search_lists_batch_taus(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, const double* taus,
+                                     int64_t ntau, const int64_t* ids_host, const int64_t* offsets_host, int64_t* out_idx, double* out_score,
+                                     int64_t* out_len, double* out_lambda_q, int32_t* out_status) {
+    if (!sp || !gr || b < 0 || ntau < 0 || !offsets_host || (b > 0 && !queries) || (ntau > 0 && !taus) || (b > 0 && ntau > 0 && !out_len) ||
+        (offsets_host[b] > 0 && (!ids_host || (ntau > 0 && (!out_idx || !out_score))))) {
+        set_err("as_search_lists_batch_taus: null argument");
+        return AS_EINVAL;
+    }
+    return lists_taus_call("as_search_lists_batch_taus", sp, gr, queries, b, d, taus, ntau, ids_host, offsets_host, true, out_idx, out_score,
+                           out_len, nullptr, out_lambda_q, out_status);
+}
+
+as_status as_lists_sweep_counters(const as_space* sp, int64_t* out, int32_t n) {
+    if (!sp || !out) {
+        set_err("as_lists_sweep_counters: null argument");
+        return AS_EINVAL;
+    }
+    for (int i = 0; i < n && i < 6; ++i) out[i] = sp->lsweep_count[i].load(std::memory_order_relaxed);
+    return AS_OK;
+}
+
 // One batched tau sweep over b > 1 queries for nt <= TAU_GROUP distinct taus in [0, 1] (under sp->bmu): as_search_batch's
 // workspaces, passes, pairs and pipelining, the scorer tail once per (query, tau) pair.  Pair (i, j): pidx / psc +
 // (i * nt + j) * topk, plen / pst [i * nt + j], plq [i]; pst -1: left to the single search.  *passes: passes that ran the tail.

@@ -157,6 +157,10 @@ struct as_space {
     mutable struct as::ListsWork* lists_ws = nullptr;
     mutable std::mutex lmu;
     mutable std::atomic<int64_t> lists_count[5] = {};
+    // as_lists_sweep_counters (the _taus forms; same buffers, same mutex): [0] calls, [1] score-kernel launches, [2] (query, item)
+    // pairs gathered, once per launch, [3] (query, item, tau) scores written, [4] lambda_q steps run, [5] host nanoseconds as
+    // lists_count[4]
+    mutable std::atomic<int64_t> lsweep_count[6] = {};
     mutable int64_t unproven_searches = 0;   // searches returned although their a-posteriori check failed on the strongest path
     mutable double kstats[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // accumulated by as_knn_rows
 };
@@ -654,6 +658,13 @@ as_status subset_batch_sweep_run(const as_space* sp, SubsetWork* w, int64_t m, c
 as_status lists_run(const as_space* sp, const int32_t* ids, const int64_t* offs, const double* queries, int64_t b, const double* lq,
                     const int32_t* status, double tau, int64_t kk, int64_t* out_idx, double* out_score, int64_t* out_len,
                     double* out_scores, int64_t* counts);
+// The tau sweep over the same lists: nt distinct finite taus, up to TAU_GROUP per gather, one upload per
+// chunk for all its groups; tau taus[u] goes to row row[u] of the ntau rows a query owns.  kk > 0: list (i, row) -> out_idx /
+// out_score + (i * ntau + row) * kk, out_len[i * ntau + row]; kk == 0: out_scores[ntau * offs[i] + row * m_i + e].  counts[0] +=
+// score-kernel launches, [1] += pairs gathered (once per launch), [2] += scores written, [3] += host nanoseconds on the tables.
+as_status lists_run_taus(const as_space* sp, const int32_t* ids, const int64_t* offs, const double* queries, int64_t b, const double* lq,
+                         const int32_t* status, const double* taus, int64_t nt, const int64_t* row, int64_t ntau, int64_t kk, int64_t* out_idx,
+                         double* out_score, int64_t* out_len, double* out_scores, int64_t* counts);
 void lists_work_free(ListsWork* w);
 double lists_kernel_us(const ListsWork* w);
 void set_lists_timing(int v);   // as_set_tuning("lists_timing", 0 | 1)

@@ -2,7 +2,9 @@
 // every (query, item) pair of a chunk of queries (lists_score_kernel: the lists cut into segments of at most LISTS_R entries, a block
 // per segment, the single-query kernel's row loop inside), one block per list selects its first k entries exactly
 // (lists_select_kernel: a radix select over LDS histograms, then a rank of at most 1024 entries).
-// Entry points: as_api.hip (as_score_lists_batch, as_search_lists_batch).
+// Tau sweeps over the lists (section 5.13): lists_score_taus_kernel blends every cosine with up to TAU_GROUP taus, the selection
+// runs a block per (list, tau) pair (lists_run_taus).
+// Entry points: as_api.hip (as_score_lists_batch, as_search_lists_batch and their _taus forms).
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -152,6 +154,130 @@ __global__ __launch_bounds__(256) void lists_score_kernel(ListsArgs a) {
 }
 static_assert(LISTS_ROWS == 4, "the lane selects of lists_score_kernel are written for four rows");
 
+// ------------------------------------------------------------------ tau sweep score kernel
+// A textual copy of lists_score_kernel with subset_score_taus_kernel's epilogue (as_subset.hip): the cosine of a (query, item)
+// pair is formed once and blended with each of nt <= TAU_GROUP taus.  Segment loop, staging, trip, lane partition, accumulation
+// order and butterfly are the original's, so for the same lambda_q a plane holds the bits lists_score_kernel writes for that
+// tau.  A copy, not a shared device function (section 5.11: sharing bodies changed the originals' generated code) -- whoever
+// changes a loop above changes it here.  The taus and their count travel in the argument struct (scalar loads); the loop over
+// them is unrolled and predicated on the wave-uniform count.
+struct ListsTausSeg {   // a segment that knows its list: list t of the chunk owns scores[nt * lfirst .. nt * (lfirst + len)) as [nt][len]
+    int64_t first;      // entry of the chunk (the ids)
+    int64_t lfirst;     // first entry of the segment's list
+    int64_t len;        // entries of the segment's list
+    int32_t query;
+    int32_t count;
+};
+struct ListsTausArgs {
+    ListsArgs s;        // (s.segs and s.tau are not read)
+    const ListsTausSeg* segs;
+    int nt;
+    double taus[TAU_GROUP];
+};
+template <bool F64, bool QLDS>
+__global__ __launch_bounds__(256) void lists_score_taus_kernel(ListsTausArgs t) {
+    const ListsArgs& a = t.s;
+    extern __shared__ double qs[];
+    const int lane = lane_id();
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    constexpr int64_t step = LISTS_WAVES * LISTS_ROWS;
+    int staged = -1;
+    for (int64_t s = blockIdx.x; s < a.nseg; s += gridDim.x) {
+        const ListsTausSeg sg = t.segs[s];   // (s is uniform: scalar loads)
+        const double* qg = a.q64 + (int64_t)sg.query * a.dp;
+        if (QLDS && sg.query != staged) {
+            __syncthreads();   // every wave has finished the previous segment's reads of qs
+            for (int64_t c = threadIdx.x; c < a.dp; c += blockDim.x) qs[c] = qg[c];
+            __syncthreads();
+            staged = sg.query;
+        }
+        const double nqv = a.nq[sg.query], lqv = a.lq[sg.query];
+        const int64_t end = sg.first + sg.count, last = end - 1;
+        int64_t g = sg.first + (int64_t)w * LISTS_ROWS;
+        int32_t next[LISTS_ROWS];
+#pragma unroll
+        for (int r = 0; r < LISTS_ROWS; ++r) next[r] = a.ids[min(g + r, last)];
+        for (; g < end; g += step) {
+            int64_t row[LISTS_ROWS];
+#pragma unroll
+            for (int r = 0; r < LISTS_ROWS; ++r) row[r] = next[r];   // (a short last group reads its last row again)
+#pragma unroll
+            for (int r = 0; r < LISTS_ROWS; ++r) next[r] = a.ids[min(g + step + r, last)];
+            double nrm = 0.0, lam = 0.0;
+            if (lane < LISTS_ROWS) {
+                const int64_t j = lane == 0 ? row[0] : lane == 1 ? row[1] : lane == 2 ? row[2] : row[3];
+                nrm = a.n64[j];
+                lam = a.lam64[j];
+            }
+            double acc[LISTS_ROWS];
+#pragma unroll
+            for (int r = 0; r < LISTS_ROWS; ++r) acc[r] = 0.0;
+            if (F64) {
+                constexpr int U = 6;
+                for (int64_t base = 0; base < a.d; base += 64 * U) {
+                    double v[LISTS_ROWS][U];
+#pragma unroll
+                    for (int r = 0; r < LISTS_ROWS; ++r) {
+                        const double* pj = a.x64 + row[r] * a.d;
+#pragma unroll
+                        for (int u = 0; u < U; ++u) {
+                            const int64_t e = base + 64 * u + lane;
+                            v[r][u] = e < a.d ? pj[e] : 0.0;
+                        }
+                    }
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        const int64_t e = base + 64 * u + lane;
+                        if (e < a.d) {
+                            const double qv = QLDS ? qs[e] : qg[e];
+#pragma unroll
+                            for (int r = 0; r < LISTS_ROWS; ++r) acc[r] += qv * v[r][u];
+                        }
+                    }
+                }
+            } else {
+                constexpr int U = 3;
+                for (int64_t base = 0; base < a.dp; base += 256 * U) {
+                    f32x4 v[LISTS_ROWS][U];
+#pragma unroll
+                    for (int r = 0; r < LISTS_ROWS; ++r) {
+                        const float* pj = a.x32 + row[r] * a.dp;
+#pragma unroll
+                        for (int u = 0; u < U; ++u) {
+                            const int64_t e = base + 256 * u + 4 * lane;   // (dp is a multiple of 32: e < dp leaves 4 floats)
+                            v[r][u] = e < a.dp ? *(const f32x4*)(pj + e) : f32x4{0, 0, 0, 0};
+                        }
+                    }
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        const int64_t e = base + 256 * u + 4 * lane;
+                        if (e < a.dp) {
+#pragma unroll
+                            for (int c4 = 0; c4 < 4; ++c4) {
+                                const double qv = QLDS ? qs[e + c4] : qg[e + c4];
+#pragma unroll
+                                for (int r = 0; r < LISTS_ROWS; ++r) acc[r] += qv * (double)v[r][u][c4];
+                            }
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < LISTS_ROWS; ++r) acc[r] = wave_sum(acc[r]);
+            if (lane < LISTS_ROWS && g + lane < end) {
+                const double dot = lane == 0 ? acc[0] : lane == 1 ? acc[1] : lane == 2 ? acc[2] : acc[3];
+                const double den = sqrt(nrm * nqv);
+                const double c = den > 0.0 ? dot / den : 0.0;
+                // entry g + lane of the chunk is entry g + lane - lfirst of its list: plane j of the list's [nt][len] block
+                double* out = a.scores + (int64_t)t.nt * sg.lfirst + (g + lane - sg.lfirst);
+#pragma unroll
+                for (int j = 0; j < TAU_GROUP; ++j)   // (unrolled: taus[j] is a scalar load, j < nt a scalar compare)
+                    if (j < t.nt) out[j * sg.len] = blend_score(t.taus[j], c, lqv, lam);
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------ selection
 // Key of an entry: 96 bits, hi = the score's bits mapped so that a larger score is a larger number (sel_ord of as_common.hpp:
 // NaN lowest, -0 as +0), lo = ~id: among equal scores the smaller index is the larger key, whatever the caller's
@@ -170,26 +296,31 @@ struct ListsSelArgs {
     int64_t* out_len;    // pinned [nb]
     int64_t* out_idx;    // pinned [nb][kk]
     double* out_score;
+    int nt;              // PLANES: tau planes per list; the blocks are the (list, plane) pairs, results pinned [nb * nt](kk)
 };
 
 // One block per list, any length.  A list of more than LSEL_CAP entries: the digits of the k-th largest key T are found most
 // significant first, each pass a histogram in LDS of the entries that agree with T's digits so far; the passes stop as soon as
 // the entries at or above T's prefix (T's unknown digits zero) number at most LSEL_CAP -- after the last pass exactly k do.
 // Then (every list) the entries with key >= T are collected in LDS and ranked; the first k go to the pinned result.
+// PLANES (the tau sweep, section 5.13): block p serves plane p % nt of list p / nt: the scores are that plane of the list's
+// [nt][len] block (lists_score_taus_kernel), the ids the list's, shared by its planes.
+template <bool PLANES>
 __global__ __launch_bounds__(LSEL_NT) void lists_select_kernel(ListsSelArgs a) {
     __shared__ unsigned int hist[LSEL_BINS];
     __shared__ unsigned long long sk[LSEL_CAP];
     __shared__ int32_t sid[LSEL_CAP], spos[LSEL_CAP];
     __shared__ unsigned int wtot[LSEL_NT / 64], r_dg, r_krem, r_cnt, s_n;
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    const ListsList L = a.lists[blockIdx.x];
+    const int64_t li = PLANES ? (int64_t)blockIdx.x / a.nt : (int64_t)blockIdx.x;
+    const ListsList L = a.lists[li];
     const int64_t m = L.len;
     if (m <= 0) {   // (uniform)
         if (t == 0) a.out_len[blockIdx.x] = 0;
         return;
     }
     const unsigned int k = (unsigned int)min(a.kk, m);
-    const double* __restrict__ sc = a.scores + L.first;
+    const double* __restrict__ sc = PLANES ? a.scores + a.nt * L.first + ((int64_t)blockIdx.x - li * a.nt) * m : a.scores + L.first;
     const int32_t* __restrict__ id = a.ids + L.first;
     unsigned long long t_hi = 0ull;
     unsigned int t_lo = 0u;
@@ -481,8 +612,8 @@ as_status lists_run(const as_space* sp, const int32_t* ids, const int64_t* offs,
             if (sel) {
                 ListsSelArgs s;
                 s.lists = (const ListsList*)(w->up_d + list_off); s.scores = w->scores; s.ids = a.ids; s.kk = kk;
-                s.out_len = w->out_len; s.out_idx = w->out_idx; s.out_score = w->out_score;
-                hipLaunchKernelGGL(lists_select_kernel, dim3((unsigned)nb), dim3(LSEL_NT), 0, w->stream, s);
+                s.out_len = w->out_len; s.out_idx = w->out_idx; s.out_score = w->out_score; s.nt = 1;
+                hipLaunchKernelGGL(lists_select_kernel<false>, dim3((unsigned)nb), dim3(LSEL_NT), 0, w->stream, s);
                 AS_HIP(hipGetLastError());
             } else {
                 // one copy per run of served queries: the scores of a query that is not served stay unwritten
@@ -520,6 +651,170 @@ as_status lists_run(const as_space* sp, const int32_t* ids, const int64_t* offs,
                     }
                     out_len[i] = want;
                 }
+        }
+        i0 = i1;
+    }
+    return AS_OK;
+}
+
+// The tau sweep (section 5.13): lists_run's chunks with ONE upload per chunk for all its tau groups, then per group of tg <= TAU_GROUP
+// taus one gather (lists_score_taus_kernel) into the chunk's [list][tg][len] planes and either one selection block per (list,
+// tau) pair or the copies out; one stream wait per (chunk, group).  tg of a chunk is the largest that fits the budget for the
+// chunk's first list (a longer list further on ends the chunk), so a list too long for the budget is alone at tg = 1.
+as_status lists_run_taus(const as_space* sp, const int32_t* ids, const int64_t* offs, const double* queries, int64_t b, const double* lq,
+                         const int32_t* status, const double* taus, int64_t nt, const int64_t* row, int64_t ntau, int64_t kk, int64_t* out_idx,
+                         double* out_score, int64_t* out_len, double* out_scores, int64_t* counts) {
+    const bool sel = kk > 0;
+    if (sel)
+        for (int64_t p = 0; p < b * ntau; ++p) out_len[p] = 0;
+    if (b <= 0 || nt <= 0 || offs[b] == 0) return AS_OK;
+    if (!sp->lists_ws) AS_TRY(lists_work_create(sp, &sp->lists_ws));
+    ListsWork* w = sp->lists_ws;
+    const int64_t d = sp->d, dp = sp->dp;
+    const int64_t budget = std::max<int64_t>(((int64_t)g_lists_budget_mib.load(std::memory_order_relaxed) << 20) / (int64_t)sizeof(double), 1);
+    const bool timing = g_lists_timing.load(std::memory_order_relaxed) != 0;
+    const bool qlds = dp <= LISTS_Q_LDS;
+    const size_t lds = qlds ? sizeof(double) * (size_t)dp : 0;
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    w->kernel_us = 0.0;
+    for (int64_t i0 = 0; i0 < b;) {
+        const int64_t m0 = std::max<int64_t>(offs[i0 + 1] - offs[i0], 1);
+        const int64_t tg = std::max<int64_t>(std::min<int64_t>(std::min<int64_t>(nt, TAU_GROUP), budget / m0), 1);
+        int64_t i1 = i0, ne = 0;
+        while (i1 < b && (i1 - i0 + 1) * tg <= LISTS_QC_MAX) {
+            const int64_t m = offs[i1 + 1] - offs[i1];
+            if (i1 > i0 && (ne + m) * tg > budget) break;
+            ne += m;
+            ++i1;
+        }
+        const int64_t nb = i1 - i0, base = offs[i0];
+        if (ne == 0) {   // empty lists only
+            i0 = i1;
+            continue;
+        }
+        const auto t0 = now();
+        const int64_t nseg_max = ne / LISTS_R + nb;
+        const size_t q_bytes = sizeof(double) * (size_t)(nb * (dp + 2));
+        const size_t seg_off = q_bytes, list_off = seg_off + sizeof(ListsTausSeg) * (size_t)nseg_max;
+        const size_t ids_off = list_off + sizeof(ListsList) * (size_t)nb, up = ids_off + sizeof(int32_t) * (size_t)ne;
+        AS_TRY(lists_reserve(w, up, ne * tg, nb * tg, kk));
+        double* hq = (double*)w->up_h;
+        double* hn = hq + nb * dp;
+        double* hl = hn + nb;
+        ListsTausSeg* hseg = (ListsTausSeg*)(w->up_h + seg_off);
+        ListsList* hlist = (ListsList*)(w->up_h + list_off);
+        int64_t nseg = 0, pairs = 0;
+        for (int64_t t = 0; t < nb; ++t) {
+            const int64_t i = i0 + t, first = offs[i] - base, m = offs[i + 1] - offs[i];
+            const double* q = queries + i * d;
+            double* qrow = hq + t * dp;
+            for (int64_t c = 0; c < d; ++c) qrow[c] = q[c];
+            for (int64_t c = d; c < dp; ++c) qrow[c] = 0.0;
+            hn[t] = host_sumsq(q, d);
+            hl[t] = lq[i];
+            const bool served = status[i] != AS_EZEROLAMBDA;
+            hlist[t].first = first;
+            hlist[t].len = served ? m : 0;
+            if (!served) continue;
+            pairs += m;
+            const int64_t ns = (m + LISTS_R - 1) / LISTS_R;   // (lists_run's segments)
+            for (int64_t u = 0, o = 0; u < ns; ++u) {
+                const int64_t cnt = m / ns + (u < m % ns ? 1 : 0);
+                hseg[nseg].first = first + o;
+                hseg[nseg].lfirst = first;
+                hseg[nseg].len = m;
+                hseg[nseg].query = (int32_t)t;
+                hseg[nseg].count = (int32_t)cnt;
+                ++nseg;
+                o += cnt;
+            }
+        }
+        memcpy(w->up_h + ids_off, ids + base, sizeof(int32_t) * (size_t)ne);
+        counts[3] += std::chrono::duration_cast<std::chrono::nanoseconds>(now() - t0).count();
+        if (nseg > 0) {
+            AS_HIP(hipMemcpyAsync(w->up_d, w->up_h, up, hipMemcpyHostToDevice, w->stream));
+            ListsTausArgs a;
+            a.s.segs = nullptr; a.s.nseg = nseg; a.s.ids = (const int32_t*)(w->up_d + ids_off);
+            a.s.x32 = sp->x32; a.s.x64 = sp->x64; a.s.n64 = sp->n64; a.s.lam64 = sp->lam64; a.s.q64 = (const double*)w->up_d;
+            a.s.nq = a.s.q64 + nb * dp; a.s.lq = a.s.nq + nb; a.s.scores = w->scores; a.s.d = d; a.s.dp = dp; a.s.tau = 0.0;
+            a.segs = (const ListsTausSeg*)(w->up_d + seg_off);
+            const unsigned grid = (unsigned)std::min<int64_t>(nseg, (int64_t)w->cus * LISTS_BLOCKS_PER_CU);
+            for (int64_t u0 = 0; u0 < nt; u0 += tg) {
+                const int64_t g = std::min<int64_t>(tg, nt - u0);   // taus of this group: planes of every list's block
+                a.nt = (int)g;
+                for (int64_t j = 0; j < TAU_GROUP; ++j) a.taus[j] = j < g ? taus[u0 + j] : 0.0;
+                if (timing) AS_HIP(hipEventRecord(w->ev[0], w->stream));
+                if (sp->x64) {
+                    if (qlds) hipLaunchKernelGGL((lists_score_taus_kernel<true, true>), dim3(grid), dim3(256), lds, w->stream, a);
+                    else hipLaunchKernelGGL((lists_score_taus_kernel<true, false>), dim3(grid), dim3(256), 0, w->stream, a);
+                } else {
+                    if (qlds) hipLaunchKernelGGL((lists_score_taus_kernel<false, true>), dim3(grid), dim3(256), lds, w->stream, a);
+                    else hipLaunchKernelGGL((lists_score_taus_kernel<false, false>), dim3(grid), dim3(256), 0, w->stream, a);
+                }
+                AS_HIP(hipGetLastError());
+                if (timing) AS_HIP(hipEventRecord(w->ev[1], w->stream));
+                counts[0] += 1;
+                counts[1] += pairs;
+                counts[2] += pairs * g;
+                if (sel) {
+                    ListsSelArgs s;
+                    s.lists = (const ListsList*)(w->up_d + list_off); s.scores = w->scores; s.ids = a.s.ids; s.kk = kk;
+                    s.out_len = w->out_len; s.out_idx = w->out_idx; s.out_score = w->out_score; s.nt = (int)g;
+                    hipLaunchKernelGGL(lists_select_kernel<true>, dim3((unsigned)(nb * g)), dim3(LSEL_NT), 0, w->stream, s);
+                    AS_HIP(hipGetLastError());
+                } else if (g == ntau) {
+                    // one group, no repeated tau: the device layout is the output's; one copy per run of served queries
+                    for (int64_t t = 0; t < nb;) {
+                        if (status[i0 + t] == AS_EZEROLAMBDA) {
+                            ++t;
+                            continue;
+                        }
+                        int64_t u = t;
+                        while (u < nb && status[i0 + u] != AS_EZEROLAMBDA) ++u;
+                        const int64_t e0 = offs[i0 + t] - base, e1 = offs[i0 + u] - base;
+                        if (e1 > e0)
+                            AS_HIP(hipMemcpyAsync(out_scores + ntau * (base + e0), w->scores + g * e0, sizeof(double) * (size_t)((e1 - e0) * g),
+                                                  hipMemcpyDeviceToHost, w->stream));
+                        t = u;
+                    }
+                } else {
+                    // per served query, one copy per run of planes whose output rows are consecutive
+                    for (int64_t t = 0; t < nb; ++t) {
+                        const int64_t m = hlist[t].len, first = hlist[t].first;
+                        if (m == 0) continue;
+                        for (int64_t j = 0; j < g;) {
+                            int64_t j1 = j + 1;
+                            while (j1 < g && row[u0 + j1] == row[u0 + j1 - 1] + 1) ++j1;
+                            AS_HIP(hipMemcpyAsync(out_scores + ntau * (base + first) + row[u0 + j] * m, w->scores + g * first + j * m,
+                                                  sizeof(double) * (size_t)((j1 - j) * m), hipMemcpyDeviceToHost, w->stream));
+                            j = j1;
+                        }
+                    }
+                }
+                AS_HIP(hipStreamSynchronize(w->stream));
+                if (timing) {
+                    float ms = 0.0f;
+                    AS_HIP(hipEventElapsedTime(&ms, w->ev[0], w->ev[1]));
+                    w->kernel_us += (double)ms * 1e3;
+                }
+                if (sel)
+                    for (int64_t t = 0; t < nb; ++t) {
+                        const int64_t i = i0 + t, want = std::min<int64_t>(kk, hlist[t].len);
+                        for (int64_t j = 0; j < g; ++j) {
+                            const int64_t p = t * g + j, o = i * ntau + row[u0 + j];
+                            if (w->out_len[p] != want) {
+                                set_err("lists: the selection returned %lld of %lld entries for query %lld, tau %lld", (long long)w->out_len[p],
+                                        (long long)want, (long long)i, (long long)row[u0 + j]);
+                                return AS_EHIP;
+                            }
+                            for (int64_t r = 0; r < want; ++r) {
+                                out_idx[o * kk + r] = w->out_idx[p * kk + r];
+                                out_score[o * kk + r] = w->out_score[p * kk + r];
+                            }
+                            out_len[o] = want;
+                        }
+                    }
+            }
         }
         i0 = i1;
     }
