@@ -474,6 +474,8 @@ void as_enable_search_stats(int32_t enabled);
  * workspace; any other value: each workspace's own switch again (ARROWSPACE_X1_FINAL_RANK when it was made; default 1).
  * "subset_batch_mib" = MiB of scores one chunk of queries of the batched filtered forms may hold (default 256; <= 0: the default);
  * the per-query list forms chunk by it too.  "lists_timing" = 1 / 0: HIP events around their score kernel (as_lists_kernel_us).
+ * "range_cap" = entries of the append buffer a range call starts with (default 65 536, or what earlier overflows grew the buffer
+ * to; <= 0: the default); "range_timing" = 1 / 0: HIP events around the range forms' compaction kernel (as_range_kernel_us).
  * Returns 0, or 1 for an unknown key.  Results never depend on it. */
 int32_t as_set_tuning(const char* key, int32_t value);
 /* same, for the workspace as_search keeps inside the space (last as_search call) */
@@ -641,6 +643,44 @@ as_status as_search_lists_batch_taus(const as_space* sp, const as_graph* gr, con
  * (measurement) host nanoseconds spent on id checks, deduplication and work tables.  as_lists_counters counts the single-tau forms
  * only. */
 as_status as_lists_sweep_counters(const as_space* sp, int64_t* out, int32_t n);
+/* ---- Extension: range search.  EVERY item of a subset (sub == NULL: every item of the space) whose S11 score is >= min_score, by
+ * (score descending, index ascending; +0.0 and -0.0 tie), not cut at topk; a NaN score never qualifies; min_score may be -inf
+ * (every item whose score is not NaN) or +inf.  The size of the answer is not known before the call, so it comes back as a handle
+ * in HOST memory (as_range), independent of the space's lifetime, freed by the caller with as_range_free; count_only != 0: the
+ * lists' lengths alone (as_range_offsets; as_range_copy -> AS_EINVAL).  As for the other filtered forms the subset restricts the
+ * answer, not the index.  as_search_range: the score of item i has the bits as_score_items returns for it, compared with an IEEE
+ * >= in fp64.  as_search_range_batch: b queries, row-major [b][d] in HOST memory, one threshold per query; list i has
+ * as_score_items_batch's bits (within 1e-12 relative of the single form's: membership differs from it only for scores that close
+ * to the threshold).  Checked before anything is launched: a null argument ("<name>: null argument", *out left NULL), a NaN
+ * threshold, a subset of another space, wrong d, a non-finite tau -> AS_EINVAL; a shard of a row-sharded index -> AS_EUNSUPPORTED.
+ * Cost: ONE ORDINARY as_search (batched: ONE as_search_batch over all b queries) for lambda_q, hits discarded: the same escalation
+ * and the same AS_EZEROLAMBDA whatever the subset and the threshold (batched: in out_status[i], that query gets an empty list, the
+ * others are served); then the filtered forms' gather of the subset's rows (batched: once per 64 queries, in chunks of queries
+ * under the "subset_batch_mib" budget) and ONE compaction kernel per call (per chunk) that reads the scores once and appends a
+ * 16-byte entry per survivor to one buffer: only survivors cross to the host, where each list is sorted (std::sort: the cost
+ * grows with the answer -- min_score = -inf over a million items is legal and slow).  If the survivors exceed the buffer (65 536
+ * entries at first, grown on demand) the compaction alone is run again, never the gather; count_only never runs it twice.  An
+ * empty subset still runs the lambda_q step; b == 0 launches nothing and returns an answer of 0 lists.  sub == NULL: the space
+ * makes a subset of all items on first use and keeps it (4 bytes per item, plus the scores).  The buffers live in the subset
+ * handle (sub == NULL: in the space) and grow on demand; calls are serialised with as_search_subset on that handle, as_search runs
+ * beside them.  out_lambda_q and out_status may be NULL. */
+typedef struct as_range as_range;
+as_status as_search_range(const as_space* sp, const as_graph* gr, const double* query, int64_t d, double tau, double min_score,
+                          const as_subset* sub, int32_t count_only, as_range** out, double* out_lambda_q);
+as_status as_search_range_batch(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau,
+                                const double* min_scores, const as_subset* sub, int32_t count_only, as_range** out,
+                                double* out_lambda_q, int32_t* out_status);
+int64_t as_range_queries(const as_range* r);                  /* lists: 1, or b; 0 for NULL */
+int64_t as_range_total(const as_range* r);                    /* survivors over all lists; 0 for NULL */
+as_status as_range_offsets(const as_range* r, int64_t* out);  /* as_range_queries + 1 entries: list i is [out[i], out[i + 1]) */
+as_status as_range_copy(const as_range* r, int64_t* out_idx, double* out_score);  /* as_range_total entries; AS_EINVAL after count_only */
+void as_range_free(as_range* r);                              /* NULL: no-op */
+/* out[0] calls of the two entries above that passed their checks, [1] compaction launches, [2] scores examined, [3] survivors
+ * returned (count_only: counted), [4] compaction relaunches after the append buffer overflowed, [5] lambda_q steps run */
+as_status as_range_counters(const as_space* sp, int64_t* out, int32_t n);
+/* measurement: the device microseconds of the compaction kernel, summed over the launches of the last range call on this space
+ * that ran under as_set_tuning("range_timing", 1) (HIP events around the kernel; off by default) */
+double as_range_kernel_us(const as_space* sp);
 
 /* ---- index persistence (extension; the reference exposes none): one flat file
  * holding the items, lambdas and graph arrays.  Loading re-ingests the items and uploads the

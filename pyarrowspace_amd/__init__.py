@@ -202,6 +202,25 @@ def _item_ids(ids_or_mask, nitems: int, what: str = "ids") -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.int64)
 
 
+def _min_scores(min_score, b: int) -> np.ndarray:
+    """The thresholds of a range search as a contiguous float64 array of b entries: a number for every query, or a 1-D
+    sequence of b numbers.  -inf and +inf are legal.  NaN, a wrong length or a wrong rank raise ValueError, anything that
+    is not a number TypeError."""
+    a = np.asarray(min_score)
+    if a.dtype.kind not in "fiu":
+        raise TypeError(f"argument 'min_score': expected a float or a sequence of floats, got dtype {a.dtype}")
+    a = a.astype(np.float64)
+    if a.ndim == 0:
+        a = np.full(b, float(a), dtype=np.float64)
+    elif a.ndim != 1:
+        raise ValueError(f"argument 'min_score': expected a float or a 1-D sequence of {b} floats, got shape {a.shape}")
+    elif a.shape[0] != b:
+        raise ValueError(f"argument 'min_score': {a.shape[0]} thresholds for {b} queries")
+    if np.isnan(a).any():
+        raise ValueError("argument 'min_score': a threshold must not be NaN")
+    return np.ascontiguousarray(a)
+
+
 def _id_lists(lists, nitems: int) -> tuple[np.ndarray, np.ndarray]:
     """B id lists as (ids int64 flat, offsets int64 [B + 1]): a 2-D integer array (B, C) is B lists of C ids; any other
     sequence holds one entry per list, each whatever `_item_ids` accepts (integer ids in any order, duplicates kept, or a
@@ -500,6 +519,109 @@ class ArrowSpace:
         if (stt[:b] == _lib.AS_EZEROLAMBDA).any():
             raise PanicException("The lambdas are zero, check the magnitude of items and eps.")
         return out
+
+    def _range_single(self, item, gl, tau, min_score, subset, count_only):
+        if not isinstance(gl, GraphLaplacian):
+            raise TypeError("argument 'gl': expected GraphLaplacian")
+        q = self._query(item)
+        if np.ndim(min_score) != 0:
+            raise ValueError("argument 'min_score': expected one float")
+        thr = float(_min_scores(min_score, 1)[0])
+        sub = subset if subset is None or isinstance(subset, ItemSubset) else self.subset(subset)
+        h, lq = C.c_void_p(), C.c_double(0.0)
+        st = _L.as_search_range(self._h, gl._h, q.ctypes.data, q.shape[0], float(tau), thr, None if sub is None else sub._h,
+                                1 if count_only else 0, C.byref(h), C.byref(lq))
+        if st:
+            _raise(st)
+        try:
+            n = int(_L.as_range_total(h))
+            if count_only:
+                return n
+            idx = np.empty(max(n, 1), dtype=np.int64)
+            sc = np.empty(max(n, 1), dtype=np.float64)
+            st = _L.as_range_copy(h, idx.ctypes.data, sc.ctypes.data)
+            if st:
+                _raise(st)
+            return list(zip(idx[:n].tolist(), sc[:n].tolist()))
+        finally:
+            _L.as_range_free(h)
+
+    def _range_batch(self, items, gl, tau, min_score, subset, count_only):
+        if not isinstance(gl, GraphLaplacian):
+            raise TypeError("argument 'gl': expected GraphLaplacian")
+        Q = np.ascontiguousarray(items, dtype=np.float64)
+        if Q.ndim != 2:
+            raise TypeError("items must be a 2-D float64 array")
+        b = Q.shape[0]
+        thr = _min_scores(min_score, b)
+        sub = subset if subset is None or isinstance(subset, ItemSubset) else self.subset(subset)
+        h = C.c_void_p()
+        stt = np.zeros(max(b, 1), dtype=np.int32)
+        st = _L.as_search_range_batch(self._h, gl._h, Q.ctypes.data_as(C.c_void_p), b, Q.shape[1], float(tau),
+                                      thr.ctypes.data_as(C.c_void_p), None if sub is None else sub._h, 1 if count_only else 0,
+                                      C.byref(h), None, stt.ctypes.data_as(C.c_void_p))
+        if st:
+            _raise(st)
+        try:
+            if (stt[:b] == _lib.AS_EZEROLAMBDA).any():
+                raise PanicException("The lambdas are zero, check the magnitude of items and eps.")
+            offs = np.zeros(b + 1, dtype=np.int64)
+            st = _L.as_range_offsets(h, offs.ctypes.data)
+            if st:
+                _raise(st)
+            if count_only:
+                return np.diff(offs)
+            n = int(offs[b])
+            idx = np.empty(max(n, 1), dtype=np.int64)
+            sc = np.empty(max(n, 1), dtype=np.float64)
+            st = _L.as_range_copy(h, idx.ctypes.data, sc.ctypes.data)
+            if st:
+                _raise(st)
+            idx, sc, o = idx.tolist(), sc.tolist(), offs.tolist()
+            return [list(zip(idx[o[i]:o[i + 1]], sc[o[i]:o[i + 1]])) for i in range(b)]
+        finally:
+            _L.as_range_free(h)
+
+    def search_range(self, item, gl: GraphLaplacian, tau: float, min_score: float, subset=None):
+        """Extension: range search -> list[(index, score)]: EVERY item of the subset whose score is >= `min_score`, by (score
+        descending, index ascending), not cut at topk; a NaN score never qualifies, `min_score` may be -inf or +inf (NaN
+        raises ValueError).  `subset`: None (every item), an `ItemSubset` of this space or anything `subset()` accepts.  The
+        filter restricts the answer, not the index, as in `search_subset`; the score of item i has the bits
+        `score_items(item, gl, tau, [i])` returns.  Costs one ordinary `search` (lambda_q comes from it; a query whose lambda_q
+        is 0 panics as there, whatever the subset and the threshold) plus a gather of the subset's rows and one compaction
+        pass over the scores on the device: only the survivors cross to the host, where they are sorted -- an answer of a
+        million items is legal and slow."""
+        return self._range_single(item, gl, tau, min_score, subset, False)
+
+    def count_range(self, item, gl: GraphLaplacian, tau: float, min_score: float, subset=None) -> int:
+        """Extension: the length of `search_range(item, gl, tau, min_score, subset)` without the list.  Costs one ordinary
+        `search` (lambda_q) plus a gather of the subset's rows and one counting pass over the scores on the device; one
+        number per query crosses to the host."""
+        return self._range_single(item, gl, tau, min_score, subset, True)
+
+    def search_range_batch(self, items, gl: GraphLaplacian, tau: float, min_score, subset=None):
+        """Extension: batched range search, B queries [B, D] against one subset -> list of B lists; list i is what
+        `search_range(items[i], gl, tau, min_score[i], subset)` returns with the score bits of `score_items_batch` (within
+        1e-12 relative of the single form's: the batched kernel sums in another order; membership differs only for scores
+        that close to the threshold).  `min_score`: one float for every query or a sequence of B floats.  Costs one
+        `search_batch` over the B queries (lambda_q comes from it; any query whose lambda_q is 0 panics as there, whatever the
+        subset), then the subset's rows are gathered once per 64 queries for an fp64 matrix product on the device and one
+        compaction pass per chunk of queries keeps the survivors."""
+        return self._range_batch(items, gl, tau, min_score, subset, False)
+
+    def count_range_batch(self, items, gl: GraphLaplacian, tau: float, min_score, subset=None) -> np.ndarray:
+        """Extension: ndarray[int64] of B: the lengths of `search_range_batch(items, gl, tau, min_score, subset)`'s lists.
+        Costs one `search_batch` over the B queries (lambda_q) plus one gather of the subset's rows per 64 queries and one
+        counting pass per chunk of queries."""
+        return self._range_batch(items, gl, tau, min_score, subset, True)
+
+    def range_counters(self) -> dict:
+        """Extension: range calls on this space since it was made, the work they launched and what they returned."""
+        out = (C.c_int64 * 6)()
+        st = _L.as_range_counters(self._h, out, 6)
+        if st:
+            _raise(st)
+        return dict(zip(("calls", "compactions", "scores_examined", "survivors", "relaunches", "lambda_steps"), list(out)))
 
     def _lists_args(self, items, gl, lists):
         if not isinstance(gl, GraphLaplacian):

@@ -56,6 +56,8 @@ SYMBOLS = [
     "as_search_subset_taus", "as_score_items_taus", "as_search_subset_batch_taus", "as_score_items_batch_taus", "as_subset_sweep_counters",
     "as_score_lists_batch", "as_search_lists_batch", "as_lists_counters", "as_lists_kernel_us",
     "as_score_lists_batch_taus", "as_search_lists_batch_taus", "as_lists_sweep_counters",
+    "as_search_range", "as_search_range_batch", "as_range_queries", "as_range_total", "as_range_offsets", "as_range_copy", "as_range_free",
+    "as_range_counters", "as_range_kernel_us",
 ]
 
 _lib = None
@@ -228,6 +230,15 @@ def load():
         "as_score_lists_batch_taus": (i32, [vp, vp, vp, i64, i64, vp, i64, vp, vp, vp, vp, vp]),
         "as_search_lists_batch_taus": (i32, [vp, vp, vp, i64, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
         "as_lists_sweep_counters": (i32, [vp, vp, i32]),
+        "as_search_range": (i32, [vp, vp, vp, i64, f64, f64, vp, i32, pvp, C.POINTER(f64)]),
+        "as_search_range_batch": (i32, [vp, vp, vp, i64, i64, f64, vp, vp, i32, pvp, vp, vp]),
+        "as_range_queries": (i64, [vp]),
+        "as_range_total": (i64, [vp]),
+        "as_range_offsets": (i32, [vp, vp]),
+        "as_range_copy": (i32, [vp, vp, vp]),
+        "as_range_free": (None, [vp]),
+        "as_range_counters": (i32, [vp, vp, i32]),
+        "as_range_kernel_us": (f64, [vp]),
         "as_subset_set_timing": (None, [vp, i32]),
         "as_subset_kernel_us": (f64, [vp]),
         "as_gang_counters": (i32, [vp, vp, i32]),

@@ -154,6 +154,7 @@ void as_free_space(as_space* sp) {
     if (sp->qcache_b3) as_query_free(sp->qcache_b3);
     if (sp->qcache_b4) as_query_free(sp->qcache_b4);
     subset_work_free(sp->score_ws);
+    as_subset_free(sp->range_all);
     lists_work_free(sp->lists_ws);
     if (sp->stream) hipStreamSynchronize(sp->stream);
     hipFree(sp->x32); hipFree(sp->xs); hipFree(sp->x8); hipFree(sp->x8h); hipFree(sp->x4); hipFree(sp->fa4); hipFree(sp->fa8); hipFree(sp->x64); hipFree(sp->n64); hipFree(sp->n32); hipFree(sp->inorm32);
@@ -1339,6 +1340,234 @@ as_status as_score_items_batch(const as_space* sp, const as_graph* gr, const dou
     AS_TRY(score_ws_ids(sp, ids.data(), m));
     return subset_batch_run(sp, sp->score_ws, m, queries, b, lq.data(), st.data(), tau, 0, 0, nullptr, nullptr, nullptr, out_scores);
 }
+
+// ---------------------------------------------------------------- range search (extension; as_range.hip)
+// the subset a range call runs on: the caller's, or the space's own subset of all items (made on first use, kept)
+static as_status range_subset(const as_space* sp, const as_subset* sub, const as_subset** out) {
+    *out = sub;
+    if (sub) return AS_OK;
+    std::lock_guard<std::mutex> lk(sp->rmu);
+    if (!sp->range_all) {
+        AS_HIP(hipSetDevice(sp->device));
+        std::vector<int32_t> ids;
+        as_subset* all = nullptr;
+        try {
+            ids.resize((size_t)sp->n);
+            all = new as_subset();
+        } catch (const std::bad_alloc&) {
+            set_err("range: out of host memory for %lld ids", (long long)sp->n);
+            return AS_ENOMEM;
+        }
+        for (int64_t i = 0; i < sp->n; ++i) ids[(size_t)i] = (int32_t)i;
+        all->sp = sp;
+        all->m = sp->n;
+        as_status s = subset_work_create(sp, all->m, &all->w);
+        if (s == AS_OK) s = subset_set_ids(all->w, ids.data(), all->m);
+        if (s != AS_OK) {
+            as_subset_free(all);
+            return s;
+        }
+        sp->range_all = all;
+    }
+    *out = sp->range_all;
+    return AS_OK;
+}
+static as_range* range_new(bool count_only) {
+    as_range* r = new (std::nothrow) as_range();
+    if (!r) {
+        set_err("range: out of host memory");
+        return nullptr;
+    }
+    try {
+        r->offs.push_back(0);
+    } catch (const std::bad_alloc&) {
+        delete r;
+        set_err("range: out of host memory");
+        return nullptr;
+    }
+    r->count_only = count_only;
+    return r;
+}
+// `n` empty lists behind those the answer holds
+static as_status range_pad(as_range* r, int64_t n) {
+    try {
+        r->offs.resize(r->offs.size() + (size_t)n, r->offs.back());
+    } catch (const std::bad_alloc&) {
+        set_err("range: out of host memory for the answer");
+        return AS_ENOMEM;
+    }
+    r->nq += n;
+    return AS_OK;
+}
+static void range_counts_add(const as_space* sp, const int64_t* counts, double us) {
+    for (int i = 0; i < 4; ++i) sp->range_count[1 + i].fetch_add(counts[i], std::memory_order_relaxed);
+    sp->range_us.store(us, std::memory_order_relaxed);
+}
+
+as_status as_search_range(const as_space* sp, const as_graph* gr, const double* query, int64_t d, double tau, double min_score,
+                          const as_subset* sub, int32_t count_only, as_range** out, double* out_lambda_q) {
+    if (out) *out = nullptr;
+    if (!sp || !gr || !query || !out) {
+        set_err("as_search_range: null argument");
+        return AS_EINVAL;
+    }
+    if (min_score != min_score) {
+        set_err("as_search_range: min_score must not be NaN");
+        return AS_EINVAL;
+    }
+    if (sub && sub->sp != sp) {
+        set_err("as_search_range: the subset was made for another space");
+        return AS_EINVAL;
+    }
+    AS_TRY(subset_checks("as_search_range", sp, gr, d, &tau, 1));
+    sp->range_count[0].fetch_add(1, std::memory_order_relaxed);
+    double lq = 0.0;
+    {
+        int64_t hidx[SUBSET_TOPK], hlen = 0;
+        double hsc[SUBSET_TOPK];
+        sp->range_count[5].fetch_add(1, std::memory_order_relaxed);
+        const as_status s = search_pooled(sp, gr, query, d, tau, hidx, hsc, &hlen, &lq);
+        if (out_lambda_q) *out_lambda_q = lq;
+        if (s != AS_OK) return s;
+    }
+    as_range* res = range_new(count_only != 0);
+    if (!res) return AS_ENOMEM;
+    as_status s = AS_OK;
+    const as_subset* on = nullptr;
+    if (sub && sub->m == 0) s = range_pad(res, 1);
+    else if ((s = range_subset(sp, sub, &on)) == AS_OK) {
+        int64_t counts[4] = {0, 0, 0, 0};
+        double us = 0.0;
+        std::lock_guard<std::mutex> lk(on->mu);
+        s = subset_score(sp, on->w, on->m, query, tau, lq);
+        if (s == AS_OK) s = range_compact(on->w, on->w->scores, on->m, on->m, 1, &min_score, count_only != 0, on->ids, res, counts, &us);
+        else (void)hipStreamSynchronize(on->w->stream);
+        range_counts_add(sp, counts, us);
+    }
+    if (s != AS_OK) {
+        delete res;
+        return s;
+    }
+    *out = res;
+    return AS_OK;
+}
+
+namespace {
+struct RangeSink {
+    const as_subset* on;
+    const double* thr;   // [b]: NaN for a query without an answer
+    bool count_only;
+    as_range* res;
+    int64_t counts[4];
+    double us;
+};
+as_status range_sink_chunk(void* ctx, SubsetWork* w, int64_t i0, int64_t nb, const double* scores, int64_t ld) {
+    RangeSink* k = (RangeSink*)ctx;
+    return range_compact(w, scores, ld, k->on->m, nb, k->thr + i0, k->count_only, k->on->ids, k->res, k->counts, &k->us);
+}
+}  // namespace
+
+as_status as_search_range_batch(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau,
+                                const double* min_scores, const as_subset* sub, int32_t count_only, as_range** out, double* out_lambda_q,
+                                int32_t* out_status) {
+    if (out) *out = nullptr;
+    if (!sp || !gr || !out || b < 0 || (b > 0 && (!queries || !min_scores))) {
+        set_err("as_search_range_batch: null argument");
+        return AS_EINVAL;
+    }
+    for (int64_t i = 0; i < b; ++i)
+        if (min_scores[i] != min_scores[i]) {
+            set_err("as_search_range_batch: min_scores[%lld] must not be NaN", (long long)i);
+            return AS_EINVAL;
+        }
+    if (sub && sub->sp != sp) {
+        set_err("as_search_range_batch: the subset was made for another space");
+        return AS_EINVAL;
+    }
+    AS_TRY(subset_checks("as_search_range_batch", sp, gr, d, &tau, 1));
+    sp->range_count[0].fetch_add(1, std::memory_order_relaxed);
+    as_range* res = range_new(count_only != 0);
+    if (!res) return AS_ENOMEM;
+    if (b == 0) {
+        *out = res;
+        return AS_OK;
+    }
+    std::vector<double> lq, thr;
+    std::vector<int32_t> st;
+    sp->range_count[5].fetch_add(1, std::memory_order_relaxed);
+    as_status s = batch_lambda_step("as_search_range_batch", sp, gr, queries, b, d, tau, lq, st);
+    if (s == AS_OK) {
+        for (int64_t i = 0; i < b; ++i) {
+            if (out_lambda_q) out_lambda_q[i] = lq[i];
+            if (out_status) out_status[i] = st[i];
+        }
+        try {
+            thr.assign(min_scores, min_scores + b);
+        } catch (const std::bad_alloc&) {
+            set_err("as_search_range_batch: out of host memory for %lld queries", (long long)b);
+            s = AS_ENOMEM;
+        }
+    }
+    const as_subset* on = nullptr;
+    if (s == AS_OK) {
+        if (sub && sub->m == 0) s = range_pad(res, b);
+        else if ((s = range_subset(sp, sub, &on)) == AS_OK) {
+            // a zero-lambda query's row of a chunk holds no answer: against a NaN threshold nothing in it survives
+            for (int64_t i = 0; i < b; ++i)
+                if (st[i] == AS_EZEROLAMBDA) thr[i] = std::numeric_limits<double>::quiet_NaN();
+            RangeSink k{on, thr.data(), count_only != 0, res, {0, 0, 0, 0}, 0.0};
+            const SubsetChunkSink sink{range_sink_chunk, &k};
+            std::lock_guard<std::mutex> lk(on->mu);
+            s = hipSetDevice(sp->device) == hipSuccess ? AS_OK : AS_EHIP;
+            if (s != AS_OK) set_err("as_search_range_batch: hipSetDevice failed");
+            else s = subset_batch_run(sp, on->w, on->m, queries, b, lq.data(), st.data(), tau, 0, 0, nullptr, nullptr, nullptr, nullptr, &sink);
+            if (s != AS_OK) (void)hipStreamSynchronize(on->w->stream);
+            range_counts_add(sp, k.counts, k.us);
+        }
+    }
+    if (s != AS_OK) {
+        delete res;
+        return s;
+    }
+    *out = res;
+    return AS_OK;
+}
+
+int64_t as_range_queries(const as_range* r) { return r ? r->nq : 0; }
+int64_t as_range_total(const as_range* r) { return r ? r->offs.back() : 0; }
+as_status as_range_offsets(const as_range* r, int64_t* out) {
+    if (!r || !out) {
+        set_err("as_range_offsets: null argument");
+        return AS_EINVAL;
+    }
+    for (int64_t i = 0; i <= r->nq; ++i) out[i] = r->offs[(size_t)i];
+    return AS_OK;
+}
+as_status as_range_copy(const as_range* r, int64_t* out_idx, double* out_score) {
+    if (!r || (r->offs.back() > 0 && (!out_idx || !out_score))) {
+        set_err("as_range_copy: null argument");
+        return AS_EINVAL;
+    }
+    if (r->count_only) {
+        set_err("as_range_copy: the answer of a count_only call holds no entries");
+        return AS_EINVAL;
+    }
+    for (size_t e = 0; e < r->idx.size(); ++e) {
+        out_idx[e] = r->idx[e];
+        out_score[e] = r->score[e];
+    }
+    return AS_OK;
+}
+void as_range_free(as_range* r) { delete r; }
+as_status as_range_counters(const as_space* sp, int64_t* out, int32_t n) {
+    if (!sp || !out) {
+        set_err("as_range_counters: null argument");
+        return AS_EINVAL;
+    }
+    for (int i = 0; i < n && i < 6; ++i) out[i] = sp->range_count[i].load(std::memory_order_relaxed);
+    return AS_OK;
+}
+double as_range_kernel_us(const as_space* sp) { return sp ? sp->range_us.load(std::memory_order_relaxed) : 0.0; }
 
 // ---------------------------------------------------------------- per-query candidate lists (extension)
 // What both forms check before anything is launched, the lambda_q step included: the offsets, the total, every id.

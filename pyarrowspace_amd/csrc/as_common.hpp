@@ -11,6 +11,7 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <vector>
 
 #include "arrowspace_hip.h"
 
@@ -46,7 +47,8 @@ void dbg(const char* fmt, ...);
 
 }  // namespace as
 
-namespace as { struct SubsetWork; struct ListsWork; }
+namespace as { struct SubsetWork; struct ListsWork; struct RangeWork; }
+struct as_subset;
 
 // ---------------------------------------------------------------- handles
 // HBM layout: x32 is the scan/MFMA operand, [np][dp] fp32,
@@ -163,6 +165,15 @@ struct as_space {
     mutable std::atomic<int64_t> lsweep_count[6] = {};
     mutable int64_t unproven_searches = 0;   // searches returned although their a-posteriori check failed on the strongest path
     mutable double kstats[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // accumulated by as_knn_rows
+    // as_search_range / as_search_range_batch with sub == NULL: a subset of all items (no host id list: position == id), made on
+    // first use under rmu and kept (4 bytes per item on the device, plus the score buffer of the route); calls are serialised by
+    // its mutex.  as_range_counters: [0] calls that passed their checks, [1] compaction launches, [2] scores examined, [3]
+    // survivors returned, [4] compaction relaunches after the append buffer overflowed, [5] lambda_q steps run.  range_us: the
+    // compaction kernel of the last call under "range_timing" (as_range_kernel_us)
+    mutable as_subset* range_all = nullptr;
+    mutable std::mutex rmu;
+    mutable std::atomic<int64_t> range_count[6] = {};
+    mutable std::atomic<double> range_us{0.0};
 };
 
 struct as_graph {
@@ -207,9 +218,18 @@ inline int64_t graph_items(const as_graph* gr) {   // items the index covers
 struct as_subset {
     const as_space* sp = nullptr;
     int64_t m = 0;
-    int64_t* ids = nullptr;      // [m] host copy (as_subset_ids)
+    int64_t* ids = nullptr;      // [m] host copy (as_subset_ids); null in the space's own subset of all items (position == id)
     as::SubsetWork* w = nullptr;
     mutable std::mutex mu;       // calls on one handle are serialised
+};
+
+// the answer of a range query (as_search_range, as_search_range_batch): host memory only, independent of the space
+struct as_range {
+    int64_t nq = 0;                // lists
+    bool count_only = false;       // offsets only
+    std::vector<int64_t> offs;     // [nq + 1]
+    std::vector<int64_t> idx;      // [offs[nq]] item ids, each list by (score descending, id ascending)
+    std::vector<double> score;
 };
 
 // ---------------------------------------------------------------- device helpers
@@ -623,6 +643,8 @@ struct SubsetWork {
     SubsetSel* sw_state = nullptr;
     int32_t* sw_sel_pos = nullptr;
     SubsetOut* sw_out = nullptr;   // pinned [sw_out_n]
+    // range search (as_range.hip): the append buffer, its counters and the thresholds, made on the first range call on this work
+    RangeWork* range = nullptr;
 };
 as_status subset_work_create(const as_space* sp, int64_t cap, SubsetWork** out);
 void subset_work_free(SubsetWork* w);
@@ -632,10 +654,16 @@ as_status subset_select(SubsetWork* w, int64_t m, int64_t k, int64_t* out_idx, d
 as_status subset_scores_out(SubsetWork* w, int64_t m, double* out);
 // The batched forms over the m ids of `w`: b queries [b][d] with their lambda_q and status (AS_EZEROLAMBDA: no output for that
 // query), in chunks of queries on the work's stream, one wait per chunk.  k > 0: the first k of every query's scores ->
-// out_idx / out_score at stride `stride`, out_len; k == 0: all scores -> out_scores [b][m].
+// out_idx / out_score at stride `stride`, out_len; k == 0: all scores -> out_scores [b][m], or, with a sink, to the sink: it is
+// called once per chunk behind the score kernel with the chunk's scores ([nb][ld], still on the device, queued on the work's
+// stream; a zero-lambda query's row holds no answer) and waits for the stream itself.
+struct SubsetChunkSink {
+    as_status (*fn)(void* ctx, SubsetWork* w, int64_t i0, int64_t nb, const double* scores, int64_t ld);
+    void* ctx;
+};
 as_status subset_batch_run(const as_space* sp, SubsetWork* w, int64_t m, const double* queries, int64_t b, const double* lq,
                            const int32_t* status, double tau, int64_t k, int64_t stride, int64_t* out_idx, double* out_score,
-                           int64_t* out_len, double* out_scores);
+                           int64_t* out_len, double* out_scores, const SubsetChunkSink* sink = nullptr);
 void set_subset_batch_mib(int v);   // as_set_tuning("subset_batch_mib", v)
 constexpr int QUERY_BATCH = 32;  // == GQ in as_search.hip: query slots of the batched workspace
 constexpr int TAU_GROUP = 8;     // taus one shared pass of a tau sweep serves (search_sweep, as_search_taus; one gather of a subset)
@@ -669,5 +697,15 @@ void lists_work_free(ListsWork* w);
 double lists_kernel_us(const ListsWork* w);
 void set_lists_timing(int v);   // as_set_tuning("lists_timing", 0 | 1)
 void set_lists_budget_mib(int v);   // as_set_tuning("subset_batch_mib", v): the value set_subset_batch_mib gets
+// Range search (as_range.hip): the survivors of nq rows of m scores ([nq][ld] on the device, queued on the
+// work's stream) against one threshold per row (NaN: that row has no answer) are appended to `res` as nq further lists, each by
+// (score descending, id ascending); ids_host maps a position to its id (null: position == id).  count_only: the lists' lengths
+// alone.  Waits for the stream.  counts[0] += compaction launches, [1] += scores examined, [2] += survivors, [3] += relaunches
+// after an overflow of the append buffer; *us += the compaction kernel's microseconds under "range_timing".
+as_status range_compact(SubsetWork* w, const double* scores, int64_t ld, int64_t m, int64_t nq, const double* thr_host, bool count_only,
+                        const int64_t* ids_host, as_range* res, int64_t* counts, double* us);
+void range_work_free(RangeWork* r);
+void set_range_cap(int v);      // as_set_tuning("range_cap", v)
+void set_range_timing(int v);   // as_set_tuning("range_timing", 0 | 1)
 
 }  // namespace as

@@ -683,6 +683,7 @@ void subset_work_free(SubsetWork* w) {
     if (w->out) (void)hipHostFree(w->out);
     subset_batch_release(w);
     subset_sweep_release(w);
+    range_work_free(w->range);
     for (int i = 0; i < 2; ++i)
         if (w->ev[i]) (void)hipEventDestroy(w->ev[i]);
     if (w->stream) (void)hipStreamDestroy(w->stream);
@@ -853,7 +854,7 @@ static as_status subset_batch_reserve(SubsetWork* w, int64_t nq, int64_t m, bool
 
 as_status subset_batch_run(const as_space* sp, SubsetWork* w, int64_t m, const double* queries, int64_t b, const double* lq,
                            const int32_t* status, double tau, int64_t k, int64_t stride, int64_t* out_idx, double* out_score,
-                           int64_t* out_len, double* out_scores) {
+                           int64_t* out_len, double* out_scores, const SubsetChunkSink* sink) {
     if (m <= 0 || b <= 0) return AS_OK;
     const bool sel = k > 0;
     if (sel) k = std::min<int64_t>(std::min<int64_t>(k, m), SUBSET_TOPK);
@@ -910,6 +911,8 @@ as_status subset_batch_run(const as_space* sp, SubsetWork* w, int64_t m, const d
                                    (const int32_t*)w->ids, m, (int)k, (const int32_t*)w->bsel_pos, (const unsigned int*)w->bhist, w->bout);
             }
             AS_HIP(hipGetLastError());
+        } else if (sink) {
+            AS_TRY(sink->fn(sink->ctx, w, i0, nb, w->bscores, m));   // (it waits for the stream: the wait below finds it idle)
         } else {
             // one copy per chunk; a zero-lambda query's row stays unwritten: the copy is split around it
             for (int64_t t = 0; t < nb;) {
