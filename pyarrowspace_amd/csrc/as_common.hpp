@@ -256,6 +256,57 @@ struct dev_tmp {
     operator T*() const { return p; }
 };
 
+// Grow-only work buffers of a handle, in device memory (dev_buf) and in pinned host memory (pin_buf): freed with their owner.
+// reserve(count): nothing if `count` elements fit already; else the old block is freed and exactly `count` elements are
+// allocated (the contents are lost; the caller pads `count` if it wants room to grow).  After a failure the buffer is empty.
+struct dev_mem {
+    static hipError_t get(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+    static void put(void* p) { (void)hipFree(p); }
+};
+struct pin_mem {
+    static hipError_t get(void** p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
+    static void put(void* p) { (void)hipHostFree(p); }
+};
+template <typename T, typename Mem>
+class work_buf {
+    T* p = nullptr;
+    size_t n = 0;
+
+public:
+    work_buf() = default;
+    work_buf(const work_buf&) = delete;
+    work_buf& operator=(const work_buf&) = delete;
+    ~work_buf() { release(); }
+    hipError_t reserve(size_t count) {
+        if (count <= n) return hipSuccess;
+        release();
+        const hipError_t e = Mem::get((void**)&p, sizeof(T) * count);
+        if (e == hipSuccess) n = count;
+        else p = nullptr;
+        return e;
+    }
+    void release() {
+        if (p) Mem::put(p);
+        p = nullptr;
+        n = 0;
+    }
+    size_t size() const { return n; }
+    operator T*() const { return p; }
+};
+template <typename T>
+using dev_buf = work_buf<T, dev_mem>;
+template <typename T>
+using pin_buf = work_buf<T, pin_mem>;
+
+// reserve() as a status: a failure names the part and the size asked for
+template <typename B>
+as_status reserve_or_err(B& buf, int64_t count, const char* part) {
+    const hipError_t e = buf.reserve((size_t)count);
+    if (e == hipSuccess) return AS_OK;
+    set_err("allocation of the %s (%lld elements) failed: %s", part, (long long)count, hipGetErrorString(e));
+    return e == hipErrorOutOfMemory ? AS_ENOMEM : AS_EHIP;
+}
+
 // HIP events of a host function: destroyed on every return path, error paths included.
 template <int N>
 struct dev_events {
@@ -594,9 +645,54 @@ as_status search_batch_sweep_launch_pair(as_query* a, as_query* b, const double*
 as_status search_batch_sweep_collect(as_query* q, int nb, const double* taus, int nt, int64_t topk, int64_t* out_idx, double* out_score,
                                      int64_t* out_len, double* out_lambda_q, int32_t* out_status);
 int query_sweep_ran(const as_query* q);
+// Small host steps the filtered, list and range searches share.
+// The query stage of a chunk at dst: [nbp][dp] queries i0 .. i0 + nb - 1 of `queries` ([.][d]), zero padded (rows >= nb all
+// zero), then [nbp] |q|^2 (host_sumsq), then [nbp] lambda_q.
+inline void stage_queries(double* dst, const double* queries, int64_t i0, int64_t nb, int64_t nbp, int64_t d, int64_t dp, const double* lq) {
+    double* hn = dst + nbp * dp;
+    double* hl = hn + nbp;
+    for (int64_t t = 0; t < nbp; ++t) {
+        double* row = dst + t * dp;
+        const int64_t dt = t < nb ? d : 0;   // (a pad row: zeros throughout)
+        const double* q = queries + (i0 + (t < nb ? t : 0)) * d;
+        for (int64_t c = 0; c < dt; ++c) row[c] = q[c];
+        for (int64_t c = dt; c < dp; ++c) row[c] = 0.0;
+        hn[t] = t < nb ? host_sumsq(q, d) : 0.0;
+        hl[t] = t < nb ? lq[i0 + t] : 0.0;
+    }
+}
+// fn(t, u) for every maximal run [t, u) of queries i0 + t, t < nb, whose status is not AS_EZEROLAMBDA: what a chunk holds for
+// the others is no answer and is not copied out
+template <typename F>
+as_status for_served_runs(const int32_t* status, int64_t i0, int64_t nb, F&& fn) {
+    for (int64_t t = 0; t < nb;) {
+        if (status[i0 + t] == AS_EZEROLAMBDA) {
+            ++t;
+            continue;
+        }
+        int64_t u = t;
+        while (u < nb && status[i0 + u] != AS_EZEROLAMBDA) ++u;
+        AS_TRY(fn(t, u));
+        t = u;
+    }
+    return AS_OK;
+}
+// waits for the stream; timing: *us += the time between the two events recorded on it
+inline as_status sync_add_elapsed(hipStream_t stream, bool timing, const hipEvent_t* ev, double* us) {
+    AS_HIP(hipStreamSynchronize(stream));
+    if (timing) {
+        float ms = 0.0f;
+        AS_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        *us += (double)ms * 1e3;
+    }
+    return AS_OK;
+}
+
 // filtered search (as_subset.hip): exact S11 scores of a list of items gathered by id, exact top-k of them.  A SubsetWork holds
-// everything a call needs on the device (ids, scores, the query, the selection's histograms and records) and the pinned result:
-// nothing is allocated per query.  One call at a time per SubsetWork (the owner's mutex).
+// everything a call needs on the device (ids, scores, the query, the selection's histograms and records) and the pinned result.
+// ONE set of grow-only buffers serves the single-query, the batched and the tau-sweep forms (subset_reserve): created for a single
+// query (nothing is allocated per single query), grown by the first larger call of another form, never shrunk.  One call at a
+// time per SubsetWork (the owner's mutex).
 constexpr int SUBSET_TOPK = 1024;   // == MAX_TOPK: entries of the final one-block sort
 struct SubsetOut {
     int64_t len;
@@ -608,41 +704,19 @@ struct SubsetWork {
     int device = 0;
     hipStream_t stream = nullptr;
     int cus = 256;                 // compute units of that device (the score kernel's grid)
-    int64_t cap = 0, dp = 0;       // ids / scores the buffers hold (< 2^31: positions are 32-bit), padded query length
-    int32_t* ids = nullptr;        // [cap]
-    double* scores = nullptr;      // [cap]
-    double* q64 = nullptr;         // [dp] the query, zero padded
-    double* hq = nullptr;          // pinned staging of the query
-    unsigned int* hist = nullptr;  // selection: one histogram per radix pass, then the counter of selected positions
-    SubsetSel* state = nullptr;    // ... the threshold's digits found so far, per pass
-    int32_t* sel_pos = nullptr;    // ... [SUBSET_TOPK] positions at or above the threshold
-    SubsetOut* out = nullptr;      // pinned, written by the sort kernel
+    int64_t cap = 0, dp = 0;       // ids the handle holds (< 2^31: positions are 32-bit), padded query length
+    dev_buf<int32_t> ids;          // [cap]
+    dev_buf<double> qd;            // the query stage (stage_queries): [rows][dp] queries, then [rows] |q|^2, then [rows] lambda_q
+    pin_buf<double> qh;            // pinned staging of the same
+    dev_buf<double> scores;        // at least [cap]; the batched forms: [chunk][m]; the sweeps: the [query][tau][m] planes of a (chunk, tau group)
+    // the selection's scratch, per row (a query, or a (query, tau) pair of a sweep)
+    dev_buf<unsigned int> hist;    // one histogram per radix pass, then the counter of selected positions
+    dev_buf<SubsetSel> state;      // the threshold's digits found so far, per pass
+    dev_buf<int32_t> sel_pos;      // [SUBSET_TOPK] positions at or above the threshold
+    pin_buf<SubsetOut> out;        // pinned, written by the sort kernel
     hipEvent_t ev[2] = {nullptr, nullptr};
     int timing = 0;                // record ev around the score kernel
     double kernel_us = 0.0;        // ... and its duration in the last timed call (the batched forms: summed over the chunks)
-    // the batched forms (subset_batch_run): made on the first batched call on this work, grown on demand
-    int64_t bq = 0;                // queries the buffers below hold (a multiple of the batched score kernel's query tile)
-    int64_t bscores_n = 0;         // doubles in bscores
-    bool bsel = false, bhist_on = false;   // the selection's result / radix buffers exist for bq queries
-    double* bqd = nullptr;         // [bq][dp] the queries, zero padded, then [bq] |q|^2, then [bq] lambda_q
-    double* bqh = nullptr;         // pinned staging of the same
-    double* bscores = nullptr;     // [chunk][m]
-    unsigned int* bhist = nullptr; // per query: what hist / state / sel_pos / out are for one
-    SubsetSel* bstate = nullptr;
-    int32_t* bsel_pos = nullptr;
-    SubsetOut* bout = nullptr;     // pinned [bq]
-    // the tau sweeps (subset_sweep_run, subset_batch_sweep_run): made on the first sweep on this work, each grown on demand.  A
-    // (query, tau) pair takes the place of a query of the batched forms.
-    int64_t sw_nq = 0;             // queries sw_qd / sw_qh hold (the batched sweep only)
-    int64_t sw_scores_n = 0;       // doubles in sw_scores
-    int64_t sw_out_n = 0, sw_hist_n = 0;   // pairs the result / the radix buffers hold
-    double* sw_qd = nullptr;       // [sw_nq][dp] queries, zero padded, then [sw_nq] |q|^2, then [sw_nq] lambda_q
-    double* sw_qh = nullptr;       // pinned staging of the same
-    double* sw_scores = nullptr;   // [query][tau][m] score planes of one (chunk, tau group)
-    unsigned int* sw_hist = nullptr;
-    SubsetSel* sw_state = nullptr;
-    int32_t* sw_sel_pos = nullptr;
-    SubsetOut* sw_out = nullptr;   // pinned [sw_out_n]
     // range search (as_range.hip): the append buffer, its counters and the thresholds, made on the first range call on this work
     RangeWork* range = nullptr;
 };

@@ -427,16 +427,13 @@ struct ListsWork {
     hipStream_t stream = nullptr;
     int cus = 256;
     // one upload per chunk: [nb][dp] queries, [nb] |q|^2, [nb] lambda_q, the segments, the lists, the ids
-    char* up_d = nullptr;
-    char* up_h = nullptr;          // pinned staging of the same
-    size_t up_bytes = 0;
-    double* scores = nullptr;      // [scores_n] the chunk's scores, entry by entry
-    int64_t scores_n = 0;
-    int64_t* out_len = nullptr;    // pinned results of the selection: [out_q], [out_e] entries at stride kk
-    int64_t* out_idx = nullptr;
-    double* out_score = nullptr;
-    int64_t out_q = 0, out_e = 0;
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    dev_buf<char> up_d;
+    pin_buf<char> up_h;            // pinned staging of the same
+    dev_buf<double> scores;        // the chunk's scores, entry by entry
+    pin_buf<int64_t> out_len;      // pinned results of the selection: one length per list, entries at stride kk
+    pin_buf<int64_t> out_idx;
+    pin_buf<double> out_score;
+    dev_events<2> ev;
     double kernel_us = 0.0;        // the score kernel summed over the chunks of the last timed call
 };
 
@@ -444,16 +441,8 @@ void lists_work_free(ListsWork* w) {
     if (!w) return;
     (void)hipSetDevice(w->device);
     if (w->stream) (void)hipStreamSynchronize(w->stream);
-    (void)hipFree(w->up_d);
-    (void)hipFree(w->scores);
-    if (w->up_h) (void)hipHostFree(w->up_h);
-    if (w->out_len) (void)hipHostFree(w->out_len);
-    if (w->out_idx) (void)hipHostFree(w->out_idx);
-    if (w->out_score) (void)hipHostFree(w->out_score);
-    for (int i = 0; i < 2; ++i)
-        if (w->ev[i]) (void)hipEventDestroy(w->ev[i]);
     if (w->stream) (void)hipStreamDestroy(w->stream);
-    delete w;
+    delete w;   // (the buffers and the events free themselves)
 }
 
 double lists_kernel_us(const ListsWork* w) { return w ? w->kernel_us : 0.0; }
@@ -467,8 +456,7 @@ static as_status lists_work_create(const as_space* sp, ListsWork** out) {
     w->device = sp->device;
     if (hipDeviceGetAttribute(&w->cus, hipDeviceAttributeMultiprocessorCount, sp->device) != hipSuccess || w->cus <= 0) w->cus = 256;
     hipError_t e;
-    if ((e = hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking)) != hipSuccess || (e = hipEventCreate(&w->ev[0])) != hipSuccess ||
-        (e = hipEventCreate(&w->ev[1])) != hipSuccess) {
+    if ((e = hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking)) != hipSuccess || (e = w->ev.create()) != hipSuccess) {
         set_err("lists: creation of the stream and events failed: %s", hipGetErrorString(e));
         lists_work_free(w);
         return AS_EHIP;
@@ -479,45 +467,17 @@ static as_status lists_work_create(const as_space* sp, ListsWork** out) {
 
 // room for a chunk: `up` bytes of upload, ne scores, and for the selection nb lists of kk entries; each grown by half again
 static as_status lists_reserve(ListsWork* w, size_t up, int64_t ne, int64_t nb, int64_t kk) {
-    hipError_t e = hipSuccess;
-    const char* what = "upload";
-    if (up > w->up_bytes) {
-        (void)hipFree(w->up_d);
-        if (w->up_h) (void)hipHostFree(w->up_h);
-        w->up_d = w->up_h = nullptr;
-        w->up_bytes = 0;
-        const size_t cap = up + up / 2;
-        if ((e = hipMalloc((void**)&w->up_d, cap)) == hipSuccess && (e = hipHostMalloc((void**)&w->up_h, cap, hipHostMallocDefault)) == hipSuccess)
-            w->up_bytes = cap;
+    if (up > std::min(w->up_d.size(), w->up_h.size())) {
+        AS_TRY(reserve_or_err(w->up_d, up + up / 2, "lists upload"));
+        AS_TRY(reserve_or_err(w->up_h, up + up / 2, "lists pinned upload"));
     }
-    if (e == hipSuccess && ne > w->scores_n) {
-        what = "scores";
-        (void)hipFree(w->scores);
-        w->scores = nullptr;
-        w->scores_n = 0;
-        const int64_t cap = ne + ne / 2;
-        if ((e = hipMalloc((void**)&w->scores, sizeof(double) * (size_t)cap)) == hipSuccess) w->scores_n = cap;
-    }
-    if (e == hipSuccess && kk > 0 && (nb > w->out_q || nb * kk > w->out_e)) {
-        what = "results";
-        if (w->out_len) (void)hipHostFree(w->out_len);
-        if (w->out_idx) (void)hipHostFree(w->out_idx);
-        if (w->out_score) (void)hipHostFree(w->out_score);
-        w->out_len = w->out_idx = nullptr;
-        w->out_score = nullptr;
-        w->out_q = w->out_e = 0;
-        const int64_t cq = std::max<int64_t>(nb + nb / 2, w->out_q), ce = std::max<int64_t>(cq * kk, w->out_e);
-        if ((e = hipHostMalloc((void**)&w->out_len, sizeof(int64_t) * (size_t)cq, hipHostMallocDefault)) == hipSuccess &&
-            (e = hipHostMalloc((void**)&w->out_idx, sizeof(int64_t) * (size_t)ce, hipHostMallocDefault)) == hipSuccess &&
-            (e = hipHostMalloc((void**)&w->out_score, sizeof(double) * (size_t)ce, hipHostMallocDefault)) == hipSuccess) {
-            w->out_q = cq;
-            w->out_e = ce;
-        }
-    }
-    if (e != hipSuccess) {
-        set_err("lists: allocation of the work buffers (%s, %lld queries, %lld entries) failed: %s", what, (long long)nb, (long long)ne,
-                hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? AS_ENOMEM : AS_EHIP;
+    if (ne > (int64_t)w->scores.size()) AS_TRY(reserve_or_err(w->scores, ne + ne / 2, "lists scores"));
+    const int64_t out_q = w->out_len.size(), out_e = std::min(w->out_idx.size(), w->out_score.size());
+    if (kk > 0 && (nb > out_q || nb * kk > out_e)) {
+        const int64_t cq = std::max<int64_t>(nb + nb / 2, out_q), ce = std::max<int64_t>(cq * kk, w->out_idx.size());
+        AS_TRY(reserve_or_err(w->out_len, cq, "lists pinned lengths"));
+        AS_TRY(reserve_or_err(w->out_idx, ce, "lists pinned ids"));
+        AS_TRY(reserve_or_err(w->out_score, ce, "lists pinned scores"));
     }
     return AS_OK;
 }
@@ -558,20 +518,14 @@ as_status lists_run(const as_space* sp, const int32_t* ids, const int64_t* offs,
         const size_t seg_off = q_bytes, list_off = seg_off + sizeof(ListsSeg) * (size_t)nseg_max;
         const size_t ids_off = list_off + sizeof(ListsList) * (size_t)nb, up = ids_off + sizeof(int32_t) * (size_t)ne;
         AS_TRY(lists_reserve(w, up, ne, nb, kk));
-        double* hq = (double*)w->up_h;
-        double* hn = hq + nb * dp;
-        double* hl = hn + nb;
-        ListsSeg* hseg = (ListsSeg*)(w->up_h + seg_off);
-        ListsList* hlist = (ListsList*)(w->up_h + list_off);
+        char* const up_h = w->up_h;
+        char* const up_d = w->up_d;
+        stage_queries((double*)up_h, queries, i0, nb, nb, d, dp, lq);
+        ListsSeg* hseg = (ListsSeg*)(up_h + seg_off);
+        ListsList* hlist = (ListsList*)(up_h + list_off);
         int64_t nseg = 0, pairs = 0;
         for (int64_t t = 0; t < nb; ++t) {
             const int64_t i = i0 + t, first = offs[i] - base, m = offs[i + 1] - offs[i];
-            const double* q = queries + i * d;
-            double* row = hq + t * dp;
-            for (int64_t c = 0; c < d; ++c) row[c] = q[c];
-            for (int64_t c = d; c < dp; ++c) row[c] = 0.0;
-            hn[t] = host_sumsq(q, d);
-            hl[t] = lq[i];
             const bool served = status[i] != AS_EZEROLAMBDA;
             hlist[t].first = first;
             hlist[t].len = served ? m : 0;
@@ -588,16 +542,16 @@ as_status lists_run(const as_space* sp, const int32_t* ids, const int64_t* offs,
                 o += cnt;
             }
         }
-        memcpy(w->up_h + ids_off, ids + base, sizeof(int32_t) * (size_t)ne);
+        memcpy(up_h + ids_off, ids + base, sizeof(int32_t) * (size_t)ne);
         counts[2] += std::chrono::duration_cast<std::chrono::nanoseconds>(now() - t0).count();
         if (nseg > 0) {
-            AS_HIP(hipMemcpyAsync(w->up_d, w->up_h, up, hipMemcpyHostToDevice, w->stream));
+            AS_HIP(hipMemcpyAsync(up_d, up_h, up, hipMemcpyHostToDevice, w->stream));
             ListsArgs a;
-            a.segs = (const ListsSeg*)(w->up_d + seg_off); a.nseg = nseg; a.ids = (const int32_t*)(w->up_d + ids_off);
-            a.x32 = sp->x32; a.x64 = sp->x64; a.n64 = sp->n64; a.lam64 = sp->lam64; a.q64 = (const double*)w->up_d;
+            a.segs = (const ListsSeg*)(up_d + seg_off); a.nseg = nseg; a.ids = (const int32_t*)(up_d + ids_off);
+            a.x32 = sp->x32; a.x64 = sp->x64; a.n64 = sp->n64; a.lam64 = sp->lam64; a.q64 = (const double*)up_d;
             a.nq = a.q64 + nb * dp; a.lq = a.nq + nb; a.scores = w->scores; a.d = d; a.dp = dp; a.tau = tau;
             const unsigned grid = (unsigned)std::min<int64_t>(nseg, (int64_t)w->cus * LISTS_BLOCKS_PER_CU);
-            if (timing) AS_HIP(hipEventRecord(w->ev[0], w->stream));
+            if (timing) AS_HIP(hipEventRecord(w->ev.e[0], w->stream));
             if (sp->x64) {
                 if (qlds) hipLaunchKernelGGL((lists_score_kernel<true, true>), dim3(grid), dim3(256), lds, w->stream, a);
                 else hipLaunchKernelGGL((lists_score_kernel<true, false>), dim3(grid), dim3(256), 0, w->stream, a);
@@ -606,37 +560,26 @@ as_status lists_run(const as_space* sp, const int32_t* ids, const int64_t* offs,
                 else hipLaunchKernelGGL((lists_score_kernel<false, false>), dim3(grid), dim3(256), 0, w->stream, a);
             }
             AS_HIP(hipGetLastError());
-            if (timing) AS_HIP(hipEventRecord(w->ev[1], w->stream));
+            if (timing) AS_HIP(hipEventRecord(w->ev.e[1], w->stream));
             counts[0] += 1;
             counts[1] += pairs;
             if (sel) {
                 ListsSelArgs s;
-                s.lists = (const ListsList*)(w->up_d + list_off); s.scores = w->scores; s.ids = a.ids; s.kk = kk;
+                s.lists = (const ListsList*)(up_d + list_off); s.scores = w->scores; s.ids = a.ids; s.kk = kk;
                 s.out_len = w->out_len; s.out_idx = w->out_idx; s.out_score = w->out_score; s.nt = 1;
                 hipLaunchKernelGGL(lists_select_kernel<false>, dim3((unsigned)nb), dim3(LSEL_NT), 0, w->stream, s);
                 AS_HIP(hipGetLastError());
             } else {
                 // one copy per run of served queries: the scores of a query that is not served stay unwritten
-                for (int64_t t = 0; t < nb;) {
-                    if (status[i0 + t] == AS_EZEROLAMBDA) {
-                        ++t;
-                        continue;
-                    }
-                    int64_t u = t;
-                    while (u < nb && status[i0 + u] != AS_EZEROLAMBDA) ++u;
+                AS_TRY(for_served_runs(status, i0, nb, [&](int64_t t, int64_t u) -> as_status {
                     const int64_t e0 = offs[i0 + t] - base, e1 = offs[i0 + u] - base;
                     if (e1 > e0)
                         AS_HIP(hipMemcpyAsync(out_scores + base + e0, w->scores + e0, sizeof(double) * (size_t)(e1 - e0), hipMemcpyDeviceToHost,
                                               w->stream));
-                    t = u;
-                }
+                    return AS_OK;
+                }));
             }
-            AS_HIP(hipStreamSynchronize(w->stream));
-            if (timing) {
-                float ms = 0.0f;
-                AS_HIP(hipEventElapsedTime(&ms, w->ev[0], w->ev[1]));
-                w->kernel_us += (double)ms * 1e3;
-            }
+            AS_TRY(sync_add_elapsed(w->stream, timing, w->ev.e, &w->kernel_us));
             if (sel)
                 for (int64_t t = 0; t < nb; ++t) {
                     const int64_t i = i0 + t, want = std::min<int64_t>(kk, hlist[t].len);
@@ -698,20 +641,14 @@ as_status lists_run_taus(const as_space* sp, const int32_t* ids, const int64_t* 
         const size_t seg_off = q_bytes, list_off = seg_off + sizeof(ListsTausSeg) * (size_t)nseg_max;
         const size_t ids_off = list_off + sizeof(ListsList) * (size_t)nb, up = ids_off + sizeof(int32_t) * (size_t)ne;
         AS_TRY(lists_reserve(w, up, ne * tg, nb * tg, kk));
-        double* hq = (double*)w->up_h;
-        double* hn = hq + nb * dp;
-        double* hl = hn + nb;
-        ListsTausSeg* hseg = (ListsTausSeg*)(w->up_h + seg_off);
-        ListsList* hlist = (ListsList*)(w->up_h + list_off);
+        char* const up_h = w->up_h;
+        char* const up_d = w->up_d;
+        stage_queries((double*)up_h, queries, i0, nb, nb, d, dp, lq);
+        ListsTausSeg* hseg = (ListsTausSeg*)(up_h + seg_off);
+        ListsList* hlist = (ListsList*)(up_h + list_off);
         int64_t nseg = 0, pairs = 0;
         for (int64_t t = 0; t < nb; ++t) {
             const int64_t i = i0 + t, first = offs[i] - base, m = offs[i + 1] - offs[i];
-            const double* q = queries + i * d;
-            double* qrow = hq + t * dp;
-            for (int64_t c = 0; c < d; ++c) qrow[c] = q[c];
-            for (int64_t c = d; c < dp; ++c) qrow[c] = 0.0;
-            hn[t] = host_sumsq(q, d);
-            hl[t] = lq[i];
             const bool served = status[i] != AS_EZEROLAMBDA;
             hlist[t].first = first;
             hlist[t].len = served ? m : 0;
@@ -729,21 +666,21 @@ as_status lists_run_taus(const as_space* sp, const int32_t* ids, const int64_t* 
                 o += cnt;
             }
         }
-        memcpy(w->up_h + ids_off, ids + base, sizeof(int32_t) * (size_t)ne);
+        memcpy(up_h + ids_off, ids + base, sizeof(int32_t) * (size_t)ne);
         counts[3] += std::chrono::duration_cast<std::chrono::nanoseconds>(now() - t0).count();
         if (nseg > 0) {
-            AS_HIP(hipMemcpyAsync(w->up_d, w->up_h, up, hipMemcpyHostToDevice, w->stream));
+            AS_HIP(hipMemcpyAsync(up_d, up_h, up, hipMemcpyHostToDevice, w->stream));
             ListsTausArgs a;
-            a.s.segs = nullptr; a.s.nseg = nseg; a.s.ids = (const int32_t*)(w->up_d + ids_off);
-            a.s.x32 = sp->x32; a.s.x64 = sp->x64; a.s.n64 = sp->n64; a.s.lam64 = sp->lam64; a.s.q64 = (const double*)w->up_d;
+            a.s.segs = nullptr; a.s.nseg = nseg; a.s.ids = (const int32_t*)(up_d + ids_off);
+            a.s.x32 = sp->x32; a.s.x64 = sp->x64; a.s.n64 = sp->n64; a.s.lam64 = sp->lam64; a.s.q64 = (const double*)up_d;
             a.s.nq = a.s.q64 + nb * dp; a.s.lq = a.s.nq + nb; a.s.scores = w->scores; a.s.d = d; a.s.dp = dp; a.s.tau = 0.0;
-            a.segs = (const ListsTausSeg*)(w->up_d + seg_off);
+            a.segs = (const ListsTausSeg*)(up_d + seg_off);
             const unsigned grid = (unsigned)std::min<int64_t>(nseg, (int64_t)w->cus * LISTS_BLOCKS_PER_CU);
             for (int64_t u0 = 0; u0 < nt; u0 += tg) {
                 const int64_t g = std::min<int64_t>(tg, nt - u0);   // taus of this group: planes of every list's block
                 a.nt = (int)g;
                 for (int64_t j = 0; j < TAU_GROUP; ++j) a.taus[j] = j < g ? taus[u0 + j] : 0.0;
-                if (timing) AS_HIP(hipEventRecord(w->ev[0], w->stream));
+                if (timing) AS_HIP(hipEventRecord(w->ev.e[0], w->stream));
                 if (sp->x64) {
                     if (qlds) hipLaunchKernelGGL((lists_score_taus_kernel<true, true>), dim3(grid), dim3(256), lds, w->stream, a);
                     else hipLaunchKernelGGL((lists_score_taus_kernel<true, false>), dim3(grid), dim3(256), 0, w->stream, a);
@@ -752,31 +689,25 @@ as_status lists_run_taus(const as_space* sp, const int32_t* ids, const int64_t* 
                     else hipLaunchKernelGGL((lists_score_taus_kernel<false, false>), dim3(grid), dim3(256), 0, w->stream, a);
                 }
                 AS_HIP(hipGetLastError());
-                if (timing) AS_HIP(hipEventRecord(w->ev[1], w->stream));
+                if (timing) AS_HIP(hipEventRecord(w->ev.e[1], w->stream));
                 counts[0] += 1;
                 counts[1] += pairs;
                 counts[2] += pairs * g;
                 if (sel) {
                     ListsSelArgs s;
-                    s.lists = (const ListsList*)(w->up_d + list_off); s.scores = w->scores; s.ids = a.s.ids; s.kk = kk;
+                    s.lists = (const ListsList*)(up_d + list_off); s.scores = w->scores; s.ids = a.s.ids; s.kk = kk;
                     s.out_len = w->out_len; s.out_idx = w->out_idx; s.out_score = w->out_score; s.nt = (int)g;
                     hipLaunchKernelGGL(lists_select_kernel<true>, dim3((unsigned)(nb * g)), dim3(LSEL_NT), 0, w->stream, s);
                     AS_HIP(hipGetLastError());
                 } else if (g == ntau) {
                     // one group, no repeated tau: the device layout is the output's; one copy per run of served queries
-                    for (int64_t t = 0; t < nb;) {
-                        if (status[i0 + t] == AS_EZEROLAMBDA) {
-                            ++t;
-                            continue;
-                        }
-                        int64_t u = t;
-                        while (u < nb && status[i0 + u] != AS_EZEROLAMBDA) ++u;
+                    AS_TRY(for_served_runs(status, i0, nb, [&](int64_t t, int64_t u) -> as_status {
                         const int64_t e0 = offs[i0 + t] - base, e1 = offs[i0 + u] - base;
                         if (e1 > e0)
                             AS_HIP(hipMemcpyAsync(out_scores + ntau * (base + e0), w->scores + g * e0, sizeof(double) * (size_t)((e1 - e0) * g),
                                                   hipMemcpyDeviceToHost, w->stream));
-                        t = u;
-                    }
+                        return AS_OK;
+                    }));
                 } else {
                     // per served query, one copy per run of planes whose output rows are consecutive
                     for (int64_t t = 0; t < nb; ++t) {
@@ -791,12 +722,7 @@ as_status lists_run_taus(const as_space* sp, const int32_t* ids, const int64_t* 
                         }
                     }
                 }
-                AS_HIP(hipStreamSynchronize(w->stream));
-                if (timing) {
-                    float ms = 0.0f;
-                    AS_HIP(hipEventElapsedTime(&ms, w->ev[0], w->ev[1]));
-                    w->kernel_us += (double)ms * 1e3;
-                }
+                AS_TRY(sync_add_elapsed(w->stream, timing, w->ev.e, &w->kernel_us));
                 if (sel)
                     for (int64_t t = 0; t < nb; ++t) {
                         const int64_t i = i0 + t, want = std::min<int64_t>(kk, hlist[t].len);

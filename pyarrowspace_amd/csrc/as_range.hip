@@ -124,76 +124,16 @@ void set_range_cap(int v) { g_range_cap.store(v > 0 ? v : 0, std::memory_order_r
 void set_range_timing(int v) { g_range_timing.store(v ? 1 : 0, std::memory_order_relaxed); }
 
 struct RangeWork {
-    RangeEntry* buf = nullptr;          // the append buffer, [buf_n]
-    int64_t buf_n = 0;
-    unsigned long long* cnt = nullptr;  // [1 + rows]: the slot counter, then one counter per row (count_only)
-    double* thr = nullptr;              // [rows]
-    int64_t rows = 0;
-    unsigned long long* hcnt = nullptr; // pinned [1 + rows]
-    double* hthr = nullptr;             // pinned [rows]
-    RangeEntry* hent = nullptr;         // pinned [hent_n]
-    int64_t hent_n = 0;
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    dev_buf<RangeEntry> buf;           // the append buffer
+    dev_buf<unsigned long long> cnt;   // [1 + rows]: the slot counter, then one counter per row (count_only)
+    dev_buf<double> thr;               // [rows]; rows: a power of two, at least 64
+    pin_buf<unsigned long long> hcnt;  // pinned [1 + rows]
+    pin_buf<double> hthr;              // pinned [rows]
+    pin_buf<RangeEntry> hent;          // pinned: the front of the append buffer, or all of it
+    dev_events<2> ev;                  // made by the first call under "range_timing"
 };
 
-void range_work_free(RangeWork* r) {
-    if (!r) return;
-    (void)hipFree(r->buf);
-    (void)hipFree(r->cnt);
-    (void)hipFree(r->thr);
-    if (r->hcnt) (void)hipHostFree(r->hcnt);
-    if (r->hthr) (void)hipHostFree(r->hthr);
-    if (r->hent) (void)hipHostFree(r->hent);
-    for (int i = 0; i < 2; ++i)
-        if (r->ev[i]) (void)hipEventDestroy(r->ev[i]);
-    delete r;
-}
-
-static as_status range_fail(hipError_t e, const char* what, int64_t n) {
-    set_err("range: allocation of the %s (%lld entries) failed: %s", what, (long long)n, hipGetErrorString(e));
-    return e == hipErrorOutOfMemory ? AS_ENOMEM : AS_EHIP;
-}
-
-static as_status range_reserve_rows(RangeWork* r, int64_t rows) {
-    if (rows <= r->rows) return AS_OK;
-    (void)hipFree(r->cnt);
-    (void)hipFree(r->thr);
-    if (r->hcnt) (void)hipHostFree(r->hcnt);
-    if (r->hthr) (void)hipHostFree(r->hthr);
-    r->cnt = r->hcnt = nullptr;
-    r->thr = r->hthr = nullptr;
-    r->rows = 0;
-    int64_t n = 64;
-    while (n < rows) n *= 2;
-    hipError_t e;
-    if ((e = hipMalloc((void**)&r->cnt, sizeof(unsigned long long) * (size_t)(n + 1))) != hipSuccess ||
-        (e = hipMalloc((void**)&r->thr, sizeof(double) * (size_t)n)) != hipSuccess ||
-        (e = hipHostMalloc((void**)&r->hcnt, sizeof(unsigned long long) * (size_t)(n + 1), hipHostMallocDefault)) != hipSuccess ||
-        (e = hipHostMalloc((void**)&r->hthr, sizeof(double) * (size_t)n, hipHostMallocDefault)) != hipSuccess)
-        return range_fail(e, "counters and thresholds", n);
-    r->rows = n;
-    return AS_OK;
-}
-static as_status range_reserve_buf(RangeWork* r, int64_t n) {
-    if (n <= r->buf_n) return AS_OK;
-    (void)hipFree(r->buf);
-    r->buf = nullptr;
-    r->buf_n = 0;
-    const hipError_t e = hipMalloc((void**)&r->buf, sizeof(RangeEntry) * (size_t)n);
-    if (e != hipSuccess) return range_fail(e, "append buffer", n);
-    r->buf_n = n;
-    return AS_OK;
-}
-static as_status range_reserve_host(RangeWork* r, int64_t n) {
-    if (n <= r->hent_n) return AS_OK;
-    if (r->hent) (void)hipHostFree(r->hent);
-    r->hent = nullptr;
-    r->hent_n = 0;
-    const hipError_t e = hipHostMalloc((void**)&r->hent, sizeof(RangeEntry) * (size_t)n, hipHostMallocDefault);
-    if (e != hipSuccess) return range_fail(e, "pinned entries", n);
-    r->hent_n = n;
-    return AS_OK;
-}
+void range_work_free(RangeWork* r) { delete r; }
 
 as_status range_compact(SubsetWork* w, const double* scores, int64_t ld, int64_t m, int64_t nq, const double* thr_host, bool count_only,
                         const int64_t* ids_host, as_range* res, int64_t* counts, double* us) {
@@ -207,17 +147,19 @@ as_status range_compact(SubsetWork* w, const double* scores, int64_t ld, int64_t
     }
     RangeWork* r = w->range;
     const bool timing = g_range_timing.load(std::memory_order_relaxed) != 0;
-    if (timing && !r->ev[0]) {
-        AS_HIP(hipEventCreate(&r->ev[0]));
-        AS_HIP(hipEventCreate(&r->ev[1]));
-    }
-    AS_TRY(range_reserve_rows(r, nq));
+    if (timing && !r->ev.e[1]) AS_HIP(r->ev.create());
+    int64_t rows = 64;
+    while (rows < nq) rows *= 2;
+    AS_TRY(reserve_or_err(r->cnt, rows + 1, "range counters"));
+    AS_TRY(reserve_or_err(r->thr, rows, "range thresholds"));
+    AS_TRY(reserve_or_err(r->hcnt, rows + 1, "range pinned counters"));
+    AS_TRY(reserve_or_err(r->hthr, rows, "range pinned thresholds"));
     const int64_t tuned = g_range_cap.load(std::memory_order_relaxed);
     int64_t cap = 0;
     if (!count_only) {
-        cap = tuned > 0 ? tuned : std::max<int64_t>(RANGE_CAP_DEFAULT, r->buf_n);
-        AS_TRY(range_reserve_buf(r, cap));
-        AS_TRY(range_reserve_host(r, std::min<int64_t>(cap, RANGE_SPEC)));
+        cap = tuned > 0 ? tuned : std::max<int64_t>(RANGE_CAP_DEFAULT, (int64_t)r->buf.size());
+        AS_TRY(reserve_or_err(r->buf, cap, "range append buffer"));
+        AS_TRY(reserve_or_err(r->hent, std::min<int64_t>(cap, RANGE_SPEC), "range pinned entries"));
     }
     int64_t live = 0;
     for (int64_t t = 0; t < nq; ++t) {
@@ -229,29 +171,22 @@ as_status range_compact(SubsetWork* w, const double* scores, int64_t ld, int64_t
     const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(trips, std::max<int64_t>(1, RC_BLOCKS / nq))), (unsigned)nq);
     const size_t cnt_bytes = sizeof(unsigned long long) * (size_t)(count_only ? nq + 1 : 1);
     auto launch = [&](int64_t c) -> as_status {
-        AS_HIP(hipMemsetAsync(r->cnt, 0, cnt_bytes, w->stream));
-        if (timing) AS_HIP(hipEventRecord(r->ev[0], w->stream));
+        RangeEntry* buf = r->buf;
+        unsigned long long* cnt = r->cnt;
+        AS_HIP(hipMemsetAsync(cnt, 0, cnt_bytes, w->stream));
+        if (timing) AS_HIP(hipEventRecord(r->ev.e[0], w->stream));
         if (count_only)
-            hipLaunchKernelGGL(range_compact_kernel<true>, grid, dim3(RC_THREADS), 0, w->stream, scores, ld, m, (const double*)r->thr, r->buf,
-                               0ull, r->cnt);
+            hipLaunchKernelGGL(range_compact_kernel<true>, grid, dim3(RC_THREADS), 0, w->stream, scores, ld, m, (const double*)r->thr, buf, 0ull, cnt);
         else
-            hipLaunchKernelGGL(range_compact_kernel<false>, grid, dim3(RC_THREADS), 0, w->stream, scores, ld, m, (const double*)r->thr, r->buf,
-                               (unsigned long long)c, r->cnt);
+            hipLaunchKernelGGL(range_compact_kernel<false>, grid, dim3(RC_THREADS), 0, w->stream, scores, ld, m, (const double*)r->thr, buf,
+                               (unsigned long long)c, cnt);
         AS_HIP(hipGetLastError());
-        if (timing) AS_HIP(hipEventRecord(r->ev[1], w->stream));
-        AS_HIP(hipMemcpyAsync(r->hcnt, r->cnt, cnt_bytes, hipMemcpyDeviceToHost, w->stream));
+        if (timing) AS_HIP(hipEventRecord(r->ev.e[1], w->stream));
+        AS_HIP(hipMemcpyAsync(r->hcnt, cnt, cnt_bytes, hipMemcpyDeviceToHost, w->stream));
         counts[0] += 1;
         return AS_OK;
     };
-    auto wait = [&]() -> as_status {
-        AS_HIP(hipStreamSynchronize(w->stream));
-        if (timing) {
-            float ms = 0.0f;
-            AS_HIP(hipEventElapsedTime(&ms, r->ev[0], r->ev[1]));
-            *us += (double)ms * 1e3;
-        }
-        return AS_OK;
-    };
+    auto wait = [&]() -> as_status { return sync_add_elapsed(w->stream, timing, r->ev.e, us); };
     AS_TRY(launch(cap));
     int64_t have = 0;   // entries of the buffer's front already on the host
     if (!count_only) {
@@ -272,8 +207,8 @@ as_status range_compact(SubsetWork* w, const double* scores, int64_t ld, int64_t
         const int64_t total = (int64_t)r->hcnt[0];
         if (total > cap) {
             // the scores are still in their buffer: only the compaction runs again, into a buffer that holds them all
-            AS_TRY(range_reserve_buf(r, std::max<int64_t>(total, std::min<int64_t>(2 * cap, (int64_t)1 << 24))));
-            AS_TRY(launch(r->buf_n));
+            AS_TRY(reserve_or_err(r->buf, std::max<int64_t>(total, std::min<int64_t>(2 * cap, (int64_t)1 << 24)), "range append buffer"));
+            AS_TRY(launch((int64_t)r->buf.size()));
             counts[3] += 1;
             have = 0;
             AS_TRY(wait());
@@ -283,7 +218,7 @@ as_status range_compact(SubsetWork* w, const double* scores, int64_t ld, int64_t
             }
         }
         if (total > have) {
-            AS_TRY(range_reserve_host(r, total));   // (a larger block: the front is copied again with the rest)
+            AS_TRY(reserve_or_err(r->hent, total, "range pinned entries"));   // (a larger block: the front is copied again with the rest)
             AS_HIP(hipMemcpyAsync(r->hent, r->buf, sizeof(RangeEntry) * (size_t)total, hipMemcpyDeviceToHost, w->stream));
             AS_HIP(hipStreamSynchronize(w->stream));
         }

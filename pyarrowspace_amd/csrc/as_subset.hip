@@ -558,11 +558,8 @@ __device__ __forceinline__ void sel_hist_body(const double* __restrict__ scores,
     for (int b = threadIdx.x; b < SEL_BINS; b += blockDim.x)
         if (lh[b]) atomicAdd(&gh[b], lh[b]);
 }
-__global__ __launch_bounds__(256) void subset_hist_kernel(const double* __restrict__ scores, int64_t m, int k, int p, SubsetSel* state,
-                                                          unsigned int* hist) {
-    sel_hist_body(scores, m, k, p, state, hist);
-}
-// the batched forms: query blockIdx.y of a chunk, its scores at stride ld, its own histograms, state, positions and result
+// The selection's kernels work on row blockIdx.y (subset_select_rows): the single query, a query of a batched chunk or a (query,
+// tau) pair of a sweep, with its scores at stride ld and its own histograms, state, positions and result
 __global__ __launch_bounds__(256) void subset_hist_batch_kernel(const double* __restrict__ scores, int64_t ld, int64_t m, int k, int p,
                                                                 SubsetSel* state, unsigned int* hist) {
     const int64_t q = blockIdx.y;
@@ -582,10 +579,6 @@ __device__ __forceinline__ void sel_collect_body(const double* __restrict__ scor
             if (slot < (unsigned int)SUBSET_TOPK) sel_pos[slot] = (int32_t)i;
         }
     }
-}
-__global__ __launch_bounds__(256) void subset_collect_kernel(const double* __restrict__ scores, int64_t m, int k, SubsetSel* state,
-                                                             unsigned int* hist, int32_t* sel_pos) {
-    sel_collect_body(scores, m, k, state, hist, sel_pos);
 }
 __global__ __launch_bounds__(256) void subset_collect_batch_kernel(const double* __restrict__ scores, int64_t ld, int64_t m, int k,
                                                                    SubsetSel* state, unsigned int* hist, int32_t* sel_pos) {
@@ -622,11 +615,6 @@ __device__ __forceinline__ void sel_sort_body(const double* __restrict__ scores,
     }
     if (t == 0) out->len = n < k ? n : k;
 }
-__global__ __launch_bounds__(1024) void subset_sort_kernel(const double* __restrict__ scores, const int32_t* __restrict__ ids, int64_t m,
-                                                           int k, const int32_t* __restrict__ sel_pos, const unsigned int* __restrict__ sel_cnt,
-                                                           SubsetOut* out) {
-    sel_sort_body(scores, ids, m, k, sel_pos, sel_cnt, out);
-}
 __global__ __launch_bounds__(1024) void subset_sort_batch_kernel(const double* __restrict__ scores, int64_t ld, const int32_t* __restrict__ ids,
                                                                  int64_t m, int k, const int32_t* __restrict__ sel_pos,
                                                                  const unsigned int* __restrict__ hist, SubsetOut* out) {
@@ -636,58 +624,32 @@ __global__ __launch_bounds__(1024) void subset_sort_batch_kernel(const double* _
 }
 
 // ------------------------------------------------------------------ host side
-static void subset_batch_release(SubsetWork* w) {
-    (void)hipFree(w->bqd);
-    (void)hipFree(w->bscores);
-    (void)hipFree(w->bhist);
-    (void)hipFree(w->bstate);
-    (void)hipFree(w->bsel_pos);
-    if (w->bqh) (void)hipHostFree(w->bqh);
-    if (w->bout) (void)hipHostFree(w->bout);
-    w->bqd = w->bqh = w->bscores = nullptr;
-    w->bhist = nullptr;
-    w->bstate = nullptr;
-    w->bsel_pos = nullptr;
-    w->bout = nullptr;
-    w->bq = w->bscores_n = 0;
-    w->bsel = w->bhist_on = false;
-}
-
-static void subset_sweep_release(SubsetWork* w) {
-    (void)hipFree(w->sw_qd);
-    (void)hipFree(w->sw_scores);
-    (void)hipFree(w->sw_hist);
-    (void)hipFree(w->sw_state);
-    (void)hipFree(w->sw_sel_pos);
-    if (w->sw_qh) (void)hipHostFree(w->sw_qh);
-    if (w->sw_out) (void)hipHostFree(w->sw_out);
-    w->sw_qd = w->sw_qh = w->sw_scores = nullptr;
-    w->sw_hist = nullptr;
-    w->sw_state = nullptr;
-    w->sw_sel_pos = nullptr;
-    w->sw_out = nullptr;
-    w->sw_nq = w->sw_scores_n = w->sw_out_n = w->sw_hist_n = 0;
+// Room for a call in the work's one buffer set: query_rows rows of the query stage, score_doubles scores (never fewer than the
+// handle's ids: the single-query forms write there) and the selection's scratch for sel_rows rows -- the pinned results
+// (want_out) and the radix select's histograms, state and positions (want_hist).  Exact sizes; a buffer that is large enough
+// stays as it is.  A buffer whose allocation failed is empty: the call fails, the next one asks again.
+static as_status subset_reserve(SubsetWork* w, int64_t query_rows, int64_t score_doubles, int64_t sel_rows, bool want_out, bool want_hist) {
+    AS_TRY(reserve_or_err(w->qd, query_rows * (w->dp + 2), "subset query stage"));
+    AS_TRY(reserve_or_err(w->qh, query_rows * (w->dp + 2), "subset pinned query stage"));
+    AS_TRY(reserve_or_err(w->scores, std::max(score_doubles, w->cap), "subset scores"));
+    if (want_out) AS_TRY(reserve_or_err(w->out, sel_rows, "subset pinned results"));
+    if (want_hist) {
+        AS_TRY(reserve_or_err(w->hist, sel_rows * SEL_HIST_WORDS, "subset selection histograms"));
+        AS_TRY(reserve_or_err(w->state, sel_rows * (SEL_PASSES + 1), "subset selection states"));
+        AS_TRY(reserve_or_err(w->sel_pos, sel_rows * SUBSET_TOPK, "subset selected positions"));
+    }
+    return AS_OK;
 }
 
 void subset_work_free(SubsetWork* w) {
     if (!w) return;
     (void)hipSetDevice(w->device);
     if (w->stream) (void)hipStreamSynchronize(w->stream);
-    (void)hipFree(w->ids);
-    (void)hipFree(w->scores);
-    (void)hipFree(w->q64);
-    (void)hipFree(w->hist);
-    (void)hipFree(w->state);
-    (void)hipFree(w->sel_pos);
-    if (w->hq) (void)hipHostFree(w->hq);
-    if (w->out) (void)hipHostFree(w->out);
-    subset_batch_release(w);
-    subset_sweep_release(w);
     range_work_free(w->range);
     for (int i = 0; i < 2; ++i)
         if (w->ev[i]) (void)hipEventDestroy(w->ev[i]);
     if (w->stream) (void)hipStreamDestroy(w->stream);
-    delete w;
+    delete w;   // (the buffers free themselves)
 }
 
 as_status subset_work_create(const as_space* sp, int64_t cap, SubsetWork** out) {
@@ -707,21 +669,19 @@ as_status subset_work_create(const as_space* sp, int64_t cap, SubsetWork** out) 
     w->dp = sp->dp;
     if (hipDeviceGetAttribute(&w->cus, hipDeviceAttributeMultiprocessorCount, sp->device) != hipSuccess || w->cus <= 0) w->cus = 256;
     hipError_t e;
-    if ((e = hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking)) != hipSuccess ||
-        (e = hipMalloc((void**)&w->ids, sizeof(int32_t) * w->cap)) != hipSuccess ||
-        (e = hipMalloc((void**)&w->scores, sizeof(double) * w->cap)) != hipSuccess ||
-        (e = hipMalloc((void**)&w->q64, sizeof(double) * w->dp)) != hipSuccess ||
-        (e = hipMalloc((void**)&w->hist, sizeof(unsigned int) * SEL_HIST_WORDS)) != hipSuccess ||
-        (e = hipMalloc((void**)&w->state, sizeof(SubsetSel) * (SEL_PASSES + 1))) != hipSuccess ||
-        (e = hipMalloc((void**)&w->sel_pos, sizeof(int32_t) * SUBSET_TOPK)) != hipSuccess ||
-        (e = hipHostMalloc((void**)&w->hq, sizeof(double) * w->dp, hipHostMallocDefault)) != hipSuccess ||
-        (e = hipHostMalloc((void**)&w->out, sizeof(SubsetOut), hipHostMallocDefault)) != hipSuccess ||
-        (e = hipEventCreate(&w->ev[0])) != hipSuccess || (e = hipEventCreate(&w->ev[1])) != hipSuccess) {
-        set_err("subset: allocation of the work buffers (%lld ids) failed: %s", (long long)w->cap, hipGetErrorString(e));
-        subset_work_free(w);
-        return e == hipErrorOutOfMemory ? AS_ENOMEM : AS_EHIP;
+    as_status s = AS_OK;
+    if ((e = hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking)) != hipSuccess || (e = hipEventCreate(&w->ev[0])) != hipSuccess ||
+        (e = hipEventCreate(&w->ev[1])) != hipSuccess) {
+        set_err("subset: creation of the stream and events failed: %s", hipGetErrorString(e));
+        s = e == hipErrorOutOfMemory ? AS_ENOMEM : AS_EHIP;
     }
-    for (int64_t c = 0; c < w->dp; ++c) w->hq[c] = 0.0;
+    // what a single query needs: nothing is allocated per single query afterwards
+    if (s == AS_OK) s = reserve_or_err(w->ids, w->cap, "subset ids");
+    if (s == AS_OK) s = subset_reserve(w, 1, w->cap, 1, true, true);
+    if (s != AS_OK) {
+        subset_work_free(w);
+        return s;
+    }
     *out = w;
     return AS_OK;
 }
@@ -733,14 +693,21 @@ as_status subset_set_ids(SubsetWork* w, const int32_t* ids_host, int64_t m) {
     return AS_OK;
 }
 
+// the single query as row 0 of the query stage, uploaded (its dp doubles: the kernels take |q|^2 and lambda_q by value)
+static as_status subset_upload_query(const as_space* sp, SubsetWork* w, const double* query, double lambda_q) {
+    stage_queries(w->qh, query, 0, 1, 1, sp->d, w->dp, &lambda_q);
+    AS_HIP(hipMemcpyAsync(w->qd, w->qh, sizeof(double) * w->dp, hipMemcpyHostToDevice, w->stream));
+    return AS_OK;
+}
+
 // scores[i] = S11 score of item ids[i], i < m, queued on the work's stream (the query is uploaded in front of the kernel)
 as_status subset_score(const as_space* sp, SubsetWork* w, int64_t m, const double* query, double tau, double lambda_q) {
     if (m <= 0) return AS_OK;
-    for (int64_t c = 0; c < sp->d; ++c) w->hq[c] = query[c];   // (the pad stays zero)
-    AS_HIP(hipMemcpyAsync(w->q64, w->hq, sizeof(double) * w->dp, hipMemcpyHostToDevice, w->stream));
+    AS_TRY(subset_reserve(w, 1, w->cap, 1, true, true));   // (nothing to do unless a larger call's allocation failed)
+    AS_TRY(subset_upload_query(sp, w, query, lambda_q));
     SubsetArgs a;
-    a.ids = w->ids; a.m = m; a.x32 = sp->x32; a.x64 = sp->x64; a.n64 = sp->n64; a.lam64 = sp->lam64; a.q64 = w->q64;
-    a.scores = w->scores; a.d = sp->d; a.dp = sp->dp; a.nq = host_sumsq(query, sp->d); a.lq = lambda_q; a.tau = tau;
+    a.ids = w->ids; a.m = m; a.x32 = sp->x32; a.x64 = sp->x64; a.n64 = sp->n64; a.lam64 = sp->lam64; a.q64 = w->qd;
+    a.scores = w->scores; a.d = sp->d; a.dp = sp->dp; a.nq = w->qh[w->dp]; a.lq = lambda_q; a.tau = tau;
     const int64_t groups = (m + SUB_ROWS - 1) / SUB_ROWS;   // one per wave and trip
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((groups + 3) / 4, (int64_t)w->cus * SUB_BLOCKS_PER_CU));
     const bool qlds = sp->dp <= SUB_Q_LDS;
@@ -758,286 +725,39 @@ as_status subset_score(const as_space* sp, SubsetWork* w, int64_t m, const doubl
     return AS_OK;
 }
 
-static as_status subset_finish_timing(SubsetWork* w) {
-    if (w->timing) {
-        float ms = 0.0f;
-        AS_HIP(hipEventElapsedTime(&ms, w->ev[0], w->ev[1]));
-        w->kernel_us = (double)ms * 1e3;
-    }
-    return AS_OK;
+// waits for the stream; under timing the score kernel's time is added to kernel_us (fresh: replaces it -- the single-query forms)
+static as_status subset_wait(SubsetWork* w, bool fresh = false) {
+    if (fresh && w->timing) w->kernel_us = 0.0;
+    return sync_add_elapsed(w->stream, w->timing != 0, w->ev, &w->kernel_us);
 }
 
-// the first k of the m scores by (score descending, position ascending) -> ids and scores; waits for the stream
-as_status subset_select(SubsetWork* w, int64_t m, int64_t k, int64_t* out_idx, double* out_score, int64_t* out_len) {
-    *out_len = 0;
-    if (m <= 0 || k <= 0) return AS_OK;
-    k = std::min<int64_t>(std::min<int64_t>(k, m), SUBSET_TOPK);
+// The first k of each of `rows` rows of m scores ([rows][ld]) by (score descending, position ascending) -> w->out[row], queued on
+// the work's stream.  m <= SUBSET_TOPK: the sort alone; else one memset, the radix passes, collect and sort.
+static as_status subset_select_rows(SubsetWork* w, const double* scores, int64_t ld, int64_t m, int64_t k, int64_t rows) {
+    const unsigned ny = (unsigned)rows;
+    const int32_t* ids = w->ids;
+    SubsetOut* out = w->out;
     if (m <= SUBSET_TOPK) {
-        hipLaunchKernelGGL(subset_sort_kernel, dim3(1), dim3(1024), 0, w->stream, (const double*)w->scores, (const int32_t*)w->ids, m, (int)k,
-                           (const int32_t*)nullptr, (const unsigned int*)nullptr, w->out);
+        hipLaunchKernelGGL(subset_sort_batch_kernel, dim3(1, ny), dim3(1024), 0, w->stream, scores, ld, ids, m, (int)k, (const int32_t*)nullptr,
+                           (const unsigned int*)nullptr, out);
     } else {
-        AS_HIP(hipMemsetAsync(w->hist, 0, sizeof(unsigned int) * SEL_HIST_WORDS, w->stream));
-        const unsigned grid = (unsigned)std::min<int64_t>((m + 2047) / 2048, 512);
-        for (int p = 0; p < SEL_PASSES; ++p)
-            hipLaunchKernelGGL(subset_hist_kernel, dim3(grid), dim3(256), 0, w->stream, (const double*)w->scores, m, (int)k, p, w->state, w->hist);
-        hipLaunchKernelGGL(subset_collect_kernel, dim3(grid), dim3(256), 0, w->stream, (const double*)w->scores, m, (int)k, w->state, w->hist,
-                           w->sel_pos);
-        hipLaunchKernelGGL(subset_sort_kernel, dim3(1), dim3(1024), 0, w->stream, (const double*)w->scores, (const int32_t*)w->ids, m, (int)k,
-                           (const int32_t*)w->sel_pos, (const unsigned int*)(w->hist + (int64_t)SEL_PASSES * SEL_BINS), w->out);
-    }
-    AS_HIP(hipGetLastError());
-    AS_HIP(hipStreamSynchronize(w->stream));
-    AS_TRY(subset_finish_timing(w));
-    const int64_t len = w->out->len;
-    if (len != k) {
-        set_err("subset: the selection returned %lld of %lld entries", (long long)len, (long long)k);
-        return AS_EHIP;
-    }
-    for (int64_t t = 0; t < len; ++t) {
-        out_idx[t] = w->out->idx[t];
-        out_score[t] = w->out->score[t];
-    }
-    *out_len = len;
-    return AS_OK;
-}
-
-// the m scores themselves, in the order of the ids; waits for the stream
-as_status subset_scores_out(SubsetWork* w, int64_t m, double* out) {
-    if (m > 0) AS_HIP(hipMemcpyAsync(out, w->scores, sizeof(double) * m, hipMemcpyDeviceToHost, w->stream));
-    AS_HIP(hipStreamSynchronize(w->stream));
-    return m > 0 ? subset_finish_timing(w) : AS_OK;
-}
-
-// ------------------------------------------------------------------ batched forms
-// Queries per chunk: the largest multiple of the score kernel's query tile whose scores ([chunk][m] doubles) fit this budget, at
-// least one tile, at most SB_QC_MAX (the selection keeps 128 KiB of histograms and a 16 KiB pinned result per query).  Results
-// never depend on it.
-static std::atomic<int> g_subset_batch_mib{256};
-void set_subset_batch_mib(int v) { g_subset_batch_mib.store(v > 0 ? v : 256, std::memory_order_relaxed); }
-constexpr int64_t SB_QC_MAX = 4096;
-
-static as_status subset_batch_reserve(SubsetWork* w, int64_t nq, int64_t m, bool sel, bool hist) {
-    hipError_t e = hipSuccess;
-    const char* what = "queries";
-    if (nq > w->bq) {
-        subset_batch_release(w);
-        const size_t qbytes = sizeof(double) * (size_t)nq * (size_t)(w->dp + 2);
-        if ((e = hipMalloc((void**)&w->bqd, qbytes)) == hipSuccess && (e = hipHostMalloc((void**)&w->bqh, qbytes, hipHostMallocDefault)) == hipSuccess)
-            w->bq = nq;
-    }
-    if (e == hipSuccess && nq * m > w->bscores_n) {
-        what = "scores";
-        (void)hipFree(w->bscores);
-        w->bscores = nullptr;
-        w->bscores_n = 0;
-        if ((e = hipMalloc((void**)&w->bscores, sizeof(double) * (size_t)(w->bq * m))) == hipSuccess) w->bscores_n = w->bq * m;
-    }
-    if (e == hipSuccess && sel && !w->bsel) {
-        what = "results";
-        if ((e = hipHostMalloc((void**)&w->bout, sizeof(SubsetOut) * (size_t)w->bq, hipHostMallocDefault)) == hipSuccess) w->bsel = true;
-    }
-    if (e == hipSuccess && hist && !w->bhist_on) {
-        what = "selection";
-        if ((e = hipMalloc((void**)&w->bhist, sizeof(unsigned int) * SEL_HIST_WORDS * (size_t)w->bq)) == hipSuccess &&
-            (e = hipMalloc((void**)&w->bstate, sizeof(SubsetSel) * (SEL_PASSES + 1) * (size_t)w->bq)) == hipSuccess &&
-            (e = hipMalloc((void**)&w->bsel_pos, sizeof(int32_t) * SUBSET_TOPK * (size_t)w->bq)) == hipSuccess)
-            w->bhist_on = true;
-    }
-    if (e != hipSuccess) {
-        set_err("subset: allocation of the batched buffers (%s, %lld queries x %lld ids) failed: %s", what, (long long)nq, (long long)m,
-                hipGetErrorString(e));
-        subset_batch_release(w);
-        return e == hipErrorOutOfMemory ? AS_ENOMEM : AS_EHIP;
-    }
-    return AS_OK;
-}
-
-as_status subset_batch_run(const as_space* sp, SubsetWork* w, int64_t m, const double* queries, int64_t b, const double* lq,
-                           const int32_t* status, double tau, int64_t k, int64_t stride, int64_t* out_idx, double* out_score,
-                           int64_t* out_len, double* out_scores, const SubsetChunkSink* sink) {
-    if (m <= 0 || b <= 0) return AS_OK;
-    const bool sel = k > 0;
-    if (sel) k = std::min<int64_t>(std::min<int64_t>(k, m), SUBSET_TOPK);
-    const int64_t budget = (int64_t)g_subset_batch_mib.load(std::memory_order_relaxed) << 20;
-    int64_t qc = budget / (m * (int64_t)sizeof(double)) / SB_Q * SB_Q;
-    qc = std::min<int64_t>(std::max<int64_t>(qc, SB_Q), SB_QC_MAX);
-    qc = std::min<int64_t>(qc, (b + SB_Q - 1) / SB_Q * SB_Q);
-    const bool hist = sel && m > SUBSET_TOPK;
-    AS_TRY(subset_batch_reserve(w, qc, m, sel, hist));
-    const int64_t d = sp->d, dp = w->dp;
-    w->kernel_us = 0.0;
-    for (int64_t i0 = 0; i0 < b; i0 += qc) {
-        const int64_t nb = std::min<int64_t>(qc, b - i0), nbp = (nb + SB_Q - 1) / SB_Q * SB_Q;
-        double* hq = w->bqh;
-        double* hn = hq + nbp * dp;
-        double* hl = hn + nbp;
-        for (int64_t t = 0; t < nbp; ++t) {
-            double* row = hq + t * dp;
-            if (t < nb) {
-                const double* q = queries + (i0 + t) * d;
-                for (int64_t c = 0; c < d; ++c) row[c] = q[c];
-                for (int64_t c = d; c < dp; ++c) row[c] = 0.0;
-                hn[t] = host_sumsq(q, d);
-                hl[t] = lq[i0 + t];
-            } else {
-                for (int64_t c = 0; c < dp; ++c) row[c] = 0.0;
-                hn[t] = hl[t] = 0.0;
-            }
-        }
-        AS_HIP(hipMemcpyAsync(w->bqd, hq, sizeof(double) * (size_t)(nbp * (dp + 2)), hipMemcpyHostToDevice, w->stream));
-        SubsetBatchArgs a;
-        a.ids = w->ids; a.m = m; a.x32 = sp->x32; a.x64 = sp->x64; a.n64 = sp->n64; a.lam64 = sp->lam64; a.q64 = w->bqd;
-        a.nq = w->bqd + nbp * dp; a.lq = a.nq + nbp; a.scores = w->bscores; a.ld = m; a.d = d; a.dp = dp; a.nq_valid = (int)nb; a.tau = tau;
-        const dim3 grid((unsigned)((m + SB_ROWS - 1) / SB_ROWS), (unsigned)(nbp / SB_Q));
-        if (w->timing) AS_HIP(hipEventRecord(w->ev[0], w->stream));
-        if (sp->x64) hipLaunchKernelGGL(subset_score_batch_kernel<true>, grid, dim3(256), 0, w->stream, a);
-        else hipLaunchKernelGGL(subset_score_batch_kernel<false>, grid, dim3(256), 0, w->stream, a);
-        AS_HIP(hipGetLastError());
-        if (w->timing) AS_HIP(hipEventRecord(w->ev[1], w->stream));
-        if (sel) {
-            const unsigned ny = (unsigned)nb;
-            if (!hist) {
-                hipLaunchKernelGGL(subset_sort_batch_kernel, dim3(1, ny), dim3(1024), 0, w->stream, (const double*)w->bscores, m,
-                                   (const int32_t*)w->ids, m, (int)k, (const int32_t*)nullptr, (const unsigned int*)nullptr, w->bout);
-            } else {
-                AS_HIP(hipMemsetAsync(w->bhist, 0, sizeof(unsigned int) * SEL_HIST_WORDS * (size_t)nb, w->stream));
-                const unsigned gx = (unsigned)std::min<int64_t>((m + 2047) / 2048, 512);
-                for (int p = 0; p < SEL_PASSES; ++p)
-                    hipLaunchKernelGGL(subset_hist_batch_kernel, dim3(gx, ny), dim3(256), 0, w->stream, (const double*)w->bscores, m, m, (int)k, p,
-                                       w->bstate, w->bhist);
-                hipLaunchKernelGGL(subset_collect_batch_kernel, dim3(gx, ny), dim3(256), 0, w->stream, (const double*)w->bscores, m, m, (int)k,
-                                   w->bstate, w->bhist, w->bsel_pos);
-                hipLaunchKernelGGL(subset_sort_batch_kernel, dim3(1, ny), dim3(1024), 0, w->stream, (const double*)w->bscores, m,
-                                   (const int32_t*)w->ids, m, (int)k, (const int32_t*)w->bsel_pos, (const unsigned int*)w->bhist, w->bout);
-            }
-            AS_HIP(hipGetLastError());
-        } else if (sink) {
-            AS_TRY(sink->fn(sink->ctx, w, i0, nb, w->bscores, m));   // (it waits for the stream: the wait below finds it idle)
-        } else {
-            // one copy per chunk; a zero-lambda query's row stays unwritten: the copy is split around it
-            for (int64_t t = 0; t < nb;) {
-                if (status[i0 + t] == AS_EZEROLAMBDA) {
-                    ++t;
-                    continue;
-                }
-                int64_t u = t;
-                while (u < nb && status[i0 + u] != AS_EZEROLAMBDA) ++u;
-                AS_HIP(hipMemcpyAsync(out_scores + (i0 + t) * m, w->bscores + t * m, sizeof(double) * (size_t)((u - t) * m), hipMemcpyDeviceToHost,
-                                      w->stream));
-                t = u;
-            }
-        }
-        AS_HIP(hipStreamSynchronize(w->stream));
-        if (w->timing) {
-            float ms = 0.0f;
-            AS_HIP(hipEventElapsedTime(&ms, w->ev[0], w->ev[1]));
-            w->kernel_us += (double)ms * 1e3;
-        }
-        if (sel)
-            for (int64_t t = 0; t < nb; ++t) {
-                const int64_t i = i0 + t;
-                out_len[i] = 0;
-                if (status[i] == AS_EZEROLAMBDA) continue;
-                const SubsetOut* o = w->bout + t;
-                if (o->len != k) {
-                    set_err("subset: the selection returned %lld of %lld entries for query %lld", (long long)o->len, (long long)k, (long long)i);
-                    return AS_EHIP;
-                }
-                for (int64_t r = 0; r < k; ++r) {
-                    out_idx[i * stride + r] = o->idx[r];
-                    out_score[i * stride + r] = o->score[r];
-                }
-                out_len[i] = k;
-            }
-    }
-    return AS_OK;
-}
-
-// ------------------------------------------------------------------ tau sweeps (DESIGN.md section 5.11)
-// The sweep's buffers: nq queries (the batched sweep; 0: none), `pairs` score planes of m doubles, and for a selection one
-// pinned result per pair (sel) and the radix select's histograms, state and positions per pair (hist).
-static as_status subset_sweep_reserve(SubsetWork* w, int64_t nq, int64_t pairs, int64_t m, bool sel, bool hist) {
-    hipError_t e = hipSuccess;
-    const char* what = "queries";
-    if (nq > w->sw_nq) {
-        (void)hipFree(w->sw_qd);
-        if (w->sw_qh) (void)hipHostFree(w->sw_qh);
-        w->sw_qd = w->sw_qh = nullptr;
-        w->sw_nq = 0;
-        const size_t qbytes = sizeof(double) * (size_t)nq * (size_t)(w->dp + 2);
-        if ((e = hipMalloc((void**)&w->sw_qd, qbytes)) == hipSuccess && (e = hipHostMalloc((void**)&w->sw_qh, qbytes, hipHostMallocDefault)) == hipSuccess)
-            w->sw_nq = nq;
-    }
-    if (e == hipSuccess && pairs * m > w->sw_scores_n) {
-        what = "scores";
-        (void)hipFree(w->sw_scores);
-        w->sw_scores = nullptr;
-        w->sw_scores_n = 0;
-        if ((e = hipMalloc((void**)&w->sw_scores, sizeof(double) * (size_t)(pairs * m))) == hipSuccess) w->sw_scores_n = pairs * m;
-    }
-    if (e == hipSuccess && sel && pairs > w->sw_out_n) {
-        what = "results";
-        if (w->sw_out) (void)hipHostFree(w->sw_out);
-        w->sw_out = nullptr;
-        w->sw_out_n = 0;
-        if ((e = hipHostMalloc((void**)&w->sw_out, sizeof(SubsetOut) * (size_t)pairs, hipHostMallocDefault)) == hipSuccess) w->sw_out_n = pairs;
-    }
-    if (e == hipSuccess && hist && pairs > w->sw_hist_n) {
-        what = "selection";
-        (void)hipFree(w->sw_hist);
-        (void)hipFree(w->sw_state);
-        (void)hipFree(w->sw_sel_pos);
-        w->sw_hist = nullptr;
-        w->sw_state = nullptr;
-        w->sw_sel_pos = nullptr;
-        w->sw_hist_n = 0;
-        if ((e = hipMalloc((void**)&w->sw_hist, sizeof(unsigned int) * SEL_HIST_WORDS * (size_t)pairs)) == hipSuccess &&
-            (e = hipMalloc((void**)&w->sw_state, sizeof(SubsetSel) * (SEL_PASSES + 1) * (size_t)pairs)) == hipSuccess &&
-            (e = hipMalloc((void**)&w->sw_sel_pos, sizeof(int32_t) * SUBSET_TOPK * (size_t)pairs)) == hipSuccess)
-            w->sw_hist_n = pairs;
-    }
-    if (e != hipSuccess) {
-        set_err("subset: allocation of the sweep buffers (%s, %lld planes x %lld ids) failed: %s", what, (long long)pairs, (long long)m,
-                hipGetErrorString(e));
-        subset_sweep_release(w);
-        return e == hipErrorOutOfMemory ? AS_ENOMEM : AS_EHIP;
-    }
-    return AS_OK;
-}
-
-// the first k of each of the `pairs` score planes (stride m) -> w->sw_out[pair]: the batched forms' selection kernels with a
-// (query, tau) pair per blockIdx.y.  m <= SUBSET_TOPK: the sort alone; else one memset, the radix passes, collect and sort.
-static as_status subset_sweep_select(SubsetWork* w, int64_t m, int64_t k, int64_t pairs) {
-    const unsigned ny = (unsigned)pairs;
-    if (m <= SUBSET_TOPK) {
-        hipLaunchKernelGGL(subset_sort_batch_kernel, dim3(1, ny), dim3(1024), 0, w->stream, (const double*)w->sw_scores, m, (const int32_t*)w->ids,
-                           m, (int)k, (const int32_t*)nullptr, (const unsigned int*)nullptr, w->sw_out);
-    } else {
-        AS_HIP(hipMemsetAsync(w->sw_hist, 0, sizeof(unsigned int) * SEL_HIST_WORDS * (size_t)pairs, w->stream));
+        unsigned int* hist = w->hist;
+        SubsetSel* state = w->state;
+        int32_t* sel_pos = w->sel_pos;
+        AS_HIP(hipMemsetAsync(hist, 0, sizeof(unsigned int) * SEL_HIST_WORDS * (size_t)rows, w->stream));
         const unsigned gx = (unsigned)std::min<int64_t>((m + 2047) / 2048, 512);
         for (int p = 0; p < SEL_PASSES; ++p)
-            hipLaunchKernelGGL(subset_hist_batch_kernel, dim3(gx, ny), dim3(256), 0, w->stream, (const double*)w->sw_scores, m, m, (int)k, p,
-                               w->sw_state, w->sw_hist);
-        hipLaunchKernelGGL(subset_collect_batch_kernel, dim3(gx, ny), dim3(256), 0, w->stream, (const double*)w->sw_scores, m, m, (int)k,
-                           w->sw_state, w->sw_hist, w->sw_sel_pos);
-        hipLaunchKernelGGL(subset_sort_batch_kernel, dim3(1, ny), dim3(1024), 0, w->stream, (const double*)w->sw_scores, m, (const int32_t*)w->ids,
-                           m, (int)k, (const int32_t*)w->sw_sel_pos, (const unsigned int*)w->sw_hist, w->sw_out);
+            hipLaunchKernelGGL(subset_hist_batch_kernel, dim3(gx, ny), dim3(256), 0, w->stream, scores, ld, m, (int)k, p, state, hist);
+        hipLaunchKernelGGL(subset_collect_batch_kernel, dim3(gx, ny), dim3(256), 0, w->stream, scores, ld, m, (int)k, state, hist, sel_pos);
+        hipLaunchKernelGGL(subset_sort_batch_kernel, dim3(1, ny), dim3(1024), 0, w->stream, scores, ld, ids, m, (int)k, (const int32_t*)sel_pos,
+                           (const unsigned int*)hist, out);
     }
     AS_HIP(hipGetLastError());
     return AS_OK;
 }
 
-static as_status subset_sweep_wait(SubsetWork* w) {
-    AS_HIP(hipStreamSynchronize(w->stream));
-    if (w->timing) {
-        float ms = 0.0f;
-        AS_HIP(hipEventElapsedTime(&ms, w->ev[0], w->ev[1]));
-        w->kernel_us += (double)ms * 1e3;
-    }
-    return AS_OK;
-}
-
-static as_status subset_sweep_list(const SubsetOut* o, int64_t k, int64_t* out_idx, double* out_score, int64_t* out_len) {
+// a row's pinned result, k entries, to the caller's arrays
+static as_status subset_list_out(const SubsetOut* o, int64_t k, int64_t* out_idx, double* out_score, int64_t* out_len) {
     if (o->len != k) {
         set_err("subset: the selection returned %lld of %lld entries", (long long)o->len, (long long)k);
         return AS_EHIP;
@@ -1050,6 +770,86 @@ static as_status subset_sweep_list(const SubsetOut* o, int64_t k, int64_t* out_i
     return AS_OK;
 }
 
+// the first k of the m scores by (score descending, position ascending) -> ids and scores; waits for the stream
+as_status subset_select(SubsetWork* w, int64_t m, int64_t k, int64_t* out_idx, double* out_score, int64_t* out_len) {
+    *out_len = 0;
+    if (m <= 0 || k <= 0) return AS_OK;
+    k = std::min<int64_t>(std::min<int64_t>(k, m), SUBSET_TOPK);
+    AS_TRY(subset_select_rows(w, w->scores, m, m, k, 1));
+    AS_TRY(subset_wait(w, true));
+    return subset_list_out(w->out, k, out_idx, out_score, out_len);
+}
+
+// the m scores themselves, in the order of the ids; waits for the stream
+as_status subset_scores_out(SubsetWork* w, int64_t m, double* out) {
+    if (m <= 0) {
+        AS_HIP(hipStreamSynchronize(w->stream));
+        return AS_OK;
+    }
+    AS_HIP(hipMemcpyAsync(out, w->scores, sizeof(double) * m, hipMemcpyDeviceToHost, w->stream));
+    return subset_wait(w, true);
+}
+
+// ------------------------------------------------------------------ batched forms
+// Queries per chunk: the largest multiple of the score kernel's query tile whose scores ([chunk][m] doubles) fit this budget, at
+// least one tile, at most SB_QC_MAX (the selection keeps 128 KiB of histograms and a 16 KiB pinned result per query).  Results
+// never depend on it.
+static std::atomic<int> g_subset_batch_mib{256};
+void set_subset_batch_mib(int v) { g_subset_batch_mib.store(v > 0 ? v : 256, std::memory_order_relaxed); }
+constexpr int64_t SB_QC_MAX = 4096;
+
+as_status subset_batch_run(const as_space* sp, SubsetWork* w, int64_t m, const double* queries, int64_t b, const double* lq,
+                           const int32_t* status, double tau, int64_t k, int64_t stride, int64_t* out_idx, double* out_score,
+                           int64_t* out_len, double* out_scores, const SubsetChunkSink* sink) {
+    if (m <= 0 || b <= 0) return AS_OK;
+    const bool sel = k > 0;
+    if (sel) k = std::min<int64_t>(std::min<int64_t>(k, m), SUBSET_TOPK);
+    const int64_t budget = (int64_t)g_subset_batch_mib.load(std::memory_order_relaxed) << 20;
+    int64_t qc = budget / (m * (int64_t)sizeof(double)) / SB_Q * SB_Q;
+    qc = std::min<int64_t>(std::max<int64_t>(qc, SB_Q), SB_QC_MAX);
+    qc = std::min<int64_t>(qc, (b + SB_Q - 1) / SB_Q * SB_Q);
+    AS_TRY(subset_reserve(w, qc, qc * m, qc, sel, sel && m > SUBSET_TOPK));
+    const int64_t d = sp->d, dp = w->dp;
+    w->kernel_us = 0.0;
+    for (int64_t i0 = 0; i0 < b; i0 += qc) {
+        const int64_t nb = std::min<int64_t>(qc, b - i0), nbp = (nb + SB_Q - 1) / SB_Q * SB_Q;
+        stage_queries(w->qh, queries, i0, nb, nbp, d, dp, lq);
+        AS_HIP(hipMemcpyAsync(w->qd, w->qh, sizeof(double) * (size_t)(nbp * (dp + 2)), hipMemcpyHostToDevice, w->stream));
+        SubsetBatchArgs a;
+        a.ids = w->ids; a.m = m; a.x32 = sp->x32; a.x64 = sp->x64; a.n64 = sp->n64; a.lam64 = sp->lam64; a.q64 = w->qd;
+        a.nq = w->qd + nbp * dp; a.lq = a.nq + nbp; a.scores = w->scores; a.ld = m; a.d = d; a.dp = dp; a.nq_valid = (int)nb; a.tau = tau;
+        const dim3 grid((unsigned)((m + SB_ROWS - 1) / SB_ROWS), (unsigned)(nbp / SB_Q));
+        if (w->timing) AS_HIP(hipEventRecord(w->ev[0], w->stream));
+        if (sp->x64) hipLaunchKernelGGL(subset_score_batch_kernel<true>, grid, dim3(256), 0, w->stream, a);
+        else hipLaunchKernelGGL(subset_score_batch_kernel<false>, grid, dim3(256), 0, w->stream, a);
+        AS_HIP(hipGetLastError());
+        if (w->timing) AS_HIP(hipEventRecord(w->ev[1], w->stream));
+        if (sel) {
+            AS_TRY(subset_select_rows(w, w->scores, m, m, k, nb));
+        } else if (sink) {
+            AS_TRY(sink->fn(sink->ctx, w, i0, nb, w->scores, m));   // (it waits for the stream: the wait below finds it idle)
+        } else {
+            // one copy per run of served queries: a zero-lambda query's row stays unwritten
+            AS_TRY(for_served_runs(status, i0, nb, [&](int64_t t, int64_t u) -> as_status {
+                AS_HIP(hipMemcpyAsync(out_scores + (i0 + t) * m, w->scores + t * m, sizeof(double) * (size_t)((u - t) * m), hipMemcpyDeviceToHost,
+                                      w->stream));
+                return AS_OK;
+            }));
+        }
+        AS_TRY(subset_wait(w));
+        if (sel)
+            for (int64_t t = 0; t < nb; ++t) {
+                const int64_t i = i0 + t;
+                out_len[i] = 0;
+                if (status[i] == AS_EZEROLAMBDA) continue;
+                AS_TRY(subset_list_out(w->out + t, k, out_idx + i * stride, out_score + i * stride, out_len + i));
+            }
+    }
+    return AS_OK;
+}
+
+// ------------------------------------------------------------------ tau sweeps (DESIGN.md section 5.11)
+// A (query, tau) pair takes the place of a query of the batched forms: a row of the scores and of the selection.
 as_status subset_sweep_run(const as_space* sp, SubsetWork* w, int64_t m, const double* query, double lambda_q, const double* taus, int64_t nt,
                            const int64_t* row, int64_t k, int64_t* out_idx, double* out_score, int64_t* out_len, double* out_scores,
                            int64_t* counts) {
@@ -1057,12 +857,11 @@ as_status subset_sweep_run(const as_space* sp, SubsetWork* w, int64_t m, const d
     const bool sel = k > 0;
     if (sel) k = std::min<int64_t>(std::min<int64_t>(k, m), SUBSET_TOPK);
     const int64_t gmax = std::min<int64_t>(nt, TAU_GROUP);
-    AS_TRY(subset_sweep_reserve(w, 0, gmax, m, sel, sel && m > SUBSET_TOPK));
-    for (int64_t c = 0; c < sp->d; ++c) w->hq[c] = query[c];   // (the pad stays zero)
-    AS_HIP(hipMemcpyAsync(w->q64, w->hq, sizeof(double) * w->dp, hipMemcpyHostToDevice, w->stream));
+    AS_TRY(subset_reserve(w, 1, gmax * m, gmax, sel, sel && m > SUBSET_TOPK));
+    AS_TRY(subset_upload_query(sp, w, query, lambda_q));
     SubsetTausArgs a;
-    a.s.ids = w->ids; a.s.m = m; a.s.x32 = sp->x32; a.s.x64 = sp->x64; a.s.n64 = sp->n64; a.s.lam64 = sp->lam64; a.s.q64 = w->q64;
-    a.s.scores = w->sw_scores; a.s.d = sp->d; a.s.dp = sp->dp; a.s.nq = host_sumsq(query, sp->d); a.s.lq = lambda_q; a.s.tau = 0.0;
+    a.s.ids = w->ids; a.s.m = m; a.s.x32 = sp->x32; a.s.x64 = sp->x64; a.s.n64 = sp->n64; a.s.lam64 = sp->lam64; a.s.q64 = w->qd;
+    a.s.scores = w->scores; a.s.d = sp->d; a.s.dp = sp->dp; a.s.nq = w->qh[w->dp]; a.s.lq = lambda_q; a.s.tau = 0.0;
     a.ld = m;
     const int64_t groups = (m + SUB_ROWS - 1) / SUB_ROWS;   // (the grid of subset_score)
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((groups + 3) / 4, (int64_t)w->cus * SUB_BLOCKS_PER_CU));
@@ -1085,15 +884,15 @@ as_status subset_sweep_run(const as_space* sp, SubsetWork* w, int64_t m, const d
         if (w->timing) AS_HIP(hipEventRecord(w->ev[1], w->stream));
         counts[0] += 1;
         counts[1] += ng;
-        if (sel) AS_TRY(subset_sweep_select(w, m, k, ng));
+        if (sel) AS_TRY(subset_select_rows(w, w->scores, m, m, k, ng));
         else
             for (int64_t j = 0; j < ng; ++j)
-                AS_HIP(hipMemcpyAsync(out_scores + row[g0 + j] * m, w->sw_scores + j * m, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, w->stream));
-        AS_TRY(subset_sweep_wait(w));
+                AS_HIP(hipMemcpyAsync(out_scores + row[g0 + j] * m, w->scores + j * m, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, w->stream));
+        AS_TRY(subset_wait(w));
         if (sel)
             for (int64_t j = 0; j < ng; ++j) {
                 const int64_t r = row[g0 + j];
-                AS_TRY(subset_sweep_list(w->sw_out + j, k, out_idx + r * k, out_score + r * k, out_len + r));
+                AS_TRY(subset_list_out(w->out + j, k, out_idx + r * k, out_score + r * k, out_len + r));
             }
     }
     return AS_OK;
@@ -1113,31 +912,16 @@ as_status subset_batch_sweep_run(const as_space* sp, SubsetWork* w, int64_t m, c
     int64_t qc = budget / (m * tg * (int64_t)sizeof(double)) / SB_Q * SB_Q;
     qc = std::min<int64_t>(std::max<int64_t>(qc, SB_Q), SB_QC_MAX / tg / SB_Q * SB_Q);
     qc = std::min<int64_t>(qc, (b + SB_Q - 1) / SB_Q * SB_Q);
-    AS_TRY(subset_sweep_reserve(w, qc, qc * tg, m, sel, sel && m > SUBSET_TOPK));
+    AS_TRY(subset_reserve(w, qc, qc * tg * m, qc * tg, sel, sel && m > SUBSET_TOPK));
     const int64_t d = sp->d, dp = w->dp;
     w->kernel_us = 0.0;
     for (int64_t i0 = 0; i0 < b; i0 += qc) {
         const int64_t nb = std::min<int64_t>(qc, b - i0), nbp = (nb + SB_Q - 1) / SB_Q * SB_Q;
-        double* hq = w->sw_qh;
-        double* hn = hq + nbp * dp;
-        double* hl = hn + nbp;
-        for (int64_t t = 0; t < nbp; ++t) {   // (the staging of subset_batch_run: the same |q|^2, the same operands)
-            double* qrow = hq + t * dp;
-            if (t < nb) {
-                const double* q = queries + (i0 + t) * d;
-                for (int64_t c = 0; c < d; ++c) qrow[c] = q[c];
-                for (int64_t c = d; c < dp; ++c) qrow[c] = 0.0;
-                hn[t] = host_sumsq(q, d);
-                hl[t] = lq[i0 + t];
-            } else {
-                for (int64_t c = 0; c < dp; ++c) qrow[c] = 0.0;
-                hn[t] = hl[t] = 0.0;
-            }
-        }
-        AS_HIP(hipMemcpyAsync(w->sw_qd, hq, sizeof(double) * (size_t)(nbp * (dp + 2)), hipMemcpyHostToDevice, w->stream));
+        stage_queries(w->qh, queries, i0, nb, nbp, d, dp, lq);
+        AS_HIP(hipMemcpyAsync(w->qd, w->qh, sizeof(double) * (size_t)(nbp * (dp + 2)), hipMemcpyHostToDevice, w->stream));
         SubsetBatchTausArgs a;
-        a.s.ids = w->ids; a.s.m = m; a.s.x32 = sp->x32; a.s.x64 = sp->x64; a.s.n64 = sp->n64; a.s.lam64 = sp->lam64; a.s.q64 = w->sw_qd;
-        a.s.nq = w->sw_qd + nbp * dp; a.s.lq = a.s.nq + nbp; a.s.scores = w->sw_scores; a.s.ld = m; a.s.d = d; a.s.dp = dp;
+        a.s.ids = w->ids; a.s.m = m; a.s.x32 = sp->x32; a.s.x64 = sp->x64; a.s.n64 = sp->n64; a.s.lam64 = sp->lam64; a.s.q64 = w->qd;
+        a.s.nq = w->qd + nbp * dp; a.s.lq = a.s.nq + nbp; a.s.scores = w->scores; a.s.ld = m; a.s.d = d; a.s.dp = dp;
         a.s.nq_valid = (int)nb; a.s.tau = 0.0;
         const dim3 grid((unsigned)((m + SB_ROWS - 1) / SB_ROWS), (unsigned)(nbp / SB_Q));
         for (int64_t g0 = 0; g0 < nt; g0 += tg) {
@@ -1151,31 +935,25 @@ as_status subset_batch_sweep_run(const as_space* sp, SubsetWork* w, int64_t m, c
             if (w->timing) AS_HIP(hipEventRecord(w->ev[1], w->stream));
             counts[0] += 1;
             counts[1] += ng;
-            if (sel) AS_TRY(subset_sweep_select(w, m, k, nb * ng));
+            if (sel) AS_TRY(subset_select_rows(w, w->scores, m, m, k, nb * ng));
             else {
-                // plane j of every query of a run in one strided copy; a zero-lambda query's rows stay unwritten: runs split around it
-                for (int64_t t = 0; t < nb;) {
-                    if (status[i0 + t] == AS_EZEROLAMBDA) {
-                        ++t;
-                        continue;
-                    }
-                    int64_t u = t;
-                    while (u < nb && status[i0 + u] != AS_EZEROLAMBDA) ++u;
+                // plane j of every query of a run of served queries in one strided copy: a zero-lambda query's rows stay unwritten
+                AS_TRY(for_served_runs(status, i0, nb, [&](int64_t t, int64_t u) -> as_status {
                     for (int64_t j = 0; j < ng; ++j)
                         AS_HIP(hipMemcpy2DAsync(out_scores + ((i0 + t) * ntau + row[g0 + j]) * m, sizeof(double) * (size_t)(ntau * m),
-                                                w->sw_scores + (t * ng + j) * m, sizeof(double) * (size_t)(ng * m), sizeof(double) * (size_t)m,
+                                                w->scores + (t * ng + j) * m, sizeof(double) * (size_t)(ng * m), sizeof(double) * (size_t)m,
                                                 (size_t)(u - t), hipMemcpyDeviceToHost, w->stream));
-                    t = u;
-                }
+                    return AS_OK;
+                }));
             }
-            AS_TRY(subset_sweep_wait(w));
+            AS_TRY(subset_wait(w));
             if (sel)
                 for (int64_t t = 0; t < nb; ++t) {
                     const int64_t i = i0 + t;
                     if (status[i] == AS_EZEROLAMBDA) continue;   // (its out_len entries are zero already)
                     for (int64_t j = 0; j < ng; ++j) {
                         const int64_t r = i * ntau + row[g0 + j];
-                        AS_TRY(subset_sweep_list(w->sw_out + t * ng + j, k, out_idx + r * k, out_score + r * k, out_len + r));
+                        AS_TRY(subset_list_out(w->out + t * ng + j, k, out_idx + r * k, out_score + r * k, out_len + r));
                     }
                 }
         }
