@@ -476,6 +476,8 @@ void as_enable_search_stats(int32_t enabled);
  * the per-query list forms chunk by it too.  "lists_timing" = 1 / 0: HIP events around their score kernel (as_lists_kernel_us).
  * "range_cap" = entries of the append buffer a range call starts with (default 65 536, or what earlier overflows grew the buffer
  * to; <= 0: the default); "range_timing" = 1 / 0: HIP events around the range forms' compaction kernel (as_range_kernel_us).
+ * "diverse_chunk" = queries per launch of the diversified forms (default 4096; <= 0: the default); "diverse_timing" = 1 / 0: HIP
+ * events around their select kernel (as_diverse_kernel_us).
  * Returns 0, or 1 for an unknown key.  Results never depend on it. */
 int32_t as_set_tuning(const char* key, int32_t value);
 /* same, for the workspace as_search keeps inside the space (last as_search call) */
@@ -681,6 +683,39 @@ as_status as_range_counters(const as_space* sp, int64_t* out, int32_t n);
 /* measurement: the device microseconds of the compaction kernel, summed over the launches of the last range call on this space
  * that ran under as_set_tuning("range_timing", 1) (HIP events around the kernel; off by default) */
 double as_range_kernel_us(const as_space* sp);
+/* ---- Extension: diversified search (greedy maximal marginal relevance).  The POOL is the hit list of the ordinary
+ * route in its order (score descending, index ascending): as_search's, or as_search_subset's with sub != NULL; batched:
+ * as_search_batch's / as_search_subset_batch's lists.  Its size P is at most the index's topk: build with topk = the pool you
+ * want, <= 1024.  With g(i, j) the cosine of items i and j (fp64 dot of the rows the filtered forms gather over the square root of
+ * the product of the stored squared norms; 0 when that product is 0; not clamped: negative cosines count), r_p the largest g of
+ * pool entry p with an entry picked so far (0 while nothing is picked) and s_p its score, step t = 0 .. min(n, P) - 1 picks the
+ * unselected p with the largest margin m_p = (1 - diversity) s_p - diversity r_p in fp64; ties go to the smallest p, a NaN margin
+ * counts as -inf.  Entry t of the answer: out_idx[t] the item, out_score[t] its S11 score with the route's bits, out_margin[t]
+ * (out_margin may be NULL) the margin it was picked with; *out_len = min(n, P).  diversity == 0 returns the first min(n, P) pool
+ * entries bit for bit; the first pick is always pool entry 0; n >= P returns the whole pool in MMR order.  The outputs hold
+ * min(n, topk') entries (topk' = min(topk, nitems), with a subset min(topk', |S|)); the batched form writes list i at stride
+ * nn = min(n, topk') and out_len[i].
+ * Checked before anything is launched: a null argument ("<name>: null argument", nothing written), n < 1, a diversity that is NaN
+ * or outside [0, 1], a subset of another space, wrong d, a non-finite tau -> AS_EINVAL; a shard of a row-sharded index ->
+ * AS_EUNSUPPORTED (codes and messages of as_search_subset).  Cost: ONE ordinary search of the route per call (batched: ONE batched
+ * search over all b queries): the pool, lambda_q, the escalations and AS_EZEROLAMBDA are that call's (batched: in out_status[i],
+ * that query gets out_len 0, the others are served); then per chunk of queries ("diverse_chunk", default 4096; <= 0: the default;
+ * results never depend on it) one upload of the pools, ONE launch in which a block per query runs the whole greedy -- per step
+ * the cosines of the unselected rows with the row just picked, (min(n, P) - 1) P row reads at most, no P x P matrix -- one
+ * download and one stream wait.  b == 0 launches nothing.  The buffers live in the space and grow on demand; the selection steps
+ * of calls on one space are serialised, as_search runs beside them.  out_lambda_q and out_status may be NULL. */
+as_status as_search_diverse(const as_space* sp, const as_graph* gr, const double* query, int64_t d, double tau, int64_t n, double diversity,
+                            const as_subset* sub, int64_t* out_idx, double* out_score, double* out_margin, int64_t* out_len,
+                            double* out_lambda_q);
+as_status as_search_diverse_batch(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau, int64_t n,
+                                  double diversity, const as_subset* sub, int64_t* out_idx, double* out_score, double* out_margin,
+                                  int64_t* out_len, double* out_lambda_q, int32_t* out_status);
+/* out[0] calls of the two entries above that passed their checks, [1] select launches, [2] picks made, [3] item-item dots computed,
+ * [4] pool steps run (ordinary searches, single or batched) */
+as_status as_diverse_counters(const as_space* sp, int64_t* out, int32_t n);
+/* measurement: the device microseconds of the select kernel, summed over the chunks of the last diversified call on this space
+ * that ran under as_set_tuning("diverse_timing", 1) (HIP events around the kernel; off by default) */
+double as_diverse_kernel_us(const as_space* sp);
 
 /* ---- index persistence (extension; the reference exposes none): one flat file
  * holding the items, lambdas and graph arrays.  Loading re-ingests the items and uploads the

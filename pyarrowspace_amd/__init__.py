@@ -623,6 +623,87 @@ class ArrowSpace:
             _raise(st)
         return dict(zip(("calls", "compactions", "scores_examined", "survivors", "relaunches", "lambda_steps"), list(out)))
 
+    @staticmethod
+    def _diverse_params(n, diversity) -> tuple[int, float]:
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
+            raise TypeError("argument 'n': expected an integer")
+        if n < 1:
+            raise ValueError(f"n must be >= 1, got {n}")
+        delta = float(diversity)
+        if not 0.0 <= delta <= 1.0:   # (NaN fails both comparisons)
+            raise ValueError(f"diversity must lie in [0, 1], got {diversity}")
+        return int(n), delta
+
+    def search_diverse(self, item, gl: GraphLaplacian, tau: float, n: int, diversity: float, subset=None, with_margins=False):
+        """Extension: diversified search (greedy maximal marginal relevance) -> list[(index, score)], or list[(index, score,
+        margin)] with `with_margins`: min(n, P) items of the POOL, the hit list of `search` (of `search_subset` with a subset;
+        P <= topk: build with topk = the pool you want, <= 1024).  Each step picks the unselected pool entry with the largest
+        margin (1 - diversity) * score - diversity * (largest cosine with an item picked so far; 0 for the first pick), ties to
+        the earlier pool entry; cosines are not clamped.  diversity = 0 returns the first entries of the pool as they are; the
+        first pick is always the pool's best hit; scores are the pool's, bit for bit.  n < 1 and a diversity outside [0, 1]
+        raise ValueError.  Costs one ordinary `search` / `search_subset` (a query whose lambda_q is 0 panics as there) plus
+        one upload of the pool, one launch that runs the whole greedy on the device and one download."""
+        if not isinstance(gl, GraphLaplacian):
+            raise TypeError("argument 'gl': expected GraphLaplacian")
+        q = self._query(item)
+        n, delta = self._diverse_params(n, diversity)
+        sub = subset if subset is None or isinstance(subset, ItemSubset) else self.subset(subset)
+        kk = min(int(gl.graph_params["topk"]), self.nitems, self.nitems if sub is None else sub.size)
+        nn = max(min(n, kk), 1)
+        idx = np.empty(nn, dtype=np.int64)
+        sc = np.empty(nn, dtype=np.float64)
+        mg = np.empty(nn, dtype=np.float64)
+        ln, lq = C.c_int64(0), C.c_double(0.0)
+        st = _L.as_search_diverse(self._h, gl._h, q.ctypes.data, q.shape[0], float(tau), n, delta, None if sub is None else sub._h,
+                                  idx.ctypes.data, sc.ctypes.data, mg.ctypes.data, C.byref(ln), C.byref(lq))
+        if st:
+            _raise(st)
+        k = ln.value
+        if with_margins:
+            return list(zip(idx[:k].tolist(), sc[:k].tolist(), mg[:k].tolist()))
+        return list(zip(idx[:k].tolist(), sc[:k].tolist()))
+
+    def search_batch_diverse(self, items, gl: GraphLaplacian, tau: float, n: int, diversity: float, subset=None, with_margins=False):
+        """Extension: batched diversified search, B queries [B, D] -> list of B lists; list i is what `search_diverse` returns
+        over the pool `search_batch` (with a subset: `search_batch_subset`) gives query i.  A query whose lambda_q is 0 gets
+        an empty list, the others are served.  Costs one `search_batch` / `search_batch_subset` over the B queries, then per
+        4096 queries one upload of the pools, one launch (a block per query runs its whole greedy) and one download."""
+        if not isinstance(gl, GraphLaplacian):
+            raise TypeError("argument 'gl': expected GraphLaplacian")
+        Q = np.ascontiguousarray(items, dtype=np.float64)
+        if Q.ndim != 2:
+            raise TypeError("items must be a 2-D float64 array")
+        n, delta = self._diverse_params(n, diversity)
+        sub = subset if subset is None or isinstance(subset, ItemSubset) else self.subset(subset)
+        b = Q.shape[0]
+        kk = min(int(gl.graph_params["topk"]), self.nitems, self.nitems if sub is None else sub.size)
+        nn = max(min(n, kk), 0)
+        idx = np.empty((max(b, 1), max(nn, 1)), dtype=np.int64)
+        sc = np.empty((max(b, 1), max(nn, 1)), dtype=np.float64)
+        mg = np.empty((max(b, 1), max(nn, 1)), dtype=np.float64)
+        ln = np.zeros(max(b, 1), dtype=np.int64)
+        stt = np.zeros(max(b, 1), dtype=np.int32)
+        st = _L.as_search_diverse_batch(self._h, gl._h, Q.ctypes.data_as(C.c_void_p), b, Q.shape[1], float(tau), n, delta,
+                                        None if sub is None else sub._h, idx.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p),
+                                        mg.ctypes.data_as(C.c_void_p), ln.ctypes.data_as(C.c_void_p), None, stt.ctypes.data_as(C.c_void_p))
+        if st:
+            _raise(st)
+        if nn == 0:
+            return [[] for _ in range(b)]
+        # (the C ABI's lists are at stride nn)
+        idx, sc, mg = (a.reshape(-1)[:b * nn].reshape(b, nn).tolist() for a in (idx, sc, mg))
+        if with_margins:
+            return [list(zip(ii[:l], ss[:l], mm[:l])) for ii, ss, mm, l in zip(idx, sc, mg, ln[:b].tolist())]
+        return [list(zip(ii[:l], ss[:l])) for ii, ss, l in zip(idx, sc, ln[:b].tolist())]
+
+    def diverse_counters(self) -> dict:
+        """Extension: diversified calls on this space since it was made and the work they launched."""
+        out = (C.c_int64 * 5)()
+        st = _L.as_diverse_counters(self._h, out, 5)
+        if st:
+            _raise(st)
+        return dict(zip(("calls", "launches", "picks", "dots", "pool_steps"), list(out)))
+
     def _lists_args(self, items, gl, lists):
         if not isinstance(gl, GraphLaplacian):
             raise TypeError("argument 'gl': expected GraphLaplacian")

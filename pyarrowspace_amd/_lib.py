@@ -58,6 +58,7 @@ SYMBOLS = [
     "as_score_lists_batch_taus", "as_search_lists_batch_taus", "as_lists_sweep_counters",
     "as_search_range", "as_search_range_batch", "as_range_queries", "as_range_total", "as_range_offsets", "as_range_copy", "as_range_free",
     "as_range_counters", "as_range_kernel_us",
+    "as_search_diverse", "as_search_diverse_batch", "as_diverse_counters", "as_diverse_kernel_us",
 ]
 
 _lib = None
@@ -239,6 +240,10 @@ def load():
         "as_range_free": (None, [vp]),
         "as_range_counters": (i32, [vp, vp, i32]),
         "as_range_kernel_us": (f64, [vp]),
+        "as_search_diverse": (i32, [vp, vp, vp, i64, f64, i64, f64, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(f64)]),
+        "as_search_diverse_batch": (i32, [vp, vp, vp, i64, i64, f64, i64, f64, vp, vp, vp, vp, vp, vp, vp]),
+        "as_diverse_counters": (i32, [vp, vp, i32]),
+        "as_diverse_kernel_us": (f64, [vp]),
         "as_subset_set_timing": (None, [vp, i32]),
         "as_subset_kernel_us": (f64, [vp]),
         "as_gang_counters": (i32, [vp, vp, i32]),

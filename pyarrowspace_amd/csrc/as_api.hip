@@ -156,6 +156,7 @@ void as_free_space(as_space* sp) {
     subset_work_free(sp->score_ws);
     as_subset_free(sp->range_all);
     lists_work_free(sp->lists_ws);
+    diverse_work_free(sp->diverse_ws);
     if (sp->stream) hipStreamSynchronize(sp->stream);
     hipFree(sp->x32); hipFree(sp->xs); hipFree(sp->x8); hipFree(sp->x8h); hipFree(sp->x4); hipFree(sp->fa4); hipFree(sp->fa8); hipFree(sp->x64); hipFree(sp->n64); hipFree(sp->n32); hipFree(sp->inorm32);
     hipFree(sp->lam64); hipFree(sp->lam32);
@@ -1568,6 +1569,119 @@ as_status as_range_counters(const as_space* sp, int64_t* out, int32_t n) {
     return AS_OK;
 }
 double as_range_kernel_us(const as_space* sp) { return sp ? sp->range_us.load(std::memory_order_relaxed) : 0.0; }
+
+// ---------------------------------------------------------------- diversified search (extension; as_diverse.hip)
+// what both forms refuse before anything is launched, the pool step included
+static as_status diverse_checks(const char* who, const as_space* sp, const as_graph* gr, int64_t d, double tau, int64_t n, double diversity,
+                                const as_subset* sub) {
+    if (n < 1) {
+        set_err("%s: n must be >= 1, got %lld", who, (long long)n);
+        return AS_EINVAL;
+    }
+    if (!(diversity >= 0.0 && diversity <= 1.0)) {
+        set_err("%s: diversity must lie in [0, 1], got %g", who, diversity);
+        return AS_EINVAL;
+    }
+    if (sub && sub->sp != sp) {
+        set_err("%s: the subset was made for another space", who);
+        return AS_EINVAL;
+    }
+    return subset_checks(who, sp, gr, d, &tau, 1);
+}
+static void diverse_counts_add(const as_space* sp, const int64_t* counts) {
+    for (int i = 0; i < 3; ++i) sp->diverse_count[1 + i].fetch_add(counts[i], std::memory_order_relaxed);
+}
+
+as_status as_search_diverse(const as_space* sp, const as_graph* gr, const double* query, int64_t d, double tau, int64_t n, double diversity,
+                            const as_subset* sub, int64_t* out_idx, double* out_score, double* out_margin, int64_t* out_len,
+                            double* out_lambda_q) {
+    if (!sp || !gr || !query || !out_idx || !out_score || !out_len) {
+        set_err("as_search_diverse: null argument");
+        return AS_EINVAL;
+    }
+    *out_len = 0;
+    AS_TRY(diverse_checks("as_search_diverse", sp, gr, d, tau, n, diversity, sub));
+    sp->diverse_count[0].fetch_add(1, std::memory_order_relaxed);
+    // the pool: ONE ordinary search of the route, its hits in its order
+    int64_t pidx[SUBSET_TOPK], plen = 0;
+    double psc[SUBSET_TOPK];
+    double lq = 0.0;
+    sp->diverse_count[4].fetch_add(1, std::memory_order_relaxed);
+    const as_status s = sub ? as_search_subset(sp, gr, query, d, tau, sub, pidx, psc, &plen, &lq)
+                            : search_pooled(sp, gr, query, d, tau, pidx, psc, &plen, &lq);
+    if (out_lambda_q) *out_lambda_q = lq;
+    if (s != AS_OK) return s;
+    if (plen <= 0) return AS_OK;
+    int64_t counts[3] = {0, 0, 0};
+    std::lock_guard<std::mutex> lk(sp->dmu);
+    AS_HIP(hipSetDevice(sp->device));
+    // (a stride of plen: the single form's outputs hold min(n, plen) entries)
+    const as_status s2 = diverse_run(sp, pidx, psc, &plen, plen, 1, n, diversity, out_idx, out_score, out_margin, out_len, counts);
+    diverse_counts_add(sp, counts);
+    return s2;
+}
+
+as_status as_search_diverse_batch(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau, int64_t n,
+                                  double diversity, const as_subset* sub, int64_t* out_idx, double* out_score, double* out_margin,
+                                  int64_t* out_len, double* out_lambda_q, int32_t* out_status) {
+    if (!sp || !gr || b < 0 || (b > 0 && (!queries || !out_len))) {
+        set_err("as_search_diverse_batch: null argument");
+        return AS_EINVAL;
+    }
+    const int64_t kk = std::min<int64_t>(std::min<int64_t>(gr->gp.topk, sp->n), sub ? sub->m : sp->n);
+    if (b > 0 && kk > 0 && (!out_idx || !out_score)) {
+        set_err("as_search_diverse_batch: null argument");
+        return AS_EINVAL;
+    }
+    for (int64_t i = 0; i < b; ++i) out_len[i] = 0;
+    AS_TRY(diverse_checks("as_search_diverse_batch", sp, gr, d, tau, n, diversity, sub));
+    sp->diverse_count[0].fetch_add(1, std::memory_order_relaxed);
+    if (b == 0) return AS_OK;
+    // the pools: ONE batched search of the route over all b queries, every list at stride kk
+    const int64_t kks = std::max<int64_t>(kk, 1);
+    std::vector<int64_t> pidx, plen;
+    std::vector<double> psc, lq;
+    std::vector<int32_t> st;
+    try {
+        pidx.resize((size_t)(b * kks));
+        psc.resize((size_t)(b * kks));
+        plen.assign((size_t)b, 0);
+        lq.assign((size_t)b, 0.0);
+        st.assign((size_t)b, 0);
+    } catch (const std::bad_alloc&) {
+        set_err("as_search_diverse_batch: out of host memory for %lld queries", (long long)b);
+        return AS_ENOMEM;
+    }
+    sp->diverse_count[4].fetch_add(1, std::memory_order_relaxed);
+    AS_TRY(sub ? as_search_subset_batch(sp, gr, queries, b, d, tau, sub, pidx.data(), psc.data(), plen.data(), lq.data(), st.data())
+               : as_search_batch(sp, gr, queries, b, d, tau, pidx.data(), psc.data(), plen.data(), lq.data(), st.data()));
+    for (int64_t i = 0; i < b; ++i) {
+        if (out_lambda_q) out_lambda_q[i] = lq[i];
+        if (out_status) out_status[i] = st[i];
+        if (st[i] == AS_EZEROLAMBDA) plen[i] = 0;
+    }
+    if (kk == 0) return AS_OK;
+    int64_t counts[3] = {0, 0, 0};
+    std::lock_guard<std::mutex> lk(sp->dmu);
+    AS_HIP(hipSetDevice(sp->device));
+    const as_status s2 = diverse_run(sp, pidx.data(), psc.data(), plen.data(), kk, b, n, diversity, out_idx, out_score, out_margin, out_len, counts);
+    diverse_counts_add(sp, counts);
+    return s2;
+}
+
+as_status as_diverse_counters(const as_space* sp, int64_t* out, int32_t n) {
+    if (!sp || !out) {
+        set_err("as_diverse_counters: null argument");
+        return AS_EINVAL;
+    }
+    for (int i = 0; i < n && i < 5; ++i) out[i] = sp->diverse_count[i].load(std::memory_order_relaxed);
+    return AS_OK;
+}
+double as_diverse_kernel_us(const as_space* sp) {
+    if (!sp) return 0.0;
+    std::lock_guard<std::mutex> lk(sp->dmu);
+    return diverse_kernel_us(sp->diverse_ws);
+}
 
 // ---------------------------------------------------------------- per-query candidate lists (extension)
 // What both forms check before anything is launched, the lambda_q step included: the offsets, the total, every id.

@@ -47,7 +47,7 @@ void dbg(const char* fmt, ...);
 
 }  // namespace as
 
-namespace as { struct SubsetWork; struct ListsWork; struct RangeWork; }
+namespace as { struct SubsetWork; struct ListsWork; struct RangeWork; struct DiverseWork; }
 struct as_subset;
 
 // ---------------------------------------------------------------- handles
@@ -174,6 +174,13 @@ struct as_space {
     mutable std::mutex rmu;
     mutable std::atomic<int64_t> range_count[6] = {};
     mutable std::atomic<double> range_us{0.0};
+    // as_search_diverse / as_search_diverse_batch: their buffers (as_diverse.hip), made on first use and grown on demand; the
+    // selection step of a call is serialised by dmu (the pool step before it is an ordinary search and takes no lock of these).
+    // as_diverse_counters: [0] calls that passed their checks, [1] select launches, [2] picks made, [3] dots computed, [4] pool
+    // steps run (ordinary searches, single or batched)
+    mutable struct as::DiverseWork* diverse_ws = nullptr;
+    mutable std::mutex dmu;
+    mutable std::atomic<int64_t> diverse_count[5] = {};
 };
 
 struct as_graph {
@@ -781,5 +788,17 @@ as_status range_compact(SubsetWork* w, const double* scores, int64_t ld, int64_t
 void range_work_free(RangeWork* r);
 void set_range_cap(int v);      // as_set_tuning("range_cap", v)
 void set_range_timing(int v);   // as_set_tuning("range_timing", 0 | 1)
+// Diversified search (as_diverse.hip): the greedy of S12 over b pools -- pool i = pool_idx / pool_score + i * kk,
+// pool_len[i] <= kk entries in the order the route returned them (0: a query that is not served) -- n picks wanted, diversity delta.
+// Pick t of query i -> out_idx / out_score / out_margin (may be null) + i * nn + t, nn = min(n, kk); out_len[i] = min(n, pool_len[i]).
+// The ids and scores handed out are the pool's own (the kernel returns positions).  Chunks of "diverse_chunk" queries: one upload,
+// one launch, one download, one stream wait each.  counts[0] += launches, [1] += picks, [2] += dots.  The buffers live in
+// sp->diverse_ws (under sp->dmu).
+as_status diverse_run(const as_space* sp, const int64_t* pool_idx, const double* pool_score, const int64_t* pool_len, int64_t kk, int64_t b,
+                      int64_t n, double delta, int64_t* out_idx, double* out_score, double* out_margin, int64_t* out_len, int64_t* counts);
+void diverse_work_free(DiverseWork* w);
+double diverse_kernel_us(const DiverseWork* w);
+void set_diverse_timing(int v);   // as_set_tuning("diverse_timing", 0 | 1)
+void set_diverse_chunk(int v);    // as_set_tuning("diverse_chunk", v)
 
 }  // namespace as

@@ -3643,6 +3643,14 @@ int32_t as_set_tuning(const char* key, int32_t value) {
         set_range_timing(value);
         return 0;
     }
+    if (key && !strcmp(key, "diverse_chunk")) {
+        set_diverse_chunk(value);
+        return 0;
+    }
+    if (key && !strcmp(key, "diverse_timing")) {
+        set_diverse_timing(value);
+        return 0;
+    }
     return 1;
 }
 
