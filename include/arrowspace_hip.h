@@ -477,7 +477,8 @@ void as_enable_search_stats(int32_t enabled);
  * "range_cap" = entries of the append buffer a range call starts with (default 65 536, or what earlier overflows grew the buffer
  * to; <= 0: the default); "range_timing" = 1 / 0: HIP events around the range forms' compaction kernel (as_range_kernel_us).
  * "diverse_chunk" = queries per launch of the diversified forms (default 4096; <= 0: the default); "diverse_timing" = 1 / 0: HIP
- * events around their select kernel (as_diverse_kernel_us).
+ * events around their select kernel (as_diverse_kernel_us).  "fused_timing" = 1 / 0: HIP events around the fused forms'
+ * accumulate kernel (as_fused_kernel_us).
  * Returns 0, or 1 for an unknown key.  Results never depend on it. */
 int32_t as_set_tuning(const char* key, int32_t value);
 /* same, for the workspace as_search keeps inside the space (last as_search call) */
@@ -716,6 +717,42 @@ as_status as_diverse_counters(const as_space* sp, int64_t* out, int32_t n);
 /* measurement: the device microseconds of the select kernel, summed over the chunks of the last diversified call on this space
  * that ran under as_set_tuning("diverse_timing", 1) (HIP events around the kernel; off by default) */
 double as_diverse_kernel_us(const as_space* sp);
+/* ---- Extension: fused multi-query search.  ONE answer to j >= 1 query vectors, row-major [j][d] in HOST memory,
+ * with finite weights w (weights == NULL: 1/j each; negative weights are legal).  s_v(i): the S11 score of item i for vector v
+ * with the bits as_score_items_batch writes at [v][i] (lambda_q of every vector from ONE as_search_batch over the j vectors, the
+ * dot from the batched score kernel).  t_v(i) = fl(w_v * s_v(i)), one rounded multiply.  Over the SERVED vectors, v ascending:
+ * mode 0 (sum): F = t of the first served vector, then F = fl(F + t_v), every sum rounded once, no FMA; mode 1 (max): F = t of
+ * the first served vector, then F = t_v if (t_v > F or F is NaN), else F -- the first largest term wins, a NaN never displaces a
+ * number, F is NaN only if every term is.  A vector whose lambda_q is 0: skip_zero == 0: the whole call returns
+ * AS_EZEROLAMBDA and no answer is written; skip_zero != 0: that vector is left out, its weight is dropped and the others are not
+ * renormalised; if no vector is served the call returns AS_EZEROLAMBDA in either setting.  out_lambda_q / out_status ([j] each,
+ * may be NULL) are written whenever the lambda_q step ran.
+ * as_search_fused: the first min(topk', |sub|) items of the subset (sub == NULL: every item; topk' = min(topk, nitems)) by (F
+ * descending, index ascending; +0.0 and -0.0 tie) -> out_idx / out_score, *out_len.  as_score_fused: F of every listed id ->
+ * out_scores[m], the caller's order, duplicates kept.  With j == 1 and w = {1.0} the search form returns list 0 of
+ * as_search_subset_batch bit for bit in both modes.
+ * Checked before anything is launched: a null argument ("<name>: null argument", nothing written), j <= 0, a mode other than 0 / 1,
+ * a NaN or infinite weight, a subset of another space, wrong d, a non-finite tau, an id outside [0, nitems) -> AS_EINVAL; a shard
+ * of a row-sharded index -> AS_EUNSUPPORTED.  Cost: ONE as_search_batch over the j vectors (hits discarded), then per chunk of
+ * vectors under the "subset_batch_mib" budget the batched filtered forms' gather and fp64 matrix product, whose [chunk][m] scores
+ * stay on the device, and ONE accumulate kernel that reads them once and folds them into an accumulator of m doubles, which
+ * carries over the chunks; at the end the filtered forms' exact selection over the accumulator (the search form: topk' entries
+ * cross to the host) or one copy of its m doubles (the score form).  An empty subset or m == 0 still runs the lambda_q step and
+ * returns an empty answer.  The buffers live in the subset handle (sub == NULL: in the space's subset of all items, made on first
+ * use; the score form: in the space's as_score_items buffers) and grow on demand; calls are serialised with the other forms on
+ * that handle, as_search runs beside them. */
+as_status as_search_fused(const as_space* sp, const as_graph* gr, const double* queries, int64_t j, int64_t d, double tau,
+                          const double* weights, int32_t mode, int32_t skip_zero, const as_subset* sub, int64_t* out_idx,
+                          double* out_score, int64_t* out_len, double* out_lambda_q, int32_t* out_status);
+as_status as_score_fused(const as_space* sp, const as_graph* gr, const double* queries, int64_t j, int64_t d, double tau,
+                         const double* weights, int32_t mode, int32_t skip_zero, const int64_t* ids_host, int64_t m, double* out_scores,
+                         double* out_lambda_q, int32_t* out_status);
+/* out[0] calls of the two entries above that passed their checks, [1] accumulate launches, [2] scores folded (served rows x m),
+ * [3] lambda_q steps run */
+as_status as_fused_counters(const as_space* sp, int64_t* out, int32_t n);
+/* measurement: the device microseconds of the accumulate kernel, summed over the chunks of the last fused call on this space that
+ * ran under as_set_tuning("fused_timing", 1) (HIP events around the kernel; off by default) */
+double as_fused_kernel_us(const as_space* sp);
 
 /* ---- index persistence (extension; the reference exposes none): one flat file
  * holding the items, lambdas and graph arrays.  Loading re-ingests the items and uploads the

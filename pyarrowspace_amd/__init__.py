@@ -221,6 +221,39 @@ def _min_scores(min_score, b: int) -> np.ndarray:
     return np.ascontiguousarray(a)
 
 
+FUSED_MODES = {"sum": 0, "max": 1}
+
+
+def _fused_args(items, gl, weights, mode, on_zero_lambda):
+    """What the fused forms check before they touch a handle -> (Q float64 [J, D] contiguous, weights float64 [J] or None,
+    mode number, skip flag).  TypeError: a `gl` that is no GraphLaplacian, items that are not 2-D, weights that are not numbers;
+    ValueError: no vector at all, an unknown mode or on_zero_lambda, a weights length other than J (or a wrong rank), a NaN or
+    infinite weight."""
+    if not isinstance(gl, GraphLaplacian):
+        raise TypeError("argument 'gl': expected GraphLaplacian")
+    Q = np.ascontiguousarray(items, dtype=np.float64)
+    if Q.ndim != 2:
+        raise TypeError("items must be a 2-D float64 array")
+    if not isinstance(mode, str) or mode not in FUSED_MODES:
+        raise ValueError(f"argument 'mode': expected 'sum' or 'max', got {mode!r}")
+    if not isinstance(on_zero_lambda, str) or on_zero_lambda not in ("raise", "skip"):
+        raise ValueError(f"argument 'on_zero_lambda': expected 'raise' or 'skip', got {on_zero_lambda!r}")
+    j = Q.shape[0]
+    if j < 1:
+        raise ValueError("items must hold at least one query vector")
+    w = None
+    if weights is not None:
+        w = np.asarray(weights)
+        if w.dtype.kind not in "fiu":
+            raise TypeError(f"argument 'weights': expected a sequence of floats, got dtype {w.dtype}")
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        if w.ndim != 1 or w.shape[0] != j:
+            raise ValueError(f"argument 'weights': expected {j} weights, one per query vector, got shape {w.shape}")
+        if not np.isfinite(w).all():
+            raise ValueError("argument 'weights': a weight must be finite")
+    return Q, w, FUSED_MODES[mode], 1 if on_zero_lambda == "skip" else 0
+
+
 def _id_lists(lists, nitems: int) -> tuple[np.ndarray, np.ndarray]:
     """B id lists as (ids int64 flat, offsets int64 [B + 1]): a 2-D integer array (B, C) is B lists of C ids; any other
     sequence holds one entry per list, each whatever `_item_ids` accepts (integer ids in any order, duplicates kept, or a
@@ -622,6 +655,55 @@ class ArrowSpace:
         if st:
             _raise(st)
         return dict(zip(("calls", "compactions", "scores_examined", "survivors", "relaunches", "lambda_steps"), list(out)))
+
+    def search_fused(self, items, gl: GraphLaplacian, tau: float, weights=None, mode="sum", subset=None, on_zero_lambda="raise"):
+        """Extension: fused multi-query search, ONE answer to J query vectors [J, D] -> list[(index, score)]: the first
+        min(topk, |subset|) items of the subset (None: every item) by (F descending, index ascending).  With s_j(i) the score
+        `score_items_batch(items, gl, tau, ids)[j, i]` and t_j(i) = weights[j] * s_j(i) (weights default to 1/J each; negative
+        weights are legal), F is, j ascending, mode "sum": t_0, then F + t_j, every product and sum rounded once; mode "max":
+        t_0, then t_j where t_j > F or F is NaN -- the numpy loop over `score_items_batch` reproduces the bits.  A vector
+        whose lambda_q is 0: on_zero_lambda="raise" panics as `search` does, for the whole call; "skip" leaves that vector out
+        (its weight is dropped, the others are not renormalised); no vector left panics in either setting.  J = 1 with weights
+        [1.0] returns `search_batch_subset(items, gl, tau, subset)[0]` bit for bit.  Costs one `search_batch` over the J
+        vectors (lambda_q), the gather and fp64 matrix product of the batched filtered forms, one pass per chunk of vectors
+        that folds the scores into an accumulator on the device, and one exact selection there: topk entries cross to the
+        host, the J x M scores never do."""
+        Q, w, m, skip = _fused_args(items, gl, weights, mode, on_zero_lambda)
+        sub = subset if subset is None or isinstance(subset, ItemSubset) else self.subset(subset)
+        kk = max(min(int(gl.graph_params["topk"]), self.nitems, self.nitems if sub is None else sub.size), 1)
+        idx = np.empty(kk, dtype=np.int64)
+        sc = np.empty(kk, dtype=np.float64)
+        ln = C.c_int64(0)
+        st = _L.as_search_fused(self._h, gl._h, Q.ctypes.data_as(C.c_void_p), Q.shape[0], Q.shape[1], float(tau),
+                                None if w is None else w.ctypes.data_as(C.c_void_p), m, skip, None if sub is None else sub._h,
+                                idx.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p), C.byref(ln), None, None)
+        if st:
+            _raise(st)
+        return list(zip(idx[:ln.value].tolist(), sc[:ln.value].tolist()))
+
+    def score_fused(self, items, gl: GraphLaplacian, tau: float, ids, weights=None, mode="sum", on_zero_lambda="raise") -> np.ndarray:
+        """Extension: the fused score F of `search_fused` (same weights, modes and zero-lambda rule) for each listed id ->
+        ndarray[float64] of len(ids): the caller's order, duplicates kept; integer ids or a boolean mask as for `subset`.
+        Equals the numpy fold of `score_items_batch(items, gl, tau, ids)` bit for bit.  Costs what `search_fused` costs
+        without the selection: the accumulator's len(ids) doubles cross to the host."""
+        Q, w, m, skip = _fused_args(items, gl, weights, mode, on_zero_lambda)
+        ids = _item_ids(ids, self.nitems, "ids")
+        out = np.empty(ids.shape[0], dtype=np.float64)
+        st = _L.as_score_fused(self._h, gl._h, Q.ctypes.data_as(C.c_void_p), Q.shape[0], Q.shape[1], float(tau),
+                               None if w is None else w.ctypes.data_as(C.c_void_p), m, skip, ids.ctypes.data_as(C.c_void_p), ids.shape[0],
+                               out.ctypes.data_as(C.c_void_p), None, None)
+        if st:
+            _raise(st)
+        return out
+
+    def fused_counters(self) -> list:
+        """Extension: [0] fused calls on this space that passed their checks, [1] accumulate launches, [2] scores folded
+        (served vectors x items), [3] lambda_q steps run."""
+        out = (C.c_int64 * 4)()
+        st = _L.as_fused_counters(self._h, out, 4)
+        if st:
+            _raise(st)
+        return list(out)
 
     @staticmethod
     def _diverse_params(n, diversity) -> tuple[int, float]:

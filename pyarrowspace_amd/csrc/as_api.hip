@@ -1570,6 +1570,145 @@ as_status as_range_counters(const as_space* sp, int64_t* out, int32_t n) {
 }
 double as_range_kernel_us(const as_space* sp) { return sp ? sp->range_us.load(std::memory_order_relaxed) : 0.0; }
 
+// ---------------------------------------------------------------- fused multi-query search (extension; as_fused.hip)
+static as_status checked_ids(const char* who, const as_space* sp, const int64_t* ids_host, int64_t m, std::vector<int32_t>& ids);   // (below)
+namespace {
+// What both forms refuse before anything is launched, then lambda_q and the status of every vector from ONE as_search_batch call
+// over the j vectors, then S13's zero-lambda rule.  `wts`: the caller's weights, or 1/j each.
+as_status fused_prepare(const char* who, const as_space* sp, const as_graph* gr, const double* queries, int64_t j, int64_t d, double tau,
+                        const double* weights, int32_t mode, int32_t skip_zero, const as_subset* sub, double* out_lambda_q, int32_t* out_status,
+                        std::vector<double>& wts, std::vector<double>& lq, std::vector<int32_t>& st) {
+    if (j <= 0) {
+        set_err("%s: j must be >= 1, got %lld", who, (long long)j);
+        return AS_EINVAL;
+    }
+    if (mode != 0 && mode != 1) {
+        set_err("%s: mode must be 0 (sum) or 1 (max), got %d", who, (int)mode);
+        return AS_EINVAL;
+    }
+    for (int64_t t = 0; weights && t < j; ++t)
+        if (!std::isfinite(weights[t])) {
+            set_err("%s: weights[%lld] must be finite", who, (long long)t);
+            return AS_EINVAL;
+        }
+    if (sub && sub->sp != sp) {
+        set_err("%s: the subset was made for another space", who);
+        return AS_EINVAL;
+    }
+    AS_TRY(subset_checks(who, sp, gr, d, &tau, 1));
+    try {
+        if (weights) wts.assign(weights, weights + j);
+        else wts.assign((size_t)j, 1.0 / (double)j);
+    } catch (const std::bad_alloc&) {
+        set_err("%s: out of host memory for %lld weights", who, (long long)j);
+        return AS_ENOMEM;
+    }
+    sp->fused_count[0].fetch_add(1, std::memory_order_relaxed);
+    sp->fused_count[3].fetch_add(1, std::memory_order_relaxed);
+    AS_TRY(batch_lambda_step(who, sp, gr, queries, j, d, tau, lq, st));
+    int64_t served = 0;
+    for (int64_t t = 0; t < j; ++t) {
+        if (out_lambda_q) out_lambda_q[t] = lq[t];
+        if (out_status) out_status[t] = st[t];
+        served += st[t] == AS_EZEROLAMBDA ? 0 : 1;
+    }
+    if (served == 0 || (served < j && !skip_zero)) {
+        set_err("The lambdas are zero, check the magnitude of items and eps.");
+        return AS_EZEROLAMBDA;
+    }
+    return AS_OK;
+}
+as_status fused_sink_chunk(void* ctx, SubsetWork*, int64_t i0, int64_t nb, const double* scores, int64_t ld) {
+    return fused_chunk((FusedCall*)ctx, i0, nb, scores, ld);
+}
+// the j score rows of the work's m ids, chunk by chunk, folded into the work's accumulator; the stream is left busy at most with
+// what the caller queues behind (the selection, or the copy of the accumulator)
+as_status fused_fold(const as_space* sp, SubsetWork* w, int64_t m, const double* queries, int64_t j, double tau, const std::vector<double>& wts,
+                     const std::vector<double>& lq, const std::vector<int32_t>& st, int32_t mode, FusedCall* call) {
+    AS_TRY(fused_begin(w, m, j, wts.data(), st.data(), mode, call));
+    const SubsetChunkSink sink{fused_sink_chunk, call};
+    return subset_batch_run(sp, w, m, queries, j, lq.data(), st.data(), tau, 0, 0, nullptr, nullptr, nullptr, nullptr, &sink);
+}
+void fused_counts_add(const as_space* sp, const FusedCall& call) {
+    sp->fused_count[1].fetch_add(call.launches, std::memory_order_relaxed);
+    sp->fused_count[2].fetch_add(call.folded, std::memory_order_relaxed);
+    sp->fused_us.store(call.us, std::memory_order_relaxed);
+}
+}  // namespace
+
+as_status as_search_fused(const as_space* sp, const as_graph* gr, const double* queries, int64_t j, int64_t d, double tau, const double* weights,
+                          int32_t mode, int32_t skip_zero, const as_subset* sub, int64_t* out_idx, double* out_score, int64_t* out_len,
+                          double* out_lambda_q, int32_t* out_status) {
+    if (!sp || !gr || !queries || !out_len || ((!sub || sub->m > 0) && (!out_idx || !out_score))) {
+        set_err("as_search_fused: null argument");
+        return AS_EINVAL;
+    }
+    *out_len = 0;
+    std::vector<double> wts, lq;
+    std::vector<int32_t> st;
+    AS_TRY(fused_prepare("as_search_fused", sp, gr, queries, j, d, tau, weights, mode, skip_zero, sub, out_lambda_q, out_status, wts, lq, st));
+    if (sub && sub->m == 0) return AS_OK;
+    const as_subset* on = nullptr;
+    AS_TRY(range_subset(sp, sub, &on));
+    const int64_t kk = std::min<int64_t>(std::min<int64_t>(gr->gp.topk, sp->n), on->m);
+    FusedCall call;
+    std::lock_guard<std::mutex> lk(on->mu);
+    AS_HIP(hipSetDevice(sp->device));
+    as_status s = fused_fold(sp, on->w, on->m, queries, j, tau, wts, lq, st, mode, &call);
+    if (s == AS_OK) s = subset_select_from(on->w, fused_acc(on->w), on->m, kk, out_idx, out_score, out_len);
+    if (s == AS_OK) s = fused_end(&call);
+    else (void)hipStreamSynchronize(on->w->stream);
+    fused_counts_add(sp, call);
+    return s;
+}
+
+as_status as_score_fused(const as_space* sp, const as_graph* gr, const double* queries, int64_t j, int64_t d, double tau, const double* weights,
+                         int32_t mode, int32_t skip_zero, const int64_t* ids_host, int64_t m, double* out_scores, double* out_lambda_q,
+                         int32_t* out_status) {
+    if (!sp || !gr || !queries || m < 0 || (m > 0 && (!ids_host || !out_scores))) {
+        set_err("as_score_fused: null argument");
+        return AS_EINVAL;
+    }
+    for (int64_t i = 0; i < m; ++i)
+        if (ids_host[i] < 0 || ids_host[i] >= sp->n) {
+            set_err("as_score_fused: id %lld is outside [0, %lld)", (long long)ids_host[i], (long long)sp->n);
+            return AS_EINVAL;
+        }
+    std::vector<double> wts, lq;
+    std::vector<int32_t> st;
+    AS_TRY(fused_prepare("as_score_fused", sp, gr, queries, j, d, tau, weights, mode, skip_zero, nullptr, out_lambda_q, out_status, wts, lq, st));
+    if (m == 0) return AS_OK;
+    std::vector<int32_t> ids;
+    AS_TRY(checked_ids("as_score_fused", sp, ids_host, m, ids));
+    FusedCall call;
+    std::lock_guard<std::mutex> lk(sp->smu);
+    AS_HIP(hipSetDevice(sp->device));
+    AS_TRY(score_ws_ids(sp, ids.data(), m));
+    SubsetWork* w = sp->score_ws;
+    as_status s = fused_fold(sp, w, m, queries, j, tau, wts, lq, st, mode, &call);
+    if (s == AS_OK && hipMemcpyAsync(out_scores, fused_acc(w), sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, w->stream) != hipSuccess) {
+        set_err("as_score_fused: the copy of the scores failed");
+        s = AS_EHIP;
+    }
+    if (hipStreamSynchronize(w->stream) != hipSuccess && s == AS_OK) {
+        set_err("as_score_fused: the wait for the stream failed");
+        s = AS_EHIP;
+    }
+    if (s == AS_OK) s = fused_end(&call);
+    fused_counts_add(sp, call);
+    return s;
+}
+
+as_status as_fused_counters(const as_space* sp, int64_t* out, int32_t n) {
+    if (!sp || !out) {
+        set_err("as_fused_counters: null argument");
+        return AS_EINVAL;
+    }
+    for (int i = 0; i < n && i < 4; ++i) out[i] = sp->fused_count[i].load(std::memory_order_relaxed);
+    return AS_OK;
+}
+double as_fused_kernel_us(const as_space* sp) { return sp ? sp->fused_us.load(std::memory_order_relaxed) : 0.0; }
+
 // ---------------------------------------------------------------- diversified search (extension; as_diverse.hip)
 // what both forms refuse before anything is launched, the pool step included
 static as_status diverse_checks(const char* who, const as_space* sp, const as_graph* gr, int64_t d, double tau, int64_t n, double diversity,

@@ -47,7 +47,7 @@ void dbg(const char* fmt, ...);
 
 }  // namespace as
 
-namespace as { struct SubsetWork; struct ListsWork; struct RangeWork; struct DiverseWork; }
+namespace as { struct SubsetWork; struct ListsWork; struct RangeWork; struct DiverseWork; struct FusedWork; }
 struct as_subset;
 
 // ---------------------------------------------------------------- handles
@@ -174,6 +174,12 @@ struct as_space {
     mutable std::mutex rmu;
     mutable std::atomic<int64_t> range_count[6] = {};
     mutable std::atomic<double> range_us{0.0};
+    // as_search_fused / as_score_fused: the search form runs on the caller's subset or on range_all, the
+    // score form on score_ws (under smu).  as_fused_counters: [0] calls that passed their checks, [1] accumulate launches, [2]
+    // scores folded (served rows x m), [3] lambda_q steps run.  fused_us: the accumulate kernel of the last call under
+    // "fused_timing" (as_fused_kernel_us)
+    mutable std::atomic<int64_t> fused_count[4] = {};
+    mutable std::atomic<double> fused_us{0.0};
     // as_search_diverse / as_search_diverse_batch: their buffers (as_diverse.hip), made on first use and grown on demand; the
     // selection step of a call is serialised by dmu (the pool step before it is an ordinary search and takes no lock of these).
     // as_diverse_counters: [0] calls that passed their checks, [1] select launches, [2] picks made, [3] dots computed, [4] pool
@@ -726,6 +732,8 @@ struct SubsetWork {
     double kernel_us = 0.0;        // ... and its duration in the last timed call (the batched forms: summed over the chunks)
     // range search (as_range.hip): the append buffer, its counters and the thresholds, made on the first range call on this work
     RangeWork* range = nullptr;
+    // fused multi-query search (as_fused.hip): the accumulator, the weights and the flags, made on the first fused call on this work
+    FusedWork* fused = nullptr;
 };
 as_status subset_work_create(const as_space* sp, int64_t cap, SubsetWork** out);
 void subset_work_free(SubsetWork* w);
@@ -737,7 +745,8 @@ as_status subset_scores_out(SubsetWork* w, int64_t m, double* out);
 // query), in chunks of queries on the work's stream, one wait per chunk.  k > 0: the first k of every query's scores ->
 // out_idx / out_score at stride `stride`, out_len; k == 0: all scores -> out_scores [b][m], or, with a sink, to the sink: it is
 // called once per chunk behind the score kernel with the chunk's scores ([nb][ld], still on the device, queued on the work's
-// stream; a zero-lambda query's row holds no answer) and waits for the stream itself.
+// stream; a zero-lambda query's row holds no answer); range search's sink waits for the stream itself, the fused forms' sink only
+// queues its kernel: the run's one wait per chunk follows either way.
 struct SubsetChunkSink {
     as_status (*fn)(void* ctx, SubsetWork* w, int64_t i0, int64_t nb, const double* scores, int64_t ld);
     void* ctx;
@@ -746,6 +755,10 @@ as_status subset_batch_run(const as_space* sp, SubsetWork* w, int64_t m, const d
                            const int32_t* status, double tau, int64_t k, int64_t stride, int64_t* out_idx, double* out_score,
                            int64_t* out_len, double* out_scores, const SubsetChunkSink* sink = nullptr);
 void set_subset_batch_mib(int v);   // as_set_tuning("subset_batch_mib", v)
+// The selection over ONE row of m scores that lie anywhere on the device (the positions are those of the work's ids), queued on
+// the work's stream behind whatever wrote them: the first k by (score descending, position ascending) -> ids and scores; waits for
+// the stream.
+as_status subset_select_from(SubsetWork* w, const double* scores, int64_t m, int64_t k, int64_t* out_idx, double* out_score, int64_t* out_len);
 constexpr int QUERY_BATCH = 32;  // == GQ in as_search.hip: query slots of the batched workspace
 constexpr int TAU_GROUP = 8;     // taus one shared pass of a tau sweep serves (search_sweep, as_search_taus; one gather of a subset)
 // Tau sweeps over the m ids of `w`: nt distinct finite taus, up to TAU_GROUP per gather.  The list / the
@@ -788,6 +801,26 @@ as_status range_compact(SubsetWork* w, const double* scores, int64_t ld, int64_t
 void range_work_free(RangeWork* r);
 void set_range_cap(int v);      // as_set_tuning("range_cap", v)
 void set_range_timing(int v);   // as_set_tuning("range_timing", 0 | 1)
+// Fused multi-query search (as_fused.hip): the fold of j rows of scores over the work's m ids into one
+// accumulator [m] on the device.  fused_begin: room for the call, its weights and served flags (status AS_EZEROLAMBDA: not
+// served) uploaded once on the work's stream.  fused_chunk: rows i0 .. i0 + nb - 1 of the call, [nb][ld] on the device, folded
+// onto the accumulator behind the kernel that wrote them -- the sink of subset_batch_run; it does not wait.  A chunk without a
+// served row launches nothing.  fused_end: after the caller's last wait for the stream.  mode 0: sum, 1: max (S13).
+struct FusedCall {
+    SubsetWork* w = nullptr;
+    int64_t m = 0;
+    int mode = 0;
+    bool fresh = true;             // no served row folded yet: the next launch initialises the accumulator
+    bool timing = false, timed = false;
+    int64_t launches = 0, folded = 0;   // accumulate launches, scores folded (served rows x m)
+    double us = 0.0;               // the accumulate kernel's microseconds under "fused_timing"
+};
+as_status fused_begin(SubsetWork* w, int64_t m, int64_t j, const double* weights, const int32_t* status, int mode, FusedCall* c);
+as_status fused_chunk(FusedCall* c, int64_t i0, int64_t nb, const double* scores, int64_t ld);
+as_status fused_end(FusedCall* c);
+const double* fused_acc(const SubsetWork* w);   // [m], valid after a call with a served row
+void fused_work_free(FusedWork* f);
+void set_fused_timing(int v);   // as_set_tuning("fused_timing", 0 | 1)
 // Diversified search (as_diverse.hip): the greedy of S12 over b pools -- pool i = pool_idx / pool_score + i * kk,
 // pool_len[i] <= kk entries in the order the route returned them (0: a query that is not served) -- n picks wanted, diversity delta.
 // Pick t of query i -> out_idx / out_score / out_margin (may be null) + i * nn + t, nn = min(n, kk); out_len[i] = min(n, pool_len[i]).

@@ -1,0 +1,187 @@
+// Fused multi-query search: ONE answer to J query vectors -- F(i) = the weighted sum, or the largest
+// weighted term, of the J S11 scores of item i.  The scores come from the batched filtered forms' score kernel (as_subset.hip),
+// unchanged, a chunk of queries at a time; this file folds each chunk's [nb][ld] block into one accumulator [m] that stays on the
+// device (fused_accumulate_kernel) and carries over the chunks, so J is not bound by the chunk size.  The order over j inside a
+// position is sequential and ascending: that order is the specification (S13), the numpy loop reproduces the bits.
+// Entry points: as_api.hip (as_search_fused, as_score_fused, as_fused_counters, as_fused_kernel_us).
+#include <algorithm>
+#include <atomic>
+#include <new>
+
+#include "as_common.hpp"
+
+namespace as {
+
+// a pair of scores of one row: rows start on an 8-byte boundary only (ld may be odd), so the type promises no more than that;
+// the load is still one 16-byte instruction
+typedef double f64x2_a8 __attribute__((ext_vector_type(2), aligned(8)));
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+
+constexpr int FA_THREADS = 256;
+constexpr int FA_ROWS = 8;             // rows whose loads are in flight together
+constexpr int FA_BLOCKS_PER_CU = 8;    // the grid: that many blocks per CU at most, the rest is the grid-stride loop
+
+// One step of S13 for one position: every product and every sum rounded once, never contracted into an FMA.
+#pragma clang fp contract(off)
+template <int MODE>
+__device__ __forceinline__ double fused_step(double f, double wj, double s, bool have) {
+    const double t = wj * s;
+    if (!have) return t;
+    if (MODE == 0) return f + t;
+    return (t > f || f != f) ? t : f;   // the first largest term wins; a NaN never displaces a number
+}
+
+// acc[i] <- the fold of rows 0 .. nb - 1 of scores ([nb][ld]) at position i < m onto acc[i], rows ascending; a row whose flag is 0
+// is skipped.  fresh: the accumulator holds nothing yet -- the first served row of the chunk initialises it (no memset, no 0 + t).
+// A thread owns a pair of neighbouring positions (16-byte loads and stores; the accumulator is 16-byte aligned) for all rows, so no
+// two threads meet in a position and the stores are plain; an odd m leaves one single position to the thread behind the last pair.
+template <int MODE>
+__global__ __launch_bounds__(FA_THREADS) void fused_accumulate_kernel(const double* __restrict__ scores, int64_t ld, int64_t m, int nb,
+                                                                      const double* __restrict__ wts, const int32_t* __restrict__ flags,
+                                                                      double* __restrict__ acc, int fresh) {
+    const int64_t pairs = m >> 1, units = pairs + (m & 1);
+    for (int64_t u = (int64_t)blockIdx.x * FA_THREADS + threadIdx.x; u < units; u += (int64_t)gridDim.x * FA_THREADS) {
+        const bool pair = u < pairs;
+        const int64_t i = 2 * u;   // (the single position of an odd m: i == m - 1)
+        bool have = fresh == 0;
+        double f0 = 0.0, f1 = 0.0;
+        if (have) {
+            if (pair) {
+                const f64x2 a = *(const f64x2*)(acc + i);
+                f0 = a[0];
+                f1 = a[1];
+            } else {
+                f0 = acc[i];
+            }
+        }
+        for (int j0 = 0; j0 < nb; j0 += FA_ROWS) {
+            double s0[FA_ROWS], s1[FA_ROWS];
+#pragma unroll
+            for (int r = 0; r < FA_ROWS; ++r) {
+                s0[r] = 0.0;
+                s1[r] = 0.0;
+                if (j0 + r < nb) {
+                    const double* p = scores + (int64_t)(j0 + r) * ld + i;
+                    if (pair) {
+                        const f64x2_a8 x = *(const f64x2_a8*)p;
+                        s0[r] = x[0];
+                        s1[r] = x[1];
+                    } else {
+                        s0[r] = *p;
+                    }
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < FA_ROWS; ++r) {
+                if (j0 + r < nb && flags[j0 + r]) {
+                    const double wj = wts[j0 + r];
+                    f0 = fused_step<MODE>(f0, wj, s0[r], have);
+                    f1 = fused_step<MODE>(f1, wj, s1[r], have);
+                    have = true;
+                }
+            }
+        }
+        if (!have) continue;   // (no served row so far: the host does not launch such a chunk)
+        if (pair) {
+            f64x2 o;
+            o[0] = f0;
+            o[1] = f1;
+            *(f64x2*)(acc + i) = o;
+        } else {
+            acc[i] = f0;
+        }
+    }
+}
+
+// ------------------------------------------------------------------ host side
+static std::atomic<int> g_fused_timing{0};
+void set_fused_timing(int v) { g_fused_timing.store(v ? 1 : 0, std::memory_order_relaxed); }
+
+struct FusedWork {
+    dev_buf<double> acc;       // [m]: F so far
+    dev_buf<double> par;       // the call's parameters, one upload: [j] weights, then [j] int32 flags (1 for a served vector)
+    pin_buf<double> hpar;      // pinned staging of the same
+    dev_events<2> ev;          // made by the first call under "fused_timing"
+    int64_t j = 0;             // vectors of the call in flight
+    const int32_t* hflags() const { return (const int32_t*)((const double*)hpar + j); }
+};
+
+void fused_work_free(FusedWork* f) { delete f; }
+
+as_status fused_begin(SubsetWork* w, int64_t m, int64_t j, const double* weights, const int32_t* status, int mode, FusedCall* c) {
+    if (!w->fused) {
+        w->fused = new (std::nothrow) FusedWork();
+        if (!w->fused) {
+            set_err("fused: out of host memory");
+            return AS_ENOMEM;
+        }
+    }
+    FusedWork* f = w->fused;
+    c->w = w;
+    c->m = m;
+    c->mode = mode;
+    c->fresh = true;
+    c->timing = g_fused_timing.load(std::memory_order_relaxed) != 0;
+    c->timed = false;
+    c->launches = c->folded = 0;
+    c->us = 0.0;
+    if (c->timing && !f->ev.e[1]) AS_HIP(f->ev.create());
+    AS_TRY(reserve_or_err(f->acc, std::max<int64_t>(m, 1), "fused accumulator"));
+    const int64_t words = j + (j + 1) / 2;   // doubles: the weights, then the flags two to a double
+    AS_TRY(reserve_or_err(f->par, words, "fused weights and flags"));
+    AS_TRY(reserve_or_err(f->hpar, words, "fused pinned weights and flags"));
+    f->j = j;
+    int32_t* hflags = (int32_t*)((double*)f->hpar + j);
+    for (int64_t t = 0; t < j; ++t) {
+        f->hpar[t] = weights[t];
+        hflags[t] = status[t] == AS_EZEROLAMBDA ? 0 : 1;
+    }
+    AS_HIP(hipMemcpyAsync(f->par, f->hpar, sizeof(double) * (size_t)j + sizeof(int32_t) * (size_t)j, hipMemcpyHostToDevice, w->stream));
+    return AS_OK;
+}
+
+// the time of the launch before this one: the stream has been waited for since (one pair of events serves every chunk)
+static as_status fused_collect_time(FusedCall* c) {
+    if (!c->timed) return AS_OK;
+    float ms = 0.0f;
+    AS_HIP(hipEventElapsedTime(&ms, c->w->fused->ev.e[0], c->w->fused->ev.e[1]));
+    c->us += (double)ms * 1e3;
+    c->timed = false;
+    return AS_OK;
+}
+
+as_status fused_chunk(FusedCall* c, int64_t i0, int64_t nb, const double* scores, int64_t ld) {
+    SubsetWork* w = c->w;
+    FusedWork* f = w->fused;
+    int64_t served = 0;
+    for (int64_t t = 0; t < nb; ++t) served += f->hflags()[i0 + t];
+    if (served == 0 || c->m <= 0) return AS_OK;
+    AS_TRY(fused_collect_time(c));
+    const int64_t units = (c->m + 1) / 2;
+    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((units + FA_THREADS - 1) / FA_THREADS, (int64_t)w->cus * FA_BLOCKS_PER_CU));
+    const double* wts = f->par + i0;
+    const int32_t* flags = (const int32_t*)((const double*)f->par + f->j) + i0;
+    double* acc = f->acc;
+    if (c->timing) AS_HIP(hipEventRecord(f->ev.e[0], w->stream));
+    if (c->mode == 0)
+        hipLaunchKernelGGL(fused_accumulate_kernel<0>, dim3(grid), dim3(FA_THREADS), 0, w->stream, scores, ld, c->m, (int)nb, wts, flags, acc,
+                           c->fresh ? 1 : 0);
+    else
+        hipLaunchKernelGGL(fused_accumulate_kernel<1>, dim3(grid), dim3(FA_THREADS), 0, w->stream, scores, ld, c->m, (int)nb, wts, flags, acc,
+                           c->fresh ? 1 : 0);
+    AS_HIP(hipGetLastError());
+    if (c->timing) {
+        AS_HIP(hipEventRecord(f->ev.e[1], w->stream));
+        c->timed = true;
+    }
+    c->fresh = false;
+    c->launches += 1;
+    c->folded += served * c->m;
+    return AS_OK;
+}
+
+as_status fused_end(FusedCall* c) { return fused_collect_time(c); }
+
+const double* fused_acc(const SubsetWork* w) { return w->fused ? (const double*)w->fused->acc : nullptr; }
+
+}  // namespace as

@@ -3651,6 +3651,10 @@ int32_t as_set_tuning(const char* key, int32_t value) {
         set_diverse_timing(value);
         return 0;
     }
+    if (key && !strcmp(key, "fused_timing")) {
+        set_fused_timing(value);
+        return 0;
+    }
     return 1;
 }
 

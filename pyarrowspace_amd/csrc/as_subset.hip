@@ -646,6 +646,7 @@ void subset_work_free(SubsetWork* w) {
     (void)hipSetDevice(w->device);
     if (w->stream) (void)hipStreamSynchronize(w->stream);
     range_work_free(w->range);
+    fused_work_free(w->fused);
     for (int i = 0; i < 2; ++i)
         if (w->ev[i]) (void)hipEventDestroy(w->ev[i]);
     if (w->stream) (void)hipStreamDestroy(w->stream);
@@ -780,6 +781,16 @@ as_status subset_select(SubsetWork* w, int64_t m, int64_t k, int64_t* out_idx, d
     return subset_list_out(w->out, k, out_idx, out_score, out_len);
 }
 
+as_status subset_select_from(SubsetWork* w, const double* scores, int64_t m, int64_t k, int64_t* out_idx, double* out_score, int64_t* out_len) {
+    *out_len = 0;
+    if (m <= 0 || k <= 0) return AS_OK;
+    k = std::min<int64_t>(std::min<int64_t>(k, m), SUBSET_TOPK);
+    AS_TRY(subset_reserve(w, 1, w->cap, 1, true, true));   // (nothing to do unless a larger call's allocation failed)
+    AS_TRY(subset_select_rows(w, scores, m, m, k, 1));
+    AS_HIP(hipStreamSynchronize(w->stream));
+    return subset_list_out(w->out, k, out_idx, out_score, out_len);
+}
+
 // the m scores themselves, in the order of the ids; waits for the stream
 as_status subset_scores_out(SubsetWork* w, int64_t m, double* out) {
     if (m <= 0) {
@@ -827,7 +838,7 @@ as_status subset_batch_run(const as_space* sp, SubsetWork* w, int64_t m, const d
         if (sel) {
             AS_TRY(subset_select_rows(w, w->scores, m, m, k, nb));
         } else if (sink) {
-            AS_TRY(sink->fn(sink->ctx, w, i0, nb, w->scores, m));   // (it waits for the stream: the wait below finds it idle)
+            AS_TRY(sink->fn(sink->ctx, w, i0, nb, w->scores, m));   // (range search's waits for the stream: the wait below finds it idle)
         } else {
             // one copy per run of served queries: a zero-lambda query's row stays unwritten
             AS_TRY(for_served_runs(status, i0, nb, [&](int64_t t, int64_t u) -> as_status {
