@@ -9,7 +9,7 @@ distance `d = 1 - max(0, cos)`, weights `1 / (1 + (d / sigma)^p)` (`GRAPH_VARIAB
 and `bench.py` keep BASELINE.json's north_star default (L2 distance, Gaussian weights).  Either way a `metric` /
 `kernel` / `lambda_mode` key in the dict, or ARROWSPACE_METRIC / _KERNEL / _LAMBDA_MODE, overrides."""
 import pyarrowspace_amd as _amd
-from pyarrowspace_amd import ArrowSpace, GraphLaplacian, ItemSubset, PanicException, set_debug  # noqa: F401
+from pyarrowspace_amd import ArrowSpace, GraphLaplacian, ItemGroups, ItemSubset, PanicException, set_debug  # noqa: F401
 
 
 class ArrowSpaceBuilder(_amd.ArrowSpaceBuilder):
@@ -18,4 +18,4 @@ class ArrowSpaceBuilder(_amd.ArrowSpaceBuilder):
     _mode = _amd.REFERENCE_MODE
 
 
-__all__ = ["ArrowSpaceBuilder", "ArrowSpace", "GraphLaplacian", "ItemSubset", "set_debug", "PanicException"]
+__all__ = ["ArrowSpaceBuilder", "ArrowSpace", "GraphLaplacian", "ItemSubset", "ItemGroups", "set_debug", "PanicException"]

@@ -478,7 +478,8 @@ void as_enable_search_stats(int32_t enabled);
  * to; <= 0: the default); "range_timing" = 1 / 0: HIP events around the range forms' compaction kernel (as_range_kernel_us).
  * "diverse_chunk" = queries per launch of the diversified forms (default 4096; <= 0: the default); "diverse_timing" = 1 / 0: HIP
  * events around their select kernel (as_diverse_kernel_us).  "fused_timing" = 1 / 0: HIP events around the fused forms'
- * accumulate kernel (as_fused_kernel_us).
+ * accumulate kernel (as_fused_kernel_us).  "grouped_timing" = 1 / 0: HIP events around the grouped forms' pick kernels
+ * (as_grouped_kernel_us).
  * Returns 0, or 1 for an unknown key.  Results never depend on it. */
 int32_t as_set_tuning(const char* key, int32_t value);
 /* same, for the workspace as_search keeps inside the space (last as_search call) */
@@ -753,6 +754,49 @@ as_status as_fused_counters(const as_space* sp, int64_t* out, int32_t n);
 /* measurement: the device microseconds of the accumulate kernel, summed over the chunks of the last fused call on this space that
  * ran under as_set_tuning("fused_timing", 1) (HIP events around the kernel; off by default) */
 double as_fused_kernel_us(const as_space* sp);
+/* ---- Extension: grouped search.  The best items of the best groups.  as_groups_create: one int64 label per item
+ * of the space (labels[n], n == nitems, HOST memory, any values; equal labels = one group) -> a handle; the labels are turned into
+ * dense group numbers (ascending label) on the host and uploaded once.  as_groups_count: distinct labels.
+ * s(i): the S11 score of item i with the bits as_score_items (single form) / as_score_items_batch (batched form) writes.  Items
+ * are ordered by (score descending, index ascending; +0.0 and -0.0 tie); an item whose score is NaN belongs to no answer.  A
+ * group's MEMBERS are its items inside the subset (sub == NULL: every item) with a non-NaN score, in that order; its HEAD is the
+ * first; a group without a member does not exist for the call.  Groups are ordered by their heads in the item order (two groups
+ * never tie).  The answer: the first min(n_groups, groups with a member) groups -> *out_ngroups; for group s its label ->
+ * out_label[s], its first min(per_group, members) members -> out_count[s] and out_idx / out_score[s * per_group + t].  The
+ * subset restricts the answer, not the index: lambda_q and the items' lambdas are the ones as_search uses.
+ * as_search_grouped: lambda_q == 0 -> AS_EZEROLAMBDA, whatever the labels and the subset.  as_search_grouped_batch: b queries
+ * [b][d]; query i's outputs at out_label / out_count + i * n_groups, out_idx / out_score + i * n_groups * per_group,
+ * out_ngroups[i]; a query whose lambda_q is 0 gets out_status[i] == AS_EZEROLAMBDA and 0 groups, the others are served.
+ * out_lambda_q / out_status (may be NULL) are written whenever the lambda_q step ran.
+ * Checked before anything is launched: a null argument ("<name>: null argument", nothing written), n_groups outside [1, 1024],
+ * per_group outside [1, 16], a groups handle or a subset of another space, wrong d, a non-finite tau -> AS_EINVAL; a shard of a
+ * row-sharded index -> AS_EUNSUPPORTED.
+ * Cost: one as_search (batched: ONE as_search_batch over the b queries), hits discarded; the filtered forms' gather and score
+ * kernel, whose scores stay on the device; per round two pick launches that each read the scores (8 bytes) and the subset's
+ * ids and group numbers (4 to 8 bytes) of every position and issue one vector atomic per run of neighbouring positions of one
+ * group inside a wave; one collapse launch and the filtered forms' exact selection over the heads; per_group - 1 further rounds
+ * over the selected groups (fewer when no selected group is that large); one gather launch, one copy.  Two waits (one when
+ * per_group == 1).  The batched form works in chunks of queries under the "subset_batch_mib" budget, which counts the scores, the
+ * collapsed scores and the per-group cells of a query.  The buffers live in the subset handle (sub == NULL: in the space's
+ * subset of all items, made on first use) and grow on demand; calls are serialised with the other forms on that handle,
+ * as_search runs beside them. */
+typedef struct as_groups as_groups;
+as_status as_groups_create(const as_space* sp, const int64_t* labels, int64_t n, as_groups** out);
+int64_t as_groups_count(const as_groups* g);                  /* NULL: 0 */
+void as_groups_free(as_groups* g);                            /* NULL: no-op */
+as_status as_search_grouped(const as_space* sp, const as_graph* gr, const double* query, int64_t d, double tau, const as_groups* groups,
+                            int64_t n_groups, int64_t per_group, const as_subset* sub, int64_t* out_label, int64_t* out_count,
+                            int64_t* out_idx, double* out_score, int64_t* out_ngroups, double* out_lambda_q);
+as_status as_search_grouped_batch(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau,
+                                  const as_groups* groups, int64_t n_groups, int64_t per_group, const as_subset* sub,
+                                  int64_t* out_label, int64_t* out_count, int64_t* out_idx, double* out_score, int64_t* out_ngroups,
+                                  double* out_lambda_q, int32_t* out_status);
+/* out[0] calls of the two entries above that passed their checks, [1] pick-kernel launches, [2] scores examined (queries x m per
+ * pick launch), [3] 64-bit max-atomics the pick kernels issued, [4] groups returned, [5] members returned, [6] lambda_q steps run */
+as_status as_grouped_counters(const as_space* sp, int64_t* out, int32_t n);
+/* measurement: the device microseconds of the pick kernels, summed over the rounds and chunks of the last grouped call on this
+ * space that ran under as_set_tuning("grouped_timing", 1) (HIP events around the kernels; off by default) */
+double as_grouped_kernel_us(const as_space* sp);
 
 /* ---- index persistence (extension; the reference exposes none): one flat file
  * holding the items, lambdas and graph arrays.  Loading re-ingests the items and uploads the

@@ -17,7 +17,7 @@ import numpy as np
 from . import _lib
 from ._lib import GraphParams, Opts
 
-__all__ = ["ArrowSpaceBuilder", "ArrowSpace", "GraphLaplacian", "ItemSubset", "set_debug", "PanicException"]
+__all__ = ["ArrowSpaceBuilder", "ArrowSpace", "GraphLaplacian", "ItemSubset", "ItemGroups", "set_debug", "PanicException"]
 __version__ = "0.1.0"
 
 _L = _lib.load()
@@ -318,6 +318,75 @@ class ItemSubset:
     def kernel_us(self) -> float:
         """Measurement only: device microseconds of the score kernel in the last timed `search_subset` call on this subset (`search_batch_subset`: summed over the call's chunks; the sweeps: over the call's launches)."""
         return float(_L.as_subset_kernel_us(self._h))
+
+
+GROUPED_MAX_GROUPS = 1024      # == SUBSET_TOPK of the library
+GROUPED_MAX_PER_GROUP = 16     # == GROUPED_MAX_PER_GROUP of the library
+
+
+def _group_labels(labels, nitems: int) -> np.ndarray:
+    """One integer label per item as a contiguous int64 array of nitems entries.  A bool or float dtype (or anything that is
+    not an integer) raises TypeError, a wrong rank or length, or a uint64 label past the int64 range, ValueError."""
+    a = np.asarray(labels)
+    if a.dtype.kind not in "iu":
+        raise TypeError(f"argument 'labels': expected one integer label per item, got dtype {a.dtype}")
+    if a.ndim != 1:
+        raise ValueError(f"argument 'labels': expected a 1-D sequence of {nitems} labels, got shape {a.shape}")
+    if a.shape[0] != nitems:
+        raise ValueError(f"argument 'labels': {a.shape[0]} labels for {nitems} items")
+    if a.dtype == np.uint64 and a.size and int(a.max()) > np.iinfo(np.int64).max:
+        raise ValueError(f"argument 'labels': label {int(a.max())} does not fit int64")
+    return np.ascontiguousarray(a, dtype=np.int64)
+
+
+def _grouped_args(gl, tau, n_groups, per_group):
+    """What the grouped forms check before they touch a handle."""
+    if not isinstance(gl, GraphLaplacian):
+        raise TypeError("argument 'gl': expected GraphLaplacian")
+    for name, v, hi in (("n_groups", n_groups, GROUPED_MAX_GROUPS), ("per_group", per_group, GROUPED_MAX_PER_GROUP)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"argument '{name}': expected an integer")
+        if v < 1 or v > hi:
+            raise ValueError(f"argument '{name}': must be in [1, {hi}], got {v}")
+    tau = float(tau)
+    if not np.isfinite(tau):
+        raise ValueError("argument 'tau': must be finite")
+    return tau, int(n_groups), int(per_group)
+
+
+class ItemGroups:
+    """Extension: one group per item of one ArrowSpace (`ArrowSpace.groups`): the items' integer labels, turned into dense group
+    numbers once and resident on the device for `search_grouped`.  Holds a reference to its ArrowSpace."""
+
+    def __new__(cls, *a, **k):
+        raise ValueError("ItemGroups cannot be constructed directly; use ArrowSpace.groups")
+
+    @classmethod
+    def _wrap(cls, handle, space, labels):
+        self = object.__new__(cls)
+        self._h = handle
+        self._space = space
+        self._labels = labels
+        return self
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and _L is not None:
+            _L.as_groups_free(h)
+            self._h = None
+        self._space = None
+
+    @property
+    def ngroups(self) -> int:
+        """Extension: the number of distinct labels."""
+        return int(_L.as_groups_count(self._h))
+
+    def __len__(self) -> int:
+        return self.ngroups
+
+    def labels(self) -> np.ndarray:
+        """Extension: the per-item labels (int64, a copy)."""
+        return self._labels.copy()
 
 
 class ArrowSpace:
@@ -704,6 +773,91 @@ class ArrowSpace:
         if st:
             _raise(st)
         return list(out)
+
+    def groups(self, labels) -> ItemGroups:
+        """Extension: an `ItemGroups` of this space from one integer label per item (a 1-D sequence or array of length nitems,
+        any int64 values; equal labels mean the same group).  The labels are grouped on the host and uploaded once.  A bool or
+        float dtype raises TypeError, a wrong length or rank ValueError."""
+        lab = _group_labels(labels, self.nitems)
+        h = C.c_void_p()
+        st = _L.as_groups_create(self._h, lab.ctypes.data_as(C.c_void_p), lab.shape[0], C.byref(h))
+        if st:
+            _raise(st)
+        return ItemGroups._wrap(h, self, lab.copy())
+
+    def _grouped_handles(self, groups, subset):
+        """The groups and the subset of a grouped call as handles of THIS space (ValueError for another space's)."""
+        grp = groups if isinstance(groups, ItemGroups) else self.groups(groups)
+        if grp._space is not self:
+            raise ValueError("argument 'groups': the groups were made for another space")
+        sub = subset if subset is None or isinstance(subset, ItemSubset) else self.subset(subset)
+        if sub is not None and sub._space is not self:
+            raise ValueError("argument 'subset': the subset was made for another space")
+        return grp, sub
+
+    @staticmethod
+    def _grouped_lists(ng, pg, ngroups, label, count, idx, sc):
+        label, count, idx, sc = label.tolist(), count.tolist(), idx.reshape(-1, pg).tolist(), sc.reshape(-1, pg).tolist()
+        return [(label[s], list(zip(idx[s][:count[s]], sc[s][:count[s]]))) for s in range(ngroups)]
+
+    def search_grouped(self, item, gl: GraphLaplacian, tau: float, groups, n_groups: int, per_group: int = 1, subset=None):
+        """Extension: grouped search -> list[(label, list[(index, score)])]: the best items of the best groups.  Items are
+        ordered by (score descending, index ascending), an item whose score is NaN belongs to no answer; a group's members
+        are its items inside the subset in that order, groups are ordered by their first member.  Returned: the first
+        min(n_groups, groups with a member) groups, each with its label and its first min(per_group, members) members;
+        1 <= n_groups <= 1024, 1 <= per_group <= 16.  `groups`: an `ItemGroups` of this space or anything `groups()` accepts;
+        `subset`: None (every item), an `ItemSubset` of this space or anything `subset()` accepts -- it restricts the answer,
+        not the index, as in `search_subset`.  The score of item i has the bits `score_items(item, gl, tau, [i])` returns.
+        Costs one ordinary `search` (lambda_q comes from it; a query whose lambda_q is 0 panics as there, whatever the labels
+        and the subset) plus a gather of the subset's rows, two passes over the scores per member rank that pick every
+        group's next member with atomics on the device, and one exact selection of the groups there: n_groups x per_group
+        entries cross to the host, the scores never do."""
+        tau, ng, pg = _grouped_args(gl, tau, n_groups, per_group)
+        q = self._query(item)
+        grp, sub = self._grouped_handles(groups, subset)
+        label, count = np.zeros(ng, dtype=np.int64), np.zeros(ng, dtype=np.int64)
+        idx, sc = np.zeros(ng * pg, dtype=np.int64), np.zeros(ng * pg, dtype=np.float64)
+        n, lq = C.c_int64(0), C.c_double(0.0)
+        st = _L.as_search_grouped(self._h, gl._h, q.ctypes.data, q.shape[0], tau, grp._h, ng, pg, None if sub is None else sub._h,
+                                  label.ctypes.data, count.ctypes.data, idx.ctypes.data, sc.ctypes.data, C.byref(n), C.byref(lq))
+        if st:
+            _raise(st)
+        return self._grouped_lists(ng, pg, n.value, label, count, idx, sc)
+
+    def search_batch_grouped(self, items, gl: GraphLaplacian, tau: float, groups, n_groups: int, per_group: int = 1, subset=None):
+        """Extension: batched grouped search, B queries [B, D] -> list of B answers; answer i is what
+        `search_grouped(items[i], gl, tau, groups, n_groups, per_group, subset)` returns with the score bits of
+        `score_items_batch` (within 1e-12 relative of the single form's: the batched kernel sums in another order).  B = 0
+        returns [] and launches nothing.  Costs one `search_batch` over the B queries (lambda_q comes from it; any query whose
+        lambda_q is 0 panics as there), then per chunk of queries the batched filtered forms' gather and fp64 matrix product
+        and the pick passes, the selection and the gather of `search_grouped` with one row per query."""
+        tau, ng, pg = _grouped_args(gl, tau, n_groups, per_group)
+        Q = np.ascontiguousarray(items, dtype=np.float64)
+        if Q.ndim != 2:
+            raise TypeError("items must be a 2-D float64 array")
+        b = Q.shape[0]
+        if b == 0:
+            return []
+        grp, sub = self._grouped_handles(groups, subset)
+        label, count = np.zeros((b, ng), dtype=np.int64), np.zeros((b, ng), dtype=np.int64)
+        idx, sc = np.zeros((b, ng * pg), dtype=np.int64), np.zeros((b, ng * pg), dtype=np.float64)
+        n, stt = np.zeros(b, dtype=np.int64), np.zeros(b, dtype=np.int32)
+        st = _L.as_search_grouped_batch(self._h, gl._h, Q.ctypes.data, b, Q.shape[1], tau, grp._h, ng, pg, None if sub is None else sub._h,
+                                        label.ctypes.data, count.ctypes.data, idx.ctypes.data, sc.ctypes.data, n.ctypes.data, None,
+                                        stt.ctypes.data)
+        if st:
+            _raise(st)
+        if (stt == _lib.AS_EZEROLAMBDA).any():
+            raise PanicException("The lambdas are zero, check the magnitude of items and eps.")
+        return [self._grouped_lists(ng, pg, int(n[i]), label[i], count[i], idx[i], sc[i]) for i in range(b)]
+
+    def grouped_counters(self) -> dict:
+        """Extension: grouped calls on this space since it was made, the work they launched and what they returned."""
+        out = (C.c_int64 * 7)()
+        st = _L.as_grouped_counters(self._h, out, 7)
+        if st:
+            _raise(st)
+        return dict(zip(("calls", "pick_launches", "scores_examined", "max_atomics", "groups", "members", "lambda_steps"), list(out)))
 
     @staticmethod
     def _diverse_params(n, diversity) -> tuple[int, float]:

@@ -1709,6 +1709,177 @@ as_status as_fused_counters(const as_space* sp, int64_t* out, int32_t n) {
 }
 double as_fused_kernel_us(const as_space* sp) { return sp ? sp->fused_us.load(std::memory_order_relaxed) : 0.0; }
 
+// ---------------------------------------------------------------- grouped search (extension; as_grouped.hip)
+as_status as_groups_create(const as_space* sp, const int64_t* labels, int64_t n, as_groups** out) {
+    if (!sp || !labels || !out) {
+        set_err("as_groups_create: null argument");
+        return AS_EINVAL;
+    }
+    *out = nullptr;
+    if (n != sp->n) {
+        set_err("as_groups_create: %lld labels for %lld items", (long long)n, (long long)sp->n);
+        return AS_EINVAL;
+    }
+    as_groups* g = nullptr;
+    try {
+        g = new as_groups();
+        g->labels.assign(labels, labels + n);
+        std::sort(g->labels.begin(), g->labels.end());
+        g->labels.erase(std::unique(g->labels.begin(), g->labels.end()), g->labels.end());
+        g->dense.resize((size_t)n);
+        g->size.assign(g->labels.size(), 0);
+    } catch (const std::bad_alloc&) {
+        delete g;
+        set_err("as_groups_create: out of host memory for %lld labels", (long long)n);
+        return AS_ENOMEM;
+    }
+    g->sp = sp;
+    g->device = sp->device;
+    g->n = n;
+    g->count = (int64_t)g->labels.size();
+    for (int64_t i = 0; i < n; ++i) {   // (group numbers fit 32 bits: space_new refuses n >= 2^31)
+        const int32_t d = (int32_t)(std::lower_bound(g->labels.begin(), g->labels.end(), labels[i]) - g->labels.begin());
+        g->dense[(size_t)i] = d;
+        g->size[(size_t)d] += 1;
+    }
+    hipError_t e = hipSetDevice(sp->device);
+    if (e == hipSuccess) e = hipMalloc((void**)&g->dense_dev, sizeof(int32_t) * (size_t)std::max<int64_t>(n, 1));
+    if (e == hipSuccess) e = hipMemcpy(g->dense_dev, g->dense.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        set_err("as_groups_create: the upload of %lld group numbers failed: %s", (long long)n, hipGetErrorString(e));
+        as_groups_free(g);
+        return e == hipErrorOutOfMemory ? AS_ENOMEM : AS_EHIP;
+    }
+    *out = g;
+    return AS_OK;
+}
+int64_t as_groups_count(const as_groups* g) { return g ? g->count : 0; }
+void as_groups_free(as_groups* g) {
+    if (!g) return;
+    if (g->dense_dev) {
+        (void)hipSetDevice(g->device);
+        (void)hipFree(g->dense_dev);
+    }
+    delete g;
+}
+
+namespace {
+// what both forms refuse before anything is launched, the lambda_q step included
+as_status grouped_checks(const char* who, const as_space* sp, const as_graph* gr, int64_t d, double tau, const as_groups* groups,
+                         int64_t n_groups, int64_t per_group, const as_subset* sub) {
+    if (n_groups < 1 || n_groups > SUBSET_TOPK) {
+        set_err("%s: n_groups must be in [1, %d], got %lld", who, SUBSET_TOPK, (long long)n_groups);
+        return AS_EINVAL;
+    }
+    if (per_group < 1 || per_group > GROUPED_MAX_PER_GROUP) {
+        set_err("%s: per_group must be in [1, %d], got %lld", who, GROUPED_MAX_PER_GROUP, (long long)per_group);
+        return AS_EINVAL;
+    }
+    if (groups->sp != sp) {
+        set_err("%s: the groups were made for another space", who);
+        return AS_EINVAL;
+    }
+    if (sub && sub->sp != sp) {
+        set_err("%s: the subset was made for another space", who);
+        return AS_EINVAL;
+    }
+    return subset_checks(who, sp, gr, d, &tau, 1);
+}
+void grouped_counts_add(const as_space* sp, const GroupedCall& call) {
+    for (int i = 0; i < 5; ++i) sp->grouped_count[1 + i].fetch_add(call.counts[i], std::memory_order_relaxed);
+    sp->grouped_us.store(call.us, std::memory_order_relaxed);
+}
+as_status grouped_sink_chunk(void* ctx, SubsetWork*, int64_t i0, int64_t nb, const double* scores, int64_t ld) {
+    return grouped_rows((GroupedCall*)ctx, i0, nb, scores, ld);
+}
+}  // namespace
+
+as_status as_search_grouped(const as_space* sp, const as_graph* gr, const double* query, int64_t d, double tau, const as_groups* groups,
+                            int64_t n_groups, int64_t per_group, const as_subset* sub, int64_t* out_label, int64_t* out_count,
+                            int64_t* out_idx, double* out_score, int64_t* out_ngroups, double* out_lambda_q) {
+    if (!sp || !gr || !query || !groups || !out_label || !out_count || !out_idx || !out_score || !out_ngroups) {
+        set_err("as_search_grouped: null argument");
+        return AS_EINVAL;
+    }
+    *out_ngroups = 0;
+    AS_TRY(grouped_checks("as_search_grouped", sp, gr, d, tau, groups, n_groups, per_group, sub));
+    sp->grouped_count[0].fetch_add(1, std::memory_order_relaxed);
+    double lq = 0.0;
+    {
+        int64_t hidx[SUBSET_TOPK], hlen = 0;
+        double hsc[SUBSET_TOPK];
+        sp->grouped_count[6].fetch_add(1, std::memory_order_relaxed);
+        const as_status s = search_pooled(sp, gr, query, d, tau, hidx, hsc, &hlen, &lq);
+        if (out_lambda_q) *out_lambda_q = lq;
+        if (s != AS_OK) return s;
+    }
+    if (sub && sub->m == 0) return AS_OK;
+    const as_subset* on = nullptr;
+    AS_TRY(range_subset(sp, sub, &on));
+    GroupedCall call;
+    call.w = on->w; call.g = groups; call.m = on->m; call.n_groups = n_groups; call.per_group = per_group;
+    call.out_label = out_label; call.out_count = out_count; call.out_idx = out_idx; call.out_score = out_score; call.out_ngroups = out_ngroups;
+    std::lock_guard<std::mutex> lk(on->mu);
+    AS_HIP(hipSetDevice(sp->device));
+    as_status s = subset_score(sp, on->w, on->m, query, tau, lq);
+    if (s == AS_OK) s = grouped_rows(&call, 0, 1, on->w->scores, on->m);
+    if (s != AS_OK) {
+        (void)hipStreamSynchronize(on->w->stream);
+        *out_ngroups = 0;
+    }
+    grouped_counts_add(sp, call);
+    return s;
+}
+
+as_status as_search_grouped_batch(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau,
+                                  const as_groups* groups, int64_t n_groups, int64_t per_group, const as_subset* sub, int64_t* out_label,
+                                  int64_t* out_count, int64_t* out_idx, double* out_score, int64_t* out_ngroups, double* out_lambda_q,
+                                  int32_t* out_status) {
+    if (!sp || !gr || !groups || b < 0 || (b > 0 && (!queries || !out_label || !out_count || !out_idx || !out_score || !out_ngroups))) {
+        set_err("as_search_grouped_batch: null argument");
+        return AS_EINVAL;
+    }
+    for (int64_t i = 0; i < b; ++i) out_ngroups[i] = 0;
+    AS_TRY(grouped_checks("as_search_grouped_batch", sp, gr, d, tau, groups, n_groups, per_group, sub));
+    sp->grouped_count[0].fetch_add(1, std::memory_order_relaxed);
+    if (b == 0) return AS_OK;
+    std::vector<double> lq;
+    std::vector<int32_t> st;
+    sp->grouped_count[6].fetch_add(1, std::memory_order_relaxed);
+    AS_TRY(batch_lambda_step("as_search_grouped_batch", sp, gr, queries, b, d, tau, lq, st));
+    for (int64_t i = 0; i < b; ++i) {
+        if (out_lambda_q) out_lambda_q[i] = lq[i];
+        if (out_status) out_status[i] = st[i];
+    }
+    if (sub && sub->m == 0) return AS_OK;
+    const as_subset* on = nullptr;
+    AS_TRY(range_subset(sp, sub, &on));
+    GroupedCall call;
+    call.w = on->w; call.g = groups; call.m = on->m; call.n_groups = n_groups; call.per_group = per_group; call.status = st.data();
+    call.out_label = out_label; call.out_count = out_count; call.out_idx = out_idx; call.out_score = out_score; call.out_ngroups = out_ngroups;
+    SubsetChunkSink sink{grouped_sink_chunk, &call};
+    sink.row_bytes = grouped_row_bytes(groups, on->m, n_groups, per_group);
+    std::lock_guard<std::mutex> lk(on->mu);
+    AS_HIP(hipSetDevice(sp->device));
+    const as_status s = subset_batch_run(sp, on->w, on->m, queries, b, lq.data(), st.data(), tau, 0, 0, nullptr, nullptr, nullptr, nullptr, &sink);
+    if (s != AS_OK) {
+        (void)hipStreamSynchronize(on->w->stream);
+        for (int64_t i = 0; i < b; ++i) out_ngroups[i] = 0;
+    }
+    grouped_counts_add(sp, call);
+    return s;
+}
+
+as_status as_grouped_counters(const as_space* sp, int64_t* out, int32_t n) {
+    if (!sp || !out) {
+        set_err("as_grouped_counters: null argument");
+        return AS_EINVAL;
+    }
+    for (int i = 0; i < n && i < 7; ++i) out[i] = sp->grouped_count[i].load(std::memory_order_relaxed);
+    return AS_OK;
+}
+double as_grouped_kernel_us(const as_space* sp) { return sp ? sp->grouped_us.load(std::memory_order_relaxed) : 0.0; }
+
 // ---------------------------------------------------------------- diversified search (extension; as_diverse.hip)
 // what both forms refuse before anything is launched, the pool step included
 static as_status diverse_checks(const char* who, const as_space* sp, const as_graph* gr, int64_t d, double tau, int64_t n, double diversity,

@@ -47,7 +47,7 @@ void dbg(const char* fmt, ...);
 
 }  // namespace as
 
-namespace as { struct SubsetWork; struct ListsWork; struct RangeWork; struct DiverseWork; struct FusedWork; }
+namespace as { struct SubsetWork; struct ListsWork; struct RangeWork; struct DiverseWork; struct FusedWork; struct GroupedWork; }
 struct as_subset;
 
 // ---------------------------------------------------------------- handles
@@ -180,6 +180,12 @@ struct as_space {
     // "fused_timing" (as_fused_kernel_us)
     mutable std::atomic<int64_t> fused_count[4] = {};
     mutable std::atomic<double> fused_us{0.0};
+    // as_search_grouped / as_search_grouped_batch: they run on the caller's subset or on range_all.
+    // as_grouped_counters: [0] calls that passed their checks, [1] pick-kernel launches, [2] scores examined (rows x m per pick
+    // launch), [3] 64-bit max-atomics the pick kernels issued, [4] groups returned, [5] members returned, [6] lambda_q steps run.
+    // grouped_us: the pick kernels of the last call under "grouped_timing" (as_grouped_kernel_us)
+    mutable std::atomic<int64_t> grouped_count[7] = {};
+    mutable std::atomic<double> grouped_us{0.0};
     // as_search_diverse / as_search_diverse_batch: their buffers (as_diverse.hip), made on first use and grown on demand; the
     // selection step of a call is serialised by dmu (the pool step before it is an ordinary search and takes no lock of these).
     // as_diverse_counters: [0] calls that passed their checks, [1] select launches, [2] picks made, [3] dots computed, [4] pool
@@ -234,6 +240,17 @@ struct as_subset {
     int64_t* ids = nullptr;      // [m] host copy (as_subset_ids); null in the space's own subset of all items (position == id)
     as::SubsetWork* w = nullptr;
     mutable std::mutex mu;       // calls on one handle are serialised
+};
+
+// the groups of the items of one space (as_groups_create): every item's dense group number, groups numbered by ascending label
+struct as_groups {
+    const as_space* sp = nullptr;
+    int device = 0;
+    int64_t n = 0, count = 0;        // items, distinct labels
+    std::vector<int32_t> dense;      // [n] item -> group
+    std::vector<int64_t> labels;     // [count] group -> the caller's label, ascending
+    std::vector<int32_t> size;       // [count] items of the group
+    int32_t* dense_dev = nullptr;    // [n] the same on the device, uploaded once
 };
 
 // the answer of a range query (as_search_range, as_search_range_batch): host memory only, independent of the space
@@ -734,6 +751,8 @@ struct SubsetWork {
     RangeWork* range = nullptr;
     // fused multi-query search (as_fused.hip): the accumulator, the weights and the flags, made on the first fused call on this work
     FusedWork* fused = nullptr;
+    // grouped search (as_grouped.hip): the cells, the collapsed scores and the picks, made on the first grouped call on this work
+    GroupedWork* grouped = nullptr;
 };
 as_status subset_work_create(const as_space* sp, int64_t cap, SubsetWork** out);
 void subset_work_free(SubsetWork* w);
@@ -750,6 +769,7 @@ as_status subset_scores_out(SubsetWork* w, int64_t m, double* out);
 struct SubsetChunkSink {
     as_status (*fn)(void* ctx, SubsetWork* w, int64_t i0, int64_t nb, const double* scores, int64_t ld);
     void* ctx;
+    int64_t row_bytes = 0;   // device bytes the sink keeps per query of a chunk beside the m scores: the chunk budget counts them
 };
 as_status subset_batch_run(const as_space* sp, SubsetWork* w, int64_t m, const double* queries, int64_t b, const double* lq,
                            const int32_t* status, double tau, int64_t k, int64_t stride, int64_t* out_idx, double* out_score,
@@ -759,6 +779,8 @@ void set_subset_batch_mib(int v);   // as_set_tuning("subset_batch_mib", v)
 // the work's stream behind whatever wrote them: the first k by (score descending, position ascending) -> ids and scores; waits for
 // the stream.
 as_status subset_select_from(SubsetWork* w, const double* scores, int64_t m, int64_t k, int64_t* out_idx, double* out_score, int64_t* out_len);
+// ... and over `rows` rows ([rows][ld]) at once: row t's list -> w->out[t] (len == min(k, m, SUBSET_TOPK)); waits for the stream.
+as_status subset_select_rows_from(SubsetWork* w, const double* scores, int64_t ld, int64_t m, int64_t k, int64_t rows);
 constexpr int QUERY_BATCH = 32;  // == GQ in as_search.hip: query slots of the batched workspace
 constexpr int TAU_GROUP = 8;     // taus one shared pass of a tau sweep serves (search_sweep, as_search_taus; one gather of a subset)
 // Tau sweeps over the m ids of `w`: nt distinct finite taus, up to TAU_GROUP per gather.  The list / the
@@ -821,6 +843,30 @@ as_status fused_end(FusedCall* c);
 const double* fused_acc(const SubsetWork* w);   // [m], valid after a call with a served row
 void fused_work_free(FusedWork* f);
 void set_fused_timing(int v);   // as_set_tuning("fused_timing", 0 | 1)
+// Grouped search (as_grouped.hip): the S14 answer of `rows` rows of scores over the work's m ids
+// ([rows][ld] on the device, queued on the work's stream): row t belongs to query i0 + t of the call.  Query i's groups -> out_label /
+// out_count + i * n_groups, their members -> out_idx / out_score + (i * n_groups + s) * per_group, out_ngroups[i].  status (null: the
+// single form) AS_EZEROLAMBDA: that query gets 0 groups.  Two waits for the stream (one when no selected group has a second
+// member to give).  counts[0] += pick launches, [1] += scores examined, [2] += max-atomics issued, [3] += groups, [4] += members;
+// us += the pick kernels' microseconds under "grouped_timing".
+constexpr int GROUPED_MAX_PER_GROUP = 16;
+struct GroupedCall {
+    SubsetWork* w = nullptr;
+    const as_groups* g = nullptr;
+    int64_t m = 0, n_groups = 0, per_group = 0;
+    const int32_t* status = nullptr;
+    int64_t* out_label = nullptr;
+    int64_t* out_count = nullptr;
+    int64_t* out_idx = nullptr;
+    double* out_score = nullptr;
+    int64_t* out_ngroups = nullptr;
+    int64_t counts[5] = {0, 0, 0, 0, 0};
+    double us = 0.0;
+};
+as_status grouped_rows(GroupedCall* c, int64_t i0, int64_t rows, const double* scores, int64_t ld);
+int64_t grouped_row_bytes(const as_groups* g, int64_t m, int64_t n_groups, int64_t per_group);   // SubsetChunkSink::row_bytes of a call
+void grouped_work_free(GroupedWork* g);
+void set_grouped_timing(int v);   // as_set_tuning("grouped_timing", 0 | 1)
 // Diversified search (as_diverse.hip): the greedy of S12 over b pools -- pool i = pool_idx / pool_score + i * kk,
 // pool_len[i] <= kk entries in the order the route returned them (0: a query that is not served) -- n picks wanted, diversity delta.
 // Pick t of query i -> out_idx / out_score / out_margin (may be null) + i * nn + t, nn = min(n, kk); out_len[i] = min(n, pool_len[i]).

@@ -3655,6 +3655,10 @@ int32_t as_set_tuning(const char* key, int32_t value) {
         set_fused_timing(value);
         return 0;
     }
+    if (key && !strcmp(key, "grouped_timing")) {
+        set_grouped_timing(value);
+        return 0;
+    }
     return 1;
 }
 

@@ -647,6 +647,7 @@ void subset_work_free(SubsetWork* w) {
     if (w->stream) (void)hipStreamSynchronize(w->stream);
     range_work_free(w->range);
     fused_work_free(w->fused);
+    grouped_work_free(w->grouped);
     for (int i = 0; i < 2; ++i)
         if (w->ev[i]) (void)hipEventDestroy(w->ev[i]);
     if (w->stream) (void)hipStreamDestroy(w->stream);
@@ -791,6 +792,20 @@ as_status subset_select_from(SubsetWork* w, const double* scores, int64_t m, int
     return subset_list_out(w->out, k, out_idx, out_score, out_len);
 }
 
+as_status subset_select_rows_from(SubsetWork* w, const double* scores, int64_t ld, int64_t m, int64_t k, int64_t rows) {
+    if (m <= 0 || k <= 0 || rows <= 0) return AS_OK;
+    k = std::min<int64_t>(std::min<int64_t>(k, m), SUBSET_TOPK);
+    AS_TRY(reserve_or_err(w->out, rows, "subset pinned results"));
+    if (m > SUBSET_TOPK) {
+        AS_TRY(reserve_or_err(w->hist, rows * SEL_HIST_WORDS, "subset selection histograms"));
+        AS_TRY(reserve_or_err(w->state, rows * (SEL_PASSES + 1), "subset selection states"));
+        AS_TRY(reserve_or_err(w->sel_pos, rows * SUBSET_TOPK, "subset selected positions"));
+    }
+    AS_TRY(subset_select_rows(w, scores, ld, m, k, rows));
+    AS_HIP(hipStreamSynchronize(w->stream));
+    return AS_OK;
+}
+
 // the m scores themselves, in the order of the ids; waits for the stream
 as_status subset_scores_out(SubsetWork* w, int64_t m, double* out) {
     if (m <= 0) {
@@ -803,8 +818,9 @@ as_status subset_scores_out(SubsetWork* w, int64_t m, double* out) {
 
 // ------------------------------------------------------------------ batched forms
 // Queries per chunk: the largest multiple of the score kernel's query tile whose scores ([chunk][m] doubles) fit this budget, at
-// least one tile, at most SB_QC_MAX (the selection keeps 128 KiB of histograms and a 16 KiB pinned result per query).  Results
-// never depend on it.
+// least one tile, at most SB_QC_MAX (the selection keeps 128 KiB of histograms and a 16 KiB pinned result per query); a sink
+// that keeps device memory per query of its own (SubsetChunkSink::row_bytes) has it counted beside the scores.  Results never
+// depend on it.
 static std::atomic<int> g_subset_batch_mib{256};
 void set_subset_batch_mib(int v) { g_subset_batch_mib.store(v > 0 ? v : 256, std::memory_order_relaxed); }
 constexpr int64_t SB_QC_MAX = 4096;
@@ -816,7 +832,7 @@ as_status subset_batch_run(const as_space* sp, SubsetWork* w, int64_t m, const d
     const bool sel = k > 0;
     if (sel) k = std::min<int64_t>(std::min<int64_t>(k, m), SUBSET_TOPK);
     const int64_t budget = (int64_t)g_subset_batch_mib.load(std::memory_order_relaxed) << 20;
-    int64_t qc = budget / (m * (int64_t)sizeof(double)) / SB_Q * SB_Q;
+    int64_t qc = budget / (m * (int64_t)sizeof(double) + (sink ? sink->row_bytes : 0)) / SB_Q * SB_Q;
     qc = std::min<int64_t>(std::max<int64_t>(qc, SB_Q), SB_QC_MAX);
     qc = std::min<int64_t>(qc, (b + SB_Q - 1) / SB_Q * SB_Q);
     AS_TRY(subset_reserve(w, qc, qc * m, qc, sel, sel && m > SUBSET_TOPK));
