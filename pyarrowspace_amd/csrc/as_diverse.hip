@@ -1,23 +1,19 @@
 // Diversified search (section 5.15): the greedy maximal-marginal-relevance pass over the hit list
 // ("pool") an ordinary search returned.  One block per query runs the whole greedy in ONE launch (diverse_select_kernel): per
 // step a block argmax over the margins of the unselected pool entries, then the cosines of the unselected rows with the row just
-// picked -- lists_score_kernel's trip (as_lists.hip) with the picked row in the query's place.  No P x P matrix is formed.
-// The trip is a textual copy of that kernel's, not a shared device function (section 5.11: sharing bodies changed the originals'
-// generated code) -- whoever changes the loop there changes it here.
+// picked -- the score kernels' four-row trip (gather_trip, as_gather.hpp) with the picked row in the query's place.  No P x P
+// matrix is formed.
 // Entry points: as_api.hip (as_search_diverse, as_search_diverse_batch).
 #include <algorithm>
 #include <atomic>
 #include <new>
 
 #include "as_common.hpp"
+#include "as_gather.hpp"
 
 namespace as {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int DIV_ROWS = 4;          // rows in flight per wave, as LISTS_ROWS
 constexpr int DIV_WAVES = 16;        // waves per block: 64 rows per trip (section 5.15: 1024 threads against 256, measured)
-constexpr int DIV_Q_LDS = 4096;      // the picked row sits in LDS up to this many doubles, as LISTS_Q_LDS
 constexpr int DIV_POOL = SUBSET_TOPK;   // entries of a pool at most (== MAX_TOPK)
 constexpr int64_t DIV_QC_DEFAULT = 4096;   // queries per chunk ("diverse_chunk")
 
@@ -43,9 +39,9 @@ __device__ __forceinline__ bool div_ahead(double ma, int pa, double mb, int pb) 
 // carries no meaning, the tie rule is part of the reduction key), then a slot per wave for the argmax.
 // Step t: every thread folds the margins (1 - delta) s - delta r of live entries t, t + NT, ... (a NaN margin is -inf), a butterfly per
 // wave and a pass over the waves' slots give every thread the same winner; then (not after the last pick) the winner's row is staged
-// and lists_score_kernel's trip runs over the live rows: one wave per row, DIV_ROWS rows at a time, every load of the four issued
-// before the first FMA.  Lane partition, accumulation order and butterfly are that kernel's, and do not depend on which of the two
-// rows is staged (every product is one multiply of the same two values): g(i, j) and g(j, i) have the same bits.
+// and the score kernels' trip (gather_trip, as_gather.hpp) runs over the live rows: one wave per row, GATHER_ROWS rows at a time.
+// Lane partition, accumulation order and butterfly are lists_score_kernel's, and do not depend on which of the two rows is
+// staged (every product is one multiply of the same two values): g(i, j) and g(j, i) have the same bits.
 template <bool F64, bool QLDS>
 __global__ __launch_bounds__(DIV_WAVES * 64) void diverse_select_kernel(DiverseArgs a) {
     extern __shared__ double dsm[];
@@ -73,7 +69,7 @@ __global__ __launch_bounds__(DIV_WAVES * 64) void diverse_select_kernel(DiverseA
     __syncthreads();
     const double ninf = -key_traits<double>::inf();
     const double om = 1.0 - a.delta;
-    constexpr int step = WAVES * DIV_ROWS;
+    constexpr int step = WAVES * GATHER_ROWS;
     for (int t = 0; t < nn; ++t) {
         const int L = P - t;   // live entries
         double bm = ninf;
@@ -130,72 +126,21 @@ __global__ __launch_bounds__(DIV_WAVES * 64) void diverse_select_kernel(DiverseA
         }
         __syncthreads();
         const int end = L - 1, last = end - 1;   // (end >= 1: t + 1 < nn <= P)
-        for (int g = w * DIV_ROWS; g < end; g += step) {
-            int64_t row[DIV_ROWS];
+        for (int g = w * GATHER_ROWS; g < end; g += step) {
+            int64_t row[GATHER_ROWS];
 #pragma unroll
-            for (int rr = 0; rr < DIV_ROWS; ++rr) row[rr] = __builtin_amdgcn_readfirstlane(id[live[min(g + rr, last)]]);   // (a short last group reads its last row again)
+            for (int rr = 0; rr < GATHER_ROWS; ++rr) row[rr] = __builtin_amdgcn_readfirstlane(id[live[min(g + rr, last)]]);   // (a short last group reads its last row again)
             double nrm = 0.0;
             int pos = 0;
-            if (lane < DIV_ROWS && g + lane < end) {
+            if (lane < GATHER_ROWS && g + lane < end) {
                 pos = live[g + lane];
                 nrm = a.n64[id[pos]];
             }
-            double acc[DIV_ROWS];
+            double acc[GATHER_ROWS];
+            gather_trip<F64, QLDS>(a.x32, a.x64, a.d, a.dp, row, qs, [&](int64_t e) { return F64 ? qg[e] : (double)qf[e]; }, lane, acc);
 #pragma unroll
-            for (int rr = 0; rr < DIV_ROWS; ++rr) acc[rr] = 0.0;
-            if (F64) {
-                constexpr int U = 6;
-                for (int64_t base = 0; base < a.d; base += 64 * U) {
-                    double v[DIV_ROWS][U];
-#pragma unroll
-                    for (int rr = 0; rr < DIV_ROWS; ++rr) {
-                        const double* pj = a.x64 + row[rr] * a.d;
-#pragma unroll
-                        for (int u = 0; u < U; ++u) {
-                            const int64_t e = base + 64 * u + lane;
-                            v[rr][u] = e < a.d ? pj[e] : 0.0;
-                        }
-                    }
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        const int64_t e = base + 64 * u + lane;
-                        if (e < a.d) {
-                            const double qv = QLDS ? qs[e] : qg[e];
-#pragma unroll
-                            for (int rr = 0; rr < DIV_ROWS; ++rr) acc[rr] += qv * v[rr][u];
-                        }
-                    }
-                }
-            } else {
-                constexpr int U = 3;
-                for (int64_t base = 0; base < a.dp; base += 256 * U) {
-                    f32x4 v[DIV_ROWS][U];
-#pragma unroll
-                    for (int rr = 0; rr < DIV_ROWS; ++rr) {
-                        const float* pj = a.x32 + row[rr] * a.dp;
-#pragma unroll
-                        for (int u = 0; u < U; ++u) {
-                            const int64_t e = base + 256 * u + 4 * lane;   // (dp is a multiple of 32: e < dp leaves 4 floats)
-                            v[rr][u] = e < a.dp ? *(const f32x4*)(pj + e) : f32x4{0, 0, 0, 0};
-                        }
-                    }
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        const int64_t e = base + 256 * u + 4 * lane;
-                        if (e < a.dp) {
-#pragma unroll
-                            for (int c4 = 0; c4 < 4; ++c4) {
-                                const double qv = QLDS ? qs[e + c4] : (double)qf[e + c4];
-#pragma unroll
-                                for (int rr = 0; rr < DIV_ROWS; ++rr) acc[rr] += qv * (double)v[rr][u][c4];
-                            }
-                        }
-                    }
-                }
-            }
-#pragma unroll
-            for (int rr = 0; rr < DIV_ROWS; ++rr) acc[rr] = wave_sum(acc[rr]);
-            if (lane < DIV_ROWS && g + lane < end) {
+            for (int rr = 0; rr < GATHER_ROWS; ++rr) acc[rr] = wave_sum(acc[rr]);
+            if (lane < GATHER_ROWS && g + lane < end) {
                 const double dot = lane == 0 ? acc[0] : lane == 1 ? acc[1] : lane == 2 ? acc[2] : acc[3];
                 const double den = sqrt(nrm * nsel);
                 const double c = den > 0.0 ? dot / den : 0.0;
@@ -206,7 +151,6 @@ __global__ __launch_bounds__(DIV_WAVES * 64) void diverse_select_kernel(DiverseA
         __syncthreads();   // r is complete; every wave has finished its reads of qs and live[]
     }
 }
-static_assert(DIV_ROWS == 4, "the lane selects of diverse_select_kernel are written for four rows");
 
 // ------------------------------------------------------------------ host side
 static std::atomic<int> g_diverse_timing{0};
@@ -290,7 +234,7 @@ as_status diverse_run(const as_space* sp, const int64_t* pool_idx, const double*
     const int64_t d = sp->d, dp = sp->dp;
     const int64_t chunk = g_diverse_chunk.load(std::memory_order_relaxed);
     const bool timing = g_diverse_timing.load(std::memory_order_relaxed) != 0;
-    const bool qlds = dp <= DIV_Q_LDS;
+    const bool qlds = dp <= GATHER_Q_LDS;
     const size_t lds = sizeof(double) * (size_t)((qlds ? dp : 0) + 2 * kk + DIV_WAVES) + sizeof(int32_t) * (size_t)(2 * kk + 2 * DIV_WAVES);
     w->kernel_us = 0.0;
     for (int64_t i0 = 0; i0 < b; i0 += chunk) {

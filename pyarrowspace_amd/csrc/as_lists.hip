@@ -2,30 +2,35 @@
 // every (query, item) pair of a chunk of queries (lists_score_kernel: the lists cut into segments of at most LISTS_R entries, a block
 // per segment, the single-query kernel's row loop inside), one block per list selects its first k entries exactly
 // (lists_select_kernel: a radix select over LDS histograms, then a rank of at most 1024 entries).
-// Tau sweeps over the lists (section 5.13): lists_score_taus_kernel blends every cosine with up to TAU_GROUP taus, the selection
-// runs a block per (list, tau) pair (lists_run_taus).
+// Tau sweeps over the lists (section 5.13): lists_score_kernel over ListsTausArgs blends every cosine with up to TAU_GROUP taus,
+// the selection runs a block per (list, tau) pair (lists_run_taus).
 // Entry points: as_api.hip (as_score_lists_batch, as_search_lists_batch and their _taus forms).
 #include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <new>
+#include <type_traits>
 
 #include "as_common.hpp"
+#include "as_gather.hpp"
 
 namespace as {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int LISTS_ROWS = 4;         // rows in flight per wave, as subset_score_kernel (as_subset.hip)
 constexpr int LISTS_WAVES = 4;        // waves per block
 constexpr int LISTS_R = 64;           // entries per segment: staging a query (dp * 8 bytes) is 2 / R of the segment's fp32 row bytes (1 / R of fp64 rows)
-constexpr int LISTS_Q_LDS = 4096;     // the query sits in LDS up to this many doubles, as SUB_Q_LDS
 constexpr int LISTS_BLOCKS_PER_CU = 4;
 constexpr int64_t LISTS_QC_MAX = 4096;   // queries per chunk at most (the pinned results and the tables are sized by it)
 
 struct ListsSeg {    // a work item of lists_score_kernel: 1 <= `count` <= LISTS_R consecutive entries of one list of the chunk
     int64_t first;   // entry of the chunk
     int32_t query;   // query of the chunk
+    int32_t count;
+};
+struct ListsTausSeg {   // a segment that knows its list: list t of the chunk owns scores[nt * lfirst .. nt * (lfirst + len)) as [nt][len]
+    int64_t first;      // entry of the chunk (the ids)
+    int64_t lfirst;     // first entry of the segment's list
+    int64_t len;        // entries of the segment's list
+    int32_t query;
     int32_t count;
 };
 struct ListsList {   // a list of the chunk for lists_select_kernel
@@ -48,142 +53,36 @@ struct ListsArgs {
     int64_t d, dp;
     double tau;
 };
-
-// A block takes segments grid-stride; per segment it stages the segment's query in LDS (QLDS; not again when the block's
-// previous segment had the same one) and runs subset_score_kernel's trip over the segment's rows: one wave per row, LISTS_ROWS
-// rows at a time, every load of the four issued before the first FMA, the ids wave-uniform and fetched one trip ahead.  Lane
-// partition, accumulation order and butterfly are that kernel's, and a row's are the same wherever its entry stands: the bits
-// of a score depend on the query, the row, tau and lambda_q only (and equal the single form's for the same lambda_q).
-template <bool F64, bool QLDS>
-__global__ __launch_bounds__(256) void lists_score_kernel(ListsArgs a) {
-    extern __shared__ double qs[];
-    const int lane = lane_id();
-    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    constexpr int64_t step = LISTS_WAVES * LISTS_ROWS;
-    int staged = -1;
-    for (int64_t s = blockIdx.x; s < a.nseg; s += gridDim.x) {
-        const ListsSeg sg = a.segs[s];   // (s is uniform: scalar loads)
-        const double* qg = a.q64 + (int64_t)sg.query * a.dp;
-        if (QLDS && sg.query != staged) {
-            __syncthreads();   // every wave has finished the previous segment's reads of qs
-            for (int64_t c = threadIdx.x; c < a.dp; c += blockDim.x) qs[c] = qg[c];
-            __syncthreads();
-            staged = sg.query;
-        }
-        const double nqv = a.nq[sg.query], lqv = a.lq[sg.query];
-        const int64_t end = sg.first + sg.count, last = end - 1;
-        int64_t g = sg.first + (int64_t)w * LISTS_ROWS;
-        int32_t next[LISTS_ROWS];
-#pragma unroll
-        for (int r = 0; r < LISTS_ROWS; ++r) next[r] = a.ids[min(g + r, last)];
-        for (; g < end; g += step) {
-            int64_t row[LISTS_ROWS];
-#pragma unroll
-            for (int r = 0; r < LISTS_ROWS; ++r) row[r] = next[r];   // (a short last group reads its last row again)
-#pragma unroll
-            for (int r = 0; r < LISTS_ROWS; ++r) next[r] = a.ids[min(g + step + r, last)];
-            double nrm = 0.0, lam = 0.0;
-            if (lane < LISTS_ROWS) {
-                const int64_t j = lane == 0 ? row[0] : lane == 1 ? row[1] : lane == 2 ? row[2] : row[3];
-                nrm = a.n64[j];
-                lam = a.lam64[j];
-            }
-            double acc[LISTS_ROWS];
-#pragma unroll
-            for (int r = 0; r < LISTS_ROWS; ++r) acc[r] = 0.0;
-            if (F64) {
-                constexpr int U = 6;
-                for (int64_t base = 0; base < a.d; base += 64 * U) {
-                    double v[LISTS_ROWS][U];
-#pragma unroll
-                    for (int r = 0; r < LISTS_ROWS; ++r) {
-                        const double* pj = a.x64 + row[r] * a.d;
-#pragma unroll
-                        for (int u = 0; u < U; ++u) {
-                            const int64_t e = base + 64 * u + lane;
-                            v[r][u] = e < a.d ? pj[e] : 0.0;
-                        }
-                    }
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        const int64_t e = base + 64 * u + lane;
-                        if (e < a.d) {
-                            const double qv = QLDS ? qs[e] : qg[e];
-#pragma unroll
-                            for (int r = 0; r < LISTS_ROWS; ++r) acc[r] += qv * v[r][u];
-                        }
-                    }
-                }
-            } else {
-                constexpr int U = 3;
-                for (int64_t base = 0; base < a.dp; base += 256 * U) {
-                    f32x4 v[LISTS_ROWS][U];
-#pragma unroll
-                    for (int r = 0; r < LISTS_ROWS; ++r) {
-                        const float* pj = a.x32 + row[r] * a.dp;
-#pragma unroll
-                        for (int u = 0; u < U; ++u) {
-                            const int64_t e = base + 256 * u + 4 * lane;   // (dp is a multiple of 32: e < dp leaves 4 floats)
-                            v[r][u] = e < a.dp ? *(const f32x4*)(pj + e) : f32x4{0, 0, 0, 0};
-                        }
-                    }
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        const int64_t e = base + 256 * u + 4 * lane;
-                        if (e < a.dp) {
-#pragma unroll
-                            for (int t = 0; t < 4; ++t) {
-                                const double qv = QLDS ? qs[e + t] : qg[e + t];
-#pragma unroll
-                                for (int r = 0; r < LISTS_ROWS; ++r) acc[r] += qv * (double)v[r][u][t];
-                            }
-                        }
-                    }
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < LISTS_ROWS; ++r) acc[r] = wave_sum(acc[r]);
-            if (lane < LISTS_ROWS && g + lane < end) {
-                const double dot = lane == 0 ? acc[0] : lane == 1 ? acc[1] : lane == 2 ? acc[2] : acc[3];
-                const double den = sqrt(nrm * nqv);
-                const double c = den > 0.0 ? dot / den : 0.0;
-                a.scores[g + lane] = blend_score(a.tau, c, lqv, lam);
-            }
-        }
-    }
-}
-static_assert(LISTS_ROWS == 4, "the lane selects of lists_score_kernel are written for four rows");
-
-// ------------------------------------------------------------------ tau sweep score kernel
-// A textual copy of lists_score_kernel with subset_score_taus_kernel's epilogue (as_subset.hip): the cosine of a (query, item)
-// pair is formed once and blended with each of nt <= TAU_GROUP taus.  Segment loop, staging, trip, lane partition, accumulation
-// order and butterfly are the original's, so for the same lambda_q a plane holds the bits lists_score_kernel writes for that
-// tau.  A copy, not a shared device function (section 5.11: sharing bodies changed the originals' generated code) -- whoever
-// changes a loop above changes it here.  The taus and their count travel in the argument struct (scalar loads); the loop over
-// them is unrolled and predicated on the wave-uniform count.
-struct ListsTausSeg {   // a segment that knows its list: list t of the chunk owns scores[nt * lfirst .. nt * (lfirst + len)) as [nt][len]
-    int64_t first;      // entry of the chunk (the ids)
-    int64_t lfirst;     // first entry of the segment's list
-    int64_t len;        // entries of the segment's list
-    int32_t query;
-    int32_t count;
-};
+// The tau sweep's arguments (section 5.13): the taus and their count travel in the struct (scalar loads)
 struct ListsTausArgs {
     ListsArgs s;        // (s.segs and s.tau are not read)
     const ListsTausSeg* segs;
     int nt;
     double taus[TAU_GROUP];
 };
-template <bool F64, bool QLDS>
-__global__ __launch_bounds__(256) void lists_score_taus_kernel(ListsTausArgs t) {
-    const ListsArgs& a = t.s;
+
+// A block takes segments grid-stride; per segment it stages the segment's query in LDS (QLDS; not again when the block's
+// previous segment had the same one) and runs subset_score_kernel's row loop over the segment's rows: one wave per row,
+// GATHER_ROWS rows at a time (gather_trip, as_gather.hpp), the ids wave-uniform and fetched one trip ahead.  A row's lane
+// partition, accumulation order and butterfly are the same wherever its entry stands: the bits of a score depend on the query,
+// the row, tau and lambda_q only (and equal the single form's for the same lambda_q).
+// Args = ListsArgs: one score per entry, scores[entry]; ListsTausArgs: the cosine is formed once and blended with each of
+// nt <= TAU_GROUP taus into the planes of the entry's list.  Everything in front of the stores is one body, so a plane holds
+// the bits the single-tau instantiation writes for that tau.
+template <bool F64, bool QLDS, class Args>
+__global__ __launch_bounds__(256) void lists_score_kernel(Args args) {
+    constexpr bool TAUS = std::is_same<Args, ListsTausArgs>::value;
+    const ListsArgs* base;   // (picked in place: handing `args` to a helper by reference cost the fp32 instantiations up to 22 VGPRs)
+    if constexpr (TAUS) base = &args.s;
+    else base = &args;
+    const ListsArgs& a = *base;
     extern __shared__ double qs[];
     const int lane = lane_id();
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    constexpr int64_t step = LISTS_WAVES * LISTS_ROWS;
+    constexpr int64_t step = LISTS_WAVES * GATHER_ROWS;
     int staged = -1;
     for (int64_t s = blockIdx.x; s < a.nseg; s += gridDim.x) {
-        const ListsTausSeg sg = t.segs[s];   // (s is uniform: scalar loads)
+        const auto sg = args.segs[s];   // (ListsSeg or ListsTausSeg; s is uniform: scalar loads)
         const double* qg = a.q64 + (int64_t)sg.query * a.dp;
         if (QLDS && sg.query != staged) {
             __syncthreads();   // every wave has finished the previous segment's reads of qs
@@ -193,86 +92,39 @@ __global__ __launch_bounds__(256) void lists_score_taus_kernel(ListsTausArgs t) 
         }
         const double nqv = a.nq[sg.query], lqv = a.lq[sg.query];
         const int64_t end = sg.first + sg.count, last = end - 1;
-        int64_t g = sg.first + (int64_t)w * LISTS_ROWS;
-        int32_t next[LISTS_ROWS];
+        int64_t g = sg.first + (int64_t)w * GATHER_ROWS;
+        int32_t next[GATHER_ROWS];
 #pragma unroll
-        for (int r = 0; r < LISTS_ROWS; ++r) next[r] = a.ids[min(g + r, last)];
+        for (int r = 0; r < GATHER_ROWS; ++r) next[r] = a.ids[min(g + r, last)];
         for (; g < end; g += step) {
-            int64_t row[LISTS_ROWS];
+            int64_t row[GATHER_ROWS];
 #pragma unroll
-            for (int r = 0; r < LISTS_ROWS; ++r) row[r] = next[r];   // (a short last group reads its last row again)
+            for (int r = 0; r < GATHER_ROWS; ++r) row[r] = next[r];   // (a short last group reads its last row again)
 #pragma unroll
-            for (int r = 0; r < LISTS_ROWS; ++r) next[r] = a.ids[min(g + step + r, last)];
+            for (int r = 0; r < GATHER_ROWS; ++r) next[r] = a.ids[min(g + step + r, last)];
             double nrm = 0.0, lam = 0.0;
-            if (lane < LISTS_ROWS) {
+            if (lane < GATHER_ROWS) {
                 const int64_t j = lane == 0 ? row[0] : lane == 1 ? row[1] : lane == 2 ? row[2] : row[3];
                 nrm = a.n64[j];
                 lam = a.lam64[j];
             }
-            double acc[LISTS_ROWS];
+            double acc[GATHER_ROWS];
+            gather_trip<F64, QLDS>(a.x32, a.x64, a.d, a.dp, row, qs, [&](int64_t e) { return qg[e]; }, lane, acc);
 #pragma unroll
-            for (int r = 0; r < LISTS_ROWS; ++r) acc[r] = 0.0;
-            if (F64) {
-                constexpr int U = 6;
-                for (int64_t base = 0; base < a.d; base += 64 * U) {
-                    double v[LISTS_ROWS][U];
-#pragma unroll
-                    for (int r = 0; r < LISTS_ROWS; ++r) {
-                        const double* pj = a.x64 + row[r] * a.d;
-#pragma unroll
-                        for (int u = 0; u < U; ++u) {
-                            const int64_t e = base + 64 * u + lane;
-                            v[r][u] = e < a.d ? pj[e] : 0.0;
-                        }
-                    }
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        const int64_t e = base + 64 * u + lane;
-                        if (e < a.d) {
-                            const double qv = QLDS ? qs[e] : qg[e];
-#pragma unroll
-                            for (int r = 0; r < LISTS_ROWS; ++r) acc[r] += qv * v[r][u];
-                        }
-                    }
-                }
-            } else {
-                constexpr int U = 3;
-                for (int64_t base = 0; base < a.dp; base += 256 * U) {
-                    f32x4 v[LISTS_ROWS][U];
-#pragma unroll
-                    for (int r = 0; r < LISTS_ROWS; ++r) {
-                        const float* pj = a.x32 + row[r] * a.dp;
-#pragma unroll
-                        for (int u = 0; u < U; ++u) {
-                            const int64_t e = base + 256 * u + 4 * lane;   // (dp is a multiple of 32: e < dp leaves 4 floats)
-                            v[r][u] = e < a.dp ? *(const f32x4*)(pj + e) : f32x4{0, 0, 0, 0};
-                        }
-                    }
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        const int64_t e = base + 256 * u + 4 * lane;
-                        if (e < a.dp) {
-#pragma unroll
-                            for (int c4 = 0; c4 < 4; ++c4) {
-                                const double qv = QLDS ? qs[e + c4] : qg[e + c4];
-#pragma unroll
-                                for (int r = 0; r < LISTS_ROWS; ++r) acc[r] += qv * (double)v[r][u][c4];
-                            }
-                        }
-                    }
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < LISTS_ROWS; ++r) acc[r] = wave_sum(acc[r]);
-            if (lane < LISTS_ROWS && g + lane < end) {
+            for (int r = 0; r < GATHER_ROWS; ++r) acc[r] = wave_sum(acc[r]);
+            if (lane < GATHER_ROWS && g + lane < end) {
                 const double dot = lane == 0 ? acc[0] : lane == 1 ? acc[1] : lane == 2 ? acc[2] : acc[3];
                 const double den = sqrt(nrm * nqv);
                 const double c = den > 0.0 ? dot / den : 0.0;
-                // entry g + lane of the chunk is entry g + lane - lfirst of its list: plane j of the list's [nt][len] block
-                double* out = a.scores + (int64_t)t.nt * sg.lfirst + (g + lane - sg.lfirst);
+                if constexpr (TAUS) {
+                    // entry g + lane of the chunk is entry g + lane - lfirst of its list: plane j of the list's [nt][len] block
+                    double* out = a.scores + (int64_t)args.nt * sg.lfirst + (g + lane - sg.lfirst);
 #pragma unroll
-                for (int j = 0; j < TAU_GROUP; ++j)   // (unrolled: taus[j] is a scalar load, j < nt a scalar compare)
-                    if (j < t.nt) out[j * sg.len] = blend_score(t.taus[j], c, lqv, lam);
+                    for (int j = 0; j < TAU_GROUP; ++j)   // (unrolled: taus[j] is a scalar load, j < nt a scalar compare)
+                        if (j < args.nt) out[j * sg.len] = blend_score(args.taus[j], c, lqv, lam);
+                } else {
+                    a.scores[g + lane] = blend_score(a.tau, c, lqv, lam);
+                }
             }
         }
     }
@@ -304,7 +156,7 @@ struct ListsSelArgs {
 // the entries at or above T's prefix (T's unknown digits zero) number at most LSEL_CAP -- after the last pass exactly k do.
 // Then (every list) the entries with key >= T are collected in LDS and ranked; the first k go to the pinned result.
 // PLANES (the tau sweep, section 5.13): block p serves plane p % nt of list p / nt: the scores are that plane of the list's
-// [nt][len] block (lists_score_taus_kernel), the ids the list's, shared by its planes.
+// [nt][len] block (lists_score_kernel over ListsTausArgs), the ids the list's, shared by its planes.
 template <bool PLANES>
 __global__ __launch_bounds__(LSEL_NT) void lists_select_kernel(ListsSelArgs a) {
     __shared__ unsigned int hist[LSEL_BINS];
@@ -494,7 +346,7 @@ as_status lists_run(const as_space* sp, const int32_t* ids, const int64_t* offs,
     const int64_t d = sp->d, dp = sp->dp;
     const int64_t budget = std::max<int64_t>(((int64_t)g_lists_budget_mib.load(std::memory_order_relaxed) << 20) / (int64_t)sizeof(double), 1);
     const bool timing = g_lists_timing.load(std::memory_order_relaxed) != 0;
-    const bool qlds = dp <= LISTS_Q_LDS;
+    const bool qlds = dp <= GATHER_Q_LDS;
     const size_t lds = qlds ? sizeof(double) * (size_t)dp : 0;
     auto now = [] { return std::chrono::steady_clock::now(); };
     w->kernel_us = 0.0;
@@ -553,11 +405,11 @@ as_status lists_run(const as_space* sp, const int32_t* ids, const int64_t* offs,
             const unsigned grid = (unsigned)std::min<int64_t>(nseg, (int64_t)w->cus * LISTS_BLOCKS_PER_CU);
             if (timing) AS_HIP(hipEventRecord(w->ev.e[0], w->stream));
             if (sp->x64) {
-                if (qlds) hipLaunchKernelGGL((lists_score_kernel<true, true>), dim3(grid), dim3(256), lds, w->stream, a);
-                else hipLaunchKernelGGL((lists_score_kernel<true, false>), dim3(grid), dim3(256), 0, w->stream, a);
+                if (qlds) hipLaunchKernelGGL((lists_score_kernel<true, true, ListsArgs>), dim3(grid), dim3(256), lds, w->stream, a);
+                else hipLaunchKernelGGL((lists_score_kernel<true, false, ListsArgs>), dim3(grid), dim3(256), 0, w->stream, a);
             } else {
-                if (qlds) hipLaunchKernelGGL((lists_score_kernel<false, true>), dim3(grid), dim3(256), lds, w->stream, a);
-                else hipLaunchKernelGGL((lists_score_kernel<false, false>), dim3(grid), dim3(256), 0, w->stream, a);
+                if (qlds) hipLaunchKernelGGL((lists_score_kernel<false, true, ListsArgs>), dim3(grid), dim3(256), lds, w->stream, a);
+                else hipLaunchKernelGGL((lists_score_kernel<false, false, ListsArgs>), dim3(grid), dim3(256), 0, w->stream, a);
             }
             AS_HIP(hipGetLastError());
             if (timing) AS_HIP(hipEventRecord(w->ev.e[1], w->stream));
@@ -601,7 +453,7 @@ as_status lists_run(const as_space* sp, const int32_t* ids, const int64_t* offs,
 }
 
 // The tau sweep (section 5.13): lists_run's chunks with ONE upload per chunk for all its tau groups, then per group of tg <= TAU_GROUP
-// taus one gather (lists_score_taus_kernel) into the chunk's [list][tg][len] planes and either one selection block per (list,
+// taus one gather (lists_score_kernel over ListsTausArgs) into the chunk's [list][tg][len] planes and either one selection block per (list,
 // tau) pair or the copies out; one stream wait per (chunk, group).  tg of a chunk is the largest that fits the budget for the
 // chunk's first list (a longer list further on ends the chunk), so a list too long for the budget is alone at tg = 1.
 as_status lists_run_taus(const as_space* sp, const int32_t* ids, const int64_t* offs, const double* queries, int64_t b, const double* lq,
@@ -616,7 +468,7 @@ as_status lists_run_taus(const as_space* sp, const int32_t* ids, const int64_t* 
     const int64_t d = sp->d, dp = sp->dp;
     const int64_t budget = std::max<int64_t>(((int64_t)g_lists_budget_mib.load(std::memory_order_relaxed) << 20) / (int64_t)sizeof(double), 1);
     const bool timing = g_lists_timing.load(std::memory_order_relaxed) != 0;
-    const bool qlds = dp <= LISTS_Q_LDS;
+    const bool qlds = dp <= GATHER_Q_LDS;
     const size_t lds = qlds ? sizeof(double) * (size_t)dp : 0;
     auto now = [] { return std::chrono::steady_clock::now(); };
     w->kernel_us = 0.0;
@@ -682,11 +534,11 @@ as_status lists_run_taus(const as_space* sp, const int32_t* ids, const int64_t* 
                 for (int64_t j = 0; j < TAU_GROUP; ++j) a.taus[j] = j < g ? taus[u0 + j] : 0.0;
                 if (timing) AS_HIP(hipEventRecord(w->ev.e[0], w->stream));
                 if (sp->x64) {
-                    if (qlds) hipLaunchKernelGGL((lists_score_taus_kernel<true, true>), dim3(grid), dim3(256), lds, w->stream, a);
-                    else hipLaunchKernelGGL((lists_score_taus_kernel<true, false>), dim3(grid), dim3(256), 0, w->stream, a);
+                    if (qlds) hipLaunchKernelGGL((lists_score_kernel<true, true, ListsTausArgs>), dim3(grid), dim3(256), lds, w->stream, a);
+                    else hipLaunchKernelGGL((lists_score_kernel<true, false, ListsTausArgs>), dim3(grid), dim3(256), 0, w->stream, a);
                 } else {
-                    if (qlds) hipLaunchKernelGGL((lists_score_taus_kernel<false, true>), dim3(grid), dim3(256), lds, w->stream, a);
-                    else hipLaunchKernelGGL((lists_score_taus_kernel<false, false>), dim3(grid), dim3(256), 0, w->stream, a);
+                    if (qlds) hipLaunchKernelGGL((lists_score_kernel<false, true, ListsTausArgs>), dim3(grid), dim3(256), lds, w->stream, a);
+                    else hipLaunchKernelGGL((lists_score_kernel<false, false, ListsTausArgs>), dim3(grid), dim3(256), 0, w->stream, a);
                 }
                 AS_HIP(hipGetLastError());
                 if (timing) AS_HIP(hipEventRecord(w->ev.e[1], w->stream));

@@ -5,15 +5,13 @@
 #include <algorithm>
 #include <atomic>
 #include <new>
+#include <type_traits>
 
 #include "as_common.hpp"
+#include "as_gather.hpp"
 
 namespace as {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int SUB_ROWS = 4;        // rows in flight per wave: every load of the four is issued before the first FMA
-constexpr int SUB_Q_LDS = 4096;    // the query sits in LDS up to this many doubles (32 KiB a block); longer ones are read from global memory
 constexpr int SUB_BLOCKS_PER_CU = 4;   // 4 blocks of 4 waves: 16 waves per CU
 
 struct SubsetArgs {
@@ -28,12 +26,26 @@ struct SubsetArgs {
     int64_t d, dp;
     double nq, lq, tau;
 };
+// The tau sweep's arguments: the taus and their count travel in the struct (scalar loads)
+struct SubsetTausArgs {
+    SubsetArgs s;   // (s.tau is not read)
+    int64_t ld;     // plane j: scores + j * ld
+    int nt;
+    double taus[TAU_GROUP];
+};
 
-// One wave per row, SUB_ROWS rows at a time, grid-stride over the id list; the ids are wave-uniform.  F64: the rows are the fp64
-// items ([n][d], rows 8-byte aligned: one double per lane and load); else the fp32 items ([np][dp], zero padded, dp a multiple of
-// 32: 16 bytes per lane and load), widened before the product.  QLDS: the query is staged in LDS once per block.
-template <bool F64, bool QLDS>
-__global__ __launch_bounds__(256) void subset_score_kernel(SubsetArgs a) {
+// One wave per row, GATHER_ROWS rows at a time (gather_trip, as_gather.hpp), grid-stride over the id list; the ids are
+// wave-uniform.  F64: the rows are the fp64 items, else the fp32 items; QLDS: the query is staged in LDS once per block.
+// Args = SubsetArgs: one score per item; SubsetTausArgs: the cosine of a (query, item) pair is formed once and blended with
+// each of nt <= TAU_GROUP taus into the planes scores[j * ld + pos].  Everything in front of the stores is one body, so for the
+// same lambda_q a plane holds the bits the single-tau instantiation of the same route writes for that tau.
+template <bool F64, bool QLDS, class Args>
+__global__ __launch_bounds__(256) void subset_score_kernel(Args args) {
+    constexpr bool TAUS = std::is_same<Args, SubsetTausArgs>::value;
+    const SubsetArgs* base;   // (picked in place, not by a helper that takes `args` by reference: as_lists.hip)
+    if constexpr (TAUS) base = &args.s;
+    else base = &args;
+    const SubsetArgs& a = *base;
     extern __shared__ double qs[];
     if (QLDS) {
         for (int64_t c = threadIdx.x; c < a.dp; c += blockDim.x) qs[c] = a.q64[c];
@@ -42,87 +54,41 @@ __global__ __launch_bounds__(256) void subset_score_kernel(SubsetArgs a) {
     const int lane = lane_id();
     // (the wave's number as a scalar: the id loads below are scalar loads then)
     const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int64_t step = (int64_t)gridDim.x * (blockDim.x >> 6) * SUB_ROWS;
-    int32_t next[SUB_ROWS];   // the ids of the next group: loaded one trip ahead, no id load in front of a trip's row loads
+    const int64_t step = (int64_t)gridDim.x * (blockDim.x >> 6) * GATHER_ROWS;
+    int32_t next[GATHER_ROWS];   // the ids of the next group: loaded one trip ahead, no id load in front of a trip's row loads
 #pragma unroll
-    for (int r = 0; r < SUB_ROWS; ++r) next[r] = a.ids[min(wave * SUB_ROWS + r, a.m - 1)];
-    for (int64_t g = wave * SUB_ROWS; g < a.m; g += step) {
-        int64_t row[SUB_ROWS];
+    for (int r = 0; r < GATHER_ROWS; ++r) next[r] = a.ids[min(wave * GATHER_ROWS + r, a.m - 1)];
+    for (int64_t g = wave * GATHER_ROWS; g < a.m; g += step) {
+        int64_t row[GATHER_ROWS];
 #pragma unroll
-        for (int r = 0; r < SUB_ROWS; ++r) row[r] = next[r];   // (a short last group reads its last row again)
+        for (int r = 0; r < GATHER_ROWS; ++r) row[r] = next[r];   // (a short last group reads its last row again)
 #pragma unroll
-        for (int r = 0; r < SUB_ROWS; ++r) next[r] = a.ids[min(g + step + r, a.m - 1)];
-        // norm and lambda of row `lane` of the group, in flight under the dot products (lanes 0 .. SUB_ROWS - 1)
+        for (int r = 0; r < GATHER_ROWS; ++r) next[r] = a.ids[min(g + step + r, a.m - 1)];
+        // norm and lambda of row `lane` of the group, in flight under the dot products (lanes 0 .. GATHER_ROWS - 1)
         double nrm = 0.0, lam = 0.0;
-        if (lane < SUB_ROWS) {
+        if (lane < GATHER_ROWS) {
             const int64_t j = lane == 0 ? row[0] : lane == 1 ? row[1] : lane == 2 ? row[2] : row[3];
             nrm = a.n64[j];
             lam = a.lam64[j];
         }
-        double acc[SUB_ROWS];
+        double acc[GATHER_ROWS];
+        gather_trip<F64, QLDS>(a.x32, a.x64, a.d, a.dp, row, qs, [&](int64_t e) { return a.q64[e]; }, lane, acc);
 #pragma unroll
-        for (int r = 0; r < SUB_ROWS; ++r) acc[r] = 0.0;
-        if (F64) {
-            constexpr int U = 6;   // 64 doubles per load of a wave: 384 columns of 4 rows before the first FMA
-            for (int64_t base = 0; base < a.d; base += 64 * U) {
-                double v[SUB_ROWS][U];
-#pragma unroll
-                for (int r = 0; r < SUB_ROWS; ++r) {
-                    const double* pj = a.x64 + row[r] * a.d;
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        const int64_t e = base + 64 * u + lane;
-                        v[r][u] = e < a.d ? pj[e] : 0.0;
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const int64_t e = base + 64 * u + lane;
-                    if (e < a.d) {
-                        const double qv = QLDS ? qs[e] : a.q64[e];
-#pragma unroll
-                        for (int r = 0; r < SUB_ROWS; ++r) acc[r] += qv * v[r][u];
-                    }
-                }
-            }
-        } else {
-            constexpr int U = 3;   // 256 floats per load of a wave: a whole 768-float row of 4 rows before the first FMA
-            for (int64_t base = 0; base < a.dp; base += 256 * U) {
-                f32x4 v[SUB_ROWS][U];
-#pragma unroll
-                for (int r = 0; r < SUB_ROWS; ++r) {
-                    const float* pj = a.x32 + row[r] * a.dp;
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        const int64_t e = base + 256 * u + 4 * lane;   // (dp is a multiple of 32: e < dp leaves 4 floats)
-                        v[r][u] = e < a.dp ? *(const f32x4*)(pj + e) : f32x4{0, 0, 0, 0};
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const int64_t e = base + 256 * u + 4 * lane;
-                    if (e < a.dp) {
-#pragma unroll
-                        for (int t = 0; t < 4; ++t) {
-                            const double qv = QLDS ? qs[e + t] : a.q64[e + t];
-#pragma unroll
-                            for (int r = 0; r < SUB_ROWS; ++r) acc[r] += qv * (double)v[r][u][t];
-                        }
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < SUB_ROWS; ++r) acc[r] = wave_sum(acc[r]);   // (__shfl_xor butterfly: every lane holds the sums)
-        if (lane < SUB_ROWS && g + lane < a.m) {
+        for (int r = 0; r < GATHER_ROWS; ++r) acc[r] = wave_sum(acc[r]);   // (__shfl_xor butterfly: every lane holds the sums)
+        if (lane < GATHER_ROWS && g + lane < a.m) {
             const double dot = lane == 0 ? acc[0] : lane == 1 ? acc[1] : lane == 2 ? acc[2] : acc[3];
             const double den = sqrt(nrm * a.nq);
             const double c = den > 0.0 ? dot / den : 0.0;
-            a.scores[g + lane] = blend_score(a.tau, c, a.lq, lam);   // lanes 0 .. 3: one 32-byte store
+            if constexpr (TAUS) {
+#pragma unroll
+                for (int j = 0; j < TAU_GROUP; ++j)   // (unrolled: taus[j] is a scalar load, j < nt a scalar compare)
+                    if (j < args.nt) a.scores[j * args.ld + g + lane] = blend_score(args.taus[j], c, a.lq, lam);   // lanes 0 .. 3: 32 bytes a plane
+            } else {
+                a.scores[g + lane] = blend_score(a.tau, c, a.lq, lam);   // lanes 0 .. 3: one 32-byte store
+            }
         }
     }
 }
-static_assert(SUB_ROWS == 4, "the lane selects of subset_score_kernel are written for four rows");
 
 // ------------------------------------------------------------------ batched score kernel
 // scores[q][i] for a tile of SB_ROWS gathered rows and SB_Q queries per block: an fp64 GEMM on v_mfma_f64_16x16x4_f64 with the
@@ -161,215 +127,22 @@ struct SubsetBatchArgs {
     int nq_valid;
     double tau;
 };
-
-template <bool F64>
-__global__ __launch_bounds__(256) void subset_score_batch_kernel(SubsetBatchArgs a) {
-    constexpr int PX = F64 ? SB_PQ : SB_PF;
-    constexpr int NR = F64 ? 16 : 4;   // rows a thread stages per K stage
-    __shared__ __attribute__((aligned(16))) double qs[SB_Q * SB_PQ];
-    __shared__ __attribute__((aligned(16))) char xs_raw[SB_ROWS * PX * (F64 ? 8 : 4)];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, wi = w >> 1, wj = w & 1;
-    const int lk = lane >> 4, lc = lane & 15;
-    const int64_t row0 = (int64_t)blockIdx.x * SB_ROWS;
-    const int64_t q0 = (int64_t)blockIdx.y * SB_Q;
-    // staging maps.  fp32 rows: thread t holds floats 4 (t & 7) .. + 3 of rows (t >> 3) + 32 i; fp64 rows: double t & 31 of rows
-    // (t >> 5) + 8 i; queries: doubles 2 (t & 15), + 1 of queries (t >> 4) + 16 i
-    const int xc = F64 ? (tid & 31) : (tid & 7) * 4, xr = F64 ? (tid >> 5) : (tid >> 3), xstep = F64 ? 8 : 32;
-    const int qc = (tid & 15) * 2, qr = tid >> 4;
-    int64_t rbase[NR];   // element offset of the staged rows; -1: past the end of the list (zeros)
-#pragma unroll
-    for (int i = 0; i < NR; ++i) {
-        const int64_t pos = row0 + xr + xstep * i;
-        rbase[i] = pos < a.m ? (int64_t)a.ids[pos] * (F64 ? a.d : a.dp) : -1;
-    }
-    const double* qsrc = a.q64 + (q0 + qr) * a.dp + qc;
-    f32x4 vf[F64 ? 1 : NR];
-    double vd[F64 ? NR : 1];
-    f64x2 vq[4];
-    auto load_stage = [&](int64_t k0) {
-#pragma unroll
-        for (int i = 0; i < NR; ++i) {
-            if (F64) vd[i] = (rbase[i] >= 0 && k0 + xc < a.d) ? a.x64[rbase[i] + k0 + xc] : 0.0;
-            else vf[i] = rbase[i] >= 0 ? *(const f32x4*)(a.x32 + rbase[i] + k0 + xc) : f32x4{0, 0, 0, 0};
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) vq[i] = *(const f64x2*)(qsrc + (int64_t)16 * i * a.dp + k0);
-    };
-    f64x4 acc[2][4];
-#pragma unroll
-    for (int ib = 0; ib < 2; ++ib)
-#pragma unroll
-        for (int jb = 0; jb < 4; ++jb) acc[ib][jb] = f64x4{0.0, 0.0, 0.0, 0.0};
-    load_stage(0);
-    for (int64_t k0 = 0; k0 < a.dp; k0 += SB_K) {
-        __syncthreads();   // the previous stage has been consumed
-#pragma unroll
-        for (int i = 0; i < NR; ++i) {
-            if (F64) ((double*)xs_raw)[(xr + xstep * i) * PX + xc] = vd[i];
-            else {
-                f32x2* dst = (f32x2*)((float*)xs_raw + (xr + xstep * i) * PX + xc);
-                dst[0] = f32x2{vf[i][0], vf[i][1]};
-                dst[1] = f32x2{vf[i][2], vf[i][3]};
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) *(f64x2*)(qs + (qr + 16 * i) * SB_PQ + qc) = vq[i];
-        __syncthreads();
-        if (k0 + SB_K < a.dp) load_stage(k0 + SB_K);   // in flight under the MFMAs below
-#pragma unroll
-        for (int ks = 0; ks < SB_K / 4; ++ks) {
-            double av[2], bv[4];
-#pragma unroll
-            for (int ib = 0; ib < 2; ++ib) av[ib] = qs[(32 * wj + 16 * ib + lc) * SB_PQ + 4 * ks + lk];
-#pragma unroll
-            for (int jb = 0; jb < 4; ++jb) {
-                const int e = (64 * wi + 16 * jb + lc) * PX + 4 * ks + lk;
-                bv[jb] = F64 ? ((const double*)xs_raw)[e] : (double)((const float*)xs_raw)[e];
-            }
-#pragma unroll
-            for (int ib = 0; ib < 2; ++ib)
-#pragma unroll
-                for (int jb = 0; jb < 4; ++jb) acc[ib][jb] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[ib], bv[jb], acc[ib][jb], 0, 0, 0);
-        }
-    }
-    // C/D of v_mfma_f64_16x16x4_f64: col = lane & 15 (position), row = (lane >> 4) + 4 reg (query)
-#pragma unroll
-    for (int jb = 0; jb < 4; ++jb) {
-        const int64_t pos = row0 + 64 * wi + 16 * jb + lc;
-        if (pos >= a.m) continue;
-        const int64_t j = a.ids[pos];
-        const double nrm = a.n64[j], lam = a.lam64[j];
-#pragma unroll
-        for (int ib = 0; ib < 2; ++ib)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int64_t q = q0 + 32 * wj + 16 * ib + lk + 4 * r;
-                if (q < a.nq_valid) {
-                    const double den = sqrt(nrm * a.nq[q]);
-                    const double c = den > 0.0 ? acc[ib][jb][r] / den : 0.0;
-                    a.scores[q * a.ld + pos] = blend_score(a.tau, c, a.lq[q], lam);
-                }
-            }
-    }
-}
-
-// ------------------------------------------------------------------ tau sweep score kernels
-// Textual copies of the two score kernels above with another epilogue: the cosine of a (query, item) pair is formed once and
-// blended with each of nt <= TAU_GROUP taus.  Gather, staging, accumulation order and the cosine's operands are the originals',
-// so for the same lambda_q a plane holds the bits the single-tau kernel of the same route writes for that tau.  Copies, not a
-// shared device function: moving the originals' bodies into one changed their generated code, and they stay as they were --
-// whoever changes a loop above changes it here.  The taus and their count travel in the argument struct (scalar loads); the
-// loop over them is unrolled and predicated on the wave-uniform count.
-struct SubsetTausArgs {
-    SubsetArgs s;   // (s.tau is not read)
-    int64_t ld;     // plane j: scores + j * ld
-    int nt;
-    double taus[TAU_GROUP];
-};
-// lanes 0 .. 3 store one score per tau to the planes scores[j * ld + pos]
-template <bool F64, bool QLDS>
-__global__ __launch_bounds__(256) void subset_score_taus_kernel(SubsetTausArgs t) {
-    const SubsetArgs& a = t.s;
-    extern __shared__ double qs[];
-    if (QLDS) {
-        for (int64_t c = threadIdx.x; c < a.dp; c += blockDim.x) qs[c] = a.q64[c];
-        __syncthreads();
-    }
-    const int lane = lane_id();
-    // (the wave's number as a scalar: the id loads below are scalar loads then)
-    const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int64_t step = (int64_t)gridDim.x * (blockDim.x >> 6) * SUB_ROWS;
-    int32_t next[SUB_ROWS];   // the ids of the next group: loaded one trip ahead, no id load in front of a trip's row loads
-#pragma unroll
-    for (int r = 0; r < SUB_ROWS; ++r) next[r] = a.ids[min(wave * SUB_ROWS + r, a.m - 1)];
-    for (int64_t g = wave * SUB_ROWS; g < a.m; g += step) {
-        int64_t row[SUB_ROWS];
-#pragma unroll
-        for (int r = 0; r < SUB_ROWS; ++r) row[r] = next[r];   // (a short last group reads its last row again)
-#pragma unroll
-        for (int r = 0; r < SUB_ROWS; ++r) next[r] = a.ids[min(g + step + r, a.m - 1)];
-        // norm and lambda of row `lane` of the group, in flight under the dot products (lanes 0 .. SUB_ROWS - 1)
-        double nrm = 0.0, lam = 0.0;
-        if (lane < SUB_ROWS) {
-            const int64_t j = lane == 0 ? row[0] : lane == 1 ? row[1] : lane == 2 ? row[2] : row[3];
-            nrm = a.n64[j];
-            lam = a.lam64[j];
-        }
-        double acc[SUB_ROWS];
-#pragma unroll
-        for (int r = 0; r < SUB_ROWS; ++r) acc[r] = 0.0;
-        if (F64) {
-            constexpr int U = 6;   // 64 doubles per load of a wave: 384 columns of 4 rows before the first FMA
-            for (int64_t base = 0; base < a.d; base += 64 * U) {
-                double v[SUB_ROWS][U];
-#pragma unroll
-                for (int r = 0; r < SUB_ROWS; ++r) {
-                    const double* pj = a.x64 + row[r] * a.d;
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        const int64_t e = base + 64 * u + lane;
-                        v[r][u] = e < a.d ? pj[e] : 0.0;
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const int64_t e = base + 64 * u + lane;
-                    if (e < a.d) {
-                        const double qv = QLDS ? qs[e] : a.q64[e];
-#pragma unroll
-                        for (int r = 0; r < SUB_ROWS; ++r) acc[r] += qv * v[r][u];
-                    }
-                }
-            }
-        } else {
-            constexpr int U = 3;   // 256 floats per load of a wave: a whole 768-float row of 4 rows before the first FMA
-            for (int64_t base = 0; base < a.dp; base += 256 * U) {
-                f32x4 v[SUB_ROWS][U];
-#pragma unroll
-                for (int r = 0; r < SUB_ROWS; ++r) {
-                    const float* pj = a.x32 + row[r] * a.dp;
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        const int64_t e = base + 256 * u + 4 * lane;   // (dp is a multiple of 32: e < dp leaves 4 floats)
-                        v[r][u] = e < a.dp ? *(const f32x4*)(pj + e) : f32x4{0, 0, 0, 0};
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const int64_t e = base + 256 * u + 4 * lane;
-                    if (e < a.dp) {
-#pragma unroll
-                        for (int t = 0; t < 4; ++t) {
-                            const double qv = QLDS ? qs[e + t] : a.q64[e + t];
-#pragma unroll
-                            for (int r = 0; r < SUB_ROWS; ++r) acc[r] += qv * (double)v[r][u][t];
-                        }
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < SUB_ROWS; ++r) acc[r] = wave_sum(acc[r]);   // (__shfl_xor butterfly: every lane holds the sums)
-        if (lane < SUB_ROWS && g + lane < a.m) {
-            const double dot = lane == 0 ? acc[0] : lane == 1 ? acc[1] : lane == 2 ? acc[2] : acc[3];
-            const double den = sqrt(nrm * a.nq);
-            const double c = den > 0.0 ? dot / den : 0.0;
-#pragma unroll
-            for (int j = 0; j < TAU_GROUP; ++j)   // (unrolled: taus[j] is a scalar load, j < nt a scalar compare)
-                if (j < t.nt) a.scores[j * t.ld + g + lane] = blend_score(t.taus[j], c, a.lq, lam);   // lanes 0 .. 3: 32 bytes a plane
-        }
-    }
-}
-
-struct SubsetBatchTausArgs {
+struct SubsetBatchTausArgs {   // the tau sweep's (section 5.11)
     SubsetBatchArgs s;   // (s.tau is not read)
     int nt;
     double taus[TAU_GROUP];
 };
-// plane (q, j) of the chunk at scores[(q * nt + j) * ld + pos]: a (query, tau) pair is a row of the selection kernels
-template <bool F64>
-__global__ __launch_bounds__(256) void subset_score_batch_taus_kernel(SubsetBatchTausArgs t) {
-    const SubsetBatchArgs& a = t.s;
+
+// Args = SubsetBatchArgs: scores[q * ld + pos]; SubsetBatchTausArgs: the cosine is blended with each of nt <= TAU_GROUP taus into
+// plane (q, j) of the chunk at scores[(q * nt + j) * ld + pos] -- a (query, tau) pair is a row of the selection kernels.  The two
+// differ in the stores alone.
+template <bool F64, class Args>
+__global__ __launch_bounds__(256) void subset_score_batch_kernel(Args args) {
+    constexpr bool TAUS = std::is_same<Args, SubsetBatchTausArgs>::value;
+    const SubsetBatchArgs* base;
+    if constexpr (TAUS) base = &args.s;
+    else base = &args;
+    const SubsetBatchArgs& a = *base;
     constexpr int PX = F64 ? SB_PQ : SB_PF;
     constexpr int NR = F64 ? 16 : 4;   // rows a thread stages per K stage
     __shared__ __attribute__((aligned(16))) double qs[SB_Q * SB_PQ];
@@ -453,11 +226,15 @@ __global__ __launch_bounds__(256) void subset_score_batch_taus_kernel(SubsetBatc
                 if (q < a.nq_valid) {
                     const double den = sqrt(nrm * a.nq[q]);
                     const double c = den > 0.0 ? acc[ib][jb][r] / den : 0.0;
-                    const double lq = a.lq[q];
-                    double* dst = a.scores + q * t.nt * a.ld + pos;   // plane (q, j): 16 lanes store 128 contiguous bytes
+                    if constexpr (TAUS) {
+                        const double lq = a.lq[q];
+                        double* dst = a.scores + q * args.nt * a.ld + pos;   // plane (q, j): 16 lanes store 128 contiguous bytes
 #pragma unroll
-                    for (int u = 0; u < TAU_GROUP; ++u)
-                        if (u < t.nt) dst[u * a.ld] = blend_score(t.taus[u], c, lq, lam);
+                        for (int u = 0; u < TAU_GROUP; ++u)
+                            if (u < args.nt) dst[u * a.ld] = blend_score(args.taus[u], c, lq, lam);
+                    } else {
+                        a.scores[q * a.ld + pos] = blend_score(a.tau, c, a.lq[q], lam);
+                    }
                 }
             }
     }
@@ -710,17 +487,17 @@ as_status subset_score(const as_space* sp, SubsetWork* w, int64_t m, const doubl
     SubsetArgs a;
     a.ids = w->ids; a.m = m; a.x32 = sp->x32; a.x64 = sp->x64; a.n64 = sp->n64; a.lam64 = sp->lam64; a.q64 = w->qd;
     a.scores = w->scores; a.d = sp->d; a.dp = sp->dp; a.nq = w->qh[w->dp]; a.lq = lambda_q; a.tau = tau;
-    const int64_t groups = (m + SUB_ROWS - 1) / SUB_ROWS;   // one per wave and trip
+    const int64_t groups = (m + GATHER_ROWS - 1) / GATHER_ROWS;   // one per wave and trip
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((groups + 3) / 4, (int64_t)w->cus * SUB_BLOCKS_PER_CU));
-    const bool qlds = sp->dp <= SUB_Q_LDS;
+    const bool qlds = sp->dp <= GATHER_Q_LDS;
     const size_t lds = qlds ? sizeof(double) * (size_t)sp->dp : 0;
     if (w->timing) AS_HIP(hipEventRecord(w->ev[0], w->stream));
     if (sp->x64) {
-        if (qlds) hipLaunchKernelGGL((subset_score_kernel<true, true>), dim3(grid), dim3(256), lds, w->stream, a);
-        else hipLaunchKernelGGL((subset_score_kernel<true, false>), dim3(grid), dim3(256), 0, w->stream, a);
+        if (qlds) hipLaunchKernelGGL((subset_score_kernel<true, true, SubsetArgs>), dim3(grid), dim3(256), lds, w->stream, a);
+        else hipLaunchKernelGGL((subset_score_kernel<true, false, SubsetArgs>), dim3(grid), dim3(256), 0, w->stream, a);
     } else {
-        if (qlds) hipLaunchKernelGGL((subset_score_kernel<false, true>), dim3(grid), dim3(256), lds, w->stream, a);
-        else hipLaunchKernelGGL((subset_score_kernel<false, false>), dim3(grid), dim3(256), 0, w->stream, a);
+        if (qlds) hipLaunchKernelGGL((subset_score_kernel<false, true, SubsetArgs>), dim3(grid), dim3(256), lds, w->stream, a);
+        else hipLaunchKernelGGL((subset_score_kernel<false, false, SubsetArgs>), dim3(grid), dim3(256), 0, w->stream, a);
     }
     AS_HIP(hipGetLastError());
     if (w->timing) AS_HIP(hipEventRecord(w->ev[1], w->stream));
@@ -847,8 +624,8 @@ as_status subset_batch_run(const as_space* sp, SubsetWork* w, int64_t m, const d
         a.nq = w->qd + nbp * dp; a.lq = a.nq + nbp; a.scores = w->scores; a.ld = m; a.d = d; a.dp = dp; a.nq_valid = (int)nb; a.tau = tau;
         const dim3 grid((unsigned)((m + SB_ROWS - 1) / SB_ROWS), (unsigned)(nbp / SB_Q));
         if (w->timing) AS_HIP(hipEventRecord(w->ev[0], w->stream));
-        if (sp->x64) hipLaunchKernelGGL(subset_score_batch_kernel<true>, grid, dim3(256), 0, w->stream, a);
-        else hipLaunchKernelGGL(subset_score_batch_kernel<false>, grid, dim3(256), 0, w->stream, a);
+        if (sp->x64) hipLaunchKernelGGL((subset_score_batch_kernel<true, SubsetBatchArgs>), grid, dim3(256), 0, w->stream, a);
+        else hipLaunchKernelGGL((subset_score_batch_kernel<false, SubsetBatchArgs>), grid, dim3(256), 0, w->stream, a);
         AS_HIP(hipGetLastError());
         if (w->timing) AS_HIP(hipEventRecord(w->ev[1], w->stream));
         if (sel) {
@@ -890,9 +667,9 @@ as_status subset_sweep_run(const as_space* sp, SubsetWork* w, int64_t m, const d
     a.s.ids = w->ids; a.s.m = m; a.s.x32 = sp->x32; a.s.x64 = sp->x64; a.s.n64 = sp->n64; a.s.lam64 = sp->lam64; a.s.q64 = w->qd;
     a.s.scores = w->scores; a.s.d = sp->d; a.s.dp = sp->dp; a.s.nq = w->qh[w->dp]; a.s.lq = lambda_q; a.s.tau = 0.0;
     a.ld = m;
-    const int64_t groups = (m + SUB_ROWS - 1) / SUB_ROWS;   // (the grid of subset_score)
+    const int64_t groups = (m + GATHER_ROWS - 1) / GATHER_ROWS;   // (the grid of subset_score)
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((groups + 3) / 4, (int64_t)w->cus * SUB_BLOCKS_PER_CU));
-    const bool qlds = sp->dp <= SUB_Q_LDS;
+    const bool qlds = sp->dp <= GATHER_Q_LDS;
     const size_t lds = qlds ? sizeof(double) * (size_t)sp->dp : 0;
     w->kernel_us = 0.0;
     for (int64_t g0 = 0; g0 < nt; g0 += TAU_GROUP) {
@@ -901,11 +678,11 @@ as_status subset_sweep_run(const as_space* sp, SubsetWork* w, int64_t m, const d
         for (int64_t j = 0; j < TAU_GROUP; ++j) a.taus[j] = j < ng ? taus[g0 + j] : 0.0;
         if (w->timing) AS_HIP(hipEventRecord(w->ev[0], w->stream));
         if (sp->x64) {
-            if (qlds) hipLaunchKernelGGL((subset_score_taus_kernel<true, true>), dim3(grid), dim3(256), lds, w->stream, a);
-            else hipLaunchKernelGGL((subset_score_taus_kernel<true, false>), dim3(grid), dim3(256), 0, w->stream, a);
+            if (qlds) hipLaunchKernelGGL((subset_score_kernel<true, true, SubsetTausArgs>), dim3(grid), dim3(256), lds, w->stream, a);
+            else hipLaunchKernelGGL((subset_score_kernel<true, false, SubsetTausArgs>), dim3(grid), dim3(256), 0, w->stream, a);
         } else {
-            if (qlds) hipLaunchKernelGGL((subset_score_taus_kernel<false, true>), dim3(grid), dim3(256), lds, w->stream, a);
-            else hipLaunchKernelGGL((subset_score_taus_kernel<false, false>), dim3(grid), dim3(256), 0, w->stream, a);
+            if (qlds) hipLaunchKernelGGL((subset_score_kernel<false, true, SubsetTausArgs>), dim3(grid), dim3(256), lds, w->stream, a);
+            else hipLaunchKernelGGL((subset_score_kernel<false, false, SubsetTausArgs>), dim3(grid), dim3(256), 0, w->stream, a);
         }
         AS_HIP(hipGetLastError());
         if (w->timing) AS_HIP(hipEventRecord(w->ev[1], w->stream));
@@ -956,8 +733,8 @@ as_status subset_batch_sweep_run(const as_space* sp, SubsetWork* w, int64_t m, c
             a.nt = (int)ng;
             for (int64_t j = 0; j < TAU_GROUP; ++j) a.taus[j] = j < ng ? taus[g0 + j] : 0.0;
             if (w->timing) AS_HIP(hipEventRecord(w->ev[0], w->stream));
-            if (sp->x64) hipLaunchKernelGGL(subset_score_batch_taus_kernel<true>, grid, dim3(256), 0, w->stream, a);
-            else hipLaunchKernelGGL(subset_score_batch_taus_kernel<false>, grid, dim3(256), 0, w->stream, a);
+            if (sp->x64) hipLaunchKernelGGL((subset_score_batch_kernel<true, SubsetBatchTausArgs>), grid, dim3(256), 0, w->stream, a);
+            else hipLaunchKernelGGL((subset_score_batch_kernel<false, SubsetBatchTausArgs>), grid, dim3(256), 0, w->stream, a);
             AS_HIP(hipGetLastError());
             if (w->timing) AS_HIP(hipEventRecord(w->ev[1], w->stream));
             counts[0] += 1;

@@ -214,10 +214,11 @@ def test_tile_and_group_edges(tiles, m, b, t):
 
 
 @pytest.mark.parametrize("f32", [False, True], ids=["x64", "x32"])
-@pytest.mark.parametrize("d", [1, 3, 31, 33, 100])
+@pytest.mark.parametrize("d", [1, 3, 31, 33, 100, 4100])
 def test_feature_count_edges(d, f32):
+    """d = 4100 (n = 300): dp > 4096, the query does not fit the LDS staging and the single-query sweep reads it from global memory."""
     import pyarrowspace_amd as asp
-    n, b, m = 900, 9, 200
+    n, b, m = (300, 5, 200) if d > 4096 else (900, 9, 200)
     X = clustered(n, d, nclust=8, seed=300 + d, normalise=d > 1)
     if d == 1:
         X = X + 3.0
