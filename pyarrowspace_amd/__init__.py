@@ -39,6 +39,61 @@ def _raise(status: int):
     raise RuntimeError(msg)
 
 
+def _check(status: int, stt=None, b: int = 0):
+    """The end of every call into the library: its status, then (batched forms) the reference's panic for any of the b queries
+    whose lambda_q is 0."""
+    if status:
+        _raise(status)
+    if stt is not None:
+        _panic_on_zero_lambda(stt, b)
+
+
+def _panic_on_zero_lambda(stt, b: int):
+    if (stt[:b] == _lib.AS_EZEROLAMBDA).any():
+        raise PanicException("The lambdas are zero, check the magnitude of items and eps.")
+
+
+def _need_gl(gl):
+    if not isinstance(gl, GraphLaplacian):
+        raise TypeError("argument 'gl': expected GraphLaplacian")
+
+
+def _queries_2d(items) -> np.ndarray:
+    Q = np.ascontiguousarray(items, dtype=np.float64)
+    if Q.ndim != 2:
+        raise TypeError("items must be a 2-D float64 array")
+    return Q
+
+
+def _handle(obj):
+    return None if obj is None else obj._h
+
+
+def _hit_buffers(count: int, kk: int):
+    """Output buffers of `count` hit lists at stride kk (never empty: the C ABI wants pointers) and one status per query."""
+    n = max(count * kk, 1)
+    return np.empty(n, dtype=np.int64), np.empty(n, dtype=np.float64), np.zeros(max(count, 1), dtype=np.int64)
+
+
+def _statuses(b: int) -> np.ndarray:
+    return np.zeros(max(b, 1), dtype=np.int32)
+
+
+def _hit_lists(idx, sc, ln, count: int, kk: int, per: int = 0):
+    """The C ABI's hit lists: list p holds ln[p] (index, score) entries at stride kk.  per > 0: nested, `per` lists per query
+    (a sweep; the caller answers an empty sweep itself)."""
+    idx, sc = idx.reshape(-1)[:count * kk].reshape(count, kk).tolist(), sc.reshape(-1)[:count * kk].reshape(count, kk).tolist()
+    # (tolist + zip: element-wise int()/float() over the arrays cost 1.5 ms per 256 queries, a fifth of the GPU time)
+    flat = [list(zip(ii[:l], ss[:l])) for ii, ss, l in zip(idx, sc, ln.reshape(-1)[:count].tolist())]
+    return [flat[i:i + per] for i in range(0, count, per)] if per else flat
+
+
+def _counters(fn, handle, names) -> dict:
+    out = (C.c_int64 * len(names))()
+    _check(fn(handle, out, len(names)))
+    return dict(zip(names, list(out)))
+
+
 def set_debug(enabled: bool) -> None:
     """src/helpers.rs:12-14: process-global flag; messages go to stderr as `[pyarrowspace] ...`."""
     _L.as_set_debug(1 if enabled else 0)
@@ -229,11 +284,8 @@ def _fused_args(items, gl, weights, mode, on_zero_lambda):
     mode number, skip flag).  TypeError: a `gl` that is no GraphLaplacian, items that are not 2-D, weights that are not numbers;
     ValueError: no vector at all, an unknown mode or on_zero_lambda, a weights length other than J (or a wrong rank), a NaN or
     infinite weight."""
-    if not isinstance(gl, GraphLaplacian):
-        raise TypeError("argument 'gl': expected GraphLaplacian")
-    Q = np.ascontiguousarray(items, dtype=np.float64)
-    if Q.ndim != 2:
-        raise TypeError("items must be a 2-D float64 array")
+    _need_gl(gl)
+    Q = _queries_2d(items)
     if not isinstance(mode, str) or mode not in FUSED_MODES:
         raise ValueError(f"argument 'mode': expected 'sum' or 'max', got {mode!r}")
     if not isinstance(on_zero_lambda, str) or on_zero_lambda not in ("raise", "skip"):
@@ -306,8 +358,7 @@ class ItemSubset:
         """Extension: the subset's item ids, sorted and unique (int64)."""
         out = np.empty(self.size, dtype=np.int64)
         st = _L.as_subset_ids(self._h, out.ctypes.data_as(C.c_void_p))
-        if st:
-            _raise(st)
+        _check(st)
         return out
 
     def set_timing(self, enabled: bool) -> None:
@@ -341,8 +392,7 @@ def _group_labels(labels, nitems: int) -> np.ndarray:
 
 def _grouped_args(gl, tau, n_groups, per_group):
     """What the grouped forms check before they touch a handle."""
-    if not isinstance(gl, GraphLaplacian):
-        raise TypeError("argument 'gl': expected GraphLaplacian")
+    _need_gl(gl)
     for name, v, hi in (("n_groups", n_groups, GROUPED_MAX_GROUPS), ("per_group", per_group, GROUPED_MAX_PER_GROUP)):
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
             raise TypeError(f"argument '{name}': expected an integer")
@@ -526,9 +576,16 @@ class ArrowSpace:
         ids = _item_ids(ids_or_mask, self.nitems, "ids_or_mask")
         h = C.c_void_p()
         st = _L.as_subset_create(self._h, ids.ctypes.data_as(C.c_void_p), ids.shape[0], C.byref(h))
-        if st:
-            _raise(st)
+        _check(st)
         return ItemSubset._wrap(h, self)
+
+    def _as_subset(self, subset, optional=False):
+        """An `ItemSubset` as it is, anything `subset()` accepts as a temporary one; optional: None stands for every item."""
+        return subset if isinstance(subset, ItemSubset) or (optional and subset is None) else self.subset(subset)
+
+    def _hits_bound(self, gl, sub=None) -> int:
+        """Entries of a hit list over the subset (None: every item): min(topk, nitems, |subset|)."""
+        return min(int(gl.graph_params["topk"]), self.nitems, self.nitems if sub is None else sub.size)
 
     def search_subset(self, item, gl: GraphLaplacian, tau: float, subset):
         """Extension: filtered search -> list[(index, score)]: the first min(topk, |subset|) items OF THE SUBSET by (score
@@ -537,34 +594,30 @@ class ArrowSpace:
         `ItemSubset` of this space (prepared once, reused over queries) or anything `subset()` accepts (a temporary one is
         made).  Costs one ordinary `search` (lambda_q comes from it; a query whose lambda_q is 0 panics as there, whatever
         the subset) plus a gather of the subset's rows and an exact selection on the device."""
-        if not isinstance(gl, GraphLaplacian):
-            raise TypeError("argument 'gl': expected GraphLaplacian")
+        _need_gl(gl)
         q = self._query(item)
-        sub = subset if isinstance(subset, ItemSubset) else self.subset(subset)
+        sub = self._as_subset(subset)
         n = max(min(int(gl.graph_params["topk"]), sub.size), 1)
         idx = np.empty(n, dtype=np.int64)
         sc = np.empty(n, dtype=np.float64)
         ln, lq = C.c_int64(0), C.c_double(0.0)
         st = _L.as_search_subset(self._h, gl._h, q.ctypes.data, q.shape[0], float(tau), sub._h, idx.ctypes.data, sc.ctypes.data,
                                  C.byref(ln), C.byref(lq))
-        if st:
-            _raise(st)
+        _check(st)
         return list(zip(idx[:ln.value].tolist(), sc[:ln.value].tolist()))
 
     def score_items(self, item, gl: GraphLaplacian, tau: float, ids) -> np.ndarray:
         """Extension: re-ranking -> ndarray[float64]: entry i is the score `search` would give item ids[i] (the caller's
         order, duplicates kept; integer ids or a boolean mask as for `subset`).  Costs one ordinary `search` (lambda_q) plus
         a gather of the listed rows."""
-        if not isinstance(gl, GraphLaplacian):
-            raise TypeError("argument 'gl': expected GraphLaplacian")
+        _need_gl(gl)
         q = self._query(item)
         ids = _item_ids(ids, self.nitems, "ids")
         out = np.empty(ids.shape[0], dtype=np.float64)
         lq = C.c_double(0.0)
         st = _L.as_score_items(self._h, gl._h, q.ctypes.data, q.shape[0], float(tau), ids.ctypes.data_as(C.c_void_p), ids.shape[0],
                                out.ctypes.data_as(C.c_void_p), C.byref(lq))
-        if st:
-            _raise(st)
+        _check(st)
         return out
 
     def search_batch_subset(self, items, gl: GraphLaplacian, tau: float, subset):
@@ -574,67 +627,46 @@ class ArrowSpace:
         Costs one `search_batch` over the B queries (lambda_q comes from it; any query whose lambda_q is 0 panics as there,
         whatever the subset), then the subset's rows are gathered once per 64 queries for an fp64 matrix product on the
         device and every query's list is selected there."""
-        if not isinstance(gl, GraphLaplacian):
-            raise TypeError("argument 'gl': expected GraphLaplacian")
-        Q = np.ascontiguousarray(items, dtype=np.float64)
-        if Q.ndim != 2:
-            raise TypeError("items must be a 2-D float64 array")
-        sub = subset if isinstance(subset, ItemSubset) else self.subset(subset)
+        _need_gl(gl)
+        Q = _queries_2d(items)
+        sub = self._as_subset(subset)
         b = Q.shape[0]
-        kk = max(min(int(gl.graph_params["topk"]), self.nitems, sub.size), 0)
-        idx = np.empty((max(b, 1), max(kk, 1)), dtype=np.int64)
-        sc = np.empty((max(b, 1), max(kk, 1)), dtype=np.float64)
-        ln = np.zeros(max(b, 1), dtype=np.int64)
-        stt = np.zeros(max(b, 1), dtype=np.int32)
+        kk = self._hits_bound(gl, sub)
+        (idx, sc, ln), stt = _hit_buffers(b, kk), _statuses(b)
         st = _L.as_search_subset_batch(self._h, gl._h, Q.ctypes.data_as(C.c_void_p), b, Q.shape[1], float(tau), sub._h,
                                        idx.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p), ln.ctypes.data_as(C.c_void_p),
                                        None, stt.ctypes.data_as(C.c_void_p))
-        if st:
-            _raise(st)
-        if (stt[:b] == _lib.AS_EZEROLAMBDA).any():
-            raise PanicException("The lambdas are zero, check the magnitude of items and eps.")
-        if kk == 0:
-            return [[] for _ in range(b)]
-        # (the C ABI's lists are at stride kk)
-        idx, sc = idx.reshape(-1)[:b * kk].reshape(b, kk), sc.reshape(-1)[:b * kk].reshape(b, kk)
-        return [list(zip(ii[:l], ss[:l])) for ii, ss, l in zip(idx.tolist(), sc.tolist(), ln[:b].tolist())]
+        _check(st, stt, b)
+        return _hit_lists(idx, sc, ln, b, kk)
 
     def score_items_batch(self, items, gl: GraphLaplacian, tau: float, ids) -> np.ndarray:
         """Extension: batched re-ranking -> ndarray[float64] of shape (B, len(ids)): entry [i, j] is what
         `score_items(items[i], gl, tau, ids)[j]` returns (the caller's order, duplicates kept; within 1e-12 relative: the
         batched kernel sums in another order).  Costs one `search_batch` over the B queries (lambda_q; a query whose lambda_q
         is 0 panics as there) plus one gather of the listed rows per 64 queries."""
-        if not isinstance(gl, GraphLaplacian):
-            raise TypeError("argument 'gl': expected GraphLaplacian")
-        Q = np.ascontiguousarray(items, dtype=np.float64)
-        if Q.ndim != 2:
-            raise TypeError("items must be a 2-D float64 array")
+        _need_gl(gl)
+        Q = _queries_2d(items)
         ids = _item_ids(ids, self.nitems, "ids")
         b, m = Q.shape[0], ids.shape[0]
         out = np.empty((b, m), dtype=np.float64)
-        stt = np.zeros(max(b, 1), dtype=np.int32)
+        stt = _statuses(b)
         st = _L.as_score_items_batch(self._h, gl._h, Q.ctypes.data_as(C.c_void_p), b, Q.shape[1], float(tau),
                                      ids.ctypes.data_as(C.c_void_p), m, out.ctypes.data_as(C.c_void_p), None,
                                      stt.ctypes.data_as(C.c_void_p))
-        if st:
-            _raise(st)
-        if (stt[:b] == _lib.AS_EZEROLAMBDA).any():
-            raise PanicException("The lambdas are zero, check the magnitude of items and eps.")
+        _check(st, stt, b)
         return out
 
     def _range_single(self, item, gl, tau, min_score, subset, count_only):
-        if not isinstance(gl, GraphLaplacian):
-            raise TypeError("argument 'gl': expected GraphLaplacian")
+        _need_gl(gl)
         q = self._query(item)
         if np.ndim(min_score) != 0:
             raise ValueError("argument 'min_score': expected one float")
         thr = float(_min_scores(min_score, 1)[0])
-        sub = subset if subset is None or isinstance(subset, ItemSubset) else self.subset(subset)
+        sub = self._as_subset(subset, optional=True)
         h, lq = C.c_void_p(), C.c_double(0.0)
-        st = _L.as_search_range(self._h, gl._h, q.ctypes.data, q.shape[0], float(tau), thr, None if sub is None else sub._h,
+        st = _L.as_search_range(self._h, gl._h, q.ctypes.data, q.shape[0], float(tau), thr, _handle(sub),
                                 1 if count_only else 0, C.byref(h), C.byref(lq))
-        if st:
-            _raise(st)
+        _check(st)
         try:
             n = int(_L.as_range_total(h))
             if count_only:
@@ -642,43 +674,35 @@ class ArrowSpace:
             idx = np.empty(max(n, 1), dtype=np.int64)
             sc = np.empty(max(n, 1), dtype=np.float64)
             st = _L.as_range_copy(h, idx.ctypes.data, sc.ctypes.data)
-            if st:
-                _raise(st)
+            _check(st)
             return list(zip(idx[:n].tolist(), sc[:n].tolist()))
         finally:
             _L.as_range_free(h)
 
     def _range_batch(self, items, gl, tau, min_score, subset, count_only):
-        if not isinstance(gl, GraphLaplacian):
-            raise TypeError("argument 'gl': expected GraphLaplacian")
-        Q = np.ascontiguousarray(items, dtype=np.float64)
-        if Q.ndim != 2:
-            raise TypeError("items must be a 2-D float64 array")
+        _need_gl(gl)
+        Q = _queries_2d(items)
         b = Q.shape[0]
         thr = _min_scores(min_score, b)
-        sub = subset if subset is None or isinstance(subset, ItemSubset) else self.subset(subset)
+        sub = self._as_subset(subset, optional=True)
         h = C.c_void_p()
-        stt = np.zeros(max(b, 1), dtype=np.int32)
+        stt = _statuses(b)
         st = _L.as_search_range_batch(self._h, gl._h, Q.ctypes.data_as(C.c_void_p), b, Q.shape[1], float(tau),
-                                      thr.ctypes.data_as(C.c_void_p), None if sub is None else sub._h, 1 if count_only else 0,
+                                      thr.ctypes.data_as(C.c_void_p), _handle(sub), 1 if count_only else 0,
                                       C.byref(h), None, stt.ctypes.data_as(C.c_void_p))
-        if st:
-            _raise(st)
+        _check(st)
         try:
-            if (stt[:b] == _lib.AS_EZEROLAMBDA).any():
-                raise PanicException("The lambdas are zero, check the magnitude of items and eps.")
+            _panic_on_zero_lambda(stt, b)   # (inside the try: the answer's handle is freed)
             offs = np.zeros(b + 1, dtype=np.int64)
             st = _L.as_range_offsets(h, offs.ctypes.data)
-            if st:
-                _raise(st)
+            _check(st)
             if count_only:
                 return np.diff(offs)
             n = int(offs[b])
             idx = np.empty(max(n, 1), dtype=np.int64)
             sc = np.empty(max(n, 1), dtype=np.float64)
             st = _L.as_range_copy(h, idx.ctypes.data, sc.ctypes.data)
-            if st:
-                _raise(st)
+            _check(st)
             idx, sc, o = idx.tolist(), sc.tolist(), offs.tolist()
             return [list(zip(idx[o[i]:o[i + 1]], sc[o[i]:o[i + 1]])) for i in range(b)]
         finally:
@@ -719,11 +743,7 @@ class ArrowSpace:
 
     def range_counters(self) -> dict:
         """Extension: range calls on this space since it was made, the work they launched and what they returned."""
-        out = (C.c_int64 * 6)()
-        st = _L.as_range_counters(self._h, out, 6)
-        if st:
-            _raise(st)
-        return dict(zip(("calls", "compactions", "scores_examined", "survivors", "relaunches", "lambda_steps"), list(out)))
+        return _counters(_L.as_range_counters, self._h, ("calls", "compactions", "scores_examined", "survivors", "relaunches", "lambda_steps"))
 
     def search_fused(self, items, gl: GraphLaplacian, tau: float, weights=None, mode="sum", subset=None, on_zero_lambda="raise"):
         """Extension: fused multi-query search, ONE answer to J query vectors [J, D] -> list[(index, score)]: the first
@@ -738,16 +758,13 @@ class ArrowSpace:
         that folds the scores into an accumulator on the device, and one exact selection there: topk entries cross to the
         host, the J x M scores never do."""
         Q, w, m, skip = _fused_args(items, gl, weights, mode, on_zero_lambda)
-        sub = subset if subset is None or isinstance(subset, ItemSubset) else self.subset(subset)
-        kk = max(min(int(gl.graph_params["topk"]), self.nitems, self.nitems if sub is None else sub.size), 1)
-        idx = np.empty(kk, dtype=np.int64)
-        sc = np.empty(kk, dtype=np.float64)
+        sub = self._as_subset(subset, optional=True)
+        idx, sc, _ = _hit_buffers(1, self._hits_bound(gl, sub))
         ln = C.c_int64(0)
         st = _L.as_search_fused(self._h, gl._h, Q.ctypes.data_as(C.c_void_p), Q.shape[0], Q.shape[1], float(tau),
-                                None if w is None else w.ctypes.data_as(C.c_void_p), m, skip, None if sub is None else sub._h,
+                                None if w is None else w.ctypes.data_as(C.c_void_p), m, skip, _handle(sub),
                                 idx.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p), C.byref(ln), None, None)
-        if st:
-            _raise(st)
+        _check(st)
         return list(zip(idx[:ln.value].tolist(), sc[:ln.value].tolist()))
 
     def score_fused(self, items, gl: GraphLaplacian, tau: float, ids, weights=None, mode="sum", on_zero_lambda="raise") -> np.ndarray:
@@ -761,18 +778,13 @@ class ArrowSpace:
         st = _L.as_score_fused(self._h, gl._h, Q.ctypes.data_as(C.c_void_p), Q.shape[0], Q.shape[1], float(tau),
                                None if w is None else w.ctypes.data_as(C.c_void_p), m, skip, ids.ctypes.data_as(C.c_void_p), ids.shape[0],
                                out.ctypes.data_as(C.c_void_p), None, None)
-        if st:
-            _raise(st)
+        _check(st)
         return out
 
     def fused_counters(self) -> list:
         """Extension: [0] fused calls on this space that passed their checks, [1] accumulate launches, [2] scores folded
         (served vectors x items), [3] lambda_q steps run."""
-        out = (C.c_int64 * 4)()
-        st = _L.as_fused_counters(self._h, out, 4)
-        if st:
-            _raise(st)
-        return list(out)
+        return list(_counters(_L.as_fused_counters, self._h, ("calls", "launches", "folded", "lambda_steps")).values())
 
     def groups(self, labels) -> ItemGroups:
         """Extension: an `ItemGroups` of this space from one integer label per item (a 1-D sequence or array of length nitems,
@@ -781,8 +793,7 @@ class ArrowSpace:
         lab = _group_labels(labels, self.nitems)
         h = C.c_void_p()
         st = _L.as_groups_create(self._h, lab.ctypes.data_as(C.c_void_p), lab.shape[0], C.byref(h))
-        if st:
-            _raise(st)
+        _check(st)
         return ItemGroups._wrap(h, self, lab.copy())
 
     def _grouped_handles(self, groups, subset):
@@ -790,7 +801,7 @@ class ArrowSpace:
         grp = groups if isinstance(groups, ItemGroups) else self.groups(groups)
         if grp._space is not self:
             raise ValueError("argument 'groups': the groups were made for another space")
-        sub = subset if subset is None or isinstance(subset, ItemSubset) else self.subset(subset)
+        sub = self._as_subset(subset, optional=True)
         if sub is not None and sub._space is not self:
             raise ValueError("argument 'subset': the subset was made for another space")
         return grp, sub
@@ -818,10 +829,9 @@ class ArrowSpace:
         label, count = np.zeros(ng, dtype=np.int64), np.zeros(ng, dtype=np.int64)
         idx, sc = np.zeros(ng * pg, dtype=np.int64), np.zeros(ng * pg, dtype=np.float64)
         n, lq = C.c_int64(0), C.c_double(0.0)
-        st = _L.as_search_grouped(self._h, gl._h, q.ctypes.data, q.shape[0], tau, grp._h, ng, pg, None if sub is None else sub._h,
+        st = _L.as_search_grouped(self._h, gl._h, q.ctypes.data, q.shape[0], tau, grp._h, ng, pg, _handle(sub),
                                   label.ctypes.data, count.ctypes.data, idx.ctypes.data, sc.ctypes.data, C.byref(n), C.byref(lq))
-        if st:
-            _raise(st)
+        _check(st)
         return self._grouped_lists(ng, pg, n.value, label, count, idx, sc)
 
     def search_batch_grouped(self, items, gl: GraphLaplacian, tau: float, groups, n_groups: int, per_group: int = 1, subset=None):
@@ -832,9 +842,7 @@ class ArrowSpace:
         lambda_q is 0 panics as there), then per chunk of queries the batched filtered forms' gather and fp64 matrix product
         and the pick passes, the selection and the gather of `search_grouped` with one row per query."""
         tau, ng, pg = _grouped_args(gl, tau, n_groups, per_group)
-        Q = np.ascontiguousarray(items, dtype=np.float64)
-        if Q.ndim != 2:
-            raise TypeError("items must be a 2-D float64 array")
+        Q = _queries_2d(items)
         b = Q.shape[0]
         if b == 0:
             return []
@@ -842,22 +850,16 @@ class ArrowSpace:
         label, count = np.zeros((b, ng), dtype=np.int64), np.zeros((b, ng), dtype=np.int64)
         idx, sc = np.zeros((b, ng * pg), dtype=np.int64), np.zeros((b, ng * pg), dtype=np.float64)
         n, stt = np.zeros(b, dtype=np.int64), np.zeros(b, dtype=np.int32)
-        st = _L.as_search_grouped_batch(self._h, gl._h, Q.ctypes.data, b, Q.shape[1], tau, grp._h, ng, pg, None if sub is None else sub._h,
+        st = _L.as_search_grouped_batch(self._h, gl._h, Q.ctypes.data, b, Q.shape[1], tau, grp._h, ng, pg, _handle(sub),
                                         label.ctypes.data, count.ctypes.data, idx.ctypes.data, sc.ctypes.data, n.ctypes.data, None,
                                         stt.ctypes.data)
-        if st:
-            _raise(st)
-        if (stt == _lib.AS_EZEROLAMBDA).any():
-            raise PanicException("The lambdas are zero, check the magnitude of items and eps.")
+        _check(st, stt, b)
         return [self._grouped_lists(ng, pg, int(n[i]), label[i], count[i], idx[i], sc[i]) for i in range(b)]
 
     def grouped_counters(self) -> dict:
         """Extension: grouped calls on this space since it was made, the work they launched and what they returned."""
-        out = (C.c_int64 * 7)()
-        st = _L.as_grouped_counters(self._h, out, 7)
-        if st:
-            _raise(st)
-        return dict(zip(("calls", "pick_launches", "scores_examined", "max_atomics", "groups", "members", "lambda_steps"), list(out)))
+        return _counters(_L.as_grouped_counters, self._h,
+                         ("calls", "pick_launches", "scores_examined", "max_atomics", "groups", "members", "lambda_steps"))
 
     @staticmethod
     def _diverse_params(n, diversity) -> tuple[int, float]:
@@ -879,21 +881,18 @@ class ArrowSpace:
         first pick is always the pool's best hit; scores are the pool's, bit for bit.  n < 1 and a diversity outside [0, 1]
         raise ValueError.  Costs one ordinary `search` / `search_subset` (a query whose lambda_q is 0 panics as there) plus
         one upload of the pool, one launch that runs the whole greedy on the device and one download."""
-        if not isinstance(gl, GraphLaplacian):
-            raise TypeError("argument 'gl': expected GraphLaplacian")
+        _need_gl(gl)
         q = self._query(item)
         n, delta = self._diverse_params(n, diversity)
-        sub = subset if subset is None or isinstance(subset, ItemSubset) else self.subset(subset)
-        kk = min(int(gl.graph_params["topk"]), self.nitems, self.nitems if sub is None else sub.size)
-        nn = max(min(n, kk), 1)
+        sub = self._as_subset(subset, optional=True)
+        nn = max(min(n, self._hits_bound(gl, sub)), 1)
         idx = np.empty(nn, dtype=np.int64)
         sc = np.empty(nn, dtype=np.float64)
         mg = np.empty(nn, dtype=np.float64)
         ln, lq = C.c_int64(0), C.c_double(0.0)
-        st = _L.as_search_diverse(self._h, gl._h, q.ctypes.data, q.shape[0], float(tau), n, delta, None if sub is None else sub._h,
+        st = _L.as_search_diverse(self._h, gl._h, q.ctypes.data, q.shape[0], float(tau), n, delta, _handle(sub),
                                   idx.ctypes.data, sc.ctypes.data, mg.ctypes.data, C.byref(ln), C.byref(lq))
-        if st:
-            _raise(st)
+        _check(st)
         k = ln.value
         if with_margins:
             return list(zip(idx[:k].tolist(), sc[:k].tolist(), mg[:k].tolist()))
@@ -904,26 +903,18 @@ class ArrowSpace:
         over the pool `search_batch` (with a subset: `search_batch_subset`) gives query i.  A query whose lambda_q is 0 gets
         an empty list, the others are served.  Costs one `search_batch` / `search_batch_subset` over the B queries, then per
         4096 queries one upload of the pools, one launch (a block per query runs its whole greedy) and one download."""
-        if not isinstance(gl, GraphLaplacian):
-            raise TypeError("argument 'gl': expected GraphLaplacian")
-        Q = np.ascontiguousarray(items, dtype=np.float64)
-        if Q.ndim != 2:
-            raise TypeError("items must be a 2-D float64 array")
+        _need_gl(gl)
+        Q = _queries_2d(items)
         n, delta = self._diverse_params(n, diversity)
-        sub = subset if subset is None or isinstance(subset, ItemSubset) else self.subset(subset)
+        sub = self._as_subset(subset, optional=True)
         b = Q.shape[0]
-        kk = min(int(gl.graph_params["topk"]), self.nitems, self.nitems if sub is None else sub.size)
-        nn = max(min(n, kk), 0)
-        idx = np.empty((max(b, 1), max(nn, 1)), dtype=np.int64)
-        sc = np.empty((max(b, 1), max(nn, 1)), dtype=np.float64)
-        mg = np.empty((max(b, 1), max(nn, 1)), dtype=np.float64)
-        ln = np.zeros(max(b, 1), dtype=np.int64)
-        stt = np.zeros(max(b, 1), dtype=np.int32)
+        nn = min(n, self._hits_bound(gl, sub))
+        (idx, sc, ln), stt = _hit_buffers(b, nn), _statuses(b)
+        mg = np.empty_like(sc)
         st = _L.as_search_diverse_batch(self._h, gl._h, Q.ctypes.data_as(C.c_void_p), b, Q.shape[1], float(tau), n, delta,
-                                        None if sub is None else sub._h, idx.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p),
+                                        _handle(sub), idx.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p),
                                         mg.ctypes.data_as(C.c_void_p), ln.ctypes.data_as(C.c_void_p), None, stt.ctypes.data_as(C.c_void_p))
-        if st:
-            _raise(st)
+        _check(st)
         if nn == 0:
             return [[] for _ in range(b)]
         # (the C ABI's lists are at stride nn)
@@ -934,18 +925,11 @@ class ArrowSpace:
 
     def diverse_counters(self) -> dict:
         """Extension: diversified calls on this space since it was made and the work they launched."""
-        out = (C.c_int64 * 5)()
-        st = _L.as_diverse_counters(self._h, out, 5)
-        if st:
-            _raise(st)
-        return dict(zip(("calls", "launches", "picks", "dots", "pool_steps"), list(out)))
+        return _counters(_L.as_diverse_counters, self._h, ("calls", "launches", "picks", "dots", "pool_steps"))
 
     def _lists_args(self, items, gl, lists):
-        if not isinstance(gl, GraphLaplacian):
-            raise TypeError("argument 'gl': expected GraphLaplacian")
-        Q = np.ascontiguousarray(items, dtype=np.float64)
-        if Q.ndim != 2:
-            raise TypeError("items must be a 2-D float64 array")
+        _need_gl(gl)
+        Q = _queries_2d(items)
         ids, offsets = _id_lists(lists, self.nitems)
         if offsets.shape[0] - 1 != Q.shape[0]:
             raise ValueError(f"argument 'lists': {offsets.shape[0] - 1} id lists for {Q.shape[0]} queries")
@@ -962,20 +946,14 @@ class ArrowSpace:
         and every list is selected there."""
         Q, ids, offsets = self._lists_args(items, gl, lists)
         b = Q.shape[0]
-        kk = max(min(int(gl.graph_params["topk"]), self.nitems), 1)
-        idx = np.empty((max(b, 1), kk), dtype=np.int64)
-        sc = np.empty((max(b, 1), kk), dtype=np.float64)
-        ln = np.zeros(max(b, 1), dtype=np.int64)
-        stt = np.zeros(max(b, 1), dtype=np.int32)
+        kk = self._hits_bound(gl)
+        (idx, sc, ln), stt = _hit_buffers(b, kk), _statuses(b)
         st = _L.as_search_lists_batch(self._h, gl._h, Q.ctypes.data_as(C.c_void_p), b, Q.shape[1], float(tau),
                                       ids.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p),
                                       idx.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p), ln.ctypes.data_as(C.c_void_p),
                                       None, stt.ctypes.data_as(C.c_void_p))
-        if st:
-            _raise(st)
-        if (stt[:b] == _lib.AS_EZEROLAMBDA).any():
-            raise PanicException("The lambdas are zero, check the magnitude of items and eps.")
-        return [list(zip(ii[:l], ss[:l])) for ii, ss, l in zip(idx[:b].tolist(), sc[:b].tolist(), ln[:b].tolist())]
+        _check(st, stt, b)
+        return _hit_lists(idx, sc, ln, b, kk)
 
     def score_lists_batch(self, items, gl: GraphLaplacian, tau: float, lists):
         """Extension: scores of per-query candidate lists -> a list of B float64 arrays (a 2-D integer array (B, C) as `lists`
@@ -987,14 +965,11 @@ class ArrowSpace:
         Q, ids, offsets = self._lists_args(items, gl, lists)
         b = Q.shape[0]
         out = np.empty(ids.shape[0], dtype=np.float64)
-        stt = np.zeros(max(b, 1), dtype=np.int32)
+        stt = _statuses(b)
         st = _L.as_score_lists_batch(self._h, gl._h, Q.ctypes.data_as(C.c_void_p), b, Q.shape[1], float(tau),
                                      ids.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p),
                                      out.ctypes.data_as(C.c_void_p), None, stt.ctypes.data_as(C.c_void_p))
-        if st:
-            _raise(st)
-        if (stt[:b] == _lib.AS_EZEROLAMBDA).any():
-            raise PanicException("The lambdas are zero, check the magnitude of items and eps.")
+        _check(st, stt, b)
         if isinstance(lists, np.ndarray) and lists.ndim == 2 and lists.dtype != np.bool_:
             return out.reshape(lists.shape)
         return [out[offsets[i]:offsets[i + 1]] for i in range(b)]
@@ -1003,11 +978,7 @@ class ArrowSpace:
         """Extension: `search_batch_lists` / `score_lists_batch` calls on this space that passed their checks, the score-kernel
         launches they made, the (query, item) pairs those scored, the lambda_q steps run (`search_batch` calls), and the host
         nanoseconds spent on id checks, deduplication and work tables."""
-        out = np.zeros(5, dtype=np.int64)
-        st = _L.as_lists_counters(self._h, out.ctypes.data_as(C.c_void_p), 5)
-        if st:
-            _raise(st)
-        return dict(zip(("calls", "score_launches", "pairs", "lambda_steps", "host_ns"), (int(v) for v in out)))
+        return _counters(_L.as_lists_counters, self._h, ("calls", "score_launches", "pairs", "lambda_steps", "host_ns"))
 
     @staticmethod
     def _taus(taus) -> np.ndarray:
@@ -1027,21 +998,13 @@ class ArrowSpace:
         Q, ids, offsets = self._lists_args(items, gl, lists)
         t = self._taus(taus)
         b, nt = Q.shape[0], t.shape[0]
-        kk = max(min(int(gl.graph_params["topk"]), self.nitems), 1)
-        idx = np.empty(max(b * nt * kk, 1), dtype=np.int64)
-        sc = np.empty(max(b * nt * kk, 1), dtype=np.float64)
-        ln = np.zeros(max(b * nt, 1), dtype=np.int64)
-        stt = np.zeros(max(b, 1), dtype=np.int32)
+        kk = self._hits_bound(gl)
+        (idx, sc, ln), stt = _hit_buffers(b * nt, kk), _statuses(b)
         st = _L.as_search_lists_batch_taus(self._h, gl._h, Q.ctypes.data_as(C.c_void_p), b, Q.shape[1], t.ctypes.data, nt,
                                            ids.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p), idx.ctypes.data,
                                            sc.ctypes.data, ln.ctypes.data, None, stt.ctypes.data)
-        if st:
-            _raise(st)
-        if (stt[:b] == _lib.AS_EZEROLAMBDA).any():
-            raise PanicException("The lambdas are zero, check the magnitude of items and eps.")
-        idx, sc, ln = idx[:b * nt * kk].reshape(b, nt, kk), sc[:b * nt * kk].reshape(b, nt, kk), ln[:b * nt].reshape(b, nt)
-        return [[list(zip(ii[:l], ss[:l])) for ii, ss, l in zip(bi, bs, bl)]
-                for bi, bs, bl in zip(idx.tolist(), sc.tolist(), ln.tolist())]
+        _check(st, stt, b)
+        return _hit_lists(idx, sc, ln, b * nt, kk, per=nt) if nt else [[] for _ in range(b)]
 
     def score_lists_batch_taus(self, items, gl: GraphLaplacian, taus, lists):
         """Extension: scores of per-query candidate lists under several taus -> a list of B float64 arrays of shape
@@ -1054,14 +1017,11 @@ class ArrowSpace:
         t = self._taus(taus)
         b, nt = Q.shape[0], t.shape[0]
         out = np.empty(nt * ids.shape[0], dtype=np.float64)
-        stt = np.zeros(max(b, 1), dtype=np.int32)
+        stt = _statuses(b)
         st = _L.as_score_lists_batch_taus(self._h, gl._h, Q.ctypes.data_as(C.c_void_p), b, Q.shape[1], t.ctypes.data, nt,
                                           ids.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p),
                                           out.ctypes.data_as(C.c_void_p), None, stt.ctypes.data)
-        if st:
-            _raise(st)
-        if (stt[:b] == _lib.AS_EZEROLAMBDA).any():
-            raise PanicException("The lambdas are zero, check the magnitude of items and eps.")
+        _check(st, stt, b)
         if isinstance(lists, np.ndarray) and lists.ndim == 2 and lists.dtype != np.bool_:
             return out.reshape(lists.shape[0], nt, lists.shape[1])
         return [out[nt * offsets[i]:nt * offsets[i + 1]].reshape(nt, offsets[i + 1] - offsets[i]) for i in range(b)]
@@ -1070,11 +1030,7 @@ class ArrowSpace:
         """Extension: `search_batch_lists_taus` / `score_lists_batch_taus` calls on this space that passed their checks, the
         score-kernel launches they made, the (query, item) pairs those gathered (once per launch, not per tau), the (query,
         item, tau) scores they wrote, and the lambda_q steps run (`search_batch` calls)."""
-        out = np.zeros(5, dtype=np.int64)
-        st = _L.as_lists_sweep_counters(self._h, out.ctypes.data_as(C.c_void_p), 5)
-        if st:
-            _raise(st)
-        return dict(zip(("calls", "score_launches", "pairs", "scores", "lambda_steps"), (int(v) for v in out)))
+        return _counters(_L.as_lists_sweep_counters, self._h, ("calls", "score_launches", "pairs", "scores", "lambda_steps"))
 
     def search_subset_taus(self, item, gl: GraphLaplacian, taus, subset):
         """Extension: filtered search under several taus -> one hit list per entry of `taus`, in order; list j is what
@@ -1082,30 +1038,24 @@ class ArrowSpace:
         does not depend on tau; a query whose lambda_q is 0 panics as there) and ONE gather of the subset's rows per up to 8
         distinct taus: every cosine is formed once and blended with each tau.  Every finite tau is served; a NaN or infinite
         one raises ValueError before anything runs; equal taus are computed once; `taus = []` returns `[]`."""
-        if not isinstance(gl, GraphLaplacian):
-            raise TypeError("argument 'gl': expected GraphLaplacian")
+        _need_gl(gl)
         q = self._query(item)
         t = self._taus(taus)
-        sub = subset if isinstance(subset, ItemSubset) else self.subset(subset)
+        sub = self._as_subset(subset)
         nt = t.shape[0]
-        kk = max(min(int(gl.graph_params["topk"]), self.nitems, sub.size), 0)
-        idx = np.empty(max(nt * kk, 1), dtype=np.int64)
-        sc = np.empty(max(nt * kk, 1), dtype=np.float64)
-        ln = np.zeros(max(nt, 1), dtype=np.int64)
+        kk = self._hits_bound(gl, sub)
+        idx, sc, ln = _hit_buffers(nt, kk)
         lq = C.c_double(0.0)
         st = _L.as_search_subset_taus(self._h, gl._h, q.ctypes.data, q.shape[0], t.ctypes.data, nt, sub._h, idx.ctypes.data, sc.ctypes.data,
                                       ln.ctypes.data, C.byref(lq))
-        if st:
-            _raise(st)
-        idx, sc = idx[:nt * kk].reshape(nt, kk), sc[:nt * kk].reshape(nt, kk)   # (the C ABI's lists are at stride kk)
-        return [list(zip(ii[:l], ss[:l])) for ii, ss, l in zip(idx.tolist(), sc.tolist(), ln[:nt].tolist())]
+        _check(st)
+        return _hit_lists(idx, sc, ln, nt, kk)
 
     def score_items_taus(self, item, gl: GraphLaplacian, taus, ids) -> np.ndarray:
         """Extension: re-ranking under several taus -> ndarray[float64] of shape (len(taus), len(ids)): row j is what
         `score_items(item, gl, taus[j], ids)` returns, with the same bits (and the bits `search_subset_taus` gives the same
         tau and item).  Costs one ordinary `search` (lambda_q) and one gather of the listed rows per up to 8 distinct taus."""
-        if not isinstance(gl, GraphLaplacian):
-            raise TypeError("argument 'gl': expected GraphLaplacian")
+        _need_gl(gl)
         q = self._query(item)
         t = self._taus(taus)
         ids = _item_ids(ids, self.nitems, "ids")
@@ -1114,8 +1064,7 @@ class ArrowSpace:
         lq = C.c_double(0.0)
         st = _L.as_score_items_taus(self._h, gl._h, q.ctypes.data, q.shape[0], t.ctypes.data, nt, ids.ctypes.data_as(C.c_void_p), m,
                                     out.ctypes.data_as(C.c_void_p), C.byref(lq))
-        if st:
-            _raise(st)
+        _check(st)
         return out
 
     def search_batch_subset_taus(self, items, gl: GraphLaplacian, taus, subset):
@@ -1125,61 +1074,40 @@ class ArrowSpace:
         one gather of the subset's rows per 64 queries and up to 8 distinct taus (fewer where the score planes would exceed
         the chunk budget).  Finite taus only (ValueError otherwise); equal taus are computed once; `taus = []` returns B empty
         lists."""
-        if not isinstance(gl, GraphLaplacian):
-            raise TypeError("argument 'gl': expected GraphLaplacian")
-        Q = np.ascontiguousarray(items, dtype=np.float64)
-        if Q.ndim != 2:
-            raise TypeError("items must be a 2-D float64 array")
+        _need_gl(gl)
+        Q = _queries_2d(items)
         t = self._taus(taus)
-        sub = subset if isinstance(subset, ItemSubset) else self.subset(subset)
+        sub = self._as_subset(subset)
         b, nt = Q.shape[0], t.shape[0]
-        kk = max(min(int(gl.graph_params["topk"]), self.nitems, sub.size), 0)
-        idx = np.empty(max(b * nt * kk, 1), dtype=np.int64)
-        sc = np.empty(max(b * nt * kk, 1), dtype=np.float64)
-        ln = np.zeros(max(b * nt, 1), dtype=np.int64)
-        stt = np.zeros(max(b, 1), dtype=np.int32)
+        kk = self._hits_bound(gl, sub)
+        (idx, sc, ln), stt = _hit_buffers(b * nt, kk), _statuses(b)
         st = _L.as_search_subset_batch_taus(self._h, gl._h, Q.ctypes.data_as(C.c_void_p), b, Q.shape[1], t.ctypes.data, nt, sub._h,
                                             idx.ctypes.data, sc.ctypes.data, ln.ctypes.data, None, stt.ctypes.data)
-        if st:
-            _raise(st)
-        if (stt[:b] == _lib.AS_EZEROLAMBDA).any():
-            raise PanicException("The lambdas are zero, check the magnitude of items and eps.")
-        idx, sc, ln = idx[:b * nt * kk].reshape(b, nt, kk), sc[:b * nt * kk].reshape(b, nt, kk), ln[:b * nt].reshape(b, nt)
-        return [[list(zip(ii[:l], ss[:l])) for ii, ss, l in zip(bi, bs, bl)]
-                for bi, bs, bl in zip(idx.tolist(), sc.tolist(), ln.tolist())]
+        _check(st, stt, b)
+        return _hit_lists(idx, sc, ln, b * nt, kk, per=nt) if nt else [[] for _ in range(b)]
 
     def score_items_batch_taus(self, items, gl: GraphLaplacian, taus, ids) -> np.ndarray:
         """Extension: batched re-ranking under several taus -> ndarray[float64] of shape (B, len(taus), len(ids)): entry
         [i, j] is row i of `score_items_batch(items, gl, taus[j], ids)`, with the same bits.  Costs one `search_batch` over the
         B queries (lambda_q; a query whose lambda_q is 0 panics as there) and one gather of the listed rows per 64 queries and
         up to 8 distinct taus."""
-        if not isinstance(gl, GraphLaplacian):
-            raise TypeError("argument 'gl': expected GraphLaplacian")
-        Q = np.ascontiguousarray(items, dtype=np.float64)
-        if Q.ndim != 2:
-            raise TypeError("items must be a 2-D float64 array")
+        _need_gl(gl)
+        Q = _queries_2d(items)
         t = self._taus(taus)
         ids = _item_ids(ids, self.nitems, "ids")
         b, nt, m = Q.shape[0], t.shape[0], ids.shape[0]
         out = np.empty((b, nt, m), dtype=np.float64)
-        stt = np.zeros(max(b, 1), dtype=np.int32)
+        stt = _statuses(b)
         st = _L.as_score_items_batch_taus(self._h, gl._h, Q.ctypes.data_as(C.c_void_p), b, Q.shape[1], t.ctypes.data, nt,
                                           ids.ctypes.data_as(C.c_void_p), m, out.ctypes.data_as(C.c_void_p), None, stt.ctypes.data)
-        if st:
-            _raise(st)
-        if (stt[:b] == _lib.AS_EZEROLAMBDA).any():
-            raise PanicException("The lambdas are zero, check the magnitude of items and eps.")
+        _check(st, stt, b)
         return out
 
     def subset_sweep_counters(self) -> dict:
         """Extension: tau sweeps over a subset on this space (all four `*_taus` forms of the filtered search), the score-kernel
         launches they made, the tau planes those launches wrote, and the lambda_q steps run (single searches plus
         `search_batch` calls)."""
-        out = np.zeros(4, dtype=np.int64)
-        st = _L.as_subset_sweep_counters(self._h, out.ctypes.data_as(C.c_void_p), 4)
-        if st:
-            _raise(st)
-        return dict(zip(("calls", "score_launches", "tau_planes", "lambda_steps"), (int(v) for v in out)))
+        return _counters(_L.as_subset_sweep_counters, self._h, ("calls", "score_launches", "tau_planes", "lambda_steps"))
 
     def sweep_counters(self) -> dict:
         """Extension: `search_taus` calls on this space, the shared passes that served them, and the taus those passes left

@@ -771,6 +771,16 @@ static as_status graph_matches(const as_space* sp, const as_graph* gr, const cha
     return AS_OK;
 }
 
+// what the getters of a family's counters share (`counts`: of the space, when there is one)
+static as_status counters_out(const char* who, const as_space* sp, int64_t* out, int32_t n, const std::atomic<int64_t>* counts, int len) {
+    if (!sp || !out) {
+        set_err("%s: null argument", who);
+        return AS_EINVAL;
+    }
+    for (int i = 0; i < n && i < len; ++i) out[i] = counts[i].load(std::memory_order_relaxed);
+    return AS_OK;
+}
+
 int32_t as_space_knn_pipe(const as_space* sp) { return sp ? sp->k2_last_pipe : -1; }
 int32_t as_last_scan_int8(const as_space* sp) { return sp && sp->qcache ? as_query_scan_int8(sp->qcache) : 0; }
 int64_t as_batch_dual_scans(const as_space* sp) { return sp ? (int64_t)sp->batch_dual_scans.load(std::memory_order_relaxed) : 0; }
@@ -984,15 +994,16 @@ as_status as_search_taus(const as_space* sp, const as_graph* gr, const double* q
 }
 
 as_status as_sweep_counters(const as_space* sp, int64_t* out, int32_t n) {
-    if (!sp || !out) {
-        set_err("as_sweep_counters: null argument");
-        return AS_EINVAL;
-    }
-    for (int i = 0; i < n && i < 3; ++i) out[i] = sp->sweep_count[i].load(std::memory_order_relaxed);
-    return AS_OK;
+    return counters_out("as_sweep_counters", sp, out, n, sp ? sp->sweep_count : nullptr, 3);
 }
 
-// ---------------------------------------------------------------- filtered search (extension; kernels: as_subset.hip)
+// ---------------------------------------------------------------- the filtered call frame (extensions)
+// What every filtered entry point is made of (subset / items, lists, range, fused, grouped and diversified search, their batched
+// and tau-sweep forms), in the order each of them keeps: its own null-argument test and the zeroing of out_len / out_ngroups; the
+// refusals before anything is launched (own_subset, ids_in_range, subset_checks -- which of the first two comes before the third
+// is the entry point's own, and stays); its `calls` counter; ONE lambda_q step (lambda_step, batch_lambda_step); the work buffers
+// (Candidates); the run; the copies of repeated taus (copy_repeated_lists, copy_repeated_rows).
+
 // what every filtered form checks alike (the tau sweeps: every tau of the list)
 static as_status subset_checks(const char* who, const as_space* sp, const as_graph* gr, int64_t d, const double* taus, int64_t ntau) {
     if (d != sp->d) {
@@ -1011,14 +1022,222 @@ static as_status subset_checks(const char* who, const as_space* sp, const as_gra
     }
     return AS_OK;
 }
-// those checks, then lambda_q by the single search on a workspace of the pool, hits discarded: its escalation, its
-// AS_EZEROLAMBDA, its out_lambda_q
-static as_status subset_lambda(const char* who, const as_space* sp, const as_graph* gr, const double* query, int64_t d, double tau, double* lq) {
-    AS_TRY(subset_checks(who, sp, gr, d, &tau, 1));
+// the first of m ids outside [0, n), or null
+static const int64_t* bad_id(const as_space* sp, const int64_t* ids, int64_t m) {
+    for (int64_t i = 0; i < m; ++i)
+        if (ids[i] < 0 || ids[i] >= sp->n) return ids + i;
+    return nullptr;
+}
+static as_status ids_in_range(const char* who, const as_space* sp, const int64_t* ids, int64_t m) {
+    if (const int64_t* bad = bad_id(sp, ids, m)) {
+        set_err("%s: id %lld is outside [0, %lld)", who, (long long)*bad, (long long)sp->n);
+        return AS_EINVAL;
+    }
+    return AS_OK;
+}
+// ids that passed ids_in_range, narrowed (item ids fit 32 bits: space_new refuses n >= 2^31)
+static as_status checked_ids(const char* who, const int64_t* ids_host, int64_t m, std::vector<int32_t>& ids) {
+    if (m >= (int64_t)1 << 31) {
+        set_err("%s: %lld ids exceed the supported maximum of 2^31 - 1 per call", who, (long long)m);
+        return AS_EUNSUPPORTED;
+    }
+    try {
+        ids.assign(ids_host, ids_host + m);
+    } catch (const std::bad_alloc&) {
+        set_err("%s: out of host memory for %lld ids", who, (long long)m);
+        return AS_ENOMEM;
+    }
+    return AS_OK;
+}
+// a subset handle (null: none was given) belongs to the space of the call
+static as_status own_subset(const char* who, const as_space* sp, const as_subset* sub) {
+    if (sub && sub->sp != sp) {
+        set_err("%s: the subset was made for another space", who);
+        return AS_EINVAL;
+    }
+    return AS_OK;
+}
+// entries of a hit list over m candidates
+static int64_t hits_bound(const as_space* sp, const as_graph* gr, int64_t m) {
+    return std::min<int64_t>(std::min<int64_t>(gr->gp.topk, sp->n), m);
+}
+
+// lambda_q of one query: ONE single search on a workspace of the pool, hits discarded -- its escalation, its AS_EZEROLAMBDA, its
+// lambda_q, published whatever the status.  `steps`: the family's counter of lambda_q steps, where it has one.
+static as_status lambda_step(const as_space* sp, const as_graph* gr, const double* query, int64_t d, double tau, std::atomic<int64_t>* steps,
+                             double* lq, double* out_lambda_q) {
+    if (steps) steps->fetch_add(1, std::memory_order_relaxed);
     int64_t hidx[SUBSET_TOPK], hlen = 0;
     double hsc[SUBSET_TOPK];
-    return search_pooled(sp, gr, query, d, tau, hidx, hsc, &hlen, lq);
+    const as_status s = search_pooled(sp, gr, query, d, tau, hidx, hsc, &hlen, lq);
+    if (out_lambda_q) *out_lambda_q = *lq;
+    return s;
 }
+// lambda_q and the status of every query of a batched form: ONE as_search_batch call over all b queries, hits discarded -- its
+// escalation, its values, published once it has returned AS_OK.  (It has then released sp->bmu: see Candidates.)
+static as_status batch_lambda_step(const char* who, const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d,
+                                   double tau, std::atomic<int64_t>* steps, std::vector<double>& lq, std::vector<int32_t>& st,
+                                   double* out_lambda_q, int32_t* out_status) {
+    if (b == 0) return AS_OK;
+    if (steps) steps->fetch_add(1, std::memory_order_relaxed);
+    const int64_t topk = std::max<int64_t>(hits_bound(sp, gr, sp->n), 1);
+    std::vector<int64_t> hidx, hlen;
+    std::vector<double> hsc;
+    try {
+        hidx.resize((size_t)(b * topk));
+        hsc.resize((size_t)(b * topk));
+        hlen.resize((size_t)b);
+        lq.assign((size_t)b, 0.0);
+        st.assign((size_t)b, 0);
+    } catch (const std::bad_alloc&) {
+        set_err("%s: out of host memory for %lld queries", who, (long long)b);
+        return AS_ENOMEM;
+    }
+    AS_TRY(as_search_batch(sp, gr, queries, b, d, tau, hidx.data(), hsc.data(), hlen.data(), lq.data(), st.data()));
+    for (int64_t i = 0; i < b; ++i) {
+        if (out_lambda_q) out_lambda_q[i] = lq[i];
+        if (out_status) out_status[i] = st[i];
+    }
+    return AS_OK;
+}
+
+// the space's work buffers for m ids (under sp->smu): grown on demand, never per call otherwise; the ids uploaded
+static as_status score_ws_ids(const as_space* sp, const int32_t* ids, int64_t m) {
+    if (!sp->score_ws || sp->score_ws->cap < m) {
+        subset_work_free(sp->score_ws);
+        sp->score_ws = nullptr;
+        int64_t cap = 1024;
+        while (cap < m) cap *= 2;
+        AS_TRY(subset_work_create(sp, cap, &sp->score_ws));
+    }
+    return subset_set_ids(sp->score_ws, ids, m);
+}
+// the space's own subset of all items (made on first use under sp->rmu, kept; no host id list: position == id)
+static as_status all_items(const as_space* sp, const as_subset** out) {
+    std::lock_guard<std::mutex> lk(sp->rmu);
+    if (!sp->range_all) {
+        AS_HIP(hipSetDevice(sp->device));
+        std::vector<int32_t> ids;
+        as_subset* all = nullptr;
+        try {
+            ids.resize((size_t)sp->n);
+            all = new as_subset();
+        } catch (const std::bad_alloc&) {
+            set_err("range: out of host memory for %lld ids", (long long)sp->n);
+            return AS_ENOMEM;
+        }
+        for (int64_t i = 0; i < sp->n; ++i) ids[(size_t)i] = (int32_t)i;
+        all->sp = sp;
+        all->m = sp->n;
+        as_status s = subset_work_create(sp, all->m, &all->w);
+        if (s == AS_OK) s = subset_set_ids(all->w, ids.data(), all->m);
+        if (s != AS_OK) {
+            as_subset_free(all);
+            return s;
+        }
+        sp->range_all = all;
+    }
+    *out = sp->range_all;
+    return AS_OK;
+}
+
+namespace {
+// The candidates of one filtered call and the work buffers they are scored on, held for the call.  Three sources: the caller's
+// subset handle (under the handle's mutex); neither a handle nor ids: the space's subset of all items (under that handle's
+// mutex); the caller's ids, checked and narrowed: sp->score_ws with the ids uploaded (under sp->smu).  The space's device is made
+// current under the lock.  `status` is looked at before anything is run; the run's status goes through fail(), so that a failed
+// run leaves nothing on the work's stream when the lock is released.
+// The lock rules of the filtered forms: the lambda_q step comes first and has returned -- as_search_batch has released sp->bmu --
+// before a handle's mutex, sp->smu or sp->lmu (the lists' buffers) is taken; sp->rmu guards only the creation of the subset of
+// all items and is released before that handle's mutex is taken; no two of these mutexes are ever held together.
+struct Candidates {
+    const as_space* sp;
+    SubsetWork* w = nullptr;
+    int64_t m = 0;
+    const int64_t* ids = nullptr;   // the handle's host ids (null: position == id, or the caller's own list)
+    as_status status = AS_OK;
+    std::unique_lock<std::mutex> lk;
+    // the caller's subset handle, or (null) the space's subset of all items
+    Candidates(const char* who, const as_space* sp_, const as_subset* sub) : sp(sp_) {
+        if (!sub && (status = all_items(sp, &sub)) != AS_OK) return;
+        if (!hold(who, sub->mu)) return;
+        w = sub->w;
+        m = sub->m;
+        ids = sub->ids;
+    }
+    // the caller's m32 ids, narrowed, in sp->score_ws
+    Candidates(const char* who, const as_space* sp_, const int32_t* ids32, int64_t m32) : sp(sp_) {
+        if (!hold(who, sp->smu)) return;
+        status = score_ws_ids(sp, ids32, m32);
+        w = sp->score_ws;
+        m = m32;
+    }
+    as_status fail(as_status s) const {
+        if (s != AS_OK && w) (void)hipStreamSynchronize(w->stream);
+        return s;
+    }
+
+  private:
+    bool hold(const char* who, std::mutex& mu) {
+        lk = std::unique_lock<std::mutex>(mu);
+        if (hipSetDevice(sp->device) == hipSuccess) return true;
+        set_err("%s: hipSetDevice failed", who);
+        status = AS_EHIP;
+        return false;
+    }
+};
+
+// The distinct taus of a sweep (bit patterns) in order of first appearance: row[u] = the entry of the list uniq[u] was taken
+// from, first[j] = the first entry with taus[j]'s bits.  Equal taus are computed once and copied (below).
+struct TauSet {
+    std::vector<double> uniq;
+    std::vector<int64_t> row, first;
+    TauSet(const double* taus, int64_t ntau) : first((size_t)ntau) {
+        for (int64_t j = 0; j < ntau; ++j) {
+            size_t u = 0;
+            while (u < uniq.size() && memcmp(&uniq[u], &taus[j], sizeof(double)) != 0) ++u;
+            if (u == uniq.size()) {
+                uniq.push_back(taus[j]);
+                row.push_back(j);
+            }
+            first[(size_t)j] = row[u];
+        }
+    }
+    int64_t ntau() const { return (int64_t)first.size(); }
+    int64_t size() const { return (int64_t)uniq.size(); }
+};
+}  // namespace
+
+// Equal taus are copies of the first one's list (b queries x ntau lists at stride kk) ...
+static void copy_repeated_lists(const TauSet& ts, int64_t b, int64_t kk, const int32_t* skip, int64_t* out_idx, double* out_score,
+                                int64_t* out_len) {
+    for (int64_t i = 0; i < b; ++i) {
+        if (skip && skip[i] == AS_EZEROLAMBDA) continue;
+        for (int64_t j = 0; j < ts.ntau(); ++j) {
+            const int64_t f = i * ts.ntau() + ts.first[(size_t)j], p = i * ts.ntau() + j;
+            if (f == p) continue;
+            for (int64_t t = 0; t < out_len[f]; ++t) {
+                out_idx[p * kk + t] = out_idx[f * kk + t];
+                out_score[p * kk + t] = out_score[f * kk + t];
+            }
+            out_len[p] = out_len[f];
+        }
+    }
+}
+// ... or of its score row: query i's ntau rows of m entries (offs: of offs[i + 1] - offs[i] entries, behind the rows of the
+// queries before it).  `skip`: the status of every query, where one with AS_EZEROLAMBDA is left out -- nothing of it was
+// written, its rows stay unwritten.
+static void copy_repeated_rows(const TauSet& ts, int64_t b, int64_t m, const int64_t* offs, const int32_t* skip, double* out) {
+    for (int64_t i = 0; i < b; ++i) {
+        if (skip && skip[i] == AS_EZEROLAMBDA) continue;
+        const int64_t mi = offs ? offs[i + 1] - offs[i] : m;
+        double* blk = out + ts.ntau() * (offs ? offs[i] : i * m);
+        for (int64_t j = 0; j < ts.ntau() && mi > 0; ++j)
+            if (ts.first[(size_t)j] != j) memcpy(blk + j * mi, blk + ts.first[(size_t)j] * mi, sizeof(double) * (size_t)mi);
+    }
+}
+
+// ---------------------------------------------------------------- filtered search (extension; kernels: as_subset.hip)
 
 as_status as_subset_create(const as_space* sp, const int64_t* ids_host, int64_t m, as_subset** out) {
     if (!sp || !out || m < 0 || (m > 0 && !ids_host)) {
@@ -1026,11 +1245,7 @@ as_status as_subset_create(const as_space* sp, const int64_t* ids_host, int64_t 
         return AS_EINVAL;
     }
     *out = nullptr;
-    for (int64_t i = 0; i < m; ++i)
-        if (ids_host[i] < 0 || ids_host[i] >= sp->n) {
-            set_err("as_subset_create: id %lld is outside [0, %lld)", (long long)ids_host[i], (long long)sp->n);
-            return AS_EINVAL;
-        }
+    AS_TRY(ids_in_range("as_subset_create", sp, ids_host, m));
     std::vector<int32_t> ids;   // (item ids fit 32 bits: space_new refuses n >= 2^31)
     as_subset* sub = nullptr;
     try {
@@ -1095,31 +1310,17 @@ as_status as_search_subset(const as_space* sp, const as_graph* gr, const double*
         return AS_EINVAL;
     }
     *out_len = 0;
-    if (sub->sp != sp) {
-        set_err("as_search_subset: the subset was made for another space");
-        return AS_EINVAL;
-    }
+    AS_TRY(own_subset("as_search_subset", sp, sub));
     double lq = 0.0;
-    const as_status s = subset_lambda("as_search_subset", sp, gr, query, d, tau, &lq);
-    if (out_lambda_q) *out_lambda_q = lq;
-    if (s != AS_OK) return s;
+    if (out_lambda_q) *out_lambda_q = lq;   // (the two plain single forms publish lambda_q = 0 with a refusal of the checks below)
+    AS_TRY(subset_checks("as_search_subset", sp, gr, d, &tau, 1));
+    AS_TRY(lambda_step(sp, gr, query, d, tau, nullptr, &lq, out_lambda_q));
     if (sub->m == 0) return AS_OK;
-    const int64_t topk = std::min<int64_t>(gr->gp.topk, sp->n);
-    std::lock_guard<std::mutex> lk(sub->mu);
-    AS_TRY(subset_score(sp, sub->w, sub->m, query, tau, lq));
-    return subset_select(sub->w, sub->m, std::min<int64_t>(topk, sub->m), out_idx, out_score, out_len);
-}
-
-// the space's work buffers for m ids (under sp->smu): grown on demand, never per call otherwise; the ids uploaded
-static as_status score_ws_ids(const as_space* sp, const int32_t* ids, int64_t m) {
-    if (!sp->score_ws || sp->score_ws->cap < m) {
-        subset_work_free(sp->score_ws);
-        sp->score_ws = nullptr;
-        int64_t cap = 1024;
-        while (cap < m) cap *= 2;
-        AS_TRY(subset_work_create(sp, cap, &sp->score_ws));
-    }
-    return subset_set_ids(sp->score_ws, ids, m);
+    Candidates c("as_search_subset", sp, sub);
+    AS_TRY(c.status);
+    as_status s = subset_score(sp, c.w, c.m, query, tau, lq);
+    if (s == AS_OK) s = subset_select(c.w, c.m, hits_bound(sp, gr, c.m), out_idx, out_score, out_len);
+    return c.fail(s);
 }
 
 as_status as_score_items(const as_space* sp, const as_graph* gr, const double* query, int64_t d, double tau, const int64_t* ids_host,
@@ -1128,31 +1329,19 @@ as_status as_score_items(const as_space* sp, const as_graph* gr, const double* q
         set_err("as_score_items: null argument");
         return AS_EINVAL;
     }
-    for (int64_t i = 0; i < m; ++i)
-        if (ids_host[i] < 0 || ids_host[i] >= sp->n) {
-            set_err("as_score_items: id %lld is outside [0, %lld)", (long long)ids_host[i], (long long)sp->n);
-            return AS_EINVAL;
-        }
+    AS_TRY(ids_in_range("as_score_items", sp, ids_host, m));
     double lq = 0.0;
-    const as_status s = subset_lambda("as_score_items", sp, gr, query, d, tau, &lq);
-    if (out_lambda_q) *out_lambda_q = lq;
-    if (s != AS_OK) return s;
+    if (out_lambda_q) *out_lambda_q = lq;   // (as in as_search_subset)
+    AS_TRY(subset_checks("as_score_items", sp, gr, d, &tau, 1));
+    AS_TRY(lambda_step(sp, gr, query, d, tau, nullptr, &lq, out_lambda_q));
     if (m == 0) return AS_OK;
-    if (m >= (int64_t)1 << 31) {
-        set_err("as_score_items: %lld ids exceed the supported maximum of 2^31 - 1 per call", (long long)m);
-        return AS_EUNSUPPORTED;
-    }
-    std::vector<int32_t> ids;   // (item ids fit 32 bits: space_new refuses n >= 2^31)
-    try {
-        ids.assign(ids_host, ids_host + m);
-    } catch (const std::bad_alloc&) {
-        set_err("as_score_items: out of host memory for %lld ids", (long long)m);
-        return AS_ENOMEM;
-    }
-    std::lock_guard<std::mutex> lk(sp->smu);
-    AS_TRY(score_ws_ids(sp, ids.data(), m));
-    AS_TRY(subset_score(sp, sp->score_ws, m, query, tau, lq));
-    return subset_scores_out(sp->score_ws, m, out_scores);
+    std::vector<int32_t> ids;
+    AS_TRY(checked_ids("as_score_items", ids_host, m, ids));
+    Candidates c("as_score_items", sp, ids.data(), m);
+    AS_TRY(c.status);
+    as_status s = subset_score(sp, c.w, m, query, tau, lq);
+    if (s == AS_OK) s = subset_scores_out(c.w, m, out_scores);
+    return c.fail(s);
 }
 
 // the batched workspaces for b > 1 queries (under sp->bmu); *unit = the passes launched together (2: a pair sharing one scan)
@@ -1253,32 +1442,7 @@ as_status as_search_batch(const as_space* sp, const as_graph* gr, const double* 
     return AS_OK;
 }
 
-// The batched filtered forms.  What both check (the single forms' checks and messages), then lambda_q and the status of every
-// query from ONE as_search_batch call over all b queries, hits discarded: its escalation, its values.  as_search_batch has
-// returned, and released sp->bmu, before the caller takes the handle's mutex: the two are never nested.
-static as_status batch_lambda_step(const char* who, const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d,
-                                   double tau, std::vector<double>& lq, std::vector<int32_t>& st) {
-    if (b == 0) return AS_OK;
-    const int64_t topk = std::max<int64_t>(std::min<int64_t>(gr->gp.topk, sp->n), 1);
-    std::vector<int64_t> hidx, hlen;
-    std::vector<double> hsc;
-    try {
-        hidx.resize((size_t)(b * topk));
-        hsc.resize((size_t)(b * topk));
-        hlen.resize((size_t)b);
-        lq.assign((size_t)b, 0.0);
-        st.assign((size_t)b, 0);
-    } catch (const std::bad_alloc&) {
-        set_err("%s: out of host memory for %lld queries", who, (long long)b);
-        return AS_ENOMEM;
-    }
-    return as_search_batch(sp, gr, queries, b, d, tau, hidx.data(), hsc.data(), hlen.data(), lq.data(), st.data());
-}
-static as_status subset_batch_lambda(const char* who, const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d,
-                                     double tau, std::vector<double>& lq, std::vector<int32_t>& st) {
-    AS_TRY(subset_checks(who, sp, gr, d, &tau, 1));
-    return batch_lambda_step(who, sp, gr, queries, b, d, tau, lq, st);
-}
+// The batched filtered forms: the single forms' checks and messages.
 
 as_status as_search_subset_batch(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau,
                                  const as_subset* sub, int64_t* out_idx, double* out_score, int64_t* out_len, double* out_lambda_q,
@@ -1288,22 +1452,16 @@ as_status as_search_subset_batch(const as_space* sp, const as_graph* gr, const d
         return AS_EINVAL;
     }
     for (int64_t i = 0; i < b; ++i) out_len[i] = 0;
-    if (sub->sp != sp) {
-        set_err("as_search_subset_batch: the subset was made for another space");
-        return AS_EINVAL;
-    }
+    AS_TRY(own_subset("as_search_subset_batch", sp, sub));
+    AS_TRY(subset_checks("as_search_subset_batch", sp, gr, d, &tau, 1));
     std::vector<double> lq;
     std::vector<int32_t> st;
-    AS_TRY(subset_batch_lambda("as_search_subset_batch", sp, gr, queries, b, d, tau, lq, st));
-    for (int64_t i = 0; i < b; ++i) {
-        if (out_lambda_q) out_lambda_q[i] = lq[i];
-        if (out_status) out_status[i] = st[i];
-    }
+    AS_TRY(batch_lambda_step("as_search_subset_batch", sp, gr, queries, b, d, tau, nullptr, lq, st, out_lambda_q, out_status));
     if (b == 0 || sub->m == 0) return AS_OK;
-    const int64_t kk = std::min<int64_t>(std::min<int64_t>(gr->gp.topk, sp->n), sub->m);
-    std::lock_guard<std::mutex> lk(sub->mu);
-    AS_HIP(hipSetDevice(sp->device));
-    return subset_batch_run(sp, sub->w, sub->m, queries, b, lq.data(), st.data(), tau, kk, kk, out_idx, out_score, out_len, nullptr);
+    const int64_t kk = hits_bound(sp, gr, sub->m);
+    Candidates c("as_search_subset_batch", sp, sub);
+    AS_TRY(c.status);
+    return c.fail(subset_batch_run(sp, c.w, c.m, queries, b, lq.data(), st.data(), tau, kk, kk, out_idx, out_score, out_len, nullptr));
 }
 
 as_status as_score_items_batch(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau,
@@ -1312,67 +1470,20 @@ as_status as_score_items_batch(const as_space* sp, const as_graph* gr, const dou
         set_err("as_score_items_batch: null argument");
         return AS_EINVAL;
     }
-    for (int64_t i = 0; i < m; ++i)
-        if (ids_host[i] < 0 || ids_host[i] >= sp->n) {
-            set_err("as_score_items_batch: id %lld is outside [0, %lld)", (long long)ids_host[i], (long long)sp->n);
-            return AS_EINVAL;
-        }
+    AS_TRY(ids_in_range("as_score_items_batch", sp, ids_host, m));
+    AS_TRY(subset_checks("as_score_items_batch", sp, gr, d, &tau, 1));
     std::vector<double> lq;
     std::vector<int32_t> st;
-    AS_TRY(subset_batch_lambda("as_score_items_batch", sp, gr, queries, b, d, tau, lq, st));
-    for (int64_t i = 0; i < b; ++i) {
-        if (out_lambda_q) out_lambda_q[i] = lq[i];
-        if (out_status) out_status[i] = st[i];
-    }
+    AS_TRY(batch_lambda_step("as_score_items_batch", sp, gr, queries, b, d, tau, nullptr, lq, st, out_lambda_q, out_status));
     if (b == 0 || m == 0) return AS_OK;
-    if (m >= (int64_t)1 << 31) {
-        set_err("as_score_items_batch: %lld ids exceed the supported maximum of 2^31 - 1 per call", (long long)m);
-        return AS_EUNSUPPORTED;
-    }
-    std::vector<int32_t> ids;   // (item ids fit 32 bits: space_new refuses n >= 2^31)
-    try {
-        ids.assign(ids_host, ids_host + m);
-    } catch (const std::bad_alloc&) {
-        set_err("as_score_items_batch: out of host memory for %lld ids", (long long)m);
-        return AS_ENOMEM;
-    }
-    std::lock_guard<std::mutex> lk(sp->smu);
-    AS_HIP(hipSetDevice(sp->device));
-    AS_TRY(score_ws_ids(sp, ids.data(), m));
-    return subset_batch_run(sp, sp->score_ws, m, queries, b, lq.data(), st.data(), tau, 0, 0, nullptr, nullptr, nullptr, out_scores);
+    std::vector<int32_t> ids;
+    AS_TRY(checked_ids("as_score_items_batch", ids_host, m, ids));
+    Candidates c("as_score_items_batch", sp, ids.data(), m);
+    AS_TRY(c.status);
+    return c.fail(subset_batch_run(sp, c.w, m, queries, b, lq.data(), st.data(), tau, 0, 0, nullptr, nullptr, nullptr, out_scores));
 }
 
 // ---------------------------------------------------------------- range search (extension; as_range.hip)
-// the subset a range call runs on: the caller's, or the space's own subset of all items (made on first use, kept)
-static as_status range_subset(const as_space* sp, const as_subset* sub, const as_subset** out) {
-    *out = sub;
-    if (sub) return AS_OK;
-    std::lock_guard<std::mutex> lk(sp->rmu);
-    if (!sp->range_all) {
-        AS_HIP(hipSetDevice(sp->device));
-        std::vector<int32_t> ids;
-        as_subset* all = nullptr;
-        try {
-            ids.resize((size_t)sp->n);
-            all = new as_subset();
-        } catch (const std::bad_alloc&) {
-            set_err("range: out of host memory for %lld ids", (long long)sp->n);
-            return AS_ENOMEM;
-        }
-        for (int64_t i = 0; i < sp->n; ++i) ids[(size_t)i] = (int32_t)i;
-        all->sp = sp;
-        all->m = sp->n;
-        as_status s = subset_work_create(sp, all->m, &all->w);
-        if (s == AS_OK) s = subset_set_ids(all->w, ids.data(), all->m);
-        if (s != AS_OK) {
-            as_subset_free(all);
-            return s;
-        }
-        sp->range_all = all;
-    }
-    *out = sp->range_all;
-    return AS_OK;
-}
 static as_range* range_new(bool count_only) {
     as_range* r = new (std::nothrow) as_range();
     if (!r) {
@@ -1416,34 +1527,25 @@ as_status as_search_range(const as_space* sp, const as_graph* gr, const double* 
         set_err("as_search_range: min_score must not be NaN");
         return AS_EINVAL;
     }
-    if (sub && sub->sp != sp) {
-        set_err("as_search_range: the subset was made for another space");
-        return AS_EINVAL;
-    }
+    AS_TRY(own_subset("as_search_range", sp, sub));
     AS_TRY(subset_checks("as_search_range", sp, gr, d, &tau, 1));
     sp->range_count[0].fetch_add(1, std::memory_order_relaxed);
     double lq = 0.0;
-    {
-        int64_t hidx[SUBSET_TOPK], hlen = 0;
-        double hsc[SUBSET_TOPK];
-        sp->range_count[5].fetch_add(1, std::memory_order_relaxed);
-        const as_status s = search_pooled(sp, gr, query, d, tau, hidx, hsc, &hlen, &lq);
-        if (out_lambda_q) *out_lambda_q = lq;
-        if (s != AS_OK) return s;
-    }
+    AS_TRY(lambda_step(sp, gr, query, d, tau, &sp->range_count[5], &lq, out_lambda_q));
     as_range* res = range_new(count_only != 0);
     if (!res) return AS_ENOMEM;
     as_status s = AS_OK;
-    const as_subset* on = nullptr;
     if (sub && sub->m == 0) s = range_pad(res, 1);
-    else if ((s = range_subset(sp, sub, &on)) == AS_OK) {
-        int64_t counts[4] = {0, 0, 0, 0};
-        double us = 0.0;
-        std::lock_guard<std::mutex> lk(on->mu);
-        s = subset_score(sp, on->w, on->m, query, tau, lq);
-        if (s == AS_OK) s = range_compact(on->w, on->w->scores, on->m, on->m, 1, &min_score, count_only != 0, on->ids, res, counts, &us);
-        else (void)hipStreamSynchronize(on->w->stream);
-        range_counts_add(sp, counts, us);
+    else {
+        Candidates c("as_search_range", sp, sub);
+        if ((s = c.status) == AS_OK) {
+            int64_t counts[4] = {0, 0, 0, 0};
+            double us = 0.0;
+            s = subset_score(sp, c.w, c.m, query, tau, lq);
+            if (s == AS_OK) s = range_compact(c.w, c.w->scores, c.m, c.m, 1, &min_score, count_only != 0, c.ids, res, counts, &us);
+            s = c.fail(s);
+            range_counts_add(sp, counts, us);
+        }
     }
     if (s != AS_OK) {
         delete res;
@@ -1455,7 +1557,7 @@ as_status as_search_range(const as_space* sp, const as_graph* gr, const double* 
 
 namespace {
 struct RangeSink {
-    const as_subset* on;
+    const Candidates* on;
     const double* thr;   // [b]: NaN for a query without an answer
     bool count_only;
     as_range* res;
@@ -1481,27 +1583,15 @@ as_status as_search_range_batch(const as_space* sp, const as_graph* gr, const do
             set_err("as_search_range_batch: min_scores[%lld] must not be NaN", (long long)i);
             return AS_EINVAL;
         }
-    if (sub && sub->sp != sp) {
-        set_err("as_search_range_batch: the subset was made for another space");
-        return AS_EINVAL;
-    }
+    AS_TRY(own_subset("as_search_range_batch", sp, sub));
     AS_TRY(subset_checks("as_search_range_batch", sp, gr, d, &tau, 1));
     sp->range_count[0].fetch_add(1, std::memory_order_relaxed);
     as_range* res = range_new(count_only != 0);
     if (!res) return AS_ENOMEM;
-    if (b == 0) {
-        *out = res;
-        return AS_OK;
-    }
     std::vector<double> lq, thr;
     std::vector<int32_t> st;
-    sp->range_count[5].fetch_add(1, std::memory_order_relaxed);
-    as_status s = batch_lambda_step("as_search_range_batch", sp, gr, queries, b, d, tau, lq, st);
+    as_status s = batch_lambda_step("as_search_range_batch", sp, gr, queries, b, d, tau, &sp->range_count[5], lq, st, out_lambda_q, out_status);
     if (s == AS_OK) {
-        for (int64_t i = 0; i < b; ++i) {
-            if (out_lambda_q) out_lambda_q[i] = lq[i];
-            if (out_status) out_status[i] = st[i];
-        }
         try {
             thr.assign(min_scores, min_scores + b);
         } catch (const std::bad_alloc&) {
@@ -1509,21 +1599,19 @@ as_status as_search_range_batch(const as_space* sp, const as_graph* gr, const do
             s = AS_ENOMEM;
         }
     }
-    const as_subset* on = nullptr;
-    if (s == AS_OK) {
+    if (s == AS_OK && b > 0) {
         if (sub && sub->m == 0) s = range_pad(res, b);
-        else if ((s = range_subset(sp, sub, &on)) == AS_OK) {
+        else {
             // a zero-lambda query's row of a chunk holds no answer: against a NaN threshold nothing in it survives
             for (int64_t i = 0; i < b; ++i)
                 if (st[i] == AS_EZEROLAMBDA) thr[i] = std::numeric_limits<double>::quiet_NaN();
-            RangeSink k{on, thr.data(), count_only != 0, res, {0, 0, 0, 0}, 0.0};
-            const SubsetChunkSink sink{range_sink_chunk, &k};
-            std::lock_guard<std::mutex> lk(on->mu);
-            s = hipSetDevice(sp->device) == hipSuccess ? AS_OK : AS_EHIP;
-            if (s != AS_OK) set_err("as_search_range_batch: hipSetDevice failed");
-            else s = subset_batch_run(sp, on->w, on->m, queries, b, lq.data(), st.data(), tau, 0, 0, nullptr, nullptr, nullptr, nullptr, &sink);
-            if (s != AS_OK) (void)hipStreamSynchronize(on->w->stream);
-            range_counts_add(sp, k.counts, k.us);
+            const Candidates c("as_search_range_batch", sp, sub);
+            if ((s = c.status) == AS_OK) {
+                RangeSink k{&c, thr.data(), count_only != 0, res, {0, 0, 0, 0}, 0.0};
+                const SubsetChunkSink sink{range_sink_chunk, &k};
+                s = c.fail(subset_batch_run(sp, c.w, c.m, queries, b, lq.data(), st.data(), tau, 0, 0, nullptr, nullptr, nullptr, nullptr, &sink));
+                range_counts_add(sp, k.counts, k.us);
+            }
         }
     }
     if (s != AS_OK) {
@@ -1561,17 +1649,11 @@ as_status as_range_copy(const as_range* r, int64_t* out_idx, double* out_score) 
 }
 void as_range_free(as_range* r) { delete r; }
 as_status as_range_counters(const as_space* sp, int64_t* out, int32_t n) {
-    if (!sp || !out) {
-        set_err("as_range_counters: null argument");
-        return AS_EINVAL;
-    }
-    for (int i = 0; i < n && i < 6; ++i) out[i] = sp->range_count[i].load(std::memory_order_relaxed);
-    return AS_OK;
+    return counters_out("as_range_counters", sp, out, n, sp ? sp->range_count : nullptr, 6);
 }
 double as_range_kernel_us(const as_space* sp) { return sp ? sp->range_us.load(std::memory_order_relaxed) : 0.0; }
 
 // ---------------------------------------------------------------- fused multi-query search (extension; as_fused.hip)
-static as_status checked_ids(const char* who, const as_space* sp, const int64_t* ids_host, int64_t m, std::vector<int32_t>& ids);   // (below)
 namespace {
 // What both forms refuse before anything is launched, then lambda_q and the status of every vector from ONE as_search_batch call
 // over the j vectors, then S13's zero-lambda rule.  `wts`: the caller's weights, or 1/j each.
@@ -1591,10 +1673,7 @@ as_status fused_prepare(const char* who, const as_space* sp, const as_graph* gr,
             set_err("%s: weights[%lld] must be finite", who, (long long)t);
             return AS_EINVAL;
         }
-    if (sub && sub->sp != sp) {
-        set_err("%s: the subset was made for another space", who);
-        return AS_EINVAL;
-    }
+    AS_TRY(own_subset(who, sp, sub));
     AS_TRY(subset_checks(who, sp, gr, d, &tau, 1));
     try {
         if (weights) wts.assign(weights, weights + j);
@@ -1604,14 +1683,9 @@ as_status fused_prepare(const char* who, const as_space* sp, const as_graph* gr,
         return AS_ENOMEM;
     }
     sp->fused_count[0].fetch_add(1, std::memory_order_relaxed);
-    sp->fused_count[3].fetch_add(1, std::memory_order_relaxed);
-    AS_TRY(batch_lambda_step(who, sp, gr, queries, j, d, tau, lq, st));
+    AS_TRY(batch_lambda_step(who, sp, gr, queries, j, d, tau, &sp->fused_count[3], lq, st, out_lambda_q, out_status));
     int64_t served = 0;
-    for (int64_t t = 0; t < j; ++t) {
-        if (out_lambda_q) out_lambda_q[t] = lq[t];
-        if (out_status) out_status[t] = st[t];
-        served += st[t] == AS_EZEROLAMBDA ? 0 : 1;
-    }
+    for (int64_t t = 0; t < j; ++t) served += st[t] == AS_EZEROLAMBDA ? 0 : 1;
     if (served == 0 || (served < j && !skip_zero)) {
         set_err("The lambdas are zero, check the magnitude of items and eps.");
         return AS_EZEROLAMBDA;
@@ -1648,16 +1722,12 @@ as_status as_search_fused(const as_space* sp, const as_graph* gr, const double* 
     std::vector<int32_t> st;
     AS_TRY(fused_prepare("as_search_fused", sp, gr, queries, j, d, tau, weights, mode, skip_zero, sub, out_lambda_q, out_status, wts, lq, st));
     if (sub && sub->m == 0) return AS_OK;
-    const as_subset* on = nullptr;
-    AS_TRY(range_subset(sp, sub, &on));
-    const int64_t kk = std::min<int64_t>(std::min<int64_t>(gr->gp.topk, sp->n), on->m);
+    const Candidates c("as_search_fused", sp, sub);
+    AS_TRY(c.status);
     FusedCall call;
-    std::lock_guard<std::mutex> lk(on->mu);
-    AS_HIP(hipSetDevice(sp->device));
-    as_status s = fused_fold(sp, on->w, on->m, queries, j, tau, wts, lq, st, mode, &call);
-    if (s == AS_OK) s = subset_select_from(on->w, fused_acc(on->w), on->m, kk, out_idx, out_score, out_len);
-    if (s == AS_OK) s = fused_end(&call);
-    else (void)hipStreamSynchronize(on->w->stream);
+    as_status s = fused_fold(sp, c.w, c.m, queries, j, tau, wts, lq, st, mode, &call);
+    if (s == AS_OK) s = subset_select_from(c.w, fused_acc(c.w), c.m, hits_bound(sp, gr, c.m), out_idx, out_score, out_len);
+    s = s == AS_OK ? fused_end(&call) : c.fail(s);
     fused_counts_add(sp, call);
     return s;
 }
@@ -1669,22 +1739,17 @@ as_status as_score_fused(const as_space* sp, const as_graph* gr, const double* q
         set_err("as_score_fused: null argument");
         return AS_EINVAL;
     }
-    for (int64_t i = 0; i < m; ++i)
-        if (ids_host[i] < 0 || ids_host[i] >= sp->n) {
-            set_err("as_score_fused: id %lld is outside [0, %lld)", (long long)ids_host[i], (long long)sp->n);
-            return AS_EINVAL;
-        }
+    AS_TRY(ids_in_range("as_score_fused", sp, ids_host, m));
     std::vector<double> wts, lq;
     std::vector<int32_t> st;
     AS_TRY(fused_prepare("as_score_fused", sp, gr, queries, j, d, tau, weights, mode, skip_zero, nullptr, out_lambda_q, out_status, wts, lq, st));
     if (m == 0) return AS_OK;
     std::vector<int32_t> ids;
-    AS_TRY(checked_ids("as_score_fused", sp, ids_host, m, ids));
+    AS_TRY(checked_ids("as_score_fused", ids_host, m, ids));
+    const Candidates c("as_score_fused", sp, ids.data(), m);
+    AS_TRY(c.status);
+    SubsetWork* w = c.w;
     FusedCall call;
-    std::lock_guard<std::mutex> lk(sp->smu);
-    AS_HIP(hipSetDevice(sp->device));
-    AS_TRY(score_ws_ids(sp, ids.data(), m));
-    SubsetWork* w = sp->score_ws;
     as_status s = fused_fold(sp, w, m, queries, j, tau, wts, lq, st, mode, &call);
     if (s == AS_OK && hipMemcpyAsync(out_scores, fused_acc(w), sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, w->stream) != hipSuccess) {
         set_err("as_score_fused: the copy of the scores failed");
@@ -1700,12 +1765,7 @@ as_status as_score_fused(const as_space* sp, const as_graph* gr, const double* q
 }
 
 as_status as_fused_counters(const as_space* sp, int64_t* out, int32_t n) {
-    if (!sp || !out) {
-        set_err("as_fused_counters: null argument");
-        return AS_EINVAL;
-    }
-    for (int i = 0; i < n && i < 4; ++i) out[i] = sp->fused_count[i].load(std::memory_order_relaxed);
-    return AS_OK;
+    return counters_out("as_fused_counters", sp, out, n, sp ? sp->fused_count : nullptr, 4);
 }
 double as_fused_kernel_us(const as_space* sp) { return sp ? sp->fused_us.load(std::memory_order_relaxed) : 0.0; }
 
@@ -1779,10 +1839,7 @@ as_status grouped_checks(const char* who, const as_space* sp, const as_graph* gr
         set_err("%s: the groups were made for another space", who);
         return AS_EINVAL;
     }
-    if (sub && sub->sp != sp) {
-        set_err("%s: the subset was made for another space", who);
-        return AS_EINVAL;
-    }
+    AS_TRY(own_subset(who, sp, sub));
     return subset_checks(who, sp, gr, d, &tau, 1);
 }
 void grouped_counts_add(const as_space* sp, const GroupedCall& call) {
@@ -1805,28 +1862,16 @@ as_status as_search_grouped(const as_space* sp, const as_graph* gr, const double
     AS_TRY(grouped_checks("as_search_grouped", sp, gr, d, tau, groups, n_groups, per_group, sub));
     sp->grouped_count[0].fetch_add(1, std::memory_order_relaxed);
     double lq = 0.0;
-    {
-        int64_t hidx[SUBSET_TOPK], hlen = 0;
-        double hsc[SUBSET_TOPK];
-        sp->grouped_count[6].fetch_add(1, std::memory_order_relaxed);
-        const as_status s = search_pooled(sp, gr, query, d, tau, hidx, hsc, &hlen, &lq);
-        if (out_lambda_q) *out_lambda_q = lq;
-        if (s != AS_OK) return s;
-    }
+    AS_TRY(lambda_step(sp, gr, query, d, tau, &sp->grouped_count[6], &lq, out_lambda_q));
     if (sub && sub->m == 0) return AS_OK;
-    const as_subset* on = nullptr;
-    AS_TRY(range_subset(sp, sub, &on));
+    const Candidates c("as_search_grouped", sp, sub);
+    AS_TRY(c.status);
     GroupedCall call;
-    call.w = on->w; call.g = groups; call.m = on->m; call.n_groups = n_groups; call.per_group = per_group;
+    call.w = c.w; call.g = groups; call.m = c.m; call.n_groups = n_groups; call.per_group = per_group;
     call.out_label = out_label; call.out_count = out_count; call.out_idx = out_idx; call.out_score = out_score; call.out_ngroups = out_ngroups;
-    std::lock_guard<std::mutex> lk(on->mu);
-    AS_HIP(hipSetDevice(sp->device));
-    as_status s = subset_score(sp, on->w, on->m, query, tau, lq);
-    if (s == AS_OK) s = grouped_rows(&call, 0, 1, on->w->scores, on->m);
-    if (s != AS_OK) {
-        (void)hipStreamSynchronize(on->w->stream);
-        *out_ngroups = 0;
-    }
+    as_status s = subset_score(sp, c.w, c.m, query, tau, lq);
+    if (s == AS_OK) s = grouped_rows(&call, 0, 1, c.w->scores, c.m);
+    if (c.fail(s) != AS_OK) *out_ngroups = 0;
     grouped_counts_add(sp, call);
     return s;
 }
@@ -1845,38 +1890,24 @@ as_status as_search_grouped_batch(const as_space* sp, const as_graph* gr, const 
     if (b == 0) return AS_OK;
     std::vector<double> lq;
     std::vector<int32_t> st;
-    sp->grouped_count[6].fetch_add(1, std::memory_order_relaxed);
-    AS_TRY(batch_lambda_step("as_search_grouped_batch", sp, gr, queries, b, d, tau, lq, st));
-    for (int64_t i = 0; i < b; ++i) {
-        if (out_lambda_q) out_lambda_q[i] = lq[i];
-        if (out_status) out_status[i] = st[i];
-    }
+    AS_TRY(batch_lambda_step("as_search_grouped_batch", sp, gr, queries, b, d, tau, &sp->grouped_count[6], lq, st, out_lambda_q, out_status));
     if (sub && sub->m == 0) return AS_OK;
-    const as_subset* on = nullptr;
-    AS_TRY(range_subset(sp, sub, &on));
+    const Candidates c("as_search_grouped_batch", sp, sub);
+    AS_TRY(c.status);
     GroupedCall call;
-    call.w = on->w; call.g = groups; call.m = on->m; call.n_groups = n_groups; call.per_group = per_group; call.status = st.data();
+    call.w = c.w; call.g = groups; call.m = c.m; call.n_groups = n_groups; call.per_group = per_group; call.status = st.data();
     call.out_label = out_label; call.out_count = out_count; call.out_idx = out_idx; call.out_score = out_score; call.out_ngroups = out_ngroups;
     SubsetChunkSink sink{grouped_sink_chunk, &call};
-    sink.row_bytes = grouped_row_bytes(groups, on->m, n_groups, per_group);
-    std::lock_guard<std::mutex> lk(on->mu);
-    AS_HIP(hipSetDevice(sp->device));
-    const as_status s = subset_batch_run(sp, on->w, on->m, queries, b, lq.data(), st.data(), tau, 0, 0, nullptr, nullptr, nullptr, nullptr, &sink);
-    if (s != AS_OK) {
-        (void)hipStreamSynchronize(on->w->stream);
+    sink.row_bytes = grouped_row_bytes(groups, c.m, n_groups, per_group);
+    const as_status s = c.fail(subset_batch_run(sp, c.w, c.m, queries, b, lq.data(), st.data(), tau, 0, 0, nullptr, nullptr, nullptr, nullptr, &sink));
+    if (s != AS_OK)
         for (int64_t i = 0; i < b; ++i) out_ngroups[i] = 0;
-    }
     grouped_counts_add(sp, call);
     return s;
 }
 
 as_status as_grouped_counters(const as_space* sp, int64_t* out, int32_t n) {
-    if (!sp || !out) {
-        set_err("as_grouped_counters: null argument");
-        return AS_EINVAL;
-    }
-    for (int i = 0; i < n && i < 7; ++i) out[i] = sp->grouped_count[i].load(std::memory_order_relaxed);
-    return AS_OK;
+    return counters_out("as_grouped_counters", sp, out, n, sp ? sp->grouped_count : nullptr, 7);
 }
 double as_grouped_kernel_us(const as_space* sp) { return sp ? sp->grouped_us.load(std::memory_order_relaxed) : 0.0; }
 
@@ -1892,10 +1923,7 @@ static as_status diverse_checks(const char* who, const as_space* sp, const as_gr
         set_err("%s: diversity must lie in [0, 1], got %g", who, diversity);
         return AS_EINVAL;
     }
-    if (sub && sub->sp != sp) {
-        set_err("%s: the subset was made for another space", who);
-        return AS_EINVAL;
-    }
+    AS_TRY(own_subset(who, sp, sub));
     return subset_checks(who, sp, gr, d, &tau, 1);
 }
 static void diverse_counts_add(const as_space* sp, const int64_t* counts) {
@@ -1938,7 +1966,7 @@ as_status as_search_diverse_batch(const as_space* sp, const as_graph* gr, const 
         set_err("as_search_diverse_batch: null argument");
         return AS_EINVAL;
     }
-    const int64_t kk = std::min<int64_t>(std::min<int64_t>(gr->gp.topk, sp->n), sub ? sub->m : sp->n);
+    const int64_t kk = hits_bound(sp, gr, sub ? sub->m : sp->n);
     if (b > 0 && kk > 0 && (!out_idx || !out_score)) {
         set_err("as_search_diverse_batch: null argument");
         return AS_EINVAL;
@@ -1980,12 +2008,7 @@ as_status as_search_diverse_batch(const as_space* sp, const as_graph* gr, const 
 }
 
 as_status as_diverse_counters(const as_space* sp, int64_t* out, int32_t n) {
-    if (!sp || !out) {
-        set_err("as_diverse_counters: null argument");
-        return AS_EINVAL;
-    }
-    for (int i = 0; i < n && i < 5; ++i) out[i] = sp->diverse_count[i].load(std::memory_order_relaxed);
-    return AS_OK;
+    return counters_out("as_diverse_counters", sp, out, n, sp ? sp->diverse_count : nullptr, 5);
 }
 double as_diverse_kernel_us(const as_space* sp) {
     if (!sp) return 0.0;
@@ -2011,11 +2034,10 @@ static as_status lists_checks(const char* who, const as_space* sp, const int64_t
         return AS_EUNSUPPORTED;
     }
     for (int64_t i = 0; i < b; ++i)
-        for (int64_t e = offs[i]; e < offs[i + 1]; ++e)
-            if (ids_host[e] < 0 || ids_host[e] >= sp->n) {
-                set_err("%s: id %lld of list %lld is outside [0, %lld)", who, (long long)ids_host[e], (long long)i, (long long)sp->n);
-                return AS_EINVAL;
-            }
+        if (const int64_t* bad = bad_id(sp, ids_host + offs[i], offs[i + 1] - offs[i])) {
+            set_err("%s: id %lld of list %lld is outside [0, %lld)", who, (long long)*bad, (long long)i, (long long)sp->n);
+            return AS_EINVAL;
+        }
     return AS_OK;
 }
 // the lists as 32-bit ids (item ids fit: space_new refuses n >= 2^31); dedupe: every list without its repeated ids, the first
@@ -2051,17 +2073,24 @@ static bool lists_ids32(const as_space* sp, const int64_t* ids_host, const int64
 static int64_t host_ns_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
 }
-// the two forms: select: the first kk of every list, else every score.  lists_count[4] takes the host time the call spends
-// serially: the checks, the wait for the helper thread after the lambda_q step, the work tables.
-static as_status lists_call(const char* who, const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau,
-                            const int64_t* ids_host, const int64_t* offs_host, bool select, int64_t* out_idx, double* out_score,
-                            int64_t* out_len, double* out_scores, double* out_lambda_q, int32_t* out_status) {
-    AS_TRY(subset_checks(who, sp, gr, d, &tau, 1));
+// The four forms.  select: the first kk of every list, else every score.  sweep: the _taus forms (section 5.13) -- every tau finite,
+// ONE lambda_q step with taus[0], the distinct taus through lists_run_taus, repeated taus copied here, counted in lsweep_count; the
+// one-tau forms run lists_run and are counted in lists_count.  Either array: [0] calls, the driver's work counts (2, the sweeps
+// 3), the lambda_q steps, then the host time the call spends serially: the checks, the wait for the helper thread after the
+// lambda_q step, the work tables.
+static as_status lists_call(const char* who, const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d,
+                            const double* taus, int64_t ntau, bool sweep, const int64_t* ids_host, const int64_t* offs_host, bool select,
+                            int64_t* out_idx, double* out_score, int64_t* out_len, double* out_scores, double* out_lambda_q,
+                            int32_t* out_status) {
+    std::atomic<int64_t>* count = sweep ? sp->lsweep_count : sp->lists_count;
+    const int nwork = sweep ? 3 : 2;
+    std::atomic<int64_t>& host_ns = count[nwork + 2];
+    AS_TRY(subset_checks(who, sp, gr, d, taus, ntau));
     auto t0 = std::chrono::steady_clock::now();
     AS_TRY(lists_checks(who, sp, ids_host, offs_host, b));
-    sp->lists_count[4].fetch_add(host_ns_since(t0), std::memory_order_relaxed);
-    sp->lists_count[0].fetch_add(1, std::memory_order_relaxed);
-    if (b == 0) return AS_OK;
+    host_ns.fetch_add(host_ns_since(t0), std::memory_order_relaxed);
+    count[0].fetch_add(1, std::memory_order_relaxed);
+    if (b == 0 || ntau == 0) return AS_OK;
     std::vector<int32_t> ids;
     std::vector<int64_t> offs;
     bool ids_ok = true;
@@ -2073,33 +2102,35 @@ static as_status lists_call(const char* who, const as_space* sp, const as_graph*
     }
     std::vector<double> lq;
     std::vector<int32_t> st;
-    sp->lists_count[3].fetch_add(1, std::memory_order_relaxed);
-    const as_status ls = batch_lambda_step(who, sp, gr, queries, b, d, tau, lq, st);
+    const as_status ls = batch_lambda_step(who, sp, gr, queries, b, d, taus[0], &count[nwork + 1], lq, st, out_lambda_q, out_status);
     t0 = std::chrono::steady_clock::now();
     if (helper.joinable()) helper.join();
-    sp->lists_count[4].fetch_add(host_ns_since(t0), std::memory_order_relaxed);
+    host_ns.fetch_add(host_ns_since(t0), std::memory_order_relaxed);
     if (ls != AS_OK) return ls;
     if (!ids_ok) {
         set_err("%s: out of host memory for %lld ids", who, (long long)offs_host[b]);
         return AS_ENOMEM;
     }
-    for (int64_t i = 0; i < b; ++i) {
-        if (out_lambda_q) out_lambda_q[i] = lq[i];
-        if (out_status) out_status[i] = st[i];
-    }
-    const int64_t kk = select ? std::min<int64_t>(gr->gp.topk, sp->n) : 0;
-    int64_t counts[3] = {0, 0, 0};
+    const int64_t kk = select ? hits_bound(sp, gr, sp->n) : 0;
+    const TauSet ts(taus, sweep ? ntau : 0);   // (the one-tau forms: empty, nothing allocated)
+    int64_t counts[4] = {0, 0, 0, 0};
     as_status r;
     {
         std::lock_guard<std::mutex> lk(sp->lmu);
         r = hipSetDevice(sp->device) == hipSuccess ? AS_OK : AS_EHIP;
         if (r != AS_OK) set_err("%s: hipSetDevice failed", who);
-        else r = lists_run(sp, ids.data(), offs.data(), queries, b, lq.data(), st.data(), tau, kk, out_idx, out_score, out_len, out_scores, counts);
+        else if (!sweep)
+            r = lists_run(sp, ids.data(), offs.data(), queries, b, lq.data(), st.data(), taus[0], kk, out_idx, out_score, out_len, out_scores, counts);
+        else
+            r = lists_run_taus(sp, ids.data(), offs.data(), queries, b, lq.data(), st.data(), ts.uniq.data(), ts.size(), ts.row.data(), ntau, kk,
+                               out_idx, out_score, out_len, out_scores, counts);
     }
-    sp->lists_count[1].fetch_add(counts[0], std::memory_order_relaxed);
-    sp->lists_count[2].fetch_add(counts[1], std::memory_order_relaxed);
-    sp->lists_count[4].fetch_add(counts[2], std::memory_order_relaxed);
-    return r;
+    for (int c = 0; c < nwork; ++c) count[1 + c].fetch_add(counts[c], std::memory_order_relaxed);
+    host_ns.fetch_add(counts[nwork], std::memory_order_relaxed);
+    if (r != AS_OK || !sweep) return r;
+    if (select) copy_repeated_lists(ts, b, kk, st.data(), out_idx, out_score, out_len);
+    else copy_repeated_rows(ts, b, 0, offs_host, st.data(), out_scores);
+    return AS_OK;
 }
 
 as_status as_score_lists_batch(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau,
@@ -2109,8 +2140,8 @@ as_status as_score_lists_batch(const as_space* sp, const as_graph* gr, const dou
         set_err("as_score_lists_batch: null argument");
         return AS_EINVAL;
     }
-    return lists_call("as_score_lists_batch", sp, gr, queries, b, d, tau, ids_host, offsets_host, false, nullptr, nullptr, nullptr, out_scores,
-                      out_lambda_q, out_status);
+    return lists_call("as_score_lists_batch", sp, gr, queries, b, d, &tau, 1, false, ids_host, offsets_host, false, nullptr, nullptr, nullptr,
+                      out_scores, out_lambda_q, out_status);
 }
 
 as_status as_search_lists_batch(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau,
@@ -2120,17 +2151,12 @@ as_status as_search_lists_batch(const as_space* sp, const as_graph* gr, const do
         set_err("as_search_lists_batch: null argument");
         return AS_EINVAL;
     }
-    return lists_call("as_search_lists_batch", sp, gr, queries, b, d, tau, ids_host, offsets_host, true, out_idx, out_score, out_len, nullptr,
-                      out_lambda_q, out_status);
+    return lists_call("as_search_lists_batch", sp, gr, queries, b, d, &tau, 1, false, ids_host, offsets_host, true, out_idx, out_score, out_len,
+                      nullptr, out_lambda_q, out_status);
 }
 
 as_status as_lists_counters(const as_space* sp, int64_t* out, int32_t n) {
-    if (!sp || !out) {
-        set_err("as_lists_counters: null argument");
-        return AS_EINVAL;
-    }
-    for (int i = 0; i < n && i < 5; ++i) out[i] = sp->lists_count[i].load(std::memory_order_relaxed);
-    return AS_OK;
+    return counters_out("as_lists_counters", sp, out, n, sp ? sp->lists_count : nullptr, 5);
 }
 
 double as_lists_kernel_us(const as_space* sp) {
@@ -2140,44 +2166,18 @@ double as_lists_kernel_us(const as_space* sp) {
 }
 
 // ---------------------------------------------------------------- tau sweeps over a subset (extension)
-// distinct taus (bit patterns) in order of first appearance: row[u] = the first j with taus[j] == uniq[u], slot[j] = its u
-static void distinct_taus(const double* taus, int64_t ntau, std::vector<double>& uniq, std::vector<int64_t>& row, std::vector<int64_t>& slot) {
-    slot.resize((size_t)ntau);
-    for (int64_t j = 0; j < ntau; ++j) {
-        int64_t u = 0;
-        while (u < (int64_t)uniq.size() && memcmp(&uniq[u], &taus[j], sizeof(double)) != 0) ++u;
-        if (u == (int64_t)uniq.size()) {
-            uniq.push_back(taus[j]);
-            row.push_back(j);
-        }
-        slot[j] = u;
+// The candidates of one sweep; the launches and tau planes the driver wrote into `counts` are counted when it goes.  It lives in
+// a block of its own: the lock is released before the caller copies the repeated taus.
+namespace {
+struct SweepCandidates : Candidates {
+    using Candidates::Candidates;
+    int64_t counts[2] = {0, 0};
+    ~SweepCandidates() {
+        sp->ssweep_count[1].fetch_add(counts[0], std::memory_order_relaxed);
+        sp->ssweep_count[2].fetch_add(counts[1], std::memory_order_relaxed);
     }
-}
-static void sweep_counts_add(const as_space* sp, const int64_t* counts) {
-    sp->ssweep_count[1].fetch_add(counts[0], std::memory_order_relaxed);
-    sp->ssweep_count[2].fetch_add(counts[1], std::memory_order_relaxed);
-}
-// lambda_q of a single sweep: ONE single search with taus[0], hits discarded
-static as_status sweep_lambda(const as_space* sp, const as_graph* gr, const double* query, int64_t d, double tau, double* lq) {
-    sp->ssweep_count[0].fetch_add(1, std::memory_order_relaxed);
-    sp->ssweep_count[3].fetch_add(1, std::memory_order_relaxed);
-    int64_t hidx[SUBSET_TOPK], hlen = 0;
-    double hsc[SUBSET_TOPK];
-    return search_pooled(sp, gr, query, d, tau, hidx, hsc, &hlen, lq);
-}
-static as_status checked_ids(const char* who, const as_space* sp, const int64_t* ids_host, int64_t m, std::vector<int32_t>& ids) {
-    if (m >= (int64_t)1 << 31) {
-        set_err("%s: %lld ids exceed the supported maximum of 2^31 - 1 per call", who, (long long)m);
-        return AS_EUNSUPPORTED;
-    }
-    try {
-        ids.assign(ids_host, ids_host + m);   // (item ids fit 32 bits: space_new refuses n >= 2^31)
-    } catch (const std::bad_alloc&) {
-        set_err("%s: out of host memory for %lld ids", who, (long long)m);
-        return AS_ENOMEM;
-    }
-    return AS_OK;
-}
+};
+}  // namespace
 
 as_status as_search_subset_taus(const as_space* sp, const as_graph* gr, const double* query, int64_t d, const double* taus, int64_t ntau,
                                 const as_subset* sub, int64_t* out_idx, double* out_score, int64_t* out_len, double* out_lambda_q) {
@@ -2186,39 +2186,22 @@ as_status as_search_subset_taus(const as_space* sp, const as_graph* gr, const do
         return AS_EINVAL;
     }
     for (int64_t j = 0; j < ntau; ++j) out_len[j] = 0;
-    if (sub->sp != sp) {
-        set_err("as_search_subset_taus: the subset was made for another space");
-        return AS_EINVAL;
-    }
+    AS_TRY(own_subset("as_search_subset_taus", sp, sub));
     AS_TRY(subset_checks("as_search_subset_taus", sp, gr, d, taus, ntau));
     if (ntau == 0) return AS_OK;
+    sp->ssweep_count[0].fetch_add(1, std::memory_order_relaxed);
     double lq = 0.0;
-    const as_status s = sweep_lambda(sp, gr, query, d, taus[0], &lq);
-    if (out_lambda_q) *out_lambda_q = lq;
-    if (s != AS_OK) return s;
+    AS_TRY(lambda_step(sp, gr, query, d, taus[0], &sp->ssweep_count[3], &lq, out_lambda_q));
     if (sub->m == 0) return AS_OK;
-    const int64_t kk = std::min<int64_t>(std::min<int64_t>(gr->gp.topk, sp->n), sub->m);
-    std::vector<double> uniq;
-    std::vector<int64_t> row, slot;
-    distinct_taus(taus, ntau, uniq, row, slot);
-    int64_t counts[2] = {0, 0};
-    as_status r;
+    const int64_t kk = hits_bound(sp, gr, sub->m);
+    const TauSet ts(taus, ntau);
     {
-        std::lock_guard<std::mutex> lk(sub->mu);
-        r = subset_sweep_run(sp, sub->w, sub->m, query, lq, uniq.data(), (int64_t)uniq.size(), row.data(), kk, out_idx, out_score, out_len,
-                             nullptr, counts);
+        SweepCandidates c("as_search_subset_taus", sp, sub);
+        AS_TRY(c.status);
+        AS_TRY(c.fail(subset_sweep_run(sp, c.w, c.m, query, lq, ts.uniq.data(), ts.size(), ts.row.data(), kk, out_idx, out_score, out_len,
+                                       nullptr, c.counts)));
     }
-    sweep_counts_add(sp, counts);
-    if (r != AS_OK) return r;
-    for (int64_t j = 0; j < ntau; ++j) {   // equal taus: copies of the first one's list
-        const int64_t f = row[slot[j]];
-        if (f == j) continue;
-        for (int64_t t = 0; t < out_len[f]; ++t) {
-            out_idx[j * kk + t] = out_idx[f * kk + t];
-            out_score[j * kk + t] = out_score[f * kk + t];
-        }
-        out_len[j] = out_len[f];
-    }
+    copy_repeated_lists(ts, 1, kk, nullptr, out_idx, out_score, out_len);
     return AS_OK;
 }
 
@@ -2228,50 +2211,23 @@ as_status as_score_items_taus(const as_space* sp, const as_graph* gr, const doub
         set_err("as_score_items_taus: null argument");
         return AS_EINVAL;
     }
-    for (int64_t i = 0; i < m; ++i)
-        if (ids_host[i] < 0 || ids_host[i] >= sp->n) {
-            set_err("as_score_items_taus: id %lld is outside [0, %lld)", (long long)ids_host[i], (long long)sp->n);
-            return AS_EINVAL;
-        }
+    AS_TRY(ids_in_range("as_score_items_taus", sp, ids_host, m));
     AS_TRY(subset_checks("as_score_items_taus", sp, gr, d, taus, ntau));
     if (ntau == 0) return AS_OK;
+    sp->ssweep_count[0].fetch_add(1, std::memory_order_relaxed);
     double lq = 0.0;
-    const as_status s = sweep_lambda(sp, gr, query, d, taus[0], &lq);
-    if (out_lambda_q) *out_lambda_q = lq;
-    if (s != AS_OK) return s;
+    AS_TRY(lambda_step(sp, gr, query, d, taus[0], &sp->ssweep_count[3], &lq, out_lambda_q));
     if (m == 0) return AS_OK;
     std::vector<int32_t> ids;
-    AS_TRY(checked_ids("as_score_items_taus", sp, ids_host, m, ids));
-    std::vector<double> uniq;
-    std::vector<int64_t> row, slot;
-    distinct_taus(taus, ntau, uniq, row, slot);
-    int64_t counts[2] = {0, 0};
-    as_status r;
+    AS_TRY(checked_ids("as_score_items_taus", ids_host, m, ids));
+    const TauSet ts(taus, ntau);
     {
-        std::lock_guard<std::mutex> lk(sp->smu);
-        r = score_ws_ids(sp, ids.data(), m);
-        if (r == AS_OK)
-            r = subset_sweep_run(sp, sp->score_ws, m, query, lq, uniq.data(), (int64_t)uniq.size(), row.data(), 0, nullptr, nullptr, nullptr,
-                                 out_scores, counts);
+        SweepCandidates c("as_score_items_taus", sp, ids.data(), m);
+        AS_TRY(c.status);
+        AS_TRY(c.fail(subset_sweep_run(sp, c.w, m, query, lq, ts.uniq.data(), ts.size(), ts.row.data(), 0, nullptr, nullptr, nullptr, out_scores,
+                                       c.counts)));
     }
-    sweep_counts_add(sp, counts);
-    if (r != AS_OK) return r;
-    for (int64_t j = 0; j < ntau; ++j)
-        if (row[slot[j]] != j) memcpy(out_scores + j * m, out_scores + row[slot[j]] * m, sizeof(double) * (size_t)m);
-    return AS_OK;
-}
-
-// lambda_q and status of every query of a batched sweep: ONE as_search_batch call with taus[0], hits discarded (it has returned,
-// and released sp->bmu, before the caller takes the handle's mutex)
-static as_status batch_sweep_lambda(const char* who, const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d,
-                                    double tau, std::vector<double>& lq, std::vector<int32_t>& st, double* out_lambda_q, int32_t* out_status) {
-    sp->ssweep_count[0].fetch_add(1, std::memory_order_relaxed);
-    sp->ssweep_count[3].fetch_add(1, std::memory_order_relaxed);
-    AS_TRY(batch_lambda_step(who, sp, gr, queries, b, d, tau, lq, st));
-    for (int64_t i = 0; i < b; ++i) {
-        if (out_lambda_q) out_lambda_q[i] = lq[i];
-        if (out_status) out_status[i] = st[i];
-    }
+    copy_repeated_rows(ts, 1, m, nullptr, nullptr, out_scores);
     return AS_OK;
 }
 
@@ -2284,42 +2240,23 @@ as_status as_search_subset_batch_taus(const as_space* sp, const as_graph* gr, co
         return AS_EINVAL;
     }
     for (int64_t p = 0; p < b * ntau; ++p) out_len[p] = 0;
-    if (sub->sp != sp) {
-        set_err("as_search_subset_batch_taus: the subset was made for another space");
-        return AS_EINVAL;
-    }
+    AS_TRY(own_subset("as_search_subset_batch_taus", sp, sub));
     AS_TRY(subset_checks("as_search_subset_batch_taus", sp, gr, d, taus, ntau));
     if (b == 0 || ntau == 0) return AS_OK;
+    sp->ssweep_count[0].fetch_add(1, std::memory_order_relaxed);
     std::vector<double> lq;
     std::vector<int32_t> st;
-    AS_TRY(batch_sweep_lambda("as_search_subset_batch_taus", sp, gr, queries, b, d, taus[0], lq, st, out_lambda_q, out_status));
+    AS_TRY(batch_lambda_step("as_search_subset_batch_taus", sp, gr, queries, b, d, taus[0], &sp->ssweep_count[3], lq, st, out_lambda_q, out_status));
     if (sub->m == 0) return AS_OK;
-    const int64_t kk = std::min<int64_t>(std::min<int64_t>(gr->gp.topk, sp->n), sub->m);
-    std::vector<double> uniq;
-    std::vector<int64_t> row, slot;
-    distinct_taus(taus, ntau, uniq, row, slot);
-    int64_t counts[2] = {0, 0};
-    as_status r;
+    const int64_t kk = hits_bound(sp, gr, sub->m);
+    const TauSet ts(taus, ntau);
     {
-        std::lock_guard<std::mutex> lk(sub->mu);
-        r = hipSetDevice(sp->device) == hipSuccess ? AS_OK : AS_EHIP;
-        if (r != AS_OK) set_err("as_search_subset_batch_taus: hipSetDevice failed");
-        else
-            r = subset_batch_sweep_run(sp, sub->w, sub->m, queries, b, lq.data(), st.data(), uniq.data(), (int64_t)uniq.size(), row.data(), ntau,
-                                       kk, out_idx, out_score, out_len, nullptr, counts);
+        SweepCandidates c("as_search_subset_batch_taus", sp, sub);
+        AS_TRY(c.status);
+        AS_TRY(c.fail(subset_batch_sweep_run(sp, c.w, c.m, queries, b, lq.data(), st.data(), ts.uniq.data(), ts.size(), ts.row.data(), ntau, kk,
+                                             out_idx, out_score, out_len, nullptr, c.counts)));
     }
-    sweep_counts_add(sp, counts);
-    if (r != AS_OK) return r;
-    for (int64_t i = 0; i < b; ++i)
-        for (int64_t j = 0; j < ntau; ++j) {
-            const int64_t f = i * ntau + row[slot[j]], p = i * ntau + j;
-            if (f == p) continue;
-            for (int64_t t = 0; t < out_len[f]; ++t) {
-                out_idx[p * kk + t] = out_idx[f * kk + t];
-                out_score[p * kk + t] = out_score[f * kk + t];
-            }
-            out_len[p] = out_len[f];
-        }
+    copy_repeated_lists(ts, b, kk, nullptr, out_idx, out_score, out_len);
     return AS_OK;
 }
 
@@ -2331,130 +2268,32 @@ as_status as_score_items_batch_taus(const as_space* sp, const as_graph* gr, cons
         set_err("as_score_items_batch_taus: null argument");
         return AS_EINVAL;
     }
-    for (int64_t i = 0; i < m; ++i)
-        if (ids_host[i] < 0 || ids_host[i] >= sp->n) {
-            set_err("as_score_items_batch_taus: id %lld is outside [0, %lld)", (long long)ids_host[i], (long long)sp->n);
-            return AS_EINVAL;
-        }
+    AS_TRY(ids_in_range("as_score_items_batch_taus", sp, ids_host, m));
     AS_TRY(subset_checks("as_score_items_batch_taus", sp, gr, d, taus, ntau));
     if (b == 0 || ntau == 0) return AS_OK;
+    sp->ssweep_count[0].fetch_add(1, std::memory_order_relaxed);
     std::vector<double> lq;
     std::vector<int32_t> st;
-    AS_TRY(batch_sweep_lambda("as_score_items_batch_taus", sp, gr, queries, b, d, taus[0], lq, st, out_lambda_q, out_status));
+    AS_TRY(batch_lambda_step("as_score_items_batch_taus", sp, gr, queries, b, d, taus[0], &sp->ssweep_count[3], lq, st, out_lambda_q, out_status));
     if (m == 0) return AS_OK;
     std::vector<int32_t> ids;
-    AS_TRY(checked_ids("as_score_items_batch_taus", sp, ids_host, m, ids));
-    std::vector<double> uniq;
-    std::vector<int64_t> row, slot;
-    distinct_taus(taus, ntau, uniq, row, slot);
-    int64_t counts[2] = {0, 0};
-    as_status r;
+    AS_TRY(checked_ids("as_score_items_batch_taus", ids_host, m, ids));
+    const TauSet ts(taus, ntau);
     {
-        std::lock_guard<std::mutex> lk(sp->smu);
-        r = hipSetDevice(sp->device) == hipSuccess ? AS_OK : AS_EHIP;
-        if (r != AS_OK) set_err("as_score_items_batch_taus: hipSetDevice failed");
-        if (r == AS_OK) r = score_ws_ids(sp, ids.data(), m);
-        if (r == AS_OK)
-            r = subset_batch_sweep_run(sp, sp->score_ws, m, queries, b, lq.data(), st.data(), uniq.data(), (int64_t)uniq.size(), row.data(), ntau,
-                                       0, nullptr, nullptr, nullptr, out_scores, counts);
+        SweepCandidates c("as_score_items_batch_taus", sp, ids.data(), m);
+        AS_TRY(c.status);
+        AS_TRY(c.fail(subset_batch_sweep_run(sp, c.w, m, queries, b, lq.data(), st.data(), ts.uniq.data(), ts.size(), ts.row.data(), ntau, 0,
+                                             nullptr, nullptr, nullptr, out_scores, c.counts)));
     }
-    sweep_counts_add(sp, counts);
-    if (r != AS_OK) return r;
-    for (int64_t i = 0; i < b; ++i) {
-        if (st[i] == AS_EZEROLAMBDA) continue;   // (its rows stay unwritten)
-        for (int64_t j = 0; j < ntau; ++j)
-            if (row[slot[j]] != j)
-                memcpy(out_scores + (i * ntau + j) * m, out_scores + (i * ntau + row[slot[j]]) * m, sizeof(double) * (size_t)m);
-    }
+    copy_repeated_rows(ts, b, m, nullptr, st.data(), out_scores);
     return AS_OK;
 }
 
 as_status as_subset_sweep_counters(const as_space* sp, int64_t* out, int32_t n) {
-    if (!sp || !out) {
-        set_err("as_subset_sweep_counters: null argument");
-        return AS_EINVAL;
-    }
-    for (int i = 0; i < n && i < 4; ++i) out[i] = sp->ssweep_count[i].load(std::memory_order_relaxed);
-    return AS_OK;
+    return counters_out("as_subset_sweep_counters", sp, out, n, sp ? sp->ssweep_count : nullptr, 4);
 }
 
 // ---------------------------------------------------------------- tau sweeps over per-query lists (extension)
-// lists_call with a list of taus: the same checks before anything is launched (every tau finite), ONE lambda_q step with taus[0]
-// beside the helper thread's deduplication, the distinct taus through lists_run_taus under sp->lmu, repeated taus copied here.
-static as_status lists_taus_call(const char* who, const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d,
-                                 const double* taus, int64_t ntau, const int64_t* ids_host, const int64_t* offs_host, bool select,
-                                 int64_t* out_idx, double* out_score, int64_t* out_len, double* out_scores, double* out_lambda_q,
-                                 int32_t* out_status) {
-    AS_TRY(subset_checks(who, sp, gr, d, taus, ntau));
-    auto t0 = std::chrono::steady_clock::now();
-    AS_TRY(lists_checks(who, sp, ids_host, offs_host, b));
-    sp->lsweep_count[5].fetch_add(host_ns_since(t0), std::memory_order_relaxed);
-    sp->lsweep_count[0].fetch_add(1, std::memory_order_relaxed);
-    if (b == 0 || ntau == 0) return AS_OK;
-    std::vector<int32_t> ids;
-    std::vector<int64_t> offs;
-    bool ids_ok = true;
-    std::thread helper;
-    try {
-        helper = std::thread([&] { ids_ok = lists_ids32(sp, ids_host, offs_host, b, select, ids, offs); });
-    } catch (const std::system_error&) {   // no thread to be had: in line
-        ids_ok = lists_ids32(sp, ids_host, offs_host, b, select, ids, offs);
-    }
-    std::vector<double> lq;
-    std::vector<int32_t> st;
-    sp->lsweep_count[4].fetch_add(1, std::memory_order_relaxed);
-    const as_status ls = batch_lambda_step(who, sp, gr, queries, b, d, taus[0], lq, st);
-    t0 = std::chrono::steady_clock::now();
-    if (helper.joinable()) helper.join();
-    sp->lsweep_count[5].fetch_add(host_ns_since(t0), std::memory_order_relaxed);
-    if (ls != AS_OK) return ls;
-    if (!ids_ok) {
-        set_err("%s: out of host memory for %lld ids", who, (long long)offs_host[b]);
-        return AS_ENOMEM;
-    }
-    for (int64_t i = 0; i < b; ++i) {
-        if (out_lambda_q) out_lambda_q[i] = lq[i];
-        if (out_status) out_status[i] = st[i];
-    }
-    const int64_t kk = select ? std::min<int64_t>(gr->gp.topk, sp->n) : 0;
-    std::vector<double> uniq;
-    std::vector<int64_t> row, slot;
-    distinct_taus(taus, ntau, uniq, row, slot);
-    int64_t counts[4] = {0, 0, 0, 0};
-    as_status r;
-    {
-        std::lock_guard<std::mutex> lk(sp->lmu);
-        r = hipSetDevice(sp->device) == hipSuccess ? AS_OK : AS_EHIP;
-        if (r != AS_OK) set_err("%s: hipSetDevice failed", who);
-        else
-            r = lists_run_taus(sp, ids.data(), offs.data(), queries, b, lq.data(), st.data(), uniq.data(), (int64_t)uniq.size(), row.data(), ntau,
-                               kk, out_idx, out_score, out_len, out_scores, counts);
-    }
-    for (int c = 0; c < 3; ++c) sp->lsweep_count[1 + c].fetch_add(counts[c], std::memory_order_relaxed);
-    sp->lsweep_count[5].fetch_add(counts[3], std::memory_order_relaxed);
-    if (r != AS_OK || uniq.size() == (size_t)ntau) return r;
-    for (int64_t i = 0; i < b; ++i) {   // equal taus: copies of the first one's list / row
-        if (st[i] == AS_EZEROLAMBDA) continue;   // (nothing of it was written)
-        const int64_t m = offs_host[i + 1] - offs_host[i];
-        for (int64_t j = 0; j < ntau; ++j) {
-            const int64_t fj = row[slot[j]];
-            if (fj == j) continue;
-            if (select) {
-                const int64_t f = i * ntau + fj, p = i * ntau + j;
-                for (int64_t t = 0; t < out_len[f]; ++t) {
-                    out_idx[p * kk + t] = out_idx[f * kk + t];
-                    out_score[p * kk + t] = out_score[f * kk + t];
-                }
-                out_len[p] = out_len[f];
-            } else if (m > 0) {
-                double* blk = out_scores + ntau * offs_host[i];
-                memcpy(blk + j * m, blk + fj * m, sizeof(double) * (size_t)m);
-            }
-        }
-    }
-    return AS_OK;
-}
-
 as_status as_score_lists_batch_taus(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, const double* taus,
                                     int64_t ntau, const int64_t* ids_host, const int64_t* offsets_host, double* out_scores,
                                     double* out_lambda_q, int32_t* out_status) {
@@ -2463,8 +2302,8 @@ as_status as_score_lists_batch_taus(const as_space* sp, const as_graph* gr, cons
         set_err("as_score_lists_batch_taus: null argument");
         return AS_EINVAL;
     }
-    return lists_taus_call("as_score_lists_batch_taus", sp, gr, queries, b, d, taus, ntau, ids_host, offsets_host, false, nullptr, nullptr,
-                           nullptr, out_scores, out_lambda_q, out_status);
+    return lists_call("as_score_lists_batch_taus", sp, gr, queries, b, d, taus, ntau, true, ids_host, offsets_host, false, nullptr, nullptr,
+                      nullptr, out_scores, out_lambda_q, out_status);
 }
 
 as_status as_search_lists_batch_taus(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, const double* taus,
@@ -2475,17 +2314,12 @@ as_status as_search_lists_batch_taus(const as_space* sp, const as_graph* gr, con
         set_err("as_search_lists_batch_taus: null argument");
         return AS_EINVAL;
     }
-    return lists_taus_call("as_search_lists_batch_taus", sp, gr, queries, b, d, taus, ntau, ids_host, offsets_host, true, out_idx, out_score,
-                           out_len, nullptr, out_lambda_q, out_status);
+    return lists_call("as_search_lists_batch_taus", sp, gr, queries, b, d, taus, ntau, true, ids_host, offsets_host, true, out_idx, out_score,
+                      out_len, nullptr, out_lambda_q, out_status);
 }
 
 as_status as_lists_sweep_counters(const as_space* sp, int64_t* out, int32_t n) {
-    if (!sp || !out) {
-        set_err("as_lists_sweep_counters: null argument");
-        return AS_EINVAL;
-    }
-    for (int i = 0; i < n && i < 6; ++i) out[i] = sp->lsweep_count[i].load(std::memory_order_relaxed);
-    return AS_OK;
+    return counters_out("as_lists_sweep_counters", sp, out, n, sp ? sp->lsweep_count : nullptr, 6);
 }
 
 // One batched tau sweep over b > 1 queries for nt <= TAU_GROUP distinct taus in [0, 1] (under sp->bmu): as_search_batch's
@@ -2622,12 +2456,7 @@ as_status as_search_batch_taus(const as_space* sp, const as_graph* gr, const dou
 }
 
 as_status as_batch_sweep_counters(const as_space* sp, int64_t* out, int32_t n) {
-    if (!sp || !out) {
-        set_err("as_batch_sweep_counters: null argument");
-        return AS_EINVAL;
-    }
-    for (int i = 0; i < n && i < 4; ++i) out[i] = sp->bsweep_count[i].load(std::memory_order_relaxed);
-    return AS_OK;
+    return counters_out("as_batch_sweep_counters", sp, out, n, sp ? sp->bsweep_count : nullptr, 4);
 }
 
 // ---------------------------------------------------------------- accessors
