@@ -479,7 +479,9 @@ void as_enable_search_stats(int32_t enabled);
  * "diverse_chunk" = queries per launch of the diversified forms (default 4096; <= 0: the default); "diverse_timing" = 1 / 0: HIP
  * events around their select kernel (as_diverse_kernel_us).  "fused_timing" = 1 / 0: HIP events around the fused forms'
  * accumulate kernel (as_fused_kernel_us).  "grouped_timing" = 1 / 0: HIP events around the grouped forms' pick kernels
- * (as_grouped_kernel_us).
+ * (as_grouped_kernel_us).  "filtered_grid_cap" = v > 0: gridDim.x of the filtered family's stride-loop kernels (the gather score
+ * kernels of the subset and list forms, the radix select's passes, the fused fold, the grouped picks, the range compaction) is
+ * clipped to at most v blocks, so tests reach the later trips of those loops at small shapes; 0 (default): no clip.
  * Returns 0, or 1 for an unknown key.  Results never depend on it. */
 int32_t as_set_tuning(const char* key, int32_t value);
 /* same, for the workspace as_search keeps inside the space (last as_search call) */

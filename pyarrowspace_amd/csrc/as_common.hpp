@@ -775,6 +775,12 @@ as_status subset_batch_run(const as_space* sp, SubsetWork* w, int64_t m, const d
                            const int32_t* status, double tau, int64_t k, int64_t stride, int64_t* out_idx, double* out_score,
                            int64_t* out_len, double* out_scores, const SubsetChunkSink* sink = nullptr);
 void set_subset_batch_mib(int v);   // as_set_tuning("subset_batch_mib", v)
+// as_set_tuning("filtered_grid_cap", v): v > 0 clips gridDim.x of the filtered family's stride-loop kernels (the gather score
+// kernels, the radix select's passes, the lists' segments, the fused fold, the grouped picks, the range compaction) to at most v
+// blocks, so that tests drive the later trips of those loops at small shapes; 0 (the default): every grid is what its call site
+// computes.  Results never depend on it.
+void set_filtered_grid_cap(int v);
+int64_t filtered_grid(int64_t blocks);   // the grid a call site computed, under the cap
 // The selection over ONE row of m scores that lie anywhere on the device (the positions are those of the work's ids), queued on
 // the work's stream behind whatever wrote them: the first k by (score descending, position ascending) -> ids and scores; waits for
 // the stream.

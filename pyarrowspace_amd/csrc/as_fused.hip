@@ -158,7 +158,7 @@ as_status fused_chunk(FusedCall* c, int64_t i0, int64_t nb, const double* scores
     if (served == 0 || c->m <= 0) return AS_OK;
     AS_TRY(fused_collect_time(c));
     const int64_t units = (c->m + 1) / 2;
-    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((units + FA_THREADS - 1) / FA_THREADS, (int64_t)w->cus * FA_BLOCKS_PER_CU));
+    const unsigned grid = (unsigned)filtered_grid(std::max<int64_t>(1, std::min<int64_t>((units + FA_THREADS - 1) / FA_THREADS, (int64_t)w->cus * FA_BLOCKS_PER_CU)));
     const double* wts = f->par + i0;
     const int32_t* flags = (const int32_t*)((const double*)f->par + f->j) + i0;
     double* acc = f->acc;

@@ -200,7 +200,7 @@ int64_t grouped_row_bytes(const as_groups* g, int64_t m, int64_t n_groups, int64
 }
 
 static unsigned pick_grid(const SubsetWork* w, int64_t m) {
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((m + GP_THREADS - 1) / GP_THREADS, (int64_t)w->cus * GP_BLOCKS_PER_CU));
+    return (unsigned)filtered_grid(std::max<int64_t>(1, std::min<int64_t>((m + GP_THREADS - 1) / GP_THREADS, (int64_t)w->cus * GP_BLOCKS_PER_CU)));
 }
 
 template <bool ROUND0>

@@ -402,7 +402,7 @@ as_status lists_run(const as_space* sp, const int32_t* ids, const int64_t* offs,
             a.segs = (const ListsSeg*)(up_d + seg_off); a.nseg = nseg; a.ids = (const int32_t*)(up_d + ids_off);
             a.x32 = sp->x32; a.x64 = sp->x64; a.n64 = sp->n64; a.lam64 = sp->lam64; a.q64 = (const double*)up_d;
             a.nq = a.q64 + nb * dp; a.lq = a.nq + nb; a.scores = w->scores; a.d = d; a.dp = dp; a.tau = tau;
-            const unsigned grid = (unsigned)std::min<int64_t>(nseg, (int64_t)w->cus * LISTS_BLOCKS_PER_CU);
+            const unsigned grid = (unsigned)filtered_grid(std::min<int64_t>(nseg, (int64_t)w->cus * LISTS_BLOCKS_PER_CU));
             if (timing) AS_HIP(hipEventRecord(w->ev.e[0], w->stream));
             if (sp->x64) {
                 if (qlds) hipLaunchKernelGGL((lists_score_kernel<true, true, ListsArgs>), dim3(grid), dim3(256), lds, w->stream, a);
@@ -527,7 +527,7 @@ as_status lists_run_taus(const as_space* sp, const int32_t* ids, const int64_t* 
             a.s.x32 = sp->x32; a.s.x64 = sp->x64; a.s.n64 = sp->n64; a.s.lam64 = sp->lam64; a.s.q64 = (const double*)up_d;
             a.s.nq = a.s.q64 + nb * dp; a.s.lq = a.s.nq + nb; a.s.scores = w->scores; a.s.d = d; a.s.dp = dp; a.s.tau = 0.0;
             a.segs = (const ListsTausSeg*)(up_d + seg_off);
-            const unsigned grid = (unsigned)std::min<int64_t>(nseg, (int64_t)w->cus * LISTS_BLOCKS_PER_CU);
+            const unsigned grid = (unsigned)filtered_grid(std::min<int64_t>(nseg, (int64_t)w->cus * LISTS_BLOCKS_PER_CU));
             for (int64_t u0 = 0; u0 < nt; u0 += tg) {
                 const int64_t g = std::min<int64_t>(tg, nt - u0);   // taus of this group: planes of every list's block
                 a.nt = (int)g;

@@ -168,7 +168,7 @@ as_status range_compact(SubsetWork* w, const double* scores, int64_t ld, int64_t
     }
     AS_HIP(hipMemcpyAsync(r->thr, r->hthr, sizeof(double) * (size_t)nq, hipMemcpyHostToDevice, w->stream));
     const int64_t trips = (m + 1 + RC_TRIP - 1) / RC_TRIP;
-    const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(trips, std::max<int64_t>(1, RC_BLOCKS / nq))), (unsigned)nq);
+    const dim3 grid((unsigned)filtered_grid(std::max<int64_t>(1, std::min<int64_t>(trips, std::max<int64_t>(1, RC_BLOCKS / nq)))), (unsigned)nq);
     const size_t cnt_bytes = sizeof(unsigned long long) * (size_t)(count_only ? nq + 1 : 1);
     auto launch = [&](int64_t c) -> as_status {
         RangeEntry* buf = r->buf;

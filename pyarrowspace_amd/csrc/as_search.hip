@@ -3635,6 +3635,10 @@ int32_t as_set_tuning(const char* key, int32_t value) {
         set_lists_timing(value);
         return 0;
     }
+    if (key && !strcmp(key, "filtered_grid_cap")) {
+        set_filtered_grid_cap(value);
+        return 0;
+    }
     if (key && !strcmp(key, "range_cap")) {
         set_range_cap(value);
         return 0;

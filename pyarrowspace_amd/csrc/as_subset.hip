@@ -14,6 +14,13 @@ namespace as {
 
 constexpr int SUB_BLOCKS_PER_CU = 4;   // 4 blocks of 4 waves: 16 waves per CU
 
+static std::atomic<int> g_filtered_grid_cap{0};
+void set_filtered_grid_cap(int v) { g_filtered_grid_cap.store(v > 0 ? v : 0, std::memory_order_relaxed); }
+int64_t filtered_grid(int64_t blocks) {
+    const int64_t cap = g_filtered_grid_cap.load(std::memory_order_relaxed);
+    return cap > 0 ? std::min<int64_t>(blocks, cap) : blocks;
+}
+
 struct SubsetArgs {
     const int32_t* ids;
     int64_t m;
@@ -488,7 +495,7 @@ as_status subset_score(const as_space* sp, SubsetWork* w, int64_t m, const doubl
     a.ids = w->ids; a.m = m; a.x32 = sp->x32; a.x64 = sp->x64; a.n64 = sp->n64; a.lam64 = sp->lam64; a.q64 = w->qd;
     a.scores = w->scores; a.d = sp->d; a.dp = sp->dp; a.nq = w->qh[w->dp]; a.lq = lambda_q; a.tau = tau;
     const int64_t groups = (m + GATHER_ROWS - 1) / GATHER_ROWS;   // one per wave and trip
-    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((groups + 3) / 4, (int64_t)w->cus * SUB_BLOCKS_PER_CU));
+    const unsigned grid = (unsigned)filtered_grid(std::max<int64_t>(1, std::min<int64_t>((groups + 3) / 4, (int64_t)w->cus * SUB_BLOCKS_PER_CU)));
     const bool qlds = sp->dp <= GATHER_Q_LDS;
     const size_t lds = qlds ? sizeof(double) * (size_t)sp->dp : 0;
     if (w->timing) AS_HIP(hipEventRecord(w->ev[0], w->stream));
@@ -524,7 +531,7 @@ static as_status subset_select_rows(SubsetWork* w, const double* scores, int64_t
         SubsetSel* state = w->state;
         int32_t* sel_pos = w->sel_pos;
         AS_HIP(hipMemsetAsync(hist, 0, sizeof(unsigned int) * SEL_HIST_WORDS * (size_t)rows, w->stream));
-        const unsigned gx = (unsigned)std::min<int64_t>((m + 2047) / 2048, 512);
+        const unsigned gx = (unsigned)filtered_grid(std::min<int64_t>((m + 2047) / 2048, 512));
         for (int p = 0; p < SEL_PASSES; ++p)
             hipLaunchKernelGGL(subset_hist_batch_kernel, dim3(gx, ny), dim3(256), 0, w->stream, scores, ld, m, (int)k, p, state, hist);
         hipLaunchKernelGGL(subset_collect_batch_kernel, dim3(gx, ny), dim3(256), 0, w->stream, scores, ld, m, (int)k, state, hist, sel_pos);
@@ -668,7 +675,7 @@ as_status subset_sweep_run(const as_space* sp, SubsetWork* w, int64_t m, const d
     a.s.scores = w->scores; a.s.d = sp->d; a.s.dp = sp->dp; a.s.nq = w->qh[w->dp]; a.s.lq = lambda_q; a.s.tau = 0.0;
     a.ld = m;
     const int64_t groups = (m + GATHER_ROWS - 1) / GATHER_ROWS;   // (the grid of subset_score)
-    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((groups + 3) / 4, (int64_t)w->cus * SUB_BLOCKS_PER_CU));
+    const unsigned grid = (unsigned)filtered_grid(std::max<int64_t>(1, std::min<int64_t>((groups + 3) / 4, (int64_t)w->cus * SUB_BLOCKS_PER_CU)));
     const bool qlds = sp->dp <= GATHER_Q_LDS;
     const size_t lds = qlds ? sizeof(double) * (size_t)sp->dp : 0;
     w->kernel_us = 0.0;

@@ -235,6 +235,47 @@ def test_a_run_of_equal_scores_across_the_threshold_of_the_radix_select():
     assert len({s for _, s in got}) == 1
 
 
+WIDE_RUNS = [(3800, 4400, 300), (3900, 5000, 1024)]
+
+
+def wide_tie_run(first, last, topk):
+    """5000 items, ids first .. last - 1 copies of 0.5 x row 20, the query 1.01 x row 20: at tau = 1 the winners are 20 and the
+    run's first topk - 1.  The threshold lies inside the run AND the run crosses position 4096, where digit 6 of the key (bits
+    12 .. 23 of ~position) changes: that pass of the radix select, not only the last, has to pick a digit by rank.  600 ties fit
+    the 1024 entries the final sort ranks, so a threshold found too low would be put right there; 1100 ties with topk = 1024 do
+    not fit, and every entry the collection drops is missed."""
+    import pyarrowspace_amd as asp
+    n, d = 5000, 32
+    X = clustered(n, d, nclust=16, seed=22)
+    gp = {"eps": calibrate_eps(X, 6), "k": 6, "topk": topk, "p": 2.0, "sigma": None}   # (before the copies: their distances are 0)
+    X[first:last] = 0.5 * X[20]
+    aspace, gl = asp.ArrowSpaceBuilder.build(gp, X)
+    q = np.ascontiguousarray(X[20] * 1.01)
+    assert aspace.query_lambda(q, gl) != 0.0
+    return aspace, gl, X, q, [20] + list(range(first, first + topk - 1))
+
+
+@pytest.mark.parametrize("first,last,topk", WIDE_RUNS)
+def test_a_run_of_equal_scores_that_reaches_the_position_digits(first, last, topk):
+    aspace, gl, X, q, winners = wide_tie_run(first, last, topk)
+    n = X.shape[0]
+    every = np.arange(n)
+    s = aspace.score_items(q, gl, 1.0, [20, first, 4095, 4096, last - 1])
+    assert len(set(s.view(np.uint64).tolist())) == 1 and s[0] > np.delete(aspace.score_items(q, gl, 1.0, every), [20] + list(range(first, last))).max()
+    forms = {"search_subset": aspace.search_subset(q, gl, 1.0, every),
+             "search_batch_lists": aspace.search_batch_lists(q[None, :], gl, 1.0, [every])[0],
+             "search_batch_lists, descending": aspace.search_batch_lists(q[None, :], gl, 1.0, [every[::-1].copy()])[0],   # the winners come last
+             "search_fused": aspace.search_fused(q[None, :], gl, 1.0, weights=[1.0], subset=every)}
+    for form, got in forms.items():
+        assert [i for i, _ in got] == winners, form
+        assert len({np.float64(v).view(np.uint64).item() for _, v in got}) == 1, form
+    # without the head and the run's first 200 the run starts at position first - 1 of the subset: it crosses 4096 again, and
+    # the next 300 ids win
+    if last - first - 200 >= topk:
+        got = aspace.search_subset(q, gl, 1.0, np.delete(every, [20] + list(range(first, first + 200))))
+        assert [i for i, _ in got] == list(range(first + 200, first + 200 + topk)) and len({v for _, v in got}) == 1
+
+
 @pytest.mark.parametrize("topk", [1024, 1])
 def test_topk_edges(topk):
     import pyarrowspace_amd as asp

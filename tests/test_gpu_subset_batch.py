@@ -268,6 +268,27 @@ def test_a_run_of_equal_scores_across_the_threshold_of_the_radix_select():
     assert got[0] == got[2] == got[4]
 
 
+@pytest.mark.parametrize("first,last,topk", [(3800, 4400, 300), (3900, 5000, 1024)])
+def test_a_run_of_equal_scores_that_reaches_the_position_digits(first, last, topk):
+    """test_gpu_subset.py's wide runs (600 ties at ids 3800 .. 4399 with topk = 300, 1100 at 3900 .. 4999 with topk = 1024): the
+    threshold lies inside the run and the run crosses position 4096, so digit 6 of the key decides -- in every row of the batched
+    selection."""
+    from test_gpu_subset import wide_tie_run
+    aspace, gl, X, q, winners = wide_tie_run(first, last, topk)
+    n = X.shape[0]
+    other = np.ascontiguousarray(X[77] * 1.01)
+    Q = np.stack([q, other, q])
+    assert aspace.query_lambda(other, gl) != 0.0
+    got = aspace.search_batch_subset(Q, gl, 1.0, np.arange(n))
+    for c in (0, 2):
+        assert [i for i, _ in got[c]] == winners
+        assert len({np.float64(v).view(np.uint64).item() for _, v in got[c]}) == 1
+    assert got[0] == got[2] and got[1] != got[0]
+    S = aspace.score_items_batch(Q, gl, 1.0, np.arange(n))
+    order = np.lexsort((np.arange(n), -(S[1] + 0.0)))[:topk]
+    assert [i for i, _ in got[1]] == order.tolist()
+
+
 # ---------------------------------------------------------------- 8. score_items_batch
 @pytest.mark.parametrize("f32", [False, True], ids=["x64", "x32"])
 def test_score_items_batch(f32):
