@@ -479,7 +479,9 @@ void as_enable_search_stats(int32_t enabled);
  * "diverse_chunk" = queries per launch of the diversified forms (default 4096; <= 0: the default); "diverse_timing" = 1 / 0: HIP
  * events around their select kernel (as_diverse_kernel_us).  "fused_timing" = 1 / 0: HIP events around the fused forms'
  * accumulate kernel (as_fused_kernel_us).  "grouped_timing" = 1 / 0: HIP events around the grouped forms' pick kernels
- * (as_grouped_kernel_us).  "filtered_grid_cap" = v > 0: gridDim.x of the filtered family's stride-loop kernels (the gather score
+ * (as_grouped_kernel_us).  "fused_batch_timing" = 1 / 0: HIP events around the batched fused forms' accumulate kernel
+ * (as_fused_batch_kernel_us); "fused_batch_mib" = MiB of accumulator rows one group of needs of those forms may hold (default
+ * 256; 0: the default; v < 0: -v KiB, so that tests reach several groups at small shapes).  "filtered_grid_cap" = v > 0: gridDim.x of the filtered family's stride-loop kernels (the gather score
  * kernels of the subset and list forms, the radix select's passes, the fused fold, the grouped picks, the range compaction) is
  * clipped to at most v blocks, so tests reach the later trips of those loops at small shapes; 0 (default): no clip.
  * Returns 0, or 1 for an unknown key.  Results never depend on it. */
@@ -756,6 +758,42 @@ as_status as_fused_counters(const as_space* sp, int64_t* out, int32_t n);
 /* measurement: the device microseconds of the accumulate kernel, summed over the chunks of the last fused call on this space that
  * ran under as_set_tuning("fused_timing", 1) (HIP events around the kernel; off by default) */
 double as_fused_kernel_us(const as_space* sp);
+/* ---- Extension: batched fused search.  b >= 1 NEEDS in one call: need y is the vectors offsets[y] ..
+ * offsets[y + 1] - 1 of the nv flattened query vectors ([nv][d], HOST memory), J_y = offsets[y + 1] - offsets[y] >= 1 of them, with
+ * the flattened finite weights weights[nv] (NULL: 1/J_y each inside need y).  offsets: int64 [b + 1], starts at 0, increases
+ * strictly, ends at nv.  tau, mode, skip_zero and the subset / the ids are common to the call.  The per-vector scores are the
+ * bits as_score_items_batch writes for the nv vectors (lambda_q of every vector from ONE as_search_batch over all nv); need y's F
+ * is the fold of as_search_fused over ITS rows, ascending, every product and sum rounded once.  b == 1 is as_search_fused /
+ * as_score_fused bit for bit.
+ * A vector whose lambda_q is 0: skip_zero == 0: the whole call returns AS_EZEROLAMBDA before any gather is launched and no answer
+ * is written; skip_zero != 0: it is left out of its need (the other weights are not renormalised); a need with no vector left is
+ * not served -- out_len[y] = 0 / a row of NaN -- and the call still returns AS_OK, also when no need at all is served (nothing is
+ * launched then).  out_status ([b], may be NULL): 0 or AS_EZEROLAMBDA per NEED (skip_zero == 0: a need that holds such a
+ * vector); out_lambda_q ([nv], may be NULL): per flattened vector; both are written whenever the lambda_q step ran.
+ * as_search_fused_batch: need y's first min(topk', |sub|) items by (F descending, index ascending) -> out_idx / out_score +
+ * y * hits_bound, out_len[y], hits_bound = min(topk, nitems, |sub|) (sub == NULL: every item).  as_score_fused_batch: F of every
+ * listed id -> out_scores[y * m + i], the caller's order, duplicates kept.
+ * Checked before any handle is touched, with nothing written: a null argument ("<name>: null argument"), b < 1, offsets that do
+ * not start at 0, increase strictly and end at nv -> AS_EINVAL.  Then as as_search_fused: mode, weights, the subset's space, d,
+ * tau, ids -> AS_EINVAL; a shard of a row-sharded index -> AS_EUNSUPPORTED.
+ * Cost: ONE as_search_batch over the nv vectors; then the needs are taken G at a time, G = the accumulator rows of m doubles that
+ * fit the "fused_batch_mib" budget (1 <= G <= 4096): the group's vectors go through the batched filtered forms' gather and fp64
+ * matrix product as ONE list of rows in chunks under "subset_batch_mib", ONE segmented accumulate kernel per chunk folds every
+ * need's rows of the chunk into that need's accumulator row, and after the group's last chunk one batched exact selection (the
+ * search form) or one copy of the rows (the score form) follows.  Answers never depend on G, the chunks or the grid.  The
+ * buffers are those of the single forms. */
+as_status as_search_fused_batch(const as_space* sp, const as_graph* gr, const double* queries, const int64_t* offsets, int64_t b, int64_t nv,
+                                int64_t d, double tau, const double* weights, int32_t mode, int32_t skip_zero, const as_subset* sub,
+                                int64_t* out_idx, double* out_score, int64_t* out_len, double* out_lambda_q, int32_t* out_status);
+as_status as_score_fused_batch(const as_space* sp, const as_graph* gr, const double* queries, const int64_t* offsets, int64_t b, int64_t nv,
+                               int64_t d, double tau, const double* weights, int32_t mode, int32_t skip_zero, const int64_t* ids_host,
+                               int64_t m, double* out_scores, double* out_lambda_q, int32_t* out_status);
+/* out[0] calls of the two entries above that passed their checks, [1] needs of those calls, [2] accumulate launches, [3] scores
+ * folded (served rows x m), [4] lambda_q steps run (one per call), [5] need groups run */
+as_status as_fused_batch_counters(const as_space* sp, int64_t* out, int32_t n);
+/* measurement: the device microseconds of the segmented accumulate kernel, summed over the chunks of the last batched fused call
+ * on this space that ran under as_set_tuning("fused_batch_timing", 1) (HIP events around the kernel; off by default) */
+double as_fused_batch_kernel_us(const as_space* sp);
 /* ---- Extension: grouped search.  The best items of the best groups.  as_groups_create: one int64 label per item
  * of the space (labels[n], n == nitems, HOST memory, any values; equal labels = one group) -> a handle; the labels are turned into
  * dense group numbers (ascending label) on the host and uploaded once.  as_groups_count: distinct labels.

@@ -306,6 +306,69 @@ def _fused_args(items, gl, weights, mode, on_zero_lambda):
     return Q, w, FUSED_MODES[mode], 1 if on_zero_lambda == "skip" else 0
 
 
+def _fused_batch_args(needs, gl, weights, mode, on_zero_lambda):
+    """What the batched fused forms check before they touch a handle: `_fused_args`' checks, need by need, the message naming
+    the need -> (V float64 [sum J_b, D] contiguous: the vectors flattened in need order, offsets int64 [B + 1], weights float64
+    [sum J_b] or None (a need whose entry is None gets 1/J_b each), mode number, skip flag).  TypeError: a `gl` that is no
+    GraphLaplacian, a need that is not 2-D, weights that are not numbers; ValueError: no needs, an empty need, a wrong weight
+    count, a NaN or infinite weight, needs of differing D, an unknown mode or on_zero_lambda."""
+    _need_gl(gl)
+    if not isinstance(mode, str) or mode not in FUSED_MODES:
+        raise ValueError(f"argument 'mode': expected 'sum' or 'max', got {mode!r}")
+    if not isinstance(on_zero_lambda, str) or on_zero_lambda not in ("raise", "skip"):
+        raise ValueError(f"argument 'on_zero_lambda': expected 'raise' or 'skip', got {on_zero_lambda!r}")
+    if isinstance(needs, np.ndarray) and needs.ndim != 3:
+        raise TypeError(f"argument 'needs': expected a 3-D array (B, J, D) or a sequence of B 2-D arrays, got shape {needs.shape}")
+    if isinstance(needs, (str, bytes)) or not hasattr(needs, "__iter__"):
+        raise TypeError("argument 'needs': expected a 3-D array (B, J, D) or a sequence of B 2-D arrays")
+    seq = list(needs)
+    if not seq:
+        raise ValueError("needs must hold at least one need")
+    mats = []
+    for b, need in enumerate(seq):
+        try:
+            Q = np.ascontiguousarray(need, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise TypeError(f"need {b} must be a 2-D float64 array") from None
+        if Q.ndim != 2:
+            raise TypeError(f"need {b} must be a 2-D float64 array, got shape {Q.shape}")
+        if Q.shape[0] < 1:
+            raise ValueError(f"need {b} must hold at least one query vector")
+        if mats and Q.shape[1] != mats[0].shape[1]:
+            raise ValueError(f"need {b} has D = {Q.shape[1]}, need 0 has D = {mats[0].shape[1]}: every need must have the same D")
+        mats.append(Q)
+    offs = np.zeros(len(mats) + 1, dtype=np.int64)
+    np.cumsum([Q.shape[0] for Q in mats], out=offs[1:])
+    w = None
+    if weights is not None:
+        if isinstance(weights, (str, bytes)):
+            raise TypeError("argument 'weights': expected one sequence of floats per need")
+        if not hasattr(weights, "__iter__"):
+            raise ValueError(f"argument 'weights': expected {len(mats)} entries, one per need, got {weights!r}")
+        wl = list(weights)
+        if len(wl) != len(mats):
+            raise ValueError(f"argument 'weights': expected {len(mats)} entries, one per need, got {len(wl)}")
+        parts = []
+        for b, (Q, wb) in enumerate(zip(mats, wl)):
+            j = Q.shape[0]
+            if wb is None:
+                parts.append(np.full(j, 1.0 / j))
+                continue
+            wb = np.asarray(wb)
+            if wb.dtype.kind not in "fiu":
+                raise TypeError(f"argument 'weights': need {b}: expected a sequence of floats, got dtype {wb.dtype}")
+            wb = np.ascontiguousarray(wb, dtype=np.float64)
+            if wb.ndim != 1 or wb.shape[0] != j:
+                raise ValueError(f"argument 'weights': need {b}: expected {j} weights, one per query vector, got shape {wb.shape}")
+            if not np.isfinite(wb).all():
+                raise ValueError(f"argument 'weights': need {b}: a weight must be finite")
+            parts.append(wb)
+        if any(wb is not None for wb in wl):
+            w = np.ascontiguousarray(np.concatenate(parts), dtype=np.float64)
+    V = np.ascontiguousarray(np.concatenate(mats, axis=0), dtype=np.float64)
+    return V, offs, w, FUSED_MODES[mode], 1 if on_zero_lambda == "skip" else 0
+
+
 def _id_lists(lists, nitems: int) -> tuple[np.ndarray, np.ndarray]:
     """B id lists as (ids int64 flat, offsets int64 [B + 1]): a 2-D integer array (B, C) is B lists of C ids; any other
     sequence holds one entry per list, each whatever `_item_ids` accepts (integer ids in any order, duplicates kept, or a
@@ -785,6 +848,54 @@ class ArrowSpace:
         """Extension: [0] fused calls on this space that passed their checks, [1] accumulate launches, [2] scores folded
         (served vectors x items), [3] lambda_q steps run."""
         return list(_counters(_L.as_fused_counters, self._h, ("calls", "launches", "folded", "lambda_steps")).values())
+
+    def search_fused_batch(self, needs, gl: GraphLaplacian, tau: float, weights=None, mode="sum", subset=None, on_zero_lambda="raise"):
+        """Extension: batched fused search, B needs of J_b query vectors each in ONE call -> list of B lists[(index, score)];
+        list b is the fused answer of need b: the first min(topk, |subset|) items by (F descending, index ascending), F the
+        fold of `search_fused` over need b's own vectors.  `needs`: a 3-D array (B, J, D), or a sequence of B 2-D arrays
+        (J_b, D), the J_b may differ.  `weights`: None (1/J_b each), a (B, J) array, or a sequence of B 1-D sequences of J_b
+        finite numbers, a None entry meaning the default for that need.  tau, mode, subset and on_zero_lambda are common to
+        the call.  With V the vectors of all needs flattened in need order, the per-vector scores are the bits of
+        `score_items_batch(V, gl, tau, ids)` -- lambda_q of every vector comes from ONE `search_batch` over V -- and every
+        need's fold is the numpy loop over its rows.  B = 1 is `search_fused` bit for bit; whether a need's answer depends on
+        the OTHER needs of the call is `search_batch`'s property and is not promised.  A vector whose lambda_q is 0:
+        on_zero_lambda="raise" panics as `search` does, for the whole call, before anything is gathered; "skip" leaves it out
+        of its need (the other weights are not renormalised), a need with no vector left gets [] and the other needs are
+        served.  Costs one `search_batch` over V, then the subset's rows are gathered once per 64 VECTORS of the call, whatever
+        need they belong to, one segmented pass per chunk folds every need's rows into that need's accumulator on the device,
+        and one batched selection follows: B x topk entries cross to the host."""
+        V, offs, w, m, skip = _fused_batch_args(needs, gl, weights, mode, on_zero_lambda)
+        sub = self._as_subset(subset, optional=True)
+        b, kk = offs.shape[0] - 1, self._hits_bound(gl, sub)
+        (idx, sc, ln), stt = _hit_buffers(b, kk), _statuses(b)
+        st = _L.as_search_fused_batch(self._h, gl._h, V.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p), b, V.shape[0], V.shape[1],
+                                      float(tau), None if w is None else w.ctypes.data_as(C.c_void_p), m, skip, _handle(sub),
+                                      idx.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p), ln.ctypes.data_as(C.c_void_p), None,
+                                      stt.ctypes.data_as(C.c_void_p))
+        _check(st)
+        return _hit_lists(idx, sc, ln, b, kk)
+
+    def score_fused_batch(self, needs, gl: GraphLaplacian, tau: float, ids, weights=None, mode="sum", on_zero_lambda="raise") -> np.ndarray:
+        """Extension: the fused scores F of `search_fused_batch` (same needs, weights, modes and zero-lambda rule) for each
+        listed id -> ndarray[float64] of shape (B, len(ids)): the caller's order, duplicates kept; integer ids or a boolean
+        mask as for `subset`.  Row b equals the numpy fold of need b's rows of `score_items_batch(V, gl, tau, ids)` bit for
+        bit; B = 1 is `score_fused`.  Under on_zero_lambda="skip" a need with no vector left gets a row of NaN.  Costs what
+        `search_fused_batch` costs without the selection: the B x len(ids) accumulators cross to the host."""
+        V, offs, w, m, skip = _fused_batch_args(needs, gl, weights, mode, on_zero_lambda)
+        ids = _item_ids(ids, self.nitems, "ids")
+        b = offs.shape[0] - 1
+        out = np.empty((b, ids.shape[0]), dtype=np.float64)
+        st = _L.as_score_fused_batch(self._h, gl._h, V.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p), b, V.shape[0], V.shape[1],
+                                     float(tau), None if w is None else w.ctypes.data_as(C.c_void_p), m, skip,
+                                     ids.ctypes.data_as(C.c_void_p), ids.shape[0], out.ctypes.data_as(C.c_void_p), None, None)
+        _check(st)
+        return out
+
+    def fused_batch_counters(self) -> dict:
+        """Extension: batched fused calls on this space since it was made that passed their checks, their needs, the
+        accumulate launches, the scores folded (served vectors x items), the lambda_q steps (one per call) and the need
+        groups run."""
+        return _counters(_L.as_fused_batch_counters, self._h, ("calls", "needs", "launches", "folded", "lambda_steps", "groups"))
 
     def groups(self, labels) -> ItemGroups:
         """Extension: an `ItemGroups` of this space from one integer label per item (a 1-D sequence or array of length nitems,

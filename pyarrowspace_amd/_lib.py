@@ -60,6 +60,7 @@ SYMBOLS = [
     "as_range_counters", "as_range_kernel_us",
     "as_search_diverse", "as_search_diverse_batch", "as_diverse_counters", "as_diverse_kernel_us",
     "as_search_fused", "as_score_fused", "as_fused_counters", "as_fused_kernel_us",
+    "as_search_fused_batch", "as_score_fused_batch", "as_fused_batch_counters", "as_fused_batch_kernel_us",
     "as_groups_create", "as_groups_count", "as_groups_free", "as_search_grouped", "as_search_grouped_batch", "as_grouped_counters",
     "as_grouped_kernel_us",
 ]
@@ -251,6 +252,10 @@ def load():
         "as_score_fused": (i32, [vp, vp, vp, i64, i64, f64, vp, i32, i32, vp, i64, vp, vp, vp]),
         "as_fused_counters": (i32, [vp, vp, i32]),
         "as_fused_kernel_us": (f64, [vp]),
+        "as_search_fused_batch": (i32, [vp, vp, vp, vp, i64, i64, i64, f64, vp, i32, i32, vp, vp, vp, vp, vp, vp]),
+        "as_score_fused_batch": (i32, [vp, vp, vp, vp, i64, i64, i64, f64, vp, i32, i32, vp, i64, vp, vp, vp]),
+        "as_fused_batch_counters": (i32, [vp, vp, i32]),
+        "as_fused_batch_kernel_us": (f64, [vp]),
         "as_groups_create": (i32, [vp, vp, i64, pvp]),
         "as_groups_count": (i64, [vp]),
         "as_groups_free": (None, [vp]),

@@ -1769,6 +1769,197 @@ as_status as_fused_counters(const as_space* sp, int64_t* out, int32_t n) {
 }
 double as_fused_kernel_us(const as_space* sp) { return sp ? sp->fused_us.load(std::memory_order_relaxed) : 0.0; }
 
+// ---------------------------------------------------------------- batched fused search (extension; as_fused.hip)
+namespace {
+// b >= 1 needs; offsets [b + 1] start at 0, increase strictly (no empty need) and end at nv: looked at before any handle is
+static as_status fused_batch_offsets(const char* who, const int64_t* offsets, int64_t b, int64_t nv) {
+    if (b < 1) {
+        set_err("%s: b must be >= 1, got %lld", who, (long long)b);
+        return AS_EINVAL;
+    }
+    if (offsets[0] != 0 || offsets[b] != nv) {
+        set_err("%s: offsets must start at 0 and end at nv = %lld, got %lld .. %lld", who, (long long)nv, (long long)offsets[0], (long long)offsets[b]);
+        return AS_EINVAL;
+    }
+    for (int64_t y = 0; y < b; ++y)
+        if (offsets[y + 1] <= offsets[y]) {
+            set_err("%s: offsets must increase strictly (need %lld is empty or runs backwards)", who, (long long)y);
+            return AS_EINVAL;
+        }
+    return AS_OK;
+}
+// What both forms refuse before anything is launched, then lambda_q and the status of every vector from ONE as_search_batch call
+// over the nv vectors, then S15's zero-lambda rule: `nst` is the status per need.  `wts`: the caller's weights, or 1/J_b each.
+struct FusedBatchArgs {
+    std::vector<double> wts, lq;
+    std::vector<int32_t> st, nst;
+    bool any = false;   // a need is served
+};
+as_status fused_batch_prepare(const char* who, const as_space* sp, const as_graph* gr, const double* queries, const int64_t* offsets, int64_t b,
+                              int64_t d, double tau, const double* weights, int32_t mode, int32_t skip_zero, const as_subset* sub,
+                              double* out_lambda_q, int32_t* out_status, FusedBatchArgs& a) {
+    const int64_t nv = offsets[b];
+    if (mode != 0 && mode != 1) {
+        set_err("%s: mode must be 0 (sum) or 1 (max), got %d", who, (int)mode);
+        return AS_EINVAL;
+    }
+    for (int64_t t = 0; weights && t < nv; ++t)
+        if (!std::isfinite(weights[t])) {
+            set_err("%s: weights[%lld] must be finite", who, (long long)t);
+            return AS_EINVAL;
+        }
+    AS_TRY(own_subset(who, sp, sub));
+    AS_TRY(subset_checks(who, sp, gr, d, &tau, 1));
+    try {
+        if (weights) a.wts.assign(weights, weights + nv);
+        else {
+            a.wts.resize((size_t)nv);
+            for (int64_t y = 0; y < b; ++y)
+                for (int64_t t = offsets[y]; t < offsets[y + 1]; ++t) a.wts[(size_t)t] = 1.0 / (double)(offsets[y + 1] - offsets[y]);
+        }
+        a.nst.assign((size_t)b, 0);
+    } catch (const std::bad_alloc&) {
+        set_err("%s: out of host memory for %lld weights", who, (long long)nv);
+        return AS_ENOMEM;
+    }
+    sp->fused_batch_count[0].fetch_add(1, std::memory_order_relaxed);
+    sp->fused_batch_count[1].fetch_add(b, std::memory_order_relaxed);
+    AS_TRY(batch_lambda_step(who, sp, gr, queries, nv, d, tau, &sp->fused_batch_count[4], a.lq, a.st, out_lambda_q, nullptr));
+    bool refused = false;
+    for (int64_t y = 0; y < b; ++y) {
+        int64_t served = 0;
+        for (int64_t t = offsets[y]; t < offsets[y + 1]; ++t) served += a.st[(size_t)t] == AS_EZEROLAMBDA ? 0 : 1;
+        const bool zero = skip_zero ? served == 0 : served < offsets[y + 1] - offsets[y];
+        a.nst[(size_t)y] = zero ? AS_EZEROLAMBDA : 0;
+        if (out_status) out_status[y] = a.nst[(size_t)y];
+        a.any = a.any || !zero;
+        refused = refused || (zero && !skip_zero);
+    }
+    if (refused) {
+        set_err("The lambdas are zero, check the magnitude of items and eps.");
+        return AS_EZEROLAMBDA;
+    }
+    return AS_OK;
+}
+as_status fused_batch_sink_chunk(void* ctx, SubsetWork*, int64_t i0, int64_t nb, const double* scores, int64_t ld) {
+    return fused_batch_chunk((FusedBatchCall*)ctx, i0, nb, scores, ld);
+}
+// needs g0 .. g0 + gn - 1 (one of them served): their slice of the vectors scored chunk by chunk, every chunk folded into the
+// group's accumulator rows; the stream is left busy at most with the last fold
+as_status fused_batch_fold_group(const as_space* sp, SubsetWork* w, int64_t m, const double* queries, const int64_t* offsets, int64_t g0, int64_t gn,
+                                 double tau, const FusedBatchArgs& a, FusedBatchCall* call) {
+    const int64_t v0 = offsets[g0], v1 = offsets[g0 + gn];
+    fused_batch_group(call, g0, gn);
+    const SubsetChunkSink sink{fused_batch_sink_chunk, call};
+    return subset_batch_run(sp, w, m, queries + v0 * sp->d, v1 - v0, a.lq.data() + v0, a.st.data() + v0, tau, 0, 0, nullptr, nullptr, nullptr, nullptr,
+                            &sink);
+}
+bool fused_batch_group_served(const FusedBatchArgs& a, int64_t g0, int64_t gn) {
+    for (int64_t t = 0; t < gn; ++t)
+        if (a.nst[(size_t)(g0 + t)] == 0) return true;
+    return false;
+}
+void fused_batch_counts_add(const as_space* sp, const FusedBatchCall& call) {
+    sp->fused_batch_count[2].fetch_add(call.launches, std::memory_order_relaxed);
+    sp->fused_batch_count[3].fetch_add(call.folded, std::memory_order_relaxed);
+    sp->fused_batch_count[5].fetch_add(call.groups, std::memory_order_relaxed);
+    sp->fused_batch_us.store(call.us, std::memory_order_relaxed);
+}
+}  // namespace
+
+as_status as_search_fused_batch(const as_space* sp, const as_graph* gr, const double* queries, const int64_t* offsets, int64_t b, int64_t nv,
+                                int64_t d, double tau, const double* weights, int32_t mode, int32_t skip_zero, const as_subset* sub,
+                                int64_t* out_idx, double* out_score, int64_t* out_len, double* out_lambda_q, int32_t* out_status) {
+    if (!sp || !gr || !queries || !offsets || !out_len || ((!sub || sub->m > 0) && (!out_idx || !out_score))) {
+        set_err("as_search_fused_batch: null argument");
+        return AS_EINVAL;
+    }
+    AS_TRY(fused_batch_offsets("as_search_fused_batch", offsets, b, nv));
+    for (int64_t y = 0; y < b; ++y) out_len[y] = 0;
+    FusedBatchArgs a;
+    AS_TRY(fused_batch_prepare("as_search_fused_batch", sp, gr, queries, offsets, b, d, tau, weights, mode, skip_zero, sub, out_lambda_q,
+                               out_status, a));
+    if ((sub && sub->m == 0) || !a.any) return AS_OK;
+    const Candidates c("as_search_fused_batch", sp, sub);
+    AS_TRY(c.status);
+    const int64_t kk = hits_bound(sp, gr, c.m), k = std::min<int64_t>(kk, SUBSET_TOPK);
+    FusedBatchCall call;
+    as_status s = fused_batch_begin(c.w, c.m, b, offsets, a.wts.data(), a.st.data(), mode, &call);
+    for (int64_t g0 = 0; s == AS_OK && g0 < b; g0 += call.gmax) {
+        const int64_t gn = std::min<int64_t>(call.gmax, b - g0);
+        if (!fused_batch_group_served(a, g0, gn)) continue;
+        s = fused_batch_fold_group(sp, c.w, c.m, queries, offsets, g0, gn, tau, a, &call);
+        if (s == AS_OK) s = subset_select_rows_from(c.w, fused_acc(c.w), c.m, c.m, k, gn);   // -> c.w->out[t]; waits
+        for (int64_t t = 0; s == AS_OK && t < gn; ++t) {
+            const int64_t y = g0 + t;
+            if (a.nst[(size_t)y] == 0) s = subset_list_out(c.w->out + t, k, out_idx + y * kk, out_score + y * kk, out_len + y);
+        }
+    }
+    if (s == AS_OK) s = fused_batch_end(&call);
+    else {
+        (void)c.fail(s);
+        for (int64_t y = 0; y < b; ++y) out_len[y] = 0;
+    }
+    fused_batch_counts_add(sp, call);
+    return s;
+}
+
+as_status as_score_fused_batch(const as_space* sp, const as_graph* gr, const double* queries, const int64_t* offsets, int64_t b, int64_t nv,
+                               int64_t d, double tau, const double* weights, int32_t mode, int32_t skip_zero, const int64_t* ids_host, int64_t m,
+                               double* out_scores, double* out_lambda_q, int32_t* out_status) {
+    if (!sp || !gr || !queries || !offsets || m < 0 || (m > 0 && (!ids_host || !out_scores))) {
+        set_err("as_score_fused_batch: null argument");
+        return AS_EINVAL;
+    }
+    AS_TRY(fused_batch_offsets("as_score_fused_batch", offsets, b, nv));
+    AS_TRY(ids_in_range("as_score_fused_batch", sp, ids_host, m));
+    FusedBatchArgs a;
+    AS_TRY(fused_batch_prepare("as_score_fused_batch", sp, gr, queries, offsets, b, d, tau, weights, mode, skip_zero, nullptr, out_lambda_q,
+                               out_status, a));
+    if (m == 0) return AS_OK;
+    // an unserved need's row: NaN
+    const auto nan_rows = [&](int64_t g0, int64_t gn) {
+        for (int64_t y = g0; y < g0 + gn; ++y)
+            if (a.nst[(size_t)y] != 0) std::fill(out_scores + y * m, out_scores + (y + 1) * m, std::numeric_limits<double>::quiet_NaN());
+    };
+    if (!a.any) {
+        nan_rows(0, b);
+        return AS_OK;
+    }
+    std::vector<int32_t> ids;
+    AS_TRY(checked_ids("as_score_fused_batch", ids_host, m, ids));
+    const Candidates c("as_score_fused_batch", sp, ids.data(), m);
+    AS_TRY(c.status);
+    SubsetWork* w = c.w;
+    FusedBatchCall call;
+    as_status s = fused_batch_begin(w, m, b, offsets, a.wts.data(), a.st.data(), mode, &call);
+    for (int64_t g0 = 0; s == AS_OK && g0 < b; g0 += call.gmax) {
+        const int64_t gn = std::min<int64_t>(call.gmax, b - g0);
+        if (fused_batch_group_served(a, g0, gn)) {
+            s = fused_batch_fold_group(sp, w, m, queries, offsets, g0, gn, tau, a, &call);
+            // the group's accumulator rows in one copy (an unserved need's row holds no answer: overwritten below)
+            if (s == AS_OK && hipMemcpyAsync(out_scores + g0 * m, fused_acc(w), sizeof(double) * (size_t)(gn * m), hipMemcpyDeviceToHost, w->stream) !=
+                                  hipSuccess) {
+                set_err("as_score_fused_batch: the copy of the scores failed");
+                s = AS_EHIP;
+            }
+            if (hipStreamSynchronize(w->stream) != hipSuccess && s == AS_OK) {
+                set_err("as_score_fused_batch: the wait for the stream failed");
+                s = AS_EHIP;
+            }
+        }
+        if (s == AS_OK) nan_rows(g0, gn);
+    }
+    if (s == AS_OK) s = fused_batch_end(&call);
+    fused_batch_counts_add(sp, call);
+    return s;
+}
+
+as_status as_fused_batch_counters(const as_space* sp, int64_t* out, int32_t n) {
+    return counters_out("as_fused_batch_counters", sp, out, n, sp ? sp->fused_batch_count : nullptr, 6);
+}
+double as_fused_batch_kernel_us(const as_space* sp) { return sp ? sp->fused_batch_us.load(std::memory_order_relaxed) : 0.0; }
+
 // ---------------------------------------------------------------- grouped search (extension; as_grouped.hip)
 as_status as_groups_create(const as_space* sp, const int64_t* labels, int64_t n, as_groups** out) {
     if (!sp || !labels || !out) {

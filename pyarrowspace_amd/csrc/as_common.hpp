@@ -180,6 +180,12 @@ struct as_space {
     // "fused_timing" (as_fused_kernel_us)
     mutable std::atomic<int64_t> fused_count[4] = {};
     mutable std::atomic<double> fused_us{0.0};
+    // as_search_fused_batch / as_score_fused_batch: on the same buffers as the single forms.
+    // as_fused_batch_counters: [0] calls that passed their checks, [1] needs of those calls, [2] accumulate launches, [3] scores
+    // folded (served rows x m), [4] lambda_q steps run (1 per call), [5] need groups begun.  fused_batch_us: the accumulate kernel
+    // of the last call under "fused_batch_timing" (as_fused_batch_kernel_us)
+    mutable std::atomic<int64_t> fused_batch_count[6] = {};
+    mutable std::atomic<double> fused_batch_us{0.0};
     // as_search_grouped / as_search_grouped_batch: they run on the caller's subset or on range_all.
     // as_grouped_counters: [0] calls that passed their checks, [1] pick-kernel launches, [2] scores examined (rows x m per pick
     // launch), [3] 64-bit max-atomics the pick kernels issued, [4] groups returned, [5] members returned, [6] lambda_q steps run.
@@ -775,6 +781,7 @@ as_status subset_batch_run(const as_space* sp, SubsetWork* w, int64_t m, const d
                            const int32_t* status, double tau, int64_t k, int64_t stride, int64_t* out_idx, double* out_score,
                            int64_t* out_len, double* out_scores, const SubsetChunkSink* sink = nullptr);
 void set_subset_batch_mib(int v);   // as_set_tuning("subset_batch_mib", v)
+constexpr int64_t SB_QC_MAX = 4096;   // queries of a chunk at most: the rows the selection serves at once
 // as_set_tuning("filtered_grid_cap", v): v > 0 clips gridDim.x of the filtered family's stride-loop kernels (the gather score
 // kernels, the radix select's passes, the lists' segments, the fused fold, the grouped picks, the range compaction) to at most v
 // blocks, so that tests drive the later trips of those loops at small shapes; 0 (the default): every grid is what its call site
@@ -787,6 +794,8 @@ int64_t filtered_grid(int64_t blocks);   // the grid a call site computed, under
 as_status subset_select_from(SubsetWork* w, const double* scores, int64_t m, int64_t k, int64_t* out_idx, double* out_score, int64_t* out_len);
 // ... and over `rows` rows ([rows][ld]) at once: row t's list -> w->out[t] (len == min(k, m, SUBSET_TOPK)); waits for the stream.
 as_status subset_select_rows_from(SubsetWork* w, const double* scores, int64_t ld, int64_t m, int64_t k, int64_t rows);
+// a row's pinned result (w->out[row]) of k entries to the caller's arrays; AS_EHIP if the selection left another length there
+as_status subset_list_out(const SubsetOut* o, int64_t k, int64_t* out_idx, double* out_score, int64_t* out_len);
 constexpr int QUERY_BATCH = 32;  // == GQ in as_search.hip: query slots of the batched workspace
 constexpr int TAU_GROUP = 8;     // taus one shared pass of a tau sweep serves (search_sweep, as_search_taus; one gather of a subset)
 // Tau sweeps over the m ids of `w`: nt distinct finite taus, up to TAU_GROUP per gather.  The list / the
@@ -849,6 +858,30 @@ as_status fused_end(FusedCall* c);
 const double* fused_acc(const SubsetWork* w);   // [m], valid after a call with a served row
 void fused_work_free(FusedWork* f);
 void set_fused_timing(int v);   // as_set_tuning("fused_timing", 0 | 1)
+// The batched form: b needs, need y = the flattened rows offs[y] .. offs[y + 1] - 1 of the call's nv
+// vectors, each folded into an accumulator row of its own.  fused_batch_begin: G = gmax needs per group from the "fused_batch_mib"
+// budget (1 <= G <= SB_QC_MAX), room for [G][m] accumulators, ONE upload of the weights, the segment offsets, every need's first
+// and last served row and the served flags (weights, status: [nv]).  fused_batch_group: needs g0 .. g0 + gn - 1 are in flight,
+// need g0 + t owns accumulator row t.  fused_batch_chunk: rows i0 .. i0 + nb - 1 of THAT GROUP's slice of the vectors, [nb][ld]
+// on the device -- the sink of a subset_batch_run over the slice; it does not wait; a chunk without a served row launches
+// nothing.  fused_batch_end: after the caller's last wait for the stream.  The rows are fused_acc(w) + t * m.
+struct FusedBatchCall {
+    SubsetWork* w = nullptr;
+    int64_t m = 0, b = 0, nv = 0;
+    int mode = 0;
+    int64_t gmax = 1;              // G
+    int64_t g0 = 0, gn = 0;        // the group in flight
+    bool timing = false, timed = false;
+    int64_t launches = 0, folded = 0, groups = 0;   // accumulate launches, scores folded (served rows x m), groups begun
+    double us = 0.0;               // the accumulate kernel's microseconds under "fused_batch_timing"
+};
+as_status fused_batch_begin(SubsetWork* w, int64_t m, int64_t b, const int64_t* offs, const double* weights, const int32_t* status, int mode,
+                            FusedBatchCall* c);
+void fused_batch_group(FusedBatchCall* c, int64_t g0, int64_t gn);
+as_status fused_batch_chunk(FusedBatchCall* c, int64_t i0, int64_t nb, const double* scores, int64_t ld);
+as_status fused_batch_end(FusedBatchCall* c);
+void set_fused_batch_timing(int v);   // as_set_tuning("fused_batch_timing", 0 | 1)
+void set_fused_batch_mib(int v);      // as_set_tuning("fused_batch_mib", v): v > 0 MiB, v < 0 -v KiB, 0 the default (256 MiB)
 // Grouped search (as_grouped.hip): the S14 answer of `rows` rows of scores over the work's m ids
 // ([rows][ld] on the device, queued on the work's stream): row t belongs to query i0 + t of the call.  Query i's groups -> out_label /
 // out_count + i * n_groups, their members -> out_idx / out_score + (i * n_groups + s) * per_group, out_ngroups[i].  status (null: the

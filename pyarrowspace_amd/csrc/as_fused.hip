@@ -4,6 +4,10 @@
 // device (fused_accumulate_kernel) and carries over the chunks, so J is not bound by the chunk size.  The order over j inside a
 // position is sequential and ascending: that order is the specification (S13), the numpy loop reproduces the bits.
 // Entry points: as_api.hip (as_search_fused, as_score_fused, as_fused_counters, as_fused_kernel_us).
+// The batched form (S15, section 5.18): B needs of J_b vectors each in one call.  The vectors of all needs are ONE flattened list
+// of rows for the score kernel; fused_accumulate_batch_kernel folds each chunk of rows segment by segment into one accumulator
+// row per need ([G][m], G needs at a time).  Entry points: as_search_fused_batch, as_score_fused_batch, as_fused_batch_counters,
+// as_fused_batch_kernel_us.
 #include <algorithm>
 #include <atomic>
 #include <new>
@@ -93,13 +97,94 @@ __global__ __launch_bounds__(FA_THREADS) void fused_accumulate_kernel(const doub
     }
 }
 
+// The segmented fold of the batched form.  The chunk scores ([nb][ld]) holds the flattened rows r0 .. r0 + nb - 1 of the call; need
+// y = need0 + blockIdx.y owns rows offs[y] .. offs[y + 1] - 1 of them, cut by the chunk's edges, and the accumulator row
+// acc + (y - gneed0) * m.  first[y] / last[y]: the flattened index of the need's first / last served row (-1: none) -- the need's
+// accumulator holds something iff its first served row lies before the rows taken here, so no launch has to be told; a need
+// without a served row at or before / at or behind this chunk leaves at once (block-uniform: y is).  Inside a need the kernel is
+// fused_accumulate_kernel: a thread owns a pair of neighbouring positions for all the need's rows, FA_ROWS loads in flight,
+// rows ascending, plain 16-byte stores.  An accumulator row starts on an 8-byte boundary only (m may be odd): f64x2_a8.
+template <int MODE>
+__global__ __launch_bounds__(FA_THREADS) void fused_accumulate_batch_kernel(const double* __restrict__ scores, int64_t ld, int64_t m, int64_t r0,
+                                                                            int nb, int64_t need0, int64_t gneed0,
+                                                                            const int64_t* __restrict__ offs, const int64_t* __restrict__ first,
+                                                                            const int64_t* __restrict__ last, const double* __restrict__ wts,
+                                                                            const int32_t* __restrict__ flags, double* __restrict__ acc) {
+    const int64_t need = need0 + blockIdx.y;
+    const int64_t o0 = offs[need], o1 = offs[need + 1];
+    const int64_t lo = o0 > r0 ? o0 : r0, hi = o1 < r0 + nb ? o1 : r0 + nb;
+    const int64_t fs = first[need];
+    if (fs < 0 || fs >= hi || last[need] < lo) return;
+    const bool carried = fs < lo;
+    const int n = (int)(hi - lo);
+    const double* __restrict__ rows = scores + (lo - r0) * ld;
+    const double* __restrict__ w = wts + lo;
+    const int32_t* __restrict__ fl = flags + lo;
+    double* __restrict__ a = acc + (need - gneed0) * m;
+    const int64_t pairs = m >> 1, units = pairs + (m & 1);
+    for (int64_t u = (int64_t)blockIdx.x * FA_THREADS + threadIdx.x; u < units; u += (int64_t)gridDim.x * FA_THREADS) {
+        const bool pair = u < pairs;
+        const int64_t i = 2 * u;   // (the single position of an odd m: i == m - 1)
+        bool have = carried;
+        double f0 = 0.0, f1 = 0.0;
+        if (have) {
+            if (pair) {
+                const f64x2_a8 x = *(const f64x2_a8*)(a + i);
+                f0 = x[0];
+                f1 = x[1];
+            } else {
+                f0 = a[i];
+            }
+        }
+        bool touched = false;
+        for (int j0 = 0; j0 < n; j0 += FA_ROWS) {
+            double s0[FA_ROWS], s1[FA_ROWS];
+#pragma unroll
+            for (int r = 0; r < FA_ROWS; ++r) {
+                s0[r] = 0.0;
+                s1[r] = 0.0;
+                if (j0 + r < n) {
+                    const double* p = rows + (int64_t)(j0 + r) * ld + i;
+                    if (pair) {
+                        const f64x2_a8 x = *(const f64x2_a8*)p;
+                        s0[r] = x[0];
+                        s1[r] = x[1];
+                    } else {
+                        s0[r] = *p;
+                    }
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < FA_ROWS; ++r) {
+                if (j0 + r < n && fl[j0 + r]) {
+                    const double wj = w[j0 + r];
+                    f0 = fused_step<MODE>(f0, wj, s0[r], have);
+                    f1 = fused_step<MODE>(f1, wj, s1[r], have);
+                    have = true;
+                    touched = true;
+                }
+            }
+        }
+        if (!touched) continue;   // (served rows before and behind this chunk, none inside: the accumulator stays as it is)
+        if (pair) {
+            f64x2_a8 o;
+            o[0] = f0;
+            o[1] = f1;
+            *(f64x2_a8*)(a + i) = o;
+        } else {
+            a[i] = f0;
+        }
+    }
+}
+
 // ------------------------------------------------------------------ host side
 static std::atomic<int> g_fused_timing{0};
 void set_fused_timing(int v) { g_fused_timing.store(v ? 1 : 0, std::memory_order_relaxed); }
 
 struct FusedWork {
-    dev_buf<double> acc;       // [m]: F so far
-    dev_buf<double> par;       // the call's parameters, one upload: [j] weights, then [j] int32 flags (1 for a served vector)
+    dev_buf<double> acc;       // [m]: F so far; the batched form: [G][m], a row per need of the group in flight
+    dev_buf<double> par;       // the call's parameters, one upload: [j] weights, then [j] int32 flags (1 for a served vector); the
+                               // batched form: [nv] weights, [b + 1] int64 offsets, [b] int64 first, [b] int64 last, [nv] int32 flags
     pin_buf<double> hpar;      // pinned staging of the same
     dev_events<2> ev;          // made by the first call under "fused_timing"
     int64_t j = 0;             // vectors of the call in flight
@@ -141,7 +226,8 @@ as_status fused_begin(SubsetWork* w, int64_t m, int64_t j, const double* weights
 }
 
 // the time of the launch before this one: the stream has been waited for since (one pair of events serves every chunk)
-static as_status fused_collect_time(FusedCall* c) {
+template <typename Call>
+static as_status fused_collect_time(Call* c) {
     if (!c->timed) return AS_OK;
     float ms = 0.0f;
     AS_HIP(hipEventElapsedTime(&ms, c->w->fused->ev.e[0], c->w->fused->ev.e[1]));
@@ -183,5 +269,119 @@ as_status fused_chunk(FusedCall* c, int64_t i0, int64_t nb, const double* scores
 as_status fused_end(FusedCall* c) { return fused_collect_time(c); }
 
 const double* fused_acc(const SubsetWork* w) { return w->fused ? (const double*)w->fused->acc : nullptr; }
+
+// ------------------------------------------------------------------ the batched form (S15, section 5.18)
+static std::atomic<int> g_fused_batch_timing{0};
+static std::atomic<int> g_fused_batch_mib{256};
+void set_fused_batch_timing(int v) { g_fused_batch_timing.store(v ? 1 : 0, std::memory_order_relaxed); }
+void set_fused_batch_mib(int v) { g_fused_batch_mib.store(v != 0 ? v : 256, std::memory_order_relaxed); }
+
+namespace {
+// the call's parameters in the pinned block and on the device, in the order of the one upload
+struct BatchPar {
+    double* wts;
+    int64_t* offs;
+    int64_t* first;
+    int64_t* last;
+    int32_t* flags;
+    BatchPar(double* base, int64_t nv, int64_t b)
+        : wts(base), offs((int64_t*)(base + nv)), first(offs + b + 1), last(first + b), flags((int32_t*)(last + b)) {}
+    static int64_t words(int64_t nv, int64_t b) { return nv + (b + 1) + 2 * b + (nv + 1) / 2; }
+    static size_t bytes(int64_t nv, int64_t b) { return sizeof(double) * (size_t)(nv + (b + 1) + 2 * b) + sizeof(int32_t) * (size_t)nv; }
+};
+}  // namespace
+
+as_status fused_batch_begin(SubsetWork* w, int64_t m, int64_t b, const int64_t* offs, const double* weights, const int32_t* status, int mode,
+                            FusedBatchCall* c) {
+    if (!w->fused) {
+        w->fused = new (std::nothrow) FusedWork();
+        if (!w->fused) {
+            set_err("fused: out of host memory");
+            return AS_ENOMEM;
+        }
+    }
+    FusedWork* f = w->fused;
+    const int64_t nv = offs[b];
+    c->w = w;
+    c->m = m;
+    c->b = b;
+    c->nv = nv;
+    c->mode = mode;
+    c->g0 = c->gn = 0;
+    c->timing = g_fused_batch_timing.load(std::memory_order_relaxed) != 0;
+    c->timed = false;
+    c->launches = c->folded = c->groups = 0;
+    c->us = 0.0;
+    // needs per group: the accumulator rows that fit the budget (v > 0: MiB; v < 0: -v KiB, for tests at small shapes)
+    const int v = g_fused_batch_mib.load(std::memory_order_relaxed);
+    const int64_t budget = v > 0 ? (int64_t)v << 20 : (int64_t)(-(int64_t)v) << 10;
+    const int64_t row = std::max<int64_t>(m, 1) * (int64_t)sizeof(double);
+    c->gmax = std::min<int64_t>(std::min<int64_t>(std::max<int64_t>(budget / row, 1), SB_QC_MAX), b);
+    if (c->timing && !f->ev.e[1]) AS_HIP(f->ev.create());
+    AS_TRY(reserve_or_err(f->acc, std::max<int64_t>(c->gmax * m, 1), "fused accumulators"));
+    const int64_t words = BatchPar::words(nv, b);
+    AS_TRY(reserve_or_err(f->par, words, "fused weights, segments and flags"));
+    AS_TRY(reserve_or_err(f->hpar, words, "fused pinned weights, segments and flags"));
+    f->j = 0;
+    const BatchPar h(f->hpar, nv, b);
+    for (int64_t y = 0; y <= b; ++y) h.offs[y] = offs[y];
+    for (int64_t y = 0; y < b; ++y) {
+        h.first[y] = h.last[y] = -1;
+        for (int64_t t = offs[y]; t < offs[y + 1]; ++t) {
+            h.wts[t] = weights[t];
+            h.flags[t] = status[t] == AS_EZEROLAMBDA ? 0 : 1;
+            if (h.flags[t]) {
+                if (h.first[y] < 0) h.first[y] = t;
+                h.last[y] = t;
+            }
+        }
+    }
+    AS_HIP(hipMemcpyAsync(f->par, f->hpar, BatchPar::bytes(nv, b), hipMemcpyHostToDevice, w->stream));
+    return AS_OK;
+}
+
+void fused_batch_group(FusedBatchCall* c, int64_t g0, int64_t gn) {
+    c->g0 = g0;
+    c->gn = gn;
+    c->groups += 1;
+}
+
+as_status fused_batch_chunk(FusedBatchCall* c, int64_t i0, int64_t nb, const double* scores, int64_t ld) {
+    SubsetWork* w = c->w;
+    FusedWork* f = w->fused;
+    const BatchPar h(f->hpar, c->nv, c->b), dv(f->par, c->nv, c->b);
+    const int64_t r0 = h.offs[c->g0] + i0;   // the chunk's rows as flattened rows of the call
+    if (nb <= 0 || c->m <= 0 || r0 + nb > h.offs[c->g0 + c->gn]) return AS_OK;   // (rows of the group in flight only)
+    int64_t served = 0;
+    for (int64_t t = 0; t < nb; ++t) served += h.flags[r0 + t];
+    if (served == 0) return AS_OK;
+    // the needs the chunk touches: the one that holds row r0 .. the one that holds row r0 + nb - 1
+    const int64_t need0 = (std::upper_bound(h.offs, h.offs + c->b + 1, r0) - h.offs) - 1;
+    const int64_t need1 = (std::upper_bound(h.offs, h.offs + c->b + 1, r0 + nb - 1) - h.offs) - 1;
+    AS_TRY(fused_collect_time(c));
+    const int64_t units = (c->m + 1) / 2;
+    const dim3 grid((unsigned)filtered_grid(std::max<int64_t>(1, std::min<int64_t>((units + FA_THREADS - 1) / FA_THREADS, (int64_t)w->cus * FA_BLOCKS_PER_CU))),
+                    (unsigned)(need1 - need0 + 1));
+    double* acc = f->acc;
+    if (c->timing) AS_HIP(hipEventRecord(f->ev.e[0], w->stream));
+    if (c->mode == 0)
+        hipLaunchKernelGGL(fused_accumulate_batch_kernel<0>, grid, dim3(FA_THREADS), 0, w->stream, scores, ld, c->m, r0, (int)nb, need0, c->g0,
+                           (const int64_t*)dv.offs, (const int64_t*)dv.first, (const int64_t*)dv.last, (const double*)dv.wts,
+                           (const int32_t*)dv.flags, acc);
+    else
+        hipLaunchKernelGGL(fused_accumulate_batch_kernel<1>, grid, dim3(FA_THREADS), 0, w->stream, scores, ld, c->m, r0, (int)nb, need0, c->g0,
+                           (const int64_t*)dv.offs, (const int64_t*)dv.first, (const int64_t*)dv.last, (const double*)dv.wts,
+                           (const int32_t*)dv.flags, acc);
+    AS_HIP(hipGetLastError());
+    if (c->timing) {
+        AS_HIP(hipEventRecord(f->ev.e[1], w->stream));
+        c->timed = true;
+    }
+    c->launches += 1;
+    c->folded += served * c->m;
+    return AS_OK;
+}
+
+as_status fused_batch_end(FusedBatchCall* c) { return fused_collect_time(c); }
 
 }  // namespace as

@@ -543,7 +543,7 @@ static as_status subset_select_rows(SubsetWork* w, const double* scores, int64_t
 }
 
 // a row's pinned result, k entries, to the caller's arrays
-static as_status subset_list_out(const SubsetOut* o, int64_t k, int64_t* out_idx, double* out_score, int64_t* out_len) {
+as_status subset_list_out(const SubsetOut* o, int64_t k, int64_t* out_idx, double* out_score, int64_t* out_len) {
     if (o->len != k) {
         set_err("subset: the selection returned %lld of %lld entries", (long long)o->len, (long long)k);
         return AS_EHIP;
@@ -607,7 +607,6 @@ as_status subset_scores_out(SubsetWork* w, int64_t m, double* out) {
 // depend on it.
 static std::atomic<int> g_subset_batch_mib{256};
 void set_subset_batch_mib(int v) { g_subset_batch_mib.store(v > 0 ? v : 256, std::memory_order_relaxed); }
-constexpr int64_t SB_QC_MAX = 4096;
 
 as_status subset_batch_run(const as_space* sp, SubsetWork* w, int64_t m, const double* queries, int64_t b, const double* lq,
                            const int32_t* status, double tau, int64_t k, int64_t stride, int64_t* out_idx, double* out_score,
