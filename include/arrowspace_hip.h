@@ -479,10 +479,11 @@ void as_enable_search_stats(int32_t enabled);
  * "diverse_chunk" = queries per launch of the diversified forms (default 4096; <= 0: the default); "diverse_timing" = 1 / 0: HIP
  * events around their select kernel (as_diverse_kernel_us).  "fused_timing" = 1 / 0: HIP events around the fused forms'
  * accumulate kernel (as_fused_kernel_us).  "grouped_timing" = 1 / 0: HIP events around the grouped forms' pick kernels
- * (as_grouped_kernel_us).  "fused_batch_timing" = 1 / 0: HIP events around the batched fused forms' accumulate kernel
+ * (as_grouped_kernel_us).  "maxsim_timing" = 1 / 0: HIP events around late-interaction search's pass A and fold kernel
+ * (as_maxsim_kernel_us).  "fused_batch_timing" = 1 / 0: HIP events around the batched fused forms' accumulate kernel
  * (as_fused_batch_kernel_us); "fused_batch_mib" = MiB of accumulator rows one group of needs of those forms may hold (default
  * 256; 0: the default; v < 0: -v KiB, so that tests reach several groups at small shapes).  "filtered_grid_cap" = v > 0: gridDim.x of the filtered family's stride-loop kernels (the gather score
- * kernels of the subset and list forms, the radix select's passes, the fused fold, the grouped picks, the range compaction) is
+ * kernels of the subset and list forms, the radix select's passes, the fused and late-interaction folds, the grouped picks, the range compaction) is
  * clipped to at most v blocks, so tests reach the later trips of those loops at small shapes; 0 (default): no clip.
  * Returns 0, or 1 for an unknown key.  Results never depend on it. */
 int32_t as_set_tuning(const char* key, int32_t value);
@@ -837,6 +838,41 @@ as_status as_grouped_counters(const as_space* sp, int64_t* out, int32_t n);
 /* measurement: the device microseconds of the pick kernels, summed over the rounds and chunks of the last grouped call on this
  * space that ran under as_set_tuning("grouped_timing", 1) (HIP events around the kernels; off by default) */
 double as_grouped_kernel_us(const as_space* sp);
+/* ---- Extension: late-interaction search (MaxSim).  ONE answer to j query vectors [j][d] (HOST memory) over the
+ * GROUPS of an as_groups handle: with s_j(i) the bits as_score_items_batch writes at [j][i], m_j(g) = the largest s_j over the
+ * members of g -- its items inside the subset (sub == NULL: every item) whose s_j is not NaN; +0.0 where the largest is a zero;
+ * NaN where g has no member under vector j -- and F(g) = the S13 "sum" fold of t_j(g) = fl(weights[j] * m_j(g)), j ascending over
+ * the served vectors, every product and sum rounded once (weights NULL: 1/j each; finite, negative values are legal).  The
+ * zero-lambda rule is as_search_fused's: skip_zero == 0: a vector whose lambda_q is 0 makes the call return AS_EZEROLAMBDA before
+ * anything else is launched; skip_zero != 0: it is left out, the other weights are not renormalised; no vector served ->
+ * AS_EZEROLAMBDA in either setting.  out_lambda_q / out_status ([j], may be NULL) are written whenever the lambda_q step ran.
+ * as_search_maxsim: the groups whose F is not NaN by (F descending, label ascending; +0.0 and -0.0 tie), the first
+ * min(n_groups, such groups) of them -> out_label / out_score [n_groups], *out_len.  as_score_maxsim: F of every listed label ->
+ * out_scores [nl], the caller's order, duplicates kept, NaN for a group without a member.
+ * Checked before anything is launched: a null argument ("<name>: null argument", nothing written), n_groups outside [1, 1024], a
+ * groups handle or a subset of another space, a label the handle does not hold, j < 1, a NaN or infinite weight, wrong d, a
+ * non-finite tau -> AS_EINVAL; a shard of a row-sharded index -> AS_EUNSUPPORTED.
+ * Cost: ONE as_search_batch over the j vectors (hits discarded); per chunk of vectors under the "subset_batch_mib" budget (which
+ * counts the 8 G bytes of a vector's cells beside its m scores, G = as_groups_count) the batched filtered forms' gather and fp64
+ * matrix product, one memset of the chunk's cells, the first pass of grouped search's pick kernel (one vector atomic per run of
+ * neighbouring positions of one group inside a wave) and ONE fold kernel that reads the [chunk][G] cells once and folds them
+ * into an accumulator of G doubles, which carries over the chunks; at the end the filtered forms' exact selection over the
+ * accumulator (n_groups entries cross to the host) or one copy of its G doubles.  One wait per chunk plus the last.  The buffers
+ * live in the subset handle (sub == NULL: in the space's subset of all items, made on first use) and grow on demand; calls are
+ * serialised with the other forms on that handle, as_search runs beside them. */
+as_status as_search_maxsim(const as_space* sp, const as_graph* gr, const double* queries, int64_t j, int64_t d, double tau,
+                           const double* weights, int32_t skip_zero, const as_groups* groups, int64_t n_groups, const as_subset* sub,
+                           int64_t* out_label, double* out_score, int64_t* out_len, double* out_lambda_q, int32_t* out_status);
+as_status as_score_maxsim(const as_space* sp, const as_graph* gr, const double* queries, int64_t j, int64_t d, double tau,
+                          const double* weights, int32_t skip_zero, const as_groups* groups, const as_subset* sub, const int64_t* labels,
+                          int64_t nl, double* out_scores, double* out_lambda_q, int32_t* out_status);
+/* out[0] calls of the two entries above that passed their checks, [1] vectors served, [2] pass-A launches, [3] 64-bit max-atomics
+ * pass A issued, [4] fold launches */
+as_status as_maxsim_counters(const as_space* sp, int64_t* out, int32_t n);
+/* measurement: device microseconds of the last late-interaction call on this space that ran under as_set_tuning("maxsim_timing",
+ * 1) (HIP events; off by default), summed over its chunks: part 1: the memsets of the cells and pass A; part 2: the fold kernel;
+ * part 0: both.  NULL or another part: 0 */
+double as_maxsim_kernel_us(const as_space* sp, int32_t part);
 
 /* ---- index persistence (extension; the reference exposes none): one flat file
  * holding the items, lambdas and graph arrays.  Loading re-ingests the items and uploads the

@@ -972,6 +972,67 @@ class ArrowSpace:
         return _counters(_L.as_grouped_counters, self._h,
                          ("calls", "pick_launches", "scores_examined", "max_atomics", "groups", "members", "lambda_steps"))
 
+    def _maxsim_args(self, items, gl, tau, groups, n_groups, weights, subset, on_zero_lambda):
+        """What the late-interaction forms check before they touch a handle: the fused forms' checks (vectors, weights, the
+        zero-lambda setting), then the grouped forms' (n_groups, tau, handles of this space)."""
+        Q, w, _, skip = _fused_args(items, gl, weights, "sum", on_zero_lambda)
+        tau, ng, _ = _grouped_args(gl, tau, n_groups, 1)
+        grp, sub = self._grouped_handles(groups, subset)
+        return Q, w, skip, tau, ng, grp, sub
+
+    def search_maxsim(self, items, gl: GraphLaplacian, tau: float, groups, n_groups: int, weights=None, subset=None, on_zero_lambda="raise"):
+        """Extension: late-interaction search (MaxSim), ONE answer to J query vectors [J, D] over GROUPS of items ->
+        list[(label, F)]: the first min(n_groups, groups with a non-NaN F) groups by (F descending, label ascending),
+        1 <= n_groups <= 1024.  With s_j(i) the score `score_items_batch(items, gl, tau, ids)[j, i]`, m_j(g) is the largest
+        s_j over the members of g -- its items inside the subset (None: every item) whose s_j is not NaN; +0.0 where the
+        largest is a zero; NaN where g has no member -- and F(g) is `search_fused`'s "sum" fold of weights[j] * m_j(g): j
+        ascending, the first served term, then F + t_j, every product and sum rounded once (weights default to 1/J each;
+        negative weights are legal).  The numpy group-by over `score_items_batch` reproduces the bits.  `groups`: an
+        `ItemGroups` of this space or anything `groups()` accepts; `subset`: as in `search_grouped`.  A vector whose lambda_q
+        is 0: `search_fused`'s rule (on_zero_lambda="raise" panics for the whole call before anything is gathered, "skip"
+        leaves the vector out with its weight, no vector left panics).  J = 1 with weights [1.0] names the heads of
+        `search_batch_grouped`; every item its own group is `search_fused`.  Costs one `search_batch` over the J vectors
+        (lambda_q), the gather and fp64 matrix product of the batched filtered forms, per chunk of vectors one pass that
+        takes every group's maximum with atomics on the device and one pass that folds the J x G maxima into an accumulator
+        there, and one exact selection: n_groups entries cross to the host, the J x M scores never do."""
+        Q, w, skip, tau, ng, grp, sub = self._maxsim_args(items, gl, tau, groups, n_groups, weights, subset, on_zero_lambda)
+        label, sc = np.zeros(ng, dtype=np.int64), np.zeros(ng, dtype=np.float64)
+        ln = C.c_int64(0)
+        st = _L.as_search_maxsim(self._h, gl._h, Q.ctypes.data_as(C.c_void_p), Q.shape[0], Q.shape[1], tau,
+                                 None if w is None else w.ctypes.data_as(C.c_void_p), skip, grp._h, ng, _handle(sub),
+                                 label.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p), C.byref(ln), None, None)
+        _check(st)
+        return list(zip(label[:ln.value].tolist(), sc[:ln.value].tolist()))
+
+    def score_maxsim(self, items, gl: GraphLaplacian, tau: float, groups, labels, weights=None, subset=None, on_zero_lambda="raise") -> np.ndarray:
+        """Extension: the late-interaction score F of `search_maxsim` (same weights, subset and zero-lambda rule) for each
+        listed group label -> ndarray[float64] of len(labels): the caller's order, duplicates kept, NaN for a group without a
+        member inside the subset.  A label that is not one of the groups raises ValueError.  Costs what `search_maxsim`
+        costs without the selection: the accumulator's G doubles cross to the host."""
+        Q, w, skip, tau, _, grp, sub = self._maxsim_args(items, gl, tau, groups, 1, weights, subset, on_zero_lambda)
+        lab = np.asarray(labels)
+        if lab.size == 0 and lab.ndim == 1:
+            lab = np.empty(0, dtype=np.int64)
+        if lab.dtype.kind not in "iu":
+            raise TypeError(f"argument 'labels': expected integer group labels, got dtype {lab.dtype}")
+        if lab.ndim != 1:
+            raise ValueError(f"argument 'labels': expected a 1-D sequence of group labels, got shape {lab.shape}")
+        known = np.isin(lab, grp._labels)
+        if not known.all():
+            raise ValueError(f"argument 'labels': label {int(lab[np.flatnonzero(~known)[0]])} is not one of the groups")
+        lab = np.ascontiguousarray(lab, dtype=np.int64)
+        out = np.empty(lab.shape[0], dtype=np.float64)
+        st = _L.as_score_maxsim(self._h, gl._h, Q.ctypes.data_as(C.c_void_p), Q.shape[0], Q.shape[1], tau,
+                                None if w is None else w.ctypes.data_as(C.c_void_p), skip, grp._h, _handle(sub),
+                                lab.ctypes.data_as(C.c_void_p), lab.shape[0], out.ctypes.data_as(C.c_void_p), None, None)
+        _check(st)
+        return out
+
+    def maxsim_counters(self) -> dict:
+        """Extension: late-interaction calls on this space since it was made that passed their checks, the vectors they
+        served, the group-maximum (pass A) launches, the 64-bit max-atomics those issued and the fold launches."""
+        return _counters(_L.as_maxsim_counters, self._h, ("calls", "vectors_served", "pass_a_launches", "max_atomics", "fold_launches"))
+
     @staticmethod
     def _diverse_params(n, diversity) -> tuple[int, float]:
         if isinstance(n, bool) or not isinstance(n, (int, np.integer)):

@@ -5,6 +5,7 @@
 #include <atomic>
 #include <chrono>
 #include <cmath>
+#include <limits>
 #include <new>
 #include <system_error>
 #include <thread>
@@ -1656,10 +1657,12 @@ double as_range_kernel_us(const as_space* sp) { return sp ? sp->range_us.load(st
 // ---------------------------------------------------------------- fused multi-query search (extension; as_fused.hip)
 namespace {
 // What both forms refuse before anything is launched, then lambda_q and the status of every vector from ONE as_search_batch call
-// over the j vectors, then S13's zero-lambda rule.  `wts`: the caller's weights, or 1/j each.
+// over the j vectors, then S13's zero-lambda rule.  `wts`: the caller's weights, or 1/j each.  calls, steps: the family's counters
+// of calls that passed their checks and of lambda_q steps (steps may be null).
 as_status fused_prepare(const char* who, const as_space* sp, const as_graph* gr, const double* queries, int64_t j, int64_t d, double tau,
                         const double* weights, int32_t mode, int32_t skip_zero, const as_subset* sub, double* out_lambda_q, int32_t* out_status,
-                        std::vector<double>& wts, std::vector<double>& lq, std::vector<int32_t>& st) {
+                        std::vector<double>& wts, std::vector<double>& lq, std::vector<int32_t>& st, std::atomic<int64_t>* calls,
+                        std::atomic<int64_t>* steps) {
     if (j <= 0) {
         set_err("%s: j must be >= 1, got %lld", who, (long long)j);
         return AS_EINVAL;
@@ -1682,8 +1685,8 @@ as_status fused_prepare(const char* who, const as_space* sp, const as_graph* gr,
         set_err("%s: out of host memory for %lld weights", who, (long long)j);
         return AS_ENOMEM;
     }
-    sp->fused_count[0].fetch_add(1, std::memory_order_relaxed);
-    AS_TRY(batch_lambda_step(who, sp, gr, queries, j, d, tau, &sp->fused_count[3], lq, st, out_lambda_q, out_status));
+    calls->fetch_add(1, std::memory_order_relaxed);
+    AS_TRY(batch_lambda_step(who, sp, gr, queries, j, d, tau, steps, lq, st, out_lambda_q, out_status));
     int64_t served = 0;
     for (int64_t t = 0; t < j; ++t) served += st[t] == AS_EZEROLAMBDA ? 0 : 1;
     if (served == 0 || (served < j && !skip_zero)) {
@@ -1720,7 +1723,8 @@ as_status as_search_fused(const as_space* sp, const as_graph* gr, const double* 
     *out_len = 0;
     std::vector<double> wts, lq;
     std::vector<int32_t> st;
-    AS_TRY(fused_prepare("as_search_fused", sp, gr, queries, j, d, tau, weights, mode, skip_zero, sub, out_lambda_q, out_status, wts, lq, st));
+    AS_TRY(fused_prepare("as_search_fused", sp, gr, queries, j, d, tau, weights, mode, skip_zero, sub, out_lambda_q, out_status, wts, lq, st,
+                         &sp->fused_count[0], &sp->fused_count[3]));
     if (sub && sub->m == 0) return AS_OK;
     const Candidates c("as_search_fused", sp, sub);
     AS_TRY(c.status);
@@ -1742,7 +1746,8 @@ as_status as_score_fused(const as_space* sp, const as_graph* gr, const double* q
     AS_TRY(ids_in_range("as_score_fused", sp, ids_host, m));
     std::vector<double> wts, lq;
     std::vector<int32_t> st;
-    AS_TRY(fused_prepare("as_score_fused", sp, gr, queries, j, d, tau, weights, mode, skip_zero, nullptr, out_lambda_q, out_status, wts, lq, st));
+    AS_TRY(fused_prepare("as_score_fused", sp, gr, queries, j, d, tau, weights, mode, skip_zero, nullptr, out_lambda_q, out_status, wts, lq, st,
+                         &sp->fused_count[0], &sp->fused_count[3]));
     if (m == 0) return AS_OK;
     std::vector<int32_t> ids;
     AS_TRY(checked_ids("as_score_fused", ids_host, m, ids));
@@ -2101,6 +2106,139 @@ as_status as_grouped_counters(const as_space* sp, int64_t* out, int32_t n) {
     return counters_out("as_grouped_counters", sp, out, n, sp ? sp->grouped_count : nullptr, 7);
 }
 double as_grouped_kernel_us(const as_space* sp) { return sp ? sp->grouped_us.load(std::memory_order_relaxed) : 0.0; }
+
+// ---------------------------------------------------------------- late-interaction search (extension; as_maxsim.hip)
+namespace {
+// what both forms refuse before anything is launched and before the fused forms' own checks
+as_status maxsim_checks(const char* who, const as_space* sp, const as_groups* groups) {
+    if (groups->sp != sp) {
+        set_err("%s: the groups were made for another space", who);
+        return AS_EINVAL;
+    }
+    return AS_OK;
+}
+as_status maxsim_sink_chunk(void* ctx, SubsetWork*, int64_t i0, int64_t nb, const double* scores, int64_t ld) {
+    return maxsim_chunk((MaxsimCall*)ctx, i0, nb, scores, ld);
+}
+// the j score rows of the work's m ids, chunk by chunk, turned into group maxima and folded into the work's accumulator; the
+// stream is left busy at most with what the caller queues behind (the selection, or the copy of the accumulator)
+as_status maxsim_fold(const as_space* sp, SubsetWork* w, int64_t m, const double* queries, int64_t j, double tau, const as_groups* groups,
+                      const std::vector<double>& wts, const std::vector<double>& lq, const std::vector<int32_t>& st, MaxsimCall* call) {
+    AS_TRY(maxsim_begin(w, groups, m, j, wts.data(), st.data(), call));
+    SubsetChunkSink sink{maxsim_sink_chunk, call};
+    sink.row_bytes = groups->count * (int64_t)sizeof(unsigned long long);
+    return subset_batch_run(sp, w, m, queries, j, lq.data(), st.data(), tau, 0, 0, nullptr, nullptr, nullptr, nullptr, &sink);
+}
+void maxsim_counts_add(const as_space* sp, const MaxsimCall& call) {
+    sp->maxsim_count[1].fetch_add(call.served, std::memory_order_relaxed);
+    sp->maxsim_count[2].fetch_add(call.passa, std::memory_order_relaxed);
+    sp->maxsim_count[3].fetch_add(call.atoms, std::memory_order_relaxed);
+    sp->maxsim_count[4].fetch_add(call.folds, std::memory_order_relaxed);
+    for (int t = 0; t < 2; ++t) sp->maxsim_us[t].store(call.us[t], std::memory_order_relaxed);
+}
+}  // namespace
+
+as_status as_search_maxsim(const as_space* sp, const as_graph* gr, const double* queries, int64_t j, int64_t d, double tau, const double* weights,
+                           int32_t skip_zero, const as_groups* groups, int64_t n_groups, const as_subset* sub, int64_t* out_label,
+                           double* out_score, int64_t* out_len, double* out_lambda_q, int32_t* out_status) {
+    if (!sp || !gr || !queries || !groups || !out_label || !out_score || !out_len) {
+        set_err("as_search_maxsim: null argument");
+        return AS_EINVAL;
+    }
+    *out_len = 0;
+    if (n_groups < 1 || n_groups > SUBSET_TOPK) {
+        set_err("as_search_maxsim: n_groups must be in [1, %d], got %lld", SUBSET_TOPK, (long long)n_groups);
+        return AS_EINVAL;
+    }
+    AS_TRY(maxsim_checks("as_search_maxsim", sp, groups));
+    std::vector<double> wts, lq;
+    std::vector<int32_t> st;
+    AS_TRY(fused_prepare("as_search_maxsim", sp, gr, queries, j, d, tau, weights, 0, skip_zero, sub, out_lambda_q, out_status, wts, lq, st,
+                         &sp->maxsim_count[0], nullptr));
+    if (sub && sub->m == 0) return AS_OK;
+    const Candidates c("as_search_maxsim", sp, sub);
+    AS_TRY(c.status);
+    MaxsimCall call;
+    int64_t grp[SUBSET_TOPK], len = 0;
+    double sc[SUBSET_TOPK];
+    as_status s = maxsim_fold(sp, c.w, c.m, queries, j, tau, groups, wts, lq, st, &call);
+    if (s == AS_OK) s = maxsim_select(&call, std::min<int64_t>(n_groups, groups->count), grp, sc, &len);
+    s = c.fail(s);
+    maxsim_counts_add(sp, call);
+    AS_TRY(s);
+    // entries that came back NaN lie behind the last group that exists
+    int64_t n = 0;
+    for (; n < len && sc[n] == sc[n]; ++n) {
+        if (grp[n] < 0 || grp[n] >= groups->count) {
+            set_err("as_search_maxsim: the selection returned group %lld", (long long)grp[n]);
+            return AS_EHIP;
+        }
+        out_label[n] = groups->labels[(size_t)grp[n]];
+        out_score[n] = sc[n];
+    }
+    *out_len = n;
+    return AS_OK;
+}
+
+as_status as_score_maxsim(const as_space* sp, const as_graph* gr, const double* queries, int64_t j, int64_t d, double tau, const double* weights,
+                          int32_t skip_zero, const as_groups* groups, const as_subset* sub, const int64_t* labels, int64_t nl, double* out_scores,
+                          double* out_lambda_q, int32_t* out_status) {
+    if (!sp || !gr || !queries || !groups || nl < 0 || (nl > 0 && (!labels || !out_scores))) {
+        set_err("as_score_maxsim: null argument");
+        return AS_EINVAL;
+    }
+    AS_TRY(maxsim_checks("as_score_maxsim", sp, groups));
+    std::vector<int64_t> pos;   // the dense group number of every listed label
+    try {
+        pos.resize((size_t)nl);
+    } catch (const std::bad_alloc&) {
+        set_err("as_score_maxsim: out of host memory for %lld labels", (long long)nl);
+        return AS_ENOMEM;
+    }
+    for (int64_t t = 0; t < nl; ++t) {
+        const auto it = std::lower_bound(groups->labels.begin(), groups->labels.end(), labels[t]);
+        if (it == groups->labels.end() || *it != labels[t]) {
+            set_err("as_score_maxsim: label %lld is not one of the groups", (long long)labels[t]);
+            return AS_EINVAL;
+        }
+        pos[(size_t)t] = it - groups->labels.begin();
+    }
+    std::vector<double> wts, lq, F;
+    std::vector<int32_t> st;
+    AS_TRY(fused_prepare("as_score_maxsim", sp, gr, queries, j, d, tau, weights, 0, skip_zero, sub, out_lambda_q, out_status, wts, lq, st,
+                         &sp->maxsim_count[0], nullptr));
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    if (nl == 0) return AS_OK;
+    if (sub && sub->m == 0) {   // no item, no member
+        for (int64_t t = 0; t < nl; ++t) out_scores[t] = nan;
+        return AS_OK;
+    }
+    try {
+        F.assign((size_t)groups->count, nan);
+    } catch (const std::bad_alloc&) {
+        set_err("as_score_maxsim: out of host memory for %lld groups", (long long)groups->count);
+        return AS_ENOMEM;
+    }
+    const Candidates c("as_score_maxsim", sp, sub);
+    AS_TRY(c.status);
+    MaxsimCall call;
+    as_status s = maxsim_fold(sp, c.w, c.m, queries, j, tau, groups, wts, lq, st, &call);
+    if (s == AS_OK) s = maxsim_scores(&call, F.data());
+    s = c.fail(s);
+    maxsim_counts_add(sp, call);
+    AS_TRY(s);
+    for (int64_t t = 0; t < nl; ++t) out_scores[t] = F[(size_t)pos[(size_t)t]];
+    return AS_OK;
+}
+
+as_status as_maxsim_counters(const as_space* sp, int64_t* out, int32_t n) {
+    return counters_out("as_maxsim_counters", sp, out, n, sp ? sp->maxsim_count : nullptr, 5);
+}
+double as_maxsim_kernel_us(const as_space* sp, int32_t part) {
+    if (!sp || part < 0 || part > 2) return 0.0;
+    const double a = sp->maxsim_us[0].load(std::memory_order_relaxed), f = sp->maxsim_us[1].load(std::memory_order_relaxed);
+    return part == 0 ? a + f : (part == 1 ? a : f);
+}
 
 // ---------------------------------------------------------------- diversified search (extension; as_diverse.hip)
 // what both forms refuse before anything is launched, the pool step included

@@ -47,7 +47,7 @@ void dbg(const char* fmt, ...);
 
 }  // namespace as
 
-namespace as { struct SubsetWork; struct ListsWork; struct RangeWork; struct DiverseWork; struct FusedWork; struct GroupedWork; }
+namespace as { struct SubsetWork; struct ListsWork; struct RangeWork; struct DiverseWork; struct FusedWork; struct GroupedWork; struct MaxsimWork; }
 struct as_subset;
 
 // ---------------------------------------------------------------- handles
@@ -192,6 +192,12 @@ struct as_space {
     // grouped_us: the pick kernels of the last call under "grouped_timing" (as_grouped_kernel_us)
     mutable std::atomic<int64_t> grouped_count[7] = {};
     mutable std::atomic<double> grouped_us{0.0};
+    // as_search_maxsim / as_score_maxsim: they run on the caller's subset or on range_all.
+    // as_maxsim_counters: [0] calls that passed their checks, [1] vectors served, [2] pass-A launches, [3] 64-bit max-atomics
+    // pass A issued, [4] fold launches.  maxsim_us: pass A (with the memset of its cells) and the fold kernel of the last call
+    // under "maxsim_timing" (as_maxsim_kernel_us)
+    mutable std::atomic<int64_t> maxsim_count[5] = {};
+    mutable std::atomic<double> maxsim_us[2] = {};
     // as_search_diverse / as_search_diverse_batch: their buffers (as_diverse.hip), made on first use and grown on demand; the
     // selection step of a call is serialised by dmu (the pool step before it is an ordinary search and takes no lock of these).
     // as_diverse_counters: [0] calls that passed their checks, [1] select launches, [2] picks made, [3] dots computed, [4] pool
@@ -759,6 +765,8 @@ struct SubsetWork {
     FusedWork* fused = nullptr;
     // grouped search (as_grouped.hip): the cells, the collapsed scores and the picks, made on the first grouped call on this work
     GroupedWork* grouped = nullptr;
+    // late-interaction search (as_maxsim.hip): the cells, the accumulator, the weights and the flags, made on the first such call on this work
+    MaxsimWork* maxsim = nullptr;
 };
 as_status subset_work_create(const as_space* sp, int64_t cap, SubsetWork** out);
 void subset_work_free(SubsetWork* w);
@@ -783,7 +791,7 @@ as_status subset_batch_run(const as_space* sp, SubsetWork* w, int64_t m, const d
 void set_subset_batch_mib(int v);   // as_set_tuning("subset_batch_mib", v)
 constexpr int64_t SB_QC_MAX = 4096;   // queries of a chunk at most: the rows the selection serves at once
 // as_set_tuning("filtered_grid_cap", v): v > 0 clips gridDim.x of the filtered family's stride-loop kernels (the gather score
-// kernels, the radix select's passes, the lists' segments, the fused fold, the grouped picks, the range compaction) to at most v
+// kernels, the radix select's passes, the lists' segments, the fused and late-interaction folds, the grouped picks, the range compaction) to at most v
 // blocks, so that tests drive the later trips of those loops at small shapes; 0 (the default): every grid is what its call site
 // computes.  Results never depend on it.
 void set_filtered_grid_cap(int v);
@@ -792,6 +800,10 @@ int64_t filtered_grid(int64_t blocks);   // the grid a call site computed, under
 // the work's stream behind whatever wrote them: the first k by (score descending, position ascending) -> ids and scores; waits for
 // the stream.
 as_status subset_select_from(SubsetWork* w, const double* scores, int64_t m, int64_t k, int64_t* out_idx, double* out_score, int64_t* out_len);
+// ... with the position -> id table of the answer as an argument ([m] int32 on the device) in place of the work's ids: the same
+// kernels over positions that are not items of the subset (late-interaction search: position == dense group number).
+as_status subset_select_from_table(SubsetWork* w, const double* scores, const int32_t* pos_ids, int64_t m, int64_t k, int64_t* out_idx,
+                                   double* out_score, int64_t* out_len);
 // ... and over `rows` rows ([rows][ld]) at once: row t's list -> w->out[t] (len == min(k, m, SUBSET_TOPK)); waits for the stream.
 as_status subset_select_rows_from(SubsetWork* w, const double* scores, int64_t ld, int64_t m, int64_t k, int64_t rows);
 // a row's pinned result (w->out[row]) of k entries to the caller's arrays; AS_EHIP if the selection left another length there
@@ -906,6 +918,33 @@ as_status grouped_rows(GroupedCall* c, int64_t i0, int64_t rows, const double* s
 int64_t grouped_row_bytes(const as_groups* g, int64_t m, int64_t n_groups, int64_t per_group);   // SubsetChunkSink::row_bytes of a call
 void grouped_work_free(GroupedWork* g);
 void set_grouped_timing(int v);   // as_set_tuning("grouped_timing", 0 | 1)
+// pass A of round 0 of the pick kernel alone (as_grouped.hip): cells[row][g] <- the largest sel_ord key of group g in row `row` of
+// scores ([rows][ld]) over the work's m ids, 0 where the group has no member; the caller zeroes the cells first; *natom += the
+// global 64-bit max-atomics issued.  Queued on the work's stream; does not wait.
+as_status group_max_launch(SubsetWork* w, const as_groups* gs, const double* scores, int64_t ld, int64_t m, int64_t rows,
+                           unsigned long long* cells, unsigned long long* natom);
+// Late-interaction search (as_maxsim.hip): F(g) = the S13 sum over the served vectors j, ascending, of
+// w_j x the largest score of group g's members under vector j, folded into an accumulator [G] on the device (G = gs->count).
+// maxsim_begin: room for the call, ONE upload of the weights and served flags (status AS_EZEROLAMBDA: not served).  maxsim_chunk:
+// rows i0 .. i0 + nb - 1 of the call, [nb][ld] on the device -- the sink of subset_batch_run (row_bytes = 8 G); per run of served
+// rows one memset of the cells and one pass-A launch, then ONE fold launch for the chunk; it does not wait; a chunk without a
+// served row launches nothing.  maxsim_select: the first k groups by (F descending, group number ascending) -> group numbers and
+// scores; waits.  maxsim_scores: the accumulator to out [G]; waits.  Both leave the counters and times of the call in *c.
+struct MaxsimCall {
+    SubsetWork* w = nullptr;
+    const as_groups* g = nullptr;
+    int64_t m = 0;
+    bool fresh = true;             // no served row folded yet: the next fold launch initialises the accumulator
+    bool timing = false, timed = false;
+    int64_t served = 0, passa = 0, atoms = 0, folds = 0;   // vectors served, pass-A launches, max-atomics issued, fold launches
+    double us[2] = {0.0, 0.0};     // pass A (with its memsets), the fold kernel: microseconds under "maxsim_timing"
+};
+as_status maxsim_begin(SubsetWork* w, const as_groups* gs, int64_t m, int64_t j, const double* weights, const int32_t* status, MaxsimCall* c);
+as_status maxsim_chunk(MaxsimCall* c, int64_t i0, int64_t nb, const double* scores, int64_t ld);
+as_status maxsim_select(MaxsimCall* c, int64_t k, int64_t* out_group, double* out_score, int64_t* out_len);
+as_status maxsim_scores(MaxsimCall* c, double* out);
+void maxsim_work_free(MaxsimWork* x);
+void set_maxsim_timing(int v);   // as_set_tuning("maxsim_timing", 0 | 1)
 // Diversified search (as_diverse.hip): the greedy of S12 over b pools -- pool i = pool_idx / pool_score + i * kk,
 // pool_len[i] <= kk entries in the order the route returned them (0: a query that is not served) -- n picks wanted, diversity delta.
 // Pick t of query i -> out_idx / out_score / out_margin (may be null) + i * nn + t, nn = min(n, kk); out_len[i] = min(n, pool_len[i]).

@@ -13,6 +13,7 @@
 #include <new>
 
 #include "as_common.hpp"
+#include "as_fused_step.hpp"   // fused_step: one step of S13, never contracted into an FMA
 
 namespace as {
 
@@ -24,16 +25,6 @@ typedef double f64x2 __attribute__((ext_vector_type(2)));
 constexpr int FA_THREADS = 256;
 constexpr int FA_ROWS = 8;             // rows whose loads are in flight together
 constexpr int FA_BLOCKS_PER_CU = 8;    // the grid: that many blocks per CU at most, the rest is the grid-stride loop
-
-// One step of S13 for one position: every product and every sum rounded once, never contracted into an FMA.
-#pragma clang fp contract(off)
-template <int MODE>
-__device__ __forceinline__ double fused_step(double f, double wj, double s, bool have) {
-    const double t = wj * s;
-    if (!have) return t;
-    if (MODE == 0) return f + t;
-    return (t > f || f != f) ? t : f;   // the first largest term wins; a NaN never displaces a number
-}
 
 // acc[i] <- the fold of rows 0 .. nb - 1 of scores ([nb][ld]) at position i < m onto acc[i], rows ascending; a row whose flag is 0
 // is skipped.  fresh: the accumulator holds nothing yet -- the first served row of the chunk initialises it (no memset, no 0 + t).

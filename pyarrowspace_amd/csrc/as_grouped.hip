@@ -215,6 +215,23 @@ static as_status pick_round(GroupedCall* c, const GroupPickArgs& a, int64_t rows
     return AS_OK;
 }
 
+// Pass A of round 0 alone, for late-interaction search (as_maxsim.hip): cells[row][g] <- the largest sel_ord key of group g among
+// the m positions of row `row` of scores ([rows][ld]); the caller has zeroed the cells (0: no member) and *natom counts the global
+// max-atomics issued.  The COMBINE form where the groups fit its table, else the plain form -- the choice pick_round makes.
+as_status group_max_launch(SubsetWork* w, const as_groups* gs, const double* scores, int64_t ld, int64_t m, int64_t rows,
+                           unsigned long long* cells, unsigned long long* natom) {
+    if (rows <= 0 || m <= 0) return AS_OK;
+    GroupPickArgs a;
+    a.scores = scores; a.ld = ld; a.m = m; a.ids = w->ids; a.dense = gs->dense_dev; a.slot_of_group = nullptr; a.G = gs->count;
+    a.cell_hi = cells; a.cell_pos = nullptr; a.prev_hi = nullptr; a.prev_pos = nullptr; a.cells_ld = gs->count;
+    a.nslots = (int)std::min<int64_t>(gs->count, 0x7fffffff); a.natom = natom;
+    const dim3 grid(pick_grid(w, m), (unsigned)rows);
+    if (a.nslots <= GP_LDS_SLOTS) hipLaunchKernelGGL((group_pick_kernel<true, false, true>), grid, dim3(GP_THREADS), 0, w->stream, a);
+    else hipLaunchKernelGGL((group_pick_kernel<true, false, false>), grid, dim3(GP_THREADS), 0, w->stream, a);
+    AS_HIP(hipGetLastError());
+    return AS_OK;
+}
+
 as_status grouped_rows(GroupedCall* c, int64_t i0, int64_t rows, const double* scores, int64_t ld) {
     SubsetWork* w = c->w;
     const as_groups* gs = c->g;

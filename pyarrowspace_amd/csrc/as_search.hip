@@ -3663,6 +3663,10 @@ int32_t as_set_tuning(const char* key, int32_t value) {
         set_grouped_timing(value);
         return 0;
     }
+    if (key && !strcmp(key, "maxsim_timing")) {
+        set_maxsim_timing(value);
+        return 0;
+    }
     if (key && !strcmp(key, "fused_batch_timing")) {
         set_fused_batch_timing(value);
         return 0;

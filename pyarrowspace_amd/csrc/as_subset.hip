@@ -432,6 +432,7 @@ void subset_work_free(SubsetWork* w) {
     range_work_free(w->range);
     fused_work_free(w->fused);
     grouped_work_free(w->grouped);
+    maxsim_work_free(w->maxsim);
     for (int i = 0; i < 2; ++i)
         if (w->ev[i]) (void)hipEventDestroy(w->ev[i]);
     if (w->stream) (void)hipStreamDestroy(w->stream);
@@ -519,9 +520,9 @@ static as_status subset_wait(SubsetWork* w, bool fresh = false) {
 
 // The first k of each of `rows` rows of m scores ([rows][ld]) by (score descending, position ascending) -> w->out[row], queued on
 // the work's stream.  m <= SUBSET_TOPK: the sort alone; else one memset, the radix passes, collect and sort.
-static as_status subset_select_rows(SubsetWork* w, const double* scores, int64_t ld, int64_t m, int64_t k, int64_t rows) {
+// ids: the position -> id table of the answer ([m] on the device): the work's ids, or a caller's own.
+static as_status subset_select_rows(SubsetWork* w, const double* scores, const int32_t* ids, int64_t ld, int64_t m, int64_t k, int64_t rows) {
     const unsigned ny = (unsigned)rows;
-    const int32_t* ids = w->ids;
     SubsetOut* out = w->out;
     if (m <= SUBSET_TOPK) {
         hipLaunchKernelGGL(subset_sort_batch_kernel, dim3(1, ny), dim3(1024), 0, w->stream, scores, ld, ids, m, (int)k, (const int32_t*)nullptr,
@@ -561,17 +562,22 @@ as_status subset_select(SubsetWork* w, int64_t m, int64_t k, int64_t* out_idx, d
     *out_len = 0;
     if (m <= 0 || k <= 0) return AS_OK;
     k = std::min<int64_t>(std::min<int64_t>(k, m), SUBSET_TOPK);
-    AS_TRY(subset_select_rows(w, w->scores, m, m, k, 1));
+    AS_TRY(subset_select_rows(w, w->scores, w->ids, m, m, k, 1));
     AS_TRY(subset_wait(w, true));
     return subset_list_out(w->out, k, out_idx, out_score, out_len);
 }
 
 as_status subset_select_from(SubsetWork* w, const double* scores, int64_t m, int64_t k, int64_t* out_idx, double* out_score, int64_t* out_len) {
+    return subset_select_from_table(w, scores, w->ids, m, k, out_idx, out_score, out_len);
+}
+
+as_status subset_select_from_table(SubsetWork* w, const double* scores, const int32_t* pos_ids, int64_t m, int64_t k, int64_t* out_idx,
+                                   double* out_score, int64_t* out_len) {
     *out_len = 0;
     if (m <= 0 || k <= 0) return AS_OK;
     k = std::min<int64_t>(std::min<int64_t>(k, m), SUBSET_TOPK);
     AS_TRY(subset_reserve(w, 1, w->cap, 1, true, true));   // (nothing to do unless a larger call's allocation failed)
-    AS_TRY(subset_select_rows(w, scores, m, m, k, 1));
+    AS_TRY(subset_select_rows(w, scores, pos_ids, m, m, k, 1));
     AS_HIP(hipStreamSynchronize(w->stream));
     return subset_list_out(w->out, k, out_idx, out_score, out_len);
 }
@@ -585,7 +591,7 @@ as_status subset_select_rows_from(SubsetWork* w, const double* scores, int64_t l
         AS_TRY(reserve_or_err(w->state, rows * (SEL_PASSES + 1), "subset selection states"));
         AS_TRY(reserve_or_err(w->sel_pos, rows * SUBSET_TOPK, "subset selected positions"));
     }
-    AS_TRY(subset_select_rows(w, scores, ld, m, k, rows));
+    AS_TRY(subset_select_rows(w, scores, w->ids, ld, m, k, rows));
     AS_HIP(hipStreamSynchronize(w->stream));
     return AS_OK;
 }
@@ -635,7 +641,7 @@ as_status subset_batch_run(const as_space* sp, SubsetWork* w, int64_t m, const d
         AS_HIP(hipGetLastError());
         if (w->timing) AS_HIP(hipEventRecord(w->ev[1], w->stream));
         if (sel) {
-            AS_TRY(subset_select_rows(w, w->scores, m, m, k, nb));
+            AS_TRY(subset_select_rows(w, w->scores, w->ids, m, m, k, nb));
         } else if (sink) {
             AS_TRY(sink->fn(sink->ctx, w, i0, nb, w->scores, m));   // (range search's waits for the stream: the wait below finds it idle)
         } else {
@@ -694,7 +700,7 @@ as_status subset_sweep_run(const as_space* sp, SubsetWork* w, int64_t m, const d
         if (w->timing) AS_HIP(hipEventRecord(w->ev[1], w->stream));
         counts[0] += 1;
         counts[1] += ng;
-        if (sel) AS_TRY(subset_select_rows(w, w->scores, m, m, k, ng));
+        if (sel) AS_TRY(subset_select_rows(w, w->scores, w->ids, m, m, k, ng));
         else
             for (int64_t j = 0; j < ng; ++j)
                 AS_HIP(hipMemcpyAsync(out_scores + row[g0 + j] * m, w->scores + j * m, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, w->stream));
@@ -745,7 +751,7 @@ as_status subset_batch_sweep_run(const as_space* sp, SubsetWork* w, int64_t m, c
             if (w->timing) AS_HIP(hipEventRecord(w->ev[1], w->stream));
             counts[0] += 1;
             counts[1] += ng;
-            if (sel) AS_TRY(subset_select_rows(w, w->scores, m, m, k, nb * ng));
+            if (sel) AS_TRY(subset_select_rows(w, w->scores, w->ids, m, m, k, nb * ng));
             else {
                 // plane j of every query of a run of served queries in one strided copy: a zero-lambda query's rows stay unwritten
                 AS_TRY(for_served_runs(status, i0, nb, [&](int64_t t, int64_t u) -> as_status {
