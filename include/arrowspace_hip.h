@@ -482,7 +482,10 @@ void as_enable_search_stats(int32_t enabled);
  * (as_grouped_kernel_us).  "maxsim_timing" = 1 / 0: HIP events around late-interaction search's pass A and fold kernel
  * (as_maxsim_kernel_us).  "fused_batch_timing" = 1 / 0: HIP events around the batched fused forms' accumulate kernel
  * (as_fused_batch_kernel_us); "fused_batch_mib" = MiB of accumulator rows one group of needs of those forms may hold (default
- * 256; 0: the default; v < 0: -v KiB, so that tests reach several groups at small shapes).  "filtered_grid_cap" = v > 0: gridDim.x of the filtered family's stride-loop kernels (the gather score
+ * 256; 0: the default; v < 0: -v KiB, so that tests reach several groups at small shapes).  "maxsim_batch_timing" = 1 / 0: HIP
+ * events around batched late-interaction search's pass A and segmented fold kernel (as_maxsim_batch_kernel_us);
+ * "maxsim_batch_mib" = MiB of accumulator rows one group of needs of those forms may hold (same values as "fused_batch_mib").
+ * "filtered_grid_cap" = v > 0: gridDim.x of the filtered family's stride-loop kernels (the gather score
  * kernels of the subset and list forms, the radix select's passes, the fused and late-interaction folds, the grouped picks, the range compaction) is
  * clipped to at most v blocks, so tests reach the later trips of those loops at small shapes; 0 (default): no clip.
  * Returns 0, or 1 for an unknown key.  Results never depend on it. */
@@ -873,6 +876,48 @@ as_status as_maxsim_counters(const as_space* sp, int64_t* out, int32_t n);
  * 1) (HIP events; off by default), summed over its chunks: part 1: the memsets of the cells and pass A; part 2: the fold kernel;
  * part 0: both.  NULL or another part: 0 */
 double as_maxsim_kernel_us(const as_space* sp, int32_t part);
+/* ---- Extension: batched late-interaction search.  b >= 1 NEEDS in one call: need y is the vectors offsets[y] ..
+ * offsets[y + 1] - 1 of the nv flattened query vectors ([nv][d], HOST memory), J_y = offsets[y + 1] - offsets[y] >= 1 of them, with
+ * the flattened finite weights weights[nv] (NULL: 1/J_y each inside need y).  offsets: int64 [b + 1], starts at 0, increases
+ * strictly, ends at nv.  tau, skip_zero, the groups, n_groups and the subset are common to the call.  The per-vector scores are
+ * the bits as_score_items_batch writes for the nv vectors (lambda_q of every vector from ONE as_search_batch over all nv); m_v(g)
+ * is as_search_maxsim's group maximum per flattened vector, and need y's F is the fold of as_search_maxsim over ITS served rows,
+ * ascending, every product and sum rounded once.  b == 1 is as_search_maxsim / as_score_maxsim bit for bit.
+ * A vector whose lambda_q is 0: skip_zero == 0: the whole call returns AS_EZEROLAMBDA before any gather is launched and no answer
+ * is written; skip_zero != 0: it is left out of its need (the other weights are not renormalised); a need with no vector left is
+ * not served -- out_len[y] = 0 / a row of NaN -- and the call still returns AS_OK, also when no need at all is served (nothing is
+ * launched then).  out_status ([b], may be NULL): 0 or AS_EZEROLAMBDA per NEED (skip_zero == 0: a need that holds such a
+ * vector); out_lambda_q ([nv], may be NULL): per flattened vector; both are written whenever the lambda_q step ran.
+ * as_search_maxsim_batch: need y's groups whose F is not NaN by (F descending, label ascending; +0.0 and -0.0 tie), the first
+ * min(n_groups, such groups) of them -> out_label / out_score + y * n_groups, out_len[y].  as_score_maxsim_batch: F of every
+ * listed label -> out_scores[y * nl + l], the caller's order, duplicates kept, NaN for a group without a member.
+ * Checked before any handle is touched, with nothing written: a null argument ("<name>: null argument"), b < 1, offsets that do
+ * not start at 0, increase strictly and end at nv -> AS_EINVAL.  (From there on a refusal of the search form leaves every
+ * out_len[y] == 0 and nothing else written.)  Then as as_search_maxsim: n_groups outside [1, 1024], a groups
+ * handle or a subset of another space, a label the handle does not hold, a NaN or infinite weight, wrong d, a non-finite tau ->
+ * AS_EINVAL; a shard of a row-sharded index -> AS_EUNSUPPORTED.
+ * Cost: ONE as_search_batch over the nv vectors; then the needs are taken Gn at a time, Gn = the accumulator rows of G doubles
+ * (G = as_groups_count) that fit the "maxsim_batch_mib" budget (1 <= Gn <= 4096): the group's vectors go through the batched
+ * filtered forms' gather and fp64 matrix product as ONE list of rows in chunks under "subset_batch_mib" (which counts the 8 G
+ * bytes of a vector's cells beside its m scores); per chunk one memset of the cells, the first pass of grouped search's pick
+ * kernel per run of served rows and ONE segmented fold kernel that folds every need's rows of the chunk into that need's
+ * accumulator row; after the group's last chunk one batched exact selection over the accumulator rows (the search form: b x
+ * n_groups entries cross to the host) or one pick kernel and one copy of the listed F (the score form: b x nl doubles cross).
+ * Answers never depend on Gn, the chunks or the grid.  The buffers are those of the single forms. */
+as_status as_search_maxsim_batch(const as_space* sp, const as_graph* gr, const double* queries, const int64_t* offsets, int64_t b, int64_t nv,
+                                 int64_t d, double tau, const double* weights, int32_t skip_zero, const as_groups* groups, int64_t n_groups,
+                                 const as_subset* sub, int64_t* out_label, double* out_score, int64_t* out_len, double* out_lambda_q,
+                                 int32_t* out_status);
+as_status as_score_maxsim_batch(const as_space* sp, const as_graph* gr, const double* queries, const int64_t* offsets, int64_t b, int64_t nv,
+                                int64_t d, double tau, const double* weights, int32_t skip_zero, const as_groups* groups, const as_subset* sub,
+                                const int64_t* labels, int64_t nl, double* out_scores, double* out_lambda_q, int32_t* out_status);
+/* out[0] calls of the two entries above that passed their checks, [1] needs of those calls, [2] vectors served, [3] pass-A
+ * launches, [4] 64-bit max-atomics pass A issued, [5] fold launches, [6] lambda_q steps run (one per call), [7] need groups run */
+as_status as_maxsim_batch_counters(const as_space* sp, int64_t* out, int32_t n);
+/* measurement: device microseconds of the last batched late-interaction call on this space that ran under
+ * as_set_tuning("maxsim_batch_timing", 1) (HIP events; off by default), summed over its chunks: part 1: the memsets of the cells
+ * and pass A; part 2: the segmented fold kernel; part 0: both.  NULL or another part: 0 */
+double as_maxsim_batch_kernel_us(const as_space* sp, int32_t part);
 
 /* ---- index persistence (extension; the reference exposes none): one flat file
  * holding the items, lambdas and graph arrays.  Loading re-ingests the items and uploads the

@@ -980,6 +980,22 @@ class ArrowSpace:
         grp, sub = self._grouped_handles(groups, subset)
         return Q, w, skip, tau, ng, grp, sub
 
+    @staticmethod
+    def _maxsim_labels(labels, grp) -> np.ndarray:
+        """The listed group labels of a score form as int64 [L] contiguous.  TypeError: a float or boolean dtype; ValueError: a
+        wrong rank, a label that is not one of the groups."""
+        lab = np.asarray(labels)
+        if lab.size == 0 and lab.ndim == 1:
+            lab = np.empty(0, dtype=np.int64)
+        if lab.dtype.kind not in "iu":
+            raise TypeError(f"argument 'labels': expected integer group labels, got dtype {lab.dtype}")
+        if lab.ndim != 1:
+            raise ValueError(f"argument 'labels': expected a 1-D sequence of group labels, got shape {lab.shape}")
+        known = np.isin(lab, grp._labels)
+        if not known.all():
+            raise ValueError(f"argument 'labels': label {int(lab[np.flatnonzero(~known)[0]])} is not one of the groups")
+        return np.ascontiguousarray(lab, dtype=np.int64)
+
     def search_maxsim(self, items, gl: GraphLaplacian, tau: float, groups, n_groups: int, weights=None, subset=None, on_zero_lambda="raise"):
         """Extension: late-interaction search (MaxSim), ONE answer to J query vectors [J, D] over GROUPS of items ->
         list[(label, F)]: the first min(n_groups, groups with a non-NaN F) groups by (F descending, label ascending),
@@ -1010,17 +1026,7 @@ class ArrowSpace:
         member inside the subset.  A label that is not one of the groups raises ValueError.  Costs what `search_maxsim`
         costs without the selection: the accumulator's G doubles cross to the host."""
         Q, w, skip, tau, _, grp, sub = self._maxsim_args(items, gl, tau, groups, 1, weights, subset, on_zero_lambda)
-        lab = np.asarray(labels)
-        if lab.size == 0 and lab.ndim == 1:
-            lab = np.empty(0, dtype=np.int64)
-        if lab.dtype.kind not in "iu":
-            raise TypeError(f"argument 'labels': expected integer group labels, got dtype {lab.dtype}")
-        if lab.ndim != 1:
-            raise ValueError(f"argument 'labels': expected a 1-D sequence of group labels, got shape {lab.shape}")
-        known = np.isin(lab, grp._labels)
-        if not known.all():
-            raise ValueError(f"argument 'labels': label {int(lab[np.flatnonzero(~known)[0]])} is not one of the groups")
-        lab = np.ascontiguousarray(lab, dtype=np.int64)
+        lab = self._maxsim_labels(labels, grp)
         out = np.empty(lab.shape[0], dtype=np.float64)
         st = _L.as_score_maxsim(self._h, gl._h, Q.ctypes.data_as(C.c_void_p), Q.shape[0], Q.shape[1], tau,
                                 None if w is None else w.ctypes.data_as(C.c_void_p), skip, grp._h, _handle(sub),
@@ -1032,6 +1038,68 @@ class ArrowSpace:
         """Extension: late-interaction calls on this space since it was made that passed their checks, the vectors they
         served, the group-maximum (pass A) launches, the 64-bit max-atomics those issued and the fold launches."""
         return _counters(_L.as_maxsim_counters, self._h, ("calls", "vectors_served", "pass_a_launches", "max_atomics", "fold_launches"))
+
+    def _maxsim_batch_args(self, needs, gl, tau, groups, n_groups, weights, subset, on_zero_lambda):
+        """What the batched late-interaction forms check before they touch a handle: the batched fused forms' checks (needs,
+        weights, the zero-lambda setting), then the grouped forms' (n_groups, tau, handles of this space)."""
+        V, offs, w, _, skip = _fused_batch_args(needs, gl, weights, "sum", on_zero_lambda)
+        tau, ng, _ = _grouped_args(gl, tau, n_groups, 1)
+        grp, sub = self._grouped_handles(groups, subset)
+        return V, offs, w, skip, tau, ng, grp, sub
+
+    def search_maxsim_batch(self, needs, gl: GraphLaplacian, tau: float, groups, n_groups: int, weights=None, subset=None,
+                            on_zero_lambda="raise"):
+        """Extension: batched late-interaction search, B needs of J_b query vectors each in ONE call -> list of B
+        lists[(label, F)]; list b is `search_maxsim`'s answer for need b: the first min(n_groups, groups with a non-NaN F_b)
+        groups by (F_b descending, label ascending), 1 <= n_groups <= 1024.  `needs` and `weights` are `search_fused_batch`'s:
+        a 3-D array (B, J, D) or a sequence of B 2-D arrays (J_b, D), the J_b may differ; weights None (1/J_b each), a (B, J)
+        array, or a sequence of B 1-D sequences of J_b finite numbers, a None entry meaning the default for that need.
+        `groups` and `subset` are `search_maxsim`'s; they, tau, n_groups and on_zero_lambda are common to the call.  With V
+        the vectors of all needs flattened in need order, the per-vector scores are the bits of `score_items_batch(V, gl,
+        tau, ids)` -- lambda_q of every vector comes from ONE `search_batch` over V -- the group maxima are `search_maxsim`'s
+        per flattened vector, and F_b is the fold over need b's OWN served rows, ascending.  B = 1 is `search_maxsim` bit for
+        bit; with every J_b = 1 and weight 1.0 the call names the heads of `search_batch_grouped`; with every item its own
+        group it is `search_fused_batch` in "sum" mode; whether a need's answer depends on the OTHER needs of the call is
+        `search_batch`'s property and is not promised.  A vector whose lambda_q is 0: on_zero_lambda="raise" panics as
+        `search` does, for the whole call, before anything is gathered; "skip" leaves it out of its need (the other weights
+        are not renormalised), a need with no vector left gets [] and the other needs are served.  Costs one `search_batch`
+        over V, then the subset's rows are gathered once per 64 VECTORS of the call, whatever need they belong to; per chunk
+        one group-maximum pass per run of served vectors and ONE segmented pass that folds every need's maxima into that
+        need's accumulator on the device; one batched selection follows: B x n_groups entries cross to the host."""
+        V, offs, w, skip, tau, ng, grp, sub = self._maxsim_batch_args(needs, gl, tau, groups, n_groups, weights, subset, on_zero_lambda)
+        b = offs.shape[0] - 1
+        (label, sc, ln), stt = _hit_buffers(b, ng), _statuses(b)
+        st = _L.as_search_maxsim_batch(self._h, gl._h, V.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p), b, V.shape[0], V.shape[1],
+                                       tau, None if w is None else w.ctypes.data_as(C.c_void_p), skip, grp._h, ng, _handle(sub),
+                                       label.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p), ln.ctypes.data_as(C.c_void_p), None,
+                                       stt.ctypes.data_as(C.c_void_p))
+        _check(st)
+        return _hit_lists(label, sc, ln, b, ng)
+
+    def score_maxsim_batch(self, needs, gl: GraphLaplacian, tau: float, groups, labels, weights=None, subset=None,
+                           on_zero_lambda="raise") -> np.ndarray:
+        """Extension: the late-interaction scores F_b of `search_maxsim_batch` (same needs, weights, subset and zero-lambda
+        rule) for each listed group label -> ndarray[float64] of shape (B, len(labels)): the caller's order, duplicates kept,
+        NaN for a group without a member inside the subset.  A label that is not one of the groups raises ValueError.  B = 1
+        is `score_maxsim`.  Under on_zero_lambda="skip" a need with no vector left gets a row of NaN.  Costs what
+        `search_maxsim_batch` costs without the selection: the listed groups are picked on the device and B x len(labels)
+        doubles cross to the host, the B x G accumulators never do."""
+        V, offs, w, skip, tau, _, grp, sub = self._maxsim_batch_args(needs, gl, tau, groups, 1, weights, subset, on_zero_lambda)
+        lab = self._maxsim_labels(labels, grp)
+        b = offs.shape[0] - 1
+        out = np.empty((b, lab.shape[0]), dtype=np.float64)
+        st = _L.as_score_maxsim_batch(self._h, gl._h, V.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p), b, V.shape[0], V.shape[1],
+                                      tau, None if w is None else w.ctypes.data_as(C.c_void_p), skip, grp._h, _handle(sub),
+                                      lab.ctypes.data_as(C.c_void_p), lab.shape[0], out.ctypes.data_as(C.c_void_p), None, None)
+        _check(st)
+        return out
+
+    def maxsim_batch_counters(self) -> dict:
+        """Extension: batched late-interaction calls on this space since it was made that passed their checks, their needs,
+        the vectors they served, the group-maximum (pass A) launches, the 64-bit max-atomics those issued, the fold launches,
+        the lambda_q steps (one per call) and the need groups run."""
+        return _counters(_L.as_maxsim_batch_counters, self._h,
+                         ("calls", "needs", "vectors_served", "pass_a_launches", "max_atomics", "fold_launches", "lambda_steps", "need_groups"))
 
     @staticmethod
     def _diverse_params(n, diversity) -> tuple[int, float]:

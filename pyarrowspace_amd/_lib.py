@@ -64,6 +64,7 @@ SYMBOLS = [
     "as_groups_create", "as_groups_count", "as_groups_free", "as_search_grouped", "as_search_grouped_batch", "as_grouped_counters",
     "as_grouped_kernel_us",
     "as_search_maxsim", "as_score_maxsim", "as_maxsim_counters", "as_maxsim_kernel_us",
+    "as_search_maxsim_batch", "as_score_maxsim_batch", "as_maxsim_batch_counters", "as_maxsim_batch_kernel_us",
 ]
 
 _lib = None
@@ -268,6 +269,10 @@ def load():
         "as_score_maxsim": (i32, [vp, vp, vp, i64, i64, f64, vp, i32, vp, vp, vp, i64, vp, vp, vp]),
         "as_maxsim_counters": (i32, [vp, vp, i32]),
         "as_maxsim_kernel_us": (f64, [vp, i32]),
+        "as_search_maxsim_batch": (i32, [vp, vp, vp, vp, i64, i64, i64, f64, vp, i32, vp, i64, vp, vp, vp, vp, vp, vp]),
+        "as_score_maxsim_batch": (i32, [vp, vp, vp, vp, i64, i64, i64, f64, vp, i32, vp, vp, vp, i64, vp, vp, vp]),
+        "as_maxsim_batch_counters": (i32, [vp, vp, i32]),
+        "as_maxsim_batch_kernel_us": (f64, [vp, i32]),
         "as_subset_set_timing": (None, [vp, i32]),
         "as_subset_kernel_us": (f64, [vp]),
         "as_gang_counters": (i32, [vp, vp, i32]),

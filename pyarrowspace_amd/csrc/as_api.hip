@@ -1795,6 +1795,7 @@ static as_status fused_batch_offsets(const char* who, const int64_t* offsets, in
 }
 // What both forms refuse before anything is launched, then lambda_q and the status of every vector from ONE as_search_batch call
 // over the nv vectors, then S15's zero-lambda rule: `nst` is the status per need.  `wts`: the caller's weights, or 1/J_b each.
+// calls, needs, steps: the family's counters of calls that passed their checks, of their needs and of lambda_q steps.
 struct FusedBatchArgs {
     std::vector<double> wts, lq;
     std::vector<int32_t> st, nst;
@@ -1802,7 +1803,8 @@ struct FusedBatchArgs {
 };
 as_status fused_batch_prepare(const char* who, const as_space* sp, const as_graph* gr, const double* queries, const int64_t* offsets, int64_t b,
                               int64_t d, double tau, const double* weights, int32_t mode, int32_t skip_zero, const as_subset* sub,
-                              double* out_lambda_q, int32_t* out_status, FusedBatchArgs& a) {
+                              double* out_lambda_q, int32_t* out_status, FusedBatchArgs& a, std::atomic<int64_t>* calls,
+                              std::atomic<int64_t>* needs, std::atomic<int64_t>* steps) {
     const int64_t nv = offsets[b];
     if (mode != 0 && mode != 1) {
         set_err("%s: mode must be 0 (sum) or 1 (max), got %d", who, (int)mode);
@@ -1827,9 +1829,9 @@ as_status fused_batch_prepare(const char* who, const as_space* sp, const as_grap
         set_err("%s: out of host memory for %lld weights", who, (long long)nv);
         return AS_ENOMEM;
     }
-    sp->fused_batch_count[0].fetch_add(1, std::memory_order_relaxed);
-    sp->fused_batch_count[1].fetch_add(b, std::memory_order_relaxed);
-    AS_TRY(batch_lambda_step(who, sp, gr, queries, nv, d, tau, &sp->fused_batch_count[4], a.lq, a.st, out_lambda_q, nullptr));
+    calls->fetch_add(1, std::memory_order_relaxed);
+    needs->fetch_add(b, std::memory_order_relaxed);
+    AS_TRY(batch_lambda_step(who, sp, gr, queries, nv, d, tau, steps, a.lq, a.st, out_lambda_q, nullptr));
     bool refused = false;
     for (int64_t y = 0; y < b; ++y) {
         int64_t served = 0;
@@ -1883,7 +1885,7 @@ as_status as_search_fused_batch(const as_space* sp, const as_graph* gr, const do
     for (int64_t y = 0; y < b; ++y) out_len[y] = 0;
     FusedBatchArgs a;
     AS_TRY(fused_batch_prepare("as_search_fused_batch", sp, gr, queries, offsets, b, d, tau, weights, mode, skip_zero, sub, out_lambda_q,
-                               out_status, a));
+                               out_status, a, &sp->fused_batch_count[0], &sp->fused_batch_count[1], &sp->fused_batch_count[4]));
     if ((sub && sub->m == 0) || !a.any) return AS_OK;
     const Candidates c("as_search_fused_batch", sp, sub);
     AS_TRY(c.status);
@@ -1894,7 +1896,7 @@ as_status as_search_fused_batch(const as_space* sp, const as_graph* gr, const do
         const int64_t gn = std::min<int64_t>(call.gmax, b - g0);
         if (!fused_batch_group_served(a, g0, gn)) continue;
         s = fused_batch_fold_group(sp, c.w, c.m, queries, offsets, g0, gn, tau, a, &call);
-        if (s == AS_OK) s = subset_select_rows_from(c.w, fused_acc(c.w), c.m, c.m, k, gn);   // -> c.w->out[t]; waits
+        if (s == AS_OK) s = subset_select_rows_from(c.w, fused_acc(c.w), c.w->ids, c.m, c.m, k, gn);   // -> c.w->out[t]; waits
         for (int64_t t = 0; s == AS_OK && t < gn; ++t) {
             const int64_t y = g0 + t;
             if (a.nst[(size_t)y] == 0) s = subset_list_out(c.w->out + t, k, out_idx + y * kk, out_score + y * kk, out_len + y);
@@ -1920,7 +1922,7 @@ as_status as_score_fused_batch(const as_space* sp, const as_graph* gr, const dou
     AS_TRY(ids_in_range("as_score_fused_batch", sp, ids_host, m));
     FusedBatchArgs a;
     AS_TRY(fused_batch_prepare("as_score_fused_batch", sp, gr, queries, offsets, b, d, tau, weights, mode, skip_zero, nullptr, out_lambda_q,
-                               out_status, a));
+                               out_status, a, &sp->fused_batch_count[0], &sp->fused_batch_count[1], &sp->fused_batch_count[4]));
     if (m == 0) return AS_OK;
     // an unserved need's row: NaN
     const auto nan_rows = [&](int64_t g0, int64_t gn) {
@@ -2237,6 +2239,159 @@ as_status as_maxsim_counters(const as_space* sp, int64_t* out, int32_t n) {
 double as_maxsim_kernel_us(const as_space* sp, int32_t part) {
     if (!sp || part < 0 || part > 2) return 0.0;
     const double a = sp->maxsim_us[0].load(std::memory_order_relaxed), f = sp->maxsim_us[1].load(std::memory_order_relaxed);
+    return part == 0 ? a + f : (part == 1 ? a : f);
+}
+
+// ---------------------------------------------------------------- batched late-interaction search (extension; as_maxsim.hip)
+namespace {
+as_status maxsim_batch_sink_chunk(void* ctx, SubsetWork*, int64_t i0, int64_t nb, const double* scores, int64_t ld) {
+    return maxsim_batch_chunk((MaxsimBatchCall*)ctx, i0, nb, scores, ld);
+}
+// needs g0 .. g0 + gn - 1 (one of them served): their slice of the vectors scored chunk by chunk, every chunk turned into group
+// maxima and folded into the group's accumulator rows; the stream is left busy at most with the last fold
+as_status maxsim_batch_fold_group(const as_space* sp, SubsetWork* w, int64_t m, const double* queries, const int64_t* offsets, int64_t g0, int64_t gn,
+                                  double tau, const as_groups* groups, const FusedBatchArgs& a, MaxsimBatchCall* call) {
+    const int64_t v0 = offsets[g0], v1 = offsets[g0 + gn];
+    maxsim_batch_group(call, g0, gn);
+    SubsetChunkSink sink{maxsim_batch_sink_chunk, call};
+    sink.row_bytes = groups->count * (int64_t)sizeof(unsigned long long);
+    return subset_batch_run(sp, w, m, queries + v0 * sp->d, v1 - v0, a.lq.data() + v0, a.st.data() + v0, tau, 0, 0, nullptr, nullptr, nullptr, nullptr,
+                            &sink);
+}
+void maxsim_batch_counts_add(const as_space* sp, const MaxsimBatchCall& call) {
+    sp->maxsim_batch_count[2].fetch_add(call.served, std::memory_order_relaxed);
+    sp->maxsim_batch_count[3].fetch_add(call.passa, std::memory_order_relaxed);
+    sp->maxsim_batch_count[4].fetch_add(call.atoms, std::memory_order_relaxed);
+    sp->maxsim_batch_count[5].fetch_add(call.folds, std::memory_order_relaxed);
+    sp->maxsim_batch_count[7].fetch_add(call.groups, std::memory_order_relaxed);
+    for (int t = 0; t < 2; ++t) sp->maxsim_batch_us[t].store(call.us[t], std::memory_order_relaxed);
+}
+}  // namespace
+
+as_status as_search_maxsim_batch(const as_space* sp, const as_graph* gr, const double* queries, const int64_t* offsets, int64_t b, int64_t nv,
+                                 int64_t d, double tau, const double* weights, int32_t skip_zero, const as_groups* groups, int64_t n_groups,
+                                 const as_subset* sub, int64_t* out_label, double* out_score, int64_t* out_len, double* out_lambda_q,
+                                 int32_t* out_status) {
+    if (!sp || !gr || !queries || !offsets || !groups || !out_label || !out_score || !out_len) {
+        set_err("as_search_maxsim_batch: null argument");
+        return AS_EINVAL;
+    }
+    AS_TRY(fused_batch_offsets("as_search_maxsim_batch", offsets, b, nv));
+    for (int64_t y = 0; y < b; ++y) out_len[y] = 0;
+    if (n_groups < 1 || n_groups > SUBSET_TOPK) {
+        set_err("as_search_maxsim_batch: n_groups must be in [1, %d], got %lld", SUBSET_TOPK, (long long)n_groups);
+        return AS_EINVAL;
+    }
+    AS_TRY(maxsim_checks("as_search_maxsim_batch", sp, groups));
+    FusedBatchArgs a;
+    AS_TRY(fused_batch_prepare("as_search_maxsim_batch", sp, gr, queries, offsets, b, d, tau, weights, 0, skip_zero, sub, out_lambda_q, out_status,
+                               a, &sp->maxsim_batch_count[0], &sp->maxsim_batch_count[1], &sp->maxsim_batch_count[6]));
+    if ((sub && sub->m == 0) || !a.any || groups->count <= 0) return AS_OK;
+    const Candidates c("as_search_maxsim_batch", sp, sub);
+    AS_TRY(c.status);
+    const int64_t k = std::min<int64_t>(n_groups, groups->count);
+    MaxsimBatchCall call;
+    as_status s = maxsim_batch_begin(c.w, groups, c.m, b, offsets, a.wts.data(), a.st.data(), &call);
+    for (int64_t g0 = 0; s == AS_OK && g0 < b; g0 += call.gmax) {
+        const int64_t gn = std::min<int64_t>(call.gmax, b - g0);
+        if (!fused_batch_group_served(a, g0, gn)) continue;
+        s = maxsim_batch_fold_group(sp, c.w, c.m, queries, offsets, g0, gn, tau, groups, a, &call);
+        if (s == AS_OK) s = maxsim_batch_select(&call, k);   // -> c.w->out[t]; waits
+        for (int64_t t = 0; s == AS_OK && t < gn; ++t) {
+            const int64_t y = g0 + t;
+            if (a.nst[(size_t)y] != 0) continue;
+            const SubsetOut* o = c.w->out + t;
+            if (o->len != k) {
+                set_err("as_search_maxsim_batch: the selection returned %lld of %lld entries", (long long)o->len, (long long)k);
+                s = AS_EHIP;
+                break;
+            }
+            // entries that came back NaN lie behind the last group that exists
+            int64_t n = 0;
+            for (; n < k && o->score[n] == o->score[n]; ++n) {
+                if (o->idx[n] < 0 || o->idx[n] >= groups->count) {
+                    set_err("as_search_maxsim_batch: the selection returned group %lld", (long long)o->idx[n]);
+                    s = AS_EHIP;
+                    break;
+                }
+                out_label[y * n_groups + n] = groups->labels[(size_t)o->idx[n]];
+                out_score[y * n_groups + n] = o->score[n];
+            }
+            if (s == AS_OK) out_len[y] = n;
+        }
+    }
+    if (s == AS_OK) s = maxsim_batch_end(&call);
+    if (s != AS_OK) {
+        (void)c.fail(s);
+        for (int64_t y = 0; y < b; ++y) out_len[y] = 0;
+    }
+    maxsim_batch_counts_add(sp, call);
+    return s;
+}
+
+as_status as_score_maxsim_batch(const as_space* sp, const as_graph* gr, const double* queries, const int64_t* offsets, int64_t b, int64_t nv,
+                                int64_t d, double tau, const double* weights, int32_t skip_zero, const as_groups* groups, const as_subset* sub,
+                                const int64_t* labels, int64_t nl, double* out_scores, double* out_lambda_q, int32_t* out_status) {
+    if (!sp || !gr || !queries || !offsets || !groups || nl < 0 || (nl > 0 && (!labels || !out_scores))) {
+        set_err("as_score_maxsim_batch: null argument");
+        return AS_EINVAL;
+    }
+    AS_TRY(fused_batch_offsets("as_score_maxsim_batch", offsets, b, nv));
+    AS_TRY(maxsim_checks("as_score_maxsim_batch", sp, groups));
+    std::vector<int32_t> pos;   // the dense group number of every listed label (group numbers fit 32 bits: as_groups_create)
+    try {
+        pos.resize((size_t)nl);
+    } catch (const std::bad_alloc&) {
+        set_err("as_score_maxsim_batch: out of host memory for %lld labels", (long long)nl);
+        return AS_ENOMEM;
+    }
+    for (int64_t t = 0; t < nl; ++t) {
+        const auto it = std::lower_bound(groups->labels.begin(), groups->labels.end(), labels[t]);
+        if (it == groups->labels.end() || *it != labels[t]) {
+            set_err("as_score_maxsim_batch: label %lld is not one of the groups", (long long)labels[t]);
+            return AS_EINVAL;
+        }
+        pos[(size_t)t] = (int32_t)(it - groups->labels.begin());
+    }
+    FusedBatchArgs a;
+    AS_TRY(fused_batch_prepare("as_score_maxsim_batch", sp, gr, queries, offsets, b, d, tau, weights, 0, skip_zero, sub, out_lambda_q, out_status, a,
+                               &sp->maxsim_batch_count[0], &sp->maxsim_batch_count[1], &sp->maxsim_batch_count[6]));
+    if (nl == 0) return AS_OK;
+    // an unserved need's row: NaN
+    const auto nan_rows = [&](int64_t g0, int64_t gn, bool all) {
+        for (int64_t y = g0; y < g0 + gn; ++y)
+            if (all || a.nst[(size_t)y] != 0) std::fill(out_scores + y * nl, out_scores + (y + 1) * nl, std::numeric_limits<double>::quiet_NaN());
+    };
+    if ((sub && sub->m == 0) || !a.any) {   // no item, no member; or no need to serve
+        nan_rows(0, b, true);
+        return AS_OK;
+    }
+    const Candidates c("as_score_maxsim_batch", sp, sub);
+    AS_TRY(c.status);
+    MaxsimBatchCall call;
+    as_status s = maxsim_batch_begin(c.w, groups, c.m, b, offsets, a.wts.data(), a.st.data(), &call);
+    if (s == AS_OK) s = maxsim_batch_labels(&call, pos.data(), nl);
+    for (int64_t g0 = 0; s == AS_OK && g0 < b; g0 += call.gmax) {
+        const int64_t gn = std::min<int64_t>(call.gmax, b - g0);
+        if (fused_batch_group_served(a, g0, gn)) {
+            s = maxsim_batch_fold_group(sp, c.w, c.m, queries, offsets, g0, gn, tau, groups, a, &call);
+            // the listed F of the group's needs in one copy (an unserved need's row holds no answer: overwritten below)
+            if (s == AS_OK) s = maxsim_batch_pick(&call, out_scores + g0 * nl);
+        }
+    }
+    if (s == AS_OK) s = maxsim_batch_end(&call);   // waits
+    s = c.fail(s);
+    if (s == AS_OK) nan_rows(0, b, false);
+    maxsim_batch_counts_add(sp, call);
+    return s;
+}
+
+as_status as_maxsim_batch_counters(const as_space* sp, int64_t* out, int32_t n) {
+    return counters_out("as_maxsim_batch_counters", sp, out, n, sp ? sp->maxsim_batch_count : nullptr, 8);
+}
+double as_maxsim_batch_kernel_us(const as_space* sp, int32_t part) {
+    if (!sp || part < 0 || part > 2) return 0.0;
+    const double a = sp->maxsim_batch_us[0].load(std::memory_order_relaxed), f = sp->maxsim_batch_us[1].load(std::memory_order_relaxed);
     return part == 0 ? a + f : (part == 1 ? a : f);
 }
 

@@ -198,6 +198,13 @@ struct as_space {
     // under "maxsim_timing" (as_maxsim_kernel_us)
     mutable std::atomic<int64_t> maxsim_count[5] = {};
     mutable std::atomic<double> maxsim_us[2] = {};
+    // as_search_maxsim_batch / as_score_maxsim_batch: on the same buffers as the single forms.
+    // as_maxsim_batch_counters: [0] calls that passed their checks, [1] needs of those calls, [2] vectors served, [3] pass-A
+    // launches, [4] 64-bit max-atomics pass A issued, [5] fold launches, [6] lambda_q steps run (1 per call), [7] need groups
+    // begun.  maxsim_batch_us: pass A (with the memset of its cells) and the segmented fold kernel of the last call under
+    // "maxsim_batch_timing" (as_maxsim_batch_kernel_us)
+    mutable std::atomic<int64_t> maxsim_batch_count[8] = {};
+    mutable std::atomic<double> maxsim_batch_us[2] = {};
     // as_search_diverse / as_search_diverse_batch: their buffers (as_diverse.hip), made on first use and grown on demand; the
     // selection step of a call is serialised by dmu (the pool step before it is an ordinary search and takes no lock of these).
     // as_diverse_counters: [0] calls that passed their checks, [1] select launches, [2] picks made, [3] dots computed, [4] pool
@@ -804,8 +811,9 @@ as_status subset_select_from(SubsetWork* w, const double* scores, int64_t m, int
 // kernels over positions that are not items of the subset (late-interaction search: position == dense group number).
 as_status subset_select_from_table(SubsetWork* w, const double* scores, const int32_t* pos_ids, int64_t m, int64_t k, int64_t* out_idx,
                                    double* out_score, int64_t* out_len);
-// ... and over `rows` rows ([rows][ld]) at once: row t's list -> w->out[t] (len == min(k, m, SUBSET_TOPK)); waits for the stream.
-as_status subset_select_rows_from(SubsetWork* w, const double* scores, int64_t ld, int64_t m, int64_t k, int64_t rows);
+// ... and over `rows` rows ([rows][ld]) at once, all under the one table pos_ids (the work's ids, or a caller's own): row t's list
+// -> w->out[t] (len == min(k, m, SUBSET_TOPK)); waits for the stream.
+as_status subset_select_rows_from(SubsetWork* w, const double* scores, const int32_t* pos_ids, int64_t ld, int64_t m, int64_t k, int64_t rows);
 // a row's pinned result (w->out[row]) of k entries to the caller's arrays; AS_EHIP if the selection left another length there
 as_status subset_list_out(const SubsetOut* o, int64_t k, int64_t* out_idx, double* out_score, int64_t* out_len);
 constexpr int QUERY_BATCH = 32;  // == GQ in as_search.hip: query slots of the batched workspace
@@ -877,6 +885,38 @@ void set_fused_timing(int v);   // as_set_tuning("fused_timing", 0 | 1)
 // need g0 + t owns accumulator row t.  fused_batch_chunk: rows i0 .. i0 + nb - 1 of THAT GROUP's slice of the vectors, [nb][ld]
 // on the device -- the sink of a subset_batch_run over the slice; it does not wait; a chunk without a served row launches
 // nothing.  fused_batch_end: after the caller's last wait for the stream.  The rows are fused_acc(w) + t * m.
+// The parameters of a call over b needs of nv flattened vectors, in the pinned block and on the device, in the order of the one
+// upload (the batched fused forms and batched late-interaction search): [nv] weights, [b + 1] int64 offsets, [b] int64 first and
+// [b] int64 last served flattened row of every need (-1: none), [nv] int32 served flags.
+struct BatchPar {
+    double* wts;
+    int64_t* offs;
+    int64_t* first;
+    int64_t* last;
+    int32_t* flags;
+    BatchPar(double* base, int64_t nv, int64_t b)
+        : wts(base), offs((int64_t*)(base + nv)), first(offs + b + 1), last(first + b), flags((int32_t*)(last + b)) {}
+    static int64_t words(int64_t nv, int64_t b) { return nv + (b + 1) + 2 * b + (nv + 1) / 2; }
+    static size_t bytes(int64_t nv, int64_t b) { return sizeof(double) * (size_t)(nv + (b + 1) + 2 * b) + sizeof(int32_t) * (size_t)nv; }
+    // filled from the caller's offsets, weights and per-vector status (AS_EZEROLAMBDA: not served); returns the served vectors
+    int64_t fill(int64_t b, const int64_t* o, const double* weights, const int32_t* status) const {
+        int64_t served = 0;
+        for (int64_t y = 0; y <= b; ++y) offs[y] = o[y];
+        for (int64_t y = 0; y < b; ++y) {
+            first[y] = last[y] = -1;
+            for (int64_t t = o[y]; t < o[y + 1]; ++t) {
+                wts[t] = weights[t];
+                flags[t] = status[t] == AS_EZEROLAMBDA ? 0 : 1;
+                if (flags[t]) {
+                    if (first[y] < 0) first[y] = t;
+                    last[y] = t;
+                    ++served;
+                }
+            }
+        }
+        return served;
+    }
+};
 struct FusedBatchCall {
     SubsetWork* w = nullptr;
     int64_t m = 0, b = 0, nv = 0;
@@ -945,6 +985,36 @@ as_status maxsim_select(MaxsimCall* c, int64_t k, int64_t* out_group, double* ou
 as_status maxsim_scores(MaxsimCall* c, double* out);
 void maxsim_work_free(MaxsimWork* x);
 void set_maxsim_timing(int v);   // as_set_tuning("maxsim_timing", 0 | 1)
+// The batched form: b needs, need y = the flattened rows offs[y] .. offs[y + 1] - 1 of the call's nv
+// vectors, each folded into an accumulator row [G] of its own.  maxsim_batch_begin: Gn = gmax needs per group from the
+// "maxsim_batch_mib" budget (1 <= Gn <= SB_QC_MAX), room for [Gn][G] accumulators, ONE upload (BatchPar).  maxsim_batch_labels
+// (the score form, once per call): the nl dense group numbers of the listed labels uploaded, room for [Gn][nl] listed scores.
+// maxsim_batch_group: needs g0 .. g0 + gn - 1 are in flight, need g0 + t owns accumulator row t.  maxsim_batch_chunk: rows
+// i0 .. i0 + nb - 1 of THAT GROUP's slice of the vectors, [nb][ld] on the device -- the sink of a subset_batch_run over the slice
+// (row_bytes = 8 G): one memset of the cells, pass A per run of served rows, ONE segmented fold launch; it does not wait; a chunk
+// without a served row launches nothing.  maxsim_batch_select: the first k groups of every need of the group in flight by (F
+// descending, group number ascending) -> w->out[t]; waits.  maxsim_batch_pick: the listed F of the group's needs -> out
+// [gn][nl], queued.  maxsim_batch_end: waits, leaves the atomics counted and the times in *c.
+struct MaxsimBatchCall {
+    SubsetWork* w = nullptr;
+    const as_groups* g = nullptr;
+    int64_t m = 0, b = 0, nv = 0, nl = 0;
+    int64_t gmax = 1;              // Gn
+    int64_t g0 = 0, gn = 0;        // the group in flight
+    bool timing = false, timed = false;
+    int64_t served = 0, passa = 0, atoms = 0, folds = 0, groups = 0;   // vectors served, pass-A launches, max-atomics, fold launches, groups begun
+    double us[2] = {0.0, 0.0};     // pass A (with its memsets), the fold kernel: microseconds under "maxsim_batch_timing"
+};
+as_status maxsim_batch_begin(SubsetWork* w, const as_groups* gs, int64_t m, int64_t b, const int64_t* offs, const double* weights,
+                             const int32_t* status, MaxsimBatchCall* c);
+as_status maxsim_batch_labels(MaxsimBatchCall* c, const int32_t* gnum_host, int64_t nl);
+void maxsim_batch_group(MaxsimBatchCall* c, int64_t g0, int64_t gn);
+as_status maxsim_batch_chunk(MaxsimBatchCall* c, int64_t i0, int64_t nb, const double* scores, int64_t ld);
+as_status maxsim_batch_select(MaxsimBatchCall* c, int64_t k);
+as_status maxsim_batch_pick(MaxsimBatchCall* c, double* out);
+as_status maxsim_batch_end(MaxsimBatchCall* c);
+void set_maxsim_batch_timing(int v);   // as_set_tuning("maxsim_batch_timing", 0 | 1)
+void set_maxsim_batch_mib(int v);      // as_set_tuning("maxsim_batch_mib", v): v > 0 MiB, v < 0 -v KiB, 0 the default (256 MiB)
 // Diversified search (as_diverse.hip): the greedy of S12 over b pools -- pool i = pool_idx / pool_score + i * kk,
 // pool_len[i] <= kk entries in the order the route returned them (0: a query that is not served) -- n picks wanted, diversity delta.
 // Pick t of query i -> out_idx / out_score / out_margin (may be null) + i * nn + t, nn = min(n, kk); out_len[i] = min(n, pool_len[i]).

@@ -267,21 +267,6 @@ static std::atomic<int> g_fused_batch_mib{256};
 void set_fused_batch_timing(int v) { g_fused_batch_timing.store(v ? 1 : 0, std::memory_order_relaxed); }
 void set_fused_batch_mib(int v) { g_fused_batch_mib.store(v != 0 ? v : 256, std::memory_order_relaxed); }
 
-namespace {
-// the call's parameters in the pinned block and on the device, in the order of the one upload
-struct BatchPar {
-    double* wts;
-    int64_t* offs;
-    int64_t* first;
-    int64_t* last;
-    int32_t* flags;
-    BatchPar(double* base, int64_t nv, int64_t b)
-        : wts(base), offs((int64_t*)(base + nv)), first(offs + b + 1), last(first + b), flags((int32_t*)(last + b)) {}
-    static int64_t words(int64_t nv, int64_t b) { return nv + (b + 1) + 2 * b + (nv + 1) / 2; }
-    static size_t bytes(int64_t nv, int64_t b) { return sizeof(double) * (size_t)(nv + (b + 1) + 2 * b) + sizeof(int32_t) * (size_t)nv; }
-};
-}  // namespace
-
 as_status fused_batch_begin(SubsetWork* w, int64_t m, int64_t b, const int64_t* offs, const double* weights, const int32_t* status, int mode,
                             FusedBatchCall* c) {
     if (!w->fused) {
@@ -314,19 +299,7 @@ as_status fused_batch_begin(SubsetWork* w, int64_t m, int64_t b, const int64_t* 
     AS_TRY(reserve_or_err(f->par, words, "fused weights, segments and flags"));
     AS_TRY(reserve_or_err(f->hpar, words, "fused pinned weights, segments and flags"));
     f->j = 0;
-    const BatchPar h(f->hpar, nv, b);
-    for (int64_t y = 0; y <= b; ++y) h.offs[y] = offs[y];
-    for (int64_t y = 0; y < b; ++y) {
-        h.first[y] = h.last[y] = -1;
-        for (int64_t t = offs[y]; t < offs[y + 1]; ++t) {
-            h.wts[t] = weights[t];
-            h.flags[t] = status[t] == AS_EZEROLAMBDA ? 0 : 1;
-            if (h.flags[t]) {
-                if (h.first[y] < 0) h.first[y] = t;
-                h.last[y] = t;
-            }
-        }
-    }
+    (void)BatchPar(f->hpar, nv, b).fill(b, offs, weights, status);
     AS_HIP(hipMemcpyAsync(f->par, f->hpar, BatchPar::bytes(nv, b), hipMemcpyHostToDevice, w->stream));
     return AS_OK;
 }

@@ -278,7 +278,7 @@ as_status grouped_rows(GroupedCall* c, int64_t i0, int64_t rows, const double* s
     const int64_t k = std::min<int64_t>(ng, m);
     int64_t one_idx[SUBSET_TOPK], one_len = 0;
     double one_score[SUBSET_TOPK];
-    if (c->status) AS_TRY(subset_select_rows_from(w, collapsed, m, m, k, rows));   // -> w->out[row]; waits
+    if (c->status) AS_TRY(subset_select_rows_from(w, collapsed, w->ids, m, m, k, rows));   // -> w->out[row]; waits
     else AS_TRY(subset_select_from(w, collapsed, m, k, one_idx, one_score, &one_len));
     if (timing) {
         float ms = 0.0f;

@@ -3675,6 +3675,14 @@ int32_t as_set_tuning(const char* key, int32_t value) {
         set_fused_batch_mib(value);
         return 0;
     }
+    if (key && !strcmp(key, "maxsim_batch_timing")) {
+        set_maxsim_batch_timing(value);
+        return 0;
+    }
+    if (key && !strcmp(key, "maxsim_batch_mib")) {
+        set_maxsim_batch_mib(value);
+        return 0;
+    }
     return 1;
 }
 

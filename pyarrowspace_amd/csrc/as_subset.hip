@@ -582,7 +582,7 @@ as_status subset_select_from_table(SubsetWork* w, const double* scores, const in
     return subset_list_out(w->out, k, out_idx, out_score, out_len);
 }
 
-as_status subset_select_rows_from(SubsetWork* w, const double* scores, int64_t ld, int64_t m, int64_t k, int64_t rows) {
+as_status subset_select_rows_from(SubsetWork* w, const double* scores, const int32_t* pos_ids, int64_t ld, int64_t m, int64_t k, int64_t rows) {
     if (m <= 0 || k <= 0 || rows <= 0) return AS_OK;
     k = std::min<int64_t>(std::min<int64_t>(k, m), SUBSET_TOPK);
     AS_TRY(reserve_or_err(w->out, rows, "subset pinned results"));
@@ -591,7 +591,7 @@ as_status subset_select_rows_from(SubsetWork* w, const double* scores, int64_t l
         AS_TRY(reserve_or_err(w->state, rows * (SEL_PASSES + 1), "subset selection states"));
         AS_TRY(reserve_or_err(w->sel_pos, rows * SUBSET_TOPK, "subset selected positions"));
     }
-    AS_TRY(subset_select_rows(w, scores, w->ids, ld, m, k, rows));
+    AS_TRY(subset_select_rows(w, scores, pos_ids, ld, m, k, rows));
     AS_HIP(hipStreamSynchronize(w->stream));
     return AS_OK;
 }
