@@ -514,9 +514,16 @@ def query_lambda(idx: dict, q) -> float:
 # `prepare_query_item(&v, gl)` (src/lib.rs:154): nnodes = D.
 def feature_graph(X, prm) -> dict:
     """SPEC F1-F5."""
-    N, D = X.shape
     m = np.einsum("ia,ia->a", X, X)
-    gram = X.T @ X
+    return feature_graph_from_gram(X.T @ X, prm, m)
+
+
+def feature_graph_from_gram(gram, prm, m=None) -> dict:
+    """SPEC F2-F5 on a given D x D Gram (any symmetric array: the staged as_feat_graph takes whatever Gram it is handed);
+    m = the squared column norms, the Gram's diagonal unless given."""
+    gram = np.asarray(gram, dtype=np.float64)
+    D = gram.shape[0]
+    m = np.diagonal(gram).copy() if m is None else np.asarray(m, dtype=np.float64)
     if prm["metric"] == METRIC_COSINE:
         den = np.sqrt(np.outer(m, m))
         c = np.where(den > 0, gram / np.where(den > 0, den, 1.0), 0.0)

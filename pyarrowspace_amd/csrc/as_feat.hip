@@ -8,7 +8,7 @@
 //   FK2  feat_knn_kernel     per column: keys to all other columns, eps, (key, index) rank, first k
 //   (K3)  csr_from_knn       union symmetrisation, weights, degrees (shared with the item graph)
 //   FK3  feat_energy_kernel  per item: T = sum_{a<b} w_ab (x_a - x_b)^2, sum of squares, E and G            -- LDS-gather-bound
-//   FK4  feat_qlambda_kernel the same functional for a query (one wave per query slot)
+//   FK4  q_prepare_feat_kernel  the same functional for a query, inside the query's staging (one block per query slot)
 #include <chrono>
 #include <vector>
 
@@ -425,59 +425,10 @@ as_status feat_energy(const as_space* sp, const as_graph* gr, int64_t r0, int64_
     return AS_OK;
 }
 
-// FK4: lambda_q of the query slots (blockIdx.x = slot), one 1024-thread block each (a single wave walking ~19 000
-// edges took 55 us on the critical path of every search); q64 is the zero-padded query the prepare kernel wrote.
-// lambda_q == 0 is the reference's zero-lambda assert (src/lib.rs:156-159).
-__global__ __launch_bounds__(1024) void feat_qlambda_kernel(const double* __restrict__ q64, int64_t d, int64_t dp, int64_t ne,
-                                                            const int32_t* __restrict__ ea, const int32_t* __restrict__ eb,
-                                                            const double* __restrict__ ew, double tau0, QInfo* info) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    double* xs = (double*)smem;
-    __shared__ double s_red[3][16];
-    const int lane = lane_id(), w = threadIdx.x >> 6, nwv = blockDim.x >> 6;
-    q64 += (int64_t)blockIdx.x * dp;
-    info += blockIdx.x;
-    double nxl = 0.0;
-    for (int64_t c = threadIdx.x; c < d; c += blockDim.x) {
-        const double v = q64[c];
-        xs[c] = v;
-        nxl += v * v;
-    }
-    __syncthreads();
-    double T = 0.0, S2 = 0.0;
-    for (int64_t e = threadIdx.x; e < ne; e += blockDim.x) {
-        const double t = xs[ea[e]] - xs[eb[e]];
-        const double en = ew[e] * (t * t);
-        T += en;
-        S2 += en * en;
-    }
-    T = wave_sum(T);
-    S2 = wave_sum(S2);
-    nxl = wave_sum(nxl);
-    if (lane == 0) {
-        s_red[0][w] = T;
-        s_red[1][w] = S2;
-        s_red[2][w] = nxl;
-    }
-    __syncthreads();
-    if (w != 0) return;
-    T = S2 = nxl = 0.0;
-    for (int w2 = 0; w2 < nwv; ++w2) {   // fixed order: deterministic
-        T += s_red[0][w2];
-        S2 += s_red[1][w2];
-        nxl += s_red[2][w2];
-    }
-    double e, g;
-    feat_finish(T, S2, nxl, xs, ne, ea, eb, ew, e, g);
-    if (lane == 0) {
-        const double lam = tau0 * (e / (e + tau0)) + (1.0 - tau0) * g;
-        info->lambda_q = lam;
-        info->status = lam == 0.0 ? AS_EZEROLAMBDA : AS_OK;
-    }
-}
-
 // q_prepare (query staging: fp64 + fp32 copies, norms, state reset) and FK4 in one launch: in feature mode lambda_q
-// needs nothing but the query, so the whole pre-scan work of a search is this one kernel.
+// needs nothing but the query, so the whole pre-scan work of a search is this one kernel.  One 1024-thread block per
+// query slot (blockIdx.z): a single wave walking ~19 000 edges took 55 us on the critical path of every search.
+// lambda_q == 0 is the reference's zero-lambda assert (src/lib.rs:156-159).
 __global__ __launch_bounds__(1024) void q_prepare_feat_kernel(const double* __restrict__ qin, int64_t d, int64_t dp, double* __restrict__ q64,
                                                               float* __restrict__ q32, QInfo* info, double tau, int64_t ne,
                                                               const int32_t* __restrict__ ea, const int32_t* __restrict__ eb,
@@ -547,16 +498,7 @@ as_status feat_query_prepare(const as_graph* gr, const double* qin, int64_t d, i
 }
 
 static as_status feat_query_attr(int64_t d) {
-    AS_HIP(hipFuncSetAttribute((const void*)feat_qlambda_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * d)));
     AS_HIP(hipFuncSetAttribute((const void*)q_prepare_feat_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * d)));
-    return AS_OK;
-}
-
-as_status feat_query_lambda(const as_graph* gr, const double* q64, int64_t dp, QInfo* info, int nslots, hipStream_t st) {
-    const size_t lds = sizeof(double) * gr->n;
-    hipLaunchKernelGGL(feat_qlambda_kernel, dim3((unsigned)nslots), dim3(1024), lds, st, q64, gr->n, dp, gr->ne, gr->ea, gr->eb, gr->ew,
-                       gr->tau0, info);
-    AS_HIP(hipGetLastError());
     return AS_OK;
 }
 

@@ -1,7 +1,8 @@
 """GPU parity of the feature mode (lambda_mode='feature', SPEC F1-F7): lambda as the reference's notes document it
 -- Rayleigh quotient + edgewise dispersion on the F x F feature-space Laplacian (/root/reference/TAUMODE.md:8,12-27,
 GRAPH_VARIABLES.md:17) -- against the fp64 CPU oracle, through the C ABI.  Bar: indices rank-exact, scores and
-lambdas 1e-9 relative (north_star allows 1e-6)."""
+lambdas 1e-9 relative (north_star allows 1e-6).  The stages one at a time, on hand-built items, Grams and vectors
+(ties at the cut, the eps line, row splits, wide rows, the ratio pass of F6): tests/test_gpu_feature_stage.py."""
 import ctypes as C
 import os
 
