@@ -485,6 +485,8 @@ void as_enable_search_stats(int32_t enabled);
  * 256; 0: the default; v < 0: -v KiB, so that tests reach several groups at small shapes).  "maxsim_batch_timing" = 1 / 0: HIP
  * events around batched late-interaction search's pass A and segmented fold kernel (as_maxsim_batch_kernel_us);
  * "maxsim_batch_mib" = MiB of accumulator rows one group of needs of those forms may hold (same values as "fused_batch_mib").
+ * "maxsim_lists_timing" = 1 / 0: HIP events around the score kernel, the fold kernel and the selection of late-interaction
+ * re-ranking of per-need documents (as_maxsim_lists_kernel_us); those forms chunk by "subset_batch_mib" too.
  * "filtered_grid_cap" = v > 0: gridDim.x of the filtered family's stride-loop kernels (the gather score
  * kernels of the subset and list forms, the radix select's passes, the fused and late-interaction folds, the grouped picks, the range compaction) is
  * clipped to at most v blocks, so tests reach the later trips of those loops at small shapes; 0 (default): no clip.
@@ -918,6 +920,47 @@ as_status as_maxsim_batch_counters(const as_space* sp, int64_t* out, int32_t n);
  * as_set_tuning("maxsim_batch_timing", 1) (HIP events; off by default), summed over its chunks: part 1: the memsets of the cells
  * and pass A; part 2: the segmented fold kernel; part 0: both.  NULL or another part: 0 */
 double as_maxsim_batch_kernel_us(const as_space* sp, int32_t part);
+/* ---- Extension: late-interaction re-ranking of per-need candidate documents.  The needs, weights, tau, skip_zero
+ * and groups of as_search_maxsim_batch, but EVERY NEED HAS ITS OWN CANDIDATE GROUPS ("documents") and there is no subset: need y's
+ * documents are need_docs[y] .. need_docs[y + 1] - 1 (need_docs: int64 [b + 1], starts at 0, does not decrease; a need may have
+ * none), document dd is the group with label doc_label[dd] (strictly ascending inside a need; needs may share labels) and its
+ * entries ids[doc_first[dd] .. doc_first[dd + 1]) are ALL the members of that group in ascending item order (doc_first: int64
+ * [nd + 1] from 0, nd = need_docs[b]).  All arrays are HOST memory.  The score of vector v of need y and an entry i is the bits
+ * as_score_lists_batch writes for the nv flattened vectors, each with its need's entries as its list (the single forms'
+ * summation order; lambda_q of every vector from ONE as_search_batch over all nv); m_v(g), F_y(g) and the zero-lambda rule are
+ * as_search_maxsim_batch's, the fold over need y's own served vectors.
+ * as_search_maxsim_lists: need y's documents whose F is not NaN by (F descending, label ascending), the first min(n_groups, such
+ * documents) -> out_label / out_score + y * n_groups, out_len[y].  as_score_maxsim_lists: F of every document -> out_scores[dd]
+ * (NaN: every entry scored NaN, or the need is not served).
+ * Checked before the lambda_q step: null arguments, the offsets (as_search_maxsim_batch), n_groups outside [1, 1024], groups of
+ * another space, need_docs / doc_first that do not start at 0 or decrease, a label that is not one of the groups or out of order,
+ * a document that is not exactly its group's members in ascending order -> AS_EINVAL; 2^31 entries or more, a shard of a
+ * row-sharded index -> AS_EUNSUPPORTED.
+ * Cost: ONE as_search_batch over the nv vectors; then per chunk of needs whose scores (served vectors x entries) fit the
+ * "subset_batch_mib" budget one upload, ONE ragged score launch (a block per segment of <= 64 entries and tile of <= T of the need's
+ * vectors staged in LDS: every row is gathered once per TILE, not once per vector), one fold launch (a wave per (need, document):
+ * maxima and the weighted sum) and the per-query list forms' selection, a block per need; b x n_groups entries (the score form: nd
+ * doubles) cross to the host, the scores never do.  Answers never depend on the chunks, the grid, the order of the needs or the
+ * other needs' documents (for the same lambda_q).  Calls on one space are serialised with the per-query list forms. */
+as_status as_search_maxsim_lists(const as_space* sp, const as_graph* gr, const double* queries, const int64_t* offsets, int64_t b, int64_t nv,
+                                 int64_t d, double tau, const double* weights, int32_t skip_zero, const as_groups* groups, int64_t n_groups,
+                                 const int64_t* need_docs, const int64_t* doc_label, const int64_t* doc_first, const int64_t* ids,
+                                 int64_t* out_label, double* out_score, int64_t* out_len, double* out_lambda_q, int32_t* out_status);
+as_status as_score_maxsim_lists(const as_space* sp, const as_graph* gr, const double* queries, const int64_t* offsets, int64_t b, int64_t nv,
+                                int64_t d, double tau, const double* weights, int32_t skip_zero, const as_groups* groups,
+                                const int64_t* need_docs, const int64_t* doc_label, const int64_t* doc_first, const int64_t* ids,
+                                double* out_scores, double* out_lambda_q, int32_t* out_status);
+/* out[0] calls of the two entries above that passed their checks, [1] needs of those calls, [2] vectors served, [3] score-kernel
+ * launches, [4] rows the score kernel was asked to gather (per need: entries x vector tiles), [5] (vector, row) dots, [6] fold
+ * launches, [7] lambda_q steps run (one per call), [8] host nanoseconds spent on the document checks and the work tables */
+as_status as_maxsim_lists_counters(const as_space* sp, int64_t* out, int32_t n);
+/* measurement: device microseconds of the last call of the two entries on this space that ran under
+ * as_set_tuning("maxsim_lists_timing", 1) (HIP events; off by default), summed over its chunks: part 1: the score kernel; part 2:
+ * the fold kernel; part 3: the selection (the score form: the copy out); part 0: all.  NULL or another part: 0 */
+double as_maxsim_lists_kernel_us(const as_space* sp, int32_t part);
+/* the score kernel's geometry on this space: *out_tile = T, the vectors of a need one tile stages (from the padded row length: as
+ * many as fit 32 KiB of LDS, 32 at most, 1 where one vector does not fit); *out_segment = entries of a segment at most (64) */
+as_status as_maxsim_lists_geometry(const as_space* sp, int64_t* out_tile, int64_t* out_segment);
 
 /* ---- index persistence (extension; the reference exposes none): one flat file
  * holding the items, lambdas and graph arrays.  Loading re-ingests the items and uploads the

@@ -467,6 +467,74 @@ def _grouped_args(gl, tau, n_groups, per_group):
     return tau, int(n_groups), int(per_group)
 
 
+def _group_members(labels):
+    """The member table of per-item labels -> (labels int64 [G] ascending and distinct, order int64 [n]: the items by (label
+    ascending, item id ascending), starts int64 [G + 1]): the members of the group with labels[g] are order[starts[g]:starts[g + 1]]."""
+    lab = np.ascontiguousarray(labels, dtype=np.int64)
+    order = np.argsort(lab, kind="stable").astype(np.int64, copy=False)
+    uniq, counts = np.unique(lab, return_counts=True)
+    starts = np.zeros(uniq.shape[0] + 1, dtype=np.int64)
+    np.cumsum(counts, out=starts[1:])
+    return uniq, order, starts
+
+
+def _label_lists(lists, b: int) -> list:
+    """The candidate documents of b needs as b contiguous int64 1-D arrays of group labels (the caller's order, duplicates kept):
+    a 2-D integer array (B, C) is B lists of C labels, any other sequence holds one 1-D sequence of labels per need (empty ones
+    allowed).  TypeError: a float or boolean dtype, something that is no sequence; ValueError: a count of lists other than b, a
+    list that is not 1-D, a uint64 label past the int64 range."""
+    if isinstance(lists, (str, bytes)) or not hasattr(lists, "__iter__"):
+        raise TypeError("argument 'lists': expected one sequence of group labels per need")
+    seq = list(lists)
+    if len(seq) != b:
+        raise ValueError(f"argument 'lists': {len(seq)} label lists for {b} needs")
+    parts = []
+    for i, l in enumerate(seq):
+        if isinstance(l, (str, bytes)):
+            raise TypeError(f"argument 'lists': need {i}: expected integer group labels")
+        a = np.asarray(l)
+        if a.size == 0 and a.ndim == 1 and a.dtype.kind not in "iub":
+            a = np.empty(0, dtype=np.int64)
+        if a.dtype.kind not in "iu":
+            raise TypeError(f"argument 'lists': need {i}: expected integer group labels, got dtype {a.dtype}")
+        if a.ndim != 1:
+            raise ValueError(f"argument 'lists': need {i}: expected a 1-D sequence of group labels, got shape {a.shape}")
+        if a.dtype == np.uint64 and a.size and int(a.max()) > np.iinfo(np.int64).max:
+            raise ValueError(f"argument 'lists': label {int(a.max())} is not one of the groups")
+        parts.append(np.ascontiguousarray(a, dtype=np.int64))
+    return parts
+
+
+def _expand_documents(parts, members):
+    """The documents of every need from its label list (`_label_lists`) and a member table (`_group_members`) -> (need_docs int64
+    [B + 1], doc_label int64 [ND], doc_first int64 [ND + 1], ids int64 [NE], inverse: B int64 arrays).  Need b's documents are
+    need_docs[b] .. need_docs[b + 1] - 1: the DISTINCT labels of its list, ascending; document dd's entries
+    ids[doc_first[dd]:doc_first[dd + 1]] are the members of its group, ascending, so that a need's entries are ordered by (label,
+    item id); inverse[b][c] is the document (counted inside need b) of the caller's entry c.  ValueError names a label that is
+    not one of the groups."""
+    uniq, order, starts = members
+    need_docs = np.zeros(len(parts) + 1, dtype=np.int64)
+    docs, inverse = [], []
+    for b, l in enumerate(parts):
+        dl, iv = np.unique(l, return_inverse=True)
+        docs.append(dl)
+        inverse.append(iv.astype(np.int64, copy=False).reshape(-1))
+        need_docs[b + 1] = need_docs[b] + dl.shape[0]
+    doc_label = np.ascontiguousarray(np.concatenate(docs), dtype=np.int64) if docs else np.empty(0, dtype=np.int64)
+    g = np.searchsorted(uniq, doc_label)
+    known = np.zeros(doc_label.shape[0], dtype=bool)
+    if uniq.shape[0]:
+        known = uniq[np.minimum(g, uniq.shape[0] - 1)] == doc_label
+    if not known.all():
+        raise ValueError(f"argument 'lists': label {int(doc_label[np.flatnonzero(~known)[0]])} is not one of the groups")
+    size = starts[g + 1] - starts[g]
+    doc_first = np.zeros(doc_label.shape[0] + 1, dtype=np.int64)
+    np.cumsum(size, out=doc_first[1:])
+    ne = int(doc_first[-1])
+    ids = order[np.repeat(starts[g] - doc_first[:-1], size) + np.arange(ne, dtype=np.int64)]
+    return need_docs, doc_label, doc_first, np.ascontiguousarray(ids, dtype=np.int64), inverse
+
+
 class ItemGroups:
     """Extension: one group per item of one ArrowSpace (`ArrowSpace.groups`): the items' integer labels, turned into dense group
     numbers once and resident on the device for `search_grouped`.  Holds a reference to its ArrowSpace."""
@@ -500,6 +568,13 @@ class ItemGroups:
     def labels(self) -> np.ndarray:
         """Extension: the per-item labels (int64, a copy)."""
         return self._labels.copy()
+
+    def _members(self):
+        """The member table of the labels (`_group_members`), made by the first call that needs it and kept."""
+        table = getattr(self, "_member_table", None)
+        if table is None:
+            table = self._member_table = _group_members(self._labels)
+        return table
 
 
 class ArrowSpace:
@@ -1100,6 +1175,82 @@ class ArrowSpace:
         the lambda_q steps (one per call) and the need groups run."""
         return _counters(_L.as_maxsim_batch_counters, self._h,
                          ("calls", "needs", "vectors_served", "pass_a_launches", "max_atomics", "fold_launches", "lambda_steps", "need_groups"))
+
+    def _maxsim_lists_args(self, needs, gl, tau, groups, n_groups, lists, weights, on_zero_lambda):
+        """What the per-need document forms check before they touch a handle: the batched fused forms' checks (needs, weights,
+        the zero-lambda setting), the grouped forms' (n_groups, tau), the label lists (`_label_lists`); then the groups as a
+        handle of this space and the documents expanded into their members (`_expand_documents`: ValueError for an unknown
+        label)."""
+        V, offs, w, _, skip = _fused_batch_args(needs, gl, weights, "sum", on_zero_lambda)
+        tau, ng, _ = _grouped_args(gl, tau, n_groups, 1)
+        parts = _label_lists(lists, offs.shape[0] - 1)
+        grp, _ = self._grouped_handles(groups, None)
+        return V, offs, w, skip, tau, ng, grp, _expand_documents(parts, grp._members())
+
+    def search_maxsim_lists(self, needs, gl: GraphLaplacian, tau: float, groups, n_groups: int, lists, weights=None, on_zero_lambda="raise"):
+        """Extension: late-interaction re-ranking of per-need candidate documents, B needs of J_b query vectors EACH WITH ITS OWN
+        list of candidate groups -> list of B lists[(label, F)]; list b holds the first min(n_groups, documents of need b with
+        a non-NaN F_b) of need b's distinct candidates by (F_b descending, label ascending), 1 <= n_groups <= 1024.  `needs`,
+        `weights` and `on_zero_lambda` are `search_maxsim_batch`'s, `groups` an `ItemGroups` of this space or anything
+        `groups()` accepts.  `lists`: B sequences of group LABELS (any order, duplicates and empty lists allowed, needs may share
+        labels) or an integer (B, C) array; a float or boolean dtype raises TypeError, a label that is not one of the groups
+        or a count of lists other than B ValueError.  There is no subset: the candidates are the filter.  With V the vectors
+        of all needs flattened in need order and ids_b the members of need b's candidates by (label, item id), the score of a
+        vector v of need b and an item of ids_b has the bits `score_lists_batch(V, gl, tau, [ids_need(v) for v in V])` writes
+        (the single forms' summation order; lambda_q of every vector from ONE `search_batch` over V); maxima, fold and the
+        zero-lambda rule are `search_maxsim_batch`'s, the fold over need b's own served vectors.  An answer does not depend on
+        the order of or duplicates in `lists[b]`, on the other needs' lists, on the chunk budget or the grid.  Against
+        `score_maxsim_batch` over the same members as a subset F agrees to 1e-12 relative (non-negative weights), not in bits.
+        Costs one `search_batch` over V, then per chunk of needs ONE ragged launch that gathers every candidate row once per
+        tile of the need's vectors (`maxsim_lists_geometry`), one launch that takes the per-document maxima and folds them, and
+        one selection, all on the device: B x n_groups entries cross to the host, the scores never do."""
+        V, offs, w, skip, tau, ng, grp, docs = self._maxsim_lists_args(needs, gl, tau, groups, n_groups, lists, weights, on_zero_lambda)
+        need_docs, doc_label, doc_first, ids, _ = docs
+        b = offs.shape[0] - 1
+        (label, sc, ln), stt = _hit_buffers(b, ng), _statuses(b)
+        vp = C.c_void_p
+        st = _L.as_search_maxsim_lists(self._h, gl._h, V.ctypes.data_as(vp), offs.ctypes.data_as(vp), b, V.shape[0], V.shape[1], tau,
+                                       None if w is None else w.ctypes.data_as(vp), skip, grp._h, ng, need_docs.ctypes.data_as(vp),
+                                       doc_label.ctypes.data_as(vp), doc_first.ctypes.data_as(vp), ids.ctypes.data_as(vp),
+                                       label.ctypes.data_as(vp), sc.ctypes.data_as(vp), ln.ctypes.data_as(vp), None, stt.ctypes.data_as(vp))
+        _check(st)
+        return _hit_lists(label, sc, ln, b, ng)
+
+    def score_maxsim_lists(self, needs, gl: GraphLaplacian, tau: float, groups, lists, weights=None, on_zero_lambda="raise"):
+        """Extension: the scores F_b of `search_maxsim_lists` (same needs, weights and zero-lambda rule) for every entry of
+        `lists[b]` -> a list of B float64 arrays in the caller's order, duplicates kept (an integer (B, C) array as `lists`
+        returns an array (B, C)); NaN for a document whose members all score NaN and, under on_zero_lambda="skip", for every
+        entry of a need with no vector left; an empty list gives an empty array.  Costs what `search_maxsim_lists` costs
+        without the selection: one double per (need, distinct document) crosses to the host."""
+        V, offs, w, skip, tau, _, grp, docs = self._maxsim_lists_args(needs, gl, tau, groups, 1, lists, weights, on_zero_lambda)
+        need_docs, doc_label, doc_first, ids, inverse = docs
+        b = offs.shape[0] - 1
+        F = np.empty(max(doc_label.shape[0], 1), dtype=np.float64)
+        vp = C.c_void_p
+        st = _L.as_score_maxsim_lists(self._h, gl._h, V.ctypes.data_as(vp), offs.ctypes.data_as(vp), b, V.shape[0], V.shape[1], tau,
+                                      None if w is None else w.ctypes.data_as(vp), skip, grp._h, need_docs.ctypes.data_as(vp),
+                                      doc_label.ctypes.data_as(vp), doc_first.ctypes.data_as(vp), ids.ctypes.data_as(vp),
+                                      F.ctypes.data_as(vp), None, None)
+        _check(st)
+        out = [F[need_docs[i]:need_docs[i + 1]][inverse[i]] for i in range(b)]
+        if isinstance(lists, np.ndarray) and lists.ndim == 2:
+            return np.stack(out).reshape(lists.shape)
+        return out
+
+    def maxsim_lists_counters(self) -> dict:
+        """Extension: `search_maxsim_lists` / `score_maxsim_lists` calls on this space that passed their checks, their needs,
+        the vectors they served, the score-kernel launches, the rows those were asked to gather (per need: entries x vector
+        tiles), the (vector, row) dots, the fold launches, the lambda_q steps (one per call) and the host nanoseconds spent on
+        the document checks and the work tables."""
+        return _counters(_L.as_maxsim_lists_counters, self._h,
+                         ("calls", "needs", "vectors_served", "score_launches", "row_reads", "pairs", "fold_launches", "lambda_steps", "host_ns"))
+
+    def maxsim_lists_geometry(self) -> dict:
+        """Extension: the score kernel's geometry of `search_maxsim_lists` on this space: `tile`, the vectors of a need staged
+        together (every candidate row is gathered once per tile), and `segment`, the entries of a work item at most."""
+        t, r = C.c_int64(0), C.c_int64(0)
+        _check(_L.as_maxsim_lists_geometry(self._h, C.byref(t), C.byref(r)))
+        return {"tile": int(t.value), "segment": int(r.value)}
 
     @staticmethod
     def _diverse_params(n, diversity) -> tuple[int, float]:

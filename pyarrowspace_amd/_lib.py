@@ -65,6 +65,7 @@ SYMBOLS = [
     "as_grouped_kernel_us",
     "as_search_maxsim", "as_score_maxsim", "as_maxsim_counters", "as_maxsim_kernel_us",
     "as_search_maxsim_batch", "as_score_maxsim_batch", "as_maxsim_batch_counters", "as_maxsim_batch_kernel_us",
+    "as_search_maxsim_lists", "as_score_maxsim_lists", "as_maxsim_lists_counters", "as_maxsim_lists_kernel_us", "as_maxsim_lists_geometry",
 ]
 
 _lib = None
@@ -273,6 +274,11 @@ def load():
         "as_score_maxsim_batch": (i32, [vp, vp, vp, vp, i64, i64, i64, f64, vp, i32, vp, vp, vp, i64, vp, vp, vp]),
         "as_maxsim_batch_counters": (i32, [vp, vp, i32]),
         "as_maxsim_batch_kernel_us": (f64, [vp, i32]),
+        "as_search_maxsim_lists": (i32, [vp, vp, vp, vp, i64, i64, i64, f64, vp, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "as_score_maxsim_lists": (i32, [vp, vp, vp, vp, i64, i64, i64, f64, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "as_maxsim_lists_counters": (i32, [vp, vp, i32]),
+        "as_maxsim_lists_kernel_us": (f64, [vp, i32]),
+        "as_maxsim_lists_geometry": (i32, [vp, C.POINTER(i64), C.POINTER(i64)]),
         "as_subset_set_timing": (None, [vp, i32]),
         "as_subset_kernel_us": (f64, [vp]),
         "as_gang_counters": (i32, [vp, vp, i32]),

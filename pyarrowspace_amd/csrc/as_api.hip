@@ -157,6 +157,7 @@ void as_free_space(as_space* sp) {
     subset_work_free(sp->score_ws);
     as_subset_free(sp->range_all);
     lists_work_free(sp->lists_ws);
+    maxsim_lists_work_free(sp->mlists_ws);
     diverse_work_free(sp->diverse_ws);
     if (sp->stream) hipStreamSynchronize(sp->stream);
     hipFree(sp->x32); hipFree(sp->xs); hipFree(sp->x8); hipFree(sp->x8h); hipFree(sp->x4); hipFree(sp->fa4); hipFree(sp->fa8); hipFree(sp->x64); hipFree(sp->n64); hipFree(sp->n32); hipFree(sp->inorm32);
@@ -2393,6 +2394,200 @@ double as_maxsim_batch_kernel_us(const as_space* sp, int32_t part) {
     if (!sp || part < 0 || part > 2) return 0.0;
     const double a = sp->maxsim_batch_us[0].load(std::memory_order_relaxed), f = sp->maxsim_batch_us[1].load(std::memory_order_relaxed);
     return part == 0 ? a + f : (part == 1 ? a : f);
+}
+
+// ---------------------------------------------------------------- late-interaction re-ranking of per-need candidate documents (extension; as_maxsim_lists.hip)
+static int64_t host_ns_since(std::chrono::steady_clock::time_point t0);
+namespace {
+// The documents of both forms, checked before the lambda_q step and narrowed: need y's documents need_docs[y] .. need_docs[y + 1] - 1
+// carry strictly ascending labels of the groups; document dd's entries doc_first[dd] .. doc_first[dd + 1] - 1 are ALL the members of
+// its group, ascending.  gnum: the documents' dense group numbers, ids32: the entries.
+as_status maxsim_lists_docs(const char* who, const as_space* sp, const as_groups* groups, int64_t b, const int64_t* need_docs,
+                            const int64_t* doc_label, const int64_t* doc_first, const int64_t* ids, std::vector<int32_t>& gnum,
+                            std::vector<int32_t>& ids32) {
+    if (need_docs[0] != 0) {
+        set_err("%s: need_docs[0] must be 0, got %lld", who, (long long)need_docs[0]);
+        return AS_EINVAL;
+    }
+    for (int64_t y = 0; y < b; ++y)
+        if (need_docs[y + 1] < need_docs[y]) {
+            set_err("%s: need_docs must not decrease (need %lld)", who, (long long)y);
+            return AS_EINVAL;
+        }
+    const int64_t nd = need_docs[b];
+    if (nd == 0) return AS_OK;
+    if (!doc_label || !doc_first || !ids) {
+        set_err("%s: null argument", who);
+        return AS_EINVAL;
+    }
+    if (doc_first[0] != 0) {
+        set_err("%s: doc_first[0] must be 0, got %lld", who, (long long)doc_first[0]);
+        return AS_EINVAL;
+    }
+    try {
+        gnum.resize((size_t)nd);
+    } catch (const std::bad_alloc&) {
+        set_err("%s: out of host memory for %lld documents", who, (long long)nd);
+        return AS_ENOMEM;
+    }
+    for (int64_t y = 0; y < b; ++y)
+        for (int64_t dd = need_docs[y]; dd < need_docs[y + 1]; ++dd) {
+            const auto it = std::lower_bound(groups->labels.begin(), groups->labels.end(), doc_label[dd]);
+            if (it == groups->labels.end() || *it != doc_label[dd]) {
+                set_err("%s: label %lld is not one of the groups", who, (long long)doc_label[dd]);
+                return AS_EINVAL;
+            }
+            if (dd > need_docs[y] && doc_label[dd] <= doc_label[dd - 1]) {
+                set_err("%s: the labels of need %lld must increase strictly", who, (long long)y);
+                return AS_EINVAL;
+            }
+            const int64_t g = it - groups->labels.begin();
+            gnum[(size_t)dd] = (int32_t)g;
+            if (doc_first[dd + 1] - doc_first[dd] != groups->size[(size_t)g]) {
+                set_err("%s: document %lld of need %lld holds %lld entries, its group has %lld members", who, (long long)(dd - need_docs[y]),
+                        (long long)y, (long long)(doc_first[dd + 1] - doc_first[dd]), (long long)groups->size[(size_t)g]);
+                return AS_EINVAL;
+            }
+        }
+    const int64_t ne = doc_first[nd];
+    if (ne >= (int64_t)1 << 31) {
+        set_err("%s: %lld entries exceed the supported maximum of 2^31 - 1 per call", who, (long long)ne);
+        return AS_EUNSUPPORTED;
+    }
+    try {
+        ids32.resize((size_t)ne);
+    } catch (const std::bad_alloc&) {
+        set_err("%s: out of host memory for %lld ids", who, (long long)ne);
+        return AS_ENOMEM;
+    }
+    for (int64_t dd = 0; dd < nd; ++dd)
+        for (int64_t e = doc_first[dd]; e < doc_first[dd + 1]; ++e) {
+            const int64_t i = ids[e];
+            if (i < 0 || i >= sp->n || groups->dense[(size_t)i] != gnum[(size_t)dd] || (e > doc_first[dd] && i <= ids[e - 1])) {
+                set_err("%s: entry %lld (item %lld) is not the next member of the group with label %lld", who, (long long)e, (long long)i,
+                        (long long)doc_label[dd]);
+                return AS_EINVAL;
+            }
+            ids32[(size_t)e] = (int32_t)i;
+        }
+    return AS_OK;
+}
+// both forms behind their null checks: kk > 0 the search form, else the score form
+as_status maxsim_lists_call(const char* who, const as_space* sp, const as_graph* gr, const double* queries, const int64_t* offsets, int64_t b,
+                            int64_t nv, int64_t d, double tau, const double* weights, int32_t skip_zero, const as_groups* groups, int64_t kk,
+                            const int64_t* need_docs, const int64_t* doc_label, const int64_t* doc_first, const int64_t* ids, int64_t* out_label,
+                            double* out_score, int64_t* out_len, double* out_F, double* out_lambda_q, int32_t* out_status) {
+    AS_TRY(maxsim_checks(who, sp, groups));
+    auto t0 = std::chrono::steady_clock::now();
+    std::vector<int32_t> gnum, ids32;
+    AS_TRY(maxsim_lists_docs(who, sp, groups, b, need_docs, doc_label, doc_first, ids, gnum, ids32));
+    int64_t host_ns = host_ns_since(t0);
+    const int64_t nd = need_docs[b];
+    FusedBatchArgs a;
+    AS_TRY(fused_batch_prepare(who, sp, gr, queries, offsets, b, d, tau, weights, 0, skip_zero, nullptr, out_lambda_q, out_status, a,
+                               &sp->maxsim_lists_count[0], &sp->maxsim_lists_count[1], &sp->maxsim_lists_count[7]));
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    if (nd == 0 || !a.any) {   // no document at all, or no need to serve
+        if (kk == 0) std::fill(out_F, out_F + nd, nan);
+        sp->maxsim_lists_count[8].fetch_add(host_ns, std::memory_order_relaxed);
+        return AS_OK;
+    }
+    MaxsimListsIn in;
+    in.queries = queries; in.voffs = offsets; in.b = b; in.lq = a.lq.data(); in.vst = a.st.data(); in.nst = a.nst.data(); in.wts = a.wts.data();
+    in.need_docs = need_docs; in.doc_first = doc_first; in.doc_gnum = gnum.data(); in.ids = ids32.data(); in.tau = tau; in.kk = kk;
+    std::vector<int64_t> grp;
+    if (kk > 0) {
+        try {
+            grp.resize((size_t)(b * kk));
+        } catch (const std::bad_alloc&) {
+            set_err("%s: out of host memory for %lld needs", who, (long long)b);
+            return AS_ENOMEM;
+        }
+    }
+    int64_t counts[6] = {0, 0, 0, 0, 0, 0};
+    double us[3] = {0.0, 0.0, 0.0};
+    as_status r;
+    {
+        std::lock_guard<std::mutex> lk(sp->lmu);
+        r = hipSetDevice(sp->device) == hipSuccess ? AS_OK : AS_EHIP;
+        if (r != AS_OK) set_err("%s: hipSetDevice failed", who);
+        else r = maxsim_lists_run(sp, in, grp.data(), out_score, out_len, out_F, counts, us);
+        for (int t = 0; t < 3; ++t) sp->maxsim_lists_us[t].store(us[t], std::memory_order_relaxed);
+    }
+    for (int c = 0; c < 5; ++c) sp->maxsim_lists_count[2 + c].fetch_add(counts[c], std::memory_order_relaxed);
+    sp->maxsim_lists_count[8].fetch_add(host_ns + counts[5], std::memory_order_relaxed);
+    if (r != AS_OK) {
+        if (kk > 0)
+            for (int64_t y = 0; y < b; ++y) out_len[y] = 0;
+        return r;
+    }
+    if (kk > 0)
+        for (int64_t y = 0; y < b; ++y)
+            for (int64_t n = 0; n < out_len[y]; ++n) {
+                const int64_t g = grp[(size_t)(y * kk + n)];
+                if (g < 0 || g >= groups->count) {
+                    set_err("%s: the selection returned group %lld", who, (long long)g);
+                    for (int64_t z = 0; z < b; ++z) out_len[z] = 0;
+                    return AS_EHIP;
+                }
+                out_label[y * kk + n] = groups->labels[(size_t)g];
+            }
+    return AS_OK;
+}
+}  // namespace
+
+as_status as_search_maxsim_lists(const as_space* sp, const as_graph* gr, const double* queries, const int64_t* offsets, int64_t b, int64_t nv,
+                                 int64_t d, double tau, const double* weights, int32_t skip_zero, const as_groups* groups, int64_t n_groups,
+                                 const int64_t* need_docs, const int64_t* doc_label, const int64_t* doc_first, const int64_t* ids,
+                                 int64_t* out_label, double* out_score, int64_t* out_len, double* out_lambda_q, int32_t* out_status) {
+    if (!sp || !gr || !queries || !offsets || !groups || !need_docs || !out_label || !out_score || !out_len) {
+        set_err("as_search_maxsim_lists: null argument");
+        return AS_EINVAL;
+    }
+    AS_TRY(fused_batch_offsets("as_search_maxsim_lists", offsets, b, nv));
+    for (int64_t y = 0; y < b; ++y) out_len[y] = 0;
+    if (n_groups < 1 || n_groups > SUBSET_TOPK) {
+        set_err("as_search_maxsim_lists: n_groups must be in [1, %d], got %lld", SUBSET_TOPK, (long long)n_groups);
+        return AS_EINVAL;
+    }
+    return maxsim_lists_call("as_search_maxsim_lists", sp, gr, queries, offsets, b, nv, d, tau, weights, skip_zero, groups, n_groups, need_docs,
+                             doc_label, doc_first, ids, out_label, out_score, out_len, nullptr, out_lambda_q, out_status);
+}
+
+as_status as_score_maxsim_lists(const as_space* sp, const as_graph* gr, const double* queries, const int64_t* offsets, int64_t b, int64_t nv,
+                                int64_t d, double tau, const double* weights, int32_t skip_zero, const as_groups* groups,
+                                const int64_t* need_docs, const int64_t* doc_label, const int64_t* doc_first, const int64_t* ids,
+                                double* out_scores, double* out_lambda_q, int32_t* out_status) {
+    if (!sp || !gr || !queries || !offsets || !groups || !need_docs) {
+        set_err("as_score_maxsim_lists: null argument");
+        return AS_EINVAL;
+    }
+    AS_TRY(fused_batch_offsets("as_score_maxsim_lists", offsets, b, nv));
+    if (need_docs[b] > 0 && !out_scores) {
+        set_err("as_score_maxsim_lists: null argument");
+        return AS_EINVAL;
+    }
+    return maxsim_lists_call("as_score_maxsim_lists", sp, gr, queries, offsets, b, nv, d, tau, weights, skip_zero, groups, 0, need_docs, doc_label,
+                             doc_first, ids, nullptr, nullptr, nullptr, out_scores, out_lambda_q, out_status);
+}
+
+as_status as_maxsim_lists_counters(const as_space* sp, int64_t* out, int32_t n) {
+    return counters_out("as_maxsim_lists_counters", sp, out, n, sp ? sp->maxsim_lists_count : nullptr, 9);
+}
+double as_maxsim_lists_kernel_us(const as_space* sp, int32_t part) {
+    if (!sp || part < 0 || part > 3) return 0.0;
+    double u[3];
+    for (int t = 0; t < 3; ++t) u[t] = sp->maxsim_lists_us[t].load(std::memory_order_relaxed);
+    return part == 0 ? u[0] + u[1] + u[2] : u[part - 1];
+}
+as_status as_maxsim_lists_geometry(const as_space* sp, int64_t* out_tile, int64_t* out_segment) {
+    if (!sp || !out_tile || !out_segment) {
+        set_err("as_maxsim_lists_geometry: null argument");
+        return AS_EINVAL;
+    }
+    *out_tile = maxsim_lists_tile(sp->dp);
+    *out_segment = maxsim_lists_segment();
+    return AS_OK;
 }
 
 // ---------------------------------------------------------------- diversified search (extension; as_diverse.hip)

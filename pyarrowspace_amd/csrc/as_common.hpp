@@ -47,7 +47,7 @@ void dbg(const char* fmt, ...);
 
 }  // namespace as
 
-namespace as { struct SubsetWork; struct ListsWork; struct RangeWork; struct DiverseWork; struct FusedWork; struct GroupedWork; struct MaxsimWork; }
+namespace as { struct SubsetWork; struct ListsWork; struct RangeWork; struct DiverseWork; struct FusedWork; struct GroupedWork; struct MaxsimWork; struct MaxsimListsWork; }
 struct as_subset;
 
 // ---------------------------------------------------------------- handles
@@ -205,6 +205,15 @@ struct as_space {
     // "maxsim_batch_timing" (as_maxsim_batch_kernel_us)
     mutable std::atomic<int64_t> maxsim_batch_count[8] = {};
     mutable std::atomic<double> maxsim_batch_us[2] = {};
+    // as_search_maxsim_lists / as_score_maxsim_lists: their buffers (as_maxsim_lists.hip), made on
+    // first use and grown on demand; calls are serialised by lmu, the per-query list forms' mutex.  as_maxsim_lists_counters: [0]
+    // calls that passed their checks, [1] needs of those calls, [2] vectors served, [3] score-kernel launches, [4] rows the score
+    // kernel was asked to gather (entries x vector tiles), [5] (vector, row) dots, [6] fold launches, [7] lambda_q steps run (1
+    // per call), [8] host nanoseconds spent on the checks and the work tables.  maxsim_lists_us: the score kernel, the fold
+    // kernel and the selection (or the copy out) of the last call under "maxsim_lists_timing" (as_maxsim_lists_kernel_us)
+    mutable struct as::MaxsimListsWork* mlists_ws = nullptr;
+    mutable std::atomic<int64_t> maxsim_lists_count[9] = {};
+    mutable std::atomic<double> maxsim_lists_us[3] = {};
     // as_search_diverse / as_search_diverse_batch: their buffers (as_diverse.hip), made on first use and grown on demand; the
     // selection step of a call is serialised by dmu (the pool step before it is an ordinary search and takes no lock of these).
     // as_diverse_counters: [0] calls that passed their checks, [1] select launches, [2] picks made, [3] dots computed, [4] pool
@@ -847,6 +856,12 @@ void lists_work_free(ListsWork* w);
 double lists_kernel_us(const ListsWork* w);
 void set_lists_timing(int v);   // as_set_tuning("lists_timing", 0 | 1)
 void set_lists_budget_mib(int v);   // as_set_tuning("subset_batch_mib", v): the value set_subset_batch_mib gets
+int64_t lists_budget_doubles();     // ... as the scores (doubles) a chunk may hold
+// lists_select_kernel over nb lists that lie anywhere on the device, queued on `stream`: list t = entries lists[2 t] ..
+// lists[2 t] + lists[2 t + 1] - 1 of scores / ids (a length of 0: no answer); the first min(kk, length) entries by (score
+// descending, id ascending; the ids of a list distinct) -> out_idx / out_score + t * kk, out_len[t] (pinned).  Does not wait.
+as_status lists_select_launch(hipStream_t stream, const int64_t* lists, const double* scores, const int32_t* ids, int64_t kk, int64_t nb,
+                              int64_t* out_len, int64_t* out_idx, double* out_score);
 // Range search (as_range.hip): the survivors of nq rows of m scores ([nq][ld] on the device, queued on the
 // work's stream) against one threshold per row (NaN: that row has no answer) are appended to `res` as nq further lists, each by
 // (score descending, id ascending); ids_host maps a position to its id (null: position == id).  count_only: the lists' lengths
@@ -1014,6 +1029,37 @@ as_status maxsim_batch_pick(MaxsimBatchCall* c, double* out);
 as_status maxsim_batch_end(MaxsimBatchCall* c);
 void set_maxsim_batch_timing(int v);   // as_set_tuning("maxsim_batch_timing", 0 | 1)
 void set_maxsim_batch_mib(int v);      // as_set_tuning("maxsim_batch_mib", v): v > 0 MiB, v < 0 -v KiB, 0 the default (256 MiB)
+// Late-interaction re-ranking of per-need candidate documents (as_maxsim_lists.hip).  The call as
+// the entry points have checked and narrowed it: b needs, need y = the flattened vectors voffs[y] .. voffs[y + 1] - 1 with their
+// lambda_q, status (AS_EZEROLAMBDA: not served) and weights, nst[y] != 0: the need is not served; need y's documents are
+// need_docs[y] .. need_docs[y + 1] - 1, document dd = the entries doc_first[dd] .. doc_first[dd + 1] - 1 of ids (its members) and
+// the dense group number doc_gnum[dd] (ascending inside a need).  kk > 0: need y's first min(kk, documents with a non-NaN F)
+// documents by (F descending, group number ascending) -> out_gnum / out_score + y * kk, out_len[y]; kk == 0: F of every document
+// -> out_F[dd] (NaN: a need that is not served, a document whose scores are all NaN).  Chunks of needs whose scores fit the
+// "subset_batch_mib" budget, one stream wait each.  counts[0] += vectors served, [1] += score launches, [2] += rows asked for, [3]
+// += dots, [4] += fold launches, [5] += host nanoseconds on the work tables; us[0..2]: the score kernel, the fold kernel, the
+// selection or copy of this call under "maxsim_lists_timing".  The buffers live in sp->mlists_ws (under sp->lmu).
+struct MaxsimListsIn {
+    const double* queries = nullptr;   // [nv][d]
+    const int64_t* voffs = nullptr;    // [b + 1]
+    int64_t b = 0;
+    const double* lq = nullptr;        // [nv]
+    const int32_t* vst = nullptr;      // [nv]
+    const int32_t* nst = nullptr;      // [b]
+    const double* wts = nullptr;       // [nv]
+    const int64_t* need_docs = nullptr;   // [b + 1]
+    const int64_t* doc_first = nullptr;   // [nd + 1]
+    const int32_t* doc_gnum = nullptr;    // [nd]
+    const int32_t* ids = nullptr;         // [doc_first[nd]]
+    double tau = 0.0;
+    int64_t kk = 0;
+};
+as_status maxsim_lists_run(const as_space* sp, const MaxsimListsIn& in, int64_t* out_gnum, double* out_score, int64_t* out_len, double* out_F,
+                           int64_t* counts, double* us);
+void maxsim_lists_work_free(MaxsimListsWork* w);
+int64_t maxsim_lists_tile(int64_t dp);   // vectors a tile of the score kernel holds at padded row length dp
+int64_t maxsim_lists_segment();          // entries a segment holds at most
+void set_maxsim_lists_timing(int v);     // as_set_tuning("maxsim_lists_timing", 0 | 1)
 // Diversified search (as_diverse.hip): the greedy of S12 over b pools -- pool i = pool_idx / pool_score + i * kk,
 // pool_len[i] <= kk entries in the order the route returned them (0: a query that is not served) -- n picks wanted, diversity delta.
 // Pick t of query i -> out_idx / out_score / out_margin (may be null) + i * nn + t, nn = min(n, kk); out_len[i] = min(n, pool_len[i]).

@@ -273,6 +273,20 @@ static std::atomic<int> g_lists_timing{0};
 static std::atomic<int> g_lists_budget_mib{256};
 void set_lists_timing(int v) { g_lists_timing.store(v ? 1 : 0, std::memory_order_relaxed); }
 void set_lists_budget_mib(int v) { g_lists_budget_mib.store(v > 0 ? v : 256, std::memory_order_relaxed); }
+int64_t lists_budget_doubles() {
+    return std::max<int64_t>(((int64_t)g_lists_budget_mib.load(std::memory_order_relaxed) << 20) / (int64_t)sizeof(double), 1);
+}
+
+as_status lists_select_launch(hipStream_t stream, const int64_t* lists, const double* scores, const int32_t* ids, int64_t kk, int64_t nb,
+                              int64_t* out_len, int64_t* out_idx, double* out_score) {
+    static_assert(sizeof(ListsList) == 2 * sizeof(int64_t), "a list is its (first, len) pair");
+    ListsSelArgs s;
+    s.lists = (const ListsList*)lists; s.scores = scores; s.ids = ids; s.kk = kk;
+    s.out_len = out_len; s.out_idx = out_idx; s.out_score = out_score; s.nt = 1;
+    hipLaunchKernelGGL(lists_select_kernel<false>, dim3((unsigned)nb), dim3(LSEL_NT), 0, stream, s);
+    AS_HIP(hipGetLastError());
+    return AS_OK;
+}
 
 struct ListsWork {
     int device = 0;

@@ -3683,6 +3683,10 @@ int32_t as_set_tuning(const char* key, int32_t value) {
         set_maxsim_batch_mib(value);
         return 0;
     }
+    if (key && !strcmp(key, "maxsim_lists_timing")) {
+        set_maxsim_lists_timing(value);
+        return 0;
+    }
     return 1;
 }
 
