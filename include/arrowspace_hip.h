@@ -281,6 +281,14 @@ int32_t as_last_scan_bits(const as_space* sp);
  * info[2] = 32-column chunks per row, info[3] = rows of the image; tiles (may be null; info[3] * info[2] * 16 bytes,
  * [tile][chunk][64 rows][16 bytes]) and fa4 (may be null; nrows level steps) are copied to the host. */
 as_status as_debug_nibble_image(const as_space* sp, void* tiles, int64_t tiles_bytes, float* fa4, int64_t nrows, double* info);
+/* Debugging aid (tests of the int8 two-digit image).  as_debug_i8_image makes the image if need be and reports in info[0..6]: 1 when
+ * it is there and usable (0: a non-finite item, no memory), U = max_i s_i |theta_i|_2 / (16256 |x_i|), V = max_i s_i |a2_i|_2 /
+ * (16256 |x_i|), the coefficient 2.001 U + V^2 + 12 * 2^-24 (beyond 1e-3 the k-NN block takes the bf16 pipe), dp8 (the columns
+ * rounded up to 64), the rows of the image (items padded to the row tile, plus one tile), the bad flag (1 non-finite item, 2 no
+ * memory).  Copied to the host, each only where its pointer is not null: x8 (rows * dp8 * 2 bytes: per row and 64-column slab 64
+ * bytes of high digits a1, then 64 of low digits a2), fa8 (nrows scales s_i sqrt(128) / 16256) and x8h (rows * dp8 bytes: the high
+ * digits alone as the coarse scan reads them, [tile of 64 rows][16-column chunk][64 rows][16 bytes]; made if need be). */
+as_status as_debug_i8_image(const as_space* sp, void* x8, int64_t x8_bytes, float* fa8, int64_t nrows, void* x8h, int64_t x8h_bytes, double* info);
 /* 1 when the last batched pass of as_search_batch (its first workspace) ran on the int8 images of items and queries
  * (v_mfma_i32_32x32x32_i8, three products per column) rather than on the bf16 head + tail of the fp32 items. */
 int32_t as_last_batch_int8(const as_space* sp);

@@ -1620,6 +1620,28 @@ class ArrowSpace:
             _raise(st)
         return {"tiles": tiles, "fa4": fa4, "r4max": float(info[1]), "chunks": chunks}
 
+    def debug_i8_image(self):
+        """Debugging aid: the int8 two-digit image as it lies in device memory -- None when the items have no usable image, else a
+        dict with `x8` (int8 [rows][slab][2][64]: per 64-column slab the high digits a1, then the low digits a2), `fa8` (the rows'
+        scales s sqrt(128) / 16256), `x8h` (int8 [tile][chunk][64 rows][16 bytes]: the high digits as the coarse scan reads them),
+        `u` and `v` (the maxima the quantiser measured), `coef` (2.001 u + v^2 + 12 * 2^-24), `dp8`, `rows` and `bad`."""
+        info = np.zeros(7, dtype=np.float64)
+        st = _L.as_debug_i8_image(self._h, None, 0, None, 0, None, 0, info.ctypes.data_as(C.c_void_p))
+        if st:
+            _raise(st)
+        if info[0] == 0.0:
+            return None
+        dp8, rows = int(info[4]), int(info[5])
+        x8 = np.zeros((rows, dp8 // 64, 2, 64), dtype=np.int8)
+        fa8 = np.zeros(rows, dtype=np.float32)
+        x8h = np.zeros((rows // 64, dp8 // 16, 64, 16), dtype=np.int8)
+        st = _L.as_debug_i8_image(self._h, x8.ctypes.data_as(C.c_void_p), x8.nbytes, fa8.ctypes.data_as(C.c_void_p), rows,
+                                  x8h.ctypes.data_as(C.c_void_p), x8h.nbytes, info.ctypes.data_as(C.c_void_p))
+        if st:
+            _raise(st)
+        return {"x8": x8, "fa8": fa8, "x8h": x8h, "u": float(info[1]), "v": float(info[2]), "coef": float(info[3]), "dp8": dp8,
+                "rows": rows, "bad": int(info[6])}
+
     def debug_last_dots(self):
         """Debugging aid: the dots the last single-query scan kept (fp32, one per item) and the error coefficient they carry:
         |dot - x.q| <= coef |x||q|."""

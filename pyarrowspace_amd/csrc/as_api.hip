@@ -820,6 +820,55 @@ as_status as_debug_nibble_image(const as_space* sp, void* tiles, int64_t tiles_b
     return AS_OK;
 }
 
+// The same for the int8 two-digit image under them: the image and its scales as they lie in HBM, the high-digit tiles, and the two
+// maxima the quantiser measured (what every int8 pass prices its dots with).
+as_status as_debug_i8_image(const as_space* sp, void* x8, int64_t x8_bytes, float* fa8, int64_t nrows, void* x8h, int64_t x8h_bytes, double* info) {
+    if (!sp || !info) {
+        set_err("as_debug_i8_image: null argument");
+        return AS_EINVAL;
+    }
+    AS_HIP(hipSetDevice(sp->device));
+    bool have = false;
+    AS_TRY(space_i8_image(sp, &have));
+    const int64_t rows = sp->np + ROW_TILE;
+    info[0] = have ? 1.0 : 0.0;
+    info[1] = sp->x8 ? sp->u8max : 0.0;
+    info[2] = sp->x8 ? sp->v8max : 0.0;
+    info[3] = sp->x8 ? sp->coef8 : 0.0;
+    info[4] = sp->x8 ? (double)sp->dp8 : 0.0;
+    info[5] = (double)rows;
+    info[6] = (double)sp->x8_bad;
+    if (!have) return AS_OK;
+    if (x8) {
+        if (x8_bytes != rows * sp->dp8 * 2) {
+            set_err("as_debug_i8_image: the image is %lld bytes", (long long)(rows * sp->dp8 * 2));
+            return AS_EINVAL;
+        }
+        AS_HIP(hipMemcpy(x8, sp->x8, (size_t)x8_bytes, hipMemcpyDeviceToHost));
+    }
+    if (fa8) {
+        if (nrows < 0 || nrows > rows) {
+            set_err("as_debug_i8_image: at most %lld rows", (long long)rows);
+            return AS_EINVAL;
+        }
+        AS_HIP(hipMemcpy(fa8, sp->fa8, sizeof(float) * (size_t)nrows, hipMemcpyDeviceToHost));
+    }
+    if (x8h) {
+        if (x8h_bytes != rows * sp->dp8) {
+            set_err("as_debug_i8_image: the high-digit tiles are %lld bytes", (long long)(rows * sp->dp8));
+            return AS_EINVAL;
+        }
+        bool have_h = false;
+        AS_TRY(space_i8h_image(sp, &have_h));
+        if (!have_h) {
+            set_err("as_debug_i8_image: no memory for the high-digit tiles");
+            return AS_ENOMEM;
+        }
+        AS_HIP(hipMemcpy(x8h, sp->x8h, (size_t)x8h_bytes, hipMemcpyDeviceToHost));
+    }
+    return AS_OK;
+}
+
 int32_t as_last_batch_int8(const as_space* sp) { return sp && sp->qcache_b ? as_query_scan_int8(sp->qcache_b) : 0; }
 
 as_status as_gang_counters(const as_space* sp, int64_t* out, int32_t n) {
