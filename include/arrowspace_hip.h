@@ -736,6 +736,39 @@ as_status as_diverse_counters(const as_space* sp, int64_t* out, int32_t n);
 /* measurement: the device microseconds of the select kernel, summed over the chunks of the last diversified call on this space
  * that ran under as_set_tuning("diverse_timing", 1) (HIP events around the kernel; off by default) */
 double as_diverse_kernel_us(const as_space* sp);
+/* ---- Extension: graph-diffusion search.  The hit list of the ordinary route (as_search, or
+ * as_search_subset with `sub`; batched: as_search_batch / as_search_subset_batch) seeds y (y[c_p] = s_p, entries with a non-finite
+ * score left out), and f <- fl(fl(alpha * S f) + fl((1 - alpha) * y)) runs `steps` times from f = y over the WHOLE item graph,
+ * S = -lap over the stored off-diagonal entries, each row summed in CSR order, every product and sum rounded once.  The search
+ * forms return the first min(topk, |sub|) items of `sub` (NULL: every item) by (f descending, index ascending) as (index, f),
+ * lists at stride min(topk, n, |sub|); the score form writes f at the m listed ids ([b][m], caller's order, duplicates kept; b = 1
+ * serves a single query); as_diffuse_seeds takes the seeds themselves -- query i's are the entries offsets_host[i] ..
+ * offsets_host[i + 1] - 1 of ids_host / values_host, ids distinct per query and inside [0, n), values finite -- and writes the whole
+ * f, [b][n] doubles: the whole block crosses to the host.  Refused before anything is launched, the route's search included:
+ * alpha outside [0, 1) or NaN, steps outside [0, 64], bad ids or seeds (AS_EINVAL); a feature-mode graph, a row-sharded graph or
+ * space (AS_EUNSUPPORTED).  A zero lambda_q: the single form returns AS_EZEROLAMBDA as as_search does; in the batched forms that
+ * query gets out_len 0 / a row of NaN and status AS_EZEROLAMBDA, the others are served.  The buffers (two f blocks of n x C
+ * doubles, C = 1, 16 or 64 columns per chunk within the "diffuse_mib" budget, default 1024 MiB for the pair: 64 columns up to 1M items) live in the space and
+ * grow on demand; the recurrences of calls on one space are serialised, as_search runs beside them.  out_lambda_q and out_status
+ * may be NULL.  Tunings (as_set_tuning; results never depend on them): "diffuse_mib", "diffuse_cols" (columns of a chunk at most),
+ * "diffuse_tile_edges" (edges of an LDS tile of the one-column kernel), "diffuse_grid_cap" (clips the step kernels' grids),
+ * "diffuse_timing" = 1 / 0. */
+as_status as_search_diffuse(const as_space* sp, const as_graph* gr, const double* query, int64_t d, double tau, double alpha, int64_t steps,
+                            const as_subset* sub, int64_t* out_idx, double* out_score, int64_t* out_len, double* out_lambda_q);
+as_status as_search_diffuse_batch(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau, double alpha,
+                                  int64_t steps, const as_subset* sub, int64_t* out_idx, double* out_score, int64_t* out_len,
+                                  double* out_lambda_q, int32_t* out_status);
+as_status as_score_diffuse_batch(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau, double alpha,
+                                 int64_t steps, const int64_t* ids_host, int64_t m, double* out_scores, double* out_lambda_q,
+                                 int32_t* out_status);
+as_status as_diffuse_seeds(const as_space* sp, const as_graph* gr, const int64_t* ids_host, const double* values_host,
+                           const int64_t* offsets_host, int64_t b, double alpha, int64_t steps, double* out_f);
+/* out[0] calls of the four entries above that passed their checks, [1] route searches run (single or batched), [2] column chunks,
+ * [3] step launches, [4] seeds uploaded */
+as_status as_diffuse_counters(const as_space* sp, int64_t* out, int32_t n);
+/* measurement: the device microseconds of the steps (step and seed kernels), summed over the chunks of the last diffusion call on
+ * this space that ran under as_set_tuning("diffuse_timing", 1) (HIP events around them; off by default) */
+double as_diffuse_kernel_us(const as_space* sp);
 /* ---- Extension: fused multi-query search.  ONE answer to j >= 1 query vectors, row-major [j][d] in HOST memory,
  * with finite weights w (weights == NULL: 1/j each; negative weights are legal).  s_v(i): the S11 score of item i for vector v
  * with the bits as_score_items_batch writes at [v][i] (lambda_q of every vector from ONE as_search_batch over the j vectors, the

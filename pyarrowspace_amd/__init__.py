@@ -1318,6 +1318,140 @@ class ArrowSpace:
         """Extension: diversified calls on this space since it was made and the work they launched."""
         return _counters(_L.as_diverse_counters, self._h, ("calls", "launches", "picks", "dots", "pool_steps"))
 
+    @staticmethod
+    def _diffuse_params(alpha, steps) -> tuple[float, int]:
+        if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)):
+            raise ValueError(f"steps must be an integer in [0, 64], got {steps!r}")
+        if not 0 <= steps <= 64:
+            raise ValueError(f"steps must lie in [0, 64], got {steps}")
+        a = float(alpha)
+        if not 0.0 <= a < 1.0:   # (NaN fails both comparisons)
+            raise ValueError(f"alpha must lie in [0, 1), got {alpha}")
+        return a, int(steps)
+
+    @staticmethod
+    def _diffuse_seeds(seeds, nitems: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """B pairs (ids, values) as (ids int64 flat, values float64 flat, offsets int64 [B + 1]); every check of `diffuse`."""
+        ids_parts, val_parts = [], []
+        for i, pair in enumerate(seeds):
+            try:
+                ids, vals = pair
+            except (TypeError, ValueError):
+                raise ValueError(f"argument 'seeds': entry {i}: expected a pair (ids, values)") from None
+            ids = np.asarray(ids)
+            if ids.size == 0:
+                ids = ids.astype(np.int64)
+            if ids.dtype.kind not in "iu":
+                raise TypeError(f"argument 'seeds': entry {i}: expected integer item ids, got dtype {ids.dtype}")
+            vals = np.ascontiguousarray(vals, dtype=np.float64)
+            if ids.ndim != 1 or vals.ndim != 1 or ids.shape[0] != vals.shape[0]:
+                raise ValueError(f"argument 'seeds': entry {i}: expected as many values as ids, got shapes {ids.shape} and {vals.shape}")
+            if ids.size and (int(ids.min()) < 0 or int(ids.max()) >= nitems):
+                raise ValueError(f"argument 'seeds': entry {i}: an id is outside [0, {nitems})")
+            if np.unique(ids).shape[0] != ids.shape[0]:
+                raise ValueError(f"argument 'seeds': entry {i}: the ids must be distinct")
+            if not np.isfinite(vals).all():
+                raise ValueError(f"argument 'seeds': entry {i}: a value is not finite")
+            ids_parts.append(ids.astype(np.int64))
+            val_parts.append(vals)
+        offs = np.zeros(len(ids_parts) + 1, dtype=np.int64)
+        if ids_parts:
+            np.cumsum([p.shape[0] for p in ids_parts], out=offs[1:])
+        ids = np.ascontiguousarray(np.concatenate(ids_parts), dtype=np.int64) if ids_parts else np.empty(0, dtype=np.int64)
+        vals = np.ascontiguousarray(np.concatenate(val_parts), dtype=np.float64) if val_parts else np.empty(0, dtype=np.float64)
+        return ids, vals, offs
+
+    def search_diffuse(self, item, gl: GraphLaplacian, tau: float, alpha: float, steps: int, subset=None):
+        """Extension: graph-diffusion search (manifold ranking over the index's k-NN graph) -> list[(index, f)]: the first
+        min(topk, |subset|) items of the subset (None: every item) by (f descending, index ascending).  The hit list of
+        `search` (of `search_subset` with a subset) seeds y (y[index] = score, a non-finite score left out), and
+        f <- alpha * S f + (1 - alpha) * y runs `steps` times from f = y over the WHOLE item graph, S = D^-1/2 A D^-1/2 (the
+        off-diagonal of `gl.to_csr()`, sign flipped), every row summed in CSR order, every product and sum rounded once, so f
+        has the bits of the numpy recurrence.  Items near the best hits on the graph rise even when their own score is
+        modest.  steps = 0 or alpha = 0 gives f = y.  The subset restricts the seeds and the answer, not the diffusion.
+        0 <= alpha < 1, 0 <= steps <= 64 (an integer), else ValueError; a feature-mode or row-sharded index raises
+        ValueError.  Costs one ordinary `search` / `search_subset` (a query whose lambda_q is 0 panics as there), then
+        `steps` passes over the graph's CSR on the device and one exact selection there: only the list crosses."""
+        _need_gl(gl)
+        q = self._query(item)
+        a, steps = self._diffuse_params(alpha, steps)
+        sub = self._as_subset(subset, optional=True)
+        n = max(self._hits_bound(gl, sub), 1)
+        idx = np.empty(n, dtype=np.int64)
+        sc = np.empty(n, dtype=np.float64)
+        ln, lq = C.c_int64(0), C.c_double(0.0)
+        st = _L.as_search_diffuse(self._h, gl._h, q.ctypes.data, q.shape[0], float(tau), a, steps, _handle(sub), idx.ctypes.data,
+                                  sc.ctypes.data, C.byref(ln), C.byref(lq))
+        _check(st)
+        return list(zip(idx[:ln.value].tolist(), sc[:ln.value].tolist()))
+
+    def search_batch_diffuse(self, items, gl: GraphLaplacian, tau: float, alpha: float, steps: int, subset=None):
+        """Extension: batched graph-diffusion search, B queries [B, D] -> list of B lists; list i is `search_diffuse` over the
+        pool `search_batch` (with a subset: `search_batch_subset`) gives query i.  A query's f depends on its own seeds,
+        alpha, steps and the graph only.  A query whose lambda_q is 0 gets an empty list, the others are served.  Costs one
+        `search_batch` / `search_batch_subset`, then per chunk of 16 or 64 queries `steps` passes over the CSR that serve the
+        whole chunk, and one selection."""
+        _need_gl(gl)
+        Q = _queries_2d(items)
+        a, steps = self._diffuse_params(alpha, steps)
+        sub = self._as_subset(subset, optional=True)
+        b = Q.shape[0]
+        kk = self._hits_bound(gl, sub)
+        (idx, sc, ln), stt = _hit_buffers(b, kk), _statuses(b)
+        vp = C.c_void_p
+        st = _L.as_search_diffuse_batch(self._h, gl._h, Q.ctypes.data_as(vp), b, Q.shape[1], float(tau), a, steps, _handle(sub),
+                                        idx.ctypes.data_as(vp), sc.ctypes.data_as(vp), ln.ctypes.data_as(vp), None, stt.ctypes.data_as(vp))
+        _check(st)
+        return _hit_lists(idx, sc, ln, b, kk)
+
+    def score_diffuse(self, item, gl: GraphLaplacian, tau: float, alpha: float, steps: int, ids) -> np.ndarray:
+        """Extension: f of `search_diffuse` (no subset) at the listed ids -> ndarray[float64] of shape (len(ids),), the caller's
+        order, duplicates kept.  A query whose lambda_q is 0 panics as `search` does.  Only len(ids) doubles cross."""
+        q = self._query(item)
+        out = self._score_diffuse(q.reshape(1, -1), gl, tau, alpha, steps, ids, True)
+        return out[0]
+
+    def score_diffuse_batch(self, items, gl: GraphLaplacian, tau: float, alpha: float, steps: int, ids) -> np.ndarray:
+        """Extension: f of `search_batch_diffuse` (no subset) at the listed ids -> ndarray[float64] of shape (B, len(ids)); a
+        query whose lambda_q is 0 gets a row of NaN, the others are served."""
+        return self._score_diffuse(_queries_2d(items), gl, tau, alpha, steps, ids, False)
+
+    def _score_diffuse(self, Q, gl, tau, alpha, steps, ids, panic):
+        _need_gl(gl)
+        a, steps = self._diffuse_params(alpha, steps)
+        ids = _item_ids(ids, self.nitems, "ids")
+        b, m = Q.shape[0], ids.shape[0]
+        out = np.empty((b, m), dtype=np.float64)
+        stt = _statuses(b)
+        vp = C.c_void_p
+        st = _L.as_score_diffuse_batch(self._h, gl._h, Q.ctypes.data_as(vp), b, Q.shape[1], float(tau), a, steps, ids.ctypes.data_as(vp), m,
+                                       out.ctypes.data_as(vp), None, stt.ctypes.data_as(vp))
+        _check(st, stt if panic else None, b)
+        return out
+
+    def diffuse(self, gl: GraphLaplacian, seeds, alpha: float, steps: int) -> np.ndarray:
+        """Extension: the raw form of graph diffusion -> ndarray[float64] of shape (B, nitems): row b is f after `steps` steps
+        of the recurrence of `search_diffuse` from the seeds of `seeds[b]`, a pair (ids, values): y[ids[j]] = values[j], 0
+        elsewhere.  The ids of a pair must be distinct and inside [0, nitems) and the values finite (ValueError); a float or
+        boolean dtype of ids raises TypeError.  It runs the recurrence and nothing else: no search, no selection.  The whole
+        B x nitems block crosses to the host (8 MB per query at a million items): use `score_diffuse` or `search_diffuse`
+        where a few entries are wanted."""
+        _need_gl(gl)
+        a, steps = self._diffuse_params(alpha, steps)
+        ids, vals, offs = self._diffuse_seeds(seeds, self.nitems)
+        b = offs.shape[0] - 1
+        out = np.empty((b, self.nitems), dtype=np.float64)
+        vp = C.c_void_p
+        st = _L.as_diffuse_seeds(self._h, gl._h, ids.ctypes.data_as(vp), vals.ctypes.data_as(vp), offs.ctypes.data_as(vp), b, a, steps,
+                                 out.ctypes.data_as(vp))
+        _check(st)
+        return out
+
+    def diffuse_counters(self) -> dict:
+        """Extension: graph-diffusion calls on this space that passed their checks, the route searches they ran (single or
+        batched), the column chunks, the step launches and the seeds uploaded."""
+        return _counters(_L.as_diffuse_counters, self._h, ("calls", "route searches", "column chunks", "step launches", "seeds uploaded"))
+
     def _lists_args(self, items, gl, lists):
         _need_gl(gl)
         Q = _queries_2d(items)

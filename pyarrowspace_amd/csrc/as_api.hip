@@ -159,6 +159,7 @@ void as_free_space(as_space* sp) {
     lists_work_free(sp->lists_ws);
     maxsim_lists_work_free(sp->mlists_ws);
     diverse_work_free(sp->diverse_ws);
+    diffuse_work_free(sp->diffuse_ws);
     if (sp->stream) hipStreamSynchronize(sp->stream);
     hipFree(sp->x32); hipFree(sp->xs); hipFree(sp->x8); hipFree(sp->x8h); hipFree(sp->x4); hipFree(sp->fa4); hipFree(sp->fa8); hipFree(sp->x64); hipFree(sp->n64); hipFree(sp->n32); hipFree(sp->inorm32);
     hipFree(sp->lam64); hipFree(sp->lam32);
@@ -1200,7 +1201,9 @@ namespace {
 // run leaves nothing on the work's stream when the lock is released.
 // The lock rules of the filtered forms: the lambda_q step comes first and has returned -- as_search_batch has released sp->bmu --
 // before a handle's mutex, sp->smu or sp->lmu (the lists' buffers) is taken; sp->rmu guards only the creation of the subset of
-// all items and is released before that handle's mutex is taken; no two of these mutexes are ever held together.
+// all items and is released before that handle's mutex is taken; no two of these mutexes are ever held together.  One mutex is
+// taken inside a handle's: sp->fmu, by the diffusion forms (their recurrence runs on the space's diffusion buffers, their selection
+// on the handle's), always in that order; nothing takes a handle's mutex, sp->smu or sp->lmu under sp->fmu.
 struct Candidates {
     const as_space* sp;
     SubsetWork* w = nullptr;
@@ -2742,6 +2745,251 @@ double as_diverse_kernel_us(const as_space* sp) {
     if (!sp) return 0.0;
     std::lock_guard<std::mutex> lk(sp->dmu);
     return diverse_kernel_us(sp->diverse_ws);
+}
+
+// ---------------------------------------------------------------- graph-diffusion search (extension; as_diffuse.hip)
+static as_status lists_checks(const char* who, const as_space* sp, const int64_t* ids_host, const int64_t* offs, int64_t b);   // (below)
+namespace {
+// what every form refuses before anything is launched, the route's search included
+as_status diffuse_param_checks(const char* who, const as_space* sp, const as_graph* gr, double alpha, int64_t steps) {
+    if (!(alpha >= 0.0 && alpha < 1.0)) {
+        set_err("%s: alpha must lie in [0, 1), got %g", who, alpha);
+        return AS_EINVAL;
+    }
+    if (steps < 0 || steps > 64) {
+        set_err("%s: steps must lie in [0, 64], got %lld", who, (long long)steps);
+        return AS_EINVAL;
+    }
+    if (gr->lambda_mode == AS_LAMBDA_FEATURE) {
+        set_err("%s: a feature-mode graph (its Laplacian is over the columns) is not supported", who);
+        return AS_EUNSUPPORTED;
+    }
+    return AS_OK;
+}
+// ... and, behind subset_checks (or graph_matches and the shard test of the raw form): the graph covers exactly the space's items
+as_status diffuse_graph_checks(const char* who, const as_space* sp, const as_graph* gr) {
+    if (gr->n != sp->n) {
+        set_err("%s: the graph (%lld nodes) does not cover exactly the %lld items of the space", who, (long long)gr->n, (long long)sp->n);
+        return AS_EINVAL;
+    }
+    return AS_OK;
+}
+as_status diffuse_checks(const char* who, const as_space* sp, const as_graph* gr, int64_t d, double tau, double alpha, int64_t steps,
+                         const as_subset* sub) {
+    AS_TRY(diffuse_param_checks(who, sp, gr, alpha, steps));
+    AS_TRY(own_subset(who, sp, sub));
+    AS_TRY(subset_checks(who, sp, gr, d, &tau, 1));
+    return diffuse_graph_checks(who, sp, gr);
+}
+// the seeds of S19 from b pools at stride kk: a pool entry whose score is not finite is left out
+as_status diffuse_pool_seeds(const char* who, const int64_t* pidx, const double* psc, const int64_t* plen, int64_t kk, int64_t b,
+                             std::vector<int64_t>& offs, std::vector<int64_t>& ids, std::vector<double>& vals) {
+    try {
+        offs.assign((size_t)b + 1, 0);
+        for (int64_t i = 0; i < b; ++i) {
+            for (int64_t p = 0; p < plen[i]; ++p)
+                if (std::isfinite(psc[i * kk + p])) {
+                    ids.push_back(pidx[i * kk + p]);
+                    vals.push_back(psc[i * kk + p]);
+                }
+            offs[(size_t)i + 1] = (int64_t)ids.size();
+        }
+    } catch (const std::bad_alloc&) {
+        set_err("%s: out of host memory for the seeds of %lld queries", who, (long long)b);
+        return AS_ENOMEM;
+    }
+    return AS_OK;
+}
+// the recurrence and its output, under sp->fmu
+as_status diffuse_locked(const char* who, const as_space* sp, const as_graph* gr, const DiffuseCall& dc) {
+    int64_t counts[3] = {0, 0, 0};
+    std::lock_guard<std::mutex> lk(sp->fmu);
+    if (hipSetDevice(sp->device) != hipSuccess) {
+        set_err("%s: hipSetDevice failed", who);
+        return AS_EHIP;
+    }
+    const as_status s = diffuse_run(sp, gr, dc, counts);
+    for (int i = 0; i < 3; ++i) sp->diffuse_count[2 + i].fetch_add(counts[i], std::memory_order_relaxed);
+    return s;
+}
+}  // namespace
+
+as_status as_search_diffuse(const as_space* sp, const as_graph* gr, const double* query, int64_t d, double tau, double alpha, int64_t steps,
+                            const as_subset* sub, int64_t* out_idx, double* out_score, int64_t* out_len, double* out_lambda_q) {
+    if (!sp || !gr || !query || !out_len || ((!sub || sub->m > 0) && (!out_idx || !out_score))) {
+        set_err("as_search_diffuse: null argument");
+        return AS_EINVAL;
+    }
+    *out_len = 0;
+    AS_TRY(diffuse_checks("as_search_diffuse", sp, gr, d, tau, alpha, steps, sub));
+    sp->diffuse_count[0].fetch_add(1, std::memory_order_relaxed);
+    // the pool: ONE ordinary search of the route, its hits in its order
+    int64_t pidx[SUBSET_TOPK], plen = 0;
+    double psc[SUBSET_TOPK];
+    double lq = 0.0;
+    sp->diffuse_count[1].fetch_add(1, std::memory_order_relaxed);
+    const as_status s = sub ? as_search_subset(sp, gr, query, d, tau, sub, pidx, psc, &plen, &lq)
+                            : search_pooled(sp, gr, query, d, tau, pidx, psc, &plen, &lq);
+    if (out_lambda_q) *out_lambda_q = lq;
+    if (s != AS_OK) return s;
+    if (sub && sub->m == 0) return AS_OK;
+    std::vector<int64_t> offs, ids;
+    std::vector<double> vals;
+    AS_TRY(diffuse_pool_seeds("as_search_diffuse", pidx, psc, &plen, SUBSET_TOPK, 1, offs, ids, vals));
+    const Candidates c("as_search_diffuse", sp, sub);
+    AS_TRY(c.status);
+    DiffuseCall dc;
+    dc.b = 1; dc.offs = offs.data(); dc.ids = ids.data(); dc.vals = vals.data(); dc.alpha = alpha; dc.steps = steps;
+    dc.sel = c.w; dc.pos_ids = c.w->ids; dc.m = c.m; dc.k = hits_bound(sp, gr, c.m); dc.stride = dc.k;
+    dc.out_idx = out_idx; dc.out_score = out_score; dc.out_len = out_len;
+    return c.fail(diffuse_locked("as_search_diffuse", sp, gr, dc));
+}
+
+namespace {
+// the pools of a batched form (ONE batched search of the route over all b queries), as seeds; served[i] = 0: a zero lambda_q
+as_status diffuse_batch_pools(const char* who, const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau,
+                              const as_subset* sub, double* out_lambda_q, int32_t* out_status, std::vector<int64_t>& offs,
+                              std::vector<int64_t>& ids, std::vector<double>& vals, std::vector<int32_t>& served) {
+    const int64_t kks = std::max<int64_t>(hits_bound(sp, gr, sub ? sub->m : sp->n), 1);
+    std::vector<int64_t> pidx, plen;
+    std::vector<double> psc, lq;
+    std::vector<int32_t> st;
+    try {
+        pidx.resize((size_t)(b * kks));
+        psc.resize((size_t)(b * kks));
+        plen.assign((size_t)b, 0);
+        lq.assign((size_t)b, 0.0);
+        st.assign((size_t)b, 0);
+        served.assign((size_t)b, 1);
+    } catch (const std::bad_alloc&) {
+        set_err("%s: out of host memory for %lld queries", who, (long long)b);
+        return AS_ENOMEM;
+    }
+    sp->diffuse_count[1].fetch_add(1, std::memory_order_relaxed);
+    AS_TRY(sub ? as_search_subset_batch(sp, gr, queries, b, d, tau, sub, pidx.data(), psc.data(), plen.data(), lq.data(), st.data())
+               : as_search_batch(sp, gr, queries, b, d, tau, pidx.data(), psc.data(), plen.data(), lq.data(), st.data()));
+    for (int64_t i = 0; i < b; ++i) {
+        if (out_lambda_q) out_lambda_q[i] = lq[i];
+        if (out_status) out_status[i] = st[i];
+        if (st[i] == AS_EZEROLAMBDA) {
+            plen[i] = 0;
+            served[i] = 0;
+        }
+    }
+    return diffuse_pool_seeds(who, pidx.data(), psc.data(), plen.data(), kks, b, offs, ids, vals);
+}
+}  // namespace
+
+as_status as_search_diffuse_batch(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau, double alpha,
+                                  int64_t steps, const as_subset* sub, int64_t* out_idx, double* out_score, int64_t* out_len,
+                                  double* out_lambda_q, int32_t* out_status) {
+    if (!sp || !gr || b < 0 || (b > 0 && (!queries || !out_len))) {
+        set_err("as_search_diffuse_batch: null argument");
+        return AS_EINVAL;
+    }
+    const int64_t kk = hits_bound(sp, gr, sub ? sub->m : sp->n);
+    if (b > 0 && kk > 0 && (!out_idx || !out_score)) {
+        set_err("as_search_diffuse_batch: null argument");
+        return AS_EINVAL;
+    }
+    for (int64_t i = 0; i < b; ++i) out_len[i] = 0;
+    AS_TRY(diffuse_checks("as_search_diffuse_batch", sp, gr, d, tau, alpha, steps, sub));
+    sp->diffuse_count[0].fetch_add(1, std::memory_order_relaxed);
+    if (b == 0) return AS_OK;
+    std::vector<int64_t> offs, ids;
+    std::vector<double> vals;
+    std::vector<int32_t> served;
+    AS_TRY(diffuse_batch_pools("as_search_diffuse_batch", sp, gr, queries, b, d, tau, sub, out_lambda_q, out_status, offs, ids, vals, served));
+    if (kk == 0) return AS_OK;
+    const Candidates c("as_search_diffuse_batch", sp, sub);
+    AS_TRY(c.status);
+    DiffuseCall dc;
+    dc.b = b; dc.offs = offs.data(); dc.ids = ids.data(); dc.vals = vals.data(); dc.served = served.data(); dc.alpha = alpha; dc.steps = steps;
+    dc.sel = c.w; dc.pos_ids = c.w->ids; dc.m = c.m; dc.k = kk; dc.stride = kk;
+    dc.out_idx = out_idx; dc.out_score = out_score; dc.out_len = out_len;
+    return c.fail(diffuse_locked("as_search_diffuse_batch", sp, gr, dc));
+}
+
+as_status as_score_diffuse_batch(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau, double alpha,
+                                 int64_t steps, const int64_t* ids_host, int64_t m, double* out_scores, double* out_lambda_q,
+                                 int32_t* out_status) {
+    if (!sp || !gr || b < 0 || m < 0 || (b > 0 && !queries) || (m > 0 && !ids_host) || (b > 0 && m > 0 && !out_scores)) {
+        set_err("as_score_diffuse_batch: null argument");
+        return AS_EINVAL;
+    }
+    AS_TRY(ids_in_range("as_score_diffuse_batch", sp, ids_host, m));
+    AS_TRY(diffuse_checks("as_score_diffuse_batch", sp, gr, d, tau, alpha, steps, nullptr));
+    std::vector<int32_t> ids32;
+    AS_TRY(checked_ids("as_score_diffuse_batch", ids_host, m, ids32));
+    sp->diffuse_count[0].fetch_add(1, std::memory_order_relaxed);
+    if (b == 0) return AS_OK;
+    std::vector<int64_t> offs, ids;
+    std::vector<double> vals;
+    std::vector<int32_t> served;
+    AS_TRY(diffuse_batch_pools("as_score_diffuse_batch", sp, gr, queries, b, d, tau, nullptr, out_lambda_q, out_status, offs, ids, vals, served));
+    if (m == 0) return AS_OK;
+    for (int64_t i = 0; i < b; ++i)
+        if (!served[(size_t)i])
+            for (int64_t j = 0; j < m; ++j) out_scores[i * m + j] = std::numeric_limits<double>::quiet_NaN();
+    DiffuseCall dc;
+    dc.b = b; dc.offs = offs.data(); dc.ids = ids.data(); dc.vals = vals.data(); dc.served = served.data(); dc.alpha = alpha; dc.steps = steps;
+    dc.pick_ids = ids32.data(); dc.m = m; dc.out_rows = out_scores;
+    return diffuse_locked("as_score_diffuse_batch", sp, gr, dc);
+}
+
+as_status as_diffuse_seeds(const as_space* sp, const as_graph* gr, const int64_t* ids_host, const double* values_host,
+                           const int64_t* offsets_host, int64_t b, double alpha, int64_t steps, double* out_f) {
+    const char* who = "as_diffuse_seeds";
+    if (!sp || !gr || b < 0 || !offsets_host || (b > 0 && !out_f)) {
+        set_err("%s: null argument", who);
+        return AS_EINVAL;
+    }
+    AS_TRY(diffuse_param_checks(who, sp, gr, alpha, steps));
+    if (offsets_host[b] > 0 && (!ids_host || !values_host)) {
+        set_err("%s: null argument", who);
+        return AS_EINVAL;
+    }
+    AS_TRY(lists_checks(who, sp, ids_host, offsets_host, b));   // the offsets, the total, every id
+    for (int64_t e = 0; e < offsets_host[b]; ++e)
+        if (!std::isfinite(values_host[e])) {
+            set_err("%s: seed value %lld is not finite", who, (long long)e);
+            return AS_EINVAL;
+        }
+    try {
+        std::vector<int64_t> seen;
+        for (int64_t i = 0; i < b; ++i) {
+            seen.assign(ids_host + offsets_host[i], ids_host + offsets_host[i + 1]);
+            std::sort(seen.begin(), seen.end());
+            if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) {
+                set_err("%s: the seed ids of query %lld are not distinct", who, (long long)i);
+                return AS_EINVAL;
+            }
+        }
+    } catch (const std::bad_alloc&) {
+        set_err("%s: out of host memory for the seeds", who);
+        return AS_ENOMEM;
+    }
+    AS_TRY(graph_matches(sp, gr, who));
+    if (sp->row_offset != 0 || gr->ncols) {
+        set_err("%s: a shard of a row-sharded index is not supported", who);
+        return AS_EUNSUPPORTED;
+    }
+    AS_TRY(diffuse_graph_checks(who, sp, gr));
+    sp->diffuse_count[0].fetch_add(1, std::memory_order_relaxed);
+    if (b == 0) return AS_OK;
+    DiffuseCall dc;
+    dc.b = b; dc.offs = offsets_host; dc.ids = ids_host; dc.vals = values_host; dc.alpha = alpha; dc.steps = steps;
+    dc.out_rows = out_f;
+    return diffuse_locked(who, sp, gr, dc);
+}
+
+as_status as_diffuse_counters(const as_space* sp, int64_t* out, int32_t n) {
+    return counters_out("as_diffuse_counters", sp, out, n, sp ? sp->diffuse_count : nullptr, 5);
+}
+double as_diffuse_kernel_us(const as_space* sp) {
+    if (!sp) return 0.0;
+    std::lock_guard<std::mutex> lk(sp->fmu);
+    return diffuse_kernel_us(sp->diffuse_ws);
 }
 
 // ---------------------------------------------------------------- per-query candidate lists (extension)

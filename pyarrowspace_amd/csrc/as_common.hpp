@@ -47,7 +47,7 @@ void dbg(const char* fmt, ...);
 
 }  // namespace as
 
-namespace as { struct SubsetWork; struct ListsWork; struct RangeWork; struct DiverseWork; struct FusedWork; struct GroupedWork; struct MaxsimWork; struct MaxsimListsWork; }
+namespace as { struct SubsetWork; struct ListsWork; struct RangeWork; struct DiverseWork; struct FusedWork; struct GroupedWork; struct MaxsimWork; struct MaxsimListsWork; struct DiffuseWork; }
 struct as_subset;
 
 // ---------------------------------------------------------------- handles
@@ -221,6 +221,15 @@ struct as_space {
     mutable struct as::DiverseWork* diverse_ws = nullptr;
     mutable std::mutex dmu;
     mutable std::atomic<int64_t> diverse_count[5] = {};
+    // as_search_diffuse / as_search_diffuse_batch / as_score_diffuse_batch / as_diffuse_seeds: their
+    // buffers (as_diffuse.hip), made on first use and grown on demand; the recurrence of a call is serialised by fmu (the pool step
+    // before it is an ordinary search and takes no lock of these; the search forms take fmu INSIDE the mutex of the handle whose
+    // selection buffers they use, always in that order, and nothing takes a handle's mutex under fmu).  as_diffuse_counters: [0]
+    // calls that passed their checks, [1] route searches run (single or batched), [2] column chunks, [3] step launches, [4] seeds
+    // uploaded
+    mutable struct as::DiffuseWork* diffuse_ws = nullptr;
+    mutable std::mutex fmu;
+    mutable std::atomic<int64_t> diffuse_count[5] = {};
 };
 
 struct as_graph {
@@ -1072,5 +1081,40 @@ void diverse_work_free(DiverseWork* w);
 double diverse_kernel_us(const DiverseWork* w);
 void set_diverse_timing(int v);   // as_set_tuning("diverse_timing", 0 | 1)
 void set_diverse_chunk(int v);    // as_set_tuning("diverse_chunk", v)
+// Graph diffusion (as_diffuse.hip): the S19 recurrence for b queries over the whole graph `gr`.  Query
+// i's seeds are the entries offs[i] .. offs[i + 1] - 1 of ids / vals (distinct ids inside [0, n), finite values: the caller has
+// checked them); served (may be null) 0: that query is left out -- no column, no output.  Column chunks of C = 1, 16 or 64 queries
+// ("diffuse_cols", "diffuse_mib"); per chunk one upload of the seed table, `steps` step launches (each followed by the seed
+// kernel) on one stream, then the output:
+//   sel != null: the first k of every served query's f over the m positions of pos_ids ([m] on the device: sel's ids) by (f
+//     descending, position ascending) -> out_idx / out_score + i * stride, out_len[i] (the selection runs on sel's stream);
+//   else pick_ids != null (host, [m]): f at those ids -> out_rows + i * m;
+//   else the whole f -> out_rows + i * n.
+// counts[0] += chunks, [1] += step launches, [2] += seeds uploaded.  The buffers live in sp->diffuse_ws (under sp->fmu).
+struct DiffuseCall {
+    int64_t b = 0;
+    const int64_t* offs = nullptr;
+    const int64_t* ids = nullptr;
+    const double* vals = nullptr;
+    const int32_t* served = nullptr;
+    double alpha = 0.0;
+    int64_t steps = 0;
+    SubsetWork* sel = nullptr;
+    const int32_t* pos_ids = nullptr;
+    int64_t m = 0, k = 0, stride = 0;
+    int64_t* out_idx = nullptr;
+    double* out_score = nullptr;
+    int64_t* out_len = nullptr;
+    const int32_t* pick_ids = nullptr;
+    double* out_rows = nullptr;
+};
+as_status diffuse_run(const as_space* sp, const as_graph* gr, const DiffuseCall& c, int64_t* counts);
+void diffuse_work_free(DiffuseWork* w);
+double diffuse_kernel_us(const DiffuseWork* w);
+void set_diffuse_timing(int v);       // as_set_tuning("diffuse_timing", 0 | 1)
+void set_diffuse_mib(int v);          // as_set_tuning("diffuse_mib", v): the byte budget of the two f buffers; 0: the default (1024 MiB)
+void set_diffuse_cols(int v);         // as_set_tuning("diffuse_cols", v): columns of a chunk at most (1, 16 or 64); 0: the default (64)
+void set_diffuse_tile_edges(int v);   // as_set_tuning("diffuse_tile_edges", v): edges of an LDS tile of the C = 1 kernel; 0: the default
+void set_diffuse_grid_cap(int v);     // as_set_tuning("diffuse_grid_cap", v): v > 0 clips the step kernels' grids; results never depend on it
 
 }  // namespace as

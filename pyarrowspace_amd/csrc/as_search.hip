@@ -3655,6 +3655,26 @@ int32_t as_set_tuning(const char* key, int32_t value) {
         set_diverse_timing(value);
         return 0;
     }
+    if (key && !strcmp(key, "diffuse_timing")) {
+        set_diffuse_timing(value);
+        return 0;
+    }
+    if (key && !strcmp(key, "diffuse_mib")) {
+        set_diffuse_mib(value);
+        return 0;
+    }
+    if (key && !strcmp(key, "diffuse_cols")) {
+        set_diffuse_cols(value);
+        return 0;
+    }
+    if (key && !strcmp(key, "diffuse_tile_edges")) {
+        set_diffuse_tile_edges(value);
+        return 0;
+    }
+    if (key && !strcmp(key, "diffuse_grid_cap")) {
+        set_diffuse_grid_cap(value);
+        return 0;
+    }
     if (key && !strcmp(key, "fused_timing")) {
         set_fused_timing(value);
         return 0;
