@@ -769,6 +769,42 @@ as_status as_diffuse_counters(const as_space* sp, int64_t* out, int32_t n);
 /* measurement: the device microseconds of the steps (step and seed kernels), summed over the chunks of the last diffusion call on
  * this space that ran under as_set_tuning("diffuse_timing", 1) (HIP events around them; off by default) */
 double as_diffuse_kernel_us(const as_space* sp);
+/* ---- Extension: fixed-point diffusion search.  The four forms above with the fixed point of the
+ * recurrence in place of `steps` steps: f = (1 - alpha) (I - alpha S)^-1 y by conjugate gradients on the device, per query and
+ * independent of every other query, started from 0 and stopped when r.r <= fl(fl(tol tol) b.b), after max_iters iterations, or
+ * when p.(I - alpha S)p is not > 0 (a breakdown; x is kept).  The seeds, the pool, S, the subset rule, the zero-lambda rule and the
+ * answer shapes are those of the forms above; every product, sum, difference and quotient is rounded once and the one reduction
+ * (64-row segments in row order, then a halving tree) has a fixed order, so the answer, the iteration count and the residual have
+ * the bits of the numpy reference whatever the column chunk, the tile or the grid.  Per query (each pointer may be NULL; [b], or one
+ * entry of the single form): out_iters the iterations run, out_residual sqrt(r.r / b.b) at the stop (0 for y = 0; NaN for a query
+ * that was not served), out_state 1 converged / 0 stopped at max_iters (or not served) / 2 breakdown.  A query that does not
+ * converge is served with the x it has; that is no error.  Refused before anything is launched: alpha outside [0, 1), tol not
+ * finite or <= 0, max_iters outside [1, 1024] (AS_EINVAL), and what the forms above refuse.  The four vectors x, r, p, q of n x C
+ * doubles stay within "diffuse_solve_mib" (default 2048 MiB: the column widths of "diffuse_mib"); "diffuse_cols",
+ * "diffuse_tile_edges", "diffuse_grid_cap" and "diffuse_timing" hold as above. */
+as_status as_search_diffuse_solve(const as_space* sp, const as_graph* gr, const double* query, int64_t d, double tau, double alpha, double tol,
+                                  int64_t max_iters, const as_subset* sub, int64_t* out_idx, double* out_score, int64_t* out_len,
+                                  double* out_lambda_q, int32_t* out_iters, double* out_residual, int32_t* out_state);
+as_status as_search_diffuse_solve_batch(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau,
+                                        double alpha, double tol, int64_t max_iters, const as_subset* sub, int64_t* out_idx,
+                                        double* out_score, int64_t* out_len, double* out_lambda_q, int32_t* out_status, int32_t* out_iters,
+                                        double* out_residual, int32_t* out_state);
+as_status as_score_diffuse_solve_batch(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau,
+                                       double alpha, double tol, int64_t max_iters, const int64_t* ids_host, int64_t m, double* out_scores,
+                                       double* out_lambda_q, int32_t* out_status, int32_t* out_iters, double* out_residual,
+                                       int32_t* out_state);
+as_status as_diffuse_solve_seeds(const as_space* sp, const as_graph* gr, const int64_t* ids_host, const double* values_host,
+                                 const int64_t* offsets_host, int64_t b, double alpha, double tol, int64_t max_iters, double* out_f,
+                                 int32_t* out_iters, double* out_residual, int32_t* out_state);
+/* out[0] calls of the four entries above that passed their checks, [1] route searches run, [2] column chunks, [3] iterations
+ * launched (per chunk: the largest iteration count of its columns), [4] host waits of the iteration loops (one at the start of a
+ * chunk, one per iteration), [5] seeds uploaded */
+as_status as_diffuse_solve_counters(const as_space* sp, int64_t* out, int32_t n);
+/* measurement, of the last solve on this space that ran under as_set_tuning("diffuse_timing", 1), summed over its chunks (HIP
+ * events): part 0 the device microseconds from the first to the last launch of the iterations (the host's waits between them
+ * included); parts 1 .. 5 the five launches of ONE sampled iteration per chunk (its second, or its only one): the apply kernel,
+ * the reduce of p.q, the update kernel, the reduce of r.r, the direction kernel (with the copy of the scalars ahead of it) */
+double as_diffuse_solve_kernel_us(const as_space* sp, int32_t part);
 /* ---- Extension: fused multi-query search.  ONE answer to j >= 1 query vectors, row-major [j][d] in HOST memory,
  * with finite weights w (weights == NULL: 1/j each; negative weights are legal).  s_v(i): the S11 score of item i for vector v
  * with the bits as_score_items_batch writes at [v][i] (lambda_q of every vector from ONE as_search_batch over the j vectors, the

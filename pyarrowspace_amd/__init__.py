@@ -1452,6 +1452,132 @@ class ArrowSpace:
         batched), the column chunks, the step launches and the seeds uploaded."""
         return _counters(_L.as_diffuse_counters, self._h, ("calls", "route searches", "column chunks", "step launches", "seeds uploaded"))
 
+    @staticmethod
+    def _diffuse_solve_params(alpha, tol, max_iters) -> tuple[float, float, int]:
+        if isinstance(max_iters, bool) or not isinstance(max_iters, (int, np.integer)):
+            raise ValueError(f"max_iters must be an integer in [1, 1024], got {max_iters!r}")
+        if not 1 <= max_iters <= 1024:
+            raise ValueError(f"max_iters must lie in [1, 1024], got {max_iters}")
+        a, t = float(alpha), float(tol)
+        if not 0.0 <= a < 1.0:   # (NaN fails both comparisons)
+            raise ValueError(f"alpha must lie in [0, 1), got {alpha}")
+        if not (np.isfinite(t) and t > 0.0):
+            raise ValueError(f"tol must be finite and > 0, got {tol}")
+        return a, t, int(max_iters)
+
+    @staticmethod
+    def _solve_info_buffers(b: int):
+        return np.zeros(b, dtype=np.int32), np.full(b, np.nan, dtype=np.float64), np.zeros(b, dtype=np.int32)
+
+    @staticmethod
+    def _solve_info(it, res, stt, single: bool) -> dict:
+        """The solve's report: per query the iterations run, sqrt(r.r / b.b) at the stop and whether it converged."""
+        if single:
+            return {"iterations": int(it[0]), "residual": float(res[0]), "converged": bool(stt[0] == 1)}
+        return {"iterations": it.astype(np.int64), "residual": res, "converged": stt == 1}
+
+    def search_diffuse_solve(self, item, gl: GraphLaplacian, tau: float, alpha: float, tol: float = 1e-8, max_iters: int = 100, subset=None,
+                             with_info: bool = False):
+        """Extension: fixed-point diffusion search -> list[(index, f)] as `search_diffuse` returns it, with the fixed point of
+        its recurrence, f = (1 - alpha) (I - alpha S)^-1 y (the manifold-ranking answer), in place of `steps` steps: conjugate
+        gradients on the device from x = 0, stopped when |r| <= tol |b| (b = (1 - alpha) y), after `max_iters` iterations, or
+        on a breakdown.  About sqrt((1 + alpha) / (1 - alpha)) ln(1 / tol) iterations, each one pass over the graph's CSR and
+        streaming passes over four vectors; the arithmetic and the order of every sum are fixed, so f has the bits of the
+        numpy reference.  with_info: -> (list, info), info = {"iterations", "residual", "converged"}.  A query that does not
+        converge is served with the iterate it has and converged = False; it does not raise.  0 <= alpha < 1, tol finite and
+        > 0, 1 <= max_iters <= 1024 (an integer), else ValueError; a feature-mode or row-sharded index raises ValueError."""
+        _need_gl(gl)
+        q = self._query(item)
+        a, t, mi = self._diffuse_solve_params(alpha, tol, max_iters)
+        sub = self._as_subset(subset, optional=True)
+        n = max(self._hits_bound(gl, sub), 1)
+        idx = np.empty(n, dtype=np.int64)
+        sc = np.empty(n, dtype=np.float64)
+        ln, lq = C.c_int64(0), C.c_double(0.0)
+        it, res, stt = self._solve_info_buffers(1)
+        st = _L.as_search_diffuse_solve(self._h, gl._h, q.ctypes.data, q.shape[0], float(tau), a, t, mi, _handle(sub), idx.ctypes.data,
+                                        sc.ctypes.data, C.byref(ln), C.byref(lq), it.ctypes.data, res.ctypes.data, stt.ctypes.data)
+        _check(st)
+        out = list(zip(idx[:ln.value].tolist(), sc[:ln.value].tolist()))
+        return (out, self._solve_info(it, res, stt, True)) if with_info else out
+
+    def search_batch_diffuse_solve(self, items, gl: GraphLaplacian, tau: float, alpha: float, tol: float = 1e-8, max_iters: int = 100,
+                                   subset=None, with_info: bool = False):
+        """Extension: batched fixed-point diffusion search, B queries [B, D] -> list of B lists; list i is
+        `search_diffuse_solve` over the pool `search_batch` (with a subset: `search_batch_subset`) gives query i.  Every query is
+        solved on its own: its f, iteration count and residual do not depend on the others; a query that has stopped is
+        frozen while the rest of its chunk of 16 or 64 goes on.  A query whose lambda_q is 0 gets an empty list (0
+        iterations, residual NaN, not converged).  with_info: -> (lists, info) with one entry per query."""
+        _need_gl(gl)
+        Q = _queries_2d(items)
+        a, t, mi = self._diffuse_solve_params(alpha, tol, max_iters)
+        sub = self._as_subset(subset, optional=True)
+        b = Q.shape[0]
+        kk = self._hits_bound(gl, sub)
+        (idx, sc, ln), stt = _hit_buffers(b, kk), _statuses(b)
+        it, res, sst = self._solve_info_buffers(b)
+        vp = C.c_void_p
+        st = _L.as_search_diffuse_solve_batch(self._h, gl._h, Q.ctypes.data_as(vp), b, Q.shape[1], float(tau), a, t, mi, _handle(sub),
+                                              idx.ctypes.data_as(vp), sc.ctypes.data_as(vp), ln.ctypes.data_as(vp), None, stt.ctypes.data_as(vp),
+                                              it.ctypes.data_as(vp), res.ctypes.data_as(vp), sst.ctypes.data_as(vp))
+        _check(st)
+        out = _hit_lists(idx, sc, ln, b, kk)
+        return (out, self._solve_info(it, res, sst, False)) if with_info else out
+
+    def score_diffuse_solve(self, item, gl: GraphLaplacian, tau: float, alpha: float, ids, tol: float = 1e-8, max_iters: int = 100,
+                            with_info: bool = False):
+        """Extension: f of `search_diffuse_solve` (no subset) at the listed ids -> ndarray[float64] of shape (len(ids),), the
+        caller's order, duplicates kept.  A query whose lambda_q is 0 panics as `search` does."""
+        q = self._query(item)
+        out, info = self._score_diffuse_solve(q.reshape(1, -1), gl, tau, alpha, ids, tol, max_iters, True)
+        return (out[0], info) if with_info else out[0]
+
+    def score_diffuse_solve_batch(self, items, gl: GraphLaplacian, tau: float, alpha: float, ids, tol: float = 1e-8, max_iters: int = 100,
+                                  with_info: bool = False):
+        """Extension: f of `search_batch_diffuse_solve` (no subset) at the listed ids -> ndarray[float64] of shape
+        (B, len(ids)); a query whose lambda_q is 0 gets a row of NaN, the others are served."""
+        out, info = self._score_diffuse_solve(_queries_2d(items), gl, tau, alpha, ids, tol, max_iters, False)
+        return (out, info) if with_info else out
+
+    def _score_diffuse_solve(self, Q, gl, tau, alpha, ids, tol, max_iters, single):
+        _need_gl(gl)
+        a, t, mi = self._diffuse_solve_params(alpha, tol, max_iters)
+        ids = _item_ids(ids, self.nitems, "ids")
+        b, m = Q.shape[0], ids.shape[0]
+        out = np.empty((b, m), dtype=np.float64)
+        stt = _statuses(b)
+        it, res, sst = self._solve_info_buffers(b)
+        vp = C.c_void_p
+        st = _L.as_score_diffuse_solve_batch(self._h, gl._h, Q.ctypes.data_as(vp), b, Q.shape[1], float(tau), a, t, mi, ids.ctypes.data_as(vp),
+                                             m, out.ctypes.data_as(vp), None, stt.ctypes.data_as(vp), it.ctypes.data_as(vp),
+                                             res.ctypes.data_as(vp), sst.ctypes.data_as(vp))
+        _check(st, stt if single else None, b)
+        return out, self._solve_info(it, res, sst, single)
+
+    def diffuse_solve(self, gl: GraphLaplacian, seeds, alpha: float, tol: float = 1e-8, max_iters: int = 100):
+        """Extension: the raw form of the fixed-point solve -> (f, info): f ndarray[float64] of shape (B, nitems), row b the
+        solve of `search_diffuse_solve` from the seeds of `seeds[b]` (pairs (ids, values) as `diffuse` takes them), info =
+        {"iterations", "residual", "converged"} with one entry per row.  No search, no selection; the whole B x nitems block
+        crosses to the host."""
+        _need_gl(gl)
+        a, t, mi = self._diffuse_solve_params(alpha, tol, max_iters)
+        ids, vals, offs = self._diffuse_seeds(seeds, self.nitems)
+        b = offs.shape[0] - 1
+        out = np.empty((b, self.nitems), dtype=np.float64)
+        it, res, sst = self._solve_info_buffers(b)
+        vp = C.c_void_p
+        st = _L.as_diffuse_solve_seeds(self._h, gl._h, ids.ctypes.data_as(vp), vals.ctypes.data_as(vp), offs.ctypes.data_as(vp), b, a, t, mi,
+                                       out.ctypes.data_as(vp), it.ctypes.data_as(vp), res.ctypes.data_as(vp), sst.ctypes.data_as(vp))
+        _check(st)
+        return out, self._solve_info(it, res, sst, False)
+
+    def diffuse_solve_counters(self) -> dict:
+        """Extension: fixed-point diffusion calls on this space that passed their checks, the route searches they ran, the
+        column chunks, the iterations launched (per chunk the largest count of its columns), the host's waits and the seeds
+        uploaded."""
+        return _counters(_L.as_diffuse_solve_counters, self._h,
+                         ("calls", "route searches", "column chunks", "iterations launched", "host waits", "seeds uploaded"))
+
     def _lists_args(self, items, gl, lists):
         _need_gl(gl)
         Q = _queries_2d(items)

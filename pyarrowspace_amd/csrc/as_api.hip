@@ -2750,14 +2750,61 @@ double as_diverse_kernel_us(const as_space* sp) {
 // ---------------------------------------------------------------- graph-diffusion search (extension; as_diffuse.hip)
 static as_status lists_checks(const char* who, const as_space* sp, const int64_t* ids_host, const int64_t* offs, int64_t b);   // (below)
 namespace {
+// what a form runs behind its pool: `steps` steps of the recurrence (S19) or, solve set, the conjugate-gradient solve of its fixed
+// point (S20; section 5.23) to `tol` within `max_iters` iterations, with the per-query outputs of the solve (each may be null)
+struct DiffuseSpec {
+    double alpha = 0.0;
+    int64_t steps = 0;
+    bool solve = false;
+    double tol = 0.0;
+    int64_t max_iters = 0;
+    int32_t* out_iters = nullptr;
+    double* out_residual = nullptr;
+    int32_t* out_state = nullptr;
+    static DiffuseSpec recurrence(double alpha, int64_t steps) {
+        DiffuseSpec ds;
+        ds.alpha = alpha; ds.steps = steps;
+        return ds;
+    }
+    static DiffuseSpec fixed_point(double alpha, double tol, int64_t max_iters, int32_t* out_iters, double* out_residual, int32_t* out_state) {
+        DiffuseSpec ds;
+        ds.alpha = alpha; ds.solve = true; ds.tol = tol; ds.max_iters = max_iters;
+        ds.out_iters = out_iters; ds.out_residual = out_residual; ds.out_state = out_state;
+        return ds;
+    }
+    std::atomic<int64_t>* count(const as_space* sp) const { return solve ? sp->diffuse_solve_count : sp->diffuse_count; }
+    void fill(DiffuseCall& dc) const {
+        dc.alpha = alpha;
+        dc.steps = steps;
+        if (solve) {
+            dc.tol = tol; dc.max_iters = max_iters; dc.out_iters = out_iters; dc.out_residual = out_residual; dc.out_state = out_state;
+        }
+    }
+    // a query the solve does not reach (zero lambda_q, an empty answer): 0 iterations, residual NaN, not converged
+    void clear_info(int64_t b) const {
+        for (int64_t i = 0; solve && i < b; ++i) {
+            if (out_iters) out_iters[i] = 0;
+            if (out_residual) out_residual[i] = std::numeric_limits<double>::quiet_NaN();
+            if (out_state) out_state[i] = 0;
+        }
+    }
+};
 // what every form refuses before anything is launched, the route's search included
-as_status diffuse_param_checks(const char* who, const as_space* sp, const as_graph* gr, double alpha, int64_t steps) {
-    if (!(alpha >= 0.0 && alpha < 1.0)) {
-        set_err("%s: alpha must lie in [0, 1), got %g", who, alpha);
+as_status diffuse_param_checks(const char* who, const as_space* sp, const as_graph* gr, const DiffuseSpec& ds) {
+    if (!(ds.alpha >= 0.0 && ds.alpha < 1.0)) {
+        set_err("%s: alpha must lie in [0, 1), got %g", who, ds.alpha);
         return AS_EINVAL;
     }
-    if (steps < 0 || steps > 64) {
-        set_err("%s: steps must lie in [0, 64], got %lld", who, (long long)steps);
+    if (!ds.solve && (ds.steps < 0 || ds.steps > 64)) {
+        set_err("%s: steps must lie in [0, 64], got %lld", who, (long long)ds.steps);
+        return AS_EINVAL;
+    }
+    if (ds.solve && !(std::isfinite(ds.tol) && ds.tol > 0.0)) {
+        set_err("%s: tol must be finite and > 0, got %g", who, ds.tol);
+        return AS_EINVAL;
+    }
+    if (ds.solve && (ds.max_iters < 1 || ds.max_iters > 1024)) {
+        set_err("%s: max_iters must lie in [1, 1024], got %lld", who, (long long)ds.max_iters);
         return AS_EINVAL;
     }
     if (gr->lambda_mode == AS_LAMBDA_FEATURE) {
@@ -2774,9 +2821,9 @@ as_status diffuse_graph_checks(const char* who, const as_space* sp, const as_gra
     }
     return AS_OK;
 }
-as_status diffuse_checks(const char* who, const as_space* sp, const as_graph* gr, int64_t d, double tau, double alpha, int64_t steps,
+as_status diffuse_checks(const char* who, const as_space* sp, const as_graph* gr, int64_t d, double tau, const DiffuseSpec& ds,
                          const as_subset* sub) {
-    AS_TRY(diffuse_param_checks(who, sp, gr, alpha, steps));
+    AS_TRY(diffuse_param_checks(who, sp, gr, ds));
     AS_TRY(own_subset(who, sp, sub));
     AS_TRY(subset_checks(who, sp, gr, d, &tau, 1));
     return diffuse_graph_checks(who, sp, gr);
@@ -2802,32 +2849,36 @@ as_status diffuse_pool_seeds(const char* who, const int64_t* pidx, const double*
 }
 // the recurrence and its output, under sp->fmu
 as_status diffuse_locked(const char* who, const as_space* sp, const as_graph* gr, const DiffuseCall& dc) {
-    int64_t counts[3] = {0, 0, 0};
+    int64_t counts[4] = {0, 0, 0, 0};   // (three of the recurrence, four of the solve)
     std::lock_guard<std::mutex> lk(sp->fmu);
     if (hipSetDevice(sp->device) != hipSuccess) {
         set_err("%s: hipSetDevice failed", who);
         return AS_EHIP;
     }
     const as_status s = diffuse_run(sp, gr, dc, counts);
-    for (int i = 0; i < 3; ++i) sp->diffuse_count[2 + i].fetch_add(counts[i], std::memory_order_relaxed);
+    std::atomic<int64_t>* cnt = dc.max_iters > 0 ? sp->diffuse_solve_count : sp->diffuse_count;
+    for (int i = 0; i < (dc.max_iters > 0 ? 4 : 3); ++i) cnt[2 + i].fetch_add(counts[i], std::memory_order_relaxed);
     return s;
 }
 }  // namespace
 
-as_status as_search_diffuse(const as_space* sp, const as_graph* gr, const double* query, int64_t d, double tau, double alpha, int64_t steps,
-                            const as_subset* sub, int64_t* out_idx, double* out_score, int64_t* out_len, double* out_lambda_q) {
+namespace {
+as_status search_diffuse_impl(const char* who, const as_space* sp, const as_graph* gr, const double* query, int64_t d, double tau,
+                              const DiffuseSpec& ds, const as_subset* sub, int64_t* out_idx, double* out_score, int64_t* out_len,
+                              double* out_lambda_q) {
     if (!sp || !gr || !query || !out_len || ((!sub || sub->m > 0) && (!out_idx || !out_score))) {
-        set_err("as_search_diffuse: null argument");
+        set_err("%s: null argument", who);
         return AS_EINVAL;
     }
     *out_len = 0;
-    AS_TRY(diffuse_checks("as_search_diffuse", sp, gr, d, tau, alpha, steps, sub));
-    sp->diffuse_count[0].fetch_add(1, std::memory_order_relaxed);
+    AS_TRY(diffuse_checks(who, sp, gr, d, tau, ds, sub));
+    ds.count(sp)[0].fetch_add(1, std::memory_order_relaxed);
+    ds.clear_info(1);
     // the pool: ONE ordinary search of the route, its hits in its order
     int64_t pidx[SUBSET_TOPK], plen = 0;
     double psc[SUBSET_TOPK];
     double lq = 0.0;
-    sp->diffuse_count[1].fetch_add(1, std::memory_order_relaxed);
+    ds.count(sp)[1].fetch_add(1, std::memory_order_relaxed);
     const as_status s = sub ? as_search_subset(sp, gr, query, d, tau, sub, pidx, psc, &plen, &lq)
                             : search_pooled(sp, gr, query, d, tau, pidx, psc, &plen, &lq);
     if (out_lambda_q) *out_lambda_q = lq;
@@ -2835,20 +2886,19 @@ as_status as_search_diffuse(const as_space* sp, const as_graph* gr, const double
     if (sub && sub->m == 0) return AS_OK;
     std::vector<int64_t> offs, ids;
     std::vector<double> vals;
-    AS_TRY(diffuse_pool_seeds("as_search_diffuse", pidx, psc, &plen, SUBSET_TOPK, 1, offs, ids, vals));
-    const Candidates c("as_search_diffuse", sp, sub);
+    AS_TRY(diffuse_pool_seeds(who, pidx, psc, &plen, SUBSET_TOPK, 1, offs, ids, vals));
+    const Candidates c(who, sp, sub);
     AS_TRY(c.status);
     DiffuseCall dc;
-    dc.b = 1; dc.offs = offs.data(); dc.ids = ids.data(); dc.vals = vals.data(); dc.alpha = alpha; dc.steps = steps;
+    dc.b = 1; dc.offs = offs.data(); dc.ids = ids.data(); dc.vals = vals.data(); ds.fill(dc);
     dc.sel = c.w; dc.pos_ids = c.w->ids; dc.m = c.m; dc.k = hits_bound(sp, gr, c.m); dc.stride = dc.k;
     dc.out_idx = out_idx; dc.out_score = out_score; dc.out_len = out_len;
-    return c.fail(diffuse_locked("as_search_diffuse", sp, gr, dc));
+    return c.fail(diffuse_locked(who, sp, gr, dc));
 }
 
-namespace {
 // the pools of a batched form (ONE batched search of the route over all b queries), as seeds; served[i] = 0: a zero lambda_q
 as_status diffuse_batch_pools(const char* who, const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau,
-                              const as_subset* sub, double* out_lambda_q, int32_t* out_status, std::vector<int64_t>& offs,
+                              const DiffuseSpec& ds, const as_subset* sub, double* out_lambda_q, int32_t* out_status, std::vector<int64_t>& offs,
                               std::vector<int64_t>& ids, std::vector<double>& vals, std::vector<int32_t>& served) {
     const int64_t kks = std::max<int64_t>(hits_bound(sp, gr, sub ? sub->m : sp->n), 1);
     std::vector<int64_t> pidx, plen;
@@ -2865,7 +2915,7 @@ as_status diffuse_batch_pools(const char* who, const as_space* sp, const as_grap
         set_err("%s: out of host memory for %lld queries", who, (long long)b);
         return AS_ENOMEM;
     }
-    sp->diffuse_count[1].fetch_add(1, std::memory_order_relaxed);
+    ds.count(sp)[1].fetch_add(1, std::memory_order_relaxed);
     AS_TRY(sub ? as_search_subset_batch(sp, gr, queries, b, d, tau, sub, pidx.data(), psc.data(), plen.data(), lq.data(), st.data())
                : as_search_batch(sp, gr, queries, b, d, tau, pidx.data(), psc.data(), plen.data(), lq.data(), st.data()));
     for (int64_t i = 0; i < b; ++i) {
@@ -2878,73 +2928,73 @@ as_status diffuse_batch_pools(const char* who, const as_space* sp, const as_grap
     }
     return diffuse_pool_seeds(who, pidx.data(), psc.data(), plen.data(), kks, b, offs, ids, vals);
 }
-}  // namespace
 
-as_status as_search_diffuse_batch(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau, double alpha,
-                                  int64_t steps, const as_subset* sub, int64_t* out_idx, double* out_score, int64_t* out_len,
-                                  double* out_lambda_q, int32_t* out_status) {
+as_status search_diffuse_batch_impl(const char* who, const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d,
+                                    double tau, const DiffuseSpec& ds, const as_subset* sub, int64_t* out_idx, double* out_score,
+                                    int64_t* out_len, double* out_lambda_q, int32_t* out_status) {
     if (!sp || !gr || b < 0 || (b > 0 && (!queries || !out_len))) {
-        set_err("as_search_diffuse_batch: null argument");
+        set_err("%s: null argument", who);
         return AS_EINVAL;
     }
     const int64_t kk = hits_bound(sp, gr, sub ? sub->m : sp->n);
     if (b > 0 && kk > 0 && (!out_idx || !out_score)) {
-        set_err("as_search_diffuse_batch: null argument");
+        set_err("%s: null argument", who);
         return AS_EINVAL;
     }
     for (int64_t i = 0; i < b; ++i) out_len[i] = 0;
-    AS_TRY(diffuse_checks("as_search_diffuse_batch", sp, gr, d, tau, alpha, steps, sub));
-    sp->diffuse_count[0].fetch_add(1, std::memory_order_relaxed);
+    AS_TRY(diffuse_checks(who, sp, gr, d, tau, ds, sub));
+    ds.count(sp)[0].fetch_add(1, std::memory_order_relaxed);
+    ds.clear_info(b);
     if (b == 0) return AS_OK;
     std::vector<int64_t> offs, ids;
     std::vector<double> vals;
     std::vector<int32_t> served;
-    AS_TRY(diffuse_batch_pools("as_search_diffuse_batch", sp, gr, queries, b, d, tau, sub, out_lambda_q, out_status, offs, ids, vals, served));
+    AS_TRY(diffuse_batch_pools(who, sp, gr, queries, b, d, tau, ds, sub, out_lambda_q, out_status, offs, ids, vals, served));
     if (kk == 0) return AS_OK;
-    const Candidates c("as_search_diffuse_batch", sp, sub);
+    const Candidates c(who, sp, sub);
     AS_TRY(c.status);
     DiffuseCall dc;
-    dc.b = b; dc.offs = offs.data(); dc.ids = ids.data(); dc.vals = vals.data(); dc.served = served.data(); dc.alpha = alpha; dc.steps = steps;
+    dc.b = b; dc.offs = offs.data(); dc.ids = ids.data(); dc.vals = vals.data(); dc.served = served.data(); ds.fill(dc);
     dc.sel = c.w; dc.pos_ids = c.w->ids; dc.m = c.m; dc.k = kk; dc.stride = kk;
     dc.out_idx = out_idx; dc.out_score = out_score; dc.out_len = out_len;
-    return c.fail(diffuse_locked("as_search_diffuse_batch", sp, gr, dc));
+    return c.fail(diffuse_locked(who, sp, gr, dc));
 }
 
-as_status as_score_diffuse_batch(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau, double alpha,
-                                 int64_t steps, const int64_t* ids_host, int64_t m, double* out_scores, double* out_lambda_q,
-                                 int32_t* out_status) {
+as_status score_diffuse_batch_impl(const char* who, const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d,
+                                   double tau, const DiffuseSpec& ds, const int64_t* ids_host, int64_t m, double* out_scores,
+                                   double* out_lambda_q, int32_t* out_status) {
     if (!sp || !gr || b < 0 || m < 0 || (b > 0 && !queries) || (m > 0 && !ids_host) || (b > 0 && m > 0 && !out_scores)) {
-        set_err("as_score_diffuse_batch: null argument");
+        set_err("%s: null argument", who);
         return AS_EINVAL;
     }
-    AS_TRY(ids_in_range("as_score_diffuse_batch", sp, ids_host, m));
-    AS_TRY(diffuse_checks("as_score_diffuse_batch", sp, gr, d, tau, alpha, steps, nullptr));
+    AS_TRY(ids_in_range(who, sp, ids_host, m));
+    AS_TRY(diffuse_checks(who, sp, gr, d, tau, ds, nullptr));
     std::vector<int32_t> ids32;
-    AS_TRY(checked_ids("as_score_diffuse_batch", ids_host, m, ids32));
-    sp->diffuse_count[0].fetch_add(1, std::memory_order_relaxed);
+    AS_TRY(checked_ids(who, ids_host, m, ids32));
+    ds.count(sp)[0].fetch_add(1, std::memory_order_relaxed);
+    ds.clear_info(b);
     if (b == 0) return AS_OK;
     std::vector<int64_t> offs, ids;
     std::vector<double> vals;
     std::vector<int32_t> served;
-    AS_TRY(diffuse_batch_pools("as_score_diffuse_batch", sp, gr, queries, b, d, tau, nullptr, out_lambda_q, out_status, offs, ids, vals, served));
+    AS_TRY(diffuse_batch_pools(who, sp, gr, queries, b, d, tau, ds, nullptr, out_lambda_q, out_status, offs, ids, vals, served));
     if (m == 0) return AS_OK;
     for (int64_t i = 0; i < b; ++i)
         if (!served[(size_t)i])
             for (int64_t j = 0; j < m; ++j) out_scores[i * m + j] = std::numeric_limits<double>::quiet_NaN();
     DiffuseCall dc;
-    dc.b = b; dc.offs = offs.data(); dc.ids = ids.data(); dc.vals = vals.data(); dc.served = served.data(); dc.alpha = alpha; dc.steps = steps;
+    dc.b = b; dc.offs = offs.data(); dc.ids = ids.data(); dc.vals = vals.data(); dc.served = served.data(); ds.fill(dc);
     dc.pick_ids = ids32.data(); dc.m = m; dc.out_rows = out_scores;
-    return diffuse_locked("as_score_diffuse_batch", sp, gr, dc);
+    return diffuse_locked(who, sp, gr, dc);
 }
 
-as_status as_diffuse_seeds(const as_space* sp, const as_graph* gr, const int64_t* ids_host, const double* values_host,
-                           const int64_t* offsets_host, int64_t b, double alpha, int64_t steps, double* out_f) {
-    const char* who = "as_diffuse_seeds";
+as_status diffuse_seeds_impl(const char* who, const as_space* sp, const as_graph* gr, const int64_t* ids_host, const double* values_host,
+                             const int64_t* offsets_host, int64_t b, const DiffuseSpec& ds, double* out_f) {
     if (!sp || !gr || b < 0 || !offsets_host || (b > 0 && !out_f)) {
         set_err("%s: null argument", who);
         return AS_EINVAL;
     }
-    AS_TRY(diffuse_param_checks(who, sp, gr, alpha, steps));
+    AS_TRY(diffuse_param_checks(who, sp, gr, ds));
     if (offsets_host[b] > 0 && (!ids_host || !values_host)) {
         set_err("%s: null argument", who);
         return AS_EINVAL;
@@ -2975,12 +3025,76 @@ as_status as_diffuse_seeds(const as_space* sp, const as_graph* gr, const int64_t
         return AS_EUNSUPPORTED;
     }
     AS_TRY(diffuse_graph_checks(who, sp, gr));
-    sp->diffuse_count[0].fetch_add(1, std::memory_order_relaxed);
+    ds.count(sp)[0].fetch_add(1, std::memory_order_relaxed);
+    ds.clear_info(b);
     if (b == 0) return AS_OK;
     DiffuseCall dc;
-    dc.b = b; dc.offs = offsets_host; dc.ids = ids_host; dc.vals = values_host; dc.alpha = alpha; dc.steps = steps;
+    dc.b = b; dc.offs = offsets_host; dc.ids = ids_host; dc.vals = values_host; ds.fill(dc);
     dc.out_rows = out_f;
     return diffuse_locked(who, sp, gr, dc);
+}
+}  // namespace
+
+as_status as_search_diffuse(const as_space* sp, const as_graph* gr, const double* query, int64_t d, double tau, double alpha, int64_t steps,
+                            const as_subset* sub, int64_t* out_idx, double* out_score, int64_t* out_len, double* out_lambda_q) {
+    return search_diffuse_impl("as_search_diffuse", sp, gr, query, d, tau, DiffuseSpec::recurrence(alpha, steps), sub, out_idx, out_score, out_len,
+                               out_lambda_q);
+}
+as_status as_search_diffuse_batch(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau, double alpha,
+                                  int64_t steps, const as_subset* sub, int64_t* out_idx, double* out_score, int64_t* out_len,
+                                  double* out_lambda_q, int32_t* out_status) {
+    return search_diffuse_batch_impl("as_search_diffuse_batch", sp, gr, queries, b, d, tau, DiffuseSpec::recurrence(alpha, steps), sub, out_idx,
+                                     out_score, out_len, out_lambda_q, out_status);
+}
+as_status as_score_diffuse_batch(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau, double alpha,
+                                 int64_t steps, const int64_t* ids_host, int64_t m, double* out_scores, double* out_lambda_q,
+                                 int32_t* out_status) {
+    return score_diffuse_batch_impl("as_score_diffuse_batch", sp, gr, queries, b, d, tau, DiffuseSpec::recurrence(alpha, steps), ids_host, m,
+                                    out_scores, out_lambda_q, out_status);
+}
+as_status as_diffuse_seeds(const as_space* sp, const as_graph* gr, const int64_t* ids_host, const double* values_host,
+                           const int64_t* offsets_host, int64_t b, double alpha, int64_t steps, double* out_f) {
+    return diffuse_seeds_impl("as_diffuse_seeds", sp, gr, ids_host, values_host, offsets_host, b, DiffuseSpec::recurrence(alpha, steps), out_f);
+}
+
+// ---- fixed-point diffusion search (extension; as_diffuse_solve.hip): the forms above with the
+// conjugate-gradient solve of the fixed point in place of `steps` steps
+as_status as_search_diffuse_solve(const as_space* sp, const as_graph* gr, const double* query, int64_t d, double tau, double alpha, double tol,
+                                  int64_t max_iters, const as_subset* sub, int64_t* out_idx, double* out_score, int64_t* out_len,
+                                  double* out_lambda_q, int32_t* out_iters, double* out_residual, int32_t* out_state) {
+    return search_diffuse_impl("as_search_diffuse_solve", sp, gr, query, d, tau,
+                               DiffuseSpec::fixed_point(alpha, tol, max_iters, out_iters, out_residual, out_state), sub, out_idx, out_score, out_len,
+                               out_lambda_q);
+}
+as_status as_search_diffuse_solve_batch(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau,
+                                        double alpha, double tol, int64_t max_iters, const as_subset* sub, int64_t* out_idx,
+                                        double* out_score, int64_t* out_len, double* out_lambda_q, int32_t* out_status, int32_t* out_iters,
+                                        double* out_residual, int32_t* out_state) {
+    return search_diffuse_batch_impl("as_search_diffuse_solve_batch", sp, gr, queries, b, d, tau,
+                                     DiffuseSpec::fixed_point(alpha, tol, max_iters, out_iters, out_residual, out_state), sub, out_idx, out_score, out_len,
+                                     out_lambda_q, out_status);
+}
+as_status as_score_diffuse_solve_batch(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau,
+                                       double alpha, double tol, int64_t max_iters, const int64_t* ids_host, int64_t m, double* out_scores,
+                                       double* out_lambda_q, int32_t* out_status, int32_t* out_iters, double* out_residual,
+                                       int32_t* out_state) {
+    return score_diffuse_batch_impl("as_score_diffuse_solve_batch", sp, gr, queries, b, d, tau,
+                                    DiffuseSpec::fixed_point(alpha, tol, max_iters, out_iters, out_residual, out_state), ids_host, m, out_scores,
+                                    out_lambda_q, out_status);
+}
+as_status as_diffuse_solve_seeds(const as_space* sp, const as_graph* gr, const int64_t* ids_host, const double* values_host,
+                                 const int64_t* offsets_host, int64_t b, double alpha, double tol, int64_t max_iters, double* out_f,
+                                 int32_t* out_iters, double* out_residual, int32_t* out_state) {
+    return diffuse_seeds_impl("as_diffuse_solve_seeds", sp, gr, ids_host, values_host, offsets_host, b,
+                              DiffuseSpec::fixed_point(alpha, tol, max_iters, out_iters, out_residual, out_state), out_f);
+}
+as_status as_diffuse_solve_counters(const as_space* sp, int64_t* out, int32_t n) {
+    return counters_out("as_diffuse_solve_counters", sp, out, n, sp ? sp->diffuse_solve_count : nullptr, 6);
+}
+double as_diffuse_solve_kernel_us(const as_space* sp, int32_t part) {
+    if (!sp) return 0.0;
+    std::lock_guard<std::mutex> lk(sp->fmu);
+    return diffuse_solve_kernel_us(sp->diffuse_ws, part);
 }
 
 as_status as_diffuse_counters(const as_space* sp, int64_t* out, int32_t n) {

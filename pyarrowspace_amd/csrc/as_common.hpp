@@ -230,6 +230,9 @@ struct as_space {
     mutable struct as::DiffuseWork* diffuse_ws = nullptr;
     mutable std::mutex fmu;
     mutable std::atomic<int64_t> diffuse_count[5] = {};
+    // the solve forms share diffuse_ws and fmu.  as_diffuse_solve_counters: [0] calls that passed their
+    // checks, [1] route searches run, [2] column chunks, [3] iterations launched, [4] host waits, [5] seeds uploaded
+    mutable std::atomic<int64_t> diffuse_solve_count[6] = {};
 };
 
 struct as_graph {
@@ -1107,6 +1110,14 @@ struct DiffuseCall {
     int64_t* out_len = nullptr;
     const int32_t* pick_ids = nullptr;
     double* out_rows = nullptr;
+    // max_iters > 0: the S20 solve of the fixed point (as_diffuse_solve.hip) in place of `steps` steps; per query (each may be
+    // null) the iterations run, sqrt(rho_last / bb) and 1 converged / 0 stopped at max_iters / 2 breakdown.  counts then holds
+    // four: [0] += chunks, [1] += iterations launched, [2] += host waits, [3] += seeds uploaded
+    double tol = 0.0;
+    int64_t max_iters = 0;
+    int32_t* out_iters = nullptr;
+    double* out_residual = nullptr;
+    int32_t* out_state = nullptr;
 };
 as_status diffuse_run(const as_space* sp, const as_graph* gr, const DiffuseCall& c, int64_t* counts);
 void diffuse_work_free(DiffuseWork* w);
@@ -1116,5 +1127,8 @@ void set_diffuse_mib(int v);          // as_set_tuning("diffuse_mib", v): the by
 void set_diffuse_cols(int v);         // as_set_tuning("diffuse_cols", v): columns of a chunk at most (1, 16 or 64); 0: the default (64)
 void set_diffuse_tile_edges(int v);   // as_set_tuning("diffuse_tile_edges", v): edges of an LDS tile of the C = 1 kernel; 0: the default
 void set_diffuse_grid_cap(int v);     // as_set_tuning("diffuse_grid_cap", v): v > 0 clips the step kernels' grids; results never depend on it
+// the S20 solve (as_diffuse_solve.hip) runs through diffuse_run with c.max_iters > 0, on the same work buffers
+double diffuse_solve_kernel_us(const DiffuseWork* w, int part);
+void set_diffuse_solve_mib(int v);    // as_set_tuning("diffuse_solve_mib", v): the byte budget of the solve's four vectors; 0: the default (2048 MiB)
 
 }  // namespace as

@@ -8,25 +8,19 @@
 // the compiler fused) -- and a row's sum runs in CSR order: the result has the bits of the numpy reference, whatever the
 // column chunk, the tile or the grid.
 // Entry points: as_api.hip (as_search_diffuse, as_search_diffuse_batch, as_score_diffuse_batch, as_diffuse_seeds).
+// The call frame, the seed table and the output paths are functions of their own (as_diffuse.hpp): the S20 solve
+// (as_diffuse_solve.hip) runs on the same work buffers and ends in the same outputs.
 #include <algorithm>
 #include <atomic>
 #include <new>
 #include <vector>
 
-#include "as_common.hpp"
+#include "as_diffuse.hpp"
 
 // S19 rounds every product and every sum once: no multiply of this file may be fused with the add behind it
 #pragma clang fp contract(off)
 
 namespace as {
-
-constexpr int DIF_THREADS = 256;          // threads of a block: the rows of a group of the C = 1 kernel
-constexpr int DIF_TILE_DEFAULT = 4096;    // edges of an LDS tile of the C = 1 kernel ("diffuse_tile_edges"): 32 KiB of products
-constexpr int DIF_TILE_MAX = 4096;
-constexpr int DIF_BLOCKS_PER_CU = 8;
-// "diffuse_mib", the budget of the two f buffers: 64 columns at 1M rows (977 MiB) -- measured 1.6x faster per query-step there than
-// 16 columns (section 5.22), although that block no longer fits the Infinity Cache
-constexpr int DIF_MIB_DEFAULT = 1024;
 
 struct DiffuseArgs {
     const int64_t* indptr;    // [n + 1]
@@ -128,24 +122,11 @@ void set_diffuse_cols(int v) { g_diffuse_cols.store(v > 0 ? v : 64, std::memory_
 void set_diffuse_tile_edges(int v) { g_diffuse_tile.store(v > 0 ? std::min(v, DIF_TILE_MAX) : DIF_TILE_DEFAULT, std::memory_order_relaxed); }
 void set_diffuse_grid_cap(int v) { g_diffuse_grid_cap.store(v > 0 ? v : 0, std::memory_order_relaxed); }
 
-static unsigned diffuse_grid(int64_t blocks) {
+unsigned diffuse_grid(int64_t blocks) {
     const int64_t cap = g_diffuse_grid_cap.load(std::memory_order_relaxed);
     blocks = std::max<int64_t>(blocks, 1);
     return (unsigned)(cap > 0 ? std::min(blocks, cap) : blocks);
 }
-
-struct DiffuseWork {
-    int device = 0;
-    int cus = 256;
-    hipStream_t stream = nullptr;
-    dev_buf<double> f[2];       // [n][C] each, ping-pong
-    dev_buf<double> rows;       // [nc][m]: the last step's output, gathered
-    dev_buf<int32_t> ids;       // the listed ids of a score call
-    dev_buf<char> seed_d;       // one upload per chunk: [ns] values, [ns] items, [ns] columns
-    pin_buf<char> seed_h;
-    dev_events<2> ev;
-    double kernel_us = 0.0;     // the steps (step and seed kernels) summed over the chunks of the last timed call
-};
 
 void diffuse_work_free(DiffuseWork* w) {
     if (!w) return;
@@ -156,6 +137,9 @@ void diffuse_work_free(DiffuseWork* w) {
 }
 
 double diffuse_kernel_us(const DiffuseWork* w) { return w ? w->kernel_us : 0.0; }
+int diffuse_cols_cap() { return g_diffuse_cols.load(std::memory_order_relaxed); }
+int diffuse_tile_edges() { return g_diffuse_tile.load(std::memory_order_relaxed); }
+bool diffuse_timing() { return g_diffuse_timing.load(std::memory_order_relaxed) != 0; }
 
 static as_status diffuse_work_create(const as_space* sp, DiffuseWork** out) {
     DiffuseWork* w = new (std::nothrow) DiffuseWork();
@@ -175,9 +159,8 @@ static as_status diffuse_work_create(const as_space* sp, DiffuseWork** out) {
     return AS_OK;
 }
 
-// columns of the next chunk: `rem` served queries are left, n rows, at most `cols_cap` columns, both f buffers within `budget` bytes
-static int diffuse_chunk_cols(int64_t rem, int64_t n, int cols_cap, int64_t budget) {
-    auto fits = [&](int c) { return c <= cols_cap && 2 * (int64_t)sizeof(double) * n * c <= budget; };
+int diffuse_chunk_cols(int64_t rem, int64_t n, int cols_cap, int64_t budget, int bufs) {
+    auto fits = [&](int c) { return c <= cols_cap && bufs * (int64_t)sizeof(double) * n * c <= budget; };
     if (rem > 32 && fits(64)) return 64;
     if (rem > 1 && fits(16)) return 16;
     return 1;
@@ -196,111 +179,140 @@ static void diffuse_step_launch(const DiffuseWork* w, const DiffuseArgs& a, int 
     else hipLaunchKernelGGL(diffuse_step_cols_kernel<64>, dim3(grid), dim3(DIF_THREADS), 0, w->stream, a);
 }
 
-static as_status diffuse_chunks(const as_space* sp, const as_graph* gr, const DiffuseCall& c, int64_t* counts) {
-    const int64_t n = gr->n;
-    std::vector<int64_t> q;   // the served queries, ascending
+as_status diffuse_frame(const as_space* sp, const as_graph* gr, const DiffuseCall& c, DiffuseFrame* fr) {
     try {
         for (int64_t i = 0; i < c.b; ++i)
-            if (!c.served || c.served[i]) q.push_back(i);
+            if (!c.served || c.served[i]) fr->q.push_back(i);
     } catch (const std::bad_alloc&) {
         set_err("diffuse: out of host memory for %lld queries", (long long)c.b);
         return AS_ENOMEM;
     }
-    const bool select = c.sel != nullptr, pick = !select && c.pick_ids != nullptr;
-    const int64_t m = select || pick ? c.m : n;
-    if (q.empty() || n <= 0 || m <= 0) return AS_OK;
+    fr->select = c.sel != nullptr;
+    fr->pick = !fr->select && c.pick_ids != nullptr;
+    fr->m = fr->select || fr->pick ? c.m : gr->n;
+    if (fr->q.empty() || gr->n <= 0 || fr->m <= 0) return AS_OK;
     if (!sp->diffuse_ws) AS_TRY(diffuse_work_create(sp, &sp->diffuse_ws));
     DiffuseWork* w = sp->diffuse_ws;
-    const bool timing = g_diffuse_timing.load(std::memory_order_relaxed) != 0;
-    const int cols_cap = g_diffuse_cols.load(std::memory_order_relaxed);
+    fr->ids_d = fr->select ? c.pos_ids : nullptr;
+    if (fr->pick) {
+        AS_TRY(reserve_or_err(w->ids, fr->m, "diffuse listed ids"));
+        AS_HIP(hipMemcpyAsync(w->ids, c.pick_ids, sizeof(int32_t) * (size_t)fr->m, hipMemcpyHostToDevice, w->stream));
+        fr->ids_d = w->ids;
+    }
+    fr->w = w;
+    return AS_OK;
+}
+
+as_status diffuse_seed_table(const DiffuseFrame& fr, const DiffuseCall& c, int64_t i0, int64_t nc, DiffuseSeeds* s) {
+    DiffuseWork* w = fr.w;
+    const std::vector<int64_t>& q = fr.q;
+    int64_t ns = 0;
+    for (int64_t t = 0; t < nc; ++t) ns += c.offs[q[i0 + t] + 1] - c.offs[q[i0 + t]];
+    const size_t item_off = sizeof(double) * (size_t)ns, col_off = item_off + sizeof(int32_t) * (size_t)ns;
+    const size_t up = col_off + sizeof(int32_t) * (size_t)ns;
+    if (up > std::min(w->seed_d.size(), w->seed_h.size())) {
+        AS_TRY(reserve_or_err(w->seed_d, up + up / 2, "diffuse seed table"));
+        AS_TRY(reserve_or_err(w->seed_h, up + up / 2, "diffuse pinned seed table"));
+    }
+    char* const sh = w->seed_h;
+    char* const sd = w->seed_d;
+    double* hv = (double*)sh;
+    int32_t* hi = (int32_t*)(sh + item_off);
+    int32_t* hc = (int32_t*)(sh + col_off);
+    int64_t z = 0;
+    for (int64_t t = 0; t < nc; ++t)
+        for (int64_t e = c.offs[q[i0 + t]]; e < c.offs[q[i0 + t] + 1]; ++e, ++z) {
+            hv[z] = c.vals[e];
+            hi[z] = (int32_t)c.ids[e];
+            hc[z] = (int32_t)t;
+        }
+    if (ns > 0) AS_HIP(hipMemcpyAsync(sd, sh, up, hipMemcpyHostToDevice, w->stream));
+    s->ns = ns;
+    s->val = (const double*)sd;
+    s->item = (const int32_t*)(sd + item_off);
+    s->col = (const int32_t*)(sd + col_off);
+    s->grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((ns + DIF_THREADS - 1) / DIF_THREADS, 1024));
+    return AS_OK;
+}
+
+void diffuse_seed_launch(const DiffuseWork* w, const DiffuseSeeds& s, double* f, int C, double om, int init) {
+    if (s.ns > 0) hipLaunchKernelGGL(diffuse_seed_kernel, dim3(s.grid), dim3(DIF_THREADS), 0, w->stream, s.item, s.col, s.val, s.ns, f, C, om, init);
+}
+
+as_status diffuse_emit(const DiffuseFrame& fr, const DiffuseCall& c, int64_t i0, int64_t nc, int C, const double* f, bool timing, double* us) {
+    DiffuseWork* w = fr.w;
+    const std::vector<int64_t>& q = fr.q;
+    const int64_t m = fr.m;
+    // the whole f in the [rows][m] layout, unless it has that layout already (one column, every item, in item order)
+    const bool gather = !(C == 1 && !fr.ids_d);
+    const double* res = f;   // [nc][m] after the gather
+    if (gather) {
+        AS_TRY(reserve_or_err(w->rows, nc * m, "diffuse gathered rows"));
+        const unsigned ggrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((m + DIF_THREADS - 1) / DIF_THREADS, (int64_t)w->cus * 8));
+        hipLaunchKernelGGL(diffuse_gather_kernel, dim3(ggrid), dim3(DIF_THREADS), 0, w->stream, f, C, (int)nc, fr.ids_d, m, (double*)w->rows);
+        AS_HIP(hipGetLastError());
+        res = w->rows;
+    }
+    if (!fr.select) {
+        // (queries that follow one another in the call: one copy)
+        bool run = true;
+        for (int64_t t = 1; t < nc; ++t) run = run && q[i0 + t] == q[i0] + t;
+        if (run) AS_HIP(hipMemcpyAsync(c.out_rows + q[i0] * m, res, sizeof(double) * (size_t)(nc * m), hipMemcpyDeviceToHost, w->stream));
+        else
+            for (int64_t t = 0; t < nc; ++t)
+                AS_HIP(hipMemcpyAsync(c.out_rows + q[i0 + t] * m, res + t * m, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, w->stream));
+    }
+    AS_TRY(sync_add_elapsed(w->stream, timing, w->ev.e, us));
+    if (fr.select) {
+        // the selection runs on the handle's stream: f is complete (the wait above)
+        const int64_t k = std::min<int64_t>(std::min<int64_t>(c.k, m), SUBSET_TOPK);
+        AS_TRY(subset_select_rows_from(c.sel, res, c.pos_ids, m, m, k, nc));   // -> c.sel->out[t]; waits
+        const SubsetOut* so = c.sel->out;
+        for (int64_t t = 0; t < nc; ++t) {
+            const int64_t i = q[i0 + t];
+            AS_TRY(subset_list_out(so + t, k, c.out_idx + i * c.stride, c.out_score + i * c.stride, c.out_len + i));
+        }
+    }
+    return AS_OK;
+}
+
+static as_status diffuse_chunks(const as_space* sp, const as_graph* gr, const DiffuseCall& c, int64_t* counts) {
+    const int64_t n = gr->n;
+    DiffuseFrame fr;
+    AS_TRY(diffuse_frame(sp, gr, c, &fr));
+    if (!fr.w) return AS_OK;
+    DiffuseWork* w = fr.w;
+    const bool timing = diffuse_timing();
+    const int cols_cap = diffuse_cols_cap();
     const int64_t budget = (int64_t)g_diffuse_mib.load(std::memory_order_relaxed) << 20;
     const double om = 1.0 - c.alpha;
     w->kernel_us = 0.0;
-    const int32_t* ids_d = select ? c.pos_ids : nullptr;
-    if (pick) {
-        AS_TRY(reserve_or_err(w->ids, m, "diffuse listed ids"));
-        AS_HIP(hipMemcpyAsync(w->ids, c.pick_ids, sizeof(int32_t) * (size_t)m, hipMemcpyHostToDevice, w->stream));
-        ids_d = w->ids;
-    }
-    const int64_t nq = (int64_t)q.size();
+    const int64_t nq = (int64_t)fr.q.size();
     for (int64_t i0 = 0; i0 < nq;) {
-        const int C = diffuse_chunk_cols(nq - i0, n, cols_cap, budget);
+        const int C = diffuse_chunk_cols(nq - i0, n, cols_cap, budget, 2);
         const int64_t nc = std::min<int64_t>(C, nq - i0);
-        int64_t ns = 0;
-        for (int64_t t = 0; t < nc; ++t) ns += c.offs[q[i0 + t] + 1] - c.offs[q[i0 + t]];
         for (int s = 0; s < 2; ++s) AS_TRY(reserve_or_err(w->f[s], n * C, "diffuse f buffers"));
-        // the whole f in the [rows][m] layout, unless it has that layout already (one column, every item, in item order)
-        const bool gather = !(C == 1 && !ids_d);
-        if (gather) AS_TRY(reserve_or_err(w->rows, nc * m, "diffuse gathered rows"));
-        const size_t item_off = sizeof(double) * (size_t)ns, col_off = item_off + sizeof(int32_t) * (size_t)ns;
-        const size_t up = col_off + sizeof(int32_t) * (size_t)ns;
-        if (up > std::min(w->seed_d.size(), w->seed_h.size())) {
-            AS_TRY(reserve_or_err(w->seed_d, up + up / 2, "diffuse seed table"));
-            AS_TRY(reserve_or_err(w->seed_h, up + up / 2, "diffuse pinned seed table"));
-        }
-        char* const sh = w->seed_h;
-        char* const sd = w->seed_d;
-        double* hv = (double*)sh;
-        int32_t* hi = (int32_t*)(sh + item_off);
-        int32_t* hc = (int32_t*)(sh + col_off);
-        int64_t z = 0;
-        for (int64_t t = 0; t < nc; ++t)
-            for (int64_t e = c.offs[q[i0 + t]]; e < c.offs[q[i0 + t] + 1]; ++e, ++z) {
-                hv[z] = c.vals[e];
-                hi[z] = (int32_t)c.ids[e];
-                hc[z] = (int32_t)t;
-            }
-        if (ns > 0) AS_HIP(hipMemcpyAsync(sd, sh, up, hipMemcpyHostToDevice, w->stream));
-        const double* dv = (const double*)sd;
-        const int32_t* di = (const int32_t*)(sd + item_off);
-        const int32_t* dc = (const int32_t*)(sd + col_off);
-        const unsigned sgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((ns + DIF_THREADS - 1) / DIF_THREADS, 1024));
+        DiffuseSeeds sd;
+        AS_TRY(diffuse_seed_table(fr, c, i0, nc, &sd));
         double* fin = w->f[0];
         double* fout = w->f[1];
         AS_HIP(hipMemsetAsync(fin, 0, sizeof(double) * (size_t)(n * C), w->stream));
-        if (ns > 0) hipLaunchKernelGGL(diffuse_seed_kernel, dim3(sgrid), dim3(DIF_THREADS), 0, w->stream, di, dc, dv, ns, fin, C, om, 1);
+        diffuse_seed_launch(w, sd, fin, C, om, 1);
         if (timing) AS_HIP(hipEventRecord(w->ev.e[0], w->stream));
         for (int64_t t = 0; t < c.steps; ++t) {
             DiffuseArgs a;
             a.indptr = gr->indptr; a.indices = gr->indices; a.lap = gr->lap; a.fin = fin; a.fout = fout; a.n = n; a.alpha = c.alpha;
-            a.tile = g_diffuse_tile.load(std::memory_order_relaxed);
+            a.tile = diffuse_tile_edges();
             diffuse_step_launch(w, a, C);
-            if (ns > 0) hipLaunchKernelGGL(diffuse_seed_kernel, dim3(sgrid), dim3(DIF_THREADS), 0, w->stream, di, dc, dv, ns, fout, C, om, 0);
+            diffuse_seed_launch(w, sd, fout, C, om, 0);
             std::swap(fin, fout);
         }
         AS_HIP(hipGetLastError());
         if (timing) AS_HIP(hipEventRecord(w->ev.e[1], w->stream));
         counts[0] += 1;
         counts[1] += c.steps;
-        counts[2] += ns;
-        const double* res = fin;   // [nc][m] after the gather
-        if (gather) {
-            const unsigned ggrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((m + DIF_THREADS - 1) / DIF_THREADS, (int64_t)w->cus * 8));
-            hipLaunchKernelGGL(diffuse_gather_kernel, dim3(ggrid), dim3(DIF_THREADS), 0, w->stream, (const double*)fin, C, (int)nc, ids_d, m,
-                               (double*)w->rows);
-            AS_HIP(hipGetLastError());
-            res = w->rows;
-        }
-        if (!select) {
-            // (queries that follow one another in the call: one copy)
-            bool run = true;
-            for (int64_t t = 1; t < nc; ++t) run = run && q[i0 + t] == q[i0] + t;
-            if (run) AS_HIP(hipMemcpyAsync(c.out_rows + q[i0] * m, res, sizeof(double) * (size_t)(nc * m), hipMemcpyDeviceToHost, w->stream));
-            else
-                for (int64_t t = 0; t < nc; ++t)
-                    AS_HIP(hipMemcpyAsync(c.out_rows + q[i0 + t] * m, res + t * m, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, w->stream));
-        }
-        AS_TRY(sync_add_elapsed(w->stream, timing, w->ev.e, &w->kernel_us));
-        if (select) {
-            // the selection runs on the handle's stream: f is complete (the wait above)
-            const int64_t k = std::min<int64_t>(std::min<int64_t>(c.k, m), SUBSET_TOPK);
-            AS_TRY(subset_select_rows_from(c.sel, res, c.pos_ids, m, m, k, nc));   // -> c.sel->out[t]; waits
-            const SubsetOut* so = c.sel->out;
-            for (int64_t t = 0; t < nc; ++t) {
-                const int64_t i = q[i0 + t];
-                AS_TRY(subset_list_out(so + t, k, c.out_idx + i * c.stride, c.out_score + i * c.stride, c.out_len + i));
-            }
-        }
+        counts[2] += sd.ns;
+        AS_TRY(diffuse_emit(fr, c, i0, nc, C, fin, timing, &w->kernel_us));
         i0 += nc;
     }
     return AS_OK;
@@ -308,7 +320,7 @@ static as_status diffuse_chunks(const as_space* sp, const as_graph* gr, const Di
 
 // (a failed run leaves nothing on the stream when the caller releases the lock)
 as_status diffuse_run(const as_space* sp, const as_graph* gr, const DiffuseCall& c, int64_t* counts) {
-    const as_status s = diffuse_chunks(sp, gr, c, counts);
+    const as_status s = c.max_iters > 0 ? diffuse_solve_chunks(sp, gr, c, counts) : diffuse_chunks(sp, gr, c, counts);
     if (s != AS_OK && sp->diffuse_ws) (void)hipStreamSynchronize(sp->diffuse_ws->stream);
     return s;
 }

@@ -3663,6 +3663,10 @@ int32_t as_set_tuning(const char* key, int32_t value) {
         set_diffuse_mib(value);
         return 0;
     }
+    if (key && !strcmp(key, "diffuse_solve_mib")) {
+        set_diffuse_solve_mib(value);
+        return 0;
+    }
     if (key && !strcmp(key, "diffuse_cols")) {
         set_diffuse_cols(value);
         return 0;
