@@ -805,6 +805,43 @@ as_status as_diffuse_solve_counters(const as_space* sp, int64_t* out, int32_t n)
  * included); parts 1 .. 5 the five launches of ONE sampled iteration per chunk (its second, or its only one): the apply kernel,
  * the reduce of p.q, the update kernel, the reduce of r.r, the direction kernel (with the copy of the scalars ahead of it) */
 double as_diffuse_solve_kernel_us(const as_space* sp, int32_t part);
+/* ---- Extension: graph eigenpairs.  The m largest eigenvalues of S (the operator of the diffusion
+ * forms above: the stored off-diagonal entries of `lap`, negated) and their eigenvectors, by block Chebyshev-filtered subspace
+ * iteration with Rayleigh-Ritz on the device: a block of C = 16 (m <= 12) or 64 columns, all iterated every time, from a start
+ * block that `seed` fixes.  out_values [m], descending (for a row with an edge, 1 - value is the normalised Laplacian's
+ * eigenvalue); out_vectors [m][n], orthonormal, row j belonging to out_values[j], its entry of largest magnitude (lowest index on
+ * ties) positive; out_residuals [m], |S v - theta v|_2 as the device formed it; out_info [4]: outer iterations, state (1: every
+ * wanted residual <= tol; 0: stopped at max_iters, the iterate it has is served; 2: the block lost a direction -- a Gram
+ * eigenvalue <= 1e-14 of the largest -- and values, vectors and residuals are not written), step launches, C.  An outer iteration:
+ * Y = S X, H = X^T Y, the host decomposes H (a cyclic Jacobi, no LAPACK), X <- X Q, Y <- Y Q, the residuals; then a Chebyshev
+ * filter of at most `degree` steps over [-1, cut], cut below the smallest Ritz value and at least 1e-3 (theta_1 + 1) below the
+ * largest, its growth capped at 2e6, and two orthonormalisations (G = X^T X = U L U^T, X <- X U L^-1/2).  The four device
+ * primitives (step, gram, rotate, colnorm2) have fixed orders and round every product and sum once: each has the bits of the numpy
+ * reference; the driver's answer depends on the host eigensolver's roundings and is checked by what an eigenpair must satisfy.  The
+ * same call returns the same bits, whatever "diffuse_grid_cap".  Refused before anything is launched: m outside [1, 48], tol not in
+ * (0, 1), max_iters outside [1, 10000], degree outside [1, 64], seed < 0, n < C, four n x C blocks beyond the "spectral_mib" budget
+ * (default 8192 MiB) (AS_EINVAL); a feature-mode or row-sharded graph (AS_EUNSUPPORTED).  The blocks are the diffusion forms' work
+ * buffers: calls on one space are serialised with them. */
+as_status as_graph_eigs(const as_space* sp, const as_graph* gr, int64_t m, double tol, int64_t max_iters, int64_t degree, int64_t seed,
+                        double* out_values, double* out_vectors, double* out_residuals, int64_t* out_info);
+/* out[0] calls that passed their checks, [1] outer iterations, [2] step launches, [3] Gram launches, [4] rotate launches, [5] host
+ * waits (one per Gram, one per residual, one for the answer) */
+as_status as_graph_eigs_counters(const as_space* sp, int64_t* out, int32_t n);
+/* measurement, of the last as_graph_eigs on this space: part 0 the call's wall microseconds, 5 the host eigensolver's, 6 the
+ * host's waits; under as_set_tuning("diffuse_timing", 1) parts 1 .. 4 the device microseconds (HIP events around every launch,
+ * which then run one at a time) of the steps, the Grams with their trees, the rotates, and colnorm2 with its tree */
+double as_graph_eigs_kernel_us(const as_space* sp, int32_t part);
+/* debug: one S21 primitive on host blocks, through exactly the launch as_graph_eigs makes.  Blocks are [n][C] doubles, C = 16 or 64.
+ * AS_SPECTRAL_STEP (n the graph's): out = fl(fl(fl(a acc) + fl(b V)) + fl(g W)) with V = a_host, W = b_host (NULL with g == 0),
+ * coef = {a, b, g, alias}; alias != 0: the result is written over W's block.  AS_SPECTRAL_GRAM: out [C][C] = A^T B (b_host NULL:
+ * B = A).  AS_SPECTRAL_ROTATE: out [n][C] = X T, t_host = T [C][C].  AS_SPECTRAL_COLNORM2: out [C], the squared column norms of
+ * Y - X theta with X = a_host, Y = b_host, t_host = theta [C]. */
+enum { AS_SPECTRAL_STEP = 0, AS_SPECTRAL_GRAM = 1, AS_SPECTRAL_ROTATE = 2, AS_SPECTRAL_COLNORM2 = 3 };
+as_status as_spectral_op(const as_space* sp, const as_graph* gr, int32_t op, int64_t n, int32_t C, const double* a_host, const double* b_host,
+                         const double* t_host, const double* coef, double* out_host);
+/* the host eigensolver of as_graph_eigs (no GPU): a symmetric n x n matrix, row-major -> w [n] ascending, v [n][n] row-major with
+ * eigenvector j in column j.  -> the Jacobi sweeps run, -1 on a bad argument or if 64 sweeps did not end it */
+int32_t as_sym_eig_host(const double* a, int32_t n, double* w, double* v);
 /* ---- Extension: fused multi-query search.  ONE answer to j >= 1 query vectors, row-major [j][d] in HOST memory,
  * with finite weights w (weights == NULL: 1/j each; negative weights are legal).  s_v(i): the S11 score of item i for vector v
  * with the bits as_score_items_batch writes at [v][i] (lambda_q of every vector from ONE as_search_batch over the j vectors, the

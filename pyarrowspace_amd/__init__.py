@@ -1578,6 +1578,74 @@ class ArrowSpace:
         return _counters(_L.as_diffuse_solve_counters, self._h,
                          ("calls", "route searches", "column chunks", "iterations launched", "host waits", "seeds uploaded"))
 
+    @staticmethod
+    def _eigsh_params(m, tol, max_iters, degree, seed) -> tuple[int, float, int, int, int, int]:
+        """The checks of `eigsh` that need no handle -> (m, tol, max_iters, degree, seed, C)."""
+        for name, v, lo, hi in (("m", m, 1, 48), ("max_iters", max_iters, 1, 10000), ("degree", degree, 1, 64), ("seed", seed, 0, 2 ** 63 - 1)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"{name} must be an integer, got {v!r}")
+            if not lo <= v <= hi:
+                raise ValueError(f"{name} must lie in [{lo}, {'2^63 - 1' if name == 'seed' else hi}], got {v}")
+        t = float(tol)
+        if not (np.isfinite(t) and 0.0 < t < 1.0):   # (NaN fails the comparisons)
+            raise ValueError(f"tol must be finite and lie in (0, 1), got {tol}")
+        return int(m), t, int(max_iters), int(degree), int(seed), 16 if m <= 12 else 64
+
+    def eigsh(self, gl: GraphLaplacian, m: int, tol: float = 1e-8, max_iters: int = 200, degree: int = 16, seed: int = 0,
+              with_info: bool = False):
+        """Extension: the m largest eigenvalues of the item graph's operator S (the S of `search_diffuse`: the off-diagonal
+        entries of the stored Laplacian, negated, i.e. D^-1/2 A D^-1/2) and their eigenvectors -> (values, vectors): values
+        ndarray[float64] of shape (m,), descending; vectors of shape (m, nitems), orthonormal, row j belonging to values[j]
+        (the layout of the block `diffuse` returns), each with its entry of largest magnitude (lowest index on ties)
+        positive.  For rows with an edge, 1 - value is the eigenvalue of the normalised Laplacian: the multiplicity of the
+        value 1 is the number of connected components among them, the next value tells the gap (a row without an edge is an
+        eigenvector of value 0).  Block Chebyshev-filtered subspace iteration with Rayleigh-Ritz on the device: a block of 16
+        columns (m <= 12) or 64, a filter of at most `degree` graph passes per outer iteration, stopped when every wanted
+        residual |S v - value v| is <= tol or after `max_iters` outer iterations.  A call that stops at max_iters is served
+        with the iterate it has and converged = False; it does not raise.  `seed` picks the start block; the same call
+        returns the same bits.  with_info: -> (values, vectors, info), info = {"iterations", "residuals" (m,), "converged",
+        "filter_steps" (graph passes launched), "block"}.  1 <= m <= 48, 0 < tol < 1, 1 <= max_iters <= 10000, 1 <= degree <=
+        64, 0 <= seed < 2^63 (integers), nitems >= the block's width, and four blocks of nitems x width doubles within the
+        "spectral_mib" tuning (default 8192 MiB), else ValueError; a feature-mode or row-sharded index raises ValueError; a
+        block that loses a direction (a breakdown) raises RuntimeError."""
+        _need_gl(gl)
+        m, t, mi, deg, sd, _ = self._eigsh_params(m, tol, max_iters, degree, seed)
+        n = self.nitems
+        values, vectors, res = np.empty(m, dtype=np.float64), np.empty((m, n), dtype=np.float64), np.empty(m, dtype=np.float64)
+        info = np.zeros(4, dtype=np.int64)
+        _check(_L.as_graph_eigs(self._h, gl._h, m, t, mi, deg, sd, values.ctypes.data, vectors.ctypes.data, res.ctypes.data, info.ctypes.data))
+        if info[1] == 2:
+            raise RuntimeError(f"eigsh: the block lost a direction in outer iteration {int(info[0])} (a Gram eigenvalue <= 1e-14 of the largest)")
+        if not with_info:
+            return values, vectors
+        return values, vectors, {"iterations": int(info[0]), "residuals": res, "converged": bool(info[1] == 1), "filter_steps": int(info[2]),
+                                 "block": int(info[3])}
+
+    def eigsh_counters(self) -> dict:
+        """Extension: `eigsh` calls on this space that passed their checks, their outer iterations, the step (graph pass), Gram
+        and rotate launches, and the host's waits (one per Gram, one per residual, one for the answer)."""
+        return _counters(_L.as_graph_eigs_counters, self._h,
+                         ("calls", "outer iterations", "step launches", "gram launches", "rotate launches", "host waits"))
+
+    def _spectral_op(self, gl: GraphLaplacian, op: str, A, B=None, T=None, coef=None, alias: bool = False):
+        """Debug: one S21 primitive on host blocks [n, C] (C = 16 or 64) through the launch `eigsh` makes.  op "step": A = V, B = W
+        (None with g == 0), coef = (a, b, g), alias: the result is written over W's block; "gram": A^T B (B None: A^T A) ->
+        [C, C]; "rotate": A T with T [C, C]; "colnorm2": the squared column norms of B - A theta with T = theta [C] -> [C]."""
+        _need_gl(gl)
+        code = {"step": 0, "gram": 1, "rotate": 2, "colnorm2": 3}[op]
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        if A.ndim != 2:
+            raise ValueError("argument 'A': expected a 2-D block")
+        n, c = A.shape
+        same = lambda X, shape: None if X is None else np.ascontiguousarray(X, dtype=np.float64).reshape(shape)   # noqa: E731
+        B = same(B, (n, c))
+        T = same(T, (c, c) if op == "rotate" else (c,))
+        cf = None if coef is None else np.array(list(coef) + [1.0 if alias else 0.0], dtype=np.float64)
+        out = np.empty({"step": (n, c), "gram": (c, c), "rotate": (n, c), "colnorm2": (c,)}[op], dtype=np.float64)
+        ptr = lambda X: None if X is None else X.ctypes.data   # noqa: E731
+        _check(_L.as_spectral_op(self._h, gl._h, code, n, c, ptr(A), ptr(B), ptr(T), ptr(cf), out.ctypes.data))
+        return out
+
     def _lists_args(self, items, gl, lists):
         _need_gl(gl)
         Q = _queries_2d(items)

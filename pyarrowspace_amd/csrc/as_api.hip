@@ -3097,6 +3097,111 @@ double as_diffuse_solve_kernel_us(const as_space* sp, int32_t part) {
     return diffuse_solve_kernel_us(sp->diffuse_ws, part);
 }
 
+// ---- graph eigenpairs (extension; as_spectral.hip)
+namespace {
+// what as_graph_eigs and as_spectral_op refuse about the graph and the blocks, before anything is launched
+as_status spectral_graph_checks(const char* who, const as_space* sp, const as_graph* gr, int64_t n, int C) {
+    if (gr->lambda_mode == AS_LAMBDA_FEATURE) {
+        set_err("%s: a feature-mode graph (its Laplacian is over the columns) is not supported", who);
+        return AS_EUNSUPPORTED;
+    }
+    AS_TRY(graph_matches(sp, gr, who));
+    if (sp->row_offset != 0 || gr->ncols) {
+        set_err("%s: a shard of a row-sharded index is not supported", who);
+        return AS_EUNSUPPORTED;
+    }
+    AS_TRY(diffuse_graph_checks(who, sp, gr));
+    if (n < C) {
+        set_err("%s: %lld rows are fewer than the %d columns of the block", who, (long long)n, C);
+        return AS_EINVAL;
+    }
+    if (4 * (int64_t)sizeof(double) * n * C > spectral_budget()) {
+        set_err("%s: four blocks of %lld x %d doubles exceed the \"spectral_mib\" budget of %lld MiB", who, (long long)n, C,
+                (long long)(spectral_budget() >> 20));
+        return AS_EINVAL;
+    }
+    return AS_OK;
+}
+}  // namespace
+
+as_status as_graph_eigs(const as_space* sp, const as_graph* gr, int64_t m, double tol, int64_t max_iters, int64_t degree, int64_t seed,
+                        double* out_values, double* out_vectors, double* out_residuals, int64_t* out_info) {
+    const char* who = "as_graph_eigs";
+    if (!sp || !gr || !out_values || !out_vectors || !out_residuals || !out_info) {
+        set_err("%s: null argument", who);
+        return AS_EINVAL;
+    }
+    if (m < 1 || m > 48) {
+        set_err("%s: m must lie in [1, 48], got %lld", who, (long long)m);
+        return AS_EINVAL;
+    }
+    if (!(std::isfinite(tol) && tol > 0.0 && tol < 1.0)) {
+        set_err("%s: tol must be finite and lie in (0, 1), got %g", who, tol);
+        return AS_EINVAL;
+    }
+    if (max_iters < 1 || max_iters > 10000) {
+        set_err("%s: max_iters must lie in [1, 10000], got %lld", who, (long long)max_iters);
+        return AS_EINVAL;
+    }
+    if (degree < 1 || degree > 64) {
+        set_err("%s: degree must lie in [1, 64], got %lld", who, (long long)degree);
+        return AS_EINVAL;
+    }
+    if (seed < 0) {
+        set_err("%s: seed must lie in [0, 2^63), got %lld", who, (long long)seed);
+        return AS_EINVAL;
+    }
+    const int C = m <= 12 ? 16 : 64;
+    AS_TRY(spectral_graph_checks(who, sp, gr, gr->n, C));
+    sp->eigs_count[0].fetch_add(1, std::memory_order_relaxed);
+    SpectralCall sc;
+    sc.m = (int)m; sc.C = C; sc.tol = tol; sc.max_iters = max_iters; sc.degree = (int)degree; sc.seed = seed;
+    sc.out_values = out_values; sc.out_vectors = out_vectors; sc.out_residuals = out_residuals; sc.out_info = out_info;
+    int64_t counts[5] = {0, 0, 0, 0, 0};
+    std::lock_guard<std::mutex> lk(sp->fmu);
+    if (hipSetDevice(sp->device) != hipSuccess) {
+        set_err("%s: hipSetDevice failed", who);
+        return AS_EHIP;
+    }
+    const as_status s = spectral_eigs(sp, gr, sc, counts);
+    for (int i = 0; i < 5; ++i) sp->eigs_count[1 + i].fetch_add(counts[i], std::memory_order_relaxed);
+    return s;
+}
+as_status as_graph_eigs_counters(const as_space* sp, int64_t* out, int32_t n) {
+    return counters_out("as_graph_eigs_counters", sp, out, n, sp ? sp->eigs_count : nullptr, 6);
+}
+double as_graph_eigs_kernel_us(const as_space* sp, int32_t part) {
+    if (!sp) return 0.0;
+    std::lock_guard<std::mutex> lk(sp->fmu);
+    return spectral_kernel_us(sp->diffuse_ws, part);
+}
+as_status as_spectral_op(const as_space* sp, const as_graph* gr, int32_t op, int64_t n, int32_t C, const double* a_host, const double* b_host,
+                         const double* t_host, const double* coef, double* out_host) {
+    const char* who = "as_spectral_op";
+    if (!sp || !gr || !a_host || !out_host) {
+        set_err("%s: null argument", who);
+        return AS_EINVAL;
+    }
+    if (op < AS_SPECTRAL_STEP || op > AS_SPECTRAL_COLNORM2 || (C != 16 && C != 64) || n < 1) {
+        set_err("%s: op must be 0 .. 3, C 16 or 64 and n >= 1, got op %d, C %d, n %lld", who, (int)op, (int)C, (long long)n);
+        return AS_EINVAL;
+    }
+    const bool step = op == AS_SPECTRAL_STEP;
+    if ((step && (!coef || n != gr->n || (coef[2] != 0.0 && !b_host) || (coef[3] != 0.0 && !b_host))) ||
+        ((op == AS_SPECTRAL_ROTATE || op == AS_SPECTRAL_COLNORM2) && !t_host) || (op == AS_SPECTRAL_COLNORM2 && !b_host)) {
+        set_err("%s: op %d lacks an argument (the step: n is the graph's, W with g != 0)", who, (int)op);
+        return AS_EINVAL;
+    }
+    AS_TRY(spectral_graph_checks(who, sp, gr, n, C));
+    std::lock_guard<std::mutex> lk(sp->fmu);
+    if (hipSetDevice(sp->device) != hipSuccess) {
+        set_err("%s: hipSetDevice failed", who);
+        return AS_EHIP;
+    }
+    return spectral_op(sp, gr, op, n, C, a_host, b_host, t_host, coef, out_host);
+}
+int32_t as_sym_eig_host(const double* a, int32_t n, double* w, double* v) { return sym_eig_host(a, n, w, v); }
+
 as_status as_diffuse_counters(const as_space* sp, int64_t* out, int32_t n) {
     return counters_out("as_diffuse_counters", sp, out, n, sp ? sp->diffuse_count : nullptr, 5);
 }

@@ -233,6 +233,9 @@ struct as_space {
     // the solve forms share diffuse_ws and fmu.  as_diffuse_solve_counters: [0] calls that passed their
     // checks, [1] route searches run, [2] column chunks, [3] iterations launched, [4] host waits, [5] seeds uploaded
     mutable std::atomic<int64_t> diffuse_solve_count[6] = {};
+    // as_graph_eigs shares diffuse_ws and fmu.  as_graph_eigs_counters: [0] calls that passed their
+    // checks, [1] outer iterations, [2] step launches, [3] Gram launches, [4] rotate launches, [5] host waits
+    mutable std::atomic<int64_t> eigs_count[6] = {};
 };
 
 struct as_graph {
@@ -1130,5 +1133,29 @@ void set_diffuse_grid_cap(int v);     // as_set_tuning("diffuse_grid_cap", v): v
 // the S20 solve (as_diffuse_solve.hip) runs through diffuse_run with c.max_iters > 0, on the same work buffers
 double diffuse_solve_kernel_us(const DiffuseWork* w, int part);
 void set_diffuse_solve_mib(int v);    // as_set_tuning("diffuse_solve_mib", v): the byte budget of the solve's four vectors; 0: the default (2048 MiB)
+// Graph eigenpairs (as_spectral.hip): the m largest eigenvalues of S = -lap and their eigenvectors, on
+// the diffusion forms' work buffers (under sp->fmu), the caller has checked every argument.  out_values [m] descending, out_vectors
+// [m][n], out_residuals [m], out_info: [0] outer iterations, [1] 1 converged / 0 stopped at max_iters / 2 breakdown (the three
+// arrays are then not written), [2] step launches, [3] C.  counts[0] += outer iterations, [1] += step launches, [2] += Gram
+// launches, [3] += rotate launches, [4] += host waits.
+struct SpectralCall {
+    int m = 0, C = 0;
+    double tol = 0.0;
+    int64_t max_iters = 0;
+    int degree = 0;
+    int64_t seed = 0;
+    double* out_values = nullptr;
+    double* out_vectors = nullptr;
+    double* out_residuals = nullptr;
+    int64_t* out_info = nullptr;
+};
+as_status spectral_eigs(const as_space* sp, const as_graph* gr, const SpectralCall& c, int64_t* counts);
+// one primitive on host blocks (as_spectral_op): n rows (the step: gr's), C = 16 or 64
+as_status spectral_op(const as_space* sp, const as_graph* gr, int op, int64_t n, int C, const double* a_host, const double* b_host,
+                      const double* t_host, const double* coef, double* out_host);
+int sym_eig_host(const double* a, int n, double* w, double* v);
+double spectral_kernel_us(const DiffuseWork* w, int part);
+int64_t spectral_budget();            // "spectral_mib" in bytes
+void set_spectral_mib(int v);         // as_set_tuning("spectral_mib", v): the byte budget of the eigensolver's four blocks; 0: the default (8192 MiB)
 
 }  // namespace as

@@ -159,6 +159,12 @@ static as_status diffuse_work_create(const as_space* sp, DiffuseWork** out) {
     return AS_OK;
 }
 
+as_status diffuse_work_get(const as_space* sp, DiffuseWork** out) {
+    if (!sp->diffuse_ws) AS_TRY(diffuse_work_create(sp, &sp->diffuse_ws));
+    *out = sp->diffuse_ws;
+    return AS_OK;
+}
+
 int diffuse_chunk_cols(int64_t rem, int64_t n, int cols_cap, int64_t budget, int bufs) {
     auto fits = [&](int c) { return c <= cols_cap && bufs * (int64_t)sizeof(double) * n * c <= budget; };
     if (rem > 32 && fits(64)) return 64;

@@ -1,5 +1,5 @@
-// What the two diffusion files share (as_diffuse.hip: the S19 recurrence; as_diffuse_solve.hip: the S20 conjugate-gradient solve of
-// its fixed point): the work buffers of a space, the column-chunk rule, the sparse seed table and its kernel, and the output
+// What the diffusion files share (as_diffuse.hip: the S19 recurrence; as_diffuse_solve.hip: the S20 conjugate-gradient solve of
+// its fixed point; as_spectral.hip: the S21 eigenpairs, which use the four blocks and the partials): the work buffers of a space, the column-chunk rule, the sparse seed table and its kernel, and the output
 // paths (gather, selection on the handle's stream, score pick, raw block).  Defined in as_diffuse.hip.
 #pragma once
 #include <vector>
@@ -18,6 +18,8 @@ constexpr int DIF_MIB_DEFAULT = 1024;
 // "diffuse_solve_mib", the budget of the solve's four vectors: twice the above, so the column widths per N are the recurrence's
 constexpr int DIF_SOLVE_MIB_DEFAULT = 2 * DIF_MIB_DEFAULT;
 constexpr int DIF_SOLVE_COLS = 64;        // the stride of the solve's per-column scalars: the widest chunk
+// "spectral_mib", the budget of the eigensolver's four blocks: 64 columns up to 4M rows.  A choice, not a measurement.
+constexpr int SPC_MIB_DEFAULT = 8192;
 
 struct DiffuseWork {
     int device = 0;
@@ -37,6 +39,13 @@ struct DiffuseWork {
     pin_buf<char> scal_h;
     double solve_us = 0.0;      // first to last launch of the iterations, summed over the chunks of the last timed solve
     double solve_part_us[5] = {};   // ... and of one sampled iteration per chunk: apply, reduce of p.q, update, reduce of r.r, direction
+    // the eigenpairs (S21): the four blocks are f[0..1] and sv[0..1], the partials of a Gram or of a column dot are `part`
+    dev_buf<double> spec_d;     // [C][C] the matrix of a rotate, [C] the Ritz values behind it
+    pin_buf<double> spec_h;     // the same pair, then a downloaded Gram [C][C] and the squared residual norms [C]
+    dev_events<2> spec_ev;      // made by the first timed call
+    // the last call: [0] its wall time; under "diffuse_timing" the device time of [1] steps, [2] Grams, [3] rotates, [4] colnorm2;
+    // [5] the host's eigensolver, [6] the host's waits
+    double spectral_us[7] = {};
 };
 
 // the tunings both files honour
@@ -56,6 +65,8 @@ struct DiffuseFrame {
     bool select = false, pick = false;
 };
 as_status diffuse_frame(const as_space* sp, const as_graph* gr, const DiffuseCall& c, DiffuseFrame* fr);
+// the space's workspace, made on first use (under sp->fmu)
+as_status diffuse_work_get(const as_space* sp, DiffuseWork** out);
 // the seed table of the chunk fr->q[i0 .. i0 + nc): built in pinned memory and uploaded on the work's stream
 struct DiffuseSeeds {
     int64_t ns = 0;

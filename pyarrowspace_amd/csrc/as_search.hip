@@ -3667,6 +3667,10 @@ int32_t as_set_tuning(const char* key, int32_t value) {
         set_diffuse_solve_mib(value);
         return 0;
     }
+    if (key && !strcmp(key, "spectral_mib")) {
+        set_spectral_mib(value);
+        return 0;
+    }
     if (key && !strcmp(key, "diffuse_cols")) {
         set_diffuse_cols(value);
         return 0;
