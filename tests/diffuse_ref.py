@@ -6,17 +6,29 @@ import numpy as np
 # the shapes of tests/test_gpu_diffuse.py (and of the CPU check of its inputs): (n, d, nclust, k, topk, metric, kernel)
 SHAPES = {"A": (257, 16, 4, 4, 8, "l2", "gaussian"),
           "B": (1000, 24, 16, 8, 15, "cosine", "rational")}
+# the shapes of tests/test_gpu_diffusion_scale.py alone, in the same layout: the sizes at which the reductions of S20 and S21 get
+# more segments than one trip of their trees takes.  C: 3 Gram segments of 1 024 rows in a tree padded to 4, 33 dot segments of 64,
+# a remainder of 5 modulo 16, 64 and 1 024.  L: the smallest n with more than 2 048 dot segments and one row in the last (2 050):
+# the 1 024 threads of the solve's tree take a second trip over the 2 048 pairs of its first level, whose upper halves (segments
+# 3 072 and up) are all padding.  M: 3 600 dot segments, so that 528 pairs of that second trip add a partial that exists.
+SCALE_SHAPES = {"C": (2053, 16, 12, 6, 10, "l2", "gaussian"),
+                "L": (131137, 8, 64, 4, 8, "l2", "gaussian"),
+                "M": (230337, 8, 64, 4, 8, "l2", "gaussian")}
+# rows calibrate_eps samples where its default of 256 is too many: 256 x n distances are about 270 MB per temporary at L's n
+EPS_SAMPLE = {"L": 64, "M": 64}
 TILE_EDGES = 8   # the "diffuse_tile_edges" the GPU test sets: rows of 3 x 8 edges and more span tiles
 TAU = 0.62
 NQ = 6
 
 
 def shape_items(name):
-    """(X, graph parameters) of a shape: the clustered() / calibrate_eps recipe of tests/test_gpu_range.py."""
+    """(X, graph parameters) of a shape of SHAPES or SCALE_SHAPES: the clustered() / calibrate_eps recipe of
+    tests/test_gpu_range.py."""
     from conftest import calibrate_eps, clustered
-    n, d, nclust, k, topk, metric, kernel = SHAPES[name]
+    n, d, nclust, k, topk, metric, kernel = SHAPES[name] if name in SHAPES else SCALE_SHAPES[name]
     X = clustered(n, d, nclust=nclust)
-    gp = {"eps": calibrate_eps(X, k, metric), "k": k, "topk": topk, "p": 2.0, "sigma": None, "metric": metric, "kernel": kernel}
+    eps = calibrate_eps(X, k, metric, sample=EPS_SAMPLE[name]) if name in EPS_SAMPLE else calibrate_eps(X, k, metric)
+    gp = {"eps": eps, "k": k, "topk": topk, "p": 2.0, "sigma": None, "metric": metric, "kernel": kernel}
     return X, gp
 
 

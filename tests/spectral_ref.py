@@ -19,6 +19,8 @@ M_MAX = 48
 U64 = (1 << 64) - 1
 # the solver cases of tests/test_gpu_spectral.py, (m, C), on both shapes of diffuse_ref.SHAPES, at TOL within MAX_ITERS
 CASES = ((1, 16), (8, 16), (12, 16), (13, 64), (19, 64), (48, 64))
+# the solver cases of tests/test_gpu_diffusion_scale.py on shape C of diffuse_ref.SCALE_SHAPES (the eigenvalue 1 has multiplicity 19)
+SCALE_CASES = ((8, 16), (13, 64), (19, 64), (48, 64))
 TOL = 1e-8
 MAX_ITERS = 60
 # max |V V^T - I| of this reference over those cases stays below this (tests/test_spectral_inputs.py prints and asserts it: the
@@ -117,14 +119,15 @@ def gram(A, B):
 
 
 def gram_loops(A, B):
-    n, C = A.shape
+    """(A [n, Ca] and B [n, Cb] -> [Ca, Cb]: a few columns of either give a few rows or columns of the Gram at a large n)"""
+    n = A.shape[0]
     ns = -(-n // GRAM_SEG)
     P = 1
     while P < ns:
         P *= 2
-    G = np.empty((C, C))
-    for i in range(C):
-        for j in range(C):
+    G = np.empty((A.shape[1], B.shape[1]))
+    for i in range(A.shape[1]):
+        for j in range(B.shape[1]):
             t = []
             for s in range(ns):
                 acc = 0.0

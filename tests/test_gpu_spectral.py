@@ -95,6 +95,12 @@ def test_gram_rotate_and_colnorm2_bits(n, cols):
 @pytest.mark.parametrize("m, cols", spr.CASES)
 @pytest.mark.parametrize("name", list(dfr.SHAPES))
 def test_solver(name, m, cols):
+    solver_checks(name, m, cols)
+
+
+def solver_checks(name, m, cols):
+    """What an answer of eigsh(m) on a shape must satisfy -> (values, vectors, info, the dense eigenvalues): also the body of
+    tests/test_gpu_diffusion_scale.py's solver test."""
     ix = index(name)
     Sd, lam, vec = dense(name)
     c0 = counters(ix)
@@ -130,6 +136,7 @@ def test_solver(name, m, cols):
     assert ix.aspace.eigsh_counters() == dict(zip(NAMES, c1))
     two = ix.aspace.eigsh(ix.gl, m, TOL, MAX_ITERS)
     assert len(two) == 2 and (two[0].view(np.uint64) == values.view(np.uint64)).all()
+    return values, vectors, info, lam
 
 
 @pytest.mark.parametrize("m", [8, 19])
