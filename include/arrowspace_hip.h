@@ -454,6 +454,10 @@ as_status as_get_graph_params(const as_graph* gr, as_graph_params* out); /* sigm
 int64_t as_graph_nnz(const as_graph* gr); /* stored Laplacian entries incl. diagonal */
 /* CSR of the normalised Laplacian: indptr int64[n+1], indices int64[nnz], values fp64[nnz] */
 as_status as_graph_csr(const as_graph* gr, int64_t* indptr, int64_t* indices, double* values);
+/* the stored CSR of an item graph as the device holds it, without the diagonal: indptr int64[n+1], indices int64[indptr[n]],
+ * dist fp64[indptr[n]] the distance d_ij of every entry (as_graph_nnz minus n entries at most); a feature-mode graph stores no
+ * distances (AS_EUNSUPPORTED) */
+as_status as_graph_csr_dist(const as_graph* gr, int64_t* indptr, int64_t* indices, double* dist);
 as_status as_graph_degrees(const as_graph* gr, double* out);
 double as_graph_tau0(const as_graph* gr);
 int32_t as_graph_lambda_mode(const as_graph* gr); /* AS_LAMBDA_* */
@@ -842,6 +846,39 @@ as_status as_spectral_op(const as_space* sp, const as_graph* gr, int32_t op, int
 /* the host eigensolver of as_graph_eigs (no GPU): a symmetric n x n matrix, row-major -> w [n] ascending, v [n][n] row-major with
  * eigenvector j in column j.  -> the Jacobi sweeps run, -1 on a bad argument or if 64 sweeps did not end it */
 int32_t as_sym_eig_host(const double* a, int32_t n, double* w, double* v);
+/* ---- Extension: connected components of the item graph.  The stored CSR of a whole item graph is
+ * used (no diagonal; `dist` per entry).  Kept entries: max_dist == NULL: every stored entry; else the entries with dist <= *max_dist
+ * (a NaN dist is never kept under a threshold; +inf keeps every entry whose dist is no NaN, -inf none).  Items i and j are joined iff
+ * at least one of the stored entries i -> j, j -> i is kept; the components are the classes of the transitive closure; the label
+ * of an item is the smallest item id of its component (an item without a kept entry is its own label).  labels_host [n] int32.
+ * info (may be NULL): the components, the size of the largest, the smallest label of that size, the components of one item, the
+ * stored entries kept (both directions as stored) and the rounds run -- every field but `rounds` is a function of the graph and
+ * the threshold alone.  On the device: parent[i] = i, then rounds of two launches -- hook (for a kept entry (i, j) with
+ * a = parent[i] != b = parent[j]: atomicMin(&parent[max(a, b)], min(a, b))) and compress (every item stores its root) -- until the
+ * host reads that a round's hook met no entry with unequal parents; `rounds` counts the hook launches.  Sizes and the four
+ * statistics are formed on the device with integer atomics; six numbers cross per threshold, and as_graph_components alone copies
+ * the labels.  The answer does not depend on "diffuse_grid_cap" nor on the order in which the atomics land.
+ * as_graph_components_sweep: nt thresholds in [1, 64], any order, duplicates allowed -> info [nt] in the caller's order; the
+ * distinct thresholds run ascending, each from the labels of the one before (the kept sets are nested); no labels cross.
+ * Refused before anything is launched: a NaN threshold, nt outside [1, 64], a graph whose row count is not the space's (AS_EINVAL);
+ * a feature-mode or row-sharded graph (AS_EUNSUPPORTED).  The buffers are the diffusion forms' workspace: calls on one space are
+ * serialised with them. */
+typedef struct as_components_info {
+    int64_t count;          /* components */
+    int64_t largest;        /* items of the largest component */
+    int64_t largest_label;  /* the smallest label whose component has that size */
+    int64_t isolated;       /* components of one item */
+    int64_t edges_kept;     /* stored entries kept, both directions as stored */
+    int64_t rounds;         /* hook launches */
+} as_components_info;
+as_status as_graph_components(const as_space* sp, const as_graph* gr, const double* max_dist, int32_t* labels_host, as_components_info* info);
+as_status as_graph_components_sweep(const as_space* sp, const as_graph* gr, const double* max_dists, int32_t nt, as_components_info* info);
+/* out[0] calls that passed their checks, [1] thresholds served (1 for a call without one), [2] hook launches, [3] compress
+ * launches, [4] host waits (one per round, one per stage for the statistics) */
+as_status as_components_counters(const as_space* sp, int64_t* out, int32_t n);
+/* measurement, of the last components call on this space under as_set_tuning("diffuse_timing", 1): part 0 the device microseconds
+ * of its hook launches, 1 of its compress launches, 2 of its statistics (sizes and reduction); part 3 its rounds (any timing) */
+double as_components_kernel_us(const as_space* sp, int32_t part);
 /* ---- Extension: fused multi-query search.  ONE answer to j >= 1 query vectors, row-major [j][d] in HOST memory,
  * with finite weights w (weights == NULL: 1/j each; negative weights are legal).  s_v(i): the S11 score of item i for vector v
  * with the bits as_score_items_batch writes at [v][i] (lambda_q of every vector from ONE as_search_batch over the j vectors, the

@@ -230,6 +230,20 @@ class GraphLaplacian:
             _raise(st)
         return indptr, indices[: indptr[-1]], values[: indptr[-1]]
 
+    def to_csr_dist(self):
+        """Extension: (indptr, indices, dist) of the stored item graph as the device holds it: no diagonal, columns ascending,
+        dist[e] the distance d_ij of entry e -- the structure of `to_csr()` with its diagonal removed.  The values
+        `ArrowSpace.components(max_dist=...)` compares its threshold with.  A feature-mode graph raises ValueError."""
+        n, nnz = self.nnodes, max(int(_L.as_graph_nnz(self._h)) - self.nnodes, 0)
+        indptr = np.empty(n + 1, dtype=np.int64)
+        indices = np.empty(max(nnz, 1), dtype=np.int64)
+        dist = np.empty(max(nnz, 1), dtype=np.float64)
+        st = _L.as_graph_csr_dist(self._h, indptr.ctypes.data_as(C.c_void_p), indices.ctypes.data_as(C.c_void_p),
+                                  dist.ctypes.data_as(C.c_void_p))
+        if st:
+            _raise(st)
+        return indptr, indices[: indptr[-1]], dist[: indptr[-1]]
+
     def build_stats(self) -> dict:
         out = np.zeros(10, dtype=np.float64)
         _L.as_build_stats(self._h, out.ctypes.data_as(C.c_void_p), 10)
@@ -1626,6 +1640,64 @@ class ArrowSpace:
         and rotate launches, and the host's waits (one per Gram, one per residual, one for the answer)."""
         return _counters(_L.as_graph_eigs_counters, self._h,
                          ("calls", "outer iterations", "step launches", "gram launches", "rotate launches", "host waits"))
+
+    _COMPONENTS_KEYS = ("count", "largest", "largest_label", "isolated", "edges_kept", "rounds")
+
+    @staticmethod
+    def _components_thresholds(max_dists, single: bool = False) -> np.ndarray:
+        """The checks of `components` / `components_sweep` that need no handle -> the thresholds as float64 [T]."""
+        what = "max_dist" if single else "max_dists"
+        vals = [max_dists] if single else (list(max_dists) if not isinstance(max_dists, (str, bytes)) and np.ndim(max_dists) == 1 else None)
+        if vals is None:
+            raise ValueError(f"{what} must be a sequence of 1 to 64 numbers, got {max_dists!r}")
+        for v in vals:
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise ValueError(f"{what} must be {'a number' if single else 'numbers'}, got {v!r}")
+        if not 1 <= len(vals) <= 64:
+            raise ValueError(f"{what} must hold 1 to 64 thresholds, got {len(vals)}")
+        t = np.array(vals, dtype=np.float64)
+        if np.isnan(t).any():
+            raise ValueError(f"{what} must not hold a NaN")
+        return t
+
+    def components(self, gl: GraphLaplacian, max_dist=None, with_info: bool = False):
+        """Extension: the connected components of the item graph -> labels, ndarray[int32] of shape (nitems,): the label of an
+        item is the smallest item id of its component.  The graph's stored entries are used (`gl.to_csr_dist()`): items i and j
+        are joined iff the entry i -> j or the entry j -> i is kept, and components are the classes of the transitive closure.
+        max_dist None: every stored entry is kept.  max_dist t: an entry is kept iff its dist <= t (a NaN dist never; +inf keeps
+        every dist that is no NaN, -inf none) -- the components a build with the same k-NN lists and a smaller eps would connect,
+        the single-linkage clusters of the k-NN graph at height t.  An item without a kept entry is its own label.
+        with_info: -> (labels, info), info = {"count" (components), "largest" (items of the largest), "largest_label" (the
+        smallest label of that size), "isolated" (components of one item), "edges_kept" (stored entries kept, both directions
+        as stored), "rounds" (hook-and-compress rounds the device ran)}; all but "rounds" are functions of the graph and t
+        alone.  The labels are integers and exact: no tolerance, no dependence on the schedule.  They are valid input to
+        `groups(labels)`, and `labels == info["largest_label"]` to `subset(...)`.  A NaN or non-numeric max_dist raises
+        ValueError before anything is launched; a feature-mode or row-sharded index raises ValueError."""
+        _need_gl(gl)
+        t = None if max_dist is None else self._components_thresholds(max_dist, single=True)
+        labels = np.empty(max(self.nitems, 1), dtype=np.int32)
+        info = np.zeros(6, dtype=np.int64)
+        _check(_L.as_graph_components(self._h, gl._h, None if t is None else t.ctypes.data, labels.ctypes.data, info.ctypes.data))
+        labels = labels[:self.nitems]
+        return (labels, dict(zip(self._COMPONENTS_KEYS, info.tolist()))) if with_info else labels
+
+    def components_sweep(self, gl: GraphLaplacian, max_dists) -> dict:
+        """Extension: the statistics of `components(gl, t, with_info=True)` for 1 to 64 thresholds -> a dict with the keys of
+        that info, each an ndarray[int64] of shape (T,) in the caller's order (any order, duplicates allowed).  The distinct
+        thresholds run in ascending order on the device, each from the labels of the one before (the kept sets are nested),
+        from ONE build: which eps connects this data, with no k-NN pass.  No labels cross to the host.  "rounds" of a
+        threshold counts the rounds its stage ran from the previous threshold's labels."""
+        _need_gl(gl)
+        t = self._components_thresholds(max_dists)
+        info = np.zeros((t.shape[0], 6), dtype=np.int64)
+        _check(_L.as_graph_components_sweep(self._h, gl._h, t.ctypes.data, t.shape[0], info.ctypes.data))
+        return {k: info[:, j].copy() for j, k in enumerate(self._COMPONENTS_KEYS)}
+
+    def components_counters(self) -> dict:
+        """Extension: `components` / `components_sweep` calls on this space that passed their checks, the thresholds they
+        served (1 for a call without one), the hook and compress launches, and the host's waits (one per round, one per
+        distinct threshold for the statistics)."""
+        return _counters(_L.as_components_counters, self._h, ("calls", "thresholds served", "hook launches", "compress launches", "host waits"))
 
     def _spectral_op(self, gl: GraphLaplacian, op: str, A, B=None, T=None, coef=None, alias: bool = False):
         """Debug: one S21 primitive on host blocks [n, C] (C = 16 or 64) through the launch `eigsh` makes.  op "step": A = V, B = W

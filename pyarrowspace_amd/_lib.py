@@ -64,6 +64,7 @@ SYMBOLS = [
     "as_search_diffuse_solve", "as_search_diffuse_solve_batch", "as_score_diffuse_solve_batch", "as_diffuse_solve_seeds",
     "as_diffuse_solve_counters", "as_diffuse_solve_kernel_us",
     "as_graph_eigs", "as_graph_eigs_counters", "as_graph_eigs_kernel_us", "as_spectral_op", "as_sym_eig_host",
+    "as_graph_components", "as_graph_components_sweep", "as_components_counters", "as_components_kernel_us", "as_graph_csr_dist",
     "as_search_fused", "as_score_fused", "as_fused_counters", "as_fused_kernel_us",
     "as_search_fused_batch", "as_score_fused_batch", "as_fused_batch_counters", "as_fused_batch_kernel_us",
     "as_groups_create", "as_groups_count", "as_groups_free", "as_search_grouped", "as_search_grouped_batch", "as_grouped_counters",
@@ -274,6 +275,11 @@ def load():
         "as_graph_eigs_kernel_us": (f64, [vp, i32]),
         "as_spectral_op": (i32, [vp, vp, i32, i64, i32, vp, vp, vp, vp, vp]),
         "as_sym_eig_host": (i32, [vp, i32, vp, vp]),
+        "as_graph_components": (i32, [vp, vp, vp, vp, vp]),
+        "as_graph_components_sweep": (i32, [vp, vp, vp, i32, vp]),
+        "as_components_counters": (i32, [vp, vp, i32]),
+        "as_components_kernel_us": (f64, [vp, i32]),
+        "as_graph_csr_dist": (i32, [vp, vp, vp, vp]),
         "as_search_fused": (i32, [vp, vp, vp, i64, i64, f64, vp, i32, i32, vp, vp, vp, C.POINTER(i64), vp, vp]),
         "as_score_fused": (i32, [vp, vp, vp, i64, i64, f64, vp, i32, i32, vp, i64, vp, vp, vp]),
         "as_fused_counters": (i32, [vp, vp, i32]),

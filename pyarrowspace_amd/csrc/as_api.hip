@@ -3202,6 +3202,78 @@ as_status as_spectral_op(const as_space* sp, const as_graph* gr, int32_t op, int
 }
 int32_t as_sym_eig_host(const double* a, int32_t n, double* w, double* v) { return sym_eig_host(a, n, w, v); }
 
+// ---- connected components (extension; as_components.hip)
+namespace {
+// what both forms refuse about the graph, before anything is launched: what the raw diffusion form refuses
+as_status components_graph_checks(const char* who, const as_space* sp, const as_graph* gr) {
+    if (gr->lambda_mode == AS_LAMBDA_FEATURE) {
+        set_err("%s: a feature-mode graph (its Laplacian is over the columns) is not supported", who);
+        return AS_EUNSUPPORTED;
+    }
+    AS_TRY(graph_matches(sp, gr, who));
+    if (sp->row_offset != 0 || gr->ncols) {
+        set_err("%s: a shard of a row-sharded index is not supported", who);
+        return AS_EUNSUPPORTED;
+    }
+    return diffuse_graph_checks(who, sp, gr);
+}
+// the call behind the checks: its counters, the lock of the diffusion forms, the run
+as_status components_locked(const char* who, const as_space* sp, const as_graph* gr, const double* ts, int32_t nt, int32_t* labels_host,
+                            as_components_info* info) {
+    sp->components_count[0].fetch_add(1, std::memory_order_relaxed);
+    sp->components_count[1].fetch_add(ts ? nt : 1, std::memory_order_relaxed);
+    int64_t counts[3] = {0, 0, 0};
+    std::lock_guard<std::mutex> lk(sp->fmu);
+    if (hipSetDevice(sp->device) != hipSuccess) {
+        set_err("%s: hipSetDevice failed", who);
+        return AS_EHIP;
+    }
+    const as_status s = components_run(sp, gr, ts, nt, labels_host, info, counts);
+    for (int i = 0; i < 3; ++i) sp->components_count[2 + i].fetch_add(counts[i], std::memory_order_relaxed);
+    return s;
+}
+}  // namespace
+
+as_status as_graph_components(const as_space* sp, const as_graph* gr, const double* max_dist, int32_t* labels_host, as_components_info* info) {
+    const char* who = "as_graph_components";
+    if (!sp || !gr || !labels_host) {
+        set_err("%s: null argument", who);
+        return AS_EINVAL;
+    }
+    if (max_dist && std::isnan(*max_dist)) {
+        set_err("%s: max_dist must not be a NaN", who);
+        return AS_EINVAL;
+    }
+    AS_TRY(components_graph_checks(who, sp, gr));
+    return components_locked(who, sp, gr, max_dist, 1, labels_host, info);
+}
+as_status as_graph_components_sweep(const as_space* sp, const as_graph* gr, const double* max_dists, int32_t nt, as_components_info* info) {
+    const char* who = "as_graph_components_sweep";
+    if (!sp || !gr || !max_dists || !info) {
+        set_err("%s: null argument", who);
+        return AS_EINVAL;
+    }
+    if (nt < 1 || nt > 64) {
+        set_err("%s: the number of thresholds must lie in [1, 64], got %d", who, (int)nt);
+        return AS_EINVAL;
+    }
+    for (int32_t i = 0; i < nt; ++i)
+        if (std::isnan(max_dists[i])) {
+            set_err("%s: max_dists[%d] must not be a NaN", who, (int)i);
+            return AS_EINVAL;
+        }
+    AS_TRY(components_graph_checks(who, sp, gr));
+    return components_locked(who, sp, gr, max_dists, nt, nullptr, info);
+}
+as_status as_components_counters(const as_space* sp, int64_t* out, int32_t n) {
+    return counters_out("as_components_counters", sp, out, n, sp ? sp->components_count : nullptr, 5);
+}
+double as_components_kernel_us(const as_space* sp, int32_t part) {
+    if (!sp) return 0.0;
+    std::lock_guard<std::mutex> lk(sp->fmu);
+    return components_kernel_us(sp->diffuse_ws, part);
+}
+
 as_status as_diffuse_counters(const as_space* sp, int64_t* out, int32_t n) {
     return counters_out("as_diffuse_counters", sp, out, n, sp ? sp->diffuse_count : nullptr, 5);
 }
@@ -3752,6 +3824,27 @@ as_status as_graph_csr(const as_graph* gr, int64_t* indptr, int64_t* indices, do
         }
     }
     indptr[n] = w;
+    return AS_OK;
+}
+
+as_status as_graph_csr_dist(const as_graph* gr, int64_t* indptr, int64_t* indices, double* dist) {
+    if (!gr || !indptr || (gr->nnz > 0 && (!indices || !dist))) {
+        set_err("as_graph_csr_dist: null argument");
+        return AS_EINVAL;
+    }
+    if (gr->lambda_mode == AS_LAMBDA_FEATURE || (gr->nnz > 0 && !gr->dist)) {
+        set_err("as_graph_csr_dist: a feature-mode graph stores no distances");
+        return AS_EUNSUPPORTED;
+    }
+    AS_HIP(hipSetDevice(gr->device));
+    const int64_t n = gr->n, nnz = gr->nnz;
+    AS_HIP(hipMemcpy(indptr, gr->indptr, sizeof(int64_t) * (n + 1), hipMemcpyDeviceToHost));
+    if (nnz) {
+        std::vector<int32_t> col(nnz);
+        AS_HIP(hipMemcpy(col.data(), gr->indices, sizeof(int32_t) * nnz, hipMemcpyDeviceToHost));
+        AS_HIP(hipMemcpy(dist, gr->dist, sizeof(double) * nnz, hipMemcpyDeviceToHost));
+        std::copy(col.begin(), col.end(), indices);
+    }
     return AS_OK;
 }
 

@@ -236,6 +236,10 @@ struct as_space {
     // as_graph_eigs shares diffuse_ws and fmu.  as_graph_eigs_counters: [0] calls that passed their
     // checks, [1] outer iterations, [2] step launches, [3] Gram launches, [4] rotate launches, [5] host waits
     mutable std::atomic<int64_t> eigs_count[6] = {};
+    // as_graph_components / as_graph_components_sweep share diffuse_ws and fmu.
+    // as_components_counters: [0] calls that passed their checks, [1] thresholds served (1 for a call without one), [2] hook
+    // launches, [3] compress launches, [4] host waits
+    mutable std::atomic<int64_t> components_count[5] = {};
 };
 
 struct as_graph {
@@ -1157,5 +1161,12 @@ int sym_eig_host(const double* a, int n, double* w, double* v);
 double spectral_kernel_us(const DiffuseWork* w, int part);
 int64_t spectral_budget();            // "spectral_mib" in bytes
 void set_spectral_mib(int v);         // as_set_tuning("spectral_mib", v): the byte budget of the eigensolver's four blocks; 0: the default (8192 MiB)
+// Connected components (as_components.hip) of the whole graph `gr`, on the diffusion forms' workspace
+// (under sp->fmu), the caller has checked every argument.  ts == null: every stored entry is kept, one stage, info [1]; else nt
+// thresholds (none a NaN), info [nt] in the caller's order: the distinct ones run ascending, each from the last one's labels.
+// labels_host (may be null): the [n] labels of the (last) stage.  counts[0] += hook launches, [1] += compress launches, [2] += host waits.
+as_status components_run(const as_space* sp, const as_graph* gr, const double* ts, int32_t nt, int32_t* labels_host, as_components_info* info,
+                         int64_t* counts);
+double components_kernel_us(const DiffuseWork* w, int part);
 
 }  // namespace as

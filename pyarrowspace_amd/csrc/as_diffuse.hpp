@@ -1,5 +1,6 @@
 // What the diffusion files share (as_diffuse.hip: the S19 recurrence; as_diffuse_solve.hip: the S20 conjugate-gradient solve of
-// its fixed point; as_spectral.hip: the S21 eigenpairs, which use the four blocks and the partials): the work buffers of a space, the column-chunk rule, the sparse seed table and its kernel, and the output
+// its fixed point; as_spectral.hip: the S21 eigenpairs, which use the four blocks and the partials; as_components.hip: the S22
+// connected components, on buffers of their own): the work buffers of a space, the column-chunk rule, the sparse seed table and its kernel, and the output
 // paths (gather, selection on the handle's stream, score pick, raw block).  Defined in as_diffuse.hip.
 #pragma once
 #include <vector>
@@ -46,6 +47,15 @@ struct DiffuseWork {
     // the last call: [0] its wall time; under "diffuse_timing" the device time of [1] steps, [2] Grams, [3] rotates, [4] colnorm2;
     // [5] the host's eigensolver, [6] the host's waits
     double spectral_us[7] = {};
+    // the connected components (S22, as_components.hip): the labels' state, the sizes of the statistics, the words a stage leaves
+    // (as_components.hip: CcStat) and their pinned copy
+    dev_buf<int32_t> cc_parent;   // [n]
+    dev_buf<int32_t> cc_size;     // [n]
+    dev_buf<unsigned long long> cc_stat_d;
+    pin_buf<unsigned long long> cc_stat_h;
+    dev_events<3> cc_ev;          // made by the first timed call
+    // the last call under "diffuse_timing": the device time of [0] its hooks, [1] its compress launches, [2] its statistics; [3] its rounds
+    double cc_us[4] = {};
 };
 
 // the tunings both files honour
