@@ -879,6 +879,33 @@ as_status as_components_counters(const as_space* sp, int64_t* out, int32_t n);
 /* measurement, of the last components call on this space under as_set_tuning("diffuse_timing", 1): part 0 the device microseconds
  * of its hook launches, 1 of its compress launches, 2 of its statistics (sizes and reduction); part 3 its rounds (any timing) */
 double as_components_kernel_us(const as_space* sp, int32_t part);
+/* ---- Extension: minimum spanning forest of the item graph.  The stored CSR of a whole item graph is
+ * used as above.  The weight of an undirected edge {u < v} is the smaller of the dists of its two stored entries, a NaN ignored
+ * (NaN if both are; -0.0 counts as +0.0 and comes back as +0.0; a NaN comes back as the quiet NaN 0x7ff8000000000000): the rule
+ * under which as_graph_components joins u and v at max_dist t iff w <= t.  Edges are ordered by (w ascending with NaN after +inf,
+ * then u, then v); under that order the minimum spanning forest is unique, and it is the answer: u_host, v_host (int32, u < v) and
+ * dist_host (fp64, the bits of the stored value that won), each with room for n - 1 edges; info->edges are written.  sort != 0:
+ * the edges come in the total order (sorted on the host); else in slot order, the edge each root emitted by ascending root id --
+ * a function of the graph alone too.  Sorted, edge number m is the merge from n - m to n - m - 1 single-linkage clusters: the
+ * components at max_dist t number n - #{w <= t}, and the forest's edges with w <= t connect exactly them.
+ * On the device: Boruvka rounds of four launches (row minimum with one 64-bit atomicMin per row, pick, link, compress) until the
+ * host reads that a round found no root with an outgoing entry; rounds <= ceil(log2(largest component)) + 1.  info (may be
+ * NULL): every field but `rounds` is a function of the graph alone, whatever "diffuse_grid_cap", "forest_row_lanes" (8, 16 or 32
+ * lanes per row of the row-minimum kernel) and the order of the atomics.  Refusals and workspace: as as_graph_components. */
+typedef struct as_forest_info {
+    int64_t edges;       /* edges of the forest */
+    int64_t components;  /* n - edges */
+    int64_t rounds;      /* rounds run, the last one (which found nothing) included */
+} as_forest_info;
+as_status as_graph_forest(const as_space* sp, const as_graph* gr, int32_t sort, int32_t* u_host, int32_t* v_host, double* dist_host,
+                          as_forest_info* info);
+/* out[0] calls that passed their checks, [1] rounds, [2] launches (init, weights, four per round, three of the emit), [3] host
+ * waits (one per round, one for the edge count, one for the edges) */
+as_status as_forest_counters(const as_space* sp, int64_t* out, int32_t n);
+/* measurement, of the last forest call on this space: under as_set_tuning("diffuse_timing", 1) the device microseconds of its
+ * part 0 row-minimum, 1 pick, 2 link, 3 compress launches, 4 init and weights, 5 emit; part 6 the host's sort and 7 the rounds
+ * (any timing); part 8 + 4 r + k: launch k (0 .. 3) of round r (0 .. 31) under timing */
+double as_forest_kernel_us(const as_space* sp, int32_t part);
 /* ---- Extension: fused multi-query search.  ONE answer to j >= 1 query vectors, row-major [j][d] in HOST memory,
  * with finite weights w (weights == NULL: 1/j each; negative weights are legal).  s_v(i): the S11 score of item i for vector v
  * with the bits as_score_items_batch writes at [v][i] (lambda_q of every vector from ONE as_search_batch over the j vectors, the

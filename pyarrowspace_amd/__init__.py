@@ -1699,6 +1699,32 @@ class ArrowSpace:
         distinct threshold for the statistics)."""
         return _counters(_L.as_components_counters, self._h, ("calls", "thresholds served", "hook launches", "compress launches", "host waits"))
 
+    def spanning_forest(self, gl: GraphLaplacian, with_info: bool = False, sort: bool = True):
+        """Extension: the minimum spanning forest of the item graph -> (u, v, dist): ndarray[int32], ndarray[int32] with u < v and
+        ndarray[float64], one entry per edge, N - (components) edges.  The graph's stored entries are used (`gl.to_csr_dist()`);
+        the weight of the undirected edge {u, v} is the smaller of its two stored dists, a NaN ignored (NaN if both are; a zero is
+        +0.0): the rule under which `components(max_dist=t)` joins u and v iff w <= t.  Edges are ordered by (w ascending with NaN
+        after +inf, then u, then v); the forest that is minimal under that order is unique and exact: no tolerance, no dependence
+        on the schedule.  sort True: the edges come in that order, so edge number m is the merge that takes the single-linkage
+        hierarchy of the k-NN graph from N - m to N - m - 1 clusters, `N - searchsorted(dist, t, "right")` is `components(t)`'s
+        count for every t (NaN weights sort last), and the edges with w <= t connect exactly its components.  sort False: the
+        device's slot order (by the id of the root that emitted the edge), a function of the graph alone too, without the host's
+        sort.  with_info: -> ((u, v, dist), info), info = {"edges", "components" (= N - edges), "rounds" (Boruvka rounds the
+        device ran)}.  A feature-mode or row-sharded index raises ValueError before anything is launched."""
+        _need_gl(gl)
+        m = max(self.nitems - 1, 1)
+        u, v, dist = np.empty(m, dtype=np.int32), np.empty(m, dtype=np.int32), np.empty(m, dtype=np.float64)
+        info = np.zeros(3, dtype=np.int64)
+        _check(_L.as_graph_forest(self._h, gl._h, 1 if sort else 0, u.ctypes.data, v.ctypes.data, dist.ctypes.data, info.ctypes.data))
+        m = int(info[0])
+        edges = (u[:m].copy(), v[:m].copy(), dist[:m].copy())
+        return (edges, dict(zip(("edges", "components", "rounds"), info.tolist()))) if with_info else edges
+
+    def spanning_forest_counters(self) -> dict:
+        """Extension: `spanning_forest` calls on this space that passed their checks, the rounds and launches they ran and the
+        host's waits (one per round, one for the edge count, one for the edges)."""
+        return _counters(_L.as_forest_counters, self._h, ("calls", "rounds", "launches", "host waits"))
+
     def _spectral_op(self, gl: GraphLaplacian, op: str, A, B=None, T=None, coef=None, alias: bool = False):
         """Debug: one S21 primitive on host blocks [n, C] (C = 16 or 64) through the launch `eigsh` makes.  op "step": A = V, B = W
         (None with g == 0), coef = (a, b, g), alias: the result is written over W's block; "gram": A^T B (B None: A^T A) ->

@@ -3274,6 +3274,35 @@ double as_components_kernel_us(const as_space* sp, int32_t part) {
     return components_kernel_us(sp->diffuse_ws, part);
 }
 
+// ---- minimum spanning forest (extension; as_forest.hip)
+as_status as_graph_forest(const as_space* sp, const as_graph* gr, int32_t sort, int32_t* u_host, int32_t* v_host, double* dist_host,
+                          as_forest_info* info) {
+    const char* who = "as_graph_forest";
+    if (!sp || !gr || !u_host || !v_host || !dist_host) {
+        set_err("%s: null argument", who);
+        return AS_EINVAL;
+    }
+    AS_TRY(components_graph_checks(who, sp, gr));
+    sp->forest_count[0].fetch_add(1, std::memory_order_relaxed);
+    int64_t counts[3] = {0, 0, 0};
+    std::lock_guard<std::mutex> lk(sp->fmu);
+    if (hipSetDevice(sp->device) != hipSuccess) {
+        set_err("%s: hipSetDevice failed", who);
+        return AS_EHIP;
+    }
+    const as_status s = forest_run(sp, gr, sort, u_host, v_host, dist_host, info, counts);
+    for (int i = 0; i < 3; ++i) sp->forest_count[1 + i].fetch_add(counts[i], std::memory_order_relaxed);
+    return s;
+}
+as_status as_forest_counters(const as_space* sp, int64_t* out, int32_t n) {
+    return counters_out("as_forest_counters", sp, out, n, sp ? sp->forest_count : nullptr, 4);
+}
+double as_forest_kernel_us(const as_space* sp, int32_t part) {
+    if (!sp) return 0.0;
+    std::lock_guard<std::mutex> lk(sp->fmu);
+    return forest_kernel_us(sp->diffuse_ws, part);
+}
+
 as_status as_diffuse_counters(const as_space* sp, int64_t* out, int32_t n) {
     return counters_out("as_diffuse_counters", sp, out, n, sp ? sp->diffuse_count : nullptr, 5);
 }

@@ -240,6 +240,9 @@ struct as_space {
     // as_components_counters: [0] calls that passed their checks, [1] thresholds served (1 for a call without one), [2] hook
     // launches, [3] compress launches, [4] host waits
     mutable std::atomic<int64_t> components_count[5] = {};
+    // as_graph_forest shares diffuse_ws and fmu.  as_forest_counters: [0] calls that passed their
+    // checks, [1] rounds, [2] launches, [3] host waits
+    mutable std::atomic<int64_t> forest_count[4] = {};
 };
 
 struct as_graph {
@@ -1168,5 +1171,12 @@ void set_spectral_mib(int v);         // as_set_tuning("spectral_mib", v): the b
 as_status components_run(const as_space* sp, const as_graph* gr, const double* ts, int32_t nt, int32_t* labels_host, as_components_info* info,
                          int64_t* counts);
 double components_kernel_us(const DiffuseWork* w, int part);
+// Minimum spanning forest (as_forest.hip) of the whole graph `gr`, on the diffusion forms' workspace
+// (under sp->fmu), the caller has checked every argument.  u_host, v_host, dist_host: room for n - 1 edges; sort != 0: the host
+// orders them by (w, u, v), else they stay in slot order.  counts[0] += rounds, [1] += launches, [2] += host waits.
+as_status forest_run(const as_space* sp, const as_graph* gr, int sort, int32_t* u_host, int32_t* v_host, double* dist_host, as_forest_info* info,
+                     int64_t* counts);
+double forest_kernel_us(const DiffuseWork* w, int part);
+void set_forest_row_lanes(int v);     // as_set_tuning("forest_row_lanes", v): 8, 16 or 32 lanes per row of the forest's rowmin kernel; else 16.  Results never depend on it
 
 }  // namespace as

@@ -1,6 +1,6 @@
 // What the diffusion files share (as_diffuse.hip: the S19 recurrence; as_diffuse_solve.hip: the S20 conjugate-gradient solve of
 // its fixed point; as_spectral.hip: the S21 eigenpairs, which use the four blocks and the partials; as_components.hip: the S22
-// connected components, on buffers of their own): the work buffers of a space, the column-chunk rule, the sparse seed table and its kernel, and the output
+// connected components and as_forest.hip: the S23 minimum spanning forest, on buffers of their own): the work buffers of a space, the column-chunk rule, the sparse seed table and its kernel, and the output
 // paths (gather, selection on the handle's stream, score pick, raw block).  Defined in as_diffuse.hip.
 #pragma once
 #include <vector>
@@ -21,6 +21,7 @@ constexpr int DIF_SOLVE_MIB_DEFAULT = 2 * DIF_MIB_DEFAULT;
 constexpr int DIF_SOLVE_COLS = 64;        // the stride of the solve's per-column scalars: the widest chunk
 // "spectral_mib", the budget of the eigensolver's four blocks: 64 columns up to 4M rows.  A choice, not a measurement.
 constexpr int SPC_MIB_DEFAULT = 8192;
+constexpr int FR_TIMED_ROUNDS = 32;      // rounds of a forest call whose four launches keep their own times under "diffuse_timing"
 
 struct DiffuseWork {
     int device = 0;
@@ -56,6 +57,18 @@ struct DiffuseWork {
     dev_events<3> cc_ev;          // made by the first timed call
     // the last call under "diffuse_timing": the device time of [0] its hooks, [1] its compress launches, [2] its statistics; [3] its rounds
     double cc_us[4] = {};
+    // the minimum spanning forest (S23, as_forest.hip): the entries' weight images; the 64-bit words of the rows, roots, slots and
+    // output with the emit's chunk counts behind them; parent, hook, the rows' candidate columns and the output's ids; the flag
+    // and edge count (as_forest.hip: FrStat) and their pinned copy
+    dev_buf<unsigned long long> fr_wkey;    // [nnz]
+    dev_buf<unsigned long long> fr_words;   // [6 n + ceil(n / 256)]
+    dev_buf<int32_t> fr_ints;               // [5 n]
+    dev_buf<unsigned long long> fr_stat_d;
+    pin_buf<unsigned long long> fr_stat_h;
+    dev_events<5> fr_ev;                    // made by the first timed call
+    // the last call: under "diffuse_timing" the device time of its [0] rowmin, [1] pick, [2] link, [3] compress launches, [4] init
+    // and weights, [5] emit; [6] the host's sort, [7] its rounds (any timing); [8 + 4 r + k] launch k of round r under timing
+    double fr_us[8 + 4 * FR_TIMED_ROUNDS] = {};
 };
 
 // the tunings both files honour

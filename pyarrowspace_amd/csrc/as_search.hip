@@ -3683,6 +3683,10 @@ int32_t as_set_tuning(const char* key, int32_t value) {
         set_diffuse_grid_cap(value);
         return 0;
     }
+    if (key && !strcmp(key, "forest_row_lanes")) {
+        set_forest_row_lanes(value);
+        return 0;
+    }
     if (key && !strcmp(key, "fused_timing")) {
         set_fused_timing(value);
         return 0;
