@@ -906,6 +906,40 @@ as_status as_forest_counters(const as_space* sp, int64_t* out, int32_t n);
  * part 0 row-minimum, 1 pick, 2 link, 3 compress launches, 4 init and weights, 5 emit; part 6 the host's sort and 7 the rounds
  * (any timing); part 8 + 4 r + k: launch k (0 .. 3) of round r (0 .. 31) under timing */
 double as_forest_kernel_us(const as_space* sp, int32_t part);
+/* ---- Extension: shortest paths over the item graph.  The stored CSR of a whole item graph is used
+ * with as_graph_forest's weights: the undirected edge {u, v} weighs the smaller of its two stored dists, a NaN ignored, -0.0 as
+ * +0.0; an edge whose weight is a NaN or negative is never crossed.  Column i has the sources ids_host[offsets_host[i] ..
+ * offsets_host[i + 1]) (distinct, inside [0, n)) at the offsets dist_host[..] (finite, >= 0; none: an empty set, +inf everywhere).
+ * d[v] is the minimum over the sources s and the paths s = p0 .. pm = v of fl(.. fl(fl(off_s + w1) + w2) .. + wm), +inf where no
+ * path leads: the least fixed point of d[v] = min(d[v], fl(d[u] + w)), which is unique because fl(x + w) is monotone in x and never
+ * below x -- the bits of a Dijkstra with the same add, whatever the schedule, "diffuse_grid_cap", "diffuse_cols",
+ * "geodesic_row_lanes" (8, 16 or 32 lanes per frontier row), "geodesic_lds_rows" (frontier rows one block keeps in LDS; 0: no such
+ * kernel; < 0: the default) and as_set_geodesic_delta (the width of a near / far bucket; 0: one bucket).  cutoff (NULL: none; a NaN
+ * is refused): a candidate above it is never stored, a source's own offset included; every d <= cutoff has the bits of the uncut
+ * answer, every other entry is +inf.
+ * as_geodesic_seeds: pick_ids_host NULL: out_d [b][n]; else out_d [b][m], d at those ids (only they cross).  info (may be NULL;
+ * int64 [2 + 2 b]): [0] column chunks, [1] words lowered, [2 ..) the rounds of every chunk, [2 + b ..) per column the items reached
+ * (the whole-block form only).
+ * as_search_geodesic: the first `seeds` (1 .. topk) hits of as_search (with a subset: as_search_subset) are the sources at offset
+ * 0; the answer is the first min(topk, |subset|) REACHED items of the subset by (d ascending, id ascending) as (id, d).  The batched
+ * form takes its lambda_q from one as_search_batch; a query whose lambda_q is 0 gets an empty list and AS_EZEROLAMBDA in out_status,
+ * the others are served.  Refusals and workspace: as as_graph_components. */
+as_status as_geodesic_seeds(const as_space* sp, const as_graph* gr, const int64_t* ids_host, const double* dist_host, const int64_t* offsets_host,
+                            int64_t b, const double* cutoff, const int64_t* pick_ids_host, int64_t m, double* out_d, int64_t* info);
+as_status as_search_geodesic(const as_space* sp, const as_graph* gr, const double* query, int64_t d, double tau, int64_t seeds,
+                             const double* cutoff, const as_subset* sub, int64_t* out_idx, double* out_d, int64_t* out_len, double* out_lambda_q);
+as_status as_search_geodesic_batch(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau, int64_t seeds,
+                                   const double* cutoff, const as_subset* sub, int64_t* out_idx, double* out_d, int64_t* out_len,
+                                   double* out_lambda_q, int32_t* out_status);
+/* [0] calls that passed their checks, [1] route searches run, [2] column chunks, [3] rounds, [4] launches, [5] host waits */
+as_status as_geodesic_counters(const as_space* sp, int64_t* out, int32_t n);
+/* measurement, of the last shortest-paths call on this space: under as_set_tuning("diffuse_timing", 1) the device microseconds of
+ * its part 0 weights launch, 1 one-block LDS launches, 2 grid-wide relax launches, 3 filter launches, 4 pull rounds; 5 the host's
+ * microseconds in the emit; any timing: 6 weights launches (0: the images were kept from the last call on this graph), 7 rounds,
+ * 8 CSR entries the pull rounds scanned (8 bytes each: the column and its stamp), 9 one-block launches, 10 grid-wide relax launches,
+ * 11 CSR entries of the rows the pull rounds relaxed (12 more bytes each, and a gathered segment of 8 C bytes) */
+double as_geodesic_kernel_us(const as_space* sp, int32_t part);
+void as_set_geodesic_delta(double v);
 /* ---- Extension: fused multi-query search.  ONE answer to j >= 1 query vectors, row-major [j][d] in HOST memory,
  * with finite weights w (weights == NULL: 1/j each; negative weights are legal).  s_v(i): the S11 score of item i for vector v
  * with the bits as_score_items_batch writes at [v][i] (lambda_q of every vector from ONE as_search_batch over the j vectors, the

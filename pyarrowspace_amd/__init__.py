@@ -1725,6 +1725,126 @@ class ArrowSpace:
         host's waits (one per round, one for the edge count, one for the edges)."""
         return _counters(_L.as_forest_counters, self._h, ("calls", "rounds", "launches", "host waits"))
 
+    @staticmethod
+    def _geodesic_cutoff(cutoff):
+        """None, or the cutoff as a ctypes double; a NaN or a non-number raises ValueError."""
+        if cutoff is None:
+            return None
+        if isinstance(cutoff, (bool, np.bool_)) or not isinstance(cutoff, (int, float, np.integer, np.floating)):
+            raise ValueError(f"cutoff must be None or a number, got {cutoff!r}")
+        if np.isnan(cutoff):
+            raise ValueError("cutoff must not be a NaN")
+        return C.c_double(float(cutoff))
+
+    @classmethod
+    def _geodesic_sources(cls, sources, nitems: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """B sources, each an item id (offset +0.0) or a pair (ids, offsets), in the flat form of `_diffuse_seeds`; its checks,
+        and no offset below zero."""
+        if isinstance(sources, (str, bytes)) or not hasattr(sources, "__len__"):
+            raise ValueError(f"argument 'sources': expected a sequence of item ids or pairs (ids, offsets), got {sources!r}")
+        pairs = []
+        for i, s in enumerate(sources):
+            if isinstance(s, (int, np.integer)) and not isinstance(s, (bool, np.bool_)):
+                pairs.append((np.array([s], dtype=np.int64), np.zeros(1)))
+            elif np.ndim(s) == 0:
+                raise TypeError(f"argument 'sources': entry {i}: expected an integer item id or a pair (ids, offsets), got {s!r}")
+            else:
+                pairs.append(s)
+        ids, offs, starts = cls._diffuse_seeds(pairs, nitems)
+        if (offs < 0.0).any():
+            raise ValueError("argument 'sources': an offset is below zero")
+        return ids, offs, starts
+
+    def _geodesic(self, gl, sources, cutoff, pick, with_info):
+        _need_gl(gl)
+        cut = self._geodesic_cutoff(cutoff)
+        ids, offs, starts = self._geodesic_sources(sources, self.nitems)
+        b = starts.shape[0] - 1
+        m = self.nitems if pick is None else pick.shape[0]
+        out = np.empty((b, m), dtype=np.float64)
+        info = np.zeros(2 + 2 * b, dtype=np.int64) if with_info else None   # (asked for: the host counts the reached items)
+        vp = C.c_void_p
+        st = _L.as_geodesic_seeds(self._h, gl._h, ids.ctypes.data_as(vp), offs.ctypes.data_as(vp), starts.ctypes.data_as(vp), b,
+                                  None if cut is None else C.byref(cut), None if pick is None else pick.ctypes.data_as(vp), m,
+                                  out.ctypes.data_as(vp), None if info is None else info.ctypes.data_as(vp))
+        _check(st)
+        if not with_info:
+            return out
+        chunks = int(info[0])
+        return out, {"rounds": info[2:2 + chunks].tolist(), "reached": info[2 + b:2 + 2 * b].copy(), "relaxations": int(info[1])}
+
+    def shortest_paths(self, gl: GraphLaplacian, sources, cutoff=None, with_info: bool = False):
+        """Extension: shortest-path (geodesic) distances over the item graph -> ndarray[float64] of shape (B, nitems): row b holds
+        every item's distance from the source set `sources[b]` along the graph's stored entries (`gl.to_csr_dist()`), +inf where
+        no path leads.  The weight of the undirected edge {u, v} is `spanning_forest`'s: the smaller of its two stored dists, a
+        NaN ignored, -0.0 as +0.0; an edge whose weight is NaN or negative is never crossed.  A source is an item id (offset 0)
+        or a pair (ids, offsets) in the form of `diffuse`'s seeds: distinct ids inside [0, nitems), offsets finite and >= 0
+        (ValueError; a float or boolean dtype of ids: TypeError); an empty set gives +inf everywhere.  d[v] is the minimum over
+        the sources s and the paths s = p0 .. pm = v of fl(.. fl(fl(offset_s + w1) + w2) .. + wm): exactly what a Dijkstra with
+        the same float64 add returns, bit for bit, with no dependence on the schedule.  cutoff (None or a number, a NaN raises
+        ValueError): a distance above it is never stored, a source's own offset included -- every d <= cutoff has the bits of
+        the uncut answer, every other entry is +inf, and the work is bounded to that geodesic ball.  with_info: -> (d, info),
+        info = {"rounds" (per column chunk), "reached" (items with a finite d, per row), "relaxations" (words lowered on the
+        device; depends on the schedule)}.  One source column runs a frontier (push) search, 2 or more run in chunks of 16 or 64
+        columns that share every pass over the CSR.  The whole B x nitems block crosses to the host: use `score_geodesic` or
+        `search_geodesic` where a few entries are wanted.  A feature-mode or row-sharded index raises ValueError."""
+        return self._geodesic(gl, sources, cutoff, None, with_info)
+
+    def score_geodesic(self, gl: GraphLaplacian, sources, ids, cutoff=None) -> np.ndarray:
+        """Extension: `shortest_paths` at the listed ids -> ndarray[float64] of shape (B, len(ids)), the caller's order, duplicates
+        kept.  The nitems-wide block stays on the device: B x len(ids) doubles cross."""
+        return self._geodesic(gl, sources, cutoff, _item_ids(ids, self.nitems, "ids"), False)
+
+    @staticmethod
+    def _geodesic_seeds(seeds, topk: int) -> int:
+        if isinstance(seeds, (bool, np.bool_)) or not isinstance(seeds, (int, np.integer)) or not 1 <= seeds <= topk:
+            raise ValueError(f"seeds must be an integer in [1, topk = {topk}], got {seeds!r}")
+        return int(seeds)
+
+    def search_geodesic(self, item, gl: GraphLaplacian, tau: float, seeds: int = 1, cutoff=None, subset=None):
+        """Extension: geodesic search -> list[(index, d)]: the first min(topk, |subset|) REACHABLE items of the subset (None: every
+        item) by (d ascending, index ascending), d the `shortest_paths` distance from the first `seeds` (1 <= seeds <= topk, else
+        ValueError) hits of `search` (with a subset: of `search_subset`), each at offset 0: the items nearest to the query's best
+        hits ALONG the manifold the k-NN graph samples, where `search_diffuse` ranks by a soft proximity.  The subset restricts
+        the sources and the answer, not the paths.  cutoff as in `shortest_paths`.  Costs one ordinary search (a query whose
+        lambda_q is 0 panics as there), a frontier search on the device and one exact selection there: only the list crosses."""
+        _need_gl(gl)
+        q = self._query(item)
+        seeds, cut = self._geodesic_seeds(seeds, int(gl.graph_params["topk"])), self._geodesic_cutoff(cutoff)
+        sub = self._as_subset(subset, optional=True)
+        n = max(self._hits_bound(gl, sub), 1)
+        idx = np.empty(n, dtype=np.int64)
+        d = np.empty(n, dtype=np.float64)
+        ln, lq = C.c_int64(0), C.c_double(0.0)
+        st = _L.as_search_geodesic(self._h, gl._h, q.ctypes.data, q.shape[0], float(tau), seeds, None if cut is None else C.byref(cut),
+                                   _handle(sub), idx.ctypes.data, d.ctypes.data, C.byref(ln), C.byref(lq))
+        _check(st)
+        return list(zip(idx[:ln.value].tolist(), d[:ln.value].tolist()))
+
+    def search_batch_geodesic(self, items, gl: GraphLaplacian, tau: float, seeds: int = 1, cutoff=None, subset=None):
+        """Extension: batched geodesic search, B queries [B, D] -> list of B lists; list i is `search_geodesic` from the hits
+        `search_batch` (with a subset: `search_batch_subset`) gives query i.  A query whose lambda_q is 0 gets an empty list, the
+        others are served.  Costs one batched search, then per chunk of 16 or 64 queries the pull rounds over the CSR that serve
+        the whole chunk, and one selection."""
+        _need_gl(gl)
+        Q = _queries_2d(items)
+        seeds, cut = self._geodesic_seeds(seeds, int(gl.graph_params["topk"])), self._geodesic_cutoff(cutoff)
+        sub = self._as_subset(subset, optional=True)
+        b = Q.shape[0]
+        kk = self._hits_bound(gl, sub)
+        (idx, d, ln), stt = _hit_buffers(b, kk), _statuses(b)
+        vp = C.c_void_p
+        st = _L.as_search_geodesic_batch(self._h, gl._h, Q.ctypes.data_as(vp), b, Q.shape[1], float(tau), seeds,
+                                         None if cut is None else C.byref(cut), _handle(sub), idx.ctypes.data_as(vp), d.ctypes.data_as(vp),
+                                         ln.ctypes.data_as(vp), None, stt.ctypes.data_as(vp))
+        _check(st)
+        return _hit_lists(idx, d, ln, b, kk)
+
+    def geodesic_counters(self) -> dict:
+        """Extension: shortest-path calls on this space that passed their checks, the route searches they ran (single or
+        batched), the column chunks, the rounds, the launches and the host's waits."""
+        return _counters(_L.as_geodesic_counters, self._h, ("calls", "route searches", "column chunks", "rounds", "launches", "host waits"))
+
     def _spectral_op(self, gl: GraphLaplacian, op: str, A, B=None, T=None, coef=None, alias: bool = False):
         """Debug: one S21 primitive on host blocks [n, C] (C = 16 or 64) through the launch `eigsh` makes.  op "step": A = V, B = W
         (None with g == 0), coef = (a, b, g), alias: the result is written over W's block; "gram": A^T B (B None: A^T A) ->

@@ -66,6 +66,8 @@ SYMBOLS = [
     "as_graph_eigs", "as_graph_eigs_counters", "as_graph_eigs_kernel_us", "as_spectral_op", "as_sym_eig_host",
     "as_graph_components", "as_graph_components_sweep", "as_components_counters", "as_components_kernel_us", "as_graph_csr_dist",
     "as_graph_forest", "as_forest_counters", "as_forest_kernel_us",
+    "as_geodesic_seeds", "as_search_geodesic", "as_search_geodesic_batch", "as_geodesic_counters", "as_geodesic_kernel_us",
+    "as_set_geodesic_delta",
     "as_search_fused", "as_score_fused", "as_fused_counters", "as_fused_kernel_us",
     "as_search_fused_batch", "as_score_fused_batch", "as_fused_batch_counters", "as_fused_batch_kernel_us",
     "as_groups_create", "as_groups_count", "as_groups_free", "as_search_grouped", "as_search_grouped_batch", "as_grouped_counters",
@@ -284,6 +286,12 @@ def load():
         "as_graph_forest": (i32, [vp, vp, i32, vp, vp, vp, vp]),
         "as_forest_counters": (i32, [vp, vp, i32]),
         "as_forest_kernel_us": (f64, [vp, i32]),
+        "as_geodesic_seeds": (i32, [vp, vp, vp, vp, vp, i64, vp, vp, i64, vp, vp]),
+        "as_search_geodesic": (i32, [vp, vp, vp, i64, f64, i64, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(f64)]),
+        "as_search_geodesic_batch": (i32, [vp, vp, vp, i64, i64, f64, i64, vp, vp, vp, vp, vp, vp, vp]),
+        "as_geodesic_counters": (i32, [vp, vp, i32]),
+        "as_geodesic_kernel_us": (f64, [vp, i32]),
+        "as_set_geodesic_delta": (None, [f64]),
         "as_search_fused": (i32, [vp, vp, vp, i64, i64, f64, vp, i32, i32, vp, vp, vp, C.POINTER(i64), vp, vp]),
         "as_score_fused": (i32, [vp, vp, vp, i64, i64, f64, vp, i32, i32, vp, i64, vp, vp, vp]),
         "as_fused_counters": (i32, [vp, vp, i32]),

@@ -2896,13 +2896,14 @@ as_status search_diffuse_impl(const char* who, const as_space* sp, const as_grap
     return c.fail(diffuse_locked(who, sp, gr, dc));
 }
 
-// the pools of a batched form (ONE batched search of the route over all b queries), as seeds; served[i] = 0: a zero lambda_q
-as_status diffuse_batch_pools(const char* who, const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau,
-                              const DiffuseSpec& ds, const as_subset* sub, double* out_lambda_q, int32_t* out_status, std::vector<int64_t>& offs,
-                              std::vector<int64_t>& ids, std::vector<double>& vals, std::vector<int32_t>& served) {
+// the pools of a batched form (ONE batched search of the route over all b queries, counted in *searches): the hit lists at stride
+// *kks; served[i] = 0 and plen[i] = 0: a zero lambda_q
+as_status batch_pools(const char* who, const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau,
+                      std::atomic<int64_t>* searches, const as_subset* sub, double* out_lambda_q, int32_t* out_status, std::vector<int64_t>& pidx,
+                      std::vector<double>& psc, std::vector<int64_t>& plen, std::vector<int32_t>& served, int64_t* kks_out) {
     const int64_t kks = std::max<int64_t>(hits_bound(sp, gr, sub ? sub->m : sp->n), 1);
-    std::vector<int64_t> pidx, plen;
-    std::vector<double> psc, lq;
+    *kks_out = kks;
+    std::vector<double> lq;
     std::vector<int32_t> st;
     try {
         pidx.resize((size_t)(b * kks));
@@ -2915,7 +2916,7 @@ as_status diffuse_batch_pools(const char* who, const as_space* sp, const as_grap
         set_err("%s: out of host memory for %lld queries", who, (long long)b);
         return AS_ENOMEM;
     }
-    ds.count(sp)[1].fetch_add(1, std::memory_order_relaxed);
+    searches->fetch_add(1, std::memory_order_relaxed);
     AS_TRY(sub ? as_search_subset_batch(sp, gr, queries, b, d, tau, sub, pidx.data(), psc.data(), plen.data(), lq.data(), st.data())
                : as_search_batch(sp, gr, queries, b, d, tau, pidx.data(), psc.data(), plen.data(), lq.data(), st.data()));
     for (int64_t i = 0; i < b; ++i) {
@@ -2926,6 +2927,16 @@ as_status diffuse_batch_pools(const char* who, const as_space* sp, const as_grap
             served[i] = 0;
         }
     }
+    return AS_OK;
+}
+// ... as the seeds of S19
+as_status diffuse_batch_pools(const char* who, const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau,
+                              const DiffuseSpec& ds, const as_subset* sub, double* out_lambda_q, int32_t* out_status, std::vector<int64_t>& offs,
+                              std::vector<int64_t>& ids, std::vector<double>& vals, std::vector<int32_t>& served) {
+    std::vector<int64_t> pidx, plen;
+    std::vector<double> psc;
+    int64_t kks = 1;
+    AS_TRY(batch_pools(who, sp, gr, queries, b, d, tau, &ds.count(sp)[1], sub, out_lambda_q, out_status, pidx, psc, plen, served, &kks));
     return diffuse_pool_seeds(who, pidx.data(), psc.data(), plen.data(), kks, b, offs, ids, vals);
 }
 
@@ -2988,21 +2999,14 @@ as_status score_diffuse_batch_impl(const char* who, const as_space* sp, const as
     return diffuse_locked(who, sp, gr, dc);
 }
 
-as_status diffuse_seeds_impl(const char* who, const as_space* sp, const as_graph* gr, const int64_t* ids_host, const double* values_host,
-                             const int64_t* offsets_host, int64_t b, const DiffuseSpec& ds, double* out_f) {
-    if (!sp || !gr || b < 0 || !offsets_host || (b > 0 && !out_f)) {
-        set_err("%s: null argument", who);
-        return AS_EINVAL;
-    }
-    AS_TRY(diffuse_param_checks(who, sp, gr, ds));
-    if (offsets_host[b] > 0 && (!ids_host || !values_host)) {
-        set_err("%s: null argument", who);
-        return AS_EINVAL;
-    }
-    AS_TRY(lists_checks(who, sp, ids_host, offsets_host, b));   // the offsets, the total, every id
+// the seed lists of a raw form: the offsets, the total, every id; finite values (nonneg: and none below zero); distinct ids per query
+as_status seed_lists_checks(const char* who, const as_space* sp, const int64_t* ids_host, const double* values_host, const int64_t* offsets_host,
+                            int64_t b, bool nonneg) {
+    AS_TRY(lists_checks(who, sp, ids_host, offsets_host, b));
     for (int64_t e = 0; e < offsets_host[b]; ++e)
-        if (!std::isfinite(values_host[e])) {
-            set_err("%s: seed value %lld is not finite", who, (long long)e);
+        if (!std::isfinite(values_host[e]) || (nonneg && values_host[e] < 0.0)) {
+            if (nonneg) set_err("%s: seed offset %lld is not finite and >= 0", who, (long long)e);
+            else set_err("%s: seed value %lld is not finite", who, (long long)e);
             return AS_EINVAL;
         }
     try {
@@ -3019,6 +3023,21 @@ as_status diffuse_seeds_impl(const char* who, const as_space* sp, const as_graph
         set_err("%s: out of host memory for the seeds", who);
         return AS_ENOMEM;
     }
+    return AS_OK;
+}
+
+as_status diffuse_seeds_impl(const char* who, const as_space* sp, const as_graph* gr, const int64_t* ids_host, const double* values_host,
+                             const int64_t* offsets_host, int64_t b, const DiffuseSpec& ds, double* out_f) {
+    if (!sp || !gr || b < 0 || !offsets_host || (b > 0 && !out_f)) {
+        set_err("%s: null argument", who);
+        return AS_EINVAL;
+    }
+    AS_TRY(diffuse_param_checks(who, sp, gr, ds));
+    if (offsets_host[b] > 0 && (!ids_host || !values_host)) {
+        set_err("%s: null argument", who);
+        return AS_EINVAL;
+    }
+    AS_TRY(seed_lists_checks(who, sp, ids_host, values_host, offsets_host, b, false));
     AS_TRY(graph_matches(sp, gr, who));
     if (sp->row_offset != 0 || gr->ncols) {
         set_err("%s: a shard of a row-sharded index is not supported", who);
@@ -3302,6 +3321,202 @@ double as_forest_kernel_us(const as_space* sp, int32_t part) {
     std::lock_guard<std::mutex> lk(sp->fmu);
     return forest_kernel_us(sp->diffuse_ws, part);
 }
+
+// ---- graph shortest paths (extension; as_geodesic.hip)
+namespace {
+// cutoff (may be null: none) as the number the kernels compare with
+as_status geodesic_cutoff(const char* who, const double* cutoff, double* out) {
+    *out = cutoff ? *cutoff : std::numeric_limits<double>::infinity();
+    if (std::isnan(*out)) {
+        set_err("%s: cutoff must not be a NaN", who);
+        return AS_EINVAL;
+    }
+    return AS_OK;
+}
+// the run and its output, under sp->fmu
+as_status geodesic_locked(const char* who, const as_space* sp, const as_graph* gr, const GeodesicCall& gc) {
+    int64_t counts[4] = {0, 0, 0, 0};
+    std::lock_guard<std::mutex> lk(sp->fmu);
+    if (hipSetDevice(sp->device) != hipSuccess) {
+        set_err("%s: hipSetDevice failed", who);
+        return AS_EHIP;
+    }
+    const as_status s = geodesic_run(sp, gr, gc, counts);
+    for (int i = 0; i < 4; ++i) sp->geodesic_count[2 + i].fetch_add(counts[i], std::memory_order_relaxed);
+    return s;
+}
+// what the search forms refuse before anything is launched, the route's search included
+as_status geodesic_search_checks(const char* who, const as_space* sp, const as_graph* gr, int64_t d, double tau, int64_t seeds,
+                                 const as_subset* sub) {
+    if (gr->lambda_mode == AS_LAMBDA_FEATURE) {
+        set_err("%s: a feature-mode graph (its Laplacian is over the columns) is not supported", who);
+        return AS_EUNSUPPORTED;
+    }
+    if (seeds < 1 || seeds > gr->gp.topk) {
+        set_err("%s: seeds must lie in [1, topk = %lld], got %lld", who, (long long)gr->gp.topk, (long long)seeds);
+        return AS_EINVAL;
+    }
+    AS_TRY(own_subset(who, sp, sub));
+    AS_TRY(subset_checks(who, sp, gr, d, &tau, 1));
+    return diffuse_graph_checks(who, sp, gr);
+}
+// the sources of S24 from b hit lists at stride kk: the first `seeds` entries of each, at offset 0
+as_status geodesic_sources(const char* who, const int64_t* pidx, const int64_t* plen, int64_t kk, int64_t b, int64_t seeds,
+                           std::vector<int64_t>& offs, std::vector<int64_t>& ids, std::vector<double>& vals) {
+    try {
+        offs.assign((size_t)b + 1, 0);
+        for (int64_t i = 0; i < b; ++i) {
+            for (int64_t p = 0; p < std::min(plen[i], seeds); ++p) ids.push_back(pidx[i * kk + p]);
+            offs[(size_t)i + 1] = (int64_t)ids.size();
+        }
+        vals.assign(ids.size(), 0.0);
+    } catch (const std::bad_alloc&) {
+        set_err("%s: out of host memory for the sources of %lld queries", who, (long long)b);
+        return AS_ENOMEM;
+    }
+    return AS_OK;
+}
+// a selected list of (id, -d), unreached items (-inf) last -> (id, d) of the reached ones
+void geodesic_list_out(int64_t* idx, double* score, int64_t* len) {
+    int64_t keep = 0;
+    while (keep < *len && score[keep] != -std::numeric_limits<double>::infinity()) {
+        score[keep] = 0.0 - score[keep];   // (-0.0 back to +0.0)
+        ++keep;
+    }
+    *len = keep;
+}
+}  // namespace
+
+as_status as_geodesic_seeds(const as_space* sp, const as_graph* gr, const int64_t* ids_host, const double* dist_host, const int64_t* offsets_host,
+                            int64_t b, const double* cutoff, const int64_t* pick_ids_host, int64_t m, double* out_d, int64_t* info) {
+    const char* who = "as_geodesic_seeds";
+    if (!sp || !gr || b < 0 || m < 0 || !offsets_host || (pick_ids_host ? (b > 0 && m > 0 && !out_d) : (b > 0 && !out_d))) {
+        set_err("%s: null argument", who);
+        return AS_EINVAL;
+    }
+    double cut = 0.0;
+    AS_TRY(geodesic_cutoff(who, cutoff, &cut));
+    if (gr->lambda_mode == AS_LAMBDA_FEATURE) {
+        set_err("%s: a feature-mode graph (its Laplacian is over the columns) is not supported", who);
+        return AS_EUNSUPPORTED;
+    }
+    if (offsets_host[b] > 0 && (!ids_host || !dist_host)) {
+        set_err("%s: null argument", who);
+        return AS_EINVAL;
+    }
+    AS_TRY(seed_lists_checks(who, sp, ids_host, dist_host, offsets_host, b, true));
+    std::vector<int32_t> ids32;
+    if (pick_ids_host) {
+        AS_TRY(ids_in_range(who, sp, pick_ids_host, m));
+        AS_TRY(checked_ids(who, pick_ids_host, m, ids32));
+    }
+    AS_TRY(components_graph_checks(who, sp, gr));
+    sp->geodesic_count[0].fetch_add(1, std::memory_order_relaxed);
+    if (info)
+        for (int64_t i = 0; i < 2 + 2 * b; ++i) info[i] = 0;
+    if (b == 0 || (pick_ids_host && m == 0)) return AS_OK;
+    GeodesicCall gc;
+    gc.dc.b = b; gc.dc.offs = offsets_host; gc.dc.ids = ids_host; gc.dc.vals = dist_host; gc.dc.out_rows = out_d;
+    if (pick_ids_host) {
+        gc.dc.pick_ids = ids32.data();
+        gc.dc.m = m;
+    }
+    gc.cutoff = cut;
+    if (info) {
+        gc.chunks = info; gc.relaxations = info + 1; gc.rounds = info + 2;
+    }
+    AS_TRY(geodesic_locked(who, sp, gr, gc));
+    if (info && !pick_ids_host)   // reached, per column: the block is on the host
+        for (int64_t i = 0; i < b; ++i)
+            for (int64_t x = 0; x < gr->n; ++x) info[2 + b + i] += std::isfinite(out_d[i * gr->n + x]);
+    return AS_OK;
+}
+
+as_status as_search_geodesic(const as_space* sp, const as_graph* gr, const double* query, int64_t d, double tau, int64_t seeds,
+                             const double* cutoff, const as_subset* sub, int64_t* out_idx, double* out_d, int64_t* out_len, double* out_lambda_q) {
+    const char* who = "as_search_geodesic";
+    if (!sp || !gr || !query || !out_len || ((!sub || sub->m > 0) && (!out_idx || !out_d))) {
+        set_err("%s: null argument", who);
+        return AS_EINVAL;
+    }
+    *out_len = 0;
+    double cut = 0.0;
+    AS_TRY(geodesic_cutoff(who, cutoff, &cut));
+    AS_TRY(geodesic_search_checks(who, sp, gr, d, tau, seeds, sub));
+    sp->geodesic_count[0].fetch_add(1, std::memory_order_relaxed);
+    // the sources: ONE ordinary search of the route, its first hits
+    int64_t pidx[SUBSET_TOPK], plen = 0;
+    double psc[SUBSET_TOPK];
+    double lq = 0.0;
+    sp->geodesic_count[1].fetch_add(1, std::memory_order_relaxed);
+    const as_status s = sub ? as_search_subset(sp, gr, query, d, tau, sub, pidx, psc, &plen, &lq)
+                            : search_pooled(sp, gr, query, d, tau, pidx, psc, &plen, &lq);
+    if (out_lambda_q) *out_lambda_q = lq;
+    if (s != AS_OK) return s;
+    if (sub && sub->m == 0) return AS_OK;
+    std::vector<int64_t> offs, ids;
+    std::vector<double> vals;
+    AS_TRY(geodesic_sources(who, pidx, &plen, SUBSET_TOPK, 1, seeds, offs, ids, vals));
+    const Candidates c(who, sp, sub);
+    AS_TRY(c.status);
+    GeodesicCall gc;
+    DiffuseCall& dc = gc.dc;
+    dc.b = 1; dc.offs = offs.data(); dc.ids = ids.data(); dc.vals = vals.data();
+    dc.sel = c.w; dc.pos_ids = c.w->ids; dc.m = c.m; dc.k = hits_bound(sp, gr, c.m); dc.stride = dc.k;
+    dc.out_idx = out_idx; dc.out_score = out_d; dc.out_len = out_len;
+    gc.cutoff = cut;
+    AS_TRY(c.fail(geodesic_locked(who, sp, gr, gc)));
+    geodesic_list_out(out_idx, out_d, out_len);
+    return AS_OK;
+}
+
+as_status as_search_geodesic_batch(const as_space* sp, const as_graph* gr, const double* queries, int64_t b, int64_t d, double tau, int64_t seeds,
+                                   const double* cutoff, const as_subset* sub, int64_t* out_idx, double* out_d, int64_t* out_len,
+                                   double* out_lambda_q, int32_t* out_status) {
+    const char* who = "as_search_geodesic_batch";
+    if (!sp || !gr || b < 0 || (b > 0 && (!queries || !out_len))) {
+        set_err("%s: null argument", who);
+        return AS_EINVAL;
+    }
+    const int64_t kk = hits_bound(sp, gr, sub ? sub->m : sp->n);
+    if (b > 0 && kk > 0 && (!out_idx || !out_d)) {
+        set_err("%s: null argument", who);
+        return AS_EINVAL;
+    }
+    for (int64_t i = 0; i < b; ++i) out_len[i] = 0;
+    double cut = 0.0;
+    AS_TRY(geodesic_cutoff(who, cutoff, &cut));
+    AS_TRY(geodesic_search_checks(who, sp, gr, d, tau, seeds, sub));
+    sp->geodesic_count[0].fetch_add(1, std::memory_order_relaxed);
+    if (b == 0) return AS_OK;
+    std::vector<int64_t> pidx, plen, offs, ids;
+    std::vector<double> psc, vals;
+    std::vector<int32_t> served;
+    int64_t kks = 1;
+    AS_TRY(batch_pools(who, sp, gr, queries, b, d, tau, &sp->geodesic_count[1], sub, out_lambda_q, out_status, pidx, psc, plen, served, &kks));
+    if (kk == 0) return AS_OK;
+    AS_TRY(geodesic_sources(who, pidx.data(), plen.data(), kks, b, seeds, offs, ids, vals));
+    const Candidates c(who, sp, sub);
+    AS_TRY(c.status);
+    GeodesicCall gc;
+    DiffuseCall& dc = gc.dc;
+    dc.b = b; dc.offs = offs.data(); dc.ids = ids.data(); dc.vals = vals.data(); dc.served = served.data();
+    dc.sel = c.w; dc.pos_ids = c.w->ids; dc.m = c.m; dc.k = kk; dc.stride = kk;
+    dc.out_idx = out_idx; dc.out_score = out_d; dc.out_len = out_len;
+    gc.cutoff = cut;
+    AS_TRY(c.fail(geodesic_locked(who, sp, gr, gc)));
+    for (int64_t i = 0; i < b; ++i) geodesic_list_out(out_idx + i * kk, out_d + i * kk, out_len + i);
+    return AS_OK;
+}
+as_status as_geodesic_counters(const as_space* sp, int64_t* out, int32_t n) {
+    return counters_out("as_geodesic_counters", sp, out, n, sp ? sp->geodesic_count : nullptr, 6);
+}
+double as_geodesic_kernel_us(const as_space* sp, int32_t part) {
+    if (!sp) return 0.0;
+    std::lock_guard<std::mutex> lk(sp->fmu);
+    return geodesic_kernel_us(sp->diffuse_ws, part);
+}
+void as_set_geodesic_delta(double v) { set_geodesic_delta(v); }
 
 as_status as_diffuse_counters(const as_space* sp, int64_t* out, int32_t n) {
     return counters_out("as_diffuse_counters", sp, out, n, sp ? sp->diffuse_count : nullptr, 5);

@@ -243,10 +243,21 @@ struct as_space {
     // as_graph_forest shares diffuse_ws and fmu.  as_forest_counters: [0] calls that passed their
     // checks, [1] rounds, [2] launches, [3] host waits
     mutable std::atomic<int64_t> forest_count[4] = {};
+    // as_geodesic_seeds / as_search_geodesic / as_search_geodesic_batch share diffuse_ws and fmu.
+    // as_geodesic_counters: [0] calls that passed their checks, [1] route searches run, [2] column chunks, [3] rounds, [4] launches,
+    // [5] host waits
+    mutable std::atomic<int64_t> geodesic_count[6] = {};
 };
+
+// the identity of a graph that survives the reuse of its address: a number no other graph of this process gets
+inline uint64_t graph_serial_next() {
+    static std::atomic<uint64_t> next{1};
+    return next.fetch_add(1, std::memory_order_relaxed);
+}
 
 struct as_graph {
     int device = 0;
+    uint64_t serial = graph_serial_next();   // what the workspace's weight images (DiffuseWork::fr_wkey) are remembered under
     int64_t n = 0;
     int64_t nnz = 0;          // adjacency entries (both directions, no diagonal)
     as_graph_params gp{};     // sigma resolved
@@ -1178,5 +1189,23 @@ as_status forest_run(const as_space* sp, const as_graph* gr, int sort, int32_t* 
                      int64_t* counts);
 double forest_kernel_us(const DiffuseWork* w, int part);
 void set_forest_row_lanes(int v);     // as_set_tuning("forest_row_lanes", v): 8, 16 or 32 lanes per row of the forest's rowmin kernel; else 16.  Results never depend on it
+// Graph shortest paths (as_geodesic.hip) over the whole graph `gr`, on the diffusion forms' workspace
+// (under sp->fmu), the caller has checked every argument.  dc: the sources as a diffusion call's seeds (vals: the offsets, finite
+// and >= 0) and one of its three outputs; the selection form ranks -d (an unreached item: -inf).  cutoff: +inf for none.
+// rounds (may be null): [served queries] the rounds of every column chunk, *chunks of them; relaxations (may be null): the words
+// lowered.  counts[0] += column chunks, [1] += rounds, [2] += launches, [3] += host waits.
+struct GeodesicCall {
+    DiffuseCall dc;
+    double cutoff = 0.0;
+    int64_t* rounds = nullptr;
+    int64_t* chunks = nullptr;
+    int64_t* relaxations = nullptr;
+};
+as_status geodesic_run(const as_space* sp, const as_graph* gr, const GeodesicCall& c, int64_t* counts);
+double geodesic_kernel_us(const DiffuseWork* w, int part);
+void set_geodesic_row_lanes(int v);   // as_set_tuning("geodesic_row_lanes", v): 8, 16 or 32 lanes per frontier row of the relax kernels; else 16
+void set_geodesic_lds_rows(int v);    // as_set_tuning("geodesic_lds_rows", v): frontier rows the one-block kernel keeps in LDS at most (up to 4096); 0: no such kernel; < 0: the default (2048)
+void set_geodesic_delta(double v);    // as_set_geodesic_delta(v), the tuning "geodesic_delta": the width of a bucket; 0 (the default): one bucket
+// Results never depend on the three.
 
 }  // namespace as

@@ -139,6 +139,7 @@ void diffuse_work_free(DiffuseWork* w) {
 double diffuse_kernel_us(const DiffuseWork* w) { return w ? w->kernel_us : 0.0; }
 int diffuse_cols_cap() { return g_diffuse_cols.load(std::memory_order_relaxed); }
 int diffuse_tile_edges() { return g_diffuse_tile.load(std::memory_order_relaxed); }
+int64_t diffuse_budget() { return (int64_t)g_diffuse_mib.load(std::memory_order_relaxed) << 20; }
 bool diffuse_timing() { return g_diffuse_timing.load(std::memory_order_relaxed) != 0; }
 
 static as_status diffuse_work_create(const as_space* sp, DiffuseWork** out) {
@@ -290,7 +291,7 @@ static as_status diffuse_chunks(const as_space* sp, const as_graph* gr, const Di
     DiffuseWork* w = fr.w;
     const bool timing = diffuse_timing();
     const int cols_cap = diffuse_cols_cap();
-    const int64_t budget = (int64_t)g_diffuse_mib.load(std::memory_order_relaxed) << 20;
+    const int64_t budget = diffuse_budget();
     const double om = 1.0 - c.alpha;
     w->kernel_us = 0.0;
     const int64_t nq = (int64_t)fr.q.size();

@@ -1,8 +1,9 @@
 // What the diffusion files share (as_diffuse.hip: the S19 recurrence; as_diffuse_solve.hip: the S20 conjugate-gradient solve of
 // its fixed point; as_spectral.hip: the S21 eigenpairs, which use the four blocks and the partials; as_components.hip: the S22
-// connected components and as_forest.hip: the S23 minimum spanning forest, on buffers of their own): the work buffers of a space, the column-chunk rule, the sparse seed table and its kernel, and the output
+// connected components, as_forest.hip: the S23 minimum spanning forest and as_geodesic.hip: the S24 shortest paths, on buffers of their own): the work buffers of a space, the column-chunk rule, the sparse seed table and its kernel, and the output
 // paths (gather, selection on the handle's stream, score pick, raw block).  Defined in as_diffuse.hip.
 #pragma once
+#include <cstring>
 #include <vector>
 
 #include "as_common.hpp"
@@ -22,6 +23,26 @@ constexpr int DIF_SOLVE_COLS = 64;        // the stride of the solve's per-colum
 // "spectral_mib", the budget of the eigensolver's four blocks: 64 columns up to 4M rows.  A choice, not a measurement.
 constexpr int SPC_MIB_DEFAULT = 8192;
 constexpr int FR_TIMED_ROUNDS = 32;      // rounds of a forest call whose four launches keep their own times under "diffuse_timing"
+
+// The order-preserving 64-bit image of an entry's undirected weight (S23; the S24 shortest paths decode it): sign-flipped bits, -0.0
+// as +0.0, every NaN as FR_NAN, above +inf's image 0xfff0000000000000
+constexpr unsigned long long FR_NAN = 0xfff8000000000000ull;
+constexpr unsigned long long FR_SIGN = 1ull << 63;
+__host__ __device__ __forceinline__ unsigned long long forest_key(double d) {
+    if (d != d) return FR_NAN;
+    if (d == 0.0) d = 0.0;
+    unsigned long long b;
+    memcpy(&b, &d, sizeof(b));
+    return (b & FR_SIGN) ? ~b : (b | FR_SIGN);
+}
+// ... and back: the fp64 bits (a NaN: the quiet NaN 0x7ff8000000000000)
+__host__ __device__ __forceinline__ unsigned long long forest_bits(unsigned long long key) {
+    if (key == FR_NAN) return 0x7ff8000000000000ull;
+    return (key & FR_SIGN) ? (key ^ FR_SIGN) : ~key;
+}
+// wkey[e] = min(image of dist[e], image of the reverse entry's dist), one launch over the CSR (as_forest.hip)
+__global__ void fr_weights_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices, const double* __restrict__ dist,
+                                  unsigned long long* __restrict__ wkey, int64_t n);
 
 struct DiffuseWork {
     int device = 0;
@@ -61,6 +82,7 @@ struct DiffuseWork {
     // output with the emit's chunk counts behind them; parent, hook, the rows' candidate columns and the output's ids; the flag
     // and edge count (as_forest.hip: FrStat) and their pinned copy
     dev_buf<unsigned long long> fr_wkey;    // [nnz]
+    uint64_t fr_wkey_serial = 0;            // the as_graph::serial whose images fr_wkey holds; 0: none
     dev_buf<unsigned long long> fr_words;   // [6 n + ceil(n / 256)]
     dev_buf<int32_t> fr_ints;               // [5 n]
     dev_buf<unsigned long long> fr_stat_d;
@@ -69,6 +91,20 @@ struct DiffuseWork {
     // the last call: under "diffuse_timing" the device time of its [0] rowmin, [1] pick, [2] link, [3] compress launches, [4] init
     // and weights, [5] emit; [6] the host's sort, [7] its rounds (any timing); [8 + 4 r + k] launch k of round r under timing
     double fr_us[8 + 4 * FR_TIMED_ROUNDS] = {};
+    // the shortest paths (S24, as_geodesic.hip): d as 64-bit words ([n] bit patterns of the push route, [n][C] doubles of the pull
+    // route); stamp, the far flags, two near lists and two far lists; the words a launch leaves (as_geodesic.hip: GdStat) and their
+    // pinned copy
+    dev_buf<unsigned long long> gd_d;       // [n C]
+    dev_buf<int32_t> gd_ints;               // [6 n]
+    dev_buf<unsigned long long> gd_stat_d;
+    pin_buf<unsigned long long> gd_stat_h;
+    dev_events<2> gd_ev;                    // made by the first timed call
+    // the last call: under "diffuse_timing" the device time of its [0] weights launch, [1] one-block LDS launches, [2] grid-wide
+    // relax launches, [3] filter launches, [4] pull rounds; [5] the host's time in the emit; any timing: [6] weights launches (0: the
+    // images were kept), [7] rounds, [8] CSR entries the pull rounds scanned (8 bytes each: column and stamp), [9] LDS launches,
+    // [10] grid-wide relax launches, [11] CSR entries of the rows the pull rounds relaxed (12 more bytes each, and a segment of
+    // 8 C bytes gathered)
+    double gd_us[12] = {};
 };
 
 // the tunings both files honour
@@ -76,6 +112,7 @@ int diffuse_cols_cap();        // "diffuse_cols"
 int diffuse_tile_edges();      // "diffuse_tile_edges"
 bool diffuse_timing();         // "diffuse_timing"
 unsigned diffuse_grid(int64_t blocks);   // "diffuse_grid_cap" clips a grid of `blocks`
+int64_t diffuse_budget();      // "diffuse_mib" in bytes
 // columns of the next chunk: `rem` served queries are left, n rows, at most `cols_cap` columns, `bufs` [n][C] buffers within `budget` bytes
 int diffuse_chunk_cols(int64_t rem, int64_t n, int cols_cap, int64_t budget, int bufs);
 

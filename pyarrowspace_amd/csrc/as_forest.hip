@@ -37,24 +37,8 @@ namespace as {
 namespace {
 
 constexpr unsigned long long FR_EMPTY = ~0ull;                  // no candidate, an unused slot: above every image
-constexpr unsigned long long FR_NAN = 0xfff8000000000000ull;    // every NaN: above +inf's image 0xfff0000000000000
-constexpr unsigned long long FR_SIGN = 1ull << 63;
 constexpr int32_t FR_DEAD = -2;    // rj of a row that has no entry into another class
 constexpr int FR_CHUNK = DIF_THREADS;   // slots of an emit chunk
-
-// the order-preserving image of a dist: sign-flipped bits, -0.0 as +0.0, every NaN as FR_NAN
-__host__ __device__ __forceinline__ unsigned long long forest_key(double d) {
-    if (d != d) return FR_NAN;
-    if (d == 0.0) d = 0.0;
-    unsigned long long b;
-    memcpy(&b, &d, sizeof(b));
-    return (b & FR_SIGN) ? ~b : (b | FR_SIGN);
-}
-// ... and back: the fp64 bits (a NaN: the quiet NaN 0x7ff8000000000000)
-__host__ __device__ __forceinline__ unsigned long long forest_bits(unsigned long long key) {
-    if (key == FR_NAN) return 0x7ff8000000000000ull;
-    return (key & FR_SIGN) ? (key ^ FR_SIGN) : ~key;
-}
 
 struct FrStat {
     unsigned long long flag;    // the number of the last round in which a root had a candidate (rounds count from 1)
@@ -93,6 +77,9 @@ __global__ __launch_bounds__(DIF_THREADS) void fr_init_kernel(FrArgs a) {
     }
 }
 
+}  // namespace
+
+// (declared in as_diffuse.hpp: the shortest paths of as_geodesic.hip launch it too)
 // wkey[e] = min(image of dist[e], image of the reverse entry's dist): FR_NAN lies above every number, so a NaN loses to one and
 // two NaNs stay FR_NAN.  The rows of a group and the lane-per-entry layout are the components hook's; the reverse entry (j, i) is
 // found by bisection in row j's ascending columns (S4 stores it; were it missing the entry's own dist would stand).
@@ -135,6 +122,8 @@ __global__ __launch_bounds__(DIF_THREADS) void fr_weights_kernel(const int64_t* 
         }
     }
 }
+
+namespace {
 
 // (a): W lanes per row, DIF_THREADS / W rows per block and trip.  The lanes of a sub-wave share the row, so every branch below
 // is uniform over the lanes the cross-lane moves read.
@@ -336,6 +325,7 @@ as_status fr_run(const as_space* sp, const as_graph* gr, int sort, int32_t* u_ho
     AS_TRY(diffuse_work_get(sp, &w));
     const bool timing = diffuse_timing();
     for (double& v : w->fr_us) v = 0.0;
+    w->fr_wkey_serial = 0;
     AS_TRY(reserve_or_err(w->fr_wkey, nnz, "forest weights"));
     AS_TRY(reserve_or_err(w->fr_words, 6 * n + chunks, "forest words"));
     AS_TRY(reserve_or_err(w->fr_ints, 5 * n, "forest ids"));
@@ -364,6 +354,7 @@ as_status fr_run(const as_space* sp, const as_graph* gr, int sort, int32_t* u_ho
                                     (const int32_t*)gr->indices, (const double*)gr->dist, (unsigned long long*)w->fr_wkey, n);
     if (timing) AS_HIP(hipEventRecord(ev[1], w->stream));
     AS_HIP(hipGetLastError());
+    w->fr_wkey_serial = gr->serial;   // the images are this graph's: the shortest paths read them without a launch of their own
     counts[1] += nnz > 0 ? 2 : 1;
     if (timing) {
         AS_HIP(hipStreamSynchronize(w->stream));

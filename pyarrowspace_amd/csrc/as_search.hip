@@ -3687,6 +3687,14 @@ int32_t as_set_tuning(const char* key, int32_t value) {
         set_forest_row_lanes(value);
         return 0;
     }
+    if (key && !strcmp(key, "geodesic_row_lanes")) {
+        set_geodesic_row_lanes(value);
+        return 0;
+    }
+    if (key && !strcmp(key, "geodesic_lds_rows")) {
+        set_geodesic_lds_rows(value);
+        return 0;
+    }
     if (key && !strcmp(key, "fused_timing")) {
         set_fused_timing(value);
         return 0;
