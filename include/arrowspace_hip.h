@@ -940,6 +940,44 @@ as_status as_geodesic_counters(const as_space* sp, int64_t* out, int32_t n);
  * 11 CSR entries of the rows the pull rounds relaxed (12 more bytes each, and a gathered segment of 8 C bytes) */
 double as_geodesic_kernel_us(const as_space* sp, int32_t part);
 void as_set_geodesic_delta(double v);
+/* ---- Extension: k-means over the items.  Only the items are read (x64 where the space keeps it,
+ * else x32 widened: what as_get_item returns); no graph is needed.  Centroids are [k][d] doubles in HOST memory, 1 <= k <= 4096,
+ * every entry finite.
+ * as_kmeans_assign: key(i, j) = fl(cn[j] - fl(2 dot(i, j))) with dot the fp64 sum over the features on the matrix pipe (its bits
+ * are not pinned, as with as_score_items_batch) and cn[j] = |c_j|^2 formed once per call on the device; out_labels[i] (int32 [n]) =
+ * the j of the smallest key, ties to the smallest j; a NaN key never wins and a row without a comparable key gets -1; out_dist
+ * (may be NULL; [n]) = max(0, fl(n64[i] + key)) with n64 the stored squared norm, NaN where the label is -1.  The k x n products
+ * never leave the device's registers.
+ * as_kmeans_update (debug): one update step from the caller's labels ([n], each in [-1, k)): the members of cluster j in ascending
+ * item id; P_s = the sum of the members numbered [256 s, 256 s + 256), added one by one in that order from the first one's row,
+ * each add rounded once; T = P_0 + P_1 + .. in that order; c_j' = T / count, one division per feature; an empty cluster keeps its
+ * centroid.  The bits of out_centroids are a function of the labels and the items alone.
+ * as_kmeans: Lloyd's loop from the centroids `init`.  Iteration t: labels_t = assign(C_{t-1}); changed_t = the items with a label
+ * >= 0 that differs from labels_{t-1} (t == 1: every item with a label >= 0) -> out_changed[t - 1]; changed_t == 0: stop,
+ * converged, the answer is (C_{t-1}, labels_t); else C_t = update(labels_t), and at t == max_iters: stop, not converged, the
+ * answer is (C_t, labels_t) -- the labels are then one step behind the centroids.  The host reads one pinned word per iteration;
+ * the labels cross once, at the end.  out_counts [k]: the members of every cluster under the labels returned; info->inertia: the
+ * sum of the last assignment's dist over the items with a label >= 0, by a fixed-order reduction (64-row halving trees, then
+ * strided partial sums and a halving tree).  Answers never depend on "kmeans_grid_cap".
+ * Refused before anything is launched: a null argument ("<name>: null argument"), d other than the space's, k outside
+ * [1, 4096], max_iters < 1, a non-finite centroid entry, a label outside [-1, k) -> AS_EINVAL; a shard of a row-sharded index ->
+ * AS_EUNSUPPORTED.  The buffers are the space's own k-means workspace, grow-only; calls on one space are serialised. */
+typedef struct as_kmeans_info {
+    int64_t iterations; /* assignments run */
+    int64_t converged;  /* 1: the last assignment changed no label */
+    int64_t empty;      /* clusters without a member under the labels returned */
+    double inertia;
+} as_kmeans_info;
+as_status as_kmeans_assign(const as_space* sp, const double* centroids, int64_t k, int64_t d, int32_t* out_labels, double* out_dist);
+as_status as_kmeans(const as_space* sp, const double* init, int64_t k, int64_t d, int64_t max_iters, double* out_centroids,
+                    int32_t* out_labels, int64_t* out_changed, int64_t* out_counts, as_kmeans_info* info);
+as_status as_kmeans_update(const as_space* sp, const int32_t* labels, const double* centroids, int64_t k, int64_t d, double* out_centroids);
+/* [0] calls that passed their checks, [1] iterations, [2] assign launches, [3] ordering launches (clear, histogram, scan, scatter),
+ * [4] update launches, [5] host waits */
+as_status as_kmeans_counters(const as_space* sp, int64_t* out, int32_t n);
+/* measurement, of the last k-means call on this space: under as_set_tuning("kmeans_timing", 1) the device microseconds of its part
+ * 0 assign launches (with the centroid norms), 1 ordering launches, 2 update launches; part 3 its iterations (any timing) */
+double as_kmeans_kernel_us(const as_space* sp, int32_t part);
 /* ---- Extension: fused multi-query search.  ONE answer to j >= 1 query vectors, row-major [j][d] in HOST memory,
  * with finite weights w (weights == NULL: 1/j each; negative weights are legal).  s_v(i): the S11 score of item i for vector v
  * with the bits as_score_items_batch writes at [v][i] (lambda_q of every vector from ONE as_search_batch over the j vectors, the

@@ -1845,6 +1845,118 @@ class ArrowSpace:
         batched), the column chunks, the rounds, the launches and the host's waits."""
         return _counters(_L.as_geodesic_counters, self._h, ("calls", "route searches", "column chunks", "rounds", "launches", "host waits"))
 
+    KMEANS_MAX_K = 4096
+
+    @classmethod
+    def _kmeans_centroids(cls, centroids, nfeatures: int, what: str = "centroids") -> np.ndarray:
+        """The checks of `assign` / `kmeans` / `_kmeans_update` on a centroid array that need no handle -> C-contiguous float64
+        [k, nfeatures]; anything else raises ValueError."""
+        try:
+            c = np.ascontiguousarray(centroids, dtype=np.float64)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"argument '{what}': expected a 2-D array of numbers ({e})") from None
+        if c.ndim != 2 or c.shape[1] != nfeatures:
+            raise ValueError(f"argument '{what}': expected shape (k, {nfeatures}), got {c.shape}")
+        if not 1 <= c.shape[0] <= cls.KMEANS_MAX_K:
+            raise ValueError(f"argument '{what}': k must lie in [1, {cls.KMEANS_MAX_K}], got {c.shape[0]}")
+        if not np.isfinite(c).all():
+            raise ValueError(f"argument '{what}': a non-finite entry")
+        return c
+
+    @classmethod
+    def _kmeans_params(cls, k, max_iters, nitems: int) -> tuple[int, int]:
+        for name, v in (("k", k), ("max_iters", max_iters)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"{name} must be an integer, got {v!r}")
+        if not 1 <= k <= min(cls.KMEANS_MAX_K, nitems):
+            raise ValueError(f"k must lie in [1, min({cls.KMEANS_MAX_K}, nitems = {nitems})], got {k}")
+        if max_iters < 1:
+            raise ValueError(f"max_iters must be at least 1, got {max_iters}")
+        return int(k), int(max_iters)
+
+    @staticmethod
+    def _kmeans_init_ids(k: int, init, seed, nitems: int) -> np.ndarray:
+        """The item ids whose rows start the centroids: init None: `np.random.default_rng(seed).choice(nitems, k, replace=False)` in
+        drawn order; else the k distinct ids of a 1-D integer `init`."""
+        if init is None:
+            return np.random.default_rng(seed).choice(nitems, k, replace=False).astype(np.int64)
+        ids = np.asarray(init)
+        if ids.ndim != 1 or ids.dtype == np.bool_ or not np.issubdtype(ids.dtype, np.integer):
+            raise ValueError("argument 'init': expected None, a 1-D integer array of item ids or a 2-D array of centroids")
+        ids = ids.astype(np.int64)
+        if ids.shape[0] != k:
+            raise ValueError(f"argument 'init': {ids.shape[0]} ids for k = {k}")
+        if ids.size and (ids.min() < 0 or ids.max() >= nitems):
+            raise ValueError(f"argument 'init': an id outside [0, {nitems})")
+        if np.unique(ids).shape[0] != k:
+            raise ValueError("argument 'init': the ids are not distinct")
+        return ids
+
+    def assign(self, centroids, with_dist: bool = False):
+        """Extension: the nearest of k centroids for every item -> labels, ndarray[int32] of shape (nitems,); with_dist: ->
+        (labels, dist), dist the float64 squared L2 distance of every item to its centroid.  centroids: (k, nfeatures), 1 <= k <=
+        4096, every entry finite (else ValueError, before the library is called).  Items are the stored items (`get_item`).
+        key(i, j) = fl(|c_j|^2 - fl(2 x_i . c_j)) with the dot in float64 on the matrix pipe; labels[i] is the j of the smallest
+        key, ties to the smallest j; an item whose keys are all NaN (a NaN or inf in its row) gets label -1 and dist NaN;
+        dist[i] = max(0, fl(|x_i|^2 + key)).  The k x nitems products stay in the device's registers: nitems labels (and
+        distances) cross to the host.  The labels are valid input to `groups(labels)` and `subset(labels == c)`.  A row-sharded
+        index raises ValueError."""
+        c = self._kmeans_centroids(centroids, self.nfeatures)
+        n = self.nitems
+        labels = np.empty(max(n, 1), dtype=np.int32)
+        dist = np.empty(max(n, 1), dtype=np.float64) if with_dist else None
+        _check(_L.as_kmeans_assign(self._h, c.ctypes.data, c.shape[0], c.shape[1], labels.ctypes.data, None if dist is None else dist.ctypes.data))
+        return (labels[:n], dist[:n]) if with_dist else labels[:n]
+
+    def kmeans(self, k: int, init=None, seed=0, max_iters: int = 25, with_info: bool = False):
+        """Extension: Lloyd's k-means over the items -> (centroids float64 (k, nfeatures), labels int32 (nitems,)).  init None: the
+        rows of the ids `np.random.default_rng(seed).choice(nitems, k, replace=False)`, in drawn order; a 1-D integer array: k
+        distinct item ids; a 2-D float array: the starting centroids (the checks of `assign`).  Iteration t assigns with
+        C_{t-1} (`assign`) and counts the items whose label changed (every item with a label >= 0 at t = 1); no change: converged,
+        the answer is (C_{t-1}, labels_t); else C_t is the mean of every cluster's members -- summed in ascending item id in
+        segments of 256 and then over the segments, one division per feature, an empty cluster keeps its centroid -- whose bits
+        are a function of the labels alone.  At t == max_iters (>= 1) the answer is (C_t, labels_t): the labels are then one step
+        behind the centroids (`assign(centroids)` gives the next).  An item with label -1 belongs to no cluster.  with_info: ->
+        (centroids, labels, info), info = {"iterations", "converged", "changed" (one integer per iteration), "inertia" (the sum of
+        the last assignment's dist), "counts" (int64 (k,), the members under the labels returned), "empty"}.  The host reads one
+        word per iteration; the labels cross once."""
+        n = self.nitems
+        k, max_iters = self._kmeans_params(k, max_iters, n)
+        if init is not None and np.ndim(init) == 2:
+            c0 = self._kmeans_centroids(init, self.nfeatures, "init")
+            if c0.shape[0] != k:
+                raise ValueError(f"argument 'init': {c0.shape[0]} centroids for k = {k}")
+        else:
+            c0 = np.stack([self.get_item(int(i))[0] for i in self._kmeans_init_ids(k, init, seed, n)])
+            c0 = self._kmeans_centroids(c0, self.nfeatures, "init")
+        cent = np.empty((k, self.nfeatures), dtype=np.float64)
+        labels = np.empty(max(n, 1), dtype=np.int32)
+        changed, counts, info = np.zeros(max_iters, dtype=np.int64), np.zeros(k, dtype=np.int64), np.zeros(4, dtype=np.int64)
+        _check(_L.as_kmeans(self._h, c0.ctypes.data, k, c0.shape[1], max_iters, cent.ctypes.data, labels.ctypes.data, changed.ctypes.data,
+                            counts.ctypes.data, info.ctypes.data))
+        if not with_info:
+            return cent, labels[:n]
+        its = int(info[0])
+        return cent, labels[:n], {"iterations": its, "converged": bool(info[1]), "changed": changed[:its].tolist(),
+                                  "inertia": float(info[3:4].view(np.float64)[0]), "counts": counts, "empty": int(info[2])}
+
+    def kmeans_counters(self) -> dict:
+        """Extension: `assign` / `kmeans` calls on this space that passed their checks, the iterations they ran, the assign,
+        ordering and update launches and the host's waits (one per iteration, one for the answer)."""
+        return _counters(_L.as_kmeans_counters, self._h,
+                         ("calls", "iterations", "assign launches", "ordering launches", "update launches", "host waits"))
+
+    def _kmeans_update(self, labels, centroids) -> np.ndarray:
+        """Debug: one S25 update step from caller-given labels ((nitems,) integers in [-1, k)) through the launches `kmeans` makes
+        -> the new centroids (k, nfeatures)."""
+        c = self._kmeans_centroids(centroids, self.nfeatures)
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        if lab.shape != (self.nitems,):
+            raise ValueError(f"argument 'labels': expected shape ({self.nitems},), got {lab.shape}")
+        out = np.empty_like(c)
+        _check(_L.as_kmeans_update(self._h, lab.ctypes.data, c.ctypes.data, c.shape[0], c.shape[1], out.ctypes.data))
+        return out
+
     def _spectral_op(self, gl: GraphLaplacian, op: str, A, B=None, T=None, coef=None, alias: bool = False):
         """Debug: one S21 primitive on host blocks [n, C] (C = 16 or 64) through the launch `eigsh` makes.  op "step": A = V, B = W
         (None with g == 0), coef = (a, b, g), alias: the result is written over W's block; "gram": A^T B (B None: A^T A) ->

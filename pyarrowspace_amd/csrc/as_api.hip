@@ -160,6 +160,7 @@ void as_free_space(as_space* sp) {
     maxsim_lists_work_free(sp->mlists_ws);
     diverse_work_free(sp->diverse_ws);
     diffuse_work_free(sp->diffuse_ws);
+    kmeans_work_free(sp->kmeans_ws);
     if (sp->stream) hipStreamSynchronize(sp->stream);
     hipFree(sp->x32); hipFree(sp->xs); hipFree(sp->x8); hipFree(sp->x8h); hipFree(sp->x4); hipFree(sp->fa4); hipFree(sp->fa8); hipFree(sp->x64); hipFree(sp->n64); hipFree(sp->n32); hipFree(sp->inorm32);
     hipFree(sp->lam64); hipFree(sp->lam32);
@@ -3517,6 +3518,112 @@ double as_geodesic_kernel_us(const as_space* sp, int32_t part) {
     return geodesic_kernel_us(sp->diffuse_ws, part);
 }
 void as_set_geodesic_delta(double v) { set_geodesic_delta(v); }
+
+// ---- k-means over the items (extension; as_kmeans.hip)
+namespace {
+// what the three forms refuse, before anything is launched
+as_status kmeans_checks(const char* who, const as_space* sp, const double* cent, int64_t k, int64_t d) {
+    if (d != sp->d) {
+        set_err("%s: the centroids have %lld features, the space %lld", who, (long long)d, (long long)sp->d);
+        return AS_EINVAL;
+    }
+    if (k < 1 || k > 4096) {
+        set_err("%s: k must lie in [1, 4096], got %lld", who, (long long)k);
+        return AS_EINVAL;
+    }
+    for (int64_t t = 0; t < k * d; ++t)
+        if (!std::isfinite(cent[t])) {
+            set_err("%s: centroid %lld holds a non-finite entry", who, (long long)(t / d));
+            return AS_EINVAL;
+        }
+    if (sp->row_offset != 0) {
+        set_err("%s: a shard of a row-sharded index is not supported", who);
+        return AS_EUNSUPPORTED;
+    }
+    return AS_OK;
+}
+// the frame of a call behind the checks: its counter, the lock and the device on entry, the run's counters on exit
+struct KmeansFrame {
+    const as_space* sp;
+    std::unique_lock<std::mutex> lk;
+    int64_t counts[5] = {0, 0, 0, 0, 0};
+    explicit KmeansFrame(const as_space* s) : sp(s), lk(s->kmu) { sp->kmeans_count[0].fetch_add(1, std::memory_order_relaxed); }
+    ~KmeansFrame() {
+        for (int i = 0; i < 5; ++i) sp->kmeans_count[1 + i].fetch_add(counts[i], std::memory_order_relaxed);
+    }
+    as_status device(const char* who) const {
+        if (hipSetDevice(sp->device) == hipSuccess) return AS_OK;
+        set_err("%s: hipSetDevice failed", who);
+        return AS_EHIP;
+    }
+};
+}  // namespace
+
+as_status as_kmeans_assign(const as_space* sp, const double* centroids, int64_t k, int64_t d, int32_t* out_labels, double* out_dist) {
+    const char* who = "as_kmeans_assign";
+    if (!sp || !centroids || !out_labels) {
+        set_err("%s: null argument", who);
+        return AS_EINVAL;
+    }
+    AS_TRY(kmeans_checks(who, sp, centroids, k, d));
+    KmeansFrame f(sp);
+    AS_TRY(f.device(who));
+    return kmeans_assign(sp, centroids, k, out_labels, out_dist, f.counts);
+}
+as_status as_kmeans(const as_space* sp, const double* init, int64_t k, int64_t d, int64_t max_iters, double* out_centroids, int32_t* out_labels,
+                    int64_t* out_changed, int64_t* out_counts, as_kmeans_info* info) {
+    const char* who = "as_kmeans";
+    if (!sp || !init || !out_centroids || !out_labels || !out_changed || !out_counts || !info) {
+        set_err("%s: null argument", who);
+        return AS_EINVAL;
+    }
+    if (max_iters < 1) {
+        set_err("%s: max_iters must be at least 1, got %lld", who, (long long)max_iters);
+        return AS_EINVAL;
+    }
+    AS_TRY(kmeans_checks(who, sp, init, k, d));
+    std::vector<int32_t> c32;
+    try {
+        c32.resize((size_t)k);
+    } catch (const std::bad_alloc&) {
+        set_err("%s: out of host memory", who);
+        return AS_ENOMEM;
+    }
+    KmeansCall c;
+    c.init = init; c.k = k; c.max_iters = max_iters; c.out_centroids = out_centroids; c.out_labels = out_labels; c.out_changed = out_changed;
+    c.out_counts32 = c32.data(); c.info = info;
+    {
+        KmeansFrame f(sp);
+        AS_TRY(f.device(who));
+        AS_TRY(kmeans_lloyd(sp, c, f.counts));
+    }
+    for (int64_t j = 0; j < k; ++j) out_counts[j] = c32[(size_t)j];
+    return AS_OK;
+}
+as_status as_kmeans_update(const as_space* sp, const int32_t* labels, const double* centroids, int64_t k, int64_t d, double* out_centroids) {
+    const char* who = "as_kmeans_update";
+    if (!sp || !labels || !centroids || !out_centroids) {
+        set_err("%s: null argument", who);
+        return AS_EINVAL;
+    }
+    AS_TRY(kmeans_checks(who, sp, centroids, k, d));
+    for (int64_t i = 0; i < sp->n; ++i)
+        if (labels[i] < -1 || labels[i] >= k) {
+            set_err("%s: label %d of item %lld lies outside [-1, %lld)", who, (int)labels[i], (long long)i, (long long)k);
+            return AS_EINVAL;
+        }
+    KmeansFrame f(sp);
+    AS_TRY(f.device(who));
+    return kmeans_update(sp, labels, centroids, k, out_centroids, f.counts);
+}
+as_status as_kmeans_counters(const as_space* sp, int64_t* out, int32_t n) {
+    return counters_out("as_kmeans_counters", sp, out, n, sp ? sp->kmeans_count : nullptr, 6);
+}
+double as_kmeans_kernel_us(const as_space* sp, int32_t part) {
+    if (!sp) return 0.0;
+    std::lock_guard<std::mutex> lk(sp->kmu);
+    return kmeans_kernel_us(sp->kmeans_ws, part);
+}
 
 as_status as_diffuse_counters(const as_space* sp, int64_t* out, int32_t n) {
     return counters_out("as_diffuse_counters", sp, out, n, sp ? sp->diffuse_count : nullptr, 5);

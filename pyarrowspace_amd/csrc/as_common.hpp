@@ -47,7 +47,7 @@ void dbg(const char* fmt, ...);
 
 }  // namespace as
 
-namespace as { struct SubsetWork; struct ListsWork; struct RangeWork; struct DiverseWork; struct FusedWork; struct GroupedWork; struct MaxsimWork; struct MaxsimListsWork; struct DiffuseWork; }
+namespace as { struct SubsetWork; struct ListsWork; struct RangeWork; struct DiverseWork; struct FusedWork; struct GroupedWork; struct MaxsimWork; struct MaxsimListsWork; struct DiffuseWork; struct KmeansWork; }
 struct as_subset;
 
 // ---------------------------------------------------------------- handles
@@ -247,6 +247,12 @@ struct as_space {
     // as_geodesic_counters: [0] calls that passed their checks, [1] route searches run, [2] column chunks, [3] rounds, [4] launches,
     // [5] host waits
     mutable std::atomic<int64_t> geodesic_count[6] = {};
+    // as_kmeans_assign / as_kmeans / as_kmeans_update: their buffers (as_kmeans.hip), made on first use
+    // and grown on demand; calls are serialised by kmu.  as_kmeans_counters: [0] calls that passed their checks, [1] iterations, [2]
+    // assign launches, [3] ordering launches, [4] update launches, [5] host waits
+    mutable struct as::KmeansWork* kmeans_ws = nullptr;
+    mutable std::mutex kmu;
+    mutable std::atomic<int64_t> kmeans_count[6] = {};
 };
 
 // the identity of a graph that survives the reuse of its address: a number no other graph of this process gets
@@ -1207,5 +1213,42 @@ void set_geodesic_row_lanes(int v);   // as_set_tuning("geodesic_row_lanes", v):
 void set_geodesic_lds_rows(int v);    // as_set_tuning("geodesic_lds_rows", v): frontier rows the one-block kernel keeps in LDS at most (up to 4096); 0: no such kernel; < 0: the default (2048)
 void set_geodesic_delta(double v);    // as_set_geodesic_delta(v), the tuning "geodesic_delta": the width of a bucket; 0 (the default): one bucket
 // Results never depend on the three.
+// k-means over the items (as_kmeans.hip): grow-only buffers of a space, under sp->kmu.
+struct KmeansWork {
+    int device = 0;
+    int cus = 256;
+    hipStream_t stream = nullptr;
+    dev_buf<int32_t> labels[2];    // [n] each: an iteration's labels and the one before's
+    dev_buf<double> dist;          // [n]
+    dev_buf<int32_t> members;      // [n] the item ids by (label, id)
+    dev_buf<int32_t> table;        // [units][k] the counting sort's histograms, then its bases
+    dev_buf<int32_t> counts;       // [kp] members, [kp + 1] starts, [kp + 1] segment starts
+    dev_buf<double> cent[2];       // [kp][dp] each, zero padded
+    dev_buf<double> cn;            // [kp]
+    dev_buf<double> part;          // [segments][dp] the update's segment sums
+    dev_buf<double> ipart;         // [ceil(n / 128) * 2] the inertia partials
+    dev_buf<unsigned long long> stat_d;   // [0] changed labels, [1] the inertia's bits, [2] empty clusters
+    pin_buf<unsigned long long> stat_h;
+    dev_events<2> ev;
+    double us[4] = {};             // the last call: under "kmeans_timing" the microseconds of its assign, ordering and update launches; [3] its iterations
+};
+// the caller has checked every argument; counts[0] += iterations, [1] += assign launches, [2] += ordering launches, [3] += update
+// launches, [4] += host waits.  Centroids are [k][d] host arrays, labels [n] int32.
+struct KmeansCall {
+    const double* init = nullptr;
+    int64_t k = 0, max_iters = 0;
+    double* out_centroids = nullptr;
+    int32_t* out_labels = nullptr;
+    int64_t* out_changed = nullptr;    // [max_iters]
+    int32_t* out_counts32 = nullptr;   // [k]
+    as_kmeans_info* info = nullptr;
+};
+as_status kmeans_assign(const as_space* sp, const double* cent, int64_t k, int32_t* labels_host, double* dist_host, int64_t* counts);
+as_status kmeans_update(const as_space* sp, const int32_t* labels_host, const double* cent, int64_t k, double* out_cent, int64_t* counts);
+as_status kmeans_lloyd(const as_space* sp, const KmeansCall& c, int64_t* counts);
+void kmeans_work_free(KmeansWork* w);
+double kmeans_kernel_us(const KmeansWork* w, int part);
+void set_kmeans_grid_cap(int v);   // as_set_tuning("kmeans_grid_cap", v): v > 0 clips the grids of the assign and ordering kernels; results never depend on it
+void set_kmeans_timing(int v);     // as_set_tuning("kmeans_timing", 0 | 1)
 
 }  // namespace as
