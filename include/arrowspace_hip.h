@@ -978,6 +978,29 @@ as_status as_kmeans_counters(const as_space* sp, int64_t* out, int32_t n);
 /* measurement, of the last k-means call on this space: under as_set_tuning("kmeans_timing", 1) the device microseconds of its part
  * 0 assign launches (with the centroid norms), 1 ordering launches, 2 update launches; part 3 its iterations (any timing) */
 double as_kmeans_kernel_us(const as_space* sp, int32_t part);
+/* ---- Extension: greedy k-means++ seeding on the device.  k item ids, 1 <= k <= min(4096, nitems),
+ * to start as_kmeans from.  The device draws nothing: `first` is the first id, uniforms [(k - 1) L] in [0, 1) row t - 1 the L
+ * draws of step t, 1 <= L <= 16 (L == 1: plain k-means++).  d(i, c) = max(0, fl(n64[i] + fl(n64[c] - fl(2 dot(i, c))))) with dot
+ * the fp64 sum over the features on the matrix pipe (bits not pinned) over the stored items; a NaN d gives the row weight 0 for
+ * good and a chosen row's own weight is +0.0.  m[i]: the smallest d to a chosen row.  The potential of m, pinned in bits given m:
+ * segments of 256 consecutive rows, zero padded; P_s = the halving tree v[j] += v[j + 128], then 64, .., then 1; T_s = T_{s-1} +
+ * P_s in ascending s; Phi = the last T.  Sample(u): t = fl(u Phi); the first segment with T_s > t (none: the last with P_s > 0);
+ * in it r starts at T_{s-1} and adds m row by row: the first row with m > 0 and r > t (none: the segment's last row with m > 0).
+ * Step t = 1 .. k - 1: the L samples c_l from the current m, m_l = min(m, d(., c_l)), l* = the smallest potential of m_l, ties
+ * to the smallest l; out_ids[t] = c_l*, m <- m_l*, out_phi[t] = its potential (out_ids[0] = first, out_phi[0] the potential of
+ * d(., first)); out_cand [(k - 1) L] the samples, out_chosen [k - 1] the l*.  A potential of 0 before a step: every remaining
+ * pick is the smallest id not yet chosen, ascending, with out_phi 0, out_cand -1, out_chosen -1; out_info[0] counts them.  With
+ * k == 1 uniforms, out_cand and out_chosen may be NULL.  One pass over the stored rows per step whatever L is, 2 k launches, one
+ * host wait.  Refused before anything is launched: a null argument, k, L or first out of range, a uniform outside [0, 1) ->
+ * AS_EINVAL; a shard of a row-sharded index -> AS_EUNSUPPORTED.  Shares the k-means workspace of the space; answers never depend
+ * on "kmeans_seed_grid_cap". */
+as_status as_kmeans_seed(const as_space* sp, int64_t k, int64_t first, const double* uniforms, int32_t L, int64_t* out_ids, double* out_phi,
+                         int64_t* out_cand, int32_t* out_chosen, int64_t* out_info);
+/* [0] calls that passed their checks, [1] steps, [2] distance launches, [3] pick launches, [4] host waits */
+as_status as_kmeans_seed_counters(const as_space* sp, int64_t* out, int32_t n);
+/* measurement, of the last as_kmeans_seed on this space: under as_set_tuning("kmeans_timing", 1) the device microseconds of its part
+ * 0 distance launches, 1 pick launches; part 2 its steps (any timing) */
+double as_kmeans_seed_kernel_us(const as_space* sp, int32_t part);
 /* ---- Extension: fused multi-query search.  ONE answer to j >= 1 query vectors, row-major [j][d] in HOST memory,
  * with finite weights w (weights == NULL: 1/j each; negative weights are legal).  s_v(i): the S11 score of item i for vector v
  * with the bits as_score_items_batch writes at [v][i] (lambda_q of every vector from ONE as_search_batch over the j vectors, the

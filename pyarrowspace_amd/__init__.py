@@ -9,6 +9,7 @@ There is no CPU fallback: importing this package without the built library fails
 from __future__ import annotations
 
 import ctypes as C
+import math
 import threading
 import os
 
@@ -1911,7 +1912,8 @@ class ArrowSpace:
     def kmeans(self, k: int, init=None, seed=0, max_iters: int = 25, with_info: bool = False):
         """Extension: Lloyd's k-means over the items -> (centroids float64 (k, nfeatures), labels int32 (nitems,)).  init None: the
         rows of the ids `np.random.default_rng(seed).choice(nitems, k, replace=False)`, in drawn order; a 1-D integer array: k
-        distinct item ids; a 2-D float array: the starting centroids (the checks of `assign`).  Iteration t assigns with
+        distinct item ids; a 2-D float array: the starting centroids (the checks of `assign`); the string "k-means++": the ids
+        of `kmeans_seed(k, seed=seed)`, seeded on the device.  Iteration t assigns with
         C_{t-1} (`assign`) and counts the items whose label changed (every item with a label >= 0 at t = 1); no change: converged,
         the answer is (C_{t-1}, labels_t); else C_t is the mean of every cluster's members -- summed in ascending item id in
         segments of 256 and then over the segments, one division per feature, an empty cluster keeps its centroid -- whose bits
@@ -1922,6 +1924,8 @@ class ArrowSpace:
         word per iteration; the labels cross once."""
         n = self.nitems
         k, max_iters = self._kmeans_params(k, max_iters, n)
+        if isinstance(init, str) and init == "k-means++":   # the ids of `kmeans_seed(k, seed=seed)`
+            init = self.kmeans_seed(k, seed=seed)
         if init is not None and np.ndim(init) == 2:
             c0 = self._kmeans_centroids(init, self.nfeatures, "init")
             if c0.shape[0] != k:
@@ -1945,6 +1949,56 @@ class ArrowSpace:
         ordering and update launches and the host's waits (one per iteration, one for the answer)."""
         return _counters(_L.as_kmeans_counters, self._h,
                          ("calls", "iterations", "assign launches", "ordering launches", "update launches", "host waits"))
+
+    KMEANS_SEED_MAX_TRIALS = 16
+
+    @classmethod
+    def _kmeans_seed_params(cls, k, trials, nitems: int, row_offset: int = 0) -> tuple[int, int]:
+        """The checks of `kmeans_seed` that need no handle -> (k, L), L = min(16, 2 + floor(ln k)) for trials None."""
+        for name, v in (("k", k),) + ((("trials", trials),) if trials is not None else ()):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"{name} must be an integer, got {v!r}")
+        if not 1 <= k <= min(cls.KMEANS_MAX_K, nitems):
+            raise ValueError(f"k must lie in [1, min({cls.KMEANS_MAX_K}, nitems = {nitems})], got {k}")
+        if trials is None:
+            trials = min(cls.KMEANS_SEED_MAX_TRIALS, 2 + int(math.floor(math.log(k))))
+        if not 1 <= trials <= cls.KMEANS_SEED_MAX_TRIALS:
+            raise ValueError(f"trials must lie in [1, {cls.KMEANS_SEED_MAX_TRIALS}], got {trials}")
+        if row_offset != 0:
+            raise ValueError("kmeans_seed: a shard of a row-sharded index is not supported")
+        return int(k), int(trials)
+
+    def kmeans_seed(self, k: int, seed=0, trials=None, with_info: bool = False):
+        """Extension: greedy k-means++ seeding on the device -> ids, ndarray[int64] of shape (k,): distinct item ids in the order
+        chosen, valid as `kmeans(k, init=ids)` (`kmeans(k, init="k-means++", seed=seed)` is that call).  1 <= k <= min(4096,
+        nitems); trials None: L = min(16, 2 + floor(ln k)) candidates a step (scikit-learn's rule), else an integer in [1, 16]
+        (1: plain k-means++); anything else raises ValueError before the library is called, as does a row-sharded index.  All
+        randomness is the host's: rng = np.random.default_rng(seed), first = rng.integers(nitems), U = rng.random((k - 1, L)).
+        Step t samples L rows with probability proportional to m (the squared distance to the nearest chosen row, in the
+        arithmetic of `assign`), by the inverse of a cumulative sum whose order is fixed, and keeps the one that
+        lowers the potential sum(m) most, ties to the first.  Once the potential is 0 (fewer distinct rows than k) the remaining
+        picks are the smallest ids not yet chosen.  An item with a NaN distance is never chosen after the first draw and counts in
+        no potential.  Every step is one pass over the stored rows whatever L is; the host waits once, for the answer.
+        with_info: -> (ids, info), info = {"phi": float64 (k,), the potential after each pick; "candidates": int64 (k - 1, L);
+        "chosen": int32 (k - 1,), the winning candidate of each step; "degenerate": the picks of the fill rule}."""
+        n = self.nitems
+        k, L = self._kmeans_seed_params(k, trials, n, int(_L.as_space_row_offset(self._h)))
+        rng = np.random.default_rng(seed)
+        first = int(rng.integers(n))
+        U = np.ascontiguousarray(rng.random((k - 1, L)))
+        ids, phi = np.empty(k, dtype=np.int64), np.empty(k, dtype=np.float64)
+        cand, chosen = np.empty((k - 1, L), dtype=np.int64), np.empty(k - 1, dtype=np.int32)
+        info = np.zeros(1, dtype=np.int64)
+        opt = (lambda a: a.ctypes.data) if k > 1 else (lambda a: None)
+        _check(_L.as_kmeans_seed(self._h, k, first, opt(U), L, ids.ctypes.data, phi.ctypes.data, opt(cand), opt(chosen), info.ctypes.data))
+        if not with_info:
+            return ids
+        return ids, {"phi": phi, "candidates": cand, "chosen": chosen, "degenerate": int(info[0])}
+
+    def kmeans_seed_counters(self) -> dict:
+        """Extension: `kmeans_seed` calls on this space that passed their checks, the steps they ran, the distance and pick launches
+        and the host's waits (one per call)."""
+        return _counters(_L.as_kmeans_seed_counters, self._h, ("calls", "steps", "distance launches", "pick launches", "host waits"))
 
     def _kmeans_update(self, labels, centroids) -> np.ndarray:
         """Debug: one S25 update step from caller-given labels ((nitems,) integers in [-1, k)) through the launches `kmeans` makes

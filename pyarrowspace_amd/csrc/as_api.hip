@@ -3625,6 +3625,62 @@ double as_kmeans_kernel_us(const as_space* sp, int32_t part) {
     return kmeans_kernel_us(sp->kmeans_ws, part);
 }
 
+// ---- k-means++ seeding (extension; as_kmeans_seed.hip)
+as_status as_kmeans_seed(const as_space* sp, int64_t k, int64_t first, const double* uniforms, int32_t L, int64_t* out_ids, double* out_phi,
+                         int64_t* out_cand, int32_t* out_chosen, int64_t* out_info) {
+    const char* who = "as_kmeans_seed";
+    if (!sp || !out_ids || !out_phi || !out_info || (k > 1 && (!uniforms || !out_cand || !out_chosen))) {
+        set_err("%s: null argument", who);
+        return AS_EINVAL;
+    }
+    if (k < 1 || k > 4096 || k > sp->n) {
+        set_err("%s: k must lie in [1, min(4096, nitems = %lld)], got %lld", who, (long long)sp->n, (long long)k);
+        return AS_EINVAL;
+    }
+    if (L < 1 || L > 16) {
+        set_err("%s: L must lie in [1, 16], got %d", who, (int)L);
+        return AS_EINVAL;
+    }
+    if (first < 0 || first >= sp->n) {
+        set_err("%s: the first id %lld lies outside [0, %lld)", who, (long long)first, (long long)sp->n);
+        return AS_EINVAL;
+    }
+    for (int64_t t = 0; t < (k - 1) * L; ++t)
+        if (!(uniforms[t] >= 0.0 && uniforms[t] < 1.0)) {
+            set_err("%s: uniform %lld lies outside [0, 1)", who, (long long)t);
+            return AS_EINVAL;
+        }
+    if (sp->row_offset != 0) {
+        set_err("%s: a shard of a row-sharded index is not supported", who);
+        return AS_EUNSUPPORTED;
+    }
+    if (sp->n > (int64_t)0x7fffff00) {
+        set_err("%s: %lld items are more than the 32-bit ids of the device words hold", who, (long long)sp->n);
+        return AS_EUNSUPPORTED;
+    }
+    KseedCall c;
+    c.k = k; c.first = first; c.uniforms = uniforms; c.L = L; c.out_ids = out_ids; c.out_phi = out_phi; c.out_cand = out_cand;
+    c.out_chosen = out_chosen; c.out_info = out_info;
+    std::unique_lock<std::mutex> lk(sp->kmu);
+    sp->kseed_count[0].fetch_add(1, std::memory_order_relaxed);
+    if (hipSetDevice(sp->device) != hipSuccess) {
+        set_err("%s: hipSetDevice failed", who);
+        return AS_EHIP;
+    }
+    int64_t counts[4] = {0, 0, 0, 0};
+    const as_status s = kmeans_seed(sp, c, counts);
+    for (int i = 0; i < 4; ++i) sp->kseed_count[1 + i].fetch_add(counts[i], std::memory_order_relaxed);
+    return s;
+}
+as_status as_kmeans_seed_counters(const as_space* sp, int64_t* out, int32_t n) {
+    return counters_out("as_kmeans_seed_counters", sp, out, n, sp ? sp->kseed_count : nullptr, 5);
+}
+double as_kmeans_seed_kernel_us(const as_space* sp, int32_t part) {
+    if (!sp) return 0.0;
+    std::lock_guard<std::mutex> lk(sp->kmu);
+    return kmeans_seed_kernel_us(sp->kmeans_ws, part);
+}
+
 as_status as_diffuse_counters(const as_space* sp, int64_t* out, int32_t n) {
     return counters_out("as_diffuse_counters", sp, out, n, sp ? sp->diffuse_count : nullptr, 5);
 }

@@ -253,6 +253,9 @@ struct as_space {
     mutable struct as::KmeansWork* kmeans_ws = nullptr;
     mutable std::mutex kmu;
     mutable std::atomic<int64_t> kmeans_count[6] = {};
+    // as_kmeans_seed runs on kmeans_ws under kmu.  as_kmeans_seed_counters: [0] calls that passed their
+    // checks, [1] steps, [2] distance launches, [3] pick launches, [4] host waits
+    mutable std::atomic<int64_t> kseed_count[5] = {};
 };
 
 // the identity of a graph that survives the reuse of its address: a number no other graph of this process gets
@@ -1213,8 +1216,22 @@ void set_geodesic_row_lanes(int v);   // as_set_tuning("geodesic_row_lanes", v):
 void set_geodesic_lds_rows(int v);    // as_set_tuning("geodesic_lds_rows", v): frontier rows the one-block kernel keeps in LDS at most (up to 4096); 0: no such kernel; < 0: the default (2048)
 void set_geodesic_delta(double v);    // as_set_geodesic_delta(v), the tuning "geodesic_delta": the width of a bucket; 0 (the default): one bucket
 // Results never depend on the three.
+// k-means++ seeding (as_kmeans_seed.hip): its grow-only buffers, a part of the k-means workspace
+struct KseedWork {
+    dev_buf<double> G;             // [segments * 256][16] min(m, d(., c_l)) of the step in flight; column l* is the committed m
+    dev_buf<double> P, T;          // [segments][16] each: the segment sums and their ascending prefixes
+    dev_buf<double> U;             // [(k - 1) L] the caller's uniforms
+    dev_buf<double> phi;           // [k]
+    dev_buf<int64_t> ids;          // [k]
+    dev_buf<int64_t> candrec;      // [(k - 1) L] the candidates every step tried
+    dev_buf<int32_t> chosen;       // [k - 1]
+    dev_buf<int32_t> words;        // [16] the candidate ids of the next distance launch, then the state words
+    dev_buf<unsigned char> mark;   // [n] 1: chosen
+    double us[3] = {};             // the last call: under "kmeans_timing" the microseconds of its distance and pick launches; [2] its steps
+};
 // k-means over the items (as_kmeans.hip): grow-only buffers of a space, under sp->kmu.
 struct KmeansWork {
+    KseedWork seed;
     int device = 0;
     int cus = 256;
     hipStream_t stream = nullptr;
@@ -1250,5 +1267,22 @@ void kmeans_work_free(KmeansWork* w);
 double kmeans_kernel_us(const KmeansWork* w, int part);
 void set_kmeans_grid_cap(int v);   // as_set_tuning("kmeans_grid_cap", v): v > 0 clips the grids of the assign and ordering kernels; results never depend on it
 void set_kmeans_timing(int v);     // as_set_tuning("kmeans_timing", 0 | 1)
+as_status kmeans_work_get(const as_space* sp, KmeansWork** out);   // the space's k-means workspace, made on first use (under sp->kmu)
+bool kmeans_timing_on();
+// k-means++ seeding (as_kmeans_seed.hip).  The caller has checked every argument; counts[0] += steps, [1] += distance launches,
+// [2] += pick launches, [3] += host waits.  Every array is the caller's host memory.
+struct KseedCall {
+    int64_t k = 0, first = 0;
+    const double* uniforms = nullptr;   // [(k - 1) L]
+    int L = 1;
+    int64_t* out_ids = nullptr;         // [k]
+    double* out_phi = nullptr;          // [k]
+    int64_t* out_cand = nullptr;        // [(k - 1) L]
+    int32_t* out_chosen = nullptr;      // [k - 1]
+    int64_t* out_info = nullptr;        // [1] the picks of the fill rule
+};
+as_status kmeans_seed(const as_space* sp, const KseedCall& c, int64_t* counts);
+double kmeans_seed_kernel_us(const KmeansWork* w, int part);
+void set_kmeans_seed_grid_cap(int v);   // as_set_tuning("kmeans_seed_grid_cap", v): v > 0 clips the distance kernel's grid; results never depend on it
 
 }  // namespace as

@@ -678,6 +678,9 @@ as_status km_guard(const as_space* sp, F&& run) {
 
 void set_kmeans_grid_cap(int v) { g_kmeans_grid_cap.store(v > 0 ? v : 0, std::memory_order_relaxed); }
 void set_kmeans_timing(int v) { g_kmeans_timing.store(v ? 1 : 0, std::memory_order_relaxed); }
+// for the seeding (as_kmeans_seed.hip), which runs on the same workspace and stream
+as_status kmeans_work_get(const as_space* sp, KmeansWork** out) { return km_work_get(sp, out); }
+bool kmeans_timing_on() { return g_kmeans_timing.load(std::memory_order_relaxed) != 0; }
 
 void kmeans_work_free(KmeansWork* w) {
     if (!w) return;
