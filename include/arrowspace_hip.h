@@ -1001,6 +1001,30 @@ as_status as_kmeans_seed_counters(const as_space* sp, int64_t* out, int32_t n);
 /* measurement, of the last as_kmeans_seed on this space: under as_set_tuning("kmeans_timing", 1) the device microseconds of its part
  * 0 distance launches, 1 pick launches; part 2 its steps (any timing) */
 double as_kmeans_seed_kernel_us(const as_space* sp, int32_t part);
+/* ---- Extension: bound-pruned Lloyd iterations.  as_kmeans_bounded takes what as_kmeans takes, refuses
+ * what it refuses, and returns the same out_centroids, out_labels, out_changed, out_counts, info->iterations, info->converged and
+ * info->empty, bit for bit.  Iteration 1 assigns every row; each later iteration measures how far the update moved every centroid,
+ * passes once over the stored rows, and sends through the fp64 GEMM-argmin only the rows for which a triangle-inequality bound
+ * (Hamerly's: the row's distance to its own centroid against a lower bound on its distance to every other one, both with the
+ * rounding error of the keys on the wrong side) cannot prove that as_kmeans_assign would put the old label strictly first.
+ * out_active [max_iters]: the rows that went through the GEMM in every iteration ([0] = n).  A row with label -1 is never active.
+ * info->inertia: the sum over the rows with a label >= 0 of the distance written by whichever kernel settled the row in the last
+ * iteration (the GEMM's dist, or the directly differenced squared distance of a skipped row), thread t of 1024 adding rows t,
+ * t + 1024, .. in that order, then a halving tree: a fixed order, not the bits of as_kmeans's inertia.
+ * as_kmeans_assign2 (debug): the m rows `ids` (HOST int64, any order, repeats allowed, each in [0, n); NULL with m == n: all rows
+ * in order) through the bounded loop's GEMM-argmin: out_labels and out_dist [m] carry the bits as_kmeans_assign gives for those
+ * rows; out_second [m] = the smallest max(0, fl(n64 + key)) over the centroids other than the label (+inf at k == 1, NaN where the
+ * label is -1).  Answers never depend on "kmeans_bounded_grid_cap". */
+as_status as_kmeans_bounded(const as_space* sp, const double* init, int64_t k, int64_t d, int64_t max_iters, double* out_centroids,
+                            int32_t* out_labels, int64_t* out_changed, int64_t* out_active, int64_t* out_counts, as_kmeans_info* info);
+as_status as_kmeans_assign2(const as_space* sp, const double* centroids, int64_t k, int64_t d, const int64_t* ids, int64_t m,
+                            int32_t* out_labels, double* out_dist, double* out_second);
+/* [0] calls that passed their checks, [1] iterations, [2] assign launches, [3] ordering launches, [4] update launches, [5] host
+ * waits, [6] filter launches, [7] shift launches, [8] the rows that went through the GEMM */
+as_status as_kmeans_bounded_counters(const as_space* sp, int64_t* out, int32_t n);
+/* measurement, of the last as_kmeans_bounded on this space: under as_set_tuning("kmeans_timing", 1) the device microseconds of its
+ * part 0 shift launches, 1 filter launches, 2 assign launches; part 3 its iterations (any timing) */
+double as_kmeans_bounded_kernel_us(const as_space* sp, int32_t part);
 /* ---- Extension: fused multi-query search.  ONE answer to j >= 1 query vectors, row-major [j][d] in HOST memory,
  * with finite weights w (weights == NULL: 1/j each; negative weights are legal).  s_v(i): the S11 score of item i for vector v
  * with the bits as_score_items_batch writes at [v][i] (lambda_q of every vector from ONE as_search_batch over the j vectors, the

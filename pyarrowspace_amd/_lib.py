@@ -70,6 +70,7 @@ SYMBOLS = [
     "as_set_geodesic_delta",
     "as_kmeans_assign", "as_kmeans", "as_kmeans_update", "as_kmeans_counters", "as_kmeans_kernel_us",
     "as_kmeans_seed", "as_kmeans_seed_counters", "as_kmeans_seed_kernel_us",
+    "as_kmeans_bounded", "as_kmeans_assign2", "as_kmeans_bounded_counters", "as_kmeans_bounded_kernel_us",
     "as_search_fused", "as_score_fused", "as_fused_counters", "as_fused_kernel_us",
     "as_search_fused_batch", "as_score_fused_batch", "as_fused_batch_counters", "as_fused_batch_kernel_us",
     "as_groups_create", "as_groups_count", "as_groups_free", "as_search_grouped", "as_search_grouped_batch", "as_grouped_counters",
@@ -302,6 +303,10 @@ def load():
         "as_kmeans_seed": (i32, [vp, i64, i64, vp, i32, vp, vp, vp, vp, vp]),
         "as_kmeans_seed_counters": (i32, [vp, vp, i32]),
         "as_kmeans_seed_kernel_us": (f64, [vp, i32]),
+        "as_kmeans_bounded": (i32, [vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, vp]),
+        "as_kmeans_assign2": (i32, [vp, vp, i64, i64, vp, i64, vp, vp, vp]),
+        "as_kmeans_bounded_counters": (i32, [vp, vp, i32]),
+        "as_kmeans_bounded_kernel_us": (f64, [vp, i32]),
         "as_search_fused": (i32, [vp, vp, vp, i64, i64, f64, vp, i32, i32, vp, vp, vp, C.POINTER(i64), vp, vp]),
         "as_score_fused": (i32, [vp, vp, vp, i64, i64, f64, vp, i32, i32, vp, i64, vp, vp, vp]),
         "as_fused_counters": (i32, [vp, vp, i32]),

@@ -256,6 +256,10 @@ struct as_space {
     // as_kmeans_seed runs on kmeans_ws under kmu.  as_kmeans_seed_counters: [0] calls that passed their
     // checks, [1] steps, [2] distance launches, [3] pick launches, [4] host waits
     mutable std::atomic<int64_t> kseed_count[5] = {};
+    // as_kmeans_bounded / as_kmeans_assign2 run on kmeans_ws under kmu.  as_kmeans_bounded_counters:
+    // [0] calls that passed their checks, [1] iterations, [2] assign launches, [3] ordering launches, [4] update launches, [5] host
+    // waits, [6] filter launches, [7] shift launches, [8] the rows that went through the GEMM
+    mutable std::atomic<int64_t> kmb_count[9] = {};
 };
 
 // the identity of a graph that survives the reuse of its address: a number no other graph of this process gets
@@ -1229,9 +1233,21 @@ struct KseedWork {
     dev_buf<unsigned char> mark;   // [n] 1: chosen
     double us[3] = {};             // the last call: under "kmeans_timing" the microseconds of its distance and pick launches; [2] its steps
 };
+// bound-pruned Lloyd iterations (as_kmeans_bounded.hip): their grow-only buffers, a part of the k-means
+// workspace
+struct KmbWork {
+    dev_buf<double> lb;            // [n] a lower bound on the distance (not squared) of a row to every centroid but its own
+    dev_buf<int32_t> list;         // [n] the active rows of the iteration in flight, in any order; its length: stat_d[3]
+    dev_buf<double> p;             // [kp] how far every centroid moved in the last update, rounded upward
+    dev_buf<double> bw;            // [4] the largest and the second-largest shift, the arg of the largest, max_j |c_j|^2
+    dev_buf<int32_t> ids, olab;    // as_kmeans_assign2: the caller's [m] rows and their labels
+    dev_buf<double> odist, osec;   // [m] each: their distances and runner-up distances
+    double us[4] = {};             // the last call: under "kmeans_timing" the microseconds of its shift, filter and assign launches; [3] its iterations
+};
 // k-means over the items (as_kmeans.hip): grow-only buffers of a space, under sp->kmu.
 struct KmeansWork {
     KseedWork seed;
+    KmbWork bounded;
     int device = 0;
     int cus = 256;
     hipStream_t stream = nullptr;
@@ -1284,5 +1300,23 @@ struct KseedCall {
 as_status kmeans_seed(const as_space* sp, const KseedCall& c, int64_t* counts);
 double kmeans_seed_kernel_us(const KmeansWork* w, int part);
 void set_kmeans_seed_grid_cap(int v);   // as_set_tuning("kmeans_seed_grid_cap", v): v > 0 clips the distance kernel's grid; results never depend on it
+// what as_kmeans.hip lends the bounded loop: its buffers (order: those of the ordering and the update too) and its launches, as the
+// plain loop makes them; counts as in kmeans_lloyd
+int kmeans_loop_kp(int64_t k);
+as_status kmeans_loop_begin(const as_space* sp, int64_t k, bool order, KmeansWork** w);
+as_status kmeans_loop_upload(const as_space* sp, KmeansWork* w, int64_t k, int which, const double* host);
+as_status kmeans_loop_download(const as_space* sp, KmeansWork* w, int64_t k, int which, double* host);
+as_status kmeans_loop_norms(const as_space* sp, KmeansWork* w, int64_t k, int cur);   // cn of cent[cur]; clears the changed-labels word
+as_status kmeans_loop_order(const as_space* sp, KmeansWork* w, int64_t k, int which, bool scatter, int64_t* counts);
+as_status kmeans_loop_update(const as_space* sp, KmeansWork* w, int64_t k, int cur, int64_t* counts);
+as_status kmeans_loop_read(KmeansWork* w, int words, int64_t* counts);
+// Bound-pruned Lloyd iterations (as_kmeans_bounded.hip).  The caller has checked every argument.  counts[0 .. 4] as in kmeans_lloyd,
+// [5] += filter launches, [6] += shift launches, [7] += the rows that went through the GEMM.  out_active: [max_iters].
+as_status kmeans_bounded(const as_space* sp, const KmeansCall& c, int64_t* out_active, int64_t* counts);
+// labels, dist and the runner-up's dist of the m rows `ids` (null: all n rows in order) under the [k][d] host centroids
+as_status kmeans_assign2(const as_space* sp, const double* cent, int64_t k, const int32_t* ids, int64_t m, int32_t* out_labels, double* out_dist,
+                         double* out_second, int64_t* counts);
+double kmeans_bounded_kernel_us(const KmeansWork* w, int part);
+void set_kmeans_bounded_grid_cap(int v);   // as_set_tuning("kmeans_bounded_grid_cap", v): v > 0 clips the grids of the bounded assign and filter kernels; results never depend on it
 
 }  // namespace as

@@ -682,6 +682,29 @@ void set_kmeans_timing(int v) { g_kmeans_timing.store(v ? 1 : 0, std::memory_ord
 as_status kmeans_work_get(const as_space* sp, KmeansWork** out) { return km_work_get(sp, out); }
 bool kmeans_timing_on() { return g_kmeans_timing.load(std::memory_order_relaxed) != 0; }
 
+// for the bounded loop (as_kmeans_bounded.hip): the buffers and the launches of the loop above, as they are
+int kmeans_loop_kp(int64_t k) { return (int)((k + KM_C - 1) / KM_C * KM_C); }
+as_status kmeans_loop_begin(const as_space* sp, int64_t k, bool order, KmeansWork** w) {
+    KmTimer tm{nullptr, false};
+    return km_begin(sp, k, order, w, &tm);
+}
+as_status kmeans_loop_upload(const as_space* sp, KmeansWork* w, int64_t k, int which, const double* host) { return km_upload(w, KmShape(sp, k), which, host); }
+as_status kmeans_loop_download(const as_space* sp, KmeansWork* w, int64_t k, int which, double* host) { return km_download(w, KmShape(sp, k), which, host); }
+as_status kmeans_loop_norms(const as_space* sp, KmeansWork* w, int64_t k, int cur) {
+    const KmShape s(sp, k);
+    hipLaunchKernelGGL(km_norms_kernel, dim3((unsigned)((s.kp + 3) / 4)), dim3(256), 0, w->stream, (const double*)w->cent[cur], (double*)w->cn,
+                       (unsigned long long*)w->stat_d, s.k, s.kp, s.dp);
+    AS_HIP(hipGetLastError());
+    return AS_OK;
+}
+as_status kmeans_loop_order(const as_space* sp, KmeansWork* w, int64_t k, int which, bool scatter, int64_t* counts) {
+    return km_order(w, KmShape(sp, k), which, scatter, KmTimer{w, kmeans_timing_on()}, counts);
+}
+as_status kmeans_loop_update(const as_space* sp, KmeansWork* w, int64_t k, int cur, int64_t* counts) {
+    return km_update(sp, w, KmShape(sp, k), cur, KmTimer{w, kmeans_timing_on()}, counts);
+}
+as_status kmeans_loop_read(KmeansWork* w, int words, int64_t* counts) { return km_read(w, words, counts); }
+
 void kmeans_work_free(KmeansWork* w) {
     if (!w) return;
     (void)hipSetDevice(w->device);

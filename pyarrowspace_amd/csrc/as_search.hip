@@ -3703,6 +3703,10 @@ int32_t as_set_tuning(const char* key, int32_t value) {
         set_kmeans_seed_grid_cap(value);
         return 0;
     }
+    if (key && !strcmp(key, "kmeans_bounded_grid_cap")) {
+        set_kmeans_bounded_grid_cap(value);
+        return 0;
+    }
     if (key && !strcmp(key, "geodesic_lds_rows")) {
         set_geodesic_lds_rows(value);
         return 0;
