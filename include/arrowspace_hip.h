@@ -1025,6 +1025,39 @@ as_status as_kmeans_bounded_counters(const as_space* sp, int64_t* out, int32_t n
 /* measurement, of the last as_kmeans_bounded on this space: under as_set_tuning("kmeans_timing", 1) the device microseconds of its
  * part 0 shift launches, 1 filter launches, 2 assign launches; part 3 its iterations (any timing) */
 double as_kmeans_bounded_kernel_us(const as_space* sp, int32_t part);
+/* ---- Extension: spherical (cosine) k-means over the items.  Items, centroids and refusals are
+ * as_kmeans's; in addition every centroid handed in must have a direction (else AS_EINVAL, "has no direction").
+ * Row scale: w_i = fl(1 / fl(sqrt(n64[i]))), n64 the stored squared norm; a row whose n64 is 0, NaN or inf, or whose w is not
+ * finite, is DEAD: label -1, cos NaN, member of no cluster.
+ * unit(v) of a centroid row: lane partials s_l (l = 0 .. 63) add fl(v_c v_c) over c = l, l + 64, .. in ascending order, product and
+ * add rounded separately; the halving tree s_l <- fl(s_l + s_{l+o}), o = 32, 16, .., 1, l < o; q = s_0; r = fl(1 / fl(sqrt(q)));
+ * unit(v)_c = fl(v_c r).  q of 0, NaN or inf, or an r that is not finite: v has no direction.
+ * as_kmeans_cos_assign: g(i, j) = x_i . unit(c_j), the fp64 sum over the features on the matrix pipe (bits not pinned);
+ * out_labels[i] = the j of the largest g, ties to the smallest j, a NaN g never wins, no comparable g or a dead row: -1; out_cos
+ * (may be NULL; [n]) = min(1, max(-1, fl(g w_i))), NaN where the label is -1.
+ * as_kmeans_spherical_update (debug): one update step from the caller's labels: y_m = fl(x_m w_m) (rounded on its own); P_s = the
+ * members [256 s, 256 s + 256) of a cluster in ascending id, added one by one from the first one's y row; T = P_0 + P_1 + ..;
+ * c_j' = unit(T_j); an empty cluster, or a T with no direction, keeps the row of `centroids` as it was handed in.  No division by
+ * the count.  The bits of out_centroids are a function of the labels, the items and w alone.
+ * as_kmeans_spherical: as_kmeans's loop with this assignment and this update from unit(init); the centroids inside the loop are
+ * unit rows already and are used as they are.  out_centroids are unit rows; info->inertia carries the COHESION, the sum of the
+ * last assignment's cos over the items with a label >= 0, in the fixed order of as_kmeans's inertia.  The host reads one pinned
+ * word per iteration.
+ * as_kmeans_spherical_scales (debug): out_w [n] = the device's w, NaN on dead rows.
+ * Shares the k-means workspace of the space; answers never depend on "kmeans_grid_cap". */
+as_status as_kmeans_cos_assign(const as_space* sp, const double* centroids, int64_t k, int64_t d, int32_t* out_labels, double* out_cos);
+as_status as_kmeans_spherical(const as_space* sp, const double* init, int64_t k, int64_t d, int64_t max_iters, double* out_centroids,
+                              int32_t* out_labels, int64_t* out_changed, int64_t* out_counts, as_kmeans_info* info);
+as_status as_kmeans_spherical_update(const as_space* sp, const int32_t* labels, const double* centroids, int64_t k, int64_t d,
+                                     double* out_centroids);
+as_status as_kmeans_spherical_scales(const as_space* sp, double* out_w);
+/* [0] calls that passed their checks, [1] iterations, [2] assign launches, [3] ordering launches, [4] update launches (partial sums
+ * and final), [5] host waits, [6] unit launches, [7] row-scale launches */
+as_status as_kmeans_spherical_counters(const as_space* sp, int64_t* out, int32_t n);
+/* measurement, of the last spherical call on this space: under as_set_tuning("kmeans_timing", 1) the device microseconds of its part
+ * 0 unit launches, 1 assign launches, 2 ordering launches, 3 update launches (partial sums and final); part 4 its iterations (any
+ * timing) */
+double as_kmeans_spherical_kernel_us(const as_space* sp, int32_t part);
 /* ---- Extension: fused multi-query search.  ONE answer to j >= 1 query vectors, row-major [j][d] in HOST memory,
  * with finite weights w (weights == NULL: 1/j each; negative weights are legal).  s_v(i): the S11 score of item i for vector v
  * with the bits as_score_items_batch writes at [v][i] (lambda_q of every vector from ONE as_search_batch over the j vectors, the

@@ -1924,8 +1924,8 @@ class ArrowSpace:
         word per iteration; the labels cross once."""
         return self._kmeans_run(False, k, init, seed, max_iters, with_info)
 
-    def _kmeans_run(self, bounded: bool, k, init, seed, max_iters, with_info):
-        """`kmeans` and `kmeans_bounded`: the checks, the starting centroids, the library call, the answer."""
+    def _kmeans_start(self, k, init, seed, max_iters):
+        """The checks of `kmeans` and the starting centroids of its `init` forms -> (k, max_iters, c0 float64 (k, nfeatures))."""
         n = self.nitems
         k, max_iters = self._kmeans_params(k, max_iters, n)
         if isinstance(init, str) and init == "k-means++":   # the ids of `kmeans_seed(k, seed=seed)`
@@ -1937,6 +1937,12 @@ class ArrowSpace:
         else:
             c0 = np.stack([self.get_item(int(i))[0] for i in self._kmeans_init_ids(k, init, seed, n)])
             c0 = self._kmeans_centroids(c0, self.nfeatures, "init")
+        return k, max_iters, c0
+
+    def _kmeans_run(self, bounded: bool, k, init, seed, max_iters, with_info):
+        """`kmeans` and `kmeans_bounded`: the checks, the starting centroids, the library call, the answer."""
+        n = self.nitems
+        k, max_iters, c0 = self._kmeans_start(k, init, seed, max_iters)
         cent = np.empty((k, self.nfeatures), dtype=np.float64)
         labels = np.empty(max(n, 1), dtype=np.int32)
         changed, counts, info = np.zeros(max_iters, dtype=np.int64), np.zeros(k, dtype=np.int64), np.zeros(4, dtype=np.int64)
@@ -2067,6 +2073,85 @@ class ArrowSpace:
         out = np.empty_like(c)
         _check(_L.as_kmeans_update(self._h, lab.ctypes.data, c.ctypes.data, c.shape[0], c.shape[1], out.ctypes.data))
         return out
+
+    @staticmethod
+    def _kmeans_directions(c: np.ndarray, what: str = "centroids") -> np.ndarray:
+        """The check of `assign_cosine` / `kmeans_spherical` that needs no handle: every row of c has a direction -- a squared length
+        that is neither 0 nor infinite, with a finite inverse root -- else ValueError."""
+        with np.errstate(all="ignore"):
+            q = np.einsum("ij,ij->i", c, c)
+            bad = ~((q > 0.0) & np.isfinite(q) & np.isfinite(1.0 / np.sqrt(q)))
+        if bad.any():
+            raise ValueError(f"argument '{what}': row {int(np.flatnonzero(bad)[0])} has no direction")
+        return c
+
+    def assign_cosine(self, centroids, with_cos: bool = False):
+        """Extension: the centroid of the largest cosine for every item -> labels, ndarray[int32] of shape
+        (nitems,); with_cos: -> (labels, cos), cos the float64 cosine of every item with its centroid.  centroids: (k, nfeatures)
+        with the checks of `assign`, and every row must have a direction (a zero row, or one whose squared length overflows, raises
+        ValueError before the library is called); they need not be unit rows: the device scales them once (`unit`, S28).
+        g(i, j) = x_i . unit(c_j) in float64 on the matrix pipe over the stored items (`get_item`); labels[i] is the j of the
+        largest g, ties to the smallest j; cos[i] = min(1, max(-1, fl(g w_i))) with w_i = fl(1 / fl(sqrt(|x_i|^2))) from the stored
+        squared norm.  An item whose squared norm is 0, NaN or inf is dead: label -1, cos NaN.  Two items of the same direction and
+        different lengths get the same label, as `search` ranks them alike; `assign` (squared L2) may part them.  The labels are
+        valid input to `groups(labels)` and `subset(labels == c)`.  A row-sharded index raises ValueError."""
+        c = self._kmeans_directions(self._kmeans_centroids(centroids, self.nfeatures))
+        n = self.nitems
+        labels = np.empty(max(n, 1), dtype=np.int32)
+        cos = np.empty(max(n, 1), dtype=np.float64) if with_cos else None
+        _check(_L.as_kmeans_cos_assign(self._h, c.ctypes.data, c.shape[0], c.shape[1], labels.ctypes.data, None if cos is None else cos.ctypes.data))
+        return (labels[:n], cos[:n]) if with_cos else labels[:n]
+
+    def kmeans_spherical(self, k: int, init=None, seed=0, max_iters: int = 25, with_info: bool = False):
+        """Extension: spherical (cosine) k-means over the items -> (centroids float64 (k, nfeatures), unit rows,
+        labels int32 (nitems,)).  Every argument is `kmeans`'s, with its checks, refusals and `init` forms; "k-means++" passes the
+        ids of `kmeans_seed(k, seed=seed)`, whose seeding is squared L2 (a cosine seeding is not built).  An init row or init
+        centroid with no direction raises ValueError.  The loop is `kmeans`'s with `assign_cosine` in place of `assign` and this
+        update: every member's row times its scale w_i, summed in ascending item id in segments of 256 and then over the segments,
+        and the sum scaled to unit length -- no division by the count; its bits are a function of the labels and the scales.  An
+        empty cluster, or a sum with no direction, keeps its centroid.  At t == max_iters the labels are one step behind the
+        centroids, as with `kmeans`.  A dead item (see `assign_cosine`) has label -1 and belongs to no cluster.  with_info: ->
+        (centroids, labels, info), info = {"iterations", "converged", "changed" (one integer per iteration), "cohesion" (the sum
+        of the last assignment's cosines over the labelled items), "counts" (int64 (k,)), "empty"}.  The host reads one word per
+        iteration; the labels cross once."""
+        n = self.nitems
+        k, max_iters, c0 = self._kmeans_start(k, init, seed, max_iters)
+        self._kmeans_directions(c0, "init")
+        cent = np.empty((k, self.nfeatures), dtype=np.float64)
+        labels = np.empty(max(n, 1), dtype=np.int32)
+        changed, counts, info = np.zeros(max_iters, dtype=np.int64), np.zeros(k, dtype=np.int64), np.zeros(4, dtype=np.int64)
+        _check(_L.as_kmeans_spherical(self._h, c0.ctypes.data, k, c0.shape[1], max_iters, cent.ctypes.data, labels.ctypes.data, changed.ctypes.data,
+                                      counts.ctypes.data, info.ctypes.data))
+        if not with_info:
+            return cent, labels[:n]
+        its = int(info[0])
+        return cent, labels[:n], {"iterations": its, "converged": bool(info[1]), "changed": changed[:its].tolist(),
+                                  "cohesion": float(info[3:4].view(np.float64)[0]), "counts": counts, "empty": int(info[2])}
+
+    def kmeans_spherical_counters(self) -> dict:
+        """Extension: `assign_cosine` / `kmeans_spherical` calls on this space that passed their checks, the iterations they ran,
+        their launches by kind and the host's waits (one per iteration, one for the answer)."""
+        return _counters(_L.as_kmeans_spherical_counters, self._h,
+                         ("calls", "iterations", "assign launches", "ordering launches", "update launches", "host waits", "unit launches",
+                          "scale launches"))
+
+    def _kmeans_spherical_update(self, labels, centroids) -> np.ndarray:
+        """Debug: one S28 update step from caller-given labels ((nitems,) integers in [-1, k)) through the launches
+        `kmeans_spherical` makes -> the new centroids (k, nfeatures): unit rows, and the row of `centroids`, as handed in, for an
+        empty cluster or a sum with no direction."""
+        c = self._kmeans_centroids(centroids, self.nfeatures)
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        if lab.shape != (self.nitems,):
+            raise ValueError(f"argument 'labels': expected shape ({self.nitems},), got {lab.shape}")
+        out = np.empty_like(c)
+        _check(_L.as_kmeans_spherical_update(self._h, lab.ctypes.data, c.ctypes.data, c.shape[0], c.shape[1], out.ctypes.data))
+        return out
+
+    def _kmeans_row_scales(self) -> np.ndarray:
+        """Debug: the device's row scales w_i = fl(1 / fl(sqrt(|x_i|^2))) of S28, float64 (nitems,), NaN on dead rows."""
+        w = np.empty(max(self.nitems, 1), dtype=np.float64)
+        _check(_L.as_kmeans_spherical_scales(self._h, w.ctypes.data))
+        return w[:self.nitems]
 
     def _spectral_op(self, gl: GraphLaplacian, op: str, A, B=None, T=None, coef=None, alias: bool = False):
         """Debug: one S21 primitive on host blocks [n, C] (C = 16 or 64) through the launch `eigsh` makes.  op "step": A = V, B = W

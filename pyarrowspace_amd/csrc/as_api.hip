@@ -3772,6 +3772,119 @@ double as_kmeans_bounded_kernel_us(const as_space* sp, int32_t part) {
     return kmeans_bounded_kernel_us(sp->kmeans_ws, part);
 }
 
+// ---- spherical k-means (extension; as_kmeans_spherical.hip)
+namespace {
+// the frame of a spherical call behind the checks, as KmeansFrame: counts[0 .. 6] go to kms_count[1 .. 7]
+struct KmsFrame {
+    const as_space* sp;
+    std::unique_lock<std::mutex> lk;
+    int64_t counts[7] = {0, 0, 0, 0, 0, 0, 0};
+    explicit KmsFrame(const as_space* s) : sp(s), lk(s->kmu) { sp->kms_count[0].fetch_add(1, std::memory_order_relaxed); }
+    ~KmsFrame() {
+        for (int i = 0; i < 7; ++i) sp->kms_count[1 + i].fetch_add(counts[i], std::memory_order_relaxed);
+    }
+    as_status device(const char* who) const {
+        if (hipSetDevice(sp->device) == hipSuccess) return AS_OK;
+        set_err("%s: hipSetDevice failed", who);
+        return AS_EHIP;
+    }
+};
+// kmeans_checks, and every centroid must have a direction: a squared length that is neither 0 nor infinite, with a finite inverse root
+as_status kms_checks(const char* who, const as_space* sp, const double* cent, int64_t k, int64_t d) {
+    AS_TRY(kmeans_checks(who, sp, cent, k, d));
+    for (int64_t j = 0; j < k; ++j) {
+        double q = 0.0;
+        for (int64_t c = 0; c < d; ++c) q += cent[j * d + c] * cent[j * d + c];
+        if (!(q > 0.0) || !std::isfinite(q) || !std::isfinite(1.0 / std::sqrt(q))) {
+            set_err("%s: centroid %lld has no direction (its squared length is %g)", who, (long long)j, q);
+            return AS_EINVAL;
+        }
+    }
+    return AS_OK;
+}
+}  // namespace
+
+as_status as_kmeans_cos_assign(const as_space* sp, const double* centroids, int64_t k, int64_t d, int32_t* out_labels, double* out_cos) {
+    const char* who = "as_kmeans_cos_assign";
+    if (!sp || !centroids || !out_labels) {
+        set_err("%s: null argument", who);
+        return AS_EINVAL;
+    }
+    AS_TRY(kms_checks(who, sp, centroids, k, d));
+    KmsFrame f(sp);
+    AS_TRY(f.device(who));
+    return kmeans_cos_assign(sp, centroids, k, out_labels, out_cos, f.counts);
+}
+as_status as_kmeans_spherical(const as_space* sp, const double* init, int64_t k, int64_t d, int64_t max_iters, double* out_centroids,
+                              int32_t* out_labels, int64_t* out_changed, int64_t* out_counts, as_kmeans_info* info) {
+    const char* who = "as_kmeans_spherical";
+    if (!sp || !init || !out_centroids || !out_labels || !out_changed || !out_counts || !info) {
+        set_err("%s: null argument", who);
+        return AS_EINVAL;
+    }
+    if (max_iters < 1) {
+        set_err("%s: max_iters must be at least 1, got %lld", who, (long long)max_iters);
+        return AS_EINVAL;
+    }
+    AS_TRY(kms_checks(who, sp, init, k, d));
+    std::vector<int32_t> c32;
+    try {
+        c32.resize((size_t)k);
+    } catch (const std::bad_alloc&) {
+        set_err("%s: out of host memory", who);
+        return AS_ENOMEM;
+    }
+    KmeansCall c;
+    c.init = init; c.k = k; c.max_iters = max_iters; c.out_centroids = out_centroids; c.out_labels = out_labels; c.out_changed = out_changed;
+    c.out_counts32 = c32.data(); c.info = info;
+    {
+        KmsFrame f(sp);
+        AS_TRY(f.device(who));
+        AS_TRY(kmeans_spherical(sp, c, f.counts));
+    }
+    for (int64_t j = 0; j < k; ++j) out_counts[j] = c32[(size_t)j];
+    return AS_OK;
+}
+as_status as_kmeans_spherical_update(const as_space* sp, const int32_t* labels, const double* centroids, int64_t k, int64_t d,
+                                     double* out_centroids) {
+    const char* who = "as_kmeans_spherical_update";
+    if (!sp || !labels || !centroids || !out_centroids) {
+        set_err("%s: null argument", who);
+        return AS_EINVAL;
+    }
+    AS_TRY(kmeans_checks(who, sp, centroids, k, d));
+    for (int64_t i = 0; i < sp->n; ++i)
+        if (labels[i] < -1 || labels[i] >= k) {
+            set_err("%s: label %d of item %lld lies outside [-1, %lld)", who, (int)labels[i], (long long)i, (long long)k);
+            return AS_EINVAL;
+        }
+    KmsFrame f(sp);
+    AS_TRY(f.device(who));
+    return kmeans_spherical_update(sp, labels, centroids, k, out_centroids, f.counts);
+}
+as_status as_kmeans_spherical_scales(const as_space* sp, double* out_w) {
+    const char* who = "as_kmeans_spherical_scales";
+    if (!sp || !out_w) {
+        set_err("%s: null argument", who);
+        return AS_EINVAL;
+    }
+    if (sp->row_offset != 0) {
+        set_err("%s: a shard of a row-sharded index is not supported", who);
+        return AS_EUNSUPPORTED;
+    }
+    KmsFrame f(sp);
+    AS_TRY(f.device(who));
+    return kmeans_spherical_scales(sp, out_w, f.counts);
+}
+as_status as_kmeans_spherical_counters(const as_space* sp, int64_t* out, int32_t n) {
+    return counters_out("as_kmeans_spherical_counters", sp, out, n, sp ? sp->kms_count : nullptr, 8);
+}
+double as_kmeans_spherical_kernel_us(const as_space* sp, int32_t part) {
+    if (!sp) return 0.0;
+    std::lock_guard<std::mutex> lk(sp->kmu);
+    return kmeans_spherical_kernel_us(sp->kmeans_ws, part);
+}
+
 as_status as_diffuse_counters(const as_space* sp, int64_t* out, int32_t n) {
     return counters_out("as_diffuse_counters", sp, out, n, sp ? sp->diffuse_count : nullptr, 5);
 }

@@ -260,6 +260,10 @@ struct as_space {
     // [0] calls that passed their checks, [1] iterations, [2] assign launches, [3] ordering launches, [4] update launches, [5] host
     // waits, [6] filter launches, [7] shift launches, [8] the rows that went through the GEMM
     mutable std::atomic<int64_t> kmb_count[9] = {};
+    // as_kmeans_cos_assign / as_kmeans_spherical run on kmeans_ws under kmu.
+    // as_kmeans_spherical_counters: [0] calls that passed their checks, [1] iterations, [2] assign launches, [3] ordering launches,
+    // [4] update launches, [5] host waits, [6] unit launches, [7] row-scale launches
+    mutable std::atomic<int64_t> kms_count[8] = {};
 };
 
 // the identity of a graph that survives the reuse of its address: a number no other graph of this process gets
@@ -1244,10 +1248,17 @@ struct KmbWork {
     dev_buf<double> odist, osec;   // [m] each: their distances and runner-up distances
     double us[4] = {};             // the last call: under "kmeans_timing" the microseconds of its shift, filter and assign launches; [3] its iterations
 };
+// spherical k-means (as_kmeans_spherical.hip): its grow-only buffers, a part of the k-means workspace
+struct KmsWork {
+    dev_buf<double> w;             // [n] 1 / sqrt(n64) of every row; NaN: a dead row
+    dev_buf<double> q;             // [kp] the squared length unit() found for every centroid row
+    double us[5] = {};             // the last call: under "kmeans_timing" the microseconds of its unit, assign and update launches ([0], [1], [3]; ordering: KmeansWork::us[1]); [4] its iterations
+};
 // k-means over the items (as_kmeans.hip): grow-only buffers of a space, under sp->kmu.
 struct KmeansWork {
     KseedWork seed;
     KmbWork bounded;
+    KmsWork spherical;
     int device = 0;
     int cus = 256;
     hipStream_t stream = nullptr;
@@ -1310,6 +1321,15 @@ as_status kmeans_loop_norms(const as_space* sp, KmeansWork* w, int64_t k, int cu
 as_status kmeans_loop_order(const as_space* sp, KmeansWork* w, int64_t k, int which, bool scatter, int64_t* counts);
 as_status kmeans_loop_update(const as_space* sp, KmeansWork* w, int64_t k, int cur, int64_t* counts);
 as_status kmeans_loop_read(KmeansWork* w, int words, int64_t* counts);
+unsigned kmeans_loop_grid(int64_t blocks);   // a grid of `blocks` under "kmeans_grid_cap"
+as_status kmeans_loop_inertia(const as_space* sp, KmeansWork* w);   // stat_d[1] <- the bits of the sum of ipart in km_inertia_kernel's order
+// Spherical k-means (as_kmeans_spherical.hip).  The caller has checked every argument.  counts[0 .. 4] as in
+// kmeans_lloyd, [5] += unit launches, [6] += row-scale launches.  info->inertia carries the cohesion.
+as_status kmeans_cos_assign(const as_space* sp, const double* cent, int64_t k, int32_t* labels_host, double* cos_host, int64_t* counts);
+as_status kmeans_spherical(const as_space* sp, const KmeansCall& c, int64_t* counts);
+as_status kmeans_spherical_update(const as_space* sp, const int32_t* labels_host, const double* cent, int64_t k, double* out_cent, int64_t* counts);
+as_status kmeans_spherical_scales(const as_space* sp, double* out_w, int64_t* counts);
+double kmeans_spherical_kernel_us(const KmeansWork* w, int part);
 // Bound-pruned Lloyd iterations (as_kmeans_bounded.hip).  The caller has checked every argument.  counts[0 .. 4] as in kmeans_lloyd,
 // [5] += filter launches, [6] += shift launches, [7] += the rows that went through the GEMM.  out_active: [max_iters].
 as_status kmeans_bounded(const as_space* sp, const KmeansCall& c, int64_t* out_active, int64_t* counts);

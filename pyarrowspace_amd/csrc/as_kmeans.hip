@@ -704,6 +704,13 @@ as_status kmeans_loop_update(const as_space* sp, KmeansWork* w, int64_t k, int c
     return km_update(sp, w, KmShape(sp, k), cur, KmTimer{w, kmeans_timing_on()}, counts);
 }
 as_status kmeans_loop_read(KmeansWork* w, int words, int64_t* counts) { return km_read(w, words, counts); }
+unsigned kmeans_loop_grid(int64_t blocks) { return km_grid(blocks); }
+as_status kmeans_loop_inertia(const as_space* sp, KmeansWork* w) {
+    hipLaunchKernelGGL(km_inertia_kernel, dim3(1), dim3(256), 0, w->stream, (const double*)w->ipart, 2 * ((sp->n + KM_ROWS - 1) / KM_ROWS),
+                       (unsigned long long*)w->stat_d);
+    AS_HIP(hipGetLastError());
+    return AS_OK;
+}
 
 void kmeans_work_free(KmeansWork* w) {
     if (!w) return;
