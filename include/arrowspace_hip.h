@@ -1058,6 +1058,29 @@ as_status as_kmeans_spherical_counters(const as_space* sp, int64_t* out, int32_t
  * 0 unit launches, 1 assign launches, 2 ordering launches, 3 update launches (partial sums and final); part 4 its iterations (any
  * timing) */
 double as_kmeans_spherical_kernel_us(const as_space* sp, int32_t part);
+/* ---- Extension: bound-pruned spherical k-means.  as_kmeans_spherical_bounded takes what
+ * as_kmeans_spherical takes, refuses what it refuses, and returns the same out_centroids, out_labels, out_changed, out_counts,
+ * info->iterations, info->converged and info->empty, bit for bit.  Iteration 1 assigns every row; each later iteration measures how
+ * far the update moved every unit centroid, passes once over the stored rows, and sends through the GEMM-argmax only the rows for
+ * which Hamerly's bound on the chord sqrt(2 - 2 cos) -- the row's own chord against a lower bound on its chord to every other
+ * centroid, each with the error E = (2 d + 16) 2^-53 of a device cosine on the wrong side -- cannot prove that
+ * as_kmeans_cos_assign would keep the label strictly first.  out_active [max_iters]: the rows assigned per iteration (n at the
+ * first).  info->inertia carries the COHESION: the cos written by whichever kernel settled each row in the last iteration (a skipped
+ * row: its directly summed dot with its new centroid times w, clamped), summed in a fixed order independent of every grid; it
+ * need not carry as_kmeans_spherical's bits.  A dead row and a row with label -1 are never active.
+ * as_kmeans_cos_assign2 (debug): the m rows `ids` ([m] in [0, n), any order, repeats allowed; NULL with m == n: all rows in order)
+ * through the bounded loop's GEMM-argmax: out_labels and out_cos [m] carry the bits as_kmeans_cos_assign gives for those rows;
+ * out_second [m] = the largest min(1, max(-1, fl(g w))) over the centroids other than the label (-inf at k == 1, NaN where the
+ * label is -1).  Answers never depend on "kmeans_bounded_grid_cap". */
+as_status as_kmeans_spherical_bounded(const as_space* sp, const double* init, int64_t k, int64_t d, int64_t max_iters, double* out_centroids,
+                                      int32_t* out_labels, int64_t* out_changed, int64_t* out_active, int64_t* out_counts, as_kmeans_info* info);
+as_status as_kmeans_cos_assign2(const as_space* sp, const double* centroids, int64_t k, int64_t d, const int64_t* ids, int64_t m,
+                                int32_t* out_labels, double* out_cos, double* out_second);
+/* [0 .. 7] as as_kmeans_spherical_counters, [8] filter launches, [9] shift launches, [10] the rows that went through the GEMM */
+as_status as_kmeans_spherical_bounded_counters(const as_space* sp, int64_t* out, int32_t n);
+/* measurement, of the last as_kmeans_spherical_bounded on this space: under as_set_tuning("kmeans_timing", 1) the device
+ * microseconds of its part 0 shift launches, 1 filter launches, 2 assign launches; part 3 its iterations (any timing) */
+double as_kmeans_spherical_bounded_kernel_us(const as_space* sp, int32_t part);
 /* ---- Extension: fused multi-query search.  ONE answer to j >= 1 query vectors, row-major [j][d] in HOST memory,
  * with finite weights w (weights == NULL: 1/j each; negative weights are legal).  s_v(i): the S11 score of item i for vector v
  * with the bits as_score_items_batch writes at [v][i] (lambda_q of every vector from ONE as_search_batch over the j vectors, the

@@ -2114,19 +2114,80 @@ class ArrowSpace:
         (centroids, labels, info), info = {"iterations", "converged", "changed" (one integer per iteration), "cohesion" (the sum
         of the last assignment's cosines over the labelled items), "counts" (int64 (k,)), "empty"}.  The host reads one word per
         iteration; the labels cross once."""
+        return self._kmeans_spherical_run(False, k, init, seed, max_iters, with_info)
+
+    def _kmeans_spherical_run(self, bounded: bool, k, init, seed, max_iters, with_info):
+        """`kmeans_spherical` and `kmeans_spherical_bounded`: the checks, the starting centroids, the library call, the answer."""
         n = self.nitems
         k, max_iters, c0 = self._kmeans_start(k, init, seed, max_iters)
         self._kmeans_directions(c0, "init")
         cent = np.empty((k, self.nfeatures), dtype=np.float64)
         labels = np.empty(max(n, 1), dtype=np.int32)
         changed, counts, info = np.zeros(max_iters, dtype=np.int64), np.zeros(k, dtype=np.int64), np.zeros(4, dtype=np.int64)
-        _check(_L.as_kmeans_spherical(self._h, c0.ctypes.data, k, c0.shape[1], max_iters, cent.ctypes.data, labels.ctypes.data, changed.ctypes.data,
-                                      counts.ctypes.data, info.ctypes.data))
+        active = np.zeros(max_iters, dtype=np.int64)
+        if bounded:
+            _check(_L.as_kmeans_spherical_bounded(self._h, c0.ctypes.data, k, c0.shape[1], max_iters, cent.ctypes.data, labels.ctypes.data,
+                                                  changed.ctypes.data, active.ctypes.data, counts.ctypes.data, info.ctypes.data))
+        else:
+            _check(_L.as_kmeans_spherical(self._h, c0.ctypes.data, k, c0.shape[1], max_iters, cent.ctypes.data, labels.ctypes.data,
+                                          changed.ctypes.data, counts.ctypes.data, info.ctypes.data))
         if not with_info:
             return cent, labels[:n]
         its = int(info[0])
-        return cent, labels[:n], {"iterations": its, "converged": bool(info[1]), "changed": changed[:its].tolist(),
-                                  "cohesion": float(info[3:4].view(np.float64)[0]), "counts": counts, "empty": int(info[2])}
+        out = {"iterations": its, "converged": bool(info[1]), "changed": changed[:its].tolist(),
+               "cohesion": float(info[3:4].view(np.float64)[0]), "counts": counts, "empty": int(info[2])}
+        if bounded:
+            out["active"] = active[:its].tolist()
+        return cent, labels[:n], out
+
+    def kmeans_spherical_bounded(self, k: int, init=None, seed=0, max_iters: int = 25, with_info: bool = False):
+        """Extension: `kmeans_spherical` with bound-pruned iterations (Hamerly's bound on the chord) -> what
+        `kmeans_spherical` returns for the same arguments, bit for bit: centroids, labels and, with_info, "iterations",
+        "converged", "changed", "counts" and "empty".  Every argument is `kmeans_spherical`'s, with its checks, refusals and
+        `init` forms.  Iteration 1 assigns every item.  Each later iteration measures how far the update moved every unit
+        centroid, passes once over the stored items, and sends through the float64 matrix-pipe assignment only the items for
+        which the triangle inequality on the chord sqrt(2 - 2 cos) -- the item's chord to its own centroid against a lower
+        bound on its chord to every other one, each with the rounding error of `assign_cosine`'s cosines on the wrong side --
+        cannot prove that `assign_cosine` would keep the label strictly first.  No low-precision operand appears.  info gains
+        "active": the items that went through the assignment in every iteration (nitems at the first); "cohesion" is the sum,
+        in a fixed order, of the cosine written by whichever kernel settled each item in the last iteration (a skipped item:
+        its directly summed dot with its centroid times its scale) and need not carry `kmeans_spherical`'s bits.  A dead item
+        is never active.  Bounds are not kept across calls.  Whether this is faster than `kmeans_spherical` depends on how
+        quickly the active set shrinks."""
+        return self._kmeans_spherical_run(True, k, init, seed, max_iters, with_info)
+
+    def kmeans_spherical_bounded_counters(self) -> dict:
+        """Extension: `kmeans_spherical_bounded` (and `_kmeans_cos_assign2`) calls on this space that passed their checks, the
+        iterations they ran, their launches by kind, the host's waits (one per iteration, one for the answer) and the items that
+        went through the matrix-pipe assignment."""
+        return _counters(_L.as_kmeans_spherical_bounded_counters, self._h,
+                         ("calls", "iterations", "assign launches", "ordering launches", "update launches", "host waits", "unit launches",
+                          "scale launches", "filter launches", "shift launches", "active rows"))
+
+    def _kmeans_cos_assign2(self, centroids, ids=None):
+        """Debug: the assignment kernel of `kmeans_spherical_bounded` over the items `ids` (1-D integers in [0, nitems), any
+        order, repeats allowed; None: all items in order) -> (labels int32, cos, second), one entry per id: labels and cos with
+        the bits of `assign_cosine(centroids, with_cos=True)` for those items, second the largest min(1, max(-1, fl(g w))) over
+        the centroids other than the label (-inf at k == 1, NaN where the label is -1)."""
+        c = self._kmeans_directions(self._kmeans_centroids(centroids, self.nfeatures))
+        m, idp, idv = self._kmeans_ids(ids)
+        labels, cos, second = np.empty(m, dtype=np.int32), np.empty(m, dtype=np.float64), np.empty(m, dtype=np.float64)
+        if m:
+            _check(_L.as_kmeans_cos_assign2(self._h, c.ctypes.data, c.shape[0], c.shape[1], idp, m, labels.ctypes.data, cos.ctypes.data,
+                                            second.ctypes.data))
+        return labels, cos, second
+
+    def _kmeans_ids(self, ids):
+        """The check of a debug form's `ids` -> (m, the pointer or None, the int64 array that owns it)."""
+        if ids is None:
+            return self.nitems, None, None
+        idv = np.asarray(ids)
+        if idv.ndim != 1 or idv.dtype == np.bool_ or not np.issubdtype(idv.dtype, np.integer):
+            raise ValueError("argument 'ids': expected None or a 1-D integer array of item ids")
+        idv = np.ascontiguousarray(idv, dtype=np.int64)
+        if idv.size and (idv.min() < 0 or idv.max() >= self.nitems):
+            raise ValueError(f"argument 'ids': an id outside [0, {self.nitems})")
+        return idv.shape[0], idv.ctypes.data, idv
 
     def kmeans_spherical_counters(self) -> dict:
         """Extension: `assign_cosine` / `kmeans_spherical` calls on this space that passed their checks, the iterations they ran,

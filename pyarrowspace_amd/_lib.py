@@ -73,6 +73,8 @@ SYMBOLS = [
     "as_kmeans_bounded", "as_kmeans_assign2", "as_kmeans_bounded_counters", "as_kmeans_bounded_kernel_us",
     "as_kmeans_cos_assign", "as_kmeans_spherical", "as_kmeans_spherical_update", "as_kmeans_spherical_scales",
     "as_kmeans_spherical_counters", "as_kmeans_spherical_kernel_us",
+    "as_kmeans_spherical_bounded", "as_kmeans_cos_assign2", "as_kmeans_spherical_bounded_counters",
+    "as_kmeans_spherical_bounded_kernel_us",
     "as_search_fused", "as_score_fused", "as_fused_counters", "as_fused_kernel_us",
     "as_search_fused_batch", "as_score_fused_batch", "as_fused_batch_counters", "as_fused_batch_kernel_us",
     "as_groups_create", "as_groups_count", "as_groups_free", "as_search_grouped", "as_search_grouped_batch", "as_grouped_counters",
@@ -315,6 +317,10 @@ def load():
         "as_kmeans_spherical_scales": (i32, [vp, vp]),
         "as_kmeans_spherical_counters": (i32, [vp, vp, i32]),
         "as_kmeans_spherical_kernel_us": (f64, [vp, i32]),
+        "as_kmeans_spherical_bounded": (i32, [vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, vp]),
+        "as_kmeans_cos_assign2": (i32, [vp, vp, i64, i64, vp, i64, vp, vp, vp]),
+        "as_kmeans_spherical_bounded_counters": (i32, [vp, vp, i32]),
+        "as_kmeans_spherical_bounded_kernel_us": (f64, [vp, i32]),
         "as_search_fused": (i32, [vp, vp, vp, i64, i64, f64, vp, i32, i32, vp, vp, vp, C.POINTER(i64), vp, vp]),
         "as_score_fused": (i32, [vp, vp, vp, i64, i64, f64, vp, i32, i32, vp, i64, vp, vp, vp]),
         "as_fused_counters": (i32, [vp, vp, i32]),

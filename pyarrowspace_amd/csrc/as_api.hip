@@ -3885,6 +3885,96 @@ double as_kmeans_spherical_kernel_us(const as_space* sp, int32_t part) {
     return kmeans_spherical_kernel_us(sp->kmeans_ws, part);
 }
 
+// ---- bound-pruned spherical k-means (extension; as_kmeans_spherical_bounded.hip)
+namespace {
+// the frame of a bounded spherical call behind the checks, as KmsFrame: counts[0 .. 9] go to ksb_count[1 .. 10]
+struct KsbFrame {
+    const as_space* sp;
+    std::unique_lock<std::mutex> lk;
+    int64_t counts[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    explicit KsbFrame(const as_space* s) : sp(s), lk(s->kmu) { sp->ksb_count[0].fetch_add(1, std::memory_order_relaxed); }
+    ~KsbFrame() {
+        for (int i = 0; i < 10; ++i) sp->ksb_count[1 + i].fetch_add(counts[i], std::memory_order_relaxed);
+    }
+    as_status device(const char* who) const {
+        if (hipSetDevice(sp->device) == hipSuccess) return AS_OK;
+        set_err("%s: hipSetDevice failed", who);
+        return AS_EHIP;
+    }
+};
+}  // namespace
+
+as_status as_kmeans_spherical_bounded(const as_space* sp, const double* init, int64_t k, int64_t d, int64_t max_iters, double* out_centroids,
+                                      int32_t* out_labels, int64_t* out_changed, int64_t* out_active, int64_t* out_counts, as_kmeans_info* info) {
+    const char* who = "as_kmeans_spherical_bounded";
+    if (!sp || !init || !out_centroids || !out_labels || !out_changed || !out_active || !out_counts || !info) {
+        set_err("%s: null argument", who);
+        return AS_EINVAL;
+    }
+    if (max_iters < 1) {
+        set_err("%s: max_iters must be at least 1, got %lld", who, (long long)max_iters);
+        return AS_EINVAL;
+    }
+    AS_TRY(kms_checks(who, sp, init, k, d));
+    std::vector<int32_t> c32;
+    try {
+        c32.resize((size_t)k);
+    } catch (const std::bad_alloc&) {
+        set_err("%s: out of host memory", who);
+        return AS_ENOMEM;
+    }
+    KmeansCall c;
+    c.init = init; c.k = k; c.max_iters = max_iters; c.out_centroids = out_centroids; c.out_labels = out_labels; c.out_changed = out_changed;
+    c.out_counts32 = c32.data(); c.info = info;
+    {
+        KsbFrame f(sp);
+        AS_TRY(f.device(who));
+        AS_TRY(kmeans_spherical_bounded(sp, c, out_active, f.counts));
+    }
+    for (int64_t j = 0; j < k; ++j) out_counts[j] = c32[(size_t)j];
+    return AS_OK;
+}
+as_status as_kmeans_cos_assign2(const as_space* sp, const double* centroids, int64_t k, int64_t d, const int64_t* ids, int64_t m,
+                                int32_t* out_labels, double* out_cos, double* out_second) {
+    const char* who = "as_kmeans_cos_assign2";
+    if (!sp || !centroids || !out_labels || !out_cos || !out_second) {
+        set_err("%s: null argument", who);
+        return AS_EINVAL;
+    }
+    AS_TRY(kms_checks(who, sp, centroids, k, d));
+    if (ids ? m < 1 : m != sp->n) {
+        set_err("%s: %lld rows asked for (with ids: at least 1; without: the space's %lld)", who, (long long)m, (long long)sp->n);
+        return AS_EINVAL;
+    }
+    std::vector<int32_t> id32;
+    if (ids) {
+        try {
+            id32.resize((size_t)m);
+        } catch (const std::bad_alloc&) {
+            set_err("%s: out of host memory", who);
+            return AS_ENOMEM;
+        }
+        for (int64_t i = 0; i < m; ++i) {
+            if (ids[i] < 0 || ids[i] >= sp->n) {
+                set_err("%s: id %lld at position %lld lies outside [0, %lld)", who, (long long)ids[i], (long long)i, (long long)sp->n);
+                return AS_EINVAL;
+            }
+            id32[(size_t)i] = (int32_t)ids[i];
+        }
+    }
+    KsbFrame f(sp);
+    AS_TRY(f.device(who));
+    return kmeans_cos_assign2(sp, centroids, k, ids ? id32.data() : nullptr, m, out_labels, out_cos, out_second, f.counts);
+}
+as_status as_kmeans_spherical_bounded_counters(const as_space* sp, int64_t* out, int32_t n) {
+    return counters_out("as_kmeans_spherical_bounded_counters", sp, out, n, sp ? sp->ksb_count : nullptr, 11);
+}
+double as_kmeans_spherical_bounded_kernel_us(const as_space* sp, int32_t part) {
+    if (!sp) return 0.0;
+    std::lock_guard<std::mutex> lk(sp->kmu);
+    return kmeans_spherical_bounded_kernel_us(sp->kmeans_ws, part);
+}
+
 as_status as_diffuse_counters(const as_space* sp, int64_t* out, int32_t n) {
     return counters_out("as_diffuse_counters", sp, out, n, sp ? sp->diffuse_count : nullptr, 5);
 }

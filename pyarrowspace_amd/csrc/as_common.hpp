@@ -264,6 +264,10 @@ struct as_space {
     // as_kmeans_spherical_counters: [0] calls that passed their checks, [1] iterations, [2] assign launches, [3] ordering launches,
     // [4] update launches, [5] host waits, [6] unit launches, [7] row-scale launches
     mutable std::atomic<int64_t> kms_count[8] = {};
+    // as_kmeans_spherical_bounded / as_kmeans_cos_assign2 run on kmeans_ws under kmu.
+    // as_kmeans_spherical_bounded_counters: [0 .. 7] as as_kmeans_spherical_counters, [8] filter launches, [9] shift launches, [10]
+    // the rows that went through the GEMM
+    mutable std::atomic<int64_t> ksb_count[11] = {};
 };
 
 // the identity of a graph that survives the reuse of its address: a number no other graph of this process gets
@@ -1254,11 +1258,17 @@ struct KmsWork {
     dev_buf<double> q;             // [kp] the squared length unit() found for every centroid row
     double us[5] = {};             // the last call: under "kmeans_timing" the microseconds of its unit, assign and update launches ([0], [1], [3]; ordering: KmeansWork::us[1]); [4] its iterations
 };
+// bound-pruned spherical k-means (as_kmeans_spherical_bounded.hip): it runs on KmsWork's scales and on
+// KmbWork's lb, list, p, bw and debug buffers, in the roles they have there
+struct KsbWork {
+    double us[4] = {};             // the last call: under "kmeans_timing" the microseconds of its shift, filter and assign launches; [3] its iterations
+};
 // k-means over the items (as_kmeans.hip): grow-only buffers of a space, under sp->kmu.
 struct KmeansWork {
     KseedWork seed;
     KmbWork bounded;
     KmsWork spherical;
+    KsbWork sbounded;
     int device = 0;
     int cus = 256;
     hipStream_t stream = nullptr;
@@ -1338,5 +1348,21 @@ as_status kmeans_assign2(const as_space* sp, const double* cent, int64_t k, cons
                          double* out_second, int64_t* counts);
 double kmeans_bounded_kernel_us(const KmeansWork* w, int part);
 void set_kmeans_bounded_grid_cap(int v);   // as_set_tuning("kmeans_bounded_grid_cap", v): v > 0 clips the grids of the bounded assign and filter kernels; results never depend on it
+// what as_kmeans_bounded.hip and as_kmeans_spherical.hip lend the bounded spherical loop: a grid of `blocks` under
+// "kmeans_bounded_grid_cap" and S27's directed margin; kms_begin (the workspace, w of every row), kms_unit and kms_update as
+// kmeans_spherical launches them, counts as kmeans_spherical's
+unsigned kmeans_bounded_grid(int64_t blocks);
+double kmeans_bounded_margin(int64_t dp);
+as_status kmeans_spherical_loop_begin(const as_space* sp, int64_t k, bool order, KmeansWork** w, int64_t* counts);
+as_status kmeans_spherical_loop_unit(const as_space* sp, KmeansWork* w, int64_t k, int which, int old, bool by_counts, int64_t* counts);
+as_status kmeans_spherical_loop_update(const as_space* sp, KmeansWork* w, int64_t k, int cur, int64_t* counts);
+// Bound-pruned spherical k-means (as_kmeans_spherical_bounded.hip).  The caller has checked every argument.
+// counts[0 .. 6] as kmeans_spherical's, [7] += filter launches, [8] += shift launches, [9] += the rows that went through the GEMM.
+// out_active: [max_iters].  info->inertia carries the cohesion.
+as_status kmeans_spherical_bounded(const as_space* sp, const KmeansCall& c, int64_t* out_active, int64_t* counts);
+// labels, cos and the runner-up's cos of the m rows `ids` (null: all n rows in order) under the [k][d] host centroids
+as_status kmeans_cos_assign2(const as_space* sp, const double* cent, int64_t k, const int32_t* ids, int64_t m, int32_t* out_labels, double* out_cos,
+                             double* out_second, int64_t* counts);
+double kmeans_spherical_bounded_kernel_us(const KmeansWork* w, int part);
 
 }  // namespace as

@@ -586,6 +586,9 @@ as_status kmb_guard(const as_space* sp, F&& run) {
 }  // namespace
 
 void set_kmeans_bounded_grid_cap(int v) { g_kmb_grid_cap.store(v > 0 ? v : 0, std::memory_order_relaxed); }
+// for the bounded spherical loop (as_kmeans_spherical_bounded.hip): a grid under the same cap, the same directed margin
+unsigned kmeans_bounded_grid(int64_t blocks) { return kmb_grid(blocks); }
+double kmeans_bounded_margin(int64_t dp) { return kmb_margin(dp); }
 double kmeans_bounded_kernel_us(const KmeansWork* w, int part) { return w && part >= 0 && part < 4 ? w->bounded.us[part] : 0.0; }
 
 as_status kmeans_bounded(const as_space* sp, const KmeansCall& c, int64_t* out_active, int64_t* counts) {

@@ -516,6 +516,16 @@ double kmeans_spherical_kernel_us(const KmeansWork* w, int part) {
     return part == 2 ? kmeans_kernel_us(w, 1) : w->spherical.us[part];
 }
 
+// for the bounded spherical loop (as_kmeans_spherical_bounded.hip): the workspace with its row scales, the unit launch and the update
+// launches of the loop above, as they are
+as_status kmeans_spherical_loop_begin(const as_space* sp, int64_t k, bool order, KmeansWork** w, int64_t* counts) { return kms_begin(sp, k, order, w, counts); }
+as_status kmeans_spherical_loop_unit(const as_space* sp, KmeansWork* w, int64_t k, int which, int old, bool by_counts, int64_t* counts) {
+    return kms_unit(w, KmsShape(sp, k), which, old, by_counts, counts);
+}
+as_status kmeans_spherical_loop_update(const as_space* sp, KmeansWork* w, int64_t k, int cur, int64_t* counts) {
+    return kms_update(sp, w, KmsShape(sp, k), cur, counts);
+}
+
 as_status kmeans_cos_assign(const as_space* sp, const double* cent, int64_t k, int32_t* labels_host, double* cos_host, int64_t* counts) {
     return kms_guard(sp, [&] { return kms_assign_run(sp, cent, k, labels_host, cos_host, counts); });
 }
